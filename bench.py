@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """bench.py - ocean timesteps/s of the MI355X-native Q-GCM PV-advance/inversion path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one ocean timestep of the hot path: qgostep -> ocinvq -> ocqbdy (+ the
 leapfrog averaging every 25th step), src/q-gcm.F:1243-1249,1328-1366, on the
 synthetic NAtl-5km-shaped 3-layer grid (961 x 961 x 3, fp64; BASELINE.json
 configs[1]) with all inputs resident in HBM.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times exactly K steps and prints the headline line
+(`value`, `ms_per_step`).  --dump-outputs DIR writes the state the timed steps
+left behind as DIR/*.npy (one GPU; see dump_outputs).  --full adds everything
+else: the objects below and the secondary figures (the reference's call sequence,
+the mixed layer, SOcn 5 km, coupled, NAtl 1 km; N > 1: weak scaling and the other
+basins), each measured in runs of its own after the headline window.
+
+Extra objects in the --full line:
   roofline      dominant kernel: algorithmic bytes per launch / HIP-event average
                 launch duration measured live on the library's stream, against the
                 nominal 8 TB/s HBM peak (MI355X_MICROARCH.md).
@@ -55,6 +62,25 @@ def synthetic_inputs(cfg):
     tx, ty = synth.wind_stress(cfg)            # double-gyre wind
     _, wek = synth.wekpo_from_tau(cfg, tx, ty)
     return po, wek
+
+
+DUMP_SAMPLE_POINTS = 1_000_000  # pom / qom sample size: with po and qo whole, 60.3 MB in all at NAtl 5 km
+DUMP_SAMPLE_SEED = 20241015
+
+
+def dump_outputs(outdir, state, scalars):
+    """--dump-outputs: what a caller of the timed path receives after its last step (OceanModel.get_state,
+    get_scalars), float64.  po.npy and qo.npy hold the whole (nxpo, nypo, nlo) fields; pom and qom, which would take
+    the total past 64 MB, go out as the values at one fixed sample of flat Fortran-order indices (the same for both,
+    drawn from DUMP_SAMPLE_SEED), pom_sample.npy and qom_sample.npy; scalars.npy holds the constraint scalars."""
+    po, pom, qo, qom = state
+    n = po.size
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(DUMP_SAMPLE_POINTS, n), replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"po": po, "qo": qo, "pom_sample": pom.ravel(order="F")[idx], "qom_sample": qom.ravel(order="F")[idx],
+              "scalars": scalars}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def host_cores():
@@ -377,8 +403,8 @@ def run_slabs(args, world, rank, local_rank, cfg5, real_stdout, barrier):
     `value` is BASELINE.json's metric: ocean timesteps/s of the FIXED NAtl 5 km basin (961 x 961 x 3) cut into `world`
     y-slabs ("scaling": "strong" - total work fixed; round 2 reported the weak-scaling figure here).  The ranks
     exchange slab summaries (tridiagonal sweeps + area integrals) and halo rows every step (qgcm_hip_slab_steps /
-    qgcm_hip.slab.SlabOcean).  Secondary keys: `weak_scaling_natl5_slab_per_gpu` (a NAtl-5km-shaped slab per GPU of a
-    basin `world` times taller), NAtl 1 km, SOcn 5 km, the mixed layer."""
+    qgcm_hip.slab.SlabOcean).  Secondary keys (--full): `weak_scaling_natl5_slab_per_gpu` (a NAtl-5km-shaped slab per
+    GPU of a basin `world` times taller), NAtl 1 km, SOcn 5 km, the mixed layer."""
     import dataclasses
 
     import torch
@@ -570,7 +596,7 @@ def run_slabs(args, world, rank, local_rank, cfg5, real_stdout, barrier):
     lib_ok = lib_status == "ok" and best[2].startswith("library")
     p2p = "halo rows by send/recv" in best[2]
     ovl = bool(lib_ok and extra.get("halo_overlap", {}).get("used", False))
-    if os.environ.get("QGCM_BENCH_NO_SECONDARY") != "1":
+    if args.full and os.environ.get("QGCM_BENCH_NO_SECONDARY") != "1":
         import threading
         from qgcm_hip import preset
 
@@ -623,8 +649,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1600)
     ap.add_argument("--warmup", type=int, default=160)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, per-kernel times, secondary figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state after the last timed step to DIR/<name>.npy (one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     real_stdout = divert_stdout()
 
     import torch
@@ -646,6 +678,8 @@ def main():
     # the multi-GPU plumbing on a one-GPU box; needs the torch.distributed.run environment)
     force_slabs = os.environ.get("QGCM_BENCH_FORCE_SLABS") == "1"
     if world > 1 or force_slabs:
+        if args.dump_outputs:
+            raise SystemExit("bench.py --dump-outputs is implemented for the one-GPU path only")
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
         # QGCM_BENCH_BACKEND=gloo + QGCM_BENCH_SAME_GPU=1: rehearsal of the multi-rank code path with
@@ -699,13 +733,37 @@ def main():
     wall = time.perf_counter() - t0
     state = model.get_state()
     finite = bool(all(np.isfinite(x).all() for x in state))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state, model.get_scalars())
 
-    # ---- per-kernel HIP-event timing for the roofline entry (rank 0) ---------
-    out = None
-    if rank == 0:
+    npts = cfg.nxpo * cfg.nypo
+    steps_per_s = world * args.steps / wall
+    out = {
+        "metric": "ocean timesteps/sec (NAtl 5km 3-layer qgostep+ocinvq+ocqbdy)",
+        "value": round(steps_per_s, 2), "unit": "steps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * wall / args.steps, 5),
+        # (the basin is fixed as N grows - BASELINE.json's metric: the N > 1 lines say "strong" too)
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "double_gyre_ocean_only NAtl 5km, 961x961x3 p-grid, dto=540s, "
+                               "Gaussian-eddy IC + double-gyre wind, oml off",
+                   "grid": [cfg.nxpo, cfg.nypo, cfg.nlo],
+                   "parallelism": "single GPU"},
+        "model_years_per_day": round(cfg.model_years_per_day(steps_per_s), 1),
+        "hip_event_ms_per_step": round(ev_ms / args.steps, 5),
+        # steps run before the timed window opens: --warmup + the untimed rehearsal of the timed call (graph
+        # capture / instantiation and the GPU's clock ramp stay outside the window, see above)
+        "untimed_steps_before_window": args.warmup + done,
+        "launch_mode": "HIP graphs: %d x 50-step block(s) + %s, %d eager step(s); built and replayed once before the window" % (
+            args.steps // 50, ("one %d-step block" % ((args.steps % 50) & ~1)) if (args.steps % 50) >= 2 else "no tail block",
+            (args.steps % 50) % 2),
+        "state_finite": finite,
+        "step_hbm_frac": round(56 * npts * 8.0 * (args.steps / (ev_ms * 1e-3)) / 1e9 / HBM_PEAK_GBS, 4),
+    }
+    # ---- --full: per-kernel HIP-event timing for the roofline entry, then the secondary figures ---------
+    if args.full:
         nprof = 100
         prof = model.profile_steps(nprof, s0=s_timed + args.steps)
-        npts = cfg.nxpo * cfg.nypo
         # Every launch is bracketed by two HIP events on the library's stream. An event record is a packet of its
         # own, so a raw bracket reads kernel + record overhead. The overhead per bracket is calibrated on the timed
         # region itself: the same steps replayed from HIP graphs (no brackets, no gaps) take ev_ms/steps each, so
@@ -735,44 +793,21 @@ def main():
         # reaches on buffers of this workload's field size: the practical ceiling beside the nominal 8 TB/s
         mix = {"k_tend": (15, 6), "k_dst_fwd": (3, 3), "k_thomas": (3, 3), "k_dst_inv": (5, 3)}.get(dom)
         stream_gbs = model.stream_mix_bandwidth(mix[0], mix[1], npts * 8, 20) if mix else None
-        steps_per_s = world * args.steps / wall
-        out = {
-            "metric": "ocean timesteps/sec (NAtl 5km 3-layer qgostep+ocinvq+ocqbdy)",
-            "value": round(steps_per_s, 2), "unit": "steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * wall / args.steps, 5),
-            # (the basin is fixed as N grows - BASELINE.json's metric: the N > 1 lines say "strong" too)
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "double_gyre_ocean_only NAtl 5km, 961x961x3 p-grid, dto=540s, "
-                                   "Gaussian-eddy IC + double-gyre wind, oml off",
-                       "grid": [cfg.nxpo, cfg.nypo, cfg.nlo],
-                       "parallelism": "single GPU"},
-            "model_years_per_day": round(cfg.model_years_per_day(steps_per_s), 1),
-            "hip_event_ms_per_step": round(ev_ms / args.steps, 5),
-            # steps run before the timed window opens: --warmup + the untimed rehearsal of the timed call (graph
-            # capture / instantiation and the GPU's clock ramp stay outside the window, see above)
-            "untimed_steps_before_window": args.warmup + done,
-            "launch_mode": "HIP graphs: %d x 50-step block(s) + %s, %d eager step(s); built and replayed once before the window" % (
-                args.steps // 50, ("one %d-step block" % ((args.steps % 50) & ~1)) if (args.steps % 50) >= 2 else "no tail block",
-                (args.steps % 50) % 2),
-            "state_finite": finite,
-            "step_hbm_frac": round(56 * npts * 8.0 * (args.steps / (ev_ms * 1e-3)) / 1e9 / HBM_PEAK_GBS, 4),
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(dom),
-                         "traffic_source": "committed rocprofv3 --pmc collection of this command (profiles/pmc_traffic.json, "
-                                           "profiles/collect.sh), not measured in this run",
-                         "avg_launch_us": round(avg_us, 3), "algorithmic_bytes_per_launch": abytes,
-                         "reference_algorithm_bytes_per_launch": f_survey * npts * 8.0,
-                         "frac_reference_algorithm_bytes": round(f_survey * npts * 8.0 / (avg_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                         "measured_copy_GBps": round(copy_gbs, 1),
-                         "measured_stream_same_mix_GBps": round(stream_gbs, 1) if stream_gbs else None,
-                         "frac_of_measured_stream": round(achieved / stream_gbs, 4) if stream_gbs else None,
-                         "event_bracket_us": {"subtracted_per_launch": round(bracket_us, 3),
-                                              "calibration": "bracketed kernel times sum to the graph-replayed step time",
-                                              "empty_launch_bracketed": round(noop_us, 3),
-                                              "empty_launch_in_train": round(train_us, 3)},
-                         "kernel_us": {k: round(1e3 * v[0] / max(v[1], 1), 3) for k, v in prof.items()}},
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(dom),
+                           "traffic_source": "committed rocprofv3 --pmc collection of this command (profiles/pmc_traffic.json, "
+                                             "profiles/collect.sh), not measured in this run",
+                           "avg_launch_us": round(avg_us, 3), "algorithmic_bytes_per_launch": abytes,
+                           "reference_algorithm_bytes_per_launch": f_survey * npts * 8.0,
+                           "frac_reference_algorithm_bytes": round(f_survey * npts * 8.0 / (avg_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                           "measured_copy_GBps": round(copy_gbs, 1),
+                           "measured_stream_same_mix_GBps": round(stream_gbs, 1) if stream_gbs else None,
+                           "frac_of_measured_stream": round(achieved / stream_gbs, 4) if stream_gbs else None,
+                           "event_bracket_us": {"subtracted_per_launch": round(bracket_us, 3),
+                                                "calibration": "bracketed kernel times sum to the graph-replayed step time",
+                                                "empty_launch_bracketed": round(noop_us, 3),
+                                                "empty_launch_in_train": round(train_us, 3)},
+                           "kernel_us": {k: round(1e3 * v[0] / max(v[1], 1), 3) for k, v in prof.items()}}
         secondary = os.environ.get("QGCM_BENCH_NO_SECONDARY") != "1"  # profiles/collect.sh profiles the main workload only
         # Secondary figure: the rate of the reference's own call sequence (what a drop-in q-gcm executable sees)
         try:

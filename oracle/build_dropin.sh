@@ -1,8 +1,8 @@
 #!/usr/bin/env bash
-# Builds the ACTUAL drop-in: the reference main program src/q-gcm.F (patched copy, dropin/patch_main.py) and the
-# rest of the reference model, compiled from the sources where they lie under /root/reference/src, with
+# Builds the ACTUAL drop-in: the reference main program src/q-gcm.F (patched copy, q-gcm_amd/fortran/dropin/patch_main.py)
+# and the rest of the reference model, compiled from the sources where they lie in the reference's src/ ($REF below), with
 # src/qgosubs.F, src/ocisubs.F (and, in coupled builds, src/qgasubs.F, src/atisubs.F) and src/omlsubs.F REPLACED by
-# the shim modules of this directory, linked against q-gcm_amd/lib/libqgcm_hip.so.  Also builds the unmodified
+# the shim modules of q-gcm_amd/fortran, linked against q-gcm_amd/lib/libqgcm_hip.so.  Also builds the unmodified
 # reference executable next to it (same flags), whose restart dump is the golden vector of the drop-in test.
 #
 #   build_dropin.sh <cfg> <nxta> <nyta> <nxaooc|nxta> <nyaooc> <ndxr> <nlo> <fnot> <beta> <mode>
@@ -10,9 +10,10 @@
 #             box_spl = box + -Dsponge_layer_k247 (the fork's sponge layer, src/qgosubs.F:203-205)
 #
 # Nothing is copied into the repository: all outputs (objects, .mod, the two executables) go to
-# q-gcm_amd/fortran/_dropin/<cfg>/, which is git-ignored; the patched copy of the main program is deleted after it
-# has been compiled.  The reference's own Makefile is not used; compile lines follow its flag split (QGOPTS only
-# where src/Makefile passes them).  -Duse_netcdf / -Dqoc_diag are dropped (no netCDF here).
+# oracle/_ref/dropin/<cfg>/, which is git-ignored and, like the reference libraries of build_ref.sh, travels with
+# the built tree to the GPU box; the patched copy of the main program is deleted after it has been compiled.  The
+# reference's own Makefile is not used; compile lines follow its flag split (QGOPTS only where src/Makefile passes
+# them).  -Duse_netcdf / -Dqoc_diag are dropped (no netCDF here).
 # LAPACK for eigmod / homsol comes from the image's MKL, as in oracle/build_ref.sh.
 set -euo pipefail
 CFG=$1; NXTA=$2; NYTA=$3; NXAOOC=$4; NYAOOC=$5; NDXR=$6; NLO=$7; FNOT=$8; BETA=$9; MODE=${10}
@@ -20,8 +21,8 @@ CFG=$1; NXTA=$2; NYTA=$3; NXAOOC=$4; NYAOOC=$5; NDXR=$6; NLO=$7; FNOT=$8; BETA=$
 REF=${QGCM_REFERENCE:-/root/reference}
 SRC=$REF/src
 HERE=$(cd "$(dirname "$0")" && pwd)
-FDIR=$(cd "$HERE/.." && pwd)
-OUT=$FDIR/_dropin/$CFG
+FDIR=$(cd "$HERE/../q-gcm_amd/fortran" && pwd)
+OUT=$HERE/_ref/dropin/$CFG
 FC=${FC:-/opt/rocm/bin/amdflang}
 MKLDIR=${MKLDIR:-/opt/conda/lib}
 LIBDIR=$(cd "$FDIR/../lib" && pwd)
@@ -97,10 +98,10 @@ if [ "$MODE" != "coupled" ]; then
   SHIM_OBJ="$SHIM_OBJ qgasubs.o atisubs.o"
 fi
 $FCO $Q -c -I"$SRC" "$SRC/conhoms.F"           # homsol -> hsbxoc / hscyoc / hscyat of the shim
-python3 "$HERE/patch_main.py" "$SRC/q-gcm.F" "$OUT/hip/q-gcm_dropin.F"
+python3 "$FDIR/dropin/patch_main.py" "$SRC/q-gcm.F" "$OUT/hip/q-gcm_dropin.F"
 # the INCLUDEd parameter lists (in_param.f, out_param.f) are found through -I
 $FCO $Q -c -I"$SRC" -o q-gcm.o q-gcm_dropin.F
 rm -f q-gcm_dropin.F
 $FC -fopenmp -o "$OUT/q-gcm_hip" $COMMON_OBJ $REST_OBJ amlsubs.o $SHIM_OBJ conhoms.o q-gcm.o \
-    -L"$LIBDIR" -lqgcm_hip -Wl,-rpath,'$ORIGIN/../../../lib' -Wl,-rpath,/opt/rocm/lib -L/opt/rocm/lib -lamdhip64 $LAPACK
+    -L"$LIBDIR" -lqgcm_hip -Wl,-rpath,'$ORIGIN/../../../../q-gcm_amd/lib' -Wl,-rpath,/opt/rocm/lib -L/opt/rocm/lib -lamdhip64 $LAPACK
 echo "built $OUT/q-gcm_ref and $OUT/q-gcm_hip ($MODE)"

@@ -50,7 +50,7 @@ sed -e "s|^      PARAMETER ( nxta = .*|      PARAMETER ( nxta = $NXTA, nyta = $N
     -e "s|^      PARAMETER ( fnot = .*|      PARAMETER ( fnot = $FNOT, beta = $BETA )|" \
     "$REF/examples/double_gyre_ocean_only/parameters_data.F.dg_oo" > parameters_data.F
 # -Dsponge_layer_k247 builds: the example dimension files lack the fork's sponge constants ("fork
-# breakage"); the two lines of src/parameters_data.F:140,144 are appended, as q-gcm_amd/fortran/dropin/build_dropin.sh does
+# breakage"); the two lines of src/parameters_data.F:140,144 are appended, as oracle/build_dropin.sh does
 case "$EXTRA" in *sponge_layer_k247*)
   sed -i -e "s|^      END MODULE parameters|      double precision :: c1_spl, l_spl\n      PARAMETER ( c1_spl = -2.5D-5, l_spl = 4.0D5 )\n      END MODULE parameters|" parameters_data.F ;;
 esac

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX from the repo root (gpurun -- 'bash profiles/collect.sh r3 [natl5|socn5|atmos|natl1_slabs|natl1_one_slab]'):
-#   natl5 (default): the default bench.py command
+#   natl5 (default): the default bench.py command with --full (the roofline entry and its 1 GiB copy probe)
 #       pass 1  rocprofv3 --kernel-trace --stats        -> kernel durations
 #       pass 2  rocprofv3 --pmc FETCH_SIZE              (own pass, kernel-trace only)
 #       pass 3  rocprofv3 --pmc WRITE_SIZE              (own pass)
@@ -19,9 +19,9 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$R"
 export QGCM_BENCH_NO_SECONDARY=1   # profile the headline workload only (no mixed-layer / SOcn secondary figures)
 if [ "$WHAT" = natl5 ]; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --no-cpu-baseline > "$OUT/bench_under_rocprof.log" 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --full --no-cpu-baseline > "$OUT/bench_under_rocprof.log" 2>&1
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/pmc_$C" -- python3 bench.py --no-cpu-baseline --steps 200 --warmup 20 > "$OUT/pmc_$C.log" 2>&1
+    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/pmc_$C" -- python3 bench.py --full --no-cpu-baseline --steps 200 --warmup 20 > "$OUT/pmc_$C.log" 2>&1
   done
   grep '^{' "$OUT/bench_under_rocprof.log" > "$OUT/bench_under_rocprof.json" || true
 else

@@ -6,6 +6,7 @@ import sys
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 DROP = os.path.join(ROOT, "q-gcm_amd", "fortran", "dropin")
+BUILD = os.path.join(ROOT, "oracle", "build_dropin.sh")  # products under oracle/_ref/dropin/<cfg>/ (exe_path)
 NSTEPS = 120
 # (ocean steps, tolerance on max|difference| / max|reference| of every restart field).  The coupled model carries
 # switches (convective adjustment of both mixed layers, src/amlsubs.F / src/omlsubs.F) that amplify rounding: the
@@ -44,7 +45,7 @@ CASES = {
 
 
 def exe_path(cfg, which):
-    return os.path.join(ROOT, "q-gcm_amd", "fortran", "_dropin", cfg, "q-gcm_" + which)
+    return os.path.join(ROOT, "oracle", "_ref", "dropin", cfg, "q-gcm_" + which)
 
 
 def golden_name(cfg, nsteps, restart=False):

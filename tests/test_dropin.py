@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from common import GOLDEN, relerr
-from dropin_cases import CASES, DROP, RUNS, RUNS_RESTART, THREADS, exe_path, golden_name, prepare_case
+from dropin_cases import BUILD, CASES, DROP, RUNS, RUNS_RESTART, THREADS, exe_path, golden_name, prepare_case
 from qgcm_hip import config, restart
 
 HAVE_REF = os.path.isdir("/root/reference/src")
@@ -24,7 +24,7 @@ HAVE_REF = os.path.isdir("/root/reference/src")
 @pytest.mark.parametrize("cfg", list(CASES))
 def test_dropin_compiles_and_links(cfg):
     dims, mode = CASES[cfg]
-    r = subprocess.run([os.path.join(DROP, "build_dropin.sh"), cfg] + [str(x) for x in dims] + [mode],
+    r = subprocess.run([BUILD, cfg] + [str(x) for x in dims] + [mode],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-3000:]
     exe = exe_path(cfg, "hip")
@@ -66,12 +66,12 @@ def test_dropin_executable_matches_the_reference_restart(cfg, nsteps, tol, rst, 
     exe = exe_path(cfg, "hip")
     if not os.path.exists(exe):
         # Row (b) of SURVEY 8 rests on this test: a GPU box whose snapshot lacks the executables must not show green.
-        # They are built by __graft_entry__.build() in the build container (make check_dropin needs /root/reference)
-        # and travel with the snapshot; only an explicit opt-out turns their absence into a skip.
+        # They are built by __graft_entry__.build() where the reference sources are (make check_dropin) into
+        # oracle/_ref/dropin/, which travels with the built tree; only an explicit opt-out turns their absence into a skip.
         if os.environ.get("QGCM_SKIP_DROPIN") == "1":
             pytest.skip("drop-in executable not built and QGCM_SKIP_DROPIN=1")
-        pytest.fail("drop-in executable %s is missing: run __graft_entry__.build() where /root/reference is mounted "
-                    "(q-gcm_amd/fortran/dropin/build_dropin.sh), or set QGCM_SKIP_DROPIN=1 to skip knowingly" % exe)
+        pytest.fail("drop-in executable %s is missing: run __graft_entry__.build() where the reference sources are "
+                    "(oracle/build_dropin.sh), or set QGCM_SKIP_DROPIN=1 to skip knowingly" % exe)
     mode = CASES[cfg][1]
     d = str(tmp_path)
     prepare_case(cfg, d, nsteps, rst)
