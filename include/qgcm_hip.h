@@ -340,6 +340,40 @@ int qgcm_hip_oml_get_diag(qgcm_hip_handle h, double *entoc, double *diag);
 int qgcm_hip_set_dtopoc(qgcm_hip_handle h, const double *dtopoc);
 int qgcm_hip_valids(qgcm_hip_handle h, double *out, int *solnok);
 
+/* ---- ocean monitors ----------------------------------------
+ * The ocean half of "call monnc_comp" (src/monitor_diag.F:479-832 with poref :173-182, del4bx / del4ch, genint) and
+ * "call couroc" (:1450-1928) on the device: instead of pulling po, pom, qo every dgnday, qgcm_hip_monitor_len(h) =
+ * 19*nlo + 16 doubles come back.  It reads the time levels qgcm_hip_get_state would return at that point (after an
+ * averaging step the averaged ones), and changes no state.  Whole-domain ocean handles only.
+ * qgcm_hip_set_mon_params: the constants the handle does not hold (dto = tdto/2 and the rest of MODULE occonst are
+ *   derived from qgcm_hip_params as src/q-gcm.F:414-436 does).
+ * qgcm_hip_set_monitor_fields: tauxo, tauyo (nxpo,nypo) (intrfac), wekto (nxto,nyto) (ocstate), sst (nxto,nyto)
+ *   (intrfac): the fields that do not evolve on the device without the mixed layer.  NULL = leave unchanged.  With the
+ *   mixed layer on (qgcm_hip_oml_init) the monitors read its own stress, wekto and sst instead.  Without it,
+ *   qgcm_hip_monitors fails, naming the field, if one was never given.  Synchronous.
+ * qgcm_hip_monitors: out, in this order (names of MODULE monitor, src/monitor_data.F:50-71):
+ *     wetmoc, watmoc, wepmoc, wapmoc, entmoc, enamoc
+ *     etamoc(nlo-1), et2moc(nlo-1), ddtpeoc(nlo-1), pkenoc, utauoc
+ *     pavgoc, qavgoc, ah2doc, ah4doc, kealoc, ddtkeoc, osfmin, osfmax, occirc, ocjpos, ocjval   (nlo each)
+ *     btdgoc, sstmin, sstmax, tmlmoc, hfmloc, occtot
+ *     umminoc, ummaxoc, vmminoc, vmmaxoc, cnmloc                                                (couroc, mixed layer)
+ *     ugminoc, ugmaxoc, vgminoc, vgmaxoc, cnqgoc                                                (nlo each)
+ *   Extrema, the transports and the jet position and value (serial zonal sums, as in the reference) use the reference's
+ *   expressions uncontracted and are bitwise the golden values of the reference build (tests/golden/mon_*.npz);
+ *   the genint integrals agree to rounding (another summation order).  All of it is bitwise reproducible from call
+ *   to call.  Runs on the handle's stream; synchronous. */
+typedef struct qgcm_hip_mon_params {
+  double rhooc, cpoc;   /* ocean density, specific heat              (MODULE occonst) */
+  double hmoc, ycexp;   /* mixed layer thickness, sst advection coupling (couroc's mixed layer: intrfac, occonst) */
+  int sb_hflux;         /* the reference's cpp options sb_hflux / nb_hflux (couroc's mixed layer at the */
+  int nb_hflux;         /* southern / northern boundary) as run-time flags */
+} qgcm_hip_mon_params;
+int qgcm_hip_monitor_len(qgcm_hip_handle h);
+int qgcm_hip_set_mon_params(qgcm_hip_handle h, const qgcm_hip_mon_params *p);
+int qgcm_hip_set_monitor_fields(qgcm_hip_handle h, const double *tauxo, const double *tauyo, const double *wekto,
+                                const double *sst);
+int qgcm_hip_monitors(qgcm_hip_handle h, double *out);
+
 /* ---- start-up / restart arithmetic and the progress sample on the device ------------
  * qgcm_hip_init_from_p: the start-up sequence of the main program (src/q-gcm.F:711-731; atmosphere :738-749) from
  *   the po, pom ALREADY on the device (qgcm_hip_set_state with qo = qom = NULL, e.g. after a restart read):

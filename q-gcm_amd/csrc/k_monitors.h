@@ -1,0 +1,385 @@
+// k_monitors.h - the ocean half of the monitoring diagnostics on the device.
+//
+// Replaces the ocean half of `call monnc_comp` (src/monitor_diag.F:479-832, with poref :173-182, del4bx :899-1020,
+// del4ch :1026-1151, genint :1155-1209) and `call couroc` (:1450-1928).  On the host these need po, pom, qo every
+// dgnday and ~30 passes per layer over them; here 19*nlo + 16 doubles come back (layout: include/qgcm_hip.h).
+//   k_mon_scan   one pass over the p grid in MON_TX x MON_TY tiles, all layers.  Per layer the lagged geostrophic
+//                velocities ugoc / vgoc of the tile + a 3-point halo go to LDS, then Del-sqd of them (2-point halo),
+//                then Del-4th at the tile's points, with the one-sided boundary forms of del4bx or the periodic wrap
+//                of del4ch.  Each workgroup writes its partial genint sums (edge weights facwe / facsn of the p, T
+//                and mixed grids) and its partial minima (maxima as minima of the negated values, exact).
+//   k_mon_jet    the zonal sums of ugeos behind the jet position ujeto, row by row in the reference's serial order.
+//   k_mon_final  one workgroup: reduces the partials in a fixed order, the arg-max over the rows and the scalar
+//                arithmetic of monnc_comp (ocnorm, rhooc, cpoc, Sverdrups, occtot) and couroc.
+// No atomics: every sum has a fixed association order, so the result is bitwise the same from call to call.  The
+// extrema (po, sst, couroc's velocities and Courant numbers), ocjpos and ocjval use the reference's expressions,
+// uncontracted (-ffp-contract=off), and min / max do not depend on the order: against the golden values of the
+// reference build (tests/golden/mon_*.npz) they are bitwise equal.  The genint integrals are sums in another order
+// than the host's: they agree to rounding.
+#pragma once
+#include "qgcm_dev.h"
+
+#define MON_TX 64           // tile width = one wave: lane = column
+#define MON_TY 16
+#define MON_NT 256          // 4 waves, 4 rows each
+#define MON_FT 1024         // threads of k_mon_final (one wave per reduced quantity)
+#define MON_NQ 13           // sums per batch (per layer; then the layer-independent ones)
+#define MON_NMN 7           // minima per batch
+#define MON_NS(nl) (MON_NQ * ((nl) + 1))
+#define MON_NM(nl) (MON_NMN * ((nl) + 1))
+#define MON_LEN(nl) (19 * (nl) + 16)
+
+// sums of layer k at MON_NQ*k + ...
+enum { MS_P = 0, MS_Q, MS_U2D, MS_U4D, MS_UKE, MS_UKEDOT, MS_V2D, MS_V4D, MS_VKE, MS_VKEDOT, MS_ETA, MS_ETA2, MS_ETADOT };
+// layer-independent sums at MON_NQ*nl + ...
+enum { MS_WEKT = 0, MS_AWEKT, MS_WEKP, MS_AWEKP, MS_ENT, MS_AENT, MS_UTAUX, MS_VTAUY, MS_SSTWEK, MS_SST, MS_UBOT, MS_VBOT, MS_ETAENT };
+// minima of layer k at MON_NMN*k + ...: pomin, -pomax, ugmin, -ugmax, vgmin, -vgmax, -vsqmax;
+// layer-independent at MON_NMN*nl + ...: sstmin, -sstmax, ummin, -ummax, vmmin, -vmmax, -vsqmax (mixed layer)
+
+struct QgMonParams {
+  QgGeom g;
+  const double *po, *pom, *qo, *wekpo, *entoc; // p grid, ldx pitch
+  const double *taux, *tauy;                   // p grid, ldx pitch
+  const double *wekto, *sst;                   // T grid, ldt pitch
+  int ldt;
+  int ntx, nblk;                               // tiles along x, tiles in all
+  int sb, nb;                                  // the cpp options sb_hflux / nb_hflux of couroc's mixed layer
+  double rdxof0, dxom2, hdxom1, dto, uvgfac, rhf0hm;
+  double rgpoc[QG_MAXL];
+  double ocnorm, rhooc, cpoc, fnot, delek;
+  double hoc[QG_MAXL], gpoc[QG_MAXL], ah2oc[QG_MAXL], ah4oc[QG_MAXL];
+  double *psum;  // (MON_NS, nblk)
+  double *pmin;  // (MON_NM, nblk)
+  double *ujet;  // (nyto, nl): ujeto of every layer (k_mon_jet -> k_mon_final)
+  double *out;   // MON_LEN(nl)
+};
+
+__device__ __forceinline__ int mon_wrap(int i, int n) { return ((i - 1) % n + n) % n + 1; }
+
+// Del-sqd of a field tabulated on (N, M) at LDS position (a, b) = global point (gi, gj): the forms of del4bx
+// (one-sided differences on the four edges) or, CYC, of del4ch (periodic in x; the halo holds periodic images).
+template <bool CYC, int W>
+__device__ __forceinline__ double mon_lap(const double (*A)[W], int a, int b, int gi, int gj, int N, int M, double f) {
+  if (gj < 1 || gj > M || (!CYC && (gi < 1 || gi > N))) return 0.0;
+  const bool yin = gj > 1 && gj < M;
+  if (yin && (CYC || (gi > 1 && gi < N))) return f * (A[b - 1][a] + A[b][a - 1] + A[b][a + 1] + A[b + 1][a] - 4.0 * A[b][a]);
+  double s;
+  if (!CYC && gi == 1) s = A[b][a + 2] - 2.0 * A[b][a + 1] + A[b][a];
+  else if (!CYC && gi == N) s = A[b][a] - 2.0 * A[b][a - 1] + A[b][a - 2];
+  else s = A[b][a - 1] - 2.0 * A[b][a] + A[b][a + 1];
+  if (gj == 1) s = s + A[b + 2][a] - 2.0 * A[b + 1][a] + A[b][a];
+  else if (gj == M) s = s + A[b][a] - 2.0 * A[b - 1][a] + A[b - 2][a];
+  else s = s + A[b - 1][a] - 2.0 * A[b][a] + A[b + 1][a];
+  return f * s;
+}
+
+__device__ __forceinline__ double mon_min(double a, double b) { return b < a ? b : a; }
+
+// one batch of MON_NQ sums + MON_NMN minima: wave butterfly, then the four waves left to right; partials of block b
+__device__ __forceinline__ void mon_flush(double *s, double *m, double (*red)[MON_NT / 64], double *psum, double *pmin,
+                                          int s0, int m0, int nblk, int b) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) s[q] += __shfl_xor(s[q], off);
+#pragma unroll
+    for (int q = 0; q < MON_NMN; ++q) m[q] = mon_min(m[q], __shfl_xor(m[q], off));
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) red[q][tid >> 6] = s[q];
+#pragma unroll
+    for (int q = 0; q < MON_NMN; ++q) red[MON_NQ + q][tid >> 6] = m[q];
+  }
+  __syncthreads();
+  if (tid < MON_NQ) {
+    double t = red[tid][0];
+    for (int w = 1; w < MON_NT / 64; ++w) t += red[tid][w];
+    psum[(long)(s0 + tid) * nblk + b] = t;
+  } else if (tid < MON_NQ + MON_NMN) {
+    double t = red[tid][0];
+    for (int w = 1; w < MON_NT / 64; ++w) t = mon_min(t, red[tid][w]);
+    pmin[(long)(m0 + tid - MON_NQ) * nblk + b] = t;
+  }
+  __syncthreads();
+}
+
+template <int NL, bool CYC>
+__global__ __launch_bounds__(MON_NT) void k_mon_scan(const QgMonParams P) {
+  constexpr int UW = MON_TX + 6, UH = MON_TY + 6, DW = MON_TX + 4, DH = MON_TY + 4;
+  __shared__ double ug[UH][UW], vg[UH][UW], d2u[DH][DW], d2v[DH][DW];
+  __shared__ double red[MON_NQ + MON_NMN][MON_NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nx = P.g.nx, ny = P.g.ny, nxt = P.g.nxt, nyt = ny - 1, ldx = P.g.ldx, ldt = P.ldt;
+  const long fs = P.g.fstride;
+  const int b = blockIdx.x, tx = b % P.ntx, ty = b / P.ntx;
+  const int i0 = tx * MON_TX + 1, j0 = ty * MON_TY + 1;
+  const int i = i0 + lane;
+  const double rdxof0 = P.rdxof0, rdt = P.rdxof0 / P.dto, dxom2 = P.dxom2;
+  const double BIG = HUGE_VAL;
+  double si[MON_NQ], mi[MON_NMN];
+#pragma unroll
+  for (int q = 0; q < MON_NQ; ++q) si[q] = 0.0;
+#pragma unroll
+  for (int q = 0; q < MON_NMN; ++q) mi[q] = BIG;
+
+#pragma unroll   // (k static: the k == 0 / k == NL - 1 terms and rgpoc[k] resolve at compile time)
+  for (int k = 0; k < NL; ++k) {
+    const double *pk = P.po + fs * k, *pmk = P.pom + fs * k, *qk = P.qo + fs * k;
+    // lagged geostrophic velocities (:627-646): ugoc on (nxpo, nyto), vgoc on (nxto, nypo); 0 off the grid
+    for (int t = tid; t < UW * UH; t += MON_NT) {
+      const int a = t % UW, bb = t / UW;
+      const int gi = i0 - 3 + a, gj = j0 - 3 + bb;
+      double u = 0.0, v = 0.0;
+      const int iu = CYC ? mon_wrap(gi, nx) : gi, iv = CYC ? mon_wrap(gi, nxt) : gi;
+      if (gj >= 1 && gj <= nyt && iu >= 1 && iu <= nx) {
+        const long o = (long)(gj - 1) * ldx + (iu - 1);
+        u = -rdxof0 * (pmk[o + ldx] - pmk[o]);
+      }
+      if (gj >= 1 && gj <= ny && iv >= 1 && iv <= nxt) {
+        const long o = (long)(gj - 1) * ldx + (iv - 1);
+        v = rdxof0 * (pmk[o + 1] - pmk[o]);
+      }
+      ug[bb][a] = u;
+      vg[bb][a] = v;
+    }
+    __syncthreads();
+    for (int t = tid; t < DW * DH; t += MON_NT) {
+      const int a = t % DW, bb = t / DW;
+      const int gi = i0 - 2 + a, gj = j0 - 2 + bb;
+      d2u[bb][a] = mon_lap<CYC, UW>(ug, a + 1, bb + 1, gi, gj, nx, nyt, dxom2);
+      d2v[bb][a] = mon_lap<CYC, UW>(vg, a + 1, bb + 1, gi, gj, nxt, ny, dxom2);
+    }
+    __syncthreads();
+
+    double s[MON_NQ], m[MON_NMN];
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) s[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < MON_NMN; ++q) m[q] = BIG;
+    const double rg = k < NL - 1 ? P.rgpoc[k] : 0.0, rgdt = rg / P.dto;
+    for (int r = wv; r < MON_TY; r += MON_NT / 64) {
+      const int j = j0 + r;
+      if (i <= nx && j <= ny) {
+        const long o = (long)(j - 1) * ldx + (i - 1);
+        const double wx = (i == 1 || i == nx) ? 0.5 : 1.0, wy = (j == 1 || j == ny) ? 0.5 : 1.0, wp = wx * wy;
+        const double p = pk[o];
+        // p grid (genint 0.5, 0.5): pint, qint (:729-730), eta terms (:557-590), extrema of po (:655-666)
+        s[MS_P] += wp * p;
+        s[MS_Q] += wp * qk[o];
+        m[0] = mon_min(m[0], p);
+        m[1] = mon_min(m[1], -p);
+        if (k < NL - 1) {
+          const double pn = pk[fs + o];
+          const double eta = rg * (pn - p);
+          const double etadot = rgdt * (p - pn - pmk[o] + pmk[fs + o]);
+          s[MS_ETA] += wp * eta;
+          s[MS_ETA2] += wp * (eta * eta);
+          s[MS_ETADOT] += wp * (eta * etadot);
+          if (k == 0) si[MS_ETAENT] += wp * (eta * P.entoc[o]);
+        }
+        if (k == 0) {
+          const double we = P.wekpo[o], en = P.entoc[o];
+          si[MS_WEKP] += wp * we;
+          si[MS_AWEKP] += wp * fabs(we);
+          si[MS_ENT] += wp * en;
+          si[MS_AENT] += wp * fabs(en);
+        }
+        // u points (genint 0.5, 1.0): (nxpo, nyto)
+        if (j <= nyt) {
+          const double ugeos = -rdxof0 * (pk[o + ldx] - p);
+          const double ugdot = -rdt * (pk[o + ldx] - pmk[o] - pmk[o + ldx] + pmk[o]); // (sic, :679-680)
+          const double d2 = d2u[r + 2][lane + 2];
+          const double d4 = mon_lap<CYC, DW>(d2u, lane + 2, r + 2, i, j, nx, nyt, dxom2);
+          s[MS_U2D] += wx * (ugeos * d2);
+          s[MS_U4D] += wx * (ugeos * d4);
+          s[MS_UKE] += wx * (ugeos * ugeos);
+          s[MS_UKEDOT] += wx * (ugeos * ugdot);
+          if (k == 0) si[MS_UTAUX] += wx * (ugeos * (0.5 * (P.taux[o + ldx] + P.taux[o])));
+          if (k == NL - 1) {
+            const double ul = ug[r + 3][lane + 3];
+            si[MS_UBOT] += wx * (ul * ul);
+          }
+        }
+        // v points (genint 1.0, 0.5): (nxto, nypo)
+        if (i <= nxt) {
+          const double vgeos = rdxof0 * (pk[o + 1] - p);
+          const double vgdot = rdt * (pk[o + 1] - p - pmk[o + 1] + pmk[o]);
+          const double d2 = d2v[r + 2][lane + 2];
+          const double d4 = mon_lap<CYC, DW>(d2v, lane + 2, r + 2, i, j, nxt, ny, dxom2);
+          s[MS_V2D] += wy * (vgeos * d2);
+          s[MS_V4D] += wy * (vgeos * d4);
+          s[MS_VKE] += wy * (vgeos * vgeos);
+          s[MS_VKEDOT] += wy * (vgeos * vgdot);
+          if (k == 0) si[MS_VTAUY] += wy * (vgeos * (0.5 * (P.tauy[o + 1] + P.tauy[o])));
+          if (k == NL - 1) {
+            const double vl = vg[r + 3][lane + 3];
+            si[MS_VBOT] += wy * (vl * vl);
+          }
+        }
+        // T cells (i, j): couroc's velocities on the cell faces (:1753-1925), in the Q-G layer ...
+        if (i <= nxt && j <= nyt) {
+          const long o1 = o + 1, on = o + ldx, on1 = on + 1;
+          const double um = (!CYC && i == 1) ? 0.0 : -rdxof0 * (pk[on] - pk[o]);
+          const double up = (!CYC && i == nxt) ? 0.0 : -rdxof0 * (pk[on1] - pk[o1]);
+          const double vm = j == 1 ? 0.0 : rdxof0 * (pk[o1] - pk[o]);
+          const double vp = j == nyt ? 0.0 : rdxof0 * (pk[on1] - pk[on]);
+          if (i == 1) { m[2] = mon_min(m[2], um); m[3] = mon_min(m[3], -um); }
+          m[2] = mon_min(m[2], up);
+          m[3] = mon_min(m[3], -up);
+          m[4] = mon_min(m[4], mon_min(vm, vp));
+          m[5] = mon_min(m[5], mon_min(-vm, -vp));
+          m[6] = mon_min(m[6], -((um + up) * (um + up) + (vm + vp) * (vm + vp)));
+          if (k == 0) {
+            // ... and in the mixed layer (:1492-1744), with the Ekman part of the stress; T-grid integrals (:786-807)
+            const double uv = P.uvgfac, rh = P.rhf0hm;
+            const double *tx = P.taux, *ty = P.tauy;
+            const double mum = (!CYC && i == 1) ? 0.0 : -uv * (pk[on] - pk[o]) + rh * (ty[on] + ty[o]);
+            const double mup = (!CYC && i == nxt) ? 0.0 : -uv * (pk[on1] - pk[o1]) + rh * (ty[on1] + ty[o1]);
+            const double mvm = j == 1 ? (P.sb ? -rh * (tx[o1] + tx[o]) : 0.0) : uv * (pk[o1] - pk[o]) - rh * (tx[o1] + tx[o]);
+            const double mvp = j == nyt ? (P.nb ? -rh * (tx[on1] + tx[on]) : 0.0) : uv * (pk[on1] - pk[on]) - rh * (tx[on1] + tx[on]);
+            if (i == 1 && j > 1 && j < nyt) { mi[2] = mon_min(mi[2], mum); mi[3] = mon_min(mi[3], -mum); } // (the corner rows start at up)
+            mi[2] = mon_min(mi[2], mup);
+            mi[3] = mon_min(mi[3], -mup);
+            mi[4] = mon_min(mi[4], mon_min(mvm, mvp));
+            mi[5] = mon_min(mi[5], mon_min(-mvm, -mvp));
+            mi[6] = mon_min(mi[6], -((mum + mup) * (mum + mup) + (mvm + mvp) * (mvm + mvp)));
+            const long ot = (long)(j - 1) * ldt + (i - 1);
+            const double wt = P.wekto[ot], ss = P.sst[ot];
+            si[MS_WEKT] += wt;
+            si[MS_AWEKT] += fabs(wt);
+            si[MS_SSTWEK] += ss * wt;
+            si[MS_SST] += ss;
+            mi[0] = mon_min(mi[0], ss);
+            mi[1] = mon_min(mi[1], -ss);
+          }
+        }
+      }
+    }
+    mon_flush(s, m, red, P.psum, P.pmin, MON_NQ * k, MON_NMN * k, P.nblk, b);
+  }
+  mon_flush(si, mi, red, P.psum, P.pmin, MON_NQ * NL, MON_NMN * NL, P.nblk, b);
+}
+
+// ujeto(j) of layer k (:671-688) in the reference's order: one wave per (row, layer) puts the row's ugeos into LDS
+// (dynamic, nxpo doubles), then one lane sums i = 1..nxpo serially and subtracts ugeos(nxpo), as the Fortran loop does -
+// bitwise the reference's ujeto, so ocjpos / ocjval are too.  grid (nyto, nlo), 64 threads.
+__global__ __launch_bounds__(64) void k_mon_jet(const QgMonParams P) {
+  extern __shared__ double urow[];
+  const int j = blockIdx.x + 1, k = blockIdx.y, nx = P.g.nx, nyt = P.g.ny - 1;
+  const double *pk = P.po + P.g.fstride * k + (long)(j - 1) * P.g.ldx;
+  for (int i = threadIdx.x; i < nx; i += 64) urow[i] = -P.rdxof0 * (pk[P.g.ldx + i] - pk[i]);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double ujet = 0.0;
+  for (int i = 0; i < nx; ++i) ujet = ujet + urow[i];
+  ujet = ujet - urow[nx - 1];
+  P.ujet[(long)k * nyt + j - 1] = fabs(ujet) / (double)P.g.nxt;
+}
+
+template <int NL>
+__global__ __launch_bounds__(MON_FT) void k_mon_final(const QgMonParams P) {
+  constexpr int NS = MON_NS(NL), NM = MON_NM(NL);
+  __shared__ double rs[NS], rm[NM], jv[NL];
+  __shared__ int jp[NL];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nblk = P.nblk;
+  const int nyt = P.g.ny - 1;
+  for (int q = wv; q < NS + NM; q += MON_FT / 64) {
+    const bool sum = q < NS;
+    const double *src = sum ? P.psum + (long)q * nblk : P.pmin + (long)(q - NS) * nblk;
+    // four independent chains per lane (four loads in flight), combined in a fixed order
+    const double z = sum ? 0.0 : HUGE_VAL;
+    double a[4] = {z, z, z, z};
+    int bb = lane;
+    for (; bb + 192 < nblk; bb += 256)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a[r] = sum ? a[r] + src[bb + 64 * r] : mon_min(a[r], src[bb + 64 * r]);
+    for (; bb < nblk; bb += 64) a[0] = sum ? a[0] + src[bb] : mon_min(a[0], src[bb]);
+    double v = sum ? (a[0] + a[1]) + (a[2] + a[3]) : mon_min(mon_min(a[0], a[1]), mon_min(a[2], a[3]));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double w = __shfl_xor(v, off);
+      v = sum ? v + w : mon_min(v, w);
+    }
+    if (lane == 0) {
+      if (sum) rs[q] = v;
+      else rm[q - NS] = v;
+    }
+  }
+  // position and value of the largest ujeto (the first row that reaches it; 0, 0 when all are zero) (:690-698)
+  for (int k = wv; k < NL; k += MON_FT / 64) {
+    double bv = 0.0;
+    int bj = 0;
+    for (int j = lane + 1; j <= nyt; j += 64) {
+      const double u = P.ujet[(long)k * nyt + j - 1];
+      if (u > bv) { bv = u; bj = j; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(bv, off);
+      const int oj = __shfl_xor(bj, off);
+      if (ov > bv || (ov == bv && ov > 0.0 && oj < bj)) { bv = ov; bj = oj; }
+    }
+    if (lane == 0) { jv[k] = bv; jp[k] = bj; }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const double on = P.ocnorm, rho = P.rhooc, fnot = P.fnot;
+  const double *I = rs + MON_NQ * NL, *X = rm + MON_NMN * NL;
+  const long fs = P.g.fstride, onorth = (long)(P.g.ny - 1) * P.g.ldx;
+  double *o = P.out;
+  *o++ = I[MS_WEKT] * on;   // wetmoc
+  *o++ = I[MS_AWEKT] * on;  // watmoc
+  *o++ = I[MS_WEKP] * on;   // wepmoc
+  *o++ = I[MS_AWEKP] * on;  // wapmoc
+  *o++ = I[MS_ENT] * on;    // entmoc
+  *o++ = I[MS_AENT] * on;   // enamoc
+  for (int k = 0; k < NL - 1; ++k) *o++ = rs[MON_NQ * k + MS_ETA] * on;                         // etamoc
+  for (int k = 0; k < NL - 1; ++k) *o++ = rs[MON_NQ * k + MS_ETA2] * on;                        // et2moc
+  for (int k = 0; k < NL - 1; ++k) *o++ = rho * P.gpoc[k] * rs[MON_NQ * k + MS_ETADOT];        // ddtpeoc (no ocnorm, :581)
+  *o++ = rho * P.gpoc[0] * I[MS_ETAENT] * on;                                                     // pkenoc
+  *o++ = rho * (I[MS_VTAUY] + I[MS_UTAUX]) * on;                                                  // utauoc
+  double occ[NL];
+  for (int k = 0; k < NL; ++k) {
+    const double *S = rs + MON_NQ * k, *M = rm + MON_NMN * k, h = P.hoc[k];
+    const double pomin = M[0], pomax = -M[1];
+    const double poref = fnot > 0.0 ? P.po[fs * k] : (fnot < 0.0 ? P.po[fs * k + onorth] : 0.0);
+    const double pmin_f = pomin / fnot, pmax_f = pomax / fnot;
+    occ[k] = 1.0e-6 * h * (P.po[fs * k] - P.po[fs * k + onorth]) / fnot;
+    o[0 * NL + k] = S[MS_P] * on;                                                        // pavgoc
+    o[1 * NL + k] = S[MS_Q] * on;                                                        // qavgoc
+    o[2 * NL + k] = -rho * P.ah2oc[k] * h * (S[MS_U2D] + S[MS_V2D]) * on;               // ah2doc
+    o[3 * NL + k] = rho * P.ah4oc[k] * h * (S[MS_U4D] + S[MS_V4D]) * on;                // ah4doc
+    o[4 * NL + k] = 0.5 * rho * h * (S[MS_UKE] + S[MS_VKE]) * on;                       // kealoc
+    o[5 * NL + k] = rho * h * (S[MS_UKEDOT] + S[MS_VKEDOT]) * on;                       // ddtkeoc
+    o[6 * NL + k] = 1.0e-6 * h * ((pmin_f < pmax_f ? pmin_f : pmax_f) - poref / fnot);  // osfmin
+    o[7 * NL + k] = 1.0e-6 * h * ((pmin_f > pmax_f ? pmin_f : pmax_f) - poref / fnot);  // osfmax
+    o[8 * NL + k] = occ[k];                                                              // occirc
+    o[9 * NL + k] = (double)jp[k];                                                       // ocjpos
+    o[10 * NL + k] = jv[k];                                                              // ocjval
+  }
+  o += 11 * NL;
+  *o++ = 0.5 * rho * P.delek * fabs(fnot) * (I[MS_UBOT] + I[MS_VBOT]) * on;  // btdgoc
+  *o++ = X[0];                                                                // sstmin
+  *o++ = -X[1];                                                               // sstmax
+  *o++ = I[MS_SST] * on;                                                      // tmlmoc
+  *o++ = rho * P.cpoc * I[MS_SSTWEK] * on;                                    // hfmloc
+  double tot = 0.0;
+  for (int k = 0; k < NL; ++k) tot += occ[k];
+  *o++ = tot;                                                                 // occtot
+  const double cfac = P.hdxom1 * P.dto;
+  *o++ = X[2];                       // umminoc
+  *o++ = -X[3];                      // ummaxoc
+  *o++ = X[4];                       // vmminoc
+  *o++ = -X[5];                      // vmmaxoc
+  *o++ = cfac * sqrt(-X[6]);         // cnmloc
+  for (int k = 0; k < NL; ++k) {
+    const double *M = rm + MON_NMN * k;
+    o[k] = M[2];                     // ugminoc
+    o[NL + k] = -M[3];               // ugmaxoc
+    o[2 * NL + k] = M[4];            // vgminoc
+    o[3 * NL + k] = -M[5];           // vgmaxoc
+    o[4 * NL + k] = cfac * sqrt(-M[6]); // cnqgoc
+  }
+}

@@ -34,6 +34,7 @@
 #include "k_fft3_unpack.h"
 #include "k_oml.h"
 #include "k_valids.h"
+#include "k_monitors.h"
 #include "k_setup.h"
 #include "slab_comm.h"
 
@@ -155,6 +156,16 @@ struct qgcm_hip_ctx {
   // validity scan (qgcm_hip_valids): partials, results, optional bottom topography
   double *val_part = nullptr, *val_out = nullptr, *dtopoc = nullptr;
   double *area_part = nullptr, *area_out = nullptr; // trapezoid area integrals of po, pom, qo (k_setup.h)
+  // ocean monitors (qgcm_hip_monitors, k_monitors.h): constants, the fields that do not evolve on the device without
+  // the mixed layer (qgcm_hip_set_monitor_fields), partials and the pinned result, all allocated on first use
+  struct {
+    bool prm_set = false;
+    qgcm_hip_mon_params prm;
+    int ldt = 0;
+    double *taux = nullptr, *tauy = nullptr, *wekto = nullptr, *sst = nullptr;
+    double *psum = nullptr, *pmin = nullptr, *ujet = nullptr, *out = nullptr;
+    double *hout = nullptr; // pinned host copy of out
+  } mon;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
   std::map<int, hipGraphExec_t> slab_graphs;
@@ -340,6 +351,10 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   double *vp[] = {c->val_part, c->val_out, c->dtopoc, c->th_cgath, c->area_part, c->area_out, c->ybnd, c->rspl};
   for (double *p : vp)
     if (p) hipFree(p);
+  double *monp[] = {c->mon.taux, c->mon.tauy, c->mon.wekto, c->mon.sst, c->mon.psum, c->mon.pmin, c->mon.ujet, c->mon.out};
+  for (double *p : monp)
+    if (p) hipFree(p);
+  if (c->mon.hout) hipHostFree(c->mon.hout);
   double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
                    c->oml.taux, c->oml.tauy, c->oml.partA, c->oml.partB, c->oml.diag};
   for (double *p : omp)
@@ -1862,6 +1877,107 @@ extern "C" int qgcm_hip_valids(qgcm_hip_handle c, double *out, int *solnok) {
   if (out)
     for (int q = 0; q < nres - 1; ++q) out[q] = h[q];
   if (solnok) *solnok = h[nres - 1] > 0.5 ? 1 : 0;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// ocean monitors: the ocean half of monnc_comp and couroc
+// ---------------------------------------------------------------------------
+extern "C" int qgcm_hip_monitor_len(qgcm_hip_handle c) { return c ? MON_LEN(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_set_mon_params(qgcm_hip_handle c, const qgcm_hip_mon_params *p) {
+  if (!c || !p) QG_FAIL("qgcm_hip_set_mon_params: null argument");
+  c->mon.prm = *p;
+  c->mon.prm_set = true;
+  return 0;
+}
+
+extern "C" int qgcm_hip_set_monitor_fields(qgcm_hip_handle c, const double *tauxo, const double *tauyo, const double *wekto,
+                                           const double *sst) {
+  if (check_ready(c, "qgcm_hip_set_monitor_fields")) return 1;
+  if (!c->whole) QG_FAIL("qgcm_hip_set_monitor_fields: only for a handle that owns the whole domain");
+  const QgGeom &g = c->g;
+  const int nyt = g.ny - 1;
+  auto &m = c->mon;
+  if (!m.ldt) m.ldt = round_up(g.nxt, 16);
+  if (tauxo) {
+    if (!m.taux && dalloc(&m.taux, (size_t)g.ldx * g.ny)) return 1;
+    if (upload2d(c, m.taux, g.ldx, tauxo, g.nx, g.ny)) return 1;
+  }
+  if (tauyo) {
+    if (!m.tauy && dalloc(&m.tauy, (size_t)g.ldx * g.ny)) return 1;
+    if (upload2d(c, m.tauy, g.ldx, tauyo, g.nx, g.ny)) return 1;
+  }
+  if (wekto) {
+    if (!m.wekto && dalloc(&m.wekto, (size_t)m.ldt * nyt)) return 1;
+    if (upload2d(c, m.wekto, m.ldt, wekto, g.nxt, nyt)) return 1;
+  }
+  if (sst) {
+    if (!m.sst && dalloc(&m.sst, (size_t)m.ldt * nyt)) return 1;
+    if (upload2d(c, m.sst, m.ldt, sst, g.nxt, nyt)) return 1;
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_monitors(qgcm_hip_handle c, double *out) {
+  if (check_ready(c, "qgcm_hip_monitors")) return 1;
+  if (!out) QG_FAIL("qgcm_hip_monitors: null argument");
+  if (!c->whole) QG_FAIL("qgcm_hip_monitors: only for a handle that owns the whole domain (y-slabs need a cross-rank reduction)");
+  if (c->g.atm) QG_FAIL("qgcm_hip_monitors: the handle is an atmosphere (only the ocean half of monnc_comp is implemented)");
+  auto &m = c->mon;
+  if (!m.prm_set) QG_FAIL("qgcm_hip_monitors: qgcm_hip_set_mon_params has not been called");
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  const int nl = g.nl, nyt = g.ny - 1;
+  QgMonParams P;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  if (c->oml.on) { // the mixed layer's own stress, wekto and sst
+    P.taux = c->oml.taux; P.tauy = c->oml.tauy; P.wekto = c->oml.wekto; P.sst = c->oml.sst[c->oml.is];
+    P.ldt = c->oml.ldt;
+  } else {
+    const char *miss = !m.taux ? "tauxo" : !m.tauy ? "tauyo" : !m.wekto ? "wekto" : !m.sst ? "sst" : nullptr;
+    if (miss) QG_FAIL("qgcm_hip_monitors: %s was never given (qgcm_hip_set_monitor_fields) and the mixed layer is off", miss);
+    P.taux = m.taux; P.tauy = m.tauy; P.wekto = m.wekto; P.sst = m.sst;
+    P.ldt = m.ldt;
+  }
+  // the time levels qgcm_hip_get_state hands out at this point of the loop (after an averaging step: the averaged ones)
+  P.po = c->p[c->ip]; P.pom = c->p[c->ip ^ 1]; P.qo = c->q[c->iq];
+  P.wekpo = c->wekpo; P.entoc = c->entoc;
+  P.ntx = (g.nx + MON_TX - 1) / MON_TX;
+  P.nblk = P.ntx * ((g.ny + MON_TY - 1) / MON_TY);
+  if (!m.psum) {
+    if (dalloc(&m.psum, (size_t)MON_NS(nl) * P.nblk) || dalloc(&m.pmin, (size_t)MON_NM(nl) * P.nblk) ||
+        dalloc(&m.ujet, (size_t)nyt * nl) || dalloc(&m.out, MON_LEN(nl)))
+      return 1;
+    HIPCHECK(hipHostMalloc((void **)&m.hout, sizeof(double) * MON_LEN(nl), hipHostMallocDefault));
+  }
+  P.psum = m.psum; P.pmin = m.pmin; P.ujet = m.ujet; P.out = m.out;
+  P.sb = m.prm.sb_hflux; P.nb = m.prm.nb_hflux;
+  // MODULE occonst as src/q-gcm.F:414-436 derives it; dto = tdto/2 exactly
+  P.dto = 0.5 * pr.tdto;
+  P.rdxof0 = 1.0 / (pr.dxo * pr.fnot);
+  P.dxom2 = 1.0 / (pr.dxo * pr.dxo);
+  P.hdxom1 = 0.5 / pr.dxo;
+  P.uvgfac = m.prm.ycexp * P.rdxof0;           // src/monitor_diag.F:1493-1494
+  P.rhf0hm = 0.5 / (pr.fnot * m.prm.hmoc);
+  for (int k = 0; k < nl - 1; ++k) P.rgpoc[k] = 1.0 / pr.gpoc[k];
+  P.ocnorm = 1.0 / ((double)g.nxt * (double)nyt); // src/parameters_data.F:88
+  P.rhooc = m.prm.rhooc; P.cpoc = m.prm.cpoc; P.fnot = pr.fnot; P.delek = pr.delek;
+  for (int k = 0; k < nl; ++k) {
+    P.hoc[k] = pr.hoc[k]; P.gpoc[k] = pr.gpoc[k]; P.ah2oc[k] = pr.ah2oc[k]; P.ah4oc[k] = pr.ah4oc[k];
+  }
+#define QG_MON(NLV)                                                                                         \
+  if (g.cyc) hipLaunchKernelGGL((k_mon_scan<NLV, true>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);     \
+  else hipLaunchKernelGGL((k_mon_scan<NLV, false>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);          \
+  hipLaunchKernelGGL(k_mon_jet, dim3(nyt, nl), dim3(64), sizeof(double) * g.nx, c->stream, P);              \
+  hipLaunchKernelGGL((k_mon_final<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P)
+  QG_SWITCH_NL(nl, QG_MON, "k_mon");
+#undef QG_MON
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(m.hout, m.out, sizeof(double) * MON_LEN(nl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  memcpy(out, m.hout, sizeof(double) * MON_LEN(nl));
   return 0;
 }
 

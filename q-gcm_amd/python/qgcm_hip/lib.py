@@ -41,6 +41,14 @@ class OmlParams(C.Structure):
     ]
 
 
+class MonParams(C.Structure):
+    """struct qgcm_hip_mon_params (include/qgcm_hip.h)."""
+    _fields_ = [
+        ("rhooc", C.c_double), ("cpoc", C.c_double), ("hmoc", C.c_double), ("ycexp", C.c_double),
+        ("sb_hflux", C.c_int), ("nb_hflux", C.c_int),
+    ]
+
+
 # every symbol include/qgcm_hip.h declares
 SYMBOLS = [
     "qgcm_hip_create", "qgcm_hip_destroy", "qgcm_hip_last_error", "qgcm_hip_abi_version",
@@ -59,6 +67,7 @@ SYMBOLS = [
     "qgcm_hip_oml_init", "qgcm_hip_oml_set_state", "qgcm_hip_oml_get_state", "qgcm_hip_oml_set_forcing",
     "qgcm_hip_oml", "qgcm_hip_oml_get_diag", "qgcm_hip_set_dtopoc", "qgcm_hip_valids",
     "qgcm_hip_init_from_p", "qgcm_hip_wekpo_from_tau", "qgcm_hip_prsamp",
+    "qgcm_hip_monitor_len", "qgcm_hip_set_mon_params", "qgcm_hip_set_monitor_fields", "qgcm_hip_monitors",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -142,6 +151,10 @@ def load_library():
     L.qgcm_hip_init_from_p.argtypes = [vp]
     L.qgcm_hip_wekpo_from_tau.argtypes = [vp, dp, dp]
     L.qgcm_hip_prsamp.argtypes = [vp, dp]
+    L.qgcm_hip_monitor_len.argtypes = [vp]
+    L.qgcm_hip_set_mon_params.argtypes = [vp, C.POINTER(MonParams)]
+    L.qgcm_hip_set_monitor_fields.argtypes = [vp, dp, dp, dp, dp]
+    L.qgcm_hip_monitors.argtypes = [vp, dp]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

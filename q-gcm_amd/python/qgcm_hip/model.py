@@ -25,6 +25,29 @@ def _f(a):
     return None if a is None else np.asfortranarray(a, dtype=np.float64)
 
 
+# layout of qgcm_hip_monitors (include/qgcm_hip.h): (name, length in units of nlo: 0 = scalar, -1 = nlo-1, 1 = nlo)
+MONITOR_LAYOUT = ([(n, 0) for n in ("wetmoc", "watmoc", "wepmoc", "wapmoc", "entmoc", "enamoc")]
+                  + [(n, -1) for n in ("etamoc", "et2moc", "ddtpeoc")] + [("pkenoc", 0), ("utauoc", 0)]
+                  + [(n, 1) for n in ("pavgoc", "qavgoc", "ah2doc", "ah4doc", "kealoc", "ddtkeoc", "osfmin", "osfmax",
+                                      "occirc", "ocjpos", "ocjval")]
+                  + [(n, 0) for n in ("btdgoc", "sstmin", "sstmax", "tmlmoc", "hfmloc", "occtot",
+                                      "umminoc", "ummaxoc", "vmminoc", "vmmaxoc", "cnmloc")]
+                  + [(n, 1) for n in ("ugminoc", "ugmaxoc", "vgminoc", "vgmaxoc", "cnqgoc")])
+
+
+def unpack_monitors(v, nl):
+    """dict name -> float or array from the packed vector of qgcm_hip_monitors; ocjpos as int (1-based row, 0: none)."""
+    out, i = {}, 0
+    for name, kind in MONITOR_LAYOUT:
+        n = {0: 1, -1: nl - 1, 1: nl}[kind]
+        x = np.array(v[i:i + n], dtype=np.float64)
+        out[name] = float(x[0]) if kind == 0 else (x.astype(np.int64) if name == "ocjpos" else x)
+        i += n
+    if i != len(v):
+        raise QgcmHipError("monitor vector has %d entries, the layout %d" % (len(v), i))
+    return out
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -236,6 +259,38 @@ class OceanModel:
         ok = C.c_int()
         check(self.L.qgcm_hip_valids(self.h, _dp(out), C.byref(ok)))
         return bool(ok.value), out
+
+    # -- ocean monitors (ocean half of `call monnc_comp` + couroc, src/monitor_diag.F) --
+    def set_monitor_params(self, oml=None, rhooc=None, cpoc=None, hmoc=None, ycexp=None, sb_hflux=None, nb_hflux=None):
+        """Constants of MODULE occonst / intrfac that monnc_comp and couroc read and the handle does not hold:
+        rhooc, cpoc, and hmoc, ycexp, sb_hflux, nb_hflux of couroc's mixed-layer velocities.  Defaults come from
+        `oml` (a qgcm_hip.OmlConfig; its defaults are the examples' input.params values)."""
+        from .config import OmlConfig
+        from .lib import MonParams
+        om = OmlConfig() if oml is None else oml
+        pick = lambda v, d: d if v is None else v
+        p = MonParams()
+        p.rhooc, p.cpoc = float(pick(rhooc, om.rhooc)), float(pick(cpoc, om.cpoc))
+        p.hmoc, p.ycexp = float(pick(hmoc, om.hmoc)), float(pick(ycexp, om.ycexp))
+        p.sb_hflux, p.nb_hflux = int(pick(sb_hflux, om.sb_hflux)), int(pick(nb_hflux, om.nb_hflux))
+        check(self.L.qgcm_hip_set_mon_params(self.h, C.byref(p)))
+
+    def set_monitor_fields(self, tauxo=None, tauyo=None, wekto=None, sst=None):
+        """tauxo, tauyo (nxpo,nypo), wekto, sst (nxto,nyto): the fields the monitors read that do not evolve on the
+        device without the mixed layer (with it on, its own arrays are read).  None = leave unchanged."""
+        a = [_f(x) for x in (tauxo, tauyo, wekto, sst)]
+        check(self.L.qgcm_hip_set_monitor_fields(self.h, *[_dp(x) for x in a]))
+
+    def monitor_vector(self):
+        """The packed result of qgcm_hip_monitors (order: include/qgcm_hip.h)."""
+        out = np.zeros(self.L.qgcm_hip_monitor_len(self.h))
+        check(self.L.qgcm_hip_monitors(self.h, _dp(out)))
+        return out
+
+    def monitors(self):
+        """The ocean variables of MODULE monitor that monnc_comp / couroc compute (src/monitor_data.F:50-71), from
+        the device state without pulling it: dict of scalars and per-layer / per-interface numpy arrays."""
+        return unpack_monitors(self.monitor_vector(), self.cfg.nlo)
 
     # -- ocean mixed layer (`call oml`, src/q-gcm.F:1232; SURVEY 8 row f1) -------
     def oml_init(self, om):
