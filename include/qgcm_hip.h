@@ -344,7 +344,7 @@ int qgcm_hip_valids(qgcm_hip_handle h, double *out, int *solnok);
  * The ocean half of "call monnc_comp" (src/monitor_diag.F:479-832 with poref :173-182, del4bx / del4ch, genint) and
  * "call couroc" (:1450-1928) on the device: instead of pulling po, pom, qo every dgnday, qgcm_hip_monitor_len(h) =
  * 19*nlo + 16 doubles come back.  It reads the time levels qgcm_hip_get_state would return at that point (after an
- * averaging step the averaged ones), and changes no state.  Whole-domain ocean handles only.
+ * averaging step the averaged ones), and changes no state.  Whole-domain ocean handles (y-slabs: below).
  * qgcm_hip_set_mon_params: the constants the handle does not hold (dto = tdto/2 and the rest of MODULE occonst are
  *   derived from qgcm_hip_params as src/q-gcm.F:414-436 does).
  * qgcm_hip_set_monitor_fields: tauxo, tauyo (nxpo,nypo) (intrfac), wekto (nxto,nyto) (ocstate), sst (nxto,nyto)
@@ -373,6 +373,40 @@ int qgcm_hip_set_mon_params(qgcm_hip_handle h, const qgcm_hip_mon_params *p);
 int qgcm_hip_set_monitor_fields(qgcm_hip_handle h, const double *tauxo, const double *tauyo, const double *wekto,
                                 const double *sst);
 int qgcm_hip_monitors(qgcm_hip_handle h, double *out);
+
+/* ---- the three diagnostics on y-slabs: per-rank summary, one all-gather, combine ----------------------------
+ * qgcm_hip_monitors, qgcm_hip_valids and qgcm_hip_prsamp refuse y-slab handles.  On slabs each rank writes a
+ * fixed-size summary of the rows it owns into a device buffer (_part), the caller all-gathers the summaries (rank r's
+ * at r * len, as comm.all_gather produces them) and every rank combines the gathered buffer (_combine): bitwise the
+ * same result on every rank, in the layout of the whole-domain call.
+ *   Ownership: p rows g0..g1 of the slab (local jlo..jhi); T rows g0..g1, or g0..g1-1 on the rank that owns row
+ *   nypo.  Every boundary rule (genint's edge weights, del4bx's one-sided forms, couroc's sb_hflux / nb_hflux rows,
+ *   the trapezoid weights) uses global rows.  Del-4th of ugoc / vgoc at an owned row reads pom up to 3 rows beyond
+ *   the owned ones: the halo rows must be current (they are between the slab step calls).
+ *   _part_len(h): doubles per summary.  _part(h, send_dev): asynchronous on the handle's stream, like
+ *   qgcm_hip_thomas_phase.  _combine(h, gath_dev, nranks, ...): synchronous; fails when the gathered g0, g1 do not
+ *   tile rows 1..nypo in rank order.  On a whole-domain handle _part + _combine with nranks = 1 work as well.
+ *   Extrema, ocjpos / ocjval, osfmin / osfmax, occirc and everything of valids are bitwise the whole-domain values;
+ *   the integrals (sums over the ranks in rank order) agree to rounding.
+ * Summary layouts (nl = nlo; "rows" = the global rows g0, g1 as doubles):
+ *   monitors  sums (13*(nl+1)) | minima, maxima negated (7*(nl+1)) | per layer the largest ujeto of the owned T rows
+ *             (nl) | its global T row, first occurrence, 0 = none (nl) | po(1,g0,k) (nl) | po(1,g1,k) (nl) | g0, g1
+ *             = 24*nl + 22 doubles.  The combine keeps a later rank's jet only if it is strictly larger.
+ *   valids    min / max as out[0..13] of qgcm_hip_valids | thin-point weights (nl) | g0, g1  = 16 + nl doubles
+ *   prsamp    po, qo at the basin centre (nl each; 0 on the ranks that do not own row (nypo+1)/2) | xintp of po, qo
+ *             over the owned rows (nl each) | min, max of sst (+-1e30 without the mixed layer) | 1 if the rank owns
+ *             the centre row | g0, g1  = 4*nl + 5 doubles
+ * qgcm_hip_set_monitor_fields and qgcm_hip_set_dtopoc take a slab's local rows, halo rows included (as
+ * qgcm_hip_oml_set_forcing). */
+int qgcm_hip_monitor_part_len(qgcm_hip_handle h);
+int qgcm_hip_monitors_part(qgcm_hip_handle h, double *send_dev);
+int qgcm_hip_monitors_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, double *out);
+int qgcm_hip_valids_part_len(qgcm_hip_handle h);
+int qgcm_hip_valids_part(qgcm_hip_handle h, double *send_dev);
+int qgcm_hip_valids_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, double *out, int *solnok);
+int qgcm_hip_prsamp_part_len(qgcm_hip_handle h);
+int qgcm_hip_prsamp_part(qgcm_hip_handle h, double *send_dev);
+int qgcm_hip_prsamp_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, double *out);
 
 /* ---- start-up / restart arithmetic and the progress sample on the device ------------
  * qgcm_hip_init_from_p: the start-up sequence of the main program (src/q-gcm.F:711-731; atmosphere :738-749) from

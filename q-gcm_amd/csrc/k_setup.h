@@ -59,18 +59,20 @@ struct QgAreaParams {
   const double *f[3]; // po, pom, qo
   double *part;       // (AREA_NB, 3*nl)
   double *out;        // (3*nl): xintp of po(1..nl), pom(1..nl), qo(1..nl)
+  int jlo, jhi;       // the local p rows summed (a y-slab: its owned rows; trapezoid weights of the basin's edge rows)
 };
 
 // block b sums rows b, b + AREA_NB, ...; fixed order (thread-strided along the row, wave butterfly, waves left to right)
 template <int NL>
 __global__ __launch_bounds__(AREA_NT) void k_area_partial(const QgAreaParams P) {
   __shared__ double red[3 * NL][AREA_NT / 64];
-  const int nx = P.g.nx, ny = P.g.ny, ldx = P.g.ldx, tid = threadIdx.x;
+  const int nx = P.g.nx, ny = P.g.nyg, ldx = P.g.ldx, tid = threadIdx.x;
   double s[3 * NL];
 #pragma unroll
   for (int v = 0; v < 3 * NL; ++v) s[v] = 0.0;
-  for (int j = 1 + blockIdx.x; j <= ny; j += AREA_NB) {
-    const double wy = (j == 1 || j == ny) ? 0.5 : 1.0;
+  for (int j = P.jlo + blockIdx.x; j <= P.jhi; j += AREA_NB) {
+    const int gj = j + P.g.joff;
+    const double wy = (gj == 1 || gj == ny) ? 0.5 : 1.0;
     for (int i = 1 + tid; i <= nx; i += AREA_NT) {
       const double w = wy * ((i == 1 || i == nx) ? 0.5 : 1.0);
       const long o = (long)(j - 1) * ldx + (i - 1);
@@ -219,4 +221,83 @@ __global__ __launch_bounds__(256) void k_wekpo(const QgWekParams P) {
     else v = 0.5 * (W(ic - 1, jt) + W(ic, jt));
   }
   P.wekpo[(long)(jo - 1) * P.g.ldx + (io - 1)] = v;
+}
+
+// ---- the progress sample on y-slabs (qgcm_hip_prsamp_part / _combine) -----------------------------------------------
+// summary of PRS_PART_LEN(nl) doubles: po, qo at the basin centre (nl each; 0 unless this rank owns row (nypo+1)/2) |
+// xintp of po, qo over the owned rows (nl each) | min, max of sst (+-1e30 without the device mixed layer) | 1 if this
+// rank owns the centre row, else 0 | g0 | g1
+#define PRS_PART_LEN(nl) (4 * (nl) + 5)
+struct QgPrsampParams {
+  QgGeom g;
+  const double *po, *qo;
+  const double *area_part; // k_area_partial's partials of this rank's rows
+  const double *vsum;      // the rank's valids summary (k_valids_part: sst min / max at [4], [5]) or nullptr
+  int jlo, jhi;
+  double *out;             // part: the summary; combine: 4*nl + 2 results, then the status
+  const double *gath;      // combine: nranks summaries, rank-major
+  int nranks;
+  double ocnorm;
+};
+
+// 64 threads
+template <int NL>
+__global__ __launch_bounds__(64) void k_prsamp_part(const QgPrsampParams P) {
+  const int lane = threadIdx.x;
+  const QgGeom &g = P.g;
+  const int jc = (g.nyg + 1) / 2 - g.joff, ic = (g.nx + 1) / 2; // src/q-gcm.F:1974-1975, local row of the centre
+  const bool own = jc >= P.jlo && jc <= P.jhi;
+  double *o = P.out;
+  if (lane < 2 * NL) { // po (fields 0) and qo (field 2) of k_area_partial, summed over the workgroups as k_area_final
+    const int v = lane < NL ? lane : NL + lane;
+    double t = 0.0;
+    for (int b = 0; b < AREA_NB; ++b) t += P.area_part[(long)b * 3 * NL + v];
+    o[2 * NL + lane] = t;
+  } else if (lane < 3 * NL) {
+    const int k = lane - 2 * NL;
+    const long oc = g.fstride * k + (long)(jc - 1) * g.ldx + (ic - 1);
+    o[k] = own ? P.po[oc] : 0.0;
+    o[NL + k] = own ? P.qo[oc] : 0.0;
+  } else if (lane == 3 * NL) {
+    o[4 * NL] = P.vsum ? P.vsum[4] : 1.0e30;
+    o[4 * NL + 1] = P.vsum ? P.vsum[5] : -1.0e30;
+    o[4 * NL + 2] = own ? 1.0 : 0.0;
+    o[4 * NL + 3] = (double)(P.jlo + g.joff);
+    o[4 * NL + 4] = (double)(P.jhi + g.joff);
+  }
+}
+
+// nranks gathered summaries -> what qgcm_hip_prsamp returns (4*nl + 2), then out[4*nl + 2] = status (0, or r + 1:
+// rank r is the first whose rows do not continue the tiling of 1..nypo).  Sums in rank order.  One thread.
+template <int NL>
+__global__ void k_prsamp_combine(const QgPrsampParams P) {
+  if (threadIdx.x != 0) return;
+  constexpr int L = PRS_PART_LEN(NL);
+  const int R = P.nranks;
+  const double *G = P.gath;
+  int bad = 0, next = 1, owner = -1;
+  for (int r = 0; r < R && !bad; ++r) {
+    const double g0 = G[(long)r * L + L - 2], g1 = G[(long)r * L + L - 1];
+    if (g0 != (double)next || g1 < g0 || g1 > (double)P.g.nyg || (r == R - 1 && g1 != (double)P.g.nyg)) bad = r + 1;
+    else next = (int)g1 + 1;
+    if (G[(long)r * L + 4 * NL + 2] != 0.0) owner = r;
+  }
+  if (!bad && owner < 0) bad = R; // (cannot happen when the rows tile 1..nypo)
+  P.out[4 * NL + 2] = (double)bad;
+  if (bad) return;
+  double *o = P.out;
+  for (int q = 0; q < 2 * NL; ++q) {
+    o[q] = G[(long)owner * L + q];
+    double t = G[2 * NL + q];
+    for (int r = 1; r < R; ++r) t += G[(long)r * L + 2 * NL + q];
+    o[2 * NL + q] = t * P.ocnorm;
+  }
+  double mn = G[4 * NL], mx = G[4 * NL + 1];
+  for (int r = 1; r < R; ++r) {
+    const double a = G[(long)r * L + 4 * NL], b = G[(long)r * L + 4 * NL + 1];
+    mn = a < mn ? a : mn;
+    mx = b > mx ? b : mx;
+  }
+  o[4 * NL] = mn;
+  o[4 * NL + 1] = mx;
 }

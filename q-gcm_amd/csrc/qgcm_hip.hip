@@ -155,6 +155,7 @@ struct qgcm_hip_ctx {
   } oml;
   // validity scan (qgcm_hip_valids): partials, results, optional bottom topography
   double *val_part = nullptr, *val_out = nullptr, *dtopoc = nullptr;
+  double *val_sum = nullptr, *prs_out = nullptr; // y-slab prsamp: this rank's valids summary (sst), combined result
   double *area_part = nullptr, *area_out = nullptr; // trapezoid area integrals of po, pom, qo (k_setup.h)
   // ocean monitors (qgcm_hip_monitors, k_monitors.h): constants, the fields that do not evolve on the device without
   // the mixed layer (qgcm_hip_set_monitor_fields), partials and the pinned result, all allocated on first use
@@ -348,7 +349,8 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
       if (p) hipFree(p);
     delete m;
   }
-  double *vp[] = {c->val_part, c->val_out, c->dtopoc, c->th_cgath, c->area_part, c->area_out, c->ybnd, c->rspl};
+  double *vp[] = {c->val_part, c->val_out, c->dtopoc, c->th_cgath, c->area_part, c->area_out, c->ybnd, c->rspl,
+                  c->val_sum, c->prs_out};
   for (double *p : vp)
     if (p) hipFree(p);
   double *monp[] = {c->mon.taux, c->mon.tauy, c->mon.wekto, c->mon.sst, c->mon.psum, c->mon.pmin, c->mon.ujet, c->mon.out};
@@ -1839,17 +1841,18 @@ extern "C" int qgcm_hip_set_dtopoc(qgcm_hip_handle c, const double *dtopoc) {
   return upload2d(c, c->dtopoc, g.ldx, dtopoc, g.nx, g.ny);
 }
 
-extern "C" int qgcm_hip_valids(qgcm_hip_handle c, double *out, int *solnok) {
-  if (check_ready(c, "qgcm_hip_valids")) return 1;
-  if (!c->whole) QG_FAIL("qgcm_hip_valids: only for a handle that owns the whole domain");
+// last owned T row (local): the T rows of a slab are jlo..jhi, and jlo..jhi-1 on the rank that owns row nypo
+static int owned_t1(const QgGeom &g) { return (g.jhi + g.joff == g.nyg) ? g.jhi - 1 : g.jhi; }
+
+// the scan of qgcm_hip_valids over the owned rows -> c->val_part (asynchronous)
+static int launch_valids_scan(qgcm_hip_ctx *c, QgValidsParams &P, const char *who) {
+  if (check_ready(c, who)) return 1;
   const QgGeom &g = c->g;
-  if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("qgcm_hip_valids: unsupported nlo");
-  const int nres = 2 * VAL_NMM + g.nl + 1;
+  if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("%s: unsupported nlo", who);
   if (!c->val_part) {
     if (dalloc(&c->val_part, (size_t)(2 * VAL_NMM + QG_MAXL) * VAL_NB)) return 1;
-    if (dalloc(&c->val_out, (size_t)2 * VAL_NMM + QG_MAXL + 1)) return 1;
+    if (dalloc(&c->val_out, (size_t)2 * VAL_NMM + QG_MAXL + 2)) return 1;
   }
-  QgValidsParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
   P.po = c->p[c->ip];
@@ -1860,23 +1863,86 @@ extern "C" int qgcm_hip_valids(qgcm_hip_handle c, double *out, int *solnok) {
     P.ldt = c->oml.ldt;
   }
   P.dtopoc = c->dtopoc;
+  P.jlo = g.jlo;
+  P.nrow = g.jhi - g.jlo + 1;
+  P.nrowt = owned_t1(g) - g.jlo + 1;
   for (int k = 0; k < g.nl - 1; ++k) P.rgpoc[k] = 1.0 / c->prm.gpoc[k]; // src/valsubs.F:390-392
   for (int k = 0; k < g.nl; ++k) P.hoc[k] = c->prm.hoc[k];
   P.part = c->val_part;
   P.out = c->val_out;
-  P.ocnorm = 1.0 / ((double)g.nxt * (double)(g.ny - 1));
-#define QG_VALIDS(NLV)                                                                       \
-  hipLaunchKernelGGL((k_valids_scan<NLV>), dim3(VAL_NB), dim3(VAL_NT), 0, c->stream, P);      \
-  hipLaunchKernelGGL((k_valids_final<NLV>), dim3(1), dim3(VAL_NT), 0, c->stream, P)
+  P.ocnorm = 1.0 / ((double)g.nxt * (double)(g.nyg - 1));
+#define QG_VALIDS(NLV) hipLaunchKernelGGL((k_valids_scan<NLV>), dim3(VAL_NB), dim3(VAL_NT), 0, c->stream, P)
   QG_SWITCH_NL(g.nl, QG_VALIDS, "k_valids");
 #undef QG_VALIDS
   HIPCHECK(hipGetLastError());
-  double h[2 * VAL_NMM + QG_MAXL + 1];
-  HIPCHECK(hipMemcpyAsync(h, c->val_out, sizeof(double) * nres, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+
+// out[0 .. nres-2], *solnok from the device vector at c->val_out
+static int valids_fetch(qgcm_hip_ctx *c, int nres, double *out, int *solnok, double *status) {
+  double h[2 * VAL_NMM + QG_MAXL + 2];
+  HIPCHECK(hipMemcpyAsync(h, c->val_out, sizeof(double) * (nres + (status ? 1 : 0)), hipMemcpyDeviceToHost, c->stream));
   HIPCHECK(hipStreamSynchronize(c->stream));
+  if (status) {
+    *status = h[nres];
+    if (h[nres] != 0.0) return 0;
+  }
   if (out)
     for (int q = 0; q < nres - 1; ++q) out[q] = h[q];
   if (solnok) *solnok = h[nres - 1] > 0.5 ? 1 : 0;
+  return 0;
+}
+
+extern "C" int qgcm_hip_valids(qgcm_hip_handle c, double *out, int *solnok) {
+  if (check_ready(c, "qgcm_hip_valids")) return 1;
+  if (!c->whole) QG_FAIL("qgcm_hip_valids: only for a handle that owns the whole domain (y-slabs: qgcm_hip_valids_part / _combine)");
+  QgValidsParams P;
+  if (launch_valids_scan(c, P, "qgcm_hip_valids")) return 1;
+#define QG_VALIDS(NLV) hipLaunchKernelGGL((k_valids_final<NLV>), dim3(1), dim3(VAL_NT), 0, c->stream, P)
+  QG_SWITCH_NL(c->g.nl, QG_VALIDS, "k_valids");
+#undef QG_VALIDS
+  HIPCHECK(hipGetLastError());
+  return valids_fetch(c, 2 * VAL_NMM + c->g.nl + 1, out, solnok, nullptr);
+}
+
+extern "C" int qgcm_hip_valids_part_len(qgcm_hip_handle c) { return c ? VAL_PART_LEN(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_valids_part(qgcm_hip_handle c, double *send_dev) {
+  if (check_ready(c, "qgcm_hip_valids_part")) return 1;
+  if (!send_dev) QG_FAIL("qgcm_hip_valids_part: null argument");
+  QgValidsParams P;
+  if (launch_valids_scan(c, P, "qgcm_hip_valids_part")) return 1;
+  P.out = send_dev;
+#define QG_VALIDS(NLV) hipLaunchKernelGGL((k_valids_part<NLV>), dim3(1), dim3(VAL_NT), 0, c->stream, P)
+  QG_SWITCH_NL(c->g.nl, QG_VALIDS, "k_valids");
+#undef QG_VALIDS
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_valids_combine(qgcm_hip_handle c, const double *gath_dev, int nranks, double *out, int *solnok) {
+  if (check_ready(c, "qgcm_hip_valids_combine")) return 1;
+  if (!gath_dev || nranks < 1) QG_FAIL("qgcm_hip_valids_combine: need the gathered summaries and nranks >= 1");
+  const QgGeom &g = c->g;
+  if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("qgcm_hip_valids_combine: unsupported nlo");
+  if (!c->val_out && dalloc(&c->val_out, (size_t)2 * VAL_NMM + QG_MAXL + 2)) return 1;
+  QgValidsParams P;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  if (c->oml.on) P.sst = c->oml.sst[c->oml.is]; // (only whether sst is scanned: the same on every rank)
+  P.out = c->val_out;
+  P.gath = gath_dev;
+  P.nranks = nranks;
+  P.ocnorm = 1.0 / ((double)g.nxt * (double)(g.nyg - 1)); // src/parameters_data.F:88
+#define QG_VALIDS(NLV) hipLaunchKernelGGL((k_valids_combine<NLV>), dim3(1), dim3(64), 0, c->stream, P)
+  QG_SWITCH_NL(g.nl, QG_VALIDS, "k_valids");
+#undef QG_VALIDS
+  HIPCHECK(hipGetLastError());
+  double st = 0.0;
+  if (valids_fetch(c, 2 * VAL_NMM + g.nl + 1, out, solnok, &st)) return 1;
+  if (st != 0.0)
+    QG_FAIL("qgcm_hip_valids_combine: the gathered summaries do not tile rows 1..%d (rank %d of %d does not continue them)",
+            g.nyg, (int)st - 1, nranks);
   return 0;
 }
 
@@ -1895,8 +1961,7 @@ extern "C" int qgcm_hip_set_mon_params(qgcm_hip_handle c, const qgcm_hip_mon_par
 extern "C" int qgcm_hip_set_monitor_fields(qgcm_hip_handle c, const double *tauxo, const double *tauyo, const double *wekto,
                                            const double *sst) {
   if (check_ready(c, "qgcm_hip_set_monitor_fields")) return 1;
-  if (!c->whole) QG_FAIL("qgcm_hip_set_monitor_fields: only for a handle that owns the whole domain");
-  const QgGeom &g = c->g;
+  const QgGeom &g = c->g; // (a y-slab: the local rows, halo rows included)
   const int nyt = g.ny - 1;
   auto &m = c->mon;
   if (!m.ldt) m.ldt = round_up(g.nxt, 16);
@@ -1919,17 +1984,15 @@ extern "C" int qgcm_hip_set_monitor_fields(qgcm_hip_handle c, const double *taux
   return 0;
 }
 
-extern "C" int qgcm_hip_monitors(qgcm_hip_handle c, double *out) {
-  if (check_ready(c, "qgcm_hip_monitors")) return 1;
-  if (!out) QG_FAIL("qgcm_hip_monitors: null argument");
-  if (!c->whole) QG_FAIL("qgcm_hip_monitors: only for a handle that owns the whole domain (y-slabs need a cross-rank reduction)");
-  if (c->g.atm) QG_FAIL("qgcm_hip_monitors: the handle is an atmosphere (only the ocean half of monnc_comp is implemented)");
+// the parameters of the monitor kernels (partials over this handle's owned rows); allocates on first use
+static int mon_params(qgcm_hip_ctx *c, QgMonParams &P, const char *who) {
+  if (check_ready(c, who)) return 1;
+  if (c->g.atm) QG_FAIL("%s: the handle is an atmosphere (only the ocean half of monnc_comp is implemented)", who);
   auto &m = c->mon;
-  if (!m.prm_set) QG_FAIL("qgcm_hip_monitors: qgcm_hip_set_mon_params has not been called");
+  if (!m.prm_set) QG_FAIL("%s: qgcm_hip_set_mon_params has not been called", who);
   const QgGeom &g = c->g;
   const qgcm_hip_params &pr = c->prm;
-  const int nl = g.nl, nyt = g.ny - 1;
-  QgMonParams P;
+  const int nl = g.nl;
   memset(&P, 0, sizeof(P));
   P.g = g;
   if (c->oml.on) { // the mixed layer's own stress, wekto and sst
@@ -1937,20 +2000,22 @@ extern "C" int qgcm_hip_monitors(qgcm_hip_handle c, double *out) {
     P.ldt = c->oml.ldt;
   } else {
     const char *miss = !m.taux ? "tauxo" : !m.tauy ? "tauyo" : !m.wekto ? "wekto" : !m.sst ? "sst" : nullptr;
-    if (miss) QG_FAIL("qgcm_hip_monitors: %s was never given (qgcm_hip_set_monitor_fields) and the mixed layer is off", miss);
+    if (miss) QG_FAIL("%s: %s was never given (qgcm_hip_set_monitor_fields) and the mixed layer is off", who, miss);
     P.taux = m.taux; P.tauy = m.tauy; P.wekto = m.wekto; P.sst = m.sst;
     P.ldt = m.ldt;
   }
   // the time levels qgcm_hip_get_state hands out at this point of the loop (after an averaging step: the averaged ones)
   P.po = c->p[c->ip]; P.pom = c->p[c->ip ^ 1]; P.qo = c->q[c->iq];
   P.wekpo = c->wekpo; P.entoc = c->entoc;
+  // the owned rows: p rows jlo..jhi, T (jet) rows jlo..owned_t1 (a whole-domain handle: 1..nypo, 1..nyto)
+  P.jlo = g.jlo; P.jhi = g.jhi; P.njet = owned_t1(g) - g.jlo + 1;
   P.ntx = (g.nx + MON_TX - 1) / MON_TX;
-  P.nblk = P.ntx * ((g.ny + MON_TY - 1) / MON_TY);
+  P.nblk = P.ntx * ((g.jhi - g.jlo + 1 + MON_TY - 1) / MON_TY);
   if (!m.psum) {
     if (dalloc(&m.psum, (size_t)MON_NS(nl) * P.nblk) || dalloc(&m.pmin, (size_t)MON_NM(nl) * P.nblk) ||
-        dalloc(&m.ujet, (size_t)nyt * nl) || dalloc(&m.out, MON_LEN(nl)))
+        dalloc(&m.ujet, (size_t)P.njet * nl) || dalloc(&m.out, MON_LEN(nl) + 1))
       return 1;
-    HIPCHECK(hipHostMalloc((void **)&m.hout, sizeof(double) * MON_LEN(nl), hipHostMallocDefault));
+    HIPCHECK(hipHostMalloc((void **)&m.hout, sizeof(double) * (MON_LEN(nl) + 1), hipHostMallocDefault));
   }
   P.psum = m.psum; P.pmin = m.pmin; P.ujet = m.ujet; P.out = m.out;
   P.sb = m.prm.sb_hflux; P.nb = m.prm.nb_hflux;
@@ -1962,21 +2027,75 @@ extern "C" int qgcm_hip_monitors(qgcm_hip_handle c, double *out) {
   P.uvgfac = m.prm.ycexp * P.rdxof0;           // src/monitor_diag.F:1493-1494
   P.rhf0hm = 0.5 / (pr.fnot * m.prm.hmoc);
   for (int k = 0; k < nl - 1; ++k) P.rgpoc[k] = 1.0 / pr.gpoc[k];
-  P.ocnorm = 1.0 / ((double)g.nxt * (double)nyt); // src/parameters_data.F:88
+  P.ocnorm = 1.0 / ((double)g.nxt * (double)(g.nyg - 1)); // src/parameters_data.F:88
   P.rhooc = m.prm.rhooc; P.cpoc = m.prm.cpoc; P.fnot = pr.fnot; P.delek = pr.delek;
   for (int k = 0; k < nl; ++k) {
     P.hoc[k] = pr.hoc[k]; P.gpoc[k] = pr.gpoc[k]; P.ah2oc[k] = pr.ah2oc[k]; P.ah4oc[k] = pr.ah4oc[k];
   }
+  return 0;
+}
+
+// the scan and the jet rows over the owned rows; then `last` (k_mon_final or k_monslab_part) reduces them
+static int launch_monitors(qgcm_hip_ctx *c, const QgMonParams &P, bool part) {
+  const QgGeom &g = c->g;
 #define QG_MON(NLV)                                                                                         \
-  if (g.cyc) hipLaunchKernelGGL((k_mon_scan<NLV, true>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);     \
-  else hipLaunchKernelGGL((k_mon_scan<NLV, false>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);          \
-  hipLaunchKernelGGL(k_mon_jet, dim3(nyt, nl), dim3(64), sizeof(double) * g.nx, c->stream, P);              \
-  hipLaunchKernelGGL((k_mon_final<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P)
+  if (c->whole && g.cyc) hipLaunchKernelGGL((k_mon_scan<NLV, true>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);  \
+  else if (c->whole) hipLaunchKernelGGL((k_mon_scan<NLV, false>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);      \
+  else if (g.cyc) hipLaunchKernelGGL((k_monslab_scan<NLV, true>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);      \
+  else hipLaunchKernelGGL((k_monslab_scan<NLV, false>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);                \
+  hipLaunchKernelGGL(k_mon_jet, dim3(P.njet, g.nl), dim3(64), sizeof(double) * g.nx, c->stream, P);         \
+  if (part) hipLaunchKernelGGL((k_monslab_part<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P);                 \
+  else hipLaunchKernelGGL((k_mon_final<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P)
+  QG_SWITCH_NL(g.nl, QG_MON, "k_mon");
+#undef QG_MON
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_monitors(qgcm_hip_handle c, double *out) {
+  if (check_ready(c, "qgcm_hip_monitors")) return 1;
+  if (!out) QG_FAIL("qgcm_hip_monitors: null argument");
+  if (!c->whole)
+    QG_FAIL("qgcm_hip_monitors: only for a handle that owns the whole domain (y-slabs: qgcm_hip_monitors_part / _combine)");
+  QgMonParams P;
+  if (mon_params(c, P, "qgcm_hip_monitors") || launch_monitors(c, P, false)) return 1;
+  auto &m = c->mon;
+  const int nl = c->g.nl;
+  HIPCHECK(hipMemcpyAsync(m.hout, m.out, sizeof(double) * MON_LEN(nl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  memcpy(out, m.hout, sizeof(double) * MON_LEN(nl));
+  return 0;
+}
+
+extern "C" int qgcm_hip_monitor_part_len(qgcm_hip_handle c) { return c ? MON_PART_LEN(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_monitors_part(qgcm_hip_handle c, double *send_dev) {
+  if (check_ready(c, "qgcm_hip_monitors_part")) return 1;
+  if (!send_dev) QG_FAIL("qgcm_hip_monitors_part: null argument");
+  QgMonParams P;
+  if (mon_params(c, P, "qgcm_hip_monitors_part")) return 1;
+  P.out = send_dev;
+  return launch_monitors(c, P, true);
+}
+
+extern "C" int qgcm_hip_monitors_combine(qgcm_hip_handle c, const double *gath_dev, int nranks, double *out) {
+  if (check_ready(c, "qgcm_hip_monitors_combine")) return 1;
+  if (!gath_dev || !out || nranks < 1) QG_FAIL("qgcm_hip_monitors_combine: need the gathered summaries, out and nranks >= 1");
+  QgMonParams P;
+  if (mon_params(c, P, "qgcm_hip_monitors_combine")) return 1;
+  P.gath = gath_dev;
+  P.nranks = nranks;
+  auto &m = c->mon;
+  const int nl = c->g.nl;
+#define QG_MON(NLV) hipLaunchKernelGGL((k_monslab_combine<NLV>), dim3(1), dim3(256), 0, c->stream, P)
   QG_SWITCH_NL(nl, QG_MON, "k_mon");
 #undef QG_MON
   HIPCHECK(hipGetLastError());
-  HIPCHECK(hipMemcpyAsync(m.hout, m.out, sizeof(double) * MON_LEN(nl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipMemcpyAsync(m.hout, m.out, sizeof(double) * (MON_LEN(nl) + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHECK(hipStreamSynchronize(c->stream));
+  if (m.hout[MON_LEN(nl)] != 0.0)
+    QG_FAIL("qgcm_hip_monitors_combine: the gathered summaries do not tile rows 1..%d (rank %d of %d does not continue them)",
+            c->g.nyg, (int)m.hout[MON_LEN(nl)] - 1, nranks);
   memcpy(out, m.hout, sizeof(double) * MON_LEN(nl));
   return 0;
 }
@@ -1984,7 +2103,8 @@ extern "C" int qgcm_hip_monitors(qgcm_hip_handle c, double *out) {
 // ---------------------------------------------------------------------------
 // start-up / restart arithmetic and the progress sample on the device
 // ---------------------------------------------------------------------------
-static int launch_area_sums(qgcm_hip_ctx *c) {
+// the trapezoid sums over the owned rows (k_area_partial); with `final` also their reduction into c->area_out
+static int launch_area_sums(qgcm_hip_ctx *c, bool final = true) {
   const QgGeom &g = c->g;
   if (!c->area_part) {
     if (dalloc(&c->area_part, (size_t)AREA_NB * 3 * QG_MAXL) || dalloc(&c->area_out, (size_t)3 * QG_MAXL)) return 1;
@@ -1994,9 +2114,10 @@ static int launch_area_sums(qgcm_hip_ctx *c) {
   P.g = g;
   P.f[0] = c->p[c->ip]; P.f[1] = c->p[c->ip ^ 1]; P.f[2] = c->q[c->iq];
   P.part = c->area_part; P.out = c->area_out;
+  P.jlo = g.jlo; P.jhi = g.jhi;
 #define QG_AREA(NLV)                                                                          \
   hipLaunchKernelGGL((k_area_partial<NLV>), dim3(AREA_NB), dim3(AREA_NT), 0, c->stream, P);     \
-  hipLaunchKernelGGL((k_area_final<NLV>), dim3(1), dim3(64), 0, c->stream, P)
+  if (final) hipLaunchKernelGGL((k_area_final<NLV>), dim3(1), dim3(64), 0, c->stream, P)
   QG_SWITCH_NL(g.nl, QG_AREA, "k_area");
 #undef QG_AREA
   HIPCHECK(hipGetLastError());
@@ -2083,7 +2204,7 @@ extern "C" int qgcm_hip_wekpo_from_tau(qgcm_hip_handle c, const double *tauxo, c
 extern "C" int qgcm_hip_prsamp(qgcm_hip_handle c, double *out) {
   if (check_ready(c, "qgcm_hip_prsamp")) return 1;
   if (!out) QG_FAIL("qgcm_hip_prsamp: null argument");
-  if (!c->whole) QG_FAIL("qgcm_hip_prsamp: only for a handle that owns the whole domain");
+  if (!c->whole) QG_FAIL("qgcm_hip_prsamp: only for a handle that owns the whole domain (y-slabs: qgcm_hip_prsamp_part / _combine)");
   const QgGeom &g = c->g;
   const int nl = g.nl;
   if (launch_area_sums(c)) return 1;
@@ -2110,6 +2231,67 @@ extern "C" int qgcm_hip_prsamp(qgcm_hip_handle c, double *out) {
     out[4 * nl] = v[4];     // min, max of sst (layout of qgcm_hip_valids)
     out[4 * nl + 1] = v[5];
   }
+  return 0;
+}
+
+extern "C" int qgcm_hip_prsamp_part_len(qgcm_hip_handle c) { return c ? PRS_PART_LEN(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_prsamp_part(qgcm_hip_handle c, double *send_dev) {
+  if (check_ready(c, "qgcm_hip_prsamp_part")) return 1;
+  if (!send_dev) QG_FAIL("qgcm_hip_prsamp_part: null argument");
+  const QgGeom &g = c->g;
+  if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("qgcm_hip_prsamp_part: unsupported nlo");
+  if (launch_area_sums(c, false)) return 1;
+  QgPrsampParams P;
+  memset(&P, 0, sizeof(P));
+  if (c->oml.on) { // min, max of sst: this rank's valids summary
+    QgValidsParams V;
+    if (launch_valids_scan(c, V, "qgcm_hip_prsamp_part")) return 1;
+    if (!c->val_sum && dalloc(&c->val_sum, (size_t)VAL_PART_LEN(QG_MAXL))) return 1;
+    V.out = c->val_sum;
+#define QG_VALIDS(NLV) hipLaunchKernelGGL((k_valids_part<NLV>), dim3(1), dim3(VAL_NT), 0, c->stream, V)
+    QG_SWITCH_NL(g.nl, QG_VALIDS, "k_valids");
+#undef QG_VALIDS
+    P.vsum = c->val_sum;
+  }
+  P.g = g;
+  P.po = c->p[c->ip];
+  P.qo = c->q[c->iq];
+  P.area_part = c->area_part;
+  P.jlo = g.jlo; P.jhi = g.jhi;
+  P.out = send_dev;
+#define QG_PRS(NLV) hipLaunchKernelGGL((k_prsamp_part<NLV>), dim3(1), dim3(64), 0, c->stream, P)
+  QG_SWITCH_NL(g.nl, QG_PRS, "k_prsamp");
+#undef QG_PRS
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_prsamp_combine(qgcm_hip_handle c, const double *gath_dev, int nranks, double *out) {
+  if (check_ready(c, "qgcm_hip_prsamp_combine")) return 1;
+  if (!gath_dev || !out || nranks < 1) QG_FAIL("qgcm_hip_prsamp_combine: need the gathered summaries, out and nranks >= 1");
+  const QgGeom &g = c->g;
+  const int nl = g.nl;
+  if (nl < 2 || nl > QG_MAXL) QG_FAIL("qgcm_hip_prsamp_combine: unsupported nlo");
+  if (!c->prs_out && dalloc(&c->prs_out, (size_t)4 * QG_MAXL + 3)) return 1;
+  QgPrsampParams P;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.out = c->prs_out;
+  P.gath = gath_dev;
+  P.nranks = nranks;
+  P.ocnorm = 1.0 / ((double)g.nxt * (double)(g.nyg - 1)); // src/parameters_data.F:88
+#define QG_PRS(NLV) hipLaunchKernelGGL((k_prsamp_combine<NLV>), dim3(1), dim3(64), 0, c->stream, P)
+  QG_SWITCH_NL(nl, QG_PRS, "k_prsamp");
+#undef QG_PRS
+  HIPCHECK(hipGetLastError());
+  double h[4 * QG_MAXL + 3];
+  HIPCHECK(hipMemcpyAsync(h, c->prs_out, sizeof(double) * (4 * nl + 3), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  if (h[4 * nl + 2] != 0.0)
+    QG_FAIL("qgcm_hip_prsamp_combine: the gathered summaries do not tile rows 1..%d (rank %d of %d does not continue them)",
+            g.nyg, (int)h[4 * nl + 2] - 1, nranks);
+  memcpy(out, h, sizeof(double) * (4 * nl + 2));
   return 0;
 }
 

@@ -68,6 +68,9 @@ SYMBOLS = [
     "qgcm_hip_oml", "qgcm_hip_oml_get_diag", "qgcm_hip_set_dtopoc", "qgcm_hip_valids",
     "qgcm_hip_init_from_p", "qgcm_hip_wekpo_from_tau", "qgcm_hip_prsamp",
     "qgcm_hip_monitor_len", "qgcm_hip_set_mon_params", "qgcm_hip_set_monitor_fields", "qgcm_hip_monitors",
+    "qgcm_hip_monitor_part_len", "qgcm_hip_monitors_part", "qgcm_hip_monitors_combine",
+    "qgcm_hip_valids_part_len", "qgcm_hip_valids_part", "qgcm_hip_valids_combine",
+    "qgcm_hip_prsamp_part_len", "qgcm_hip_prsamp_part", "qgcm_hip_prsamp_combine",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -155,6 +158,13 @@ def load_library():
     L.qgcm_hip_set_mon_params.argtypes = [vp, C.POINTER(MonParams)]
     L.qgcm_hip_set_monitor_fields.argtypes = [vp, dp, dp, dp, dp]
     L.qgcm_hip_monitors.argtypes = [vp, dp]
+    for n in ("qgcm_hip_monitor_part_len", "qgcm_hip_valids_part_len", "qgcm_hip_prsamp_part_len"):
+        getattr(L, n).argtypes = [vp]
+    for n in ("qgcm_hip_monitors_part", "qgcm_hip_valids_part", "qgcm_hip_prsamp_part"):
+        getattr(L, n).argtypes = [vp, vp]
+    L.qgcm_hip_monitors_combine.argtypes = [vp, vp, C.c_int, dp]
+    L.qgcm_hip_valids_combine.argtypes = [vp, vp, C.c_int, dp, C.POINTER(C.c_int)]
+    L.qgcm_hip_prsamp_combine.argtypes = [vp, vp, C.c_int, dp]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

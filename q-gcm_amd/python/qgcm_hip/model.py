@@ -48,6 +48,26 @@ def unpack_monitors(v, nl):
     return out
 
 
+def mon_params(oml=None, rhooc=None, cpoc=None, hmoc=None, ycexp=None, sb_hflux=None, nb_hflux=None):
+    """struct qgcm_hip_mon_params: the given values, the others from `oml` (a qgcm_hip.OmlConfig; its defaults are the
+    examples' input.params values)."""
+    from .config import OmlConfig
+    from .lib import MonParams
+    om = OmlConfig() if oml is None else oml
+    pick = lambda v, d: d if v is None else v
+    p = MonParams()
+    p.rhooc, p.cpoc = float(pick(rhooc, om.rhooc)), float(pick(cpoc, om.cpoc))
+    p.hmoc, p.ycexp = float(pick(hmoc, om.hmoc)), float(pick(ycexp, om.ycexp))
+    p.sb_hflux, p.nb_hflux = int(pick(sb_hflux, om.sb_hflux)), int(pick(nb_hflux, om.nb_hflux))
+    return p
+
+
+def prsamp_dict(out, nl):
+    """dict of the packed result of qgcm_hip_prsamp (4*nlo + 2 doubles)."""
+    return dict(po_centre=out[:nl].copy(), qo_centre=out[nl:2 * nl].copy(), pavgoc=out[2 * nl:3 * nl].copy(),
+                qavgoc=out[3 * nl:4 * nl].copy(), sstmin=out[4 * nl], sstmax=out[4 * nl + 1])
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -156,8 +176,7 @@ class OceanModel:
         nl = self.cfg.nlo
         out = np.zeros(4 * nl + 2)
         check(self.L.qgcm_hip_prsamp(self.h, _dp(out)))
-        return dict(po_centre=out[:nl].copy(), qo_centre=out[nl:2 * nl].copy(), pavgoc=out[2 * nl:3 * nl].copy(),
-                    qavgoc=out[3 * nl:4 * nl].copy(), sstmin=out[4 * nl], sstmax=out[4 * nl + 1])
+        return prsamp_dict(out, nl)
 
     def set_state(self, po=None, pom=None, qo=None, qom=None):
         a = [_f(x) for x in (po, pom, qo, qom)]
@@ -265,14 +284,7 @@ class OceanModel:
         """Constants of MODULE occonst / intrfac that monnc_comp and couroc read and the handle does not hold:
         rhooc, cpoc, and hmoc, ycexp, sb_hflux, nb_hflux of couroc's mixed-layer velocities.  Defaults come from
         `oml` (a qgcm_hip.OmlConfig; its defaults are the examples' input.params values)."""
-        from .config import OmlConfig
-        from .lib import MonParams
-        om = OmlConfig() if oml is None else oml
-        pick = lambda v, d: d if v is None else v
-        p = MonParams()
-        p.rhooc, p.cpoc = float(pick(rhooc, om.rhooc)), float(pick(cpoc, om.cpoc))
-        p.hmoc, p.ycexp = float(pick(hmoc, om.hmoc)), float(pick(ycexp, om.ycexp))
-        p.sb_hflux, p.nb_hflux = int(pick(sb_hflux, om.sb_hflux)), int(pick(nb_hflux, om.nb_hflux))
+        p = mon_params(oml, rhooc, cpoc, hmoc, ycexp, sb_hflux, nb_hflux)
         check(self.L.qgcm_hip_set_mon_params(self.h, C.byref(p)))
 
     def set_monitor_fields(self, tauxo=None, tauyo=None, wekto=None, sst=None):

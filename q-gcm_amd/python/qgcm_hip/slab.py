@@ -345,6 +345,52 @@ class HipSlab:
              np.asfortranarray(tauxo[:, sl], dtype=np.float64), np.asfortranarray(tauyo[:, sl], dtype=np.float64)]
         check(self.L.qgcm_hip_oml_set_forcing(self.h, *[_dp(x) for x in a]))
 
+    # diagnostics: the ocean monitors, valids and prsamp as per-rank summaries (SlabOcean.monitors / valids / prsamp)
+    def set_monitor_params(self, oml=None, **kw):
+        """As OceanModel.set_monitor_params."""
+        from .model import mon_params
+        check(self.L.qgcm_hip_set_mon_params(self.h, C.byref(mon_params(oml, **kw))))
+
+    def set_monitor_fields(self, tauxo=None, tauyo=None, wekto=None, sst=None):
+        """GLOBAL arrays: tauxo, tauyo (nxpo, nypo), wekto, sst (nxto, nyto); the local rows (incl. halo rows) are cut
+        out here.  None = leave unchanged.  With the mixed layer on the monitors read its own arrays."""
+        sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
+        cut = lambda x, rows: None if x is None else np.asfortranarray(np.asarray(x, dtype=np.float64)[:, rows])
+        a = [cut(tauxo, sl), cut(tauyo, sl), cut(wekto, self.t_slice()), cut(sst, self.t_slice())]
+        check(self.L.qgcm_hip_set_monitor_fields(self.h, *[_dp(x) for x in a]))
+
+    def set_dtopoc(self, dtopoc):
+        """GLOBAL bottom topography (nxpo, nypo) for valids, None = flat."""
+        sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
+        d = None if dtopoc is None else np.asfortranarray(np.asarray(dtopoc, dtype=np.float64)[:, sl])
+        check(self.L.qgcm_hip_set_dtopoc(self.h, _dp(d)))
+
+    def diag_part_len(self, kind):
+        return {"monitors": self.L.qgcm_hip_monitor_part_len, "valids": self.L.qgcm_hip_valids_part_len,
+                "prsamp": self.L.qgcm_hip_prsamp_part_len}[kind](self.h)
+
+    def diag_part(self, kind, send):
+        """This rank's summary of `kind` -> send (device buffer of diag_part_len(kind) doubles); asynchronous."""
+        fn = {"monitors": self.L.qgcm_hip_monitors_part, "valids": self.L.qgcm_hip_valids_part,
+              "prsamp": self.L.qgcm_hip_prsamp_part}[kind]
+        check(fn(self.h, self._ptr(send)))
+        self._done()
+
+    def diag_combine(self, kind, gath):
+        """All ranks' summaries (rank-major) -> the whole-domain call's packed result (valids: (solnok, out))."""
+        nl, P = self.cfg.nlo, self.nranks
+        if kind == "monitors":
+            out = np.zeros(self.L.qgcm_hip_monitor_len(self.h))
+            check(self.L.qgcm_hip_monitors_combine(self.h, self._ptr(gath), P, _dp(out)))
+            return out
+        if kind == "valids":
+            out, ok = np.zeros(14 + nl), C.c_int()
+            check(self.L.qgcm_hip_valids_combine(self.h, self._ptr(gath), P, _dp(out), C.byref(ok)))
+            return bool(ok.value), out
+        out = np.zeros(4 * nl + 2)
+        check(self.L.qgcm_hip_prsamp_combine(self.h, self._ptr(gath), P, _dp(out)))
+        return out
+
     def set_scalars(self, s):
         s = np.ascontiguousarray(s, dtype=np.float64)
         check(self.L.qgcm_hip_set_scalars(self.h, _dp(s)))
@@ -539,6 +585,41 @@ class SlabOcean:
             for i, x in enumerate(self.slabs):
                 x.stage(3, self.h_from_lo[i], self.h_from_hi[i], None, 0)
             self._halo_pending = False
+
+    # diagnostics, collective: every rank calls them between steps() calls and gets the same result --------------
+    def diagnostic(self, kind):
+        """kind = "monitors", "valids" or "prsamp": every local slab writes its summary, one all-gather, every local
+        slab combines the gathered buffer.  Returns the list of the local slabs' results (bitwise the same)."""
+        S = self.slabs
+        bufs = getattr(self, "_diag_bufs", None)
+        if bufs is None:
+            bufs = self._diag_bufs = {}
+        if kind not in bufs:
+            n = [x.diag_part_len(kind) for x in S]
+            bufs[kind] = ([x.new_buffer(m) for x, m in zip(S, n)], [x.new_buffer(m * self.P) for x, m in zip(S, n)])
+            self._settle()
+        send, gath = bufs[kind]
+        self._join()  # the halo rows the scans read must be current
+        for i, x in enumerate(S):
+            x.diag_part(kind, send[i])
+        for x in S:  # the summaries are complete before a transport reads them (LocalComm copies on torch's stream)
+            x.sync()
+        self._comm(self.comm.all_gather, gath, send)
+        return [x.diag_combine(kind, gath[i]) for i, x in enumerate(S)]
+
+    def monitors(self):
+        """As OceanModel.monitors(): the ocean half of monnc_comp and couroc over the whole basin."""
+        from .model import unpack_monitors
+        return unpack_monitors(self.diagnostic("monitors")[0], self.cfg.nlo)
+
+    def valids(self):
+        """As OceanModel.valids(): (solnok, out)."""
+        return self.diagnostic("valids")[0]
+
+    def prsamp(self):
+        """As OceanModel.prsamp()."""
+        from .model import prsamp_dict
+        return prsamp_dict(self.diagnostic("prsamp")[0], self.cfg.nlo)
 
     def homsol(self):
         """homsol of the box ocean (src/conhoms.F:549-641) ON the slabs: the modal Helmholtz problems of a step are
