@@ -425,6 +425,48 @@ int qgcm_hip_init_from_p(qgcm_hip_handle h);
 int qgcm_hip_wekpo_from_tau(qgcm_hip_handle h, const double *tauxo, const double *tauyo);
 int qgcm_hip_prsamp(qgcm_hip_handle h, double *out);
 
+/* ---- time averages of the ocean -----------------------------------------------------------------
+ * Running mean of po (the fork's -Docnc_avg_k247: avg_ocn_k247, src/timavge.F:624-662; ocnc_avgout_k247,
+ * src/nc_subs.F:1944-2052):
+ * qgcm_hip_poavg_enable(h, on): on = 1 starts a sum at zero (unless it is on already); while it is on, every step of
+ *   qgcm_hip_steps (graphs included) and every slab stage 2 (qgcm_hip_slab_steps) adds the step's new po - after
+ *   ocqbdy, BEFORE the step's leapfrog averaging - and counts it.  on = 0 stops adding; the sum stays readable.  Off
+ *   (the default), the step's launches are exactly those without this feature.
+ * qgcm_hip_poavg_out(h, po_avg, nsum, reset): po_avg (nxpo, rows, nlo) = rnsum * sum with rnsum = 1/nsum (the
+ *   reference's one reciprocal, then a multiply; fails when nothing has been summed); NULL = do not fetch.  *nsum
+ *   (may be NULL) = the count.  reset != 0 then zeroes sum and count.  Synchronous.
+ * tavocn / tavout, ocean half (src/timavge.F:425-619, 667-880):
+ * qgcm_hip_set_tav_params: hmoc, ycexp, tsbdy, tnbdy and the sb_hflux / nb_hflux branches of tavocn.  Without it the
+ *   mixed layer's parameters are used (qgcm_hip_oml_init); with neither, qgcm_hip_tavocn fails.
+ * qgcm_hip_set_tav_fields: fnetoc (nxto,nyto) for a handle without the mixed layer (zero if never given; with the
+ *   mixed layer on, its own fnetoc is read).  tauxo, tauyo, wekto, sst come from the mixed layer when it is on, else
+ *   from qgcm_hip_set_monitor_fields, as for the monitors.  NULL = unchanged.  Synchronous.
+ * qgcm_hip_tavocn(h): adds one contribution from the state on the device (the time levels qgcm_hip_get_state would
+ *   return, i.e. after a step's averaging) and counts it; asynchronous.
+ * qgcm_hip_tav_reset(h): tavini - zeroes the sums and the count.
+ * qgcm_hip_tav_out(h, fields, nsumoc): tavout's arithmetic (rnsoc = 1/nsumoc, 0 when nsumoc = 0) into
+ *   fields[0 .. QGCM_HIP_TAV_NOUT-1], dense Fortran order, NULL = skip (only requested fields are computed and
+ *   copied): txocav, tyocav, wpocav (nxpo,nypo) | wtocav, fmocav, sstav (nxto,nyto) | pocav, qocav (nxpo,nypo,nlo) |
+ *   uufo, tufo, utufo (nxpo,nyto) | vvfo, tvfo, vtvfo (nxto,nypo) | uptpoc (nxpo,nyto) | vptpoc (nxto,nypo).  The sums
+ *   are not changed.  *nsumoc (may be NULL) = the count.  Synchronous.
+ * On a y-slab handle every call acts on the owned rows: p rows g0..g1, T rows g0..g1 (g0..g1-1 on the rank that owns
+ * row nypo); the outputs have that many rows.  The flux terms at a slab edge read the halo rows of po, tauyo and sst,
+ * which are current between slab steps.  Bitwise the reference's arithmetic (elementwise, uncontracted). */
+#define QGCM_HIP_TAV_NOUT 16
+typedef struct qgcm_hip_tav_params {
+  double hmoc, ycexp;   /* mixed layer thickness, sst advection coupling (intrfac, occonst) */
+  double tsbdy, tnbdy;  /* boundary temperatures of the options below (intrfac) */
+  int sb_hflux;         /* the reference's cpp options sb_hflux / nb_hflux as run-time flags */
+  int nb_hflux;
+} qgcm_hip_tav_params;
+int qgcm_hip_poavg_enable(qgcm_hip_handle h, int on);
+int qgcm_hip_poavg_out(qgcm_hip_handle h, double *po_avg, int *nsum, int reset);
+int qgcm_hip_set_tav_params(qgcm_hip_handle h, const qgcm_hip_tav_params *p);
+int qgcm_hip_set_tav_fields(qgcm_hip_handle h, const double *fnetoc);
+int qgcm_hip_tavocn(qgcm_hip_handle h);
+int qgcm_hip_tav_reset(qgcm_hip_handle h);
+int qgcm_hip_tav_out(qgcm_hip_handle h, double *const *fields, int *nsumoc);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

@@ -35,6 +35,7 @@
 #include "k_oml.h"
 #include "k_valids.h"
 #include "k_monitors.h"
+#include "k_tavg.h"
 #include "k_setup.h"
 #include "slab_comm.h"
 
@@ -67,10 +68,11 @@ static thread_local char g_err[512] = "";
     if (e_ != hipSuccess) QG_FAIL("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_COUNT };
+enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_COUNT };
 // (k_oml = k_oml_step, the sst step + raw entrainment; k_oml_entoc = the entrainment on the p grid)
 static const char *kKernelNames[KN_COUNT] = {"k_tend",   "k_cyc_bsums", "k_dst_fwd", "k_thomas", "k_dst_inv",
-                                             "k_constr", "k_unpack",  "k_ocqbdy", "k_lf_average", "k_oml", "k_oml_entoc", "k_noop", "k_noop_train"};
+                                             "k_constr", "k_unpack",  "k_ocqbdy", "k_lf_average", "k_oml", "k_oml_entoc", "k_noop", "k_noop_train",
+                                             "k_poavg_add"};
 
 // Device copy of the Thomas pivot tables of one set of diagonals (see QgThomasParams / build_pivots).
 struct QgThomasTab {
@@ -167,6 +169,20 @@ struct qgcm_hip_ctx {
     double *psum = nullptr, *pmin = nullptr, *ujet = nullptr, *out = nullptr;
     double *hout = nullptr; // pinned host copy of out
   } mon;
+  // running mean of po (qgcm_hip_poavg_enable, k_tavg.h): the sum over the owned rows and its count; while `on`
+  // every step of qgcm_hip_steps / the slab stage 2 adds its po before the leapfrog averaging
+  struct {
+    bool on = false;
+    double *sum = nullptr;
+    long n = 0;
+  } poavg;
+  // tavocn / tavout (qgcm_hip_tavocn, k_tavg.h): sums, means (allocated on first use), fnetoc without the mixed layer
+  struct {
+    bool prm_set = false;
+    qgcm_hip_tav_params prm;
+    double *sum = nullptr, *mean = nullptr, *fnet = nullptr;
+    long n = 0;
+  } tav;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
   std::map<int, hipGraphExec_t> slab_graphs;
@@ -357,6 +373,9 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : monp)
     if (p) hipFree(p);
   if (c->mon.hout) hipHostFree(c->mon.hout);
+  double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet};
+  for (double *p : tavp)
+    if (p) hipFree(p);
   double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
                    c->oml.taux, c->oml.tauy, c->oml.partA, c->oml.partB, c->oml.diag};
   for (double *p : omp)
@@ -2295,6 +2314,211 @@ extern "C" int qgcm_hip_prsamp_combine(qgcm_hip_handle c, const double *gath_dev
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// time averages of the ocean (k_tavg.h): the fork's running mean of po (avg_ocn_k247 / ocnc_avgout_k247)
+// and tavocn / tavout.  A y-slab handle sums and returns its owned rows.
+// ---------------------------------------------------------------------------
+static int tav_ready(qgcm_hip_ctx *c, const char *who) {
+  if (check_ready(c, who)) return 1;
+  if (c->g.atm) QG_FAIL("%s: the handle is an atmosphere (only the ocean's time averages are implemented)", who);
+  return 0;
+}
+
+// po(:, owned rows, :) into the sum (asynchronous); counts the contribution.  Nothing while the sum is off.
+static int launch_poavg(qgcm_hip_ctx *c) {
+  if (!c->poavg.on) return 0;
+  const QgGeom &g = c->g;
+  const long n2 = (long)(g.jhi - g.jlo + 1) * g.ldx / 2;
+  const unsigned nb = (unsigned)std::min<long>((n2 + TAV_NT - 1) / TAV_NT, 4096);
+  KTimer t(c, KN_POAVG);
+  hipLaunchKernelGGL(k_poavg_add, dim3(nb, g.nl), dim3(TAV_NT), 0, c->stream, c->poavg.sum, (const double *)c->p[c->ip],
+                     (long)(g.jlo - 1) * g.ldx, n2, g.fstride);
+  HIPCHECK(hipGetLastError());
+  c->poavg.n++;
+  return 0;
+}
+
+extern "C" int qgcm_hip_poavg_enable(qgcm_hip_handle c, int on) {
+  if (tav_ready(c, "qgcm_hip_poavg_enable")) return 1;
+  auto &a = c->poavg;
+  if (on && !a.on) { // the sum starts at zero
+    const size_t n = (size_t)c->g.fstride * c->g.nl;
+    if (!a.sum && dalloc(&a.sum, n)) return 1;
+    HIPCHECK(hipMemsetAsync(a.sum, 0, n * sizeof(double), c->stream));
+    a.n = 0;
+  }
+  a.on = on != 0;
+  return 0;
+}
+
+// owned rows of `nf` fields of fstride doubles at src into dense (nx_out, rows, nf) host arrays
+static int download_owned(qgcm_hip_ctx *c, double *dst, const double *src, int nx_out, int j0, int rows, int nf) {
+  const QgGeom &g = c->g;
+  for (int k = 0; k < nf; ++k)
+    if (download2d(c, dst + (size_t)k * nx_out * rows, src + (size_t)k * g.fstride + (size_t)(j0 - 1) * g.ldx, g.ldx,
+                   nx_out, rows))
+      return 1;
+  return 0;
+}
+
+extern "C" int qgcm_hip_poavg_out(qgcm_hip_handle c, double *po_avg, int *nsum, int reset) {
+  if (tav_ready(c, "qgcm_hip_poavg_out")) return 1;
+  auto &a = c->poavg;
+  if (po_avg) {
+    if (!a.sum || a.n == 0) QG_FAIL("qgcm_hip_poavg_out: no step has been summed (qgcm_hip_poavg_enable)");
+    const QgGeom &g = c->g;
+    const int rows = g.jhi - g.jlo + 1;
+    if (download_owned(c, po_avg, a.sum, g.nx, g.jlo, rows, g.nl)) return 1;
+    const double rnsum = 1.0 / (double)a.n; // src/nc_subs.F: rnsum = 1.0d0 / dble( nsum_ocavg ), then rnsum * po_avg
+    const size_t n = (size_t)g.nx * rows * g.nl;
+    for (size_t i = 0; i < n; ++i) po_avg[i] = rnsum * po_avg[i];
+  }
+  if (nsum) *nsum = (int)a.n;
+  if (reset && a.sum) {
+    HIPCHECK(hipMemsetAsync(a.sum, 0, (size_t)c->g.fstride * c->g.nl * sizeof(double), c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    a.n = 0;
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_set_tav_params(qgcm_hip_handle c, const qgcm_hip_tav_params *p) {
+  if (!c || !p) QG_FAIL("qgcm_hip_set_tav_params: null argument");
+  if (!(p->hmoc > 0.0)) QG_FAIL("qgcm_hip_set_tav_params: need hmoc > 0");
+  c->tav.prm = *p;
+  c->tav.prm_set = true;
+  return 0;
+}
+
+extern "C" int qgcm_hip_set_tav_fields(qgcm_hip_handle c, const double *fnetoc) {
+  if (tav_ready(c, "qgcm_hip_set_tav_fields")) return 1;
+  const QgGeom &g = c->g;
+  const int ldt = round_up(g.nxt, 16), nyt = g.ny - 1;
+  if (fnetoc) {
+    if (!c->tav.fnet && dalloc(&c->tav.fnet, (size_t)ldt * nyt)) return 1;
+    if (upload2d(c, c->tav.fnet, ldt, fnetoc, g.nxt, nyt)) return 1;
+  }
+  return 0;
+}
+
+static int tav_params(qgcm_hip_ctx *c, QgTavParams &P, const char *who) {
+  if (tav_ready(c, who)) return 1;
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  qgcm_hip_tav_params q;
+  if (c->tav.prm_set) {
+    q = c->tav.prm;
+  } else if (c->oml.on) {
+    const qgcm_hip_oml_params &o = c->oml.prm;
+    q.hmoc = o.hmoc; q.ycexp = o.ycexp; q.tsbdy = o.tsbdy; q.tnbdy = o.tnbdy; q.sb_hflux = o.sb_hflux; q.nb_hflux = o.nb_hflux;
+  } else {
+    QG_FAIL("%s: qgcm_hip_set_tav_params has not been called and the mixed layer is off", who);
+  }
+  if (c->oml.on) { // the mixed layer's own stress, wekto, sst and fnetoc
+    P.taux = c->oml.taux; P.tauy = c->oml.tauy; P.wekto = c->oml.wekto; P.sst = c->oml.sst[c->oml.is];
+    P.fnet = c->oml.fnet; P.ldt = c->oml.ldt;
+  } else { // the monitor fields (qgcm_hip_set_monitor_fields) and fnetoc of qgcm_hip_set_tav_fields (zero if never set)
+    const auto &m = c->mon;
+    const char *miss = !m.taux ? "tauxo" : !m.tauy ? "tauyo" : !m.wekto ? "wekto" : !m.sst ? "sst" : nullptr;
+    if (miss) QG_FAIL("%s: %s was never given (qgcm_hip_set_monitor_fields) and the mixed layer is off", who, miss);
+    P.taux = m.taux; P.tauy = m.tauy; P.wekto = m.wekto; P.sst = m.sst;
+    P.fnet = c->tav.fnet; P.ldt = m.ldt;
+  }
+  // the time levels qgcm_hip_get_state hands out here: after an averaging step, the averaged ones
+  P.po = c->p[c->ip]; P.qo = c->q[c->iq]; P.wekpo = c->wekpo;
+  P.jlo = g.jlo; P.jhi = g.jhi; P.jt1 = owned_t1(g);
+  const double rdxof0 = 1.0 / (pr.dxo * pr.fnot); // src/q-gcm.F:436
+  P.uvgfac = q.ycexp * rdxof0;                    // src/timavge.F:447-448
+  P.rhf0hm = 0.5 / (pr.fnot * q.hmoc);
+  P.tsbdy = q.tsbdy; P.tnbdy = q.tnbdy;
+  if (!c->tav.sum) {
+    if (dalloc(&c->tav.sum, (size_t)TAV_NSUM(g.nl) * g.fstride)) return 1;
+    c->tav.n = 0;
+  }
+  P.sum = c->tav.sum;
+  // (the flags select the template; kept here so that launch_tavocn needs nothing else)
+  P.mask = (q.sb_hflux ? 1u : 0u) | (q.nb_hflux ? 2u : 0u);
+  return 0;
+}
+
+extern "C" int qgcm_hip_tavocn(qgcm_hip_handle c) {
+  QgTavParams P;
+  if (tav_params(c, P, "qgcm_hip_tavocn")) return 1;
+  const QgGeom &g = c->g;
+  const bool sb = P.mask & 1u, nb = P.mask & 2u;
+  P.mask = 0;
+  const dim3 grid((g.nx + TAV_NT - 1) / TAV_NT, g.jhi - g.jlo + 1);
+#define QG_TAV3(NLV, CY)                                                                                   \
+  if (sb && nb) hipLaunchKernelGGL((k_tav_accum<NLV, CY, true, true>), grid, dim3(TAV_NT), 0, c->stream, P);       \
+  else if (sb) hipLaunchKernelGGL((k_tav_accum<NLV, CY, true, false>), grid, dim3(TAV_NT), 0, c->stream, P);       \
+  else if (nb) hipLaunchKernelGGL((k_tav_accum<NLV, CY, false, true>), grid, dim3(TAV_NT), 0, c->stream, P);       \
+  else hipLaunchKernelGGL((k_tav_accum<NLV, CY, false, false>), grid, dim3(TAV_NT), 0, c->stream, P)
+#define QG_TAV(NLV)         \
+  if (g.cyc) {              \
+    QG_TAV3(NLV, true);     \
+  } else {                  \
+    QG_TAV3(NLV, false);    \
+  }
+  QG_SWITCH_NL(g.nl, QG_TAV, "k_tav_accum");
+#undef QG_TAV
+#undef QG_TAV3
+  HIPCHECK(hipGetLastError());
+  c->tav.n++; // nsumoc = nsumoc + 1
+  return 0;
+}
+
+extern "C" int qgcm_hip_tav_reset(qgcm_hip_handle c) {
+  if (tav_ready(c, "qgcm_hip_tav_reset")) return 1;
+  if (c->tav.sum) HIPCHECK(hipMemsetAsync(c->tav.sum, 0, (size_t)TAV_NSUM(c->g.nl) * c->g.fstride * sizeof(double), c->stream));
+  c->tav.n = 0;
+  return 0;
+}
+
+extern "C" int qgcm_hip_tav_out(qgcm_hip_handle c, double *const *fields, int *nsumoc) {
+  if (tav_ready(c, "qgcm_hip_tav_out")) return 1;
+  if (nsumoc) *nsumoc = (int)c->tav.n;
+  if (!fields) return 0;
+  const QgGeom &g = c->g;
+  const int nl = g.nl;
+  // the ABI's 16 outputs -> (first field of the mean buffer, number of fields, p or T rows, columns)
+  struct Out { int f, nf; bool trow; int nx; };
+  const int u = TAV_UU(nl), e = TAV_NSUM(nl);
+  const Out map[QGCM_HIP_TAV_NOUT] = {{TAV_TX, 1, false, g.nx}, {TAV_TY, 1, false, g.nx}, {TAV_WP, 1, false, g.nx},
+                                      {TAV_WT, 1, true, g.nxt}, {TAV_FM, 1, true, g.nxt}, {TAV_SST, 1, true, g.nxt},
+                                      {TAV_P0, nl, false, g.nx}, {TAV_P0 + nl, nl, false, g.nx},
+                                      {u, 1, true, g.nx}, {u + 1, 1, true, g.nx}, {u + 2, 1, true, g.nx},
+                                      {u + 3, 1, false, g.nxt}, {u + 4, 1, false, g.nxt}, {u + 5, 1, false, g.nxt},
+                                      {e, 1, true, g.nx}, {e + 1, 1, false, g.nxt}};
+  unsigned mask = 0;
+  for (int o = 0; o < QGCM_HIP_TAV_NOUT; ++o)
+    if (fields[o])
+      for (int k = 0; k < map[o].nf; ++k) mask |= 1u << (map[o].f + k);
+  if (!mask) return 0;
+  if (!c->tav.mean && dalloc(&c->tav.mean, (size_t)TAV_NMEAN(nl) * g.fstride)) return 1;
+  if (!c->tav.sum && dalloc(&c->tav.sum, (size_t)TAV_NSUM(nl) * g.fstride)) return 1;
+  QgTavParams P;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.jlo = g.jlo; P.jhi = g.jhi; P.jt1 = owned_t1(g);
+  P.sum = c->tav.sum; P.mean = c->tav.mean; P.mask = mask;
+  P.rnsoc = c->tav.n == 0 ? 0.0 : 1.0 / (double)c->tav.n; // src/timavge.F:723-727
+  const dim3 grid((g.nx + TAV_NT - 1) / TAV_NT, g.jhi - g.jlo + 1);
+#define QG_TAVM(NLV) hipLaunchKernelGGL((k_tav_mean<NLV>), grid, dim3(TAV_NT), 0, c->stream, P)
+  QG_SWITCH_NL(nl, QG_TAVM, "k_tav_mean");
+#undef QG_TAVM
+  HIPCHECK(hipGetLastError());
+  const int np = g.jhi - g.jlo + 1, nt = owned_t1(g) - g.jlo + 1;
+  for (int o = 0; o < QGCM_HIP_TAV_NOUT; ++o)
+    if (fields[o] && download_owned(c, fields[o], c->tav.mean + (size_t)map[o].f * g.fstride, map[o].nx, g.jlo,
+                                    map[o].trow ? nt : np, map[o].nf))
+      return 1;
+  return 0;
+}
+
+static int launch_poavg(qgcm_hip_ctx *c);
+
 static int one_step(qgcm_hip_ctx *c, int s) {
   if (c->oml.on && launch_oml(c, false)) return 1; // src/q-gcm.F:1232; its final reduction rides in launch_tend
   const bool fused_constr = !c->g.cyc && can_fuse_dst_unpack(c) && !c->no_fused_constr; // see ocinvq_impl
@@ -2306,7 +2530,8 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   const bool avg = (s - 1) % c->avg_period == 0;
   const bool avg_box = fused_constr && c->g.nl <= 4 && tend_wtq(c);
   const bool avg_cyc = c->g.cyc && can_fuse_fft3_unpack(c) && !c->no_fused_constr; // (ocinvq_impl: launch_fft3_unpack(c, true))
-  c->avg_now = avg && (avg_box || avg_cyc) && !c->no_fused_avg;
+  // (while the po sum is on, the averaging step runs unfused: the sum must see this step's po before it is averaged)
+  c->avg_now = avg && (avg_box || avg_cyc) && !c->no_fused_avg && !c->poavg.on;
   const bool avg_fused = c->avg_now;
   int rc = launch_tend(c, fused_constr, c->oml.on);
   if (!rc) {
@@ -2315,6 +2540,7 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   }
   c->avg_now = false;
   if (rc) return 1;
+  if (c->poavg.on && launch_poavg(c)) return 1; // avg_ocn_k247 right after ocqbdy, src/q-gcm.F:1250-1252
   if (avg_fused) {
     KTimer t(c, KN_LFAVG);
     hipLaunchKernelGGL(k_lf_average_scalars, dim3(1), dim3(64), 0, c->stream, c->sc, c->g.nl, c->g.cyc ? 1 : 0);
@@ -2354,7 +2580,7 @@ static const size_t kMaxGraphs = 96;
 static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   const int phase = (s0 - 1) % c->avg_period;
   const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : 0; // mixed layer on/off and its buffer rotation
-  const long long key = ((long long)B << 32) | (omk << 24) | (c->ip << 16) | (c->iq << 8) | phase;
+  const long long key = ((long long)B << 32) | ((long long)c->poavg.on << 31) | (omk << 24) | (c->ip << 16) | (c->iq << 8) | phase;
   auto it = c->graphs.find(key);
   if (it != c->graphs.end()) {
     it->second.used = c->graph_call;
@@ -2376,10 +2602,12 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   }
   hipGraph_t graph;
   const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
+  const long pn0 = c->poavg.n;
   HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
   for (int s = s0; s < s0 + B && !rc; ++s) rc = one_step(c, s);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
+  c->poavg.n = pn0;
   c->ip = ip0; // capture does not execute: restore the rotation state
   c->iq = iq0;
   c->oml.is = is0;
@@ -2406,6 +2634,7 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
     hipGraphExec_t ge;
     if (get_graph(c, s, B, &ge)) return 1;
     if (!dry) HIPCHECK(hipGraphLaunch(ge, c->stream));
+    if (!dry && c->poavg.on) c->poavg.n += B;
     s += B;
     n -= B;
     if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
@@ -2773,12 +3002,14 @@ extern "C" int qgcm_hip_slab_stage(qgcm_hip_handle c, int stage, double *a, doub
         // the fused kernel also writes the halo messages (first / last three owned rows of po, edge row of qo)
         if (launch_dst_unpack(c, true, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr, fused_constr)) return 1;
         c->ip ^= 1;
+        if (launch_poavg(c)) return 1;
         return oml_halo_pack(c, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr);
       }
       if (can_fuse_fft3_unpack(c)) { // long rows: inverse rows + unpack + halo messages in one launch (k_fft3_unpack.h)
         if (qgcm_hip_constr(c)) return 1;
         if (launch_fft3_unpack(c, false, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr)) return 1;
         c->ip ^= 1;
+        if (launch_poavg(c)) return 1;
         return oml_halo_pack(c, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr);
       }
       if (dst_box_rides_constr(c)) { // box: the constraint solve rides in the inverse-row launch
@@ -2790,6 +3021,7 @@ extern "C" int qgcm_hip_slab_stage(qgcm_hip_handle c, int stage, double *a, doub
       // the unpack launch also writes the halo messages (first / last three owned rows of po, edge row of qo)
       if (check_ready(c, "qgcm_hip_slab_stage") || launch_unpack(c, true, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr)) return 1;
       c->ip ^= 1;
+      if (launch_poavg(c)) return 1; // the new po of the owned rows, before stage 3 averages it
       return oml_halo_pack(c, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr);
     case 3:
       if (nranks > 1 && qgcm_hip_halo_unpack(c, a, b)) return 1;
@@ -3060,19 +3292,21 @@ static int slab_join(qgcm_hip_ctx *c) {
 static int get_slab_graph(qgcm_hip_ctx *c, int s0, hipGraphExec_t *out) {
   const int phase = (s0 - 1) % 25;
   const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : 0; // mixed layer on/off and its buffer rotation
-  const int key = (omk << 20) | (c->ip << 16) | (c->iq << 8) | phase;
+  const int key = ((int)c->poavg.on << 28) | (omk << 20) | (c->ip << 16) | (c->iq << 8) | phase;
   auto it = c->slab_graphs.find(key);
   if (it != c->slab_graphs.end()) {
     *out = it->second;
     return 0;
   }
   const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
+  const long pn0 = c->poavg.n;
   hipGraph_t graph;
   HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
   for (int k = 0; k < kGraphBlock && !rc; ++k) rc = slab_step(c, s0 + k, k + 1 < kGraphBlock);
   if (!rc) rc = slab_join(c);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
+  c->poavg.n = pn0;
   if (rc && c->sc_comm) c->sc_comm->pending = c->sc_comm->outer_done = false;
   c->ip = ip0; // nothing ran: the rotation state is that of the block's first step
   c->iq = iq0;
@@ -3098,6 +3332,7 @@ extern "C" int qgcm_hip_slab_steps(qgcm_hip_handle c, int s0, int n) {
     hipGraphExec_t ge;
     if (get_slab_graph(c, s, &ge)) return 1;
     HIPCHECK(hipGraphLaunch(ge, c->stream));
+    if (c->poavg.on) c->poavg.n += kGraphBlock;
     if (c->oml.on) oml_rotate(c, kGraphBlock); // the p and q rotations are back where they started, sst has moved on
     s += kGraphBlock; // 50 steps: both rotations are back where they started
     n -= kGraphBlock;

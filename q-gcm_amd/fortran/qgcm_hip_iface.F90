@@ -31,6 +31,12 @@ module qgcm_hip_iface
     integer(c_int) :: sb_flag, nb_flag   ! sb_hflux, nb_hflux of the C struct (those names are cpp macros in reference builds)
   end type qgcm_hip_oml_params
 
+  ! struct qgcm_hip_tav_params: constants of tavocn
+  type, bind(C) :: qgcm_hip_tav_params
+    real(c_double) :: hmoc, ycexp, tsbdy, tnbdy
+    integer(c_int) :: sb_flag, nb_flag   ! sb_hflux, nb_hflux of the C struct
+  end type qgcm_hip_tav_params
+
   interface
     integer(c_int) function qgcm_hip_create(h, prm, device) bind(C, name='qgcm_hip_create')
       import :: c_ptr, c_int, qgcm_hip_params
@@ -284,6 +290,44 @@ module qgcm_hip_iface
       import :: c_ptr, c_int
       type(c_ptr), value :: h
       integer(c_int), value :: on
+    end function
+    ! time averages of the ocean (include/qgcm_hip.h): running mean of po (avg_ocn_k247 / ocnc_avgout_k247) and
+    ! tavocn / tavout; fields(16) holds c_loc of the outputs wanted (c_null_ptr = skip), in the header's order
+    integer(c_int) function qgcm_hip_poavg_enable(h, on) bind(C, name='qgcm_hip_poavg_enable')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function qgcm_hip_poavg_out(h, po_avg, nsum, reset) bind(C, name='qgcm_hip_poavg_out')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: po_avg(*)
+      integer(c_int), intent(out) :: nsum
+      integer(c_int), value :: reset
+    end function
+    integer(c_int) function qgcm_hip_set_tav_params(h, p) bind(C, name='qgcm_hip_set_tav_params')
+      import :: c_ptr, c_int, qgcm_hip_tav_params
+      type(c_ptr), value :: h
+      type(qgcm_hip_tav_params), intent(in) :: p
+    end function
+    integer(c_int) function qgcm_hip_set_tav_fields(h, fnetoc) bind(C, name='qgcm_hip_set_tav_fields')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(in) :: fnetoc(*)
+    end function
+    integer(c_int) function qgcm_hip_tavocn(h) bind(C, name='qgcm_hip_tavocn')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_tav_reset(h) bind(C, name='qgcm_hip_tav_reset')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_tav_out(h, fields, nsumoc) bind(C, name='qgcm_hip_tav_out')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      type(c_ptr), intent(in) :: fields(16)
+      integer(c_int), intent(out) :: nsumoc
     end function
   end interface
 

@@ -49,6 +49,17 @@ class MonParams(C.Structure):
     ]
 
 
+class TavParams(C.Structure):
+    """struct qgcm_hip_tav_params (include/qgcm_hip.h)."""
+    _fields_ = [
+        ("hmoc", C.c_double), ("ycexp", C.c_double), ("tsbdy", C.c_double), ("tnbdy", C.c_double),
+        ("sb_hflux", C.c_int), ("nb_hflux", C.c_int),
+    ]
+
+
+TAV_NOUT = 16  # QGCM_HIP_TAV_NOUT
+
+
 # every symbol include/qgcm_hip.h declares
 SYMBOLS = [
     "qgcm_hip_create", "qgcm_hip_destroy", "qgcm_hip_last_error", "qgcm_hip_abi_version",
@@ -71,6 +82,8 @@ SYMBOLS = [
     "qgcm_hip_monitor_part_len", "qgcm_hip_monitors_part", "qgcm_hip_monitors_combine",
     "qgcm_hip_valids_part_len", "qgcm_hip_valids_part", "qgcm_hip_valids_combine",
     "qgcm_hip_prsamp_part_len", "qgcm_hip_prsamp_part", "qgcm_hip_prsamp_combine",
+    "qgcm_hip_poavg_enable", "qgcm_hip_poavg_out", "qgcm_hip_set_tav_params", "qgcm_hip_set_tav_fields",
+    "qgcm_hip_tavocn", "qgcm_hip_tav_reset", "qgcm_hip_tav_out",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -165,6 +178,13 @@ def load_library():
     L.qgcm_hip_monitors_combine.argtypes = [vp, vp, C.c_int, dp]
     L.qgcm_hip_valids_combine.argtypes = [vp, vp, C.c_int, dp, C.POINTER(C.c_int)]
     L.qgcm_hip_prsamp_combine.argtypes = [vp, vp, C.c_int, dp]
+    L.qgcm_hip_poavg_enable.argtypes = [vp, C.c_int]
+    L.qgcm_hip_poavg_out.argtypes = [vp, dp, C.POINTER(C.c_int), C.c_int]
+    L.qgcm_hip_set_tav_params.argtypes = [vp, C.POINTER(TavParams)]
+    L.qgcm_hip_set_tav_fields.argtypes = [vp, dp]
+    L.qgcm_hip_tavocn.argtypes = [vp]
+    L.qgcm_hip_tav_reset.argtypes = [vp]
+    L.qgcm_hip_tav_out.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_int)]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

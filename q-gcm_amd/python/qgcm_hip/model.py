@@ -68,6 +68,50 @@ def prsamp_dict(out, nl):
                 qavgoc=out[3 * nl:4 * nl].copy(), sstmin=out[4 * nl], sstmax=out[4 * nl + 1])
 
 
+# outputs of qgcm_hip_tav_out in ABI order (names of MODULE timavge / tavout) and their grids: p = (nxpo, p rows),
+# t = (nxto, T rows), p3 = (nxpo, p rows, nlo), u = (nxpo, T rows), v = (nxto, p rows)
+TAV_LAYOUT = (("txocav", "p"), ("tyocav", "p"), ("wpocav", "p"), ("wtocav", "t"), ("fmocav", "t"), ("sstav", "t"),
+              ("pocav", "p3"), ("qocav", "p3"), ("uufo", "u"), ("tufo", "u"), ("utufo", "u"), ("vvfo", "v"),
+              ("tvfo", "v"), ("vtvfo", "v"), ("uptpoc", "u"), ("vptpoc", "v"))
+
+
+def tav_params(oml=None, hmoc=None, ycexp=None, tsbdy=None, tnbdy=None, sb_hflux=None, nb_hflux=None):
+    """struct qgcm_hip_tav_params: the given values, the others from `oml` (a qgcm_hip.OmlConfig)."""
+    from .config import OmlConfig
+    from .lib import TavParams
+    om = OmlConfig() if oml is None else oml
+    pick = lambda v, d: d if v is None else v
+    p = TavParams()
+    p.hmoc, p.ycexp = float(pick(hmoc, om.hmoc)), float(pick(ycexp, om.ycexp))
+    p.tsbdy, p.tnbdy = float(pick(tsbdy, om.tsbdy)), float(pick(tnbdy, om.tnbdy))
+    p.sb_hflux, p.nb_hflux = int(pick(sb_hflux, om.sb_hflux)), int(pick(nb_hflux, om.nb_hflux))
+    return p
+
+
+def read_time_means(L, h, cfg, np_rows, nt_rows, names=None):
+    """qgcm_hip_tav_out for the given names (None = all): (dict name -> array, nsumoc)."""
+    from .lib import TAV_NOUT
+    shape = dict(p=(cfg.nxpo, np_rows), t=(cfg.nxto, nt_rows), p3=(cfg.nxpo, np_rows, cfg.nlo), u=(cfg.nxpo, nt_rows),
+                 v=(cfg.nxto, np_rows))
+    want = [n for n, _ in TAV_LAYOUT] if names is None else list(names)
+    out, ptrs = {}, (C.POINTER(C.c_double) * TAV_NOUT)()
+    for i, (name, grid) in enumerate(TAV_LAYOUT):
+        if name in want:
+            out[name] = np.zeros(shape[grid], order="F")
+            ptrs[i] = _dp(out[name])
+    n = C.c_int()
+    check(L.qgcm_hip_tav_out(h, ptrs, C.byref(n)))
+    return out, n.value
+
+
+def read_po_mean(L, h, cfg, np_rows, reset):
+    """qgcm_hip_poavg_out: (po_avg / nsum (nxpo, p rows, nlo), nsum)."""
+    a = np.zeros((cfg.nxpo, np_rows, cfg.nlo), order="F")
+    n = C.c_int()
+    check(L.qgcm_hip_poavg_out(h, _dp(a), C.byref(n), int(bool(reset))))
+    return a, n.value
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -303,6 +347,42 @@ class OceanModel:
         """The ocean variables of MODULE monitor that monnc_comp / couroc compute (src/monitor_data.F:50-71), from
         the device state without pulling it: dict of scalars and per-layer / per-interface numpy arrays."""
         return unpack_monitors(self.monitor_vector(), self.cfg.nlo)
+
+    # -- time averages (avg_ocn_k247 / ocnc_avgout_k247, tavocn / tavout; DESIGN 6f) --------------------------
+    def enable_po_mean(self, on=True):
+        """Start (at zero) or stop the running sum of po: while on, every step of steps() adds its po after ocqbdy
+        and before the leapfrog averaging (avg_ocn_k247, src/q-gcm.F:1250-1252)."""
+        check(self.L.qgcm_hip_poavg_enable(self.h, int(bool(on))))
+
+    def po_mean(self, reset=False, count=False):
+        """po_avg * (1/nsum) (nxpo, nypo, nlo), as ocnc_avgout_k247 scales it; reset=True then zeroes sum and count.
+        count=True returns (mean, nsum)."""
+        a, n = read_po_mean(self.L, self.h, self.cfg, self.cfg.nypo, reset)
+        return (a, n) if count else a
+
+    def set_time_mean_params(self, oml=None, **kw):
+        """hmoc, ycexp, tsbdy, tnbdy, sb_hflux, nb_hflux of tavocn (defaults from `oml`, a qgcm_hip.OmlConfig).
+        Without this call the mixed layer's parameters are used."""
+        check(self.L.qgcm_hip_set_tav_params(self.h, C.byref(tav_params(oml, **kw))))
+
+    def set_time_mean_fields(self, fnetoc=None):
+        """fnetoc (nxto, nyto) for tavocn without the mixed layer (zero if never given)."""
+        check(self.L.qgcm_hip_set_tav_fields(self.h, _dp(_f(fnetoc))))
+
+    def tavocn(self):
+        """One tavocn contribution from the device state (src/timavge.F:425-619)."""
+        check(self.L.qgcm_hip_tavocn(self.h))
+
+    def time_means(self, names=None):
+        """tavout's means (src/timavge.F:667-880) keyed by the reference's names (TAV_LAYOUT), plus "nsumoc".  The
+        sums are not changed.  names: the subset to compute and copy (None = all)."""
+        out, n = read_time_means(self.L, self.h, self.cfg, self.cfg.nypo, self.cfg.nyto, names)
+        out["nsumoc"] = n
+        return out
+
+    def reset_time_means(self):
+        """tavini: zero the sums and the count."""
+        check(self.L.qgcm_hip_tav_reset(self.h))
 
     # -- ocean mixed layer (`call oml`, src/q-gcm.F:1232; SURVEY 8 row f1) -------
     def oml_init(self, om):

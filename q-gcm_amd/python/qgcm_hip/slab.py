@@ -359,6 +359,40 @@ class HipSlab:
         a = [cut(tauxo, sl), cut(tauyo, sl), cut(wekto, self.t_slice()), cut(sst, self.t_slice())]
         check(self.L.qgcm_hip_set_monitor_fields(self.h, *[_dp(x) for x in a]))
 
+    # time averages of the owned rows (SlabOcean.po_mean / time_means assemble the basin)
+    def owned_t_rows(self):
+        """Owned T rows: g1 - g0 + 1, one less on the rank that owns row nypo."""
+        return self.g1 - self.g0 + (0 if self.g1 == self.cfg.nypo else 1)
+
+    def enable_po_mean(self, on=True):
+        check(self.L.qgcm_hip_poavg_enable(self.h, int(bool(on))))
+
+    def po_mean(self, reset=False):
+        """(po_avg / nsum of the owned rows (nxpo, g1-g0+1, nlo), nsum)."""
+        from .model import read_po_mean
+        return read_po_mean(self.L, self.h, self.cfg, self.g1 - self.g0 + 1, reset)
+
+    def set_time_mean_params(self, oml=None, **kw):
+        from .model import tav_params
+        check(self.L.qgcm_hip_set_tav_params(self.h, C.byref(tav_params(oml, **kw))))
+
+    def set_time_mean_fields(self, fnetoc=None):
+        """GLOBAL fnetoc (nxto, nyto); the local T rows are cut out here."""
+        f = None if fnetoc is None else np.asfortranarray(np.asarray(fnetoc, dtype=np.float64)[:, self.t_slice()])
+        check(self.L.qgcm_hip_set_tav_fields(self.h, _dp(f)))
+
+    def tavocn(self):
+        check(self.L.qgcm_hip_tavocn(self.h))
+        self._done()
+
+    def time_means(self, names=None):
+        """(dict of the owned rows' means, nsumoc)."""
+        from .model import read_time_means
+        return read_time_means(self.L, self.h, self.cfg, self.g1 - self.g0 + 1, self.owned_t_rows(), names)
+
+    def reset_time_means(self):
+        check(self.L.qgcm_hip_tav_reset(self.h))
+
     def set_dtopoc(self, dtopoc):
         """GLOBAL bottom topography (nxpo, nypo) for valids, None = flat."""
         sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
@@ -620,6 +654,88 @@ class SlabOcean:
         """As OceanModel.prsamp()."""
         from .model import prsamp_dict
         return prsamp_dict(self.diagnostic("prsamp")[0], self.cfg.nlo)
+
+    # time averages (DESIGN 6f): every rank sums its owned rows; a readout assembles the basin with one all-gather
+    def _assemble(self, parts):
+        """parts[i]: dict name -> owned-row array (rows on axis 1) of local slab i.  One all-gather of the packed arrays
+        (g0, g1, then every field padded to the largest slab's rows); returns dict name -> whole-basin array."""
+        from .model import TAV_LAYOUT
+        S, cfg = self.slabs, self.cfg
+        grids = dict(TAV_LAYOUT)
+        names = sorted(parts[0])
+        rmax = max(g1 - g0 + 1 for g0, g1 in partition(cfg.nypo, self.P))
+        rmax = max([rmax] + [x.g1 - x.g0 + 1 for x in S])
+        tail = lambda a: a.shape[2] if a.ndim == 3 else 1
+        sizes = [(n, parts[0][n].shape[0], tail(parts[0][n])) for n in names]
+        ln = 2 + sum(nx * rmax * k for _, nx, k in sizes)
+        send, gath = [], []
+        for x, d in zip(S, parts):
+            v = np.zeros(ln)
+            v[0], v[1] = x.g0, x.g1
+            o = 2
+            for n, nx, k in sizes:
+                buf = np.zeros((nx, rmax, k), order="F")
+                a = d[n].reshape(nx, -1, k, order="F")
+                buf[:, :a.shape[1], :] = a
+                v[o:o + nx * rmax * k] = buf.ravel(order="F")
+                o += nx * rmax * k
+            t = x.new_buffer(ln)
+            t.copy_(x.torch.from_numpy(v))
+            send.append(t)
+            gath.append(x.new_buffer(ln * self.P))
+        self._settle()
+        self._comm(self.comm.all_gather, gath, send)
+        g = gath[0].cpu().numpy().reshape(self.P, ln)
+        out = {}
+        o = 2
+        for n, nx, k in sizes:
+            tgrid = grids.get(n) in ("t", "u")  # T-row fields: one row fewer on the rank that owns row nypo
+            full = np.zeros((nx, cfg.nyto if tgrid else cfg.nypo, k), order="F")
+            for r in range(self.P):
+                g0, g1 = int(g[r, 0]), int(g[r, 1])
+                rows = g1 - g0 + 1 - (1 if tgrid and g1 == cfg.nypo else 0)
+                blk = g[r, o:o + nx * rmax * k].reshape(nx, rmax, k, order="F")
+                full[:, g0 - 1:g0 - 1 + rows, :] = blk[:, :rows, :]
+            out[n] = full if parts[0][n].ndim == 3 else full[:, :, 0]
+            o += nx * rmax * k
+        return out
+
+    def enable_po_mean(self, on=True):
+        for x in self.slabs:
+            x.enable_po_mean(on)
+
+    def po_mean(self, reset=False, count=False):
+        """As OceanModel.po_mean: the whole basin's running mean of po, assembled from the owned rows (collective)."""
+        self._join()
+        res = [x.po_mean(reset) for x in self.slabs]
+        a = self._assemble([{"po": m} for m, _ in res])["po"]
+        return (a, res[0][1]) if count else a
+
+    def set_time_mean_params(self, oml=None, **kw):
+        for x in self.slabs:
+            x.set_time_mean_params(oml, **kw)
+
+    def set_time_mean_fields(self, fnetoc=None):
+        for x in self.slabs:
+            x.set_time_mean_fields(fnetoc)
+
+    def tavocn(self):
+        """One tavocn contribution on every slab (no exchange: the halo rows the fluxes read are current)."""
+        self._join()
+        for x in self.slabs:
+            x.tavocn()
+
+    def time_means(self, names=None):
+        """As OceanModel.time_means: the whole basin's means, assembled from the owned rows (collective)."""
+        self._join()
+        res = [x.time_means(names) for x in self.slabs]
+        out = self._assemble([d for d, _ in res])
+        out["nsumoc"] = res[0][1]
+        return out
+
+    def reset_time_means(self):
+        for x in self.slabs:
+            x.reset_time_means()
 
     def homsol(self):
         """homsol of the box ocean (src/conhoms.F:549-641) ON the slabs: the modal Helmholtz problems of a step are

@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Golden values of the ocean's time averages (tavini / tavocn / tavout and avg_ocn_k247, src/timavge.F) from the TRUE
+reference.
+
+Compiles the reference's timavge.F unmodified, with the modules it USEs and a small driver of this script's own, in a
+temporary directory (one build per case: the dimensions and the boundary options are compile-time).  timavge.F is
+preprocessed with -DPRIVATE=PUBLIC so that the driver can read the ocean sums of MODULE timavge (besides the access
+attributes the word occurs only in OpenMP directives, which are comments in this build without -fopenmp).  The driver fills MODULE ocstate / intrfac with the stepped states of the
+tiny fixtures and synthetic forcing, calls tavini, tavocn on three states, avg_ocn_k247 on four, then tavout, and
+writes the scaled MODULE timavge arrays.  tavout's eddy fluxes uptpoc / vptpoc are locals of tavout (written only to
+netCDF): they are derived here from the reference's scaled arrays with tavout's own expression.  The mean of po is
+ocnc_avgout_k247's scaling (netCDF-only in the reference), restated in the driver: rnsum = 1/nsum, rnsum * po_avg.
+All reference sources, objects and .mod files stay in the temporary directory, which is deleted.
+
+  python tests/golden/make_golden_tavg.py     # writes tests/golden/tav_{box_tiny,box_tiny_sb,cyc_tiny}.npz
+"""
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.normpath(os.path.join(HERE, "..", ".."))
+sys.path.insert(0, os.path.join(ROOT, "q-gcm_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+REF = os.environ.get("QGCM_REFERENCE", "/root/reference")
+FC = os.environ.get("FC", "/opt/rocm/bin/amdflang")
+MODS = ["atconst_data.F", "occonst_data.F", "ocstate_data.F", "intrfac_data.F", "timinfo_data.F", "nc_subs.F"]
+TAV_STATES = ("steps25", "steps26", "steps60")          # tavocn inputs (after the step's averaging)
+AVG_STATES = ("ocqbdy", "steps2", "steps25", "steps60")  # avg_ocn_k247 inputs
+SUMS = ("txocav", "tyocav", "wpocav", "wtocav", "fmocav", "sstav", "pocav", "qocav", "uufo", "tufo", "utufo",
+        "vvfo", "tvfo", "vtvfo")
+
+DRIVER = r"""
+program tav_driver
+  use parameters, only : nxpo, nypo, nxto, nyto, nlo, fnot
+  use occonst, only : dxo, ycexp, rdxof0
+  use ocstate, only : po, qo, wekpo, wekto, po_avg
+  use intrfac, only : sst, tauxo, tauyo, fnetoc, hmoc, tsbdy, tnbdy
+  use timinfo, only : nsum_ocavg
+  use timavge
+  implicit none
+  integer :: ntav, navg, s
+  double precision :: sc(5), rnsum
+  open (10, file='in.bin', access='stream', form='unformatted', status='old')
+  read (10) sc
+  dxo = sc(1); ycexp = sc(2); hmoc = sc(3); tsbdy = sc(4); tnbdy = sc(5)
+  rdxof0 = 1.0d0/(dxo*fnot)
+  read (10) ntav, navg
+  call tavini
+  do s = 1, ntav
+    read (10) po, qo, wekpo, tauxo, tauyo, wekto, sst, fnetoc
+    call tavocn
+  end do
+  po_avg = 0.0d0
+  nsum_ocavg = 0
+  do s = 1, navg
+    read (10) po
+    call avg_ocn_k247
+  end do
+  close (10)
+  call tavout
+  rnsum = 1.0d0 / dble( nsum_ocavg )
+  open (11, file='out.bin', access='stream', form='unformatted', status='replace')
+  write (11) dble(nsumoc), dble(nsum_ocavg)
+  write (11) txocav, tyocav, wpocav, wtocav, fmocav, sstav, pocav, qocav, uufo, tufo, utufo, vvfo, tvfo, vtvfo
+  write (11) po_avg
+  po_avg = rnsum * po_avg
+  write (11) po_avg
+  close (11)
+end program tav_driver
+"""
+
+
+def build(wrk, dims, opts):
+    nxta, nyta, nxaooc, nyaooc, ndxr, nlo, fnot, beta = dims
+    src = os.path.join(REF, "src")
+    with open(os.path.join(REF, "examples", "double_gyre_ocean_only", "parameters_data.F.dg_oo")) as f:
+        lines = f.read().split("\n")
+    for i, ln in enumerate(lines):
+        if ln.startswith("      PARAMETER ( nxta = "):
+            lines[i] = "      PARAMETER ( nxta = %s, nyta = %s, nla = 3 )" % (nxta, nyta)
+        elif ln.startswith("      PARAMETER ( nxaooc = "):
+            lines[i] = "      PARAMETER ( nxaooc = %s, nyaooc = %s, ndxr = %s, nlo = %s )" % (nxaooc, nyaooc, ndxr, nlo)
+        elif ln.startswith("      PARAMETER ( fnot = "):
+            lines[i] = "      PARAMETER ( fnot = %s, beta = %s )" % (fnot, beta)
+    with open(os.path.join(wrk, "parameters_data.F"), "w") as f:
+        f.write("\n".join(lines))
+    with open(os.path.join(wrk, "tav_driver.F90"), "w") as f:
+        f.write(DRIVER)
+    q = ["-Docean_only", "-Docnc_avg_k247"] + ["-D" + o for o in opts]
+    fc = [FC, "-cpp", "-ffixed-line-length-132", "-O2"] + q
+    objs = []
+    for f in ["parameters_data.F"] + [os.path.join(src, m) for m in MODS]:
+        subprocess.check_call(fc + ["-c", "-I" + src, f], cwd=wrk)
+        objs.append(os.path.splitext(os.path.basename(f))[0] + ".o")
+    subprocess.check_call(fc + ["-DPRIVATE=PUBLIC", "-c", "-I" + src, os.path.join(src, "timavge.F")], cwd=wrk)
+    objs.append("timavge.o")
+    subprocess.check_call([FC, "-cpp", "-O2", "-c", "tav_driver.F90"], cwd=wrk)
+    subprocess.check_call([FC, "-o", "tav_driver", "tav_driver.o"] + objs, cwd=wrk)
+
+
+def inputs(cfg, g, om):
+    """Per tavocn call: the fixture's state and forcing of its own (seeded), all stored in the golden file."""
+    from qgcm_hip import synth
+    calls = []
+    for n, st in enumerate(TAV_STATES):
+        sst, _, fnet, tx, ty = synth.mixed_layer_fields(cfg, om, seed=5 + n)
+        wekto, wekpo = synth.wekpo_from_tau(cfg, tx, ty)
+        calls.append(dict(po=g[st + "_po"], qo=g[st + "_qo"], wekpo=wekpo, tauxo=tx, tauyo=ty, wekto=wekto, sst=sst,
+                          fnetoc=fnet))
+    return calls
+
+
+def run(wrk, cfg, om, calls, avg):
+    with open(os.path.join(wrk, "in.bin"), "wb") as fh:
+        fh.write(np.array([cfg.dxo, om.ycexp, om.hmoc, om.tsbdy, om.tnbdy], dtype=np.float64).tobytes())
+        fh.write(np.array([len(calls), len(avg)], dtype=np.int32).tobytes())
+        for f in calls:
+            for k in ("po", "qo", "wekpo", "tauxo", "tauyo", "wekto", "sst", "fnetoc"):
+                fh.write(np.asfortranarray(f[k], dtype=np.float64).tobytes(order="F"))
+        for p in avg:
+            fh.write(np.asfortranarray(p, dtype=np.float64).tobytes(order="F"))
+    subprocess.check_call([os.path.join(wrk, "tav_driver")], cwd=wrk)
+    out = np.fromfile(os.path.join(wrk, "out.bin"), dtype=np.float64)
+    nxp, nyp, nl = cfg.nxpo, cfg.nypo, cfg.nlo
+    nxt, nyt = nxp - 1, nyp - 1
+    shapes = dict(txocav=(nxp, nyp), tyocav=(nxp, nyp), wpocav=(nxp, nyp), wtocav=(nxt, nyt), fmocav=(nxt, nyt),
+                  sstav=(nxt, nyt), pocav=(nxp, nyp, nl), qocav=(nxp, nyp, nl), uufo=(nxp, nyt), tufo=(nxp, nyt),
+                  utufo=(nxp, nyt), vvfo=(nxt, nyp), tvfo=(nxt, nyp), vtvfo=(nxt, nyp), po_sum=(nxp, nyp, nl),
+                  po_mean=(nxp, nyp, nl))
+    res = dict(nsumoc=int(out[0]), nsum_ocavg=int(out[1]))
+    o = 2
+    for k in SUMS + ("po_sum", "po_mean"):
+        n = int(np.prod(shapes[k]))
+        res[k] = out[o:o + n].reshape(shapes[k], order="F")
+        o += n
+    assert o == len(out)
+    res["uptpoc"] = res["utufo"] - res["uufo"] * res["tufo"]   # tavout, src/timavge.F:859
+    res["vptpoc"] = res["vtvfo"] - res["vvfo"] * res["tvfo"]   # tavout, src/timavge.F:869
+    return res
+
+
+# (golden file, fixture, reference configuration, cpp options)
+CASES = [("box_tiny", "box_tiny", "box_tiny", []), ("box_tiny_sb", "box_tiny", "box_tiny", ["sb_hflux"]),
+         ("cyc_tiny", "cyc_tiny", "cyc_tiny", ["cyclic_ocean", "nb_hflux"])]
+
+if __name__ == "__main__":
+    import ref_binding
+    from qgcm_hip import oml_preset, preset
+    for out_name, fixture, refcfg, opts in CASES:
+        cfg = preset(fixture)
+        om = oml_preset(cfg, sb_hflux="sb_hflux" in opts, nb_hflux="nb_hflux" in opts)
+        g = np.load(os.path.join(HERE, fixture + ".npz"))
+        calls = inputs(cfg, g, om)
+        avg = [g[s + "_po"] for s in AVG_STATES]
+        wrk = tempfile.mkdtemp(prefix="tavg_")
+        try:
+            build(wrk, ref_binding.CONFIGS[refcfg][:8], opts)
+            res = run(wrk, cfg, om, calls, avg)
+        finally:
+            shutil.rmtree(wrk, ignore_errors=True)
+        out = {"c_" + k: np.float64(v) for k, v in dict(dxo=cfg.dxo, fnot=cfg.fnot, ycexp=om.ycexp, hmoc=om.hmoc,
+                                                        tsbdy=om.tsbdy, tnbdy=om.tnbdy).items()}
+        out.update(c_cyclic=np.int64(cfg.cyclic), c_sb_hflux=np.int64("sb_hflux" in opts),
+                   c_nb_hflux=np.int64("nb_hflux" in opts))
+        for n, f in enumerate(calls):
+            out.update({"in%d_%s" % (n, k): v for k, v in f.items()})
+        out["avg_po"] = np.stack(avg)
+        out.update({"out_" + k: np.asarray(v) for k, v in res.items()})
+        np.savez_compressed(os.path.join(HERE, "tav_%s.npz" % out_name), **out)
+        sys.stderr.write("wrote tav_%s.npz (nsumoc %d, nsum_ocavg %d)\n" % (out_name, res["nsumoc"], res["nsum_ocavg"]))
