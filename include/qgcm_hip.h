@@ -467,6 +467,43 @@ int qgcm_hip_tavocn(qgcm_hip_handle h);
 int qgcm_hip_tav_reset(qgcm_hip_handle h);
 int qgcm_hip_tav_out(qgcm_hip_handle h, double *const *fields, int *nsumoc);
 
+/* ---- periodic ocean dumps ------------------------------------------------------------------------------
+ * The reference's qocdiag_out (src/qocdiag.F:303-687) and ocnc_out (src/nc_subs.F:837-1072), called at every
+ * mod(ntdone,noutoc) == 0, at the subsampled points (1+(i-1)*nsko, 1+(j-1)*nsko); a subsample of n points has
+ * min(mod(n,nsko),1) + (n-mod(n,nsko))/nsko of them (ipwk, jpwk on the p grid, itwk, jtwk on the T grid).
+ * qgcm_hip_qocdiag_len(h, nsko): the doubles qgcm_hip_qocdiag writes (-1 on error).
+ * qgcm_hip_qocdiag(h, nsko, out): the vorticity budget from the state on the device - po, pom, qo, qom, the forcing's
+ *   wekpo and the entoc on the device - as out[term][k][jp][ip] (ip fastest; terms dqdt, qotjac, qt2dif, qt4dif,
+ *   qotent; per layer exactly what the reference hands nf_put_vara_double).  qt2dif is always produced (zero when every
+ *   ah2oc is 0; the reference then skips writing it).  Equals the reference's dump when called between qgcm_hip_oml
+ *   and qgcm_hip_qgostep, or at any time with the mixed layer off.  Synchronous.
+ * qgcm_hip_qocdiag_schedule(h, nsko, every, capacity): while set, qgcm_hip_steps records the budget of every step s
+ *   with (s-1) % every == 0 after the step's oml and before its tendency (the reference's mod(ntdone,noutoc) == 0 with
+ *   ntdone = s-1, every = noutoc/nstr) into a device ring of `capacity` snapshots of qgcm_hip_qocdiag_len doubles.  A
+ *   qgcm_hip_steps call that would record more snapshots than the ring has free fails before it launches anything.
+ *   every = 0 removes the schedule and frees the ring.  Whole-domain handles only.  Other steps issue the launches of a
+ *   run without a schedule, and the state is bitwise the same.
+ * qgcm_hip_qocdiag_read(h, out, steps_out, max, nread): the unread snapshots, oldest first, at most max of them, into
+ *   out (consecutive snapshots) and their step numbers into steps_out (may be NULL); frees them; *nread = how many.
+ *   max <= 0: *nread = the number unread, nothing is copied.  Synchronous.
+ * qgcm_hip_ocnc_sample_len(h, nsko, outfloc) / qgcm_hip_ocnc_sample(h, nsko, outfloc, out): ocnc_out's fields, the
+ *   selected ones concatenated in its order: sst (itwk, jtwk) | po (ipwk, jpwk, nlo) | qo (ipwk, jpwk, nlo) |
+ *   wekto (itwk, jtwk) | h = (po(k+1)-po(k))/gpoc(k) (ipwk, jpwk, nlo-1) | tauxo, tauyo (ipwk, jpwk each).  outfloc is the
+ *   reference's 7-flag vector (1 = write; outfloc(6) selects tauxo and tauyo, outfloc(7) is not read).  sst, wekto,
+ *   tauxo and tauyo come from the mixed layer when it is on, else from qgcm_hip_set_monitor_fields (the call fails,
+ *   naming the field, if a requested one was never given).  Synchronous.
+ * qgcm_hip_subsample_rows(h, nsko, mp0, mp1, mt0, mt1): on a y-slab handle the calls above compute the subsample rows
+ *   [mp0, mp1) of the p grid and [mt0, mt1) of the T grid (0-based: global row 1 + m*nsko) that the rank owns (T rows
+ *   as the slab monitors own them); a whole-domain handle gets [0, jpwk) and [0, jtwk).  NULL = not wanted.
+ * Bitwise the reference's arithmetic (-ffp-contract=off); every boundary rule uses global rows. */
+long qgcm_hip_qocdiag_len(qgcm_hip_handle h, int nsko);
+int qgcm_hip_qocdiag(qgcm_hip_handle h, int nsko, double *out);
+int qgcm_hip_qocdiag_schedule(qgcm_hip_handle h, int nsko, int every, int capacity);
+int qgcm_hip_qocdiag_read(qgcm_hip_handle h, double *out, int *steps_out, int max, int *nread);
+long qgcm_hip_ocnc_sample_len(qgcm_hip_handle h, int nsko, const int *outfloc);
+int qgcm_hip_ocnc_sample(qgcm_hip_handle h, int nsko, const int *outfloc, double *out);
+int qgcm_hip_subsample_rows(qgcm_hip_handle h, int nsko, int *mp0, int *mp1, int *mt0, int *mt1);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

@@ -36,6 +36,7 @@
 #include "k_valids.h"
 #include "k_monitors.h"
 #include "k_tavg.h"
+#include "k_qocdiag.h"
 #include "k_setup.h"
 #include "slab_comm.h"
 
@@ -183,6 +184,16 @@ struct qgcm_hip_ctx {
     double *sum = nullptr, *mean = nullptr, *fnet = nullptr;
     long n = 0;
   } tav;
+  // periodic ocean dumps (qgcm_hip_qocdiag / _ocnc_sample, k_qocdiag.h): device result buffer (grown on demand); the
+  // schedule of qgcm_hip_qocdiag_schedule: a ring of `cap` snapshots of `len` doubles, oldest at `head`
+  struct {
+    double *buf = nullptr;
+    size_t nbuf = 0;
+    int nsko = 0, every = 0, cap = 0, head = 0, count = 0;
+    size_t len = 0;
+    double *ring = nullptr;
+    std::vector<int> steps; // step number of each ring slot
+  } qd;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
   std::map<int, hipGraphExec_t> slab_graphs;
@@ -373,7 +384,7 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : monp)
     if (p) hipFree(p);
   if (c->mon.hout) hipHostFree(c->mon.hout);
-  double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet};
+  double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet, c->qd.buf, c->qd.ring};
   for (double *p : tavp)
     if (p) hipFree(p);
   double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
@@ -2517,10 +2528,286 @@ extern "C" int qgcm_hip_tav_out(qgcm_hip_handle c, double *const *fields, int *n
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// periodic ocean dumps (k_qocdiag.h): qocdiag_out's vorticity budget and ocnc_out's subsample.  A y-slab
+// handle computes the subsample rows it owns.
+// ---------------------------------------------------------------------------
+// points of a subsample of n points: the reference's min(mod(n,nsko),1) + (n-mod(n,nsko))/nsko (src/qocdiag.F:360-363)
+static int qd_count(int n, int nsko) {
+  const int m = n % nsko;
+  return std::min(m, 1) + (n - m) / nsko;
+}
+
+// subsample rows [m0, m1) (0-based: global row 1 + m*nsko) among the global rows g0..g1
+static void qd_rows(int g0, int g1, int nsko, int *m0, int *m1) {
+  *m0 = (g0 - 1 + nsko - 1) / nsko;
+  *m1 = std::max(*m0, (g1 - 1) / nsko + 1);
+}
+
+static int qd_ready(qgcm_hip_ctx *c, int nsko, const char *who) {
+  if (check_ready(c, who)) return 1;
+  if (c->g.atm) QG_FAIL("%s: the handle is an atmosphere (only the ocean's dumps are implemented)", who);
+  if (nsko < 1) QG_FAIL("%s: nsko = %d (need >= 1)", who, nsko);
+  return 0;
+}
+
+static size_t qd_len(const qgcm_hip_ctx *c, int nsko) {
+  const QgGeom &g = c->g;
+  int m0, m1;
+  qd_rows(g.jlo + g.joff, g.jhi + g.joff, nsko, &m0, &m1);
+  return (size_t)QD_NTERM * g.nl * (m1 - m0) * qd_count(g.nx, nsko);
+}
+
+static int qd_grow(qgcm_hip_ctx *c, size_t n) {
+  auto &q = c->qd;
+  if (q.nbuf >= n) return 0;
+  if (q.buf) {
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    HIPCHECK(hipFree(q.buf));
+    q.buf = nullptr;
+    q.nbuf = 0;
+  }
+  if (dalloc(&q.buf, n)) return 1;
+  q.nbuf = n;
+  return 0;
+}
+
+// the budget of the state on the device into out (device, qd_len doubles); asynchronous
+static int launch_qocdiag(qgcm_hip_ctx *c, int nsko, double *out) {
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  QgQocdiagParams P;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.pom = c->p[c->ip ^ 1]; P.po = c->p[c->ip]; P.qo = c->q[c->iq]; P.qom = c->q[c->iq ^ 1];
+  P.wekpo = c->wekpo; P.entoc = c->entoc; P.out = out;
+  int m0, m1;
+  qd_rows(g.jlo + g.joff, g.jhi + g.joff, nsko, &m0, &m1);
+  if (m1 == m0) return 0; // no subsample row on this slab
+  P.nsko = nsko; P.ipwk = qd_count(g.nx, nsko); P.jpn = m1 - m0; P.m0 = m0;
+  P.jlo = g.jlo; P.jhi = g.jhi;
+  // scalar prologue, src/qocdiag.F:369-380 (dxom2 = 1/dxo**2 of occonst, rdto = 1/dto with dto = tdto/2 exactly)
+  P.adfaco = 1.0 / (12.0 * pr.dxo * pr.dyo * pr.fnot);
+  P.dxom2 = 1.0 / (pr.dxo * pr.dxo);
+  P.bcfaco = pr.bccooc * P.dxom2 / (0.5 * pr.bccooc + 1.0);
+  P.fohfac[0] = pr.fnot / pr.hoc[0];
+  P.fohfac[1] = pr.fnot / pr.hoc[1];
+  P.bdrfac = 0.5 * (pr.fnot >= 0.0 ? 1.0 : -1.0) * pr.delek / pr.hoc[g.nl - 1];
+  P.rdto = 1.0 / (0.5 * pr.tdto);
+  for (int k = 0; k < g.nl; ++k) {
+    P.ah2fac[k] = pr.ah2oc[k] / pr.fnot;
+    P.ah4fac[k] = pr.ah4oc[k] / pr.fnot;
+  }
+  P.ntx = (g.nx + QD_TX - 1) / QD_TX;
+  const int nty = (g.jhi - g.jlo + 1 + QD_TY - 1) / QD_TY;
+  const dim3 grid(P.ntx * nty, 1, g.nl);
+  if (g.cyc) hipLaunchKernelGGL(k_qocdiag<true>, grid, dim3(QD_NT), 0, c->stream, P);
+  else hipLaunchKernelGGL(k_qocdiag<false>, grid, dim3(QD_NT), 0, c->stream, P);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_subsample_rows(qgcm_hip_handle c, int nsko, int *mp0, int *mp1, int *mt0, int *mt1) {
+  if (qd_ready(c, nsko, "qgcm_hip_subsample_rows")) return 1;
+  const QgGeom &g = c->g;
+  int a, b;
+  qd_rows(g.jlo + g.joff, g.jhi + g.joff, nsko, &a, &b);
+  if (mp0) *mp0 = a;
+  if (mp1) *mp1 = b;
+  qd_rows(g.jlo + g.joff, owned_t1(g) + g.joff, nsko, &a, &b);
+  if (mt0) *mt0 = a;
+  if (mt1) *mt1 = b;
+  return 0;
+}
+
+extern "C" long qgcm_hip_qocdiag_len(qgcm_hip_handle c, int nsko) {
+  if (qd_ready(c, nsko, "qgcm_hip_qocdiag_len")) return -1;
+  return (long)qd_len(c, nsko);
+}
+
+extern "C" int qgcm_hip_qocdiag(qgcm_hip_handle c, int nsko, double *out) {
+  if (qd_ready(c, nsko, "qgcm_hip_qocdiag")) return 1;
+  if (!out) QG_FAIL("qgcm_hip_qocdiag: null argument");
+  const size_t n = qd_len(c, nsko);
+  if (n == 0) return 0;
+  if (qd_grow(c, n) || launch_qocdiag(c, nsko, c->qd.buf)) return 1;
+  HIPCHECK(hipMemcpyAsync(out, c->qd.buf, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// inside qgcm_hip_steps: is step s a dump step of the schedule, and how many dumps fall on steps s0 .. s0+n-1
+static bool qd_due(const qgcm_hip_ctx *c, int s) { return c->qd.every > 0 && (s - 1) % c->qd.every == 0; }
+static long qd_dumps(const qgcm_hip_ctx *c, int s0, int n) {
+  const int e = c->qd.every;
+  if (e <= 0 || n <= 0) return 0;
+  auto upto = [e](long x) { return x < 0 ? 0L : x / e + 1; }; // multiples of e in 0..x
+  return upto((long)s0 + n - 2) - upto((long)s0 - 2);
+}
+// steps from s before the next dump step (n if none comes within n)
+static int qd_run(const qgcm_hip_ctx *c, int s, int n) {
+  if (c->qd.every <= 0) return n;
+  const int r = (s - 1) % c->qd.every;
+  return std::min(n, r == 0 ? 0 : c->qd.every - r);
+}
+
+// one_step of a dump step: the budget after the step's oml, before its tendency, into the next ring slot
+static int qd_record(qgcm_hip_ctx *c, int s) {
+  auto &q = c->qd;
+  if (q.count >= q.cap) QG_FAIL("qgcm_hip_steps: the dump ring is full at step %d", s); // (steps_impl checks first)
+  const int slot = (q.head + q.count) % q.cap;
+  if (launch_qocdiag(c, q.nsko, q.ring + (size_t)slot * q.len)) return 1;
+  q.steps[slot] = s;
+  q.count++;
+  return 0;
+}
+
+extern "C" int qgcm_hip_qocdiag_schedule(qgcm_hip_handle c, int nsko, int every, int capacity) {
+  if (check_ready(c, "qgcm_hip_qocdiag_schedule")) return 1;
+  auto &q = c->qd;
+  if (every == 0) {
+    if (q.ring) {
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      HIPCHECK(hipFree(q.ring));
+    }
+    q.ring = nullptr;
+    q.every = q.cap = q.head = q.count = q.nsko = 0;
+    q.len = 0;
+    q.steps.clear();
+    return 0;
+  }
+  if (qd_ready(c, nsko, "qgcm_hip_qocdiag_schedule")) return 1;
+  if (!c->whole) QG_FAIL("qgcm_hip_qocdiag_schedule: this handle is a y-slab; the scheduled dump is whole-domain only (call qgcm_hip_qocdiag between slab steps)");
+  if (every < 0 || capacity < 1) QG_FAIL("qgcm_hip_qocdiag_schedule: need every >= 0 and capacity >= 1");
+  if (qgcm_hip_qocdiag_schedule(c, 0, 0, 0)) return 1;
+  const size_t len = qd_len(c, nsko);
+  if (dalloc(&q.ring, len * (size_t)capacity)) return 1;
+  q.nsko = nsko; q.every = every; q.cap = capacity; q.len = len;
+  q.steps.assign(capacity, 0);
+  return 0;
+}
+
+extern "C" int qgcm_hip_qocdiag_read(qgcm_hip_handle c, double *out, int *steps_out, int max, int *nread) {
+  if (check_ready(c, "qgcm_hip_qocdiag_read")) return 1;
+  if (!nread) QG_FAIL("qgcm_hip_qocdiag_read: null argument");
+  auto &q = c->qd;
+  if (max <= 0) { // a query: how many snapshots are unread
+    *nread = q.count;
+    return 0;
+  }
+  if (!out) QG_FAIL("qgcm_hip_qocdiag_read: null argument");
+  const int n = std::min(max, q.count);
+  for (int r = 0; r < n; ++r) {
+    const int slot = (q.head + r) % q.cap;
+    HIPCHECK(hipMemcpyAsync(out + (size_t)r * q.len, q.ring + (size_t)slot * q.len, q.len * sizeof(double),
+                            hipMemcpyDeviceToHost, c->stream));
+    if (steps_out) steps_out[r] = q.steps[slot];
+  }
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  q.head = q.cap ? (q.head + n) % q.cap : 0;
+  q.count -= n;
+  *nread = n;
+  return 0;
+}
+
+// ocnc_out's fields (flags outfloc(1..6); outfloc(7) is not read, src/nc_subs.F:1067): the source arrays and sizes
+struct QdField { bool tgrid; int nplanes; };
+static int ocnc_fields(qgcm_hip_ctx *c, const int *outfloc, QdField f[7]) {
+  const int nl = c->g.nl;
+  const QdField all[7] = {{true, 1}, {false, nl}, {false, nl}, {true, 1}, {false, nl - 1}, {false, 1}, {false, 1}};
+  for (int n = 0; n < 7; ++n) {
+    f[n] = all[n];
+    const int flag = outfloc[n < 6 ? n : 5]; // tauxo and tauyo share outfloc(6)
+    if (flag != 1) f[n].nplanes = 0;
+  }
+  return 0;
+}
+
+static size_t ocnc_len(qgcm_hip_ctx *c, int nsko, const int *outfloc) {
+  const QgGeom &g = c->g;
+  QdField f[7];
+  ocnc_fields(c, outfloc, f);
+  int p0, p1, t0, t1;
+  qd_rows(g.jlo + g.joff, g.jhi + g.joff, nsko, &p0, &p1);
+  qd_rows(g.jlo + g.joff, owned_t1(g) + g.joff, nsko, &t0, &t1);
+  const size_t np = (size_t)qd_count(g.nx, nsko) * (p1 - p0), nt = (size_t)qd_count(g.nxt, nsko) * (t1 - t0);
+  size_t n = 0;
+  for (int k = 0; k < 7; ++k) n += (size_t)f[k].nplanes * (f[k].tgrid ? nt : np);
+  return n;
+}
+
+extern "C" long qgcm_hip_ocnc_sample_len(qgcm_hip_handle c, int nsko, const int *outfloc) {
+  if (qd_ready(c, nsko, "qgcm_hip_ocnc_sample_len")) return -1;
+  if (!outfloc) { snprintf(g_err, sizeof(g_err), "qgcm_hip_ocnc_sample_len: null argument"); return -1; }
+  return (long)ocnc_len(c, nsko, outfloc);
+}
+
+extern "C" int qgcm_hip_ocnc_sample(qgcm_hip_handle c, int nsko, const int *outfloc, double *out) {
+  if (qd_ready(c, nsko, "qgcm_hip_ocnc_sample")) return 1;
+  if (!outfloc || !out) QG_FAIL("qgcm_hip_ocnc_sample: null argument");
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  QdField f[7];
+  ocnc_fields(c, outfloc, f);
+  // sst, wekto, tauxo, tauyo: the mixed layer's when it is on, else the monitor fields (qgcm_hip_set_monitor_fields)
+  const double *sst, *wekto, *taux, *tauy;
+  int ldt;
+  if (c->oml.on) {
+    sst = c->oml.sst[c->oml.is]; wekto = c->oml.wekto; taux = c->oml.taux; tauy = c->oml.tauy; ldt = c->oml.ldt;
+  } else {
+    const auto &m = c->mon;
+    sst = m.sst; wekto = m.wekto; taux = m.taux; tauy = m.tauy; ldt = m.ldt;
+    const char *miss = (f[0].nplanes && !sst) ? "sst" : (f[3].nplanes && !wekto) ? "wekto"
+                       : (f[5].nplanes && !taux) ? "tauxo" : (f[6].nplanes && !tauy) ? "tauyo" : nullptr;
+    if (miss) QG_FAIL("qgcm_hip_ocnc_sample: %s was never given (qgcm_hip_set_monitor_fields) and the mixed layer is off", miss);
+  }
+  const size_t n = ocnc_len(c, nsko, outfloc);
+  if (n == 0) return 0;
+  if (qd_grow(c, n)) return 1;
+  int p0, p1, t0, t1;
+  qd_rows(g.jlo + g.joff, g.jhi + g.joff, nsko, &p0, &p1);
+  qd_rows(g.jlo + g.joff, owned_t1(g) + g.joff, nsko, &t0, &t1);
+  const double *po = c->p[c->ip], *qo = c->q[c->iq];
+  size_t off = 0;
+  for (int k = 0; k < 7; ++k) {
+    if (!f[k].nplanes) continue;
+    QgSampleParams S;
+    memset(&S, 0, sizeof(S));
+    S.nsko = nsko;
+    S.ni = qd_count(f[k].tgrid ? g.nxt : g.nx, nsko);
+    S.nj = f[k].tgrid ? t1 - t0 : p1 - p0;
+    S.ld = f[k].tgrid ? ldt : g.ldx;
+    S.lj0 = 1 + (f[k].tgrid ? t0 : p0) * nsko - g.joff; // T row j lives in local row j of its array
+    S.out = c->qd.buf + off;
+    for (int z = 0; z < f[k].nplanes; ++z) {
+      switch (k) {
+        case 0: S.src[z] = sst; break;
+        case 1: S.src[z] = po + z * g.fstride; break;
+        case 2: S.src[z] = qo + z * g.fstride; break;
+        case 3: S.src[z] = wekto; break;
+        case 4: // h = rgpoc*(po(k+1) - po(k)), rgpoc = 1/gpoc(k) (src/nc_subs.F:1014-1023)
+          S.src[z] = po + z * g.fstride; S.src2[z] = po + (z + 1) * g.fstride; S.rg[z] = 1.0 / pr.gpoc[z];
+          break;
+        case 5: S.src[z] = taux; break;
+        default: S.src[z] = tauy; break;
+      }
+    }
+    if (S.nj > 0) {
+      hipLaunchKernelGGL(k_ocnc_sample, dim3((S.ni + 255) / 256, S.nj, f[k].nplanes), dim3(256), 0, c->stream, S);
+      HIPCHECK(hipGetLastError());
+    }
+    off += (size_t)f[k].nplanes * S.ni * S.nj;
+  }
+  HIPCHECK(hipMemcpyAsync(out, c->qd.buf, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 static int launch_poavg(qgcm_hip_ctx *c);
 
 static int one_step(qgcm_hip_ctx *c, int s) {
   if (c->oml.on && launch_oml(c, false)) return 1; // src/q-gcm.F:1232; its final reduction rides in launch_tend
+  if (qd_due(c, s) && qd_record(c, s)) return 1;    // qocdiag_out after oml, before qgostep (src/q-gcm.F:1234-1239)
   const bool fused_constr = !c->g.cyc && can_fuse_dst_unpack(c) && !c->no_fused_constr; // see ocinvq_impl
   if (check_ready(c, "qgcm_hip_steps")) return 1;
   // Leapfrog averaging (src/q-gcm.F:1345-1351) after this step: where the box ocean's fused kernels run, they store the
@@ -2603,6 +2890,7 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   hipGraph_t graph;
   const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
   const long pn0 = c->poavg.n;
+  if (qd_dumps(c, s0, B)) QG_FAIL("qgcm_hip_steps: internal: a graph block would hold a dump step"); // (steps_impl cuts)
   HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
   for (int s = s0; s < s0 + B && !rc; ++s) rc = one_step(c, s);
@@ -2625,23 +2913,48 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
 }
 
 // dry = true only instantiates the graphs the run will replay (so that a timed region does not pay for it)
+// With a dump schedule (qgcm_hip_qocdiag_schedule) the graph blocks end before every dump step, and the dump step (and
+// a single step left before one) runs eagerly: the blocks of the other steps are the graphs of a run without one.
 static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
   int s = s0;
+  if (!dry && c->qd.every > 0) {
+    const long d = qd_dumps(c, s0, n);
+    if (d > c->qd.cap - c->qd.count)
+      QG_FAIL("qgcm_hip_steps: steps %d..%d would record %ld dumps, the ring has room for %d (qgcm_hip_qocdiag_read)",
+              s0, s0 + n - 1, d, c->qd.cap - c->qd.count);
+  }
   if (!dry) c->graph_call++; // (a dry pass belongs to the call that follows it: qgcm_hip_time_steps, prepare + steps)
-  const int is0 = c->oml.is, ism0 = c->oml.ism;
-  while (!c->profiling && n >= 2) {
-    const int B = n >= kGraphBlock50 ? kGraphBlock50 : (n & ~1);
-    hipGraphExec_t ge;
-    if (get_graph(c, s, B, &ge)) return 1;
-    if (!dry) HIPCHECK(hipGraphLaunch(ge, c->stream));
-    if (!dry && c->poavg.on) c->poavg.n += B;
-    s += B;
-    n -= B;
-    if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
+  const int is0 = c->oml.is, ism0 = c->oml.ism, ip0 = c->ip, iq0 = c->iq;
+  while (n > 0) {
+    const int m = qd_run(c, s, n); // steps before the next dump step
+    if (!c->profiling && m >= 2) {
+      const int B = m >= kGraphBlock50 ? kGraphBlock50 : (m & ~1);
+      hipGraphExec_t ge;
+      if (get_graph(c, s, B, &ge)) return 1;
+      if (!dry) HIPCHECK(hipGraphLaunch(ge, c->stream));
+      if (!dry && c->poavg.on) c->poavg.n += B;
+      s += B;
+      n -= B;
+      if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
+      continue;
+    }
+    if (c->qd.every <= 0) break; // no schedule: the tail below
+    // a dump step, or the single step before one: eagerly (a dry pass follows the rotations it would make)
+    if (!dry) {
+      if (one_step(c, s)) return 1;
+    } else {
+      c->ip ^= 1;
+      c->iq ^= 1;
+      if (c->oml.on) oml_rotate(c, 1);
+    }
+    ++s;
+    --n;
   }
   if (dry) {
     c->oml.is = is0;
     c->oml.ism = ism0;
+    c->ip = ip0;
+    c->iq = iq0;
     return 0;
   }
   for (; n > 0; --n, ++s)

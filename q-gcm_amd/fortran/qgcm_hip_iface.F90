@@ -329,6 +329,50 @@ module qgcm_hip_iface
       type(c_ptr), intent(in) :: fields(16)
       integer(c_int), intent(out) :: nsumoc
     end function
+    ! periodic ocean dumps (qocdiag_out, ocnc_out; DESIGN 6g)
+    integer(c_long) function qgcm_hip_qocdiag_len(h, nsko) bind(C, name='qgcm_hip_qocdiag_len')
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsko
+    end function
+    integer(c_int) function qgcm_hip_qocdiag(h, nsko, out) bind(C, name='qgcm_hip_qocdiag')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsko
+      real(c_double), intent(out) :: out(*)
+    end function
+    integer(c_int) function qgcm_hip_qocdiag_schedule(h, nsko, every, capacity) bind(C, name='qgcm_hip_qocdiag_schedule')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsko, every, capacity
+    end function
+    ! out, steps_out: c_loc of the caller's arrays, or c_null_ptr (steps_out not wanted; out with max <= 0, the query)
+    integer(c_int) function qgcm_hip_qocdiag_read(h, out, steps_out, max, nread) bind(C, name='qgcm_hip_qocdiag_read')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      type(c_ptr), value :: out, steps_out
+      integer(c_int), value :: max
+      integer(c_int), intent(out) :: nread
+    end function
+    integer(c_long) function qgcm_hip_ocnc_sample_len(h, nsko, outfloc) bind(C, name='qgcm_hip_ocnc_sample_len')
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsko
+      integer(c_int), intent(in) :: outfloc(7)
+    end function
+    integer(c_int) function qgcm_hip_ocnc_sample(h, nsko, outfloc, out) bind(C, name='qgcm_hip_ocnc_sample')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsko
+      integer(c_int), intent(in) :: outfloc(7)
+      real(c_double), intent(out) :: out(*)
+    end function
+    integer(c_int) function qgcm_hip_subsample_rows(h, nsko, mp0, mp1, mt0, mt1) bind(C, name='qgcm_hip_subsample_rows')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsko
+      integer(c_int), intent(out) :: mp0, mp1, mt0, mt1
+    end function
   end interface
 
 contains

@@ -84,6 +84,8 @@ SYMBOLS = [
     "qgcm_hip_prsamp_part_len", "qgcm_hip_prsamp_part", "qgcm_hip_prsamp_combine",
     "qgcm_hip_poavg_enable", "qgcm_hip_poavg_out", "qgcm_hip_set_tav_params", "qgcm_hip_set_tav_fields",
     "qgcm_hip_tavocn", "qgcm_hip_tav_reset", "qgcm_hip_tav_out",
+    "qgcm_hip_qocdiag_len", "qgcm_hip_qocdiag", "qgcm_hip_qocdiag_schedule", "qgcm_hip_qocdiag_read",
+    "qgcm_hip_ocnc_sample_len", "qgcm_hip_ocnc_sample", "qgcm_hip_subsample_rows",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -185,6 +187,16 @@ def load_library():
     L.qgcm_hip_tavocn.argtypes = [vp]
     L.qgcm_hip_tav_reset.argtypes = [vp]
     L.qgcm_hip_tav_out.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_int)]
+    ip = C.POINTER(C.c_int)
+    L.qgcm_hip_qocdiag_len.argtypes = [vp, C.c_int]
+    L.qgcm_hip_qocdiag_len.restype = C.c_long
+    L.qgcm_hip_qocdiag.argtypes = [vp, C.c_int, dp]
+    L.qgcm_hip_qocdiag_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.qgcm_hip_qocdiag_read.argtypes = [vp, dp, ip, C.c_int, ip]
+    L.qgcm_hip_ocnc_sample_len.argtypes = [vp, C.c_int, ip]
+    L.qgcm_hip_ocnc_sample_len.restype = C.c_long
+    L.qgcm_hip_ocnc_sample.argtypes = [vp, C.c_int, ip, dp]
+    L.qgcm_hip_subsample_rows.argtypes = [vp, C.c_int, ip, ip, ip, ip]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

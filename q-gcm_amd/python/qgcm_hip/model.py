@@ -112,6 +112,62 @@ def read_po_mean(L, h, cfg, np_rows, reset):
     return a, n.value
 
 
+# periodic ocean dumps (qgcm_hip_qocdiag / qgcm_hip_ocnc_sample)
+QOCDIAG_TERMS = ("dqdt", "qotjac", "qt2dif", "qt4dif", "qotent")
+OCNC_FIELDS = ("sst", "po", "qo", "wekto", "h", "tauxo", "tauyo")  # ocnc_out's order; tauxo, tauyo share outfloc(6)
+
+
+def subsample_count(n, nsko):
+    """Points of a subsample: min(mod(n,nsko),1) + (n-mod(n,nsko))/nsko (src/qocdiag.F:360-363)."""
+    m = n % nsko
+    return min(m, 1) + (n - m) // nsko
+
+
+def subsample_rows(L, h, nsko):
+    """(mp0, mp1, mt0, mt1): the subsample rows [mp0, mp1) of the p grid and [mt0, mt1) of the T grid this handle owns."""
+    r = [C.c_int() for _ in range(4)]
+    check(L.qgcm_hip_subsample_rows(h, int(nsko), *[C.byref(x) for x in r]))
+    return tuple(x.value for x in r)
+
+
+def unpack_budget(v, nl, ipwk):
+    """dict term -> (nlo, rows, ipwk) array from the packed out[term][k][jp][ip] of qgcm_hip_qocdiag."""
+    a = v.reshape(len(QOCDIAG_TERMS), nl, -1, ipwk)
+    return {t: a[n].copy() for n, t in enumerate(QOCDIAG_TERMS)}
+
+
+def read_budget(L, h, cfg, nsko):
+    n = L.qgcm_hip_qocdiag_len(h, int(nsko))
+    if n < 0:
+        check(1)
+    out = np.zeros(n)
+    check(L.qgcm_hip_qocdiag(h, int(nsko), _dp(out)))
+    return unpack_budget(out, cfg.nlo, subsample_count(cfg.nxpo, nsko))
+
+
+def read_ocnc(L, h, cfg, nsko, outfloc):
+    """ocnc_out's selected fields: dict name -> array (planes, rows, columns) (one plane for the 2-d fields)."""
+    fl = (C.c_int * 7)(*[int(x) for x in outfloc])
+    n = L.qgcm_hip_ocnc_sample_len(h, int(nsko), fl)
+    if n < 0:
+        check(1)
+    out = np.zeros(n)
+    check(L.qgcm_hip_ocnc_sample(h, int(nsko), fl, _dp(out)))
+    mp0, mp1, mt0, mt1 = subsample_rows(L, h, nsko)
+    ip, it = subsample_count(cfg.nxpo, nsko), subsample_count(cfg.nxto, nsko)
+    nl, res, o = cfg.nlo, {}, 0
+    shapes = dict(sst=(1, mt1 - mt0, it), po=(nl, mp1 - mp0, ip), qo=(nl, mp1 - mp0, ip), wekto=(1, mt1 - mt0, it),
+                  h=(nl - 1, mp1 - mp0, ip), tauxo=(1, mp1 - mp0, ip), tauyo=(1, mp1 - mp0, ip))
+    for f, name in enumerate(OCNC_FIELDS):
+        if int(outfloc[min(f, 5)]) != 1:
+            continue
+        m = int(np.prod(shapes[name]))
+        res[name] = out[o:o + m].reshape(shapes[name])
+        o += m
+    assert o == n
+    return res
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -383,6 +439,40 @@ class OceanModel:
     def reset_time_means(self):
         """tavini: zero the sums and the count."""
         check(self.L.qgcm_hip_tav_reset(self.h))
+
+    # -- periodic ocean dumps (qocdiag_out, ocnc_out; DESIGN 6g) ---------------------------------------------------
+    def vorticity_budget(self, nsko=1):
+        """qocdiag_out's terms from the device state (po, pom, qo, qom, the wekpo given, the entoc on the device):
+        dict dqdt, qotjac, qt2dif, qt4dif, qotent of (nlo, jpwk, ipwk) arrays at the points (1+i*nsko, 1+j*nsko).
+        The reference's dump when called between oml() and qgostep(), or at any time with the mixed layer off."""
+        return read_budget(self.L, self.h, self.cfg, nsko)
+
+    def schedule_vorticity_budget(self, nsko, every, capacity=1):
+        """Record the budget inside steps() on every step s with (s-1) % every == 0, after the step's oml and before
+        its tendency, into a device ring of `capacity` snapshots.  every = 0 removes the schedule."""
+        check(self.L.qgcm_hip_qocdiag_schedule(self.h, int(nsko), int(every), int(capacity)))
+        self._qd_nsko = int(nsko)
+
+    def read_vorticity_budgets(self):
+        """The unread scheduled snapshots, oldest first, as a list of (step, dict); they are freed."""
+        n = C.c_int()
+        check(self.L.qgcm_hip_qocdiag_read(self.h, None, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        nsko = self._qd_nsko
+        ln = self.L.qgcm_hip_qocdiag_len(self.h, nsko)
+        out = np.zeros(n.value * ln)
+        st = (C.c_int * n.value)()
+        got = C.c_int()
+        check(self.L.qgcm_hip_qocdiag_read(self.h, _dp(out), st, n.value, C.byref(got)))
+        ip = subsample_count(self.cfg.nxpo, nsko)
+        return [(st[r], unpack_budget(out[r * ln:(r + 1) * ln], self.cfg.nlo, ip)) for r in range(got.value)]
+
+    def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
+        """ocnc_out's subsampled fields (the selected ones): sst, wekto (jtwk, itwk); po, qo (nlo, jpwk, ipwk);
+        h (nlo-1, jpwk, ipwk); tauxo, tauyo (jpwk, ipwk)."""
+        r = read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
+        return {k: (v[0] if k in ("sst", "wekto", "tauxo", "tauyo") else v) for k, v in r.items()}
 
     # -- ocean mixed layer (`call oml`, src/q-gcm.F:1232; SURVEY 8 row f1) -------
     def oml_init(self, om):

@@ -393,6 +393,23 @@ class HipSlab:
     def reset_time_means(self):
         check(self.L.qgcm_hip_tav_reset(self.h))
 
+    # periodic ocean dumps: the subsample rows this rank owns (subsample_rows)
+    def subsample_rows(self, nsko):
+        """(mp0, mp1, mt0, mt1): the p-grid subsample rows [mp0, mp1) and T-grid rows [mt0, mt1) this rank owns."""
+        from .model import subsample_rows
+        return subsample_rows(self.L, self.h, nsko)
+
+    def vorticity_budget(self, nsko=1):
+        """As OceanModel.vorticity_budget for the owned subsample rows: (nlo, mp1 - mp0, ipwk) arrays."""
+        from .model import read_budget
+        return read_budget(self.L, self.h, self.cfg, nsko)
+
+    def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
+        """As OceanModel.ocean_dump for the owned subsample rows."""
+        from .model import read_ocnc
+        r = read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
+        return {k: (v[0] if k in ("sst", "wekto", "tauxo", "tauyo") else v) for k, v in r.items()}
+
     def set_dtopoc(self, dtopoc):
         """GLOBAL bottom topography (nxpo, nypo) for valids, None = flat."""
         sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
@@ -736,6 +753,64 @@ class SlabOcean:
     def reset_time_means(self):
         for x in self.slabs:
             x.reset_time_means()
+
+    # periodic ocean dumps, collective: the owned subsample rows of every rank, one all-gather -----------
+    def _gather_subsample(self, parts, rows, nsko, tnames=()):
+        """parts[i]: dict name -> (planes, rows, columns) owned subsample rows of local slab i; rows[i] its
+        (mp0, mp1, mt0, mt1) (HipSlab.subsample_rows), T-grid rows for the names in `tnames`.  One all-gather of the
+        packed blocks (row ranges, then every field padded to the largest rank's rows); dict name -> basin array."""
+        from .model import subsample_count
+        S, cfg = self.slabs, self.cfg
+        names = sorted(parts[0])
+        first = lambda g0: (g0 - 1 + nsko - 1) // nsko
+        rmax = max([max(first(g0), (g1 - 1) // nsko + 1) - first(g0) for g0, g1 in partition(cfg.nypo, self.P)]
+                   + [r[1] - r[0] for r in rows] + [1])
+        sizes = [(n, parts[0][n].shape[0], parts[0][n].shape[2]) for n in names]
+        ln = 4 + sum(k * rmax * nc for _, k, nc in sizes)
+        send, gath = [], []
+        for x, d, r in zip(S, parts, rows):
+            v = np.zeros(ln)
+            v[:4] = r
+            o = 4
+            for n, k, nc in sizes:
+                buf = np.zeros((k, rmax, nc))
+                buf[:, :d[n].shape[1], :] = d[n]
+                v[o:o + buf.size] = buf.ravel()
+                o += buf.size
+            t = x.new_buffer(ln)
+            t.copy_(x.torch.from_numpy(v))
+            send.append(t)
+            gath.append(x.new_buffer(ln * self.P))
+        self._settle()
+        self._comm(self.comm.all_gather, gath, send)
+        g = gath[0].cpu().numpy().reshape(self.P, ln)
+        out, o = {}, 4
+        for n, k, nc in sizes:
+            tg = n in tnames
+            full = np.zeros((k, subsample_count(cfg.nyto if tg else cfg.nypo, nsko), nc))
+            for r in range(self.P):
+                m0, m1 = (int(g[r, 2]), int(g[r, 3])) if tg else (int(g[r, 0]), int(g[r, 1]))
+                blk = g[r, o:o + k * rmax * nc].reshape(k, rmax, nc)
+                full[:, m0:m1, :] = blk[:, :m1 - m0, :]
+            out[n] = full
+            o += k * rmax * nc
+        return out
+
+    def vorticity_budget(self, nsko=1):
+        """As OceanModel.vorticity_budget: the whole basin's (nlo, jpwk, ipwk) arrays, assembled from the owned
+        subsample rows of every rank (collective)."""
+        self._join()
+        return self._gather_subsample([x.vorticity_budget(nsko) for x in self.slabs],
+                                      [x.subsample_rows(nsko) for x in self.slabs], nsko)
+
+    def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
+        """As OceanModel.ocean_dump: the whole basin's subsampled fields (collective)."""
+        self._join()
+        flat = ("sst", "wekto", "tauxo", "tauyo")
+        parts = [{n: (v[None] if n in flat else v) for n, v in x.ocean_dump(nsko, outfloc).items()}
+                 for x in self.slabs]
+        out = self._gather_subsample(parts, [x.subsample_rows(nsko) for x in self.slabs], nsko, ("sst", "wekto"))
+        return {n: (v[0] if n in flat else v) for n, v in out.items()}
 
     def homsol(self):
         """homsol of the box ocean (src/conhoms.F:549-641) ON the slabs: the modal Helmholtz problems of a step are
