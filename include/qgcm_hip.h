@@ -408,6 +408,49 @@ int qgcm_hip_prsamp_part_len(qgcm_hip_handle h);
 int qgcm_hip_prsamp_part(qgcm_hip_handle h, double *send_dev);
 int qgcm_hip_prsamp_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, double *out);
 
+/* ---- atmosphere monitors and valids -----------------------------------------------------------
+ * The atmosphere half of "call monnc_comp" (src/monitor_diag.F:160-172, 185-475 with del4ch and genint), "call courat"
+ * (:1213-1444) and the atmospheric half of "call valids" (src/valsubs.F:120-269) on an atmosphere handle
+ * (qgcm_hip_params.atmos = 1) that owns the whole domain.  They read pa, pam, qa at the time levels qgcm_hip_get_state
+ * would return (after an averaging step the averaged ones), wekpa and entat of qgcm_hip_set_forcing and the fields
+ * below, and change no state.  dta = tdta/2, gpat, hat, ah4at, rdxaf0, hdxam1 and atnorm = 1/(nxta*nyta) come from
+ * qgcm_hip_params.  Every entry point refuses an ocean handle and a y-slab handle, naming which.
+ * qgcm_hip_set_atm_mon_params: the constants the handle does not hold (struct below); fails when the ocean's cells
+ *   do not lie on the atmosphere's T grid.
+ * qgcm_hip_set_atm_monitor_fields: what xforc / aml leave in MODULE intrfac / atstate on the host: wekta, ast, hmixa
+ *   (nxta,nyta), tauxa, tauya (nxpa,nypa), uekat (nxpa,nyta), vekat (nxta,nypa).  NULL = leave unchanged.  Synchronous.
+ * qgcm_hip_atm_monitor_len(h) = 18*nla + 11 (-1 for an ocean handle).  qgcm_hip_atm_monitors(h, out) fails,
+ *   naming what is missing, before qgcm_hip_set_atm_mon_params or when one of the seven fields was never given.
+ *   Out, in this order (names of MODULE monitor, src/monitor_data.F):
+ *     wetmat, watmat, wepmat, wapmat
+ *     entmat(nla-1), enamat(nla-1), etamat(nla-1), et2mat(nla-1), ddtpeat(nla-1), pkenat(nla-1)
+ *     utauat
+ *     pavgat(nla), qavgat(nla), ah4dat(nla), kealat(nla), ddtkeat(nla), atstpos(nla), atstval(nla)
+ *     tmlmat, hmlmat, astmin, astmax, hcmlat, tmaooc, olrtop
+ *     umminat, ummaxat, vmminat, vmmaxat, cnmlat                                   (courat, mixed layer)
+ *     ugminat(nla), ugmaxat(nla), vgminat(nla), vgmaxat(nla), cnqgat(nla)        (courat, Q-G layers)
+ *   As the reference writes them: ddtpeat without the atnorm factor, entmat / enamat / pkenat zero beyond interface 1,
+ *   vkedot (in ddtkeat) the integral of Del-sqd(lagged v).  Extrema, Courant numbers, atstpos / atstval (serial
+ *   zonal sums) and tmaooc (serial sum) are bitwise the reference's; the genint integrals agree to rounding.  Bitwise
+ *   reproducible from call to call.  Runs on the handle's stream; synchronous.
+ * qgcm_hip_atm_valids(h, out, solnok): out[12] = min, max of pa, qa, ast, wekta, tauxa, tauya (bitwise);
+ *   *solnok = 0 if |pa| >= 1e7, |qa| >= 0.05, |ast| >= 90, |wekta| >= 1, |tauxa| or |tauya| >= 10 (the reference's
+ *   limits), else 1.  Needs wekta, tauxa, tauya, ast.  The neighbourhood print-out stays on the host.  Synchronous. */
+typedef struct qgcm_hip_atm_mon_params {
+  double rhoat, cpat;       /* atmospheric density, specific heat          (MODULE atconst) */
+  double hmat, davgat;      /* fixed mixed layer depth, mean topography    (MODULE atconst) */
+  double aup[QGCM_HIP_MAXL - 1]; /* Aup(nla, 1..nla-1)                     (MODULE radiate) */
+  double bup, cup, dup;     /* Bup(nla), Cup(nla), Dup(nla)                (MODULE radiate) */
+  int nx1, ny1;             /* first atmosphere T cell above the ocean     (MODULE parameters) */
+  int nxaooc, nyaooc;       /* atmosphere T cells above the ocean          (MODULE parameters) */
+} qgcm_hip_atm_mon_params;
+int qgcm_hip_set_atm_mon_params(qgcm_hip_handle h, const qgcm_hip_atm_mon_params *p);
+int qgcm_hip_set_atm_monitor_fields(qgcm_hip_handle h, const double *wekta, const double *tauxa, const double *tauya,
+                                    const double *ast, const double *hmixa, const double *uekat, const double *vekat);
+int qgcm_hip_atm_monitor_len(qgcm_hip_handle h);
+int qgcm_hip_atm_monitors(qgcm_hip_handle h, double *out);
+int qgcm_hip_atm_valids(qgcm_hip_handle h, double *out, int *solnok);
+
 /* ---- start-up / restart arithmetic and the progress sample on the device ------------
  * qgcm_hip_init_from_p: the start-up sequence of the main program (src/q-gcm.F:711-731; atmosphere :738-749) from
  *   the po, pom ALREADY on the device (qgcm_hip_set_state with qo = qom = NULL, e.g. after a restart read):

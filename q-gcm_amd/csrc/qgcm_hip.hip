@@ -35,6 +35,7 @@
 #include "k_oml.h"
 #include "k_valids.h"
 #include "k_monitors.h"
+#include "k_atm_monitors.h"
 #include "k_tavg.h"
 #include "k_qocdiag.h"
 #include "k_setup.h"
@@ -170,6 +171,17 @@ struct qgcm_hip_ctx {
     double *psum = nullptr, *pmin = nullptr, *ujet = nullptr, *out = nullptr;
     double *hout = nullptr; // pinned host copy of out
   } mon;
+  // atmosphere monitors and valids (qgcm_hip_atm_monitors / _atm_valids, k_atm_monitors.h): constants, the fields
+  // xforc / aml leave on the host (qgcm_hip_set_atm_monitor_fields), partials and the pinned result
+  struct {
+    bool prm_set = false;
+    qgcm_hip_atm_mon_params prm;
+    int ldt = 0;
+    double *wekta = nullptr, *tauxa = nullptr, *tauya = nullptr, *ast = nullptr, *hmixa = nullptr, *uekat = nullptr,
+           *vekat = nullptr;
+    double *psum = nullptr, *pmin = nullptr, *chain = nullptr, *out = nullptr;
+    double *hout = nullptr; // pinned host copy of out
+  } atmon;
   // running mean of po (qgcm_hip_poavg_enable, k_tavg.h): the sum over the owned rows and its count; while `on`
   // every step of qgcm_hip_steps / the slab stage 2 adds its po before the leapfrog averaging
   struct {
@@ -384,6 +396,11 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : monp)
     if (p) hipFree(p);
   if (c->mon.hout) hipHostFree(c->mon.hout);
+  double *atmp[] = {c->atmon.wekta, c->atmon.tauxa, c->atmon.tauya, c->atmon.ast, c->atmon.hmixa, c->atmon.uekat,
+                    c->atmon.vekat, c->atmon.psum, c->atmon.pmin, c->atmon.chain, c->atmon.out};
+  for (double *p : atmp)
+    if (p) hipFree(p);
+  if (c->atmon.hout) hipHostFree(c->atmon.hout);
   double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet, c->qd.buf, c->qd.ring};
   for (double *p : tavp)
     if (p) hipFree(p);
@@ -2127,6 +2144,141 @@ extern "C" int qgcm_hip_monitors_combine(qgcm_hip_handle c, const double *gath_d
     QG_FAIL("qgcm_hip_monitors_combine: the gathered summaries do not tile rows 1..%d (rank %d of %d does not continue them)",
             c->g.nyg, (int)m.hout[MON_LEN(nl)] - 1, nranks);
   memcpy(out, m.hout, sizeof(double) * MON_LEN(nl));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// atmosphere monitors and valids: the atmosphere half of monnc_comp, courat and valids
+// ---------------------------------------------------------------------------
+// the atmosphere handles these entry points serve: whole-domain atmosphere handles only
+static int atm_only(qgcm_hip_ctx *c, const char *who) {
+  if (!c) QG_FAIL("%s: null handle", who);
+  if (!c->g.atm) QG_FAIL("%s: the handle is an ocean (qgcm_hip_monitors / qgcm_hip_valids serve it)", who);
+  if (!c->whole) QG_FAIL("%s: the handle is a y-slab (the atmosphere's diagnostics need the whole domain)", who);
+  return check_ready(c, who);
+}
+
+extern "C" int qgcm_hip_atm_monitor_len(qgcm_hip_handle c) { return c && c->g.atm ? ATMON_LEN(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_set_atm_mon_params(qgcm_hip_handle c, const qgcm_hip_atm_mon_params *p) {
+  if (atm_only(c, "qgcm_hip_set_atm_mon_params")) return 1;
+  if (!p) QG_FAIL("qgcm_hip_set_atm_mon_params: null argument");
+  const int nxt = c->g.nx - 1, nyt = c->g.ny - 1;
+  if (p->nxaooc < 1 || p->nyaooc < 1 || p->nx1 < 1 || p->ny1 < 1 || p->nx1 + p->nxaooc - 1 > nxt ||
+      p->ny1 + p->nyaooc - 1 > nyt)
+    QG_FAIL("qgcm_hip_set_atm_mon_params: the ocean's cells nx1 = %d, ny1 = %d, nxaooc = %d, nyaooc = %d do not lie "
+            "on the atmosphere's %d x %d T grid", p->nx1, p->ny1, p->nxaooc, p->nyaooc, nxt, nyt);
+  c->atmon.prm = *p;
+  c->atmon.prm_set = true;
+  return 0;
+}
+
+extern "C" int qgcm_hip_set_atm_monitor_fields(qgcm_hip_handle c, const double *wekta, const double *tauxa,
+                                               const double *tauya, const double *ast, const double *hmixa,
+                                               const double *uekat, const double *vekat) {
+  if (atm_only(c, "qgcm_hip_set_atm_monitor_fields")) return 1;
+  const QgGeom &g = c->g;
+  const int nxt = g.nx - 1, nyt = g.ny - 1;
+  auto &m = c->atmon;
+  if (!m.ldt) m.ldt = round_up(nxt, 16);
+  // (field, device buffer, pitch, width, rows)
+  struct F { const double *src; double **dst; int ld, nx, ny; } fs[] = {
+      {wekta, &m.wekta, m.ldt, nxt, nyt}, {tauxa, &m.tauxa, g.ldx, g.nx, g.ny}, {tauya, &m.tauya, g.ldx, g.nx, g.ny},
+      {ast, &m.ast, m.ldt, nxt, nyt},     {hmixa, &m.hmixa, m.ldt, nxt, nyt},   {uekat, &m.uekat, g.ldx, g.nx, nyt},
+      {vekat, &m.vekat, m.ldt, nxt, g.ny}};
+  for (const F &f : fs) {
+    if (!f.src) continue;
+    if (!*f.dst && dalloc(f.dst, (size_t)f.ld * f.ny)) return 1;
+    if (upload2d(c, *f.dst, f.ld, f.src, f.nx, f.ny)) return 1;
+  }
+  return 0;
+}
+
+// the kernel parameters; `mon`: the monitors (constants, every field), else the valids (pa, qa, wekta, tauxa, tauya,
+// ast).  Allocates the partials on first use.
+static int atmon_params(qgcm_hip_ctx *c, QgAtmonParams &P, bool mon, const char *who) {
+  if (atm_only(c, who)) return 1;
+  auto &m = c->atmon;
+  if (mon && !m.prm_set) QG_FAIL("%s: qgcm_hip_set_atm_mon_params has not been called", who);
+  const char *miss = !m.wekta ? "wekta" : !m.tauxa ? "tauxa" : !m.tauya ? "tauya" : !m.ast ? "ast" : nullptr;
+  if (!miss && mon) miss = !m.hmixa ? "hmixa" : !m.uekat ? "uekat" : !m.vekat ? "vekat" : nullptr;
+  if (miss) QG_FAIL("%s: %s was never given (qgcm_hip_set_atm_monitor_fields)", who, miss);
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  const int nl = g.nl, nyt = g.ny - 1;
+  if ((size_t)(g.nx > ATMON_CHUNK ? g.nx : ATMON_CHUNK) * sizeof(double) > 65536)
+    QG_FAIL("%s: nxpa = %d exceeds the LDS row of k_atmon_chain", who, g.nx);
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  // the time levels qgcm_hip_get_state hands out at this point of the loop (after an averaging step: the averaged ones)
+  P.pa = c->p[c->ip]; P.pam = c->p[c->ip ^ 1]; P.qa = c->q[c->iq];
+  P.wekpa = c->wekpo; P.entat = c->entoc;
+  P.wekta = m.wekta; P.tauxa = m.tauxa; P.tauya = m.tauya; P.ast = m.ast; P.hmixa = m.hmixa; P.uekat = m.uekat;
+  P.vekat = m.vekat;
+  P.ldt = m.ldt;
+  P.ntx = (g.nx + MON_TX - 1) / MON_TX;
+  P.nblk = P.ntx * ((g.ny + MON_TY - 1) / MON_TY);
+  if (!m.out) {
+    if (dalloc(&m.psum, (size_t)MON_NS(nl) * P.nblk) || dalloc(&m.pmin, (size_t)MON_NM(nl) * P.nblk) ||
+        dalloc(&m.chain, (size_t)nyt * nl + 1) || dalloc(&m.out, ATMON_LEN(nl)))
+      return 1;
+    HIPCHECK(hipHostMalloc((void **)&m.hout, sizeof(double) * ATMON_LEN(nl), hipHostMallocDefault));
+  }
+  P.psum = m.psum; P.pmin = m.pmin; P.chain = m.chain; P.out = m.out;
+  // MODULE atconst as src/q-gcm.F:392-441 derives it; dta = tdta/2 exactly; atnorm: src/parameters_data.F:87
+  P.dta = 0.5 * pr.tdto;
+  P.rdxaf0 = 1.0 / (pr.dxo * pr.fnot);
+  P.dxam2 = 1.0 / (pr.dxo * pr.dxo);
+  P.hdxam1 = 0.5 / pr.dxo;
+  P.atnorm = 1.0 / (double)((g.nx - 1) * nyt);
+  const qgcm_hip_atm_mon_params &q = m.prm;
+  P.rhoat = q.rhoat; P.cpat = q.cpat; P.hmat = q.hmat; P.davgat = q.davgat;
+  P.bup = q.bup; P.cup = q.cup; P.dup = q.dup;
+  P.nx1 = q.nx1; P.ny1 = q.ny1; P.nxaooc = q.nxaooc; P.nyaooc = q.nyaooc;
+  for (int k = 0; k < nl - 1; ++k) { P.aup[k] = q.aup[k]; P.rgpat[k] = 1.0 / pr.gpoc[k]; P.gpat[k] = pr.gpoc[k]; }
+  for (int k = 0; k < nl; ++k) { P.hat[k] = pr.hoc[k]; P.ah4at[k] = pr.ah4oc[k]; }
+  return 0;
+}
+
+extern "C" int qgcm_hip_atm_monitors(qgcm_hip_handle c, double *out) {
+  if (atm_only(c, "qgcm_hip_atm_monitors")) return 1;
+  if (!out) QG_FAIL("qgcm_hip_atm_monitors: null argument");
+  QgAtmonParams P;
+  if (atmon_params(c, P, true, "qgcm_hip_atm_monitors")) return 1;
+  const QgGeom &g = c->g;
+  const int nl = g.nl, nyt = g.ny - 1;
+  const size_t lds = sizeof(double) * (g.nx > ATMON_CHUNK ? g.nx : ATMON_CHUNK);
+#define QG_ATMON(NLV)                                                                                 \
+  hipLaunchKernelGGL((k_atmon_scan<NLV>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);               \
+  hipLaunchKernelGGL(k_atmon_chain, dim3(nyt * nl + 1), dim3(64), lds, c->stream, P);                 \
+  hipLaunchKernelGGL((k_atmon_final<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P)
+  QG_SWITCH_NL(nl, QG_ATMON, "k_atmon");
+#undef QG_ATMON
+  HIPCHECK(hipGetLastError());
+  auto &m = c->atmon;
+  HIPCHECK(hipMemcpyAsync(m.hout, m.out, sizeof(double) * ATMON_LEN(nl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  memcpy(out, m.hout, sizeof(double) * ATMON_LEN(nl));
+  return 0;
+}
+
+extern "C" int qgcm_hip_atm_valids(qgcm_hip_handle c, double *out, int *solnok) {
+  if (atm_only(c, "qgcm_hip_atm_valids")) return 1;
+  if (!out || !solnok) QG_FAIL("qgcm_hip_atm_valids: null argument");
+  QgAtmonParams P;
+  if (atmon_params(c, P, false, "qgcm_hip_atm_valids")) return 1;
+  hipLaunchKernelGGL(k_atval, dim3(1), dim3(MON_FT), 0, c->stream, P);
+  HIPCHECK(hipGetLastError());
+  auto &m = c->atmon;
+  HIPCHECK(hipMemcpyAsync(m.hout, m.out, sizeof(double) * ATVAL_N, hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  memcpy(out, m.hout, sizeof(double) * ATVAL_N);
+  // the limits of src/valsubs.F:78-97: patext, qatext, astext, wtaext, tauext (tauxa and tauya share theirs)
+  static const double ext[6] = {1.0e7, 0.05, 90.0, 1.0, 10.0, 10.0};
+  int ok = 1;
+  for (int f = 0; f < 6; ++f)
+    if (fabs(out[2 * f]) >= ext[f] || fabs(out[2 * f + 1]) >= ext[f]) ok = 0;
+  *solnok = ok;
   return 0;
 }
 

@@ -37,6 +37,14 @@ module qgcm_hip_iface
     integer(c_int) :: sb_flag, nb_flag   ! sb_hflux, nb_hflux of the C struct
   end type qgcm_hip_tav_params
 
+  ! struct qgcm_hip_atm_mon_params: constants of the atmosphere monitors (qgcm_hip_set_atm_mon_params)
+  type, bind(C) :: qgcm_hip_atm_mon_params
+    real(c_double) :: rhoat, cpat, hmat, davgat
+    real(c_double) :: aup(QGCM_HIP_MAXL-1)   ! Aup(nla, 1..nla-1)
+    real(c_double) :: bup, cup, dup          ! Bup(nla), Cup(nla), Dup(nla)
+    integer(c_int) :: nx1, ny1, nxaooc, nyaooc
+  end type qgcm_hip_atm_mon_params
+
   interface
     integer(c_int) function qgcm_hip_create(h, prm, device) bind(C, name='qgcm_hip_create')
       import :: c_ptr, c_int, qgcm_hip_params
@@ -372,6 +380,34 @@ module qgcm_hip_iface
       type(c_ptr), value :: h
       integer(c_int), value :: nsko
       integer(c_int), intent(out) :: mp0, mp1, mt0, mt1
+    end function
+    ! atmosphere monitors and valids (the atmosphere half of monnc_comp, courat, valids; DESIGN 6h)
+    integer(c_int) function qgcm_hip_set_atm_mon_params(h, p) bind(C, name='qgcm_hip_set_atm_mon_params')
+      import :: c_ptr, c_int, qgcm_hip_atm_mon_params
+      type(c_ptr), value :: h
+      type(qgcm_hip_atm_mon_params), intent(in) :: p
+    end function
+    ! c_loc of the caller's arrays, or c_null_ptr to leave a field unchanged
+    integer(c_int) function qgcm_hip_set_atm_monitor_fields(h, wekta, tauxa, tauya, ast, hmixa, uekat, vekat) &
+        bind(C, name='qgcm_hip_set_atm_monitor_fields')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      type(c_ptr), value :: wekta, tauxa, tauya, ast, hmixa, uekat, vekat
+    end function
+    integer(c_int) function qgcm_hip_atm_monitor_len(h) bind(C, name='qgcm_hip_atm_monitor_len')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_atm_monitors(h, out) bind(C, name='qgcm_hip_atm_monitors')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: out(*)
+    end function
+    integer(c_int) function qgcm_hip_atm_valids(h, out, solnok) bind(C, name='qgcm_hip_atm_valids')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: out(12)
+      integer(c_int), intent(out) :: solnok
     end function
   end interface
 

@@ -49,6 +49,15 @@ class MonParams(C.Structure):
     ]
 
 
+class AtmMonParams(C.Structure):
+    """struct qgcm_hip_atm_mon_params (include/qgcm_hip.h)."""
+    _fields_ = [
+        ("rhoat", C.c_double), ("cpat", C.c_double), ("hmat", C.c_double), ("davgat", C.c_double),
+        ("aup", C.c_double * (MAXL - 1)), ("bup", C.c_double), ("cup", C.c_double), ("dup", C.c_double),
+        ("nx1", C.c_int), ("ny1", C.c_int), ("nxaooc", C.c_int), ("nyaooc", C.c_int),
+    ]
+
+
 class TavParams(C.Structure):
     """struct qgcm_hip_tav_params (include/qgcm_hip.h)."""
     _fields_ = [
@@ -82,6 +91,8 @@ SYMBOLS = [
     "qgcm_hip_monitor_part_len", "qgcm_hip_monitors_part", "qgcm_hip_monitors_combine",
     "qgcm_hip_valids_part_len", "qgcm_hip_valids_part", "qgcm_hip_valids_combine",
     "qgcm_hip_prsamp_part_len", "qgcm_hip_prsamp_part", "qgcm_hip_prsamp_combine",
+    "qgcm_hip_set_atm_mon_params", "qgcm_hip_set_atm_monitor_fields", "qgcm_hip_atm_monitor_len",
+    "qgcm_hip_atm_monitors", "qgcm_hip_atm_valids",
     "qgcm_hip_poavg_enable", "qgcm_hip_poavg_out", "qgcm_hip_set_tav_params", "qgcm_hip_set_tav_fields",
     "qgcm_hip_tavocn", "qgcm_hip_tav_reset", "qgcm_hip_tav_out",
     "qgcm_hip_qocdiag_len", "qgcm_hip_qocdiag", "qgcm_hip_qocdiag_schedule", "qgcm_hip_qocdiag_read",
@@ -180,6 +191,11 @@ def load_library():
     L.qgcm_hip_monitors_combine.argtypes = [vp, vp, C.c_int, dp]
     L.qgcm_hip_valids_combine.argtypes = [vp, vp, C.c_int, dp, C.POINTER(C.c_int)]
     L.qgcm_hip_prsamp_combine.argtypes = [vp, vp, C.c_int, dp]
+    L.qgcm_hip_set_atm_mon_params.argtypes = [vp, C.POINTER(AtmMonParams)]
+    L.qgcm_hip_set_atm_monitor_fields.argtypes = [vp] + [dp] * 7
+    L.qgcm_hip_atm_monitor_len.argtypes = [vp]
+    L.qgcm_hip_atm_monitors.argtypes = [vp, dp]
+    L.qgcm_hip_atm_valids.argtypes = [vp, dp, C.POINTER(C.c_int)]
     L.qgcm_hip_poavg_enable.argtypes = [vp, C.c_int]
     L.qgcm_hip_poavg_out.argtypes = [vp, dp, C.POINTER(C.c_int), C.c_int]
     L.qgcm_hip_set_tav_params.argtypes = [vp, C.POINTER(TavParams)]

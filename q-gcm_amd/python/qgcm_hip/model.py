@@ -35,6 +35,63 @@ MONITOR_LAYOUT = ([(n, 0) for n in ("wetmoc", "watmoc", "wepmoc", "wapmoc", "ent
                   + [(n, 1) for n in ("ugminoc", "ugmaxoc", "vgminoc", "vgmaxoc", "cnqgoc")])
 
 
+# layout of qgcm_hip_atm_monitors (include/qgcm_hip.h), as MONITOR_LAYOUT: (name, length in units of nla)
+ATM_MONITOR_LAYOUT = ([(n, 0) for n in ("wetmat", "watmat", "wepmat", "wapmat")]
+                      + [(n, -1) for n in ("entmat", "enamat", "etamat", "et2mat", "ddtpeat", "pkenat")]
+                      + [("utauat", 0)]
+                      + [(n, 1) for n in ("pavgat", "qavgat", "ah4dat", "kealat", "ddtkeat", "atstpos", "atstval")]
+                      + [(n, 0) for n in ("tmlmat", "hmlmat", "astmin", "astmax", "hcmlat", "tmaooc", "olrtop",
+                                          "umminat", "ummaxat", "vmminat", "vmmaxat", "cnmlat")]
+                      + [(n, 1) for n in ("ugminat", "ugmaxat", "vgminat", "vgmaxat", "cnqgat")])
+
+# the twelve numbers of qgcm_hip_atm_valids
+ATM_VALIDS_NAMES = ("pamin", "pamax", "qamin", "qamax", "astmin", "astmax", "wekmin", "wekmax", "txamin", "txamax",
+                    "tyamin", "tyamax")
+
+
+def unpack_atm_monitors(v, nl):
+    """dict name -> float or array from the packed vector of qgcm_hip_atm_monitors; atstpos as int (0: none)."""
+    return _unpack(v, nl, ATM_MONITOR_LAYOUT, "atstpos")
+
+
+def _unpack(v, nl, layout, posname):
+    out, i = {}, 0
+    for name, kind in layout:
+        n = {0: 1, -1: nl - 1, 1: nl}[kind]
+        x = np.array(v[i:i + n], dtype=np.float64)
+        out[name] = float(x[0]) if kind == 0 else (x.astype(np.int64) if name == posname else x)
+        i += n
+    if i != len(v):
+        raise QgcmHipError("monitor vector has %d entries, the layout %d" % (len(v), i))
+    return out
+
+
+def atm_mon_params(acfg, ocean=None, rhoat=1.0, cpat=1.0e3, hmat=1000.0, davgat=0.0, aup=None, bup=0.0, cup=0.0,
+                   dup=0.0, nx1=None, ny1=None, nxaooc=None, nyaooc=None):
+    """struct qgcm_hip_atm_mon_params for the atmosphere `acfg` (an AtmosConfig).  rhoat, cpat, hmat default to
+    examples/double_gyre_coupled's input.params (1.0 kg m^-3, 1.0e3 J kg^-1 K^-1, 1000 m); davgat = 0 is a flat
+    atmosphere.  aup (= Aup(nla, 1..nla-1)), bup, cup, dup (= Bup(nla), Cup(nla), Dup(nla)) are computed by radiate
+    at start-up, not read from input.params: they default to 0 (olrtop = 0).  The ocean's cells: nxaooc, nyaooc from
+    `ocean` (an OceanConfig) or given; nx1, ny1 default to src/parameters_data.F:86, 1 + (nxta - nxaooc)/2."""
+    from .lib import AtmMonParams
+    nxa = ocean.nxaooc if nxaooc is None and ocean is not None else nxaooc
+    nya = ocean.nyaooc if nyaooc is None and ocean is not None else nyaooc
+    if nxa is None or nya is None:
+        raise QgcmHipError("atm_mon_params: give the ocean's configuration or nxaooc, nyaooc")
+    p = AtmMonParams()
+    p.rhoat, p.cpat, p.hmat, p.davgat = float(rhoat), float(cpat), float(hmat), float(davgat)
+    a = np.zeros(acfg.nla - 1) if aup is None else np.asarray(aup, dtype=np.float64)
+    if len(a) != acfg.nla - 1:
+        raise QgcmHipError("aup needs nla-1 = %d values" % (acfg.nla - 1))
+    for k, v in enumerate(a):
+        p.aup[k] = float(v)
+    p.bup, p.cup, p.dup = float(bup), float(cup), float(dup)
+    p.nxaooc, p.nyaooc = int(nxa), int(nya)
+    p.nx1 = 1 + (acfg.nxta - p.nxaooc) // 2 if nx1 is None else int(nx1)
+    p.ny1 = 1 + (acfg.nyta - p.nyaooc) // 2 if ny1 is None else int(ny1)
+    return p
+
+
 def unpack_monitors(v, nl):
     """dict name -> float or array from the packed vector of qgcm_hip_monitors; ocjpos as int (1-based row, 0: none)."""
     out, i = {}, 0
@@ -614,6 +671,39 @@ class AtmosModel(OceanModel):
         b = np.zeros(4 * self.cfg.nlo)
         check(self.L.qgcm_hip_get_bsums(self.h, _dp(b)))
         return b
+
+    # -- atmosphere monitors and valids (atmosphere half of `call monnc_comp` + courat, valids) ---------
+    def set_atm_monitor_params(self, ocean=None, **kw):
+        """Constants of MODULE atconst / radiate / parameters that monnc_comp reads and the handle does not hold;
+        keywords and defaults: qgcm_hip.model.atm_mon_params (rhoat = 1.0, cpat = 1.0e3, hmat = 1000 as in
+        examples/double_gyre_coupled's input.params; davgat, aup, bup, cup, dup = 0; nxaooc, nyaooc from `ocean`,
+        an OceanConfig, and nx1, ny1 centred as src/parameters_data.F places the ocean)."""
+        p = atm_mon_params(self.cfg, ocean, **kw)
+        check(self.L.qgcm_hip_set_atm_mon_params(self.h, C.byref(p)))
+
+    def set_atm_monitor_fields(self, wekta=None, tauxa=None, tauya=None, ast=None, hmixa=None, uekat=None, vekat=None):
+        """wekta, ast, hmixa (nxta,nyta), tauxa, tauya (nxpa,nypa), uekat (nxpa,nyta), vekat (nxta,nypa): what xforc /
+        aml leave on the host.  None = leave unchanged."""
+        a = [_f(x) for x in (wekta, tauxa, tauya, ast, hmixa, uekat, vekat)]
+        check(self.L.qgcm_hip_set_atm_monitor_fields(self.h, *[_dp(x) for x in a]))
+
+    def monitor_vector(self):
+        """The packed result of qgcm_hip_atm_monitors (order: include/qgcm_hip.h)."""
+        out = np.zeros(self.L.qgcm_hip_atm_monitor_len(self.h))
+        check(self.L.qgcm_hip_atm_monitors(self.h, _dp(out)))
+        return out
+
+    def monitors(self):
+        """The atmosphere variables of MODULE monitor that monnc_comp / courat compute, from the device state without
+        pulling it: dict keyed by the reference's names (ATM_MONITOR_LAYOUT)."""
+        return unpack_atm_monitors(self.monitor_vector(), self.cfg.nla)
+
+    def atm_valids(self):
+        """(solnok, out): out = min, max of pa, qa, ast, wekta, tauxa, tauya (src/valsubs.F:120-269)."""
+        out = np.zeros(len(ATM_VALIDS_NAMES))
+        ok = C.c_int()
+        check(self.L.qgcm_hip_atm_valids(self.h, _dp(out), C.byref(ok)))
+        return bool(ok.value), out
 
     pa = OceanModel.po
     pam = OceanModel.pom
