@@ -547,6 +547,49 @@ long qgcm_hip_ocnc_sample_len(qgcm_hip_handle h, int nsko, const int *outfloc);
 int qgcm_hip_ocnc_sample(qgcm_hip_handle h, int nsko, const int *outfloc, double *out);
 int qgcm_hip_subsample_rows(qgcm_hip_handle h, int nsko, int *mp0, int *mp1, int *mt0, int *mt1);
 
+/* ---- time averages and periodic dump of the atmosphere --------------------------------------------------
+ * tavatm / tavout, atmosphere half (src/timavge.F:278-421, 715-801), and atnc_out (src/nc_subs.F:1077-1326) on an
+ * atmosphere handle (qgcm_hip_params.atmos = 1).  They read pa, qa at the time levels qgcm_hip_get_state would return
+ * (after an averaging step the averaged ones), tauxa, tauya, wekta, ast, hmixa of qgcm_hip_set_atm_monitor_fields, hmat
+ * of qgcm_hip_set_atm_mon_params, gpat and rdxaf0 = 1/(dxa*fnot) from qgcm_hip_params.  Every entry point refuses an
+ * ocean handle; the ocean's qgcm_hip_tavocn / _tav_out / _tav_reset / _set_tav_fields refuse an atmosphere handle.
+ * qgcm_hip_set_atm_tav_fields(h, fnetat): fnetat (nxta,nyta) of MODULE intrfac.  NULL = leave unchanged.  Synchronous.
+ * qgcm_hip_tavatm(h): adds one contribution to the 14 sums and counts it (nsumat); asynchronous.  Fails, naming what is
+ *   missing, before qgcm_hip_set_atm_mon_params (hmat), before tauxa, tauya, wekta, ast were given, or before fnetat.
+ * qgcm_hip_atm_tav_reset(h): tavini's atmosphere half - zeroes the sums and the count.
+ * qgcm_hip_atm_tav_out(h, fields, nsumat): tavout's arithmetic (rnsat = 1/nsumat, 0 when nsumat = 0) into
+ *   fields[0 .. QGCM_HIP_ATM_TAV_NOUT-1], dense Fortran order, NULL = skip (only requested means are computed and
+ *   copied): txatav, tyatav (nxpa,nypa) | wtatav, fmatav, astav (nxta,nyta) | patav, qatav (nxpa,nypa,nla) |
+ *   uufa, tufa, utufa (nxpa,nyta) | vvfa, tvfa, vtvfa (nxta,nypa) | uptpat (nxpa,nyta) | vptpat (nxta,nypa).  The sums
+ *   are not changed.  *nsumat (may be NULL) = the count.  Synchronous.
+ * qgcm_hip_tavatm_schedule(h, every, phase): while set, qgcm_hip_steps and qgcm_hip_coupled_steps add one contribution
+ *   after every atmospheric step nt with nt % every == phase - after the step's own averaging at mod(nt-1,100) == 0, as
+ *   the reference orders them (src/q-gcm.F:1370-1405 before 1477-1479) - and count it like an explicit call: the result
+ *   is that of qgcm_hip_tavatm between two windows that end at nt.  The reference's cadence is every = ntavat,
+ *   phase = mod(nmidat + nsteps0, ntavat).  Inside a coupled window the forcing is held: a scheduled contribution reads
+ *   the fields as they were last set.  A call whose steps hold a contribution fails before it launches anything when an
+ *   input is missing.  Graph blocks end after scheduled steps; the contribution is launched on the handle's stream
+ *   between replays (never captured) and the step kernels are those of a run without a schedule (qgcm_hip_prepare_steps
+ *   / _time_steps cut in the same places; qgcm_hip_profile_steps counts one k_tavat_accum launch per scheduled step).
+ *   every = 0 removes the schedule (the default: launches and graphs are then exactly those without this feature).
+ *   Refuses every < 0 and phase outside [0, every).
+ * qgcm_hip_atnc_sample_len(h, nska, outflat) (-1 on error) / qgcm_hip_atnc_sample(h, nska, outflat, out): atnc_out's
+ *   fields at the points (1+(i-1)*nska, 1+(j-1)*nska), the selected ones concatenated in its order, each plane with i
+ *   fastest, as the reference hands nf_put_vara_double: ast (itwk, jtwk) | pa (ipwk, jpwk, nla) | qa (ipwk, jpwk, nla) |
+ *   wekta (itwk, jtwk) | ha = (pa(k)-pa(k+1))/gpat(k) (ipwk, jpwk, nla-1) | tauxa, tauya (ipwk, jpwk each) | hmixa
+ *   (itwk, jtwk).  outflat is the reference's 7-flag vector (1 = write; outflat(6) selects tauxa and tauya).  A grid of
+ *   n points has min(mod(n,nska),1) + (n-mod(n,nska))/nska of them.  Refuses nska < 1, a NULL outflat and a selected
+ *   field that was never given (unselected ones need not be set).  Synchronous.
+ * Bitwise the reference's arithmetic (elementwise, uncontracted). */
+#define QGCM_HIP_ATM_TAV_NOUT 15
+int qgcm_hip_set_atm_tav_fields(qgcm_hip_handle h, const double *fnetat);
+int qgcm_hip_tavatm(qgcm_hip_handle h);
+int qgcm_hip_atm_tav_reset(qgcm_hip_handle h);
+int qgcm_hip_atm_tav_out(qgcm_hip_handle h, double *const *fields, int *nsumat);
+int qgcm_hip_tavatm_schedule(qgcm_hip_handle h, int every, int phase);
+long qgcm_hip_atnc_sample_len(qgcm_hip_handle h, int nska, const int *outflat);
+int qgcm_hip_atnc_sample(qgcm_hip_handle h, int nska, const int *outflat, double *out);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

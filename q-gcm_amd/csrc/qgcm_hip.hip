@@ -37,6 +37,7 @@
 #include "k_monitors.h"
 #include "k_atm_monitors.h"
 #include "k_tavg.h"
+#include "k_atm_tavg.h"
 #include "k_qocdiag.h"
 #include "k_setup.h"
 #include "slab_comm.h"
@@ -70,11 +71,11 @@ static thread_local char g_err[512] = "";
     if (e_ != hipSuccess) QG_FAIL("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_COUNT };
+enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_TAVAT, KN_COUNT };
 // (k_oml = k_oml_step, the sst step + raw entrainment; k_oml_entoc = the entrainment on the p grid)
 static const char *kKernelNames[KN_COUNT] = {"k_tend",   "k_cyc_bsums", "k_dst_fwd", "k_thomas", "k_dst_inv",
                                              "k_constr", "k_unpack",  "k_ocqbdy", "k_lf_average", "k_oml", "k_oml_entoc", "k_noop", "k_noop_train",
-                                             "k_poavg_add"};
+                                             "k_poavg_add", "k_tavat_accum"};
 
 // Device copy of the Thomas pivot tables of one set of diagonals (see QgThomasParams / build_pivots).
 struct QgThomasTab {
@@ -196,6 +197,15 @@ struct qgcm_hip_ctx {
     double *sum = nullptr, *mean = nullptr, *fnet = nullptr;
     long n = 0;
   } tav;
+  // the atmosphere's tavatm / tavout and atnc_out (qgcm_hip_tavatm / _atnc_sample, k_atm_tavg.h): sums in the ocean's
+  // layout, means (allocated on first use), fnetat, the dump's result buffer (grown on demand) and the schedule of
+  // qgcm_hip_tavatm_schedule (a contribution after every step nt with nt % every == phase; every = 0: none)
+  struct {
+    double *sum = nullptr, *mean = nullptr, *fnet = nullptr, *buf = nullptr;
+    size_t nbuf = 0;
+    long n = 0;
+    int every = 0, phase = 0;
+  } atav;
   // periodic ocean dumps (qgcm_hip_qocdiag / _ocnc_sample, k_qocdiag.h): device result buffer (grown on demand); the
   // schedule of qgcm_hip_qocdiag_schedule: a ring of `cap` snapshots of `len` doubles, oldest at `head`
   struct {
@@ -401,7 +411,8 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : atmp)
     if (p) hipFree(p);
   if (c->atmon.hout) hipHostFree(c->atmon.hout);
-  double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet, c->qd.buf, c->qd.ring};
+  double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet, c->qd.buf, c->qd.ring,
+                    c->atav.sum, c->atav.mean, c->atav.fnet, c->atav.buf};
   for (double *p : tavp)
     if (p) hipFree(p);
   double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
@@ -2955,6 +2966,235 @@ extern "C" int qgcm_hip_ocnc_sample(qgcm_hip_handle c, int nsko, const int *outf
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// time averages and periodic dump of the atmosphere (k_atm_tavg.h): tavatm, tavout's atmosphere half and
+// atnc_out on a whole-domain atmosphere handle.  The fields xforc / aml leave on the host come from
+// qgcm_hip_set_atm_monitor_fields, hmat from qgcm_hip_set_atm_mon_params, fnetat from qgcm_hip_set_atm_tav_fields.
+// ---------------------------------------------------------------------------
+static int atav_ready(qgcm_hip_ctx *c, const char *who) {
+  if (!c) QG_FAIL("%s: null handle", who);
+  if (!c->g.atm) QG_FAIL("%s: the handle is an ocean (qgcm_hip_tavocn / qgcm_hip_ocnc_sample serve it)", who);
+  if (!c->whole) QG_FAIL("%s: the handle is a y-slab (the atmosphere's diagnostics need the whole domain)", who);
+  return check_ready(c, who);
+}
+
+extern "C" int qgcm_hip_set_atm_tav_fields(qgcm_hip_handle c, const double *fnetat) {
+  if (atav_ready(c, "qgcm_hip_set_atm_tav_fields")) return 1;
+  const QgGeom &g = c->g;
+  auto &m = c->atmon;
+  if (!m.ldt) m.ldt = round_up(g.nxt, 16); // (the pitch of the other T-grid fields, qgcm_hip_set_atm_monitor_fields)
+  if (fnetat) {
+    if (!c->atav.fnet && dalloc(&c->atav.fnet, (size_t)m.ldt * (g.ny - 1))) return 1;
+    if (upload2d(c, c->atav.fnet, m.ldt, fnetat, g.nxt, g.ny - 1)) return 1;
+  }
+  return 0;
+}
+
+// the parameters of one contribution; fails, naming it, when an input was never given.  Allocates the sums.
+static int atav_params(qgcm_hip_ctx *c, QgTavParams &P, const char *who) {
+  if (atav_ready(c, who)) return 1;
+  const auto &m = c->atmon;
+  if (!m.prm_set) QG_FAIL("%s: hmat is missing (qgcm_hip_set_atm_mon_params has not been called)", who);
+  if (!(m.prm.hmat > 0.0)) QG_FAIL("%s: hmat = %g (need > 0, qgcm_hip_set_atm_mon_params)", who, m.prm.hmat);
+  const char *miss = !m.tauxa ? "tauxa" : !m.tauya ? "tauya" : !m.wekta ? "wekta" : !m.ast ? "ast" : nullptr;
+  if (miss) QG_FAIL("%s: %s was never given (qgcm_hip_set_atm_monitor_fields)", who, miss);
+  if (!c->atav.fnet) QG_FAIL("%s: fnetat was never given (qgcm_hip_set_atm_tav_fields)", who);
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  // the time levels qgcm_hip_get_state hands out here: after an averaging step, the averaged ones
+  P.po = c->p[c->ip]; P.qo = c->q[c->iq];
+  P.taux = m.tauxa; P.tauy = m.tauya; P.wekto = m.wekta; P.sst = m.ast; P.fnet = c->atav.fnet; P.ldt = m.ldt;
+  P.jlo = 1; P.jhi = g.ny; P.jt1 = g.ny - 1;
+  P.uvgfac = 1.0 / (pr.dxo * pr.fnot);           // rdxaf0 of MODULE atconst (src/q-gcm.F:392-441)
+  P.rhf0hm = 0.5 / (pr.fnot * m.prm.hmat);       // src/timavge.F:301
+  if (!c->atav.sum) {
+    if (dalloc(&c->atav.sum, (size_t)TAV_NSUM(g.nl) * g.fstride)) return 1;
+    c->atav.n = 0;
+  }
+  P.sum = c->atav.sum;
+  return 0;
+}
+
+// one contribution from the state on the device (asynchronous); counts it
+static int launch_tavatm(qgcm_hip_ctx *c, const char *who) {
+  QgTavParams P;
+  if (atav_params(c, P, who)) return 1;
+  const QgGeom &g = c->g;
+  const dim3 grid((g.nx + TAV_NT - 1) / TAV_NT, g.ny);
+  KTimer t(c, KN_TAVAT);
+#define QG_ATAV(NLV) hipLaunchKernelGGL((k_tavat_accum<NLV>), grid, dim3(TAV_NT), 0, c->stream, P)
+  QG_SWITCH_NL(g.nl, QG_ATAV, "k_tavat_accum");
+#undef QG_ATAV
+  HIPCHECK(hipGetLastError());
+  c->atav.n++; // nsumat = nsumat + 1
+  return 0;
+}
+
+extern "C" int qgcm_hip_tavatm(qgcm_hip_handle c) { return launch_tavatm(c, "qgcm_hip_tavatm"); }
+
+extern "C" int qgcm_hip_atm_tav_reset(qgcm_hip_handle c) {
+  if (atav_ready(c, "qgcm_hip_atm_tav_reset")) return 1;
+  if (c->atav.sum) HIPCHECK(hipMemsetAsync(c->atav.sum, 0, (size_t)TAV_NSUM(c->g.nl) * c->g.fstride * sizeof(double), c->stream));
+  c->atav.n = 0;
+  return 0;
+}
+
+extern "C" int qgcm_hip_atm_tav_out(qgcm_hip_handle c, double *const *fields, int *nsumat) {
+  if (atav_ready(c, "qgcm_hip_atm_tav_out")) return 1;
+  if (nsumat) *nsumat = (int)c->atav.n;
+  if (!fields) return 0;
+  const QgGeom &g = c->g;
+  const int nl = g.nl;
+  // the ABI's 15 outputs -> (first field of the mean buffer, number of fields, p or T rows, columns)
+  struct Out { int f, nf; bool trow; int nx; };
+  const int u = TAV_UU(nl), e = TAV_NSUM(nl);
+  const Out map[QGCM_HIP_ATM_TAV_NOUT] = {{TAV_TX, 1, false, g.nx}, {TAV_TY, 1, false, g.nx},
+                                          {TAV_WT, 1, true, g.nxt}, {TAV_FM, 1, true, g.nxt}, {TAV_SST, 1, true, g.nxt},
+                                          {TAV_P0, nl, false, g.nx}, {TAV_P0 + nl, nl, false, g.nx},
+                                          {u, 1, true, g.nx}, {u + 1, 1, true, g.nx}, {u + 2, 1, true, g.nx},
+                                          {u + 3, 1, false, g.nxt}, {u + 4, 1, false, g.nxt}, {u + 5, 1, false, g.nxt},
+                                          {e, 1, true, g.nx}, {e + 1, 1, false, g.nxt}};
+  unsigned mask = 0;
+  for (int o = 0; o < QGCM_HIP_ATM_TAV_NOUT; ++o)
+    if (fields[o])
+      for (int k = 0; k < map[o].nf; ++k) mask |= 1u << (map[o].f + k);
+  if (!mask) return 0;
+  if (!c->atav.mean && dalloc(&c->atav.mean, (size_t)TAV_NMEAN(nl) * g.fstride)) return 1;
+  if (!c->atav.sum && dalloc(&c->atav.sum, (size_t)TAV_NSUM(nl) * g.fstride)) return 1;
+  QgTavParams P;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.jlo = 1; P.jhi = g.ny; P.jt1 = g.ny - 1;
+  P.sum = c->atav.sum; P.mean = c->atav.mean; P.mask = mask;
+  P.rnsoc = c->atav.n == 0 ? 0.0 : 1.0 / (double)c->atav.n; // rnsat, src/timavge.F:716-720
+  const dim3 grid((g.nx + TAV_NT - 1) / TAV_NT, g.ny);
+#define QG_TAVM(NLV) hipLaunchKernelGGL((k_tav_mean<NLV>), grid, dim3(TAV_NT), 0, c->stream, P)
+  QG_SWITCH_NL(nl, QG_TAVM, "k_tav_mean");
+#undef QG_TAVM
+  HIPCHECK(hipGetLastError());
+  for (int o = 0; o < QGCM_HIP_ATM_TAV_NOUT; ++o)
+    if (fields[o] && download_owned(c, fields[o], c->atav.mean + (size_t)map[o].f * g.fstride, map[o].nx, 1,
+                                    map[o].trow ? g.ny - 1 : g.ny, map[o].nf))
+      return 1;
+  return 0;
+}
+
+// inside qgcm_hip_steps / qgcm_hip_coupled_steps: is step s an accumulation step of the schedule, how many fall on
+// steps s0 .. s0+n-1, and how many steps from s up to and including the next one (n if none comes within n)
+static bool at_due(const qgcm_hip_ctx *c, int s) { return c->atav.every > 0 && s % c->atav.every == c->atav.phase; }
+static long at_count(const qgcm_hip_ctx *c, int s0, int n) {
+  const int e = c->atav.every, ph = c->atav.phase;
+  if (e <= 0 || n <= 0) return 0;
+  auto upto = [e, ph](long x) { return x < ph ? 0L : (x - ph) / e + 1; }; // due steps in 0..x
+  return upto((long)s0 + n - 1) - upto((long)s0 - 1);
+}
+static int at_run(const qgcm_hip_ctx *c, int s, int n) {
+  const int e = c->atav.every;
+  if (e <= 0) return n;
+  const int d = ((c->atav.phase - s % e) % e + e) % e; // steps from s to the next due step
+  return std::min(n, d + 1);
+}
+
+extern "C" int qgcm_hip_tavatm_schedule(qgcm_hip_handle c, int every, int phase) {
+  if (atav_ready(c, "qgcm_hip_tavatm_schedule")) return 1;
+  if (every < 0) QG_FAIL("qgcm_hip_tavatm_schedule: every = %d (need >= 0; 0 removes the schedule)", every);
+  if (every > 0 && (phase < 0 || phase >= every))
+    QG_FAIL("qgcm_hip_tavatm_schedule: phase = %d outside [0, %d)", phase, every);
+  c->atav.every = every;
+  c->atav.phase = every > 0 ? phase : 0;
+  return 0;
+}
+
+// atnc_out's fields in its order (src/nc_subs.F:1133-1322): T grid?, planes, flag index (tauxa, tauya share
+// outflat(6))
+struct AtncField { bool tgrid; int nplanes; };
+static void atnc_fields(const qgcm_hip_ctx *c, const int *outflat, AtncField f[8]) {
+  const int nl = c->g.nl;
+  const AtncField all[8] = {{true, 1}, {false, nl}, {false, nl}, {true, 1}, {false, nl - 1}, {false, 1}, {false, 1}, {true, 1}};
+  static const int flag[8] = {0, 1, 2, 3, 4, 5, 5, 6};
+  for (int n = 0; n < 8; ++n) {
+    f[n] = all[n];
+    if (outflat[flag[n]] != 1) f[n].nplanes = 0;
+  }
+}
+
+static size_t atnc_len(const qgcm_hip_ctx *c, int nska, const int *outflat) {
+  const QgGeom &g = c->g;
+  AtncField f[8];
+  atnc_fields(c, outflat, f);
+  const size_t np = (size_t)qd_count(g.nx, nska) * qd_count(g.ny, nska), nt = (size_t)qd_count(g.nxt, nska) * qd_count(g.ny - 1, nska);
+  size_t n = 0;
+  for (int k = 0; k < 8; ++k) n += (size_t)f[k].nplanes * (f[k].tgrid ? nt : np);
+  return n;
+}
+
+extern "C" long qgcm_hip_atnc_sample_len(qgcm_hip_handle c, int nska, const int *outflat) {
+  if (atav_ready(c, "qgcm_hip_atnc_sample_len")) return -1;
+  if (!outflat) { snprintf(g_err, sizeof(g_err), "qgcm_hip_atnc_sample_len: null argument"); return -1; }
+  if (nska < 1) { snprintf(g_err, sizeof(g_err), "qgcm_hip_atnc_sample_len: nska = %d (need >= 1)", nska); return -1; }
+  return (long)atnc_len(c, nska, outflat);
+}
+
+extern "C" int qgcm_hip_atnc_sample(qgcm_hip_handle c, int nska, const int *outflat, double *out) {
+  if (atav_ready(c, "qgcm_hip_atnc_sample")) return 1;
+  if (!outflat || !out) QG_FAIL("qgcm_hip_atnc_sample: null argument");
+  if (nska < 1) QG_FAIL("qgcm_hip_atnc_sample: nska = %d (need >= 1)", nska);
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  const auto &m = c->atmon;
+  AtncField f[8];
+  atnc_fields(c, outflat, f);
+  const double *fld[8] = {m.ast, nullptr, nullptr, m.wekta, nullptr, m.tauxa, m.tauya, m.hmixa};
+  static const char *names[8] = {"ast", "pa", "qa", "wekta", "ha", "tauxa", "tauya", "hmixa"};
+  for (int k = 0; k < 8; ++k)
+    if (f[k].nplanes && k != 1 && k != 2 && k != 4 && !fld[k])
+      QG_FAIL("qgcm_hip_atnc_sample: %s was never given (qgcm_hip_set_atm_monitor_fields)", names[k]);
+  const size_t n = atnc_len(c, nska, outflat);
+  if (n == 0) return 0;
+  auto &a = c->atav;
+  if (a.nbuf < n) {
+    if (a.buf) {
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      HIPCHECK(hipFree(a.buf));
+      a.buf = nullptr;
+      a.nbuf = 0;
+    }
+    if (dalloc(&a.buf, n)) return 1;
+    a.nbuf = n;
+  }
+  QgAtncParams S;
+  memset(&S, 0, sizeof(S));
+  S.nska = nska;
+  S.out = a.buf;
+  const double *pa = c->p[c->ip], *qa = c->q[c->iq];
+  const int ip = qd_count(g.nx, nska), jp = qd_count(g.ny, nska), it = qd_count(g.nxt, nska), jt = qd_count(g.ny - 1, nska);
+  int z = 0;
+  long off = 0;
+  for (int k = 0; k < 8; ++k)
+    for (int p = 0; p < f[k].nplanes; ++p, ++z) {
+      if (z >= ATNC_MAXP) QG_FAIL("qgcm_hip_atnc_sample: internal: more than %d planes", ATNC_MAXP);
+      const bool t = f[k].tgrid;
+      S.ni[z] = t ? it : ip;
+      S.nj[z] = t ? jt : jp;
+      S.ld[z] = t ? m.ldt : g.ldx;
+      S.off[z] = off;
+      switch (k) {
+        case 1: S.src[z] = pa + p * g.fstride; break;
+        case 2: S.src[z] = qa + p * g.fstride; break;
+        case 4: S.src[z] = pa + p * g.fstride; S.src2[z] = pa + (p + 1) * g.fstride; S.gp[z] = pr.gpoc[p]; break;
+        default: S.src[z] = fld[k]; break;
+      }
+      off += (long)S.ni[z] * S.nj[z];
+    }
+  hipLaunchKernelGGL(k_atnc_sample, dim3((ip + 255) / 256, jp, z), dim3(256), 0, c->stream, S);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(out, a.buf, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 static int launch_poavg(qgcm_hip_ctx *c);
 
 static int one_step(qgcm_hip_ctx *c, int s) {
@@ -3043,6 +3283,7 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
   const long pn0 = c->poavg.n;
   if (qd_dumps(c, s0, B)) QG_FAIL("qgcm_hip_steps: internal: a graph block would hold a dump step"); // (steps_impl cuts)
+  if (at_count(c, s0, B - 1)) QG_FAIL("qgcm_hip_steps: internal: a graph block would hold an accumulation step");
   HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
   for (int s = s0; s < s0 + B && !rc; ++s) rc = one_step(c, s);
@@ -3067,6 +3308,9 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
 // dry = true only instantiates the graphs the run will replay (so that a timed region does not pay for it)
 // With a dump schedule (qgcm_hip_qocdiag_schedule) the graph blocks end before every dump step, and the dump step (and
 // a single step left before one) runs eagerly: the blocks of the other steps are the graphs of a run without one.
+// With an accumulation schedule (qgcm_hip_tavatm_schedule) the graph blocks end after every accumulation step, and the
+// contribution is launched on the stream between two replays (never captured); a single step left before one runs
+// eagerly.  The dry pass cuts in the same places.
 static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
   int s = s0;
   if (!dry && c->qd.every > 0) {
@@ -3075,10 +3319,15 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       QG_FAIL("qgcm_hip_steps: steps %d..%d would record %ld dumps, the ring has room for %d (qgcm_hip_qocdiag_read)",
               s0, s0 + n - 1, d, c->qd.cap - c->qd.count);
   }
+  if (!dry && at_count(c, s0, n) > 0) { // every input of the contributions is there before anything is launched
+    QgTavParams P;
+    if (atav_params(c, P, "qgcm_hip_steps (qgcm_hip_tavatm_schedule)")) return 1;
+  }
   if (!dry) c->graph_call++; // (a dry pass belongs to the call that follows it: qgcm_hip_time_steps, prepare + steps)
   const int is0 = c->oml.is, ism0 = c->oml.ism, ip0 = c->ip, iq0 = c->iq;
   while (n > 0) {
-    const int m = qd_run(c, s, n); // steps before the next dump step
+    // steps before the next dump step; steps up to and including the next accumulation step
+    const int m = std::min(qd_run(c, s, n), at_run(c, s, n));
     if (!c->profiling && m >= 2) {
       const int B = m >= kGraphBlock50 ? kGraphBlock50 : (m & ~1);
       hipGraphExec_t ge;
@@ -3088,12 +3337,15 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       s += B;
       n -= B;
       if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
+      if (!dry && at_due(c, s - 1) && launch_tavatm(c, "qgcm_hip_steps")) return 1; // tavatm after the block's last step
       continue;
     }
-    if (c->qd.every <= 0) break; // no schedule: the tail below
-    // a dump step, or the single step before one: eagerly (a dry pass follows the rotations it would make)
+    if (c->qd.every <= 0 && c->atav.every <= 0) break; // no schedule: the tail below
+    // a dump step, an accumulation step, or the single step before one: eagerly (a dry pass follows the rotations it
+    // would make)
     if (!dry) {
       if (one_step(c, s)) return 1;
+      if (at_due(c, s) && launch_tavatm(c, "qgcm_hip_steps")) return 1; // after the step's averaging (src/q-gcm.F:1477-1479)
     } else {
       c->ip ^= 1;
       c->iq ^= 1;

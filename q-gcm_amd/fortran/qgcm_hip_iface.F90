@@ -409,6 +409,45 @@ module qgcm_hip_iface
       real(c_double), intent(out) :: out(12)
       integer(c_int), intent(out) :: solnok
     end function
+    ! time averages and periodic dump of the atmosphere (tavatm / tavout, atnc_out; DESIGN 6i).  Not called by the
+    ! drop-in, which still pulls the state before tavatm / atnc_out (INTEGRATION.md)
+    integer(c_int) function qgcm_hip_set_atm_tav_fields(h, fnetat) bind(C, name='qgcm_hip_set_atm_tav_fields')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(in) :: fnetat(*)
+    end function
+    integer(c_int) function qgcm_hip_tavatm(h) bind(C, name='qgcm_hip_tavatm')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_atm_tav_reset(h) bind(C, name='qgcm_hip_atm_tav_reset')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_atm_tav_out(h, fields, nsumat) bind(C, name='qgcm_hip_atm_tav_out')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      type(c_ptr), intent(in) :: fields(15)
+      integer(c_int), intent(out) :: nsumat
+    end function
+    integer(c_int) function qgcm_hip_tavatm_schedule(h, every, phase) bind(C, name='qgcm_hip_tavatm_schedule')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: every, phase
+    end function
+    integer(c_long) function qgcm_hip_atnc_sample_len(h, nska, outflat) bind(C, name='qgcm_hip_atnc_sample_len')
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: h
+      integer(c_int), value :: nska
+      integer(c_int), intent(in) :: outflat(7)
+    end function
+    integer(c_int) function qgcm_hip_atnc_sample(h, nska, outflat, out) bind(C, name='qgcm_hip_atnc_sample')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: nska
+      integer(c_int), intent(in) :: outflat(7)
+      real(c_double), intent(out) :: out(*)
+    end function
   end interface
 
 contains

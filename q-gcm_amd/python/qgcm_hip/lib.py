@@ -67,6 +67,7 @@ class TavParams(C.Structure):
 
 
 TAV_NOUT = 16  # QGCM_HIP_TAV_NOUT
+ATM_TAV_NOUT = 15  # QGCM_HIP_ATM_TAV_NOUT
 
 
 # every symbol include/qgcm_hip.h declares
@@ -97,6 +98,8 @@ SYMBOLS = [
     "qgcm_hip_tavocn", "qgcm_hip_tav_reset", "qgcm_hip_tav_out",
     "qgcm_hip_qocdiag_len", "qgcm_hip_qocdiag", "qgcm_hip_qocdiag_schedule", "qgcm_hip_qocdiag_read",
     "qgcm_hip_ocnc_sample_len", "qgcm_hip_ocnc_sample", "qgcm_hip_subsample_rows",
+    "qgcm_hip_set_atm_tav_fields", "qgcm_hip_tavatm", "qgcm_hip_atm_tav_reset", "qgcm_hip_atm_tav_out",
+    "qgcm_hip_tavatm_schedule", "qgcm_hip_atnc_sample_len", "qgcm_hip_atnc_sample",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -213,6 +216,14 @@ def load_library():
     L.qgcm_hip_ocnc_sample_len.restype = C.c_long
     L.qgcm_hip_ocnc_sample.argtypes = [vp, C.c_int, ip, dp]
     L.qgcm_hip_subsample_rows.argtypes = [vp, C.c_int, ip, ip, ip, ip]
+    L.qgcm_hip_set_atm_tav_fields.argtypes = [vp, dp]
+    L.qgcm_hip_tavatm.argtypes = [vp]
+    L.qgcm_hip_atm_tav_reset.argtypes = [vp]
+    L.qgcm_hip_atm_tav_out.argtypes = [vp, C.POINTER(dp), ip]
+    L.qgcm_hip_tavatm_schedule.argtypes = [vp, C.c_int, C.c_int]
+    L.qgcm_hip_atnc_sample_len.argtypes = [vp, C.c_int, ip]
+    L.qgcm_hip_atnc_sample_len.restype = C.c_long
+    L.qgcm_hip_atnc_sample.argtypes = [vp, C.c_int, ip, dp]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

@@ -225,6 +225,60 @@ def read_ocnc(L, h, cfg, nsko, outfloc):
     return res
 
 
+# the atmosphere's time averages and dump (qgcm_hip_atm_tav_out / qgcm_hip_atnc_sample): outputs of
+# qgcm_hip_atm_tav_out in ABI order (names of MODULE timavge / tavout) and their grids, as TAV_LAYOUT:
+# p = (nxpa, nypa), t = (nxta, nyta), p3 = (nxpa, nypa, nla), u = (nxpa, nyta), v = (nxta, nypa)
+ATM_TAV_LAYOUT = (("txatav", "p"), ("tyatav", "p"), ("wtatav", "t"), ("fmatav", "t"), ("astav", "t"), ("patav", "p3"),
+                  ("qatav", "p3"), ("uufa", "u"), ("tufa", "u"), ("utufa", "u"), ("vvfa", "v"), ("tvfa", "v"),
+                  ("vtvfa", "v"), ("uptpat", "u"), ("vptpat", "v"))
+# atnc_out's fields in its order: (name, grid, planes in units of nla: 0 = one plane, 1 = nla, -1 = nla-1, flag index)
+# (tauxa and tauya share outflat(6))
+ATNC_FIELDS = (("ast", "t", 0, 0), ("pa", "p", 1, 1), ("qa", "p", 1, 2), ("wekta", "t", 0, 3), ("ha", "p", -1, 4),
+               ("tauxa", "p", 0, 5), ("tauya", "p", 0, 5), ("hmixa", "t", 0, 6))
+
+
+def read_atm_time_means(L, h, acfg, names=None):
+    """qgcm_hip_atm_tav_out for the given names (None = all): (dict name -> array, nsumat)."""
+    from .lib import ATM_TAV_NOUT
+    nxp, nyp, nl = acfg.nxpa, acfg.nypa, acfg.nla
+    shape = dict(p=(nxp, nyp), t=(nxp - 1, nyp - 1), p3=(nxp, nyp, nl), u=(nxp, nyp - 1), v=(nxp - 1, nyp))
+    want = [n for n, _ in ATM_TAV_LAYOUT] if names is None else list(names)
+    unknown = set(want) - set(n for n, _ in ATM_TAV_LAYOUT)
+    if unknown:
+        raise QgcmHipError("unknown time means %s (ATM_TAV_LAYOUT)" % sorted(unknown))
+    out, ptrs = {}, (C.POINTER(C.c_double) * ATM_TAV_NOUT)()
+    for i, (name, grid) in enumerate(ATM_TAV_LAYOUT):
+        if name in want:
+            out[name] = np.zeros(shape[grid], order="F")
+            ptrs[i] = _dp(out[name])
+    n = C.c_int()
+    check(L.qgcm_hip_atm_tav_out(h, ptrs, C.byref(n)))
+    return out, n.value
+
+
+def read_atnc(L, h, acfg, nska, outflat):
+    """atnc_out's selected fields: dict name -> array (planes, rows, columns) (one plane for the 2-d fields)."""
+    fl = (C.c_int * 7)(*[int(x) for x in outflat])
+    n = L.qgcm_hip_atnc_sample_len(h, int(nska), fl)
+    if n < 0:
+        check(1)
+    out = np.zeros(n)
+    check(L.qgcm_hip_atnc_sample(h, int(nska), fl, _dp(out)))
+    nl = acfg.nla
+    cnt = dict(p=(subsample_count(acfg.nypa, nska), subsample_count(acfg.nxpa, nska)),
+               t=(subsample_count(acfg.nypa - 1, nska), subsample_count(acfg.nxpa - 1, nska)))
+    res, o = {}, 0
+    for name, grid, planes, flag in ATNC_FIELDS:
+        if int(outflat[flag]) != 1:
+            continue
+        shp = ({0: 1, 1: nl, -1: nl - 1}[planes],) + cnt[grid]
+        m = int(np.prod(shp))
+        res[name] = out[o:o + m].reshape(shp)
+        o += m
+    assert o == n
+    return res
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -704,6 +758,40 @@ class AtmosModel(OceanModel):
         ok = C.c_int()
         check(self.L.qgcm_hip_atm_valids(self.h, _dp(out), C.byref(ok)))
         return bool(ok.value), out
+
+    # -- time averages and periodic dump (tavatm / tavout's atmosphere half, atnc_out) ---------------------
+    # (tavocn() stays the ocean's and refuses this handle)
+    def set_time_mean_fields(self, fnetat=None):
+        """fnetat (nxta, nyta) that tavatm sums (MODULE intrfac).  None = leave unchanged."""
+        check(self.L.qgcm_hip_set_atm_tav_fields(self.h, _dp(_f(fnetat))))
+
+    def tavatm(self):
+        """One tavatm contribution from the device state (src/timavge.F:278-421); tauxa, tauya, wekta, ast come from
+        set_atm_monitor_fields, hmat from set_atm_monitor_params, fnetat from set_time_mean_fields."""
+        check(self.L.qgcm_hip_tavatm(self.h))
+
+    def time_means(self, names=None):
+        """tavout's atmosphere means (src/timavge.F:715-801) keyed by the reference's names (ATM_TAV_LAYOUT), plus
+        "nsumat".  The sums are not changed.  names: the subset to compute and copy (None = all)."""
+        out, n = read_atm_time_means(self.L, self.h, self.cfg, names)
+        out["nsumat"] = n
+        return out
+
+    def reset_time_means(self):
+        """tavini's atmosphere half: zero the sums and the count."""
+        check(self.L.qgcm_hip_atm_tav_reset(self.h))
+
+    def schedule_time_means(self, every, phase=0):
+        """Add a tavatm contribution inside steps() / coupled_steps() after every step nt with nt % every == phase
+        (after the step's averaging); the reference's cadence is every = ntavat, phase = (nmidat + nsteps0) % ntavat.
+        every = 0 removes the schedule."""
+        check(self.L.qgcm_hip_tavatm_schedule(self.h, int(every), int(phase)))
+
+    def atmos_dump(self, nska=1, outflat=(1, 1, 1, 1, 1, 1, 1)):
+        """atnc_out's subsampled fields (the selected ones): ast, wekta, hmixa (jtwk, itwk); tauxa, tauya (jpwk, ipwk);
+        pa, qa (nla, jpwk, ipwk); ha = (pa(k)-pa(k+1))/gpat(k) (nla-1, jpwk, ipwk)."""
+        r = read_atnc(self.L, self.h, self.cfg, nska, outflat)
+        return {k: (v if k in ("pa", "qa", "ha") else v[0]) for k, v in r.items()}
 
     pa = OceanModel.po
     pam = OceanModel.pom
