@@ -590,6 +590,53 @@ int qgcm_hip_tavatm_schedule(qgcm_hip_handle h, int every, int phase);
 long qgcm_hip_atnc_sample_len(qgcm_hip_handle h, int nska, const int *outflat);
 int qgcm_hip_atnc_sample(qgcm_hip_handle h, int nska, const int *outflat, double *out);
 
+/* ---- covariance matrices ---------------------------------------------------------------------------------
+ * covini / covocn / covatm of src/covaria_diag.F (-Dget_covar) on the handle's fluid: an ocean handle subsamples
+ * po(:,:,1) with psampl and sst with tsampl (covocn), an atmosphere handle pa(:,:,1) and ast (covatm); each vector then
+ * goes through dssp (Algorithm AS 41, wt = 1): mean update and rank-1 update of a packed lower triangle of
+ * nmat = nvar(nvar+1)/2 entries, nvar = (nxt/nsi)*(nyt/nsi).  Packed index k = i(i+1)/2 + j (0-based, j <= i), the
+ * reference's i(i-1)/2 + j less one.  Lengths and indices are 64-bit.  Bitwise the reference's arithmetic.
+ * qgcm_hip_cov_init(h, nsi, rank, nranks): covini for this handle: allocates and zeroes two matrices (only the packed
+ *   rows this rank holds), two means and the counts.  nsi = 0 frees everything (the schedule too).  Refuses nsi < 2 and
+ *   an nsi that does not divide nxto and nyto (nxta, nyta), the rule of src/parameters_data.F:126-127.  A whole-domain
+ *   handle is rank 0 of 1; rank r of nranks y-slabs holds matrix rows [i_r, i_{r+1}), i_r the smallest i with
+ *   i(i+1)/2 >= floor(r*nmat/nranks) (whole rows, balanced by element count; together they tile [0, nmat)).  A failed
+ *   allocation fails with its byte count.  QGCM_HIP_COV_NT=1 in the environment at this call selects non-temporal
+ *   loads and stores in the rank-1 update (the same numbers).
+ * qgcm_hip_cov_size(h, &nvar, &nmat, &k0, &k1): the sizes and the packed range [k0, k1) this handle holds (NULL = skip).
+ * qgcm_hip_cov_add(h): one covocn / covatm (whole-domain handles) from the state at the time levels
+ *   qgcm_hip_get_state returns; sst comes from the device mixed layer when it is on, else from
+ *   qgcm_hip_set_monitor_fields; ast from qgcm_hip_set_atm_monitor_fields.  Fails, naming the field, when one was never
+ *   given.  Asynchronous.
+ * qgcm_hip_cov_reset(h): covini again on the same sizes (matrices, means and counts to zero).
+ * qgcm_hip_cov_out(h, which, avg, swt, nunit, k0, count, cov): which = 0: p (avgpo / swtpo / nupo / covpo, or the
+ *   atmosphere's pa names), 1: T (sst / ast).  avg (nvar), swt, nunit and the packed entries k0 .. k0+count-1 (must lie
+ *   in this handle's range) into cov; any pointer may be NULL.  Synchronous.
+ * qgcm_hip_cov_schedule(h, every, phase): while set, qgcm_hip_steps and qgcm_hip_coupled_steps add one contribution
+ *   after every step s with s % every == phase, after the step's averaging and after a scheduled tavatm contribution of
+ *   the same step (src/q-gcm.F:1477-1489).  The reference's cadence: atmosphere (steps nt) every = ntcovat,
+ *   phase = mod(nsteps0, ntcovat); ocean (ocean steps s, nt = 1 + (s-1)*nstr, in plain and coupled windows alike)
+ *   every = ntcovoc/nstr, phase = mod((nsteps0 + nstr - 1)/nstr, every): covocn at nt reads the state of the last
+ *   ocean step at or before nt.  Graph blocks end after scheduled steps; the contribution is launched between replays
+ *   (never captured), and qgcm_hip_profile_steps counts one "k_cov" per contribution.  every = 0 removes the schedule
+ *   (launches and graphs are then exactly those without this feature).  A window whose steps hold a contribution fails
+ *   before it launches anything when an input is missing.  Refuses y-slab handles, every < 0 and phase outside
+ *   [0, every).
+ * y-slabs: qgcm_hip_cov_part_len(h) (-1 on error) = doubles of one rank's row sums (the same on every rank);
+ *   qgcm_hip_cov_part(h, send_dev) writes this rank's row sums (asynchronous); after an all-gather of the parts in
+ *   rank order, qgcm_hip_cov_combine(h, gath_dev, nranks) forms the whole-domain vectors and means on every rank
+ *   (bitwise those of a whole-domain handle) and updates the rows this rank holds.  It waits for the combine and fails
+ *   when the gathered row ranges do not tile the rows. */
+int qgcm_hip_cov_init(qgcm_hip_handle h, int nsi, int rank, int nranks);
+int qgcm_hip_cov_size(qgcm_hip_handle h, long *nvar, long *nmat, long *k0, long *k1);
+int qgcm_hip_cov_add(qgcm_hip_handle h);
+int qgcm_hip_cov_reset(qgcm_hip_handle h);
+int qgcm_hip_cov_out(qgcm_hip_handle h, int which, double *avg, double *swt, long *nunit, long k0, long count, double *cov);
+int qgcm_hip_cov_schedule(qgcm_hip_handle h, int every, int phase);
+long qgcm_hip_cov_part_len(qgcm_hip_handle h);
+int qgcm_hip_cov_part(qgcm_hip_handle h, double *send_dev);
+int qgcm_hip_cov_combine(qgcm_hip_handle h, const double *gath_dev, int nranks);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

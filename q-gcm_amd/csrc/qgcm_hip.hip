@@ -38,6 +38,7 @@
 #include "k_atm_monitors.h"
 #include "k_tavg.h"
 #include "k_atm_tavg.h"
+#include "k_cov.h"
 #include "k_qocdiag.h"
 #include "k_setup.h"
 #include "slab_comm.h"
@@ -71,11 +72,11 @@ static thread_local char g_err[512] = "";
     if (e_ != hipSuccess) QG_FAIL("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_TAVAT, KN_COUNT };
+enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_TAVAT, KN_COV, KN_COUNT };
 // (k_oml = k_oml_step, the sst step + raw entrainment; k_oml_entoc = the entrainment on the p grid)
 static const char *kKernelNames[KN_COUNT] = {"k_tend",   "k_cyc_bsums", "k_dst_fwd", "k_thomas", "k_dst_inv",
                                              "k_constr", "k_unpack",  "k_ocqbdy", "k_lf_average", "k_oml", "k_oml_entoc", "k_noop", "k_noop_train",
-                                             "k_poavg_add", "k_tavat_accum"};
+                                             "k_poavg_add", "k_tavat_accum", "k_cov"};
 
 // Device copy of the Thomas pivot tables of one set of diagonals (see QgThomasParams / build_pivots).
 struct QgThomasTab {
@@ -206,6 +207,19 @@ struct qgcm_hip_ctx {
     long n = 0;
     int every = 0, phase = 0;
   } atav;
+  // covariance matrices (qgcm_hip_cov_*, k_cov.h): covini's state for the handle's fluid - the packed rows [k0, k1)
+  // of the p and T matrices this handle holds, both means, the deviation vectors, this handle's row-sum part, the
+  // counts nunit / sumwt of dssp (host), the combine's status word and the schedule of qgcm_hip_cov_schedule
+  struct {
+    int nsi = 0, nbx = 0, nby = 0, nvar = 0, every = 0, phase = 0;
+    bool nt = false; // non-temporal loads / stores in k_cov_rank1 (matrices past the Infinity Cache, QGCM_HIP_COV_NT)
+    long nmat = 0, k0 = 0, k1 = 0, part_len = 0;
+    double *mat[2] = {nullptr, nullptr}, *mean[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};
+    double *part = nullptr;
+    int *status = nullptr;
+    long nu[2] = {0, 0};
+    double swt[2] = {0.0, 0.0};
+  } cov;
   // periodic ocean dumps (qgcm_hip_qocdiag / _ocnc_sample, k_qocdiag.h): device result buffer (grown on demand); the
   // schedule of qgcm_hip_qocdiag_schedule: a ring of `cap` snapshots of `len` doubles, oldest at `head`
   struct {
@@ -412,9 +426,12 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
     if (p) hipFree(p);
   if (c->atmon.hout) hipHostFree(c->atmon.hout);
   double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet, c->qd.buf, c->qd.ring,
-                    c->atav.sum, c->atav.mean, c->atav.fnet, c->atav.buf};
+                    c->atav.sum, c->atav.mean, c->atav.fnet, c->atav.buf,
+                    c->cov.mat[0], c->cov.mat[1], c->cov.mean[0], c->cov.mean[1], c->cov.dev[0], c->cov.dev[1],
+                    c->cov.part};
   for (double *p : tavp)
     if (p) hipFree(p);
+  if (c->cov.status) hipFree(c->cov.status);
   double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
                    c->oml.taux, c->oml.tauy, c->oml.partA, c->oml.partB, c->oml.diag};
   for (double *p : omp)
@@ -3083,19 +3100,24 @@ extern "C" int qgcm_hip_atm_tav_out(qgcm_hip_handle c, double *const *fields, in
 
 // inside qgcm_hip_steps / qgcm_hip_coupled_steps: is step s an accumulation step of the schedule, how many fall on
 // steps s0 .. s0+n-1, and how many steps from s up to and including the next one (n if none comes within n)
-static bool at_due(const qgcm_hip_ctx *c, int s) { return c->atav.every > 0 && s % c->atav.every == c->atav.phase; }
-static long at_count(const qgcm_hip_ctx *c, int s0, int n) {
-  const int e = c->atav.every, ph = c->atav.phase;
+// (sched_*: the same for any schedule (every, phase); cv_*: the covariance schedule of qgcm_hip_cov_schedule)
+static bool sched_due(int e, int ph, int s) { return e > 0 && s % e == ph; }
+static long sched_count(int e, int ph, int s0, int n) {
   if (e <= 0 || n <= 0) return 0;
   auto upto = [e, ph](long x) { return x < ph ? 0L : (x - ph) / e + 1; }; // due steps in 0..x
   return upto((long)s0 + n - 1) - upto((long)s0 - 1);
 }
-static int at_run(const qgcm_hip_ctx *c, int s, int n) {
-  const int e = c->atav.every;
+static int sched_run(int e, int ph, int s, int n) {
   if (e <= 0) return n;
-  const int d = ((c->atav.phase - s % e) % e + e) % e; // steps from s to the next due step
+  const int d = ((ph - s % e) % e + e) % e; // steps from s to the next due step
   return std::min(n, d + 1);
 }
+static bool at_due(const qgcm_hip_ctx *c, int s) { return sched_due(c->atav.every, c->atav.phase, s); }
+static long at_count(const qgcm_hip_ctx *c, int s0, int n) { return sched_count(c->atav.every, c->atav.phase, s0, n); }
+static int at_run(const qgcm_hip_ctx *c, int s, int n) { return sched_run(c->atav.every, c->atav.phase, s, n); }
+static bool cv_due(const qgcm_hip_ctx *c, int s) { return sched_due(c->cov.every, c->cov.phase, s); }
+static long cv_count(const qgcm_hip_ctx *c, int s0, int n) { return sched_count(c->cov.every, c->cov.phase, s0, n); }
+static int cv_run(const qgcm_hip_ctx *c, int s, int n) { return sched_run(c->cov.every, c->cov.phase, s, n); }
 
 extern "C" int qgcm_hip_tavatm_schedule(qgcm_hip_handle c, int every, int phase) {
   if (atav_ready(c, "qgcm_hip_tavatm_schedule")) return 1;
@@ -3195,6 +3217,294 @@ extern "C" int qgcm_hip_atnc_sample(qgcm_hip_handle c, int nska, const int *outf
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// covariance matrices (k_cov.h): covini / covocn / covatm of src/covaria_diag.F for the handle's fluid
+// (an ocean handle: po and sst, covocn; an atmosphere handle: pa and ast, covatm).  The matrices are split across
+// y-slab ranks by whole matrix rows; a whole-domain handle holds them all.
+// ---------------------------------------------------------------------------
+static void cov_free(qgcm_hip_ctx *c) {
+  auto &v = c->cov;
+  double *f[] = {v.mat[0], v.mat[1], v.mean[0], v.mean[1], v.dev[0], v.dev[1], v.part};
+  for (double *p : f)
+    if (p) hipFree(p);
+  if (v.status) hipFree(v.status);
+  v = {}; // (the schedule goes with the matrices)
+}
+
+// n doubles, zeroed; a failure names the bytes
+static int cov_alloc(double **p, size_t n, const char *what) {
+  const size_t bytes = n * sizeof(double);
+  if (hipMalloc((void **)p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    QG_FAIL("qgcm_hip_cov_init: allocating %s (%zu bytes, %.2f GB) failed", what, bytes, bytes / 1e9);
+  }
+  HIPCHECK(hipMemset(*p, 0, bytes));
+  HIPCHECK(hipStreamSynchronize(nullptr)); // (the fill runs on the null stream: see dalloc)
+  return 0;
+}
+
+static int cov_ready(qgcm_hip_ctx *c, const char *who) {
+  if (check_ready(c, who)) return 1;
+  if (c->cov.nsi == 0) QG_FAIL("%s: the covariances are off (qgcm_hip_cov_init)", who);
+  return 0;
+}
+
+// the first packed row of rank r's share: the smallest i with i(i+1)/2 >= r*nmat/nranks (whole rows, balanced by
+// element count; rank 0 starts at 0, rank nranks ends at nvar)
+static long cov_row_split(long nvar, int r, int nranks) {
+  const long nmat = nvar * (nvar + 1) / 2;
+  const long t = (long)((__int128)nmat * r / nranks);
+  long i = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while (i > 0 && (i - 1) * i / 2 >= t) --i;
+  while (i * (i + 1) / 2 < t) ++i;
+  return i;
+}
+
+extern "C" int qgcm_hip_cov_init(qgcm_hip_handle c, int nsi, int rank, int nranks) {
+  if (check_ready(c, "qgcm_hip_cov_init")) return 1;
+  const QgGeom &g = c->g;
+  if (nsi == 0) {
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    cov_free(c);
+    return 0;
+  }
+  const int nyt = g.nyg - 1;
+  if (nsi < 2 || g.nxt % nsi != 0 || nyt % nsi != 0)
+    QG_FAIL("qgcm_hip_cov_init: nsi = %d must be >= 2 and divide %s = %d and %s = %d (src/parameters_data.F:126-127)",
+            nsi, g.atm ? "nxta" : "nxto", g.nxt, g.atm ? "nyta" : "nyto", nyt);
+  if (nsi > COV_MAXNSI) QG_FAIL("qgcm_hip_cov_init: nsi = %d exceeds the row-sum kernel's %d", nsi, COV_MAXNSI);
+  if (nranks < 1 || rank < 0 || rank >= nranks) QG_FAIL("qgcm_hip_cov_init: rank %d of %d", rank, nranks);
+  if (c->whole && nranks != 1)
+    QG_FAIL("qgcm_hip_cov_init: a whole-domain handle holds the whole matrices (rank 0 of 1, not %d of %d)", rank, nranks);
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  cov_free(c);
+  auto &v = c->cov;
+  v.nbx = g.nxt / nsi;
+  v.nby = nyt / nsi;
+  v.nvar = v.nbx * v.nby;
+  v.nmat = (long)v.nvar * (v.nvar + 1) / 2;
+  const long i0 = cov_row_split(v.nvar, rank, nranks), i1 = cov_row_split(v.nvar, rank + 1, nranks);
+  v.k0 = i0 * (i0 + 1) / 2;
+  v.k1 = i1 * (i1 + 1) / 2;
+  v.part_len = COV_HDR + (long)(g.nyg + nyt) * v.nbx; // the whole domain's rows: any slab's fit
+  const size_t nm = (size_t)((v.k1 - v.k0 + 1) & ~1L); // even: k_cov_rank1 moves pairs
+  // non-temporal loads / stores when the two matrices cannot stay in the 256 MiB Infinity Cache between contributions
+  // (measured faster at SOcn 5 km and 385 x 97, slower at NAtl 5 km); QGCM_HIP_COV_NT=0 / 1 forces
+  const char *env = getenv("QGCM_HIP_COV_NT");
+  v.nt = (env && (env[0] == '0' || env[0] == '1')) ? env[0] == '1' : 2.0 * 8.0 * (double)(v.k1 - v.k0) > 256.0 * (1 << 20);
+  int rc = 0;
+  for (int w = 0; w < 2 && !rc; ++w)
+    rc = (nm && cov_alloc(&v.mat[w], nm, w ? "the T covariance matrix" : "the p covariance matrix")) ||
+         cov_alloc(&v.mean[w], v.nvar, "a mean") || cov_alloc(&v.dev[w], v.nvar, "a deviation vector");
+  if (!rc) rc = cov_alloc(&v.part, v.part_len, "the row sums");
+  if (!rc && hipMalloc((void **)&v.status, sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    v.status = nullptr;
+    snprintf(g_err, sizeof(g_err), "qgcm_hip_cov_init: allocating the status word failed");
+    rc = 1;
+  }
+  if (rc) {
+    char keep[sizeof(g_err)];
+    memcpy(keep, g_err, sizeof(keep));
+    cov_free(c);
+    memcpy(g_err, keep, sizeof(keep));
+    return 1;
+  }
+  v.nsi = nsi;
+  return 0;
+}
+
+extern "C" int qgcm_hip_cov_size(qgcm_hip_handle c, long *nvar, long *nmat, long *k0, long *k1) {
+  if (cov_ready(c, "qgcm_hip_cov_size")) return 1;
+  const auto &v = c->cov;
+  if (nvar) *nvar = v.nvar;
+  if (nmat) *nmat = v.nmat;
+  if (k0) *k0 = v.k0;
+  if (k1) *k1 = v.k1;
+  return 0;
+}
+
+extern "C" int qgcm_hip_cov_reset(qgcm_hip_handle c) {
+  if (cov_ready(c, "qgcm_hip_cov_reset")) return 1;
+  auto &v = c->cov;
+  const size_t nm = (size_t)((v.k1 - v.k0 + 1) & ~1L);
+  for (int w = 0; w < 2; ++w) {
+    if (nm) HIPCHECK(hipMemsetAsync(v.mat[w], 0, nm * sizeof(double), c->stream));
+    HIPCHECK(hipMemsetAsync(v.mean[w], 0, (size_t)v.nvar * sizeof(double), c->stream));
+    v.nu[w] = 0;
+    v.swt[w] = 0.0;
+  }
+  return 0;
+}
+
+// the T field a contribution reads (nullptr: missing, named in g_err)
+static const double *cov_tfield(qgcm_hip_ctx *c, int *ldt, const char *who) {
+  if (c->g.atm) {
+    if (!c->atmon.ast) { snprintf(g_err, sizeof(g_err), "%s: ast was never given (qgcm_hip_set_atm_monitor_fields)", who); return nullptr; }
+    *ldt = c->atmon.ldt;
+    return c->atmon.ast;
+  }
+  if (c->oml.on) {
+    *ldt = c->oml.ldt;
+    return c->oml.sst[c->oml.is];
+  }
+  if (!c->mon.sst) {
+    snprintf(g_err, sizeof(g_err), "%s: sst was never given (qgcm_hip_set_monitor_fields) and the mixed layer is off", who);
+    return nullptr;
+  }
+  *ldt = c->mon.ldt;
+  return c->mon.sst;
+}
+
+// everything a scheduled contribution needs is there (checked before a window launches anything)
+static int cov_inputs(qgcm_hip_ctx *c, const char *who) {
+  if (cov_ready(c, who)) return 1;
+  int ldt = 0;
+  return cov_tfield(c, &ldt, who) ? 0 : 1;
+}
+
+// this handle's row sums into out (part_len doubles, device); fails, naming it, when the T field is missing
+static int launch_cov_rowsums(qgcm_hip_ctx *c, double *out, const char *who) {
+  if (cov_ready(c, who)) return 1;
+  const QgGeom &g = c->g;
+  QgCovRowParams R;
+  memset(&R, 0, sizeof(R));
+  if (!(R.t = cov_tfield(c, &R.ldt, who))) return 1;
+  R.p = c->p[c->ip]; // layer 1 at the time level qgcm_hip_get_state hands out
+  R.ldx = g.ldx;
+  R.nsi = c->cov.nsi;
+  R.nbx = c->cov.nbx;
+  R.jp0 = g.jlo;
+  R.nrp = g.jhi - g.jlo + 1;
+  R.jt0 = g.jlo;
+  R.nrt = owned_t1(g) - g.jlo + 1;
+  R.joff = g.joff;
+  R.out = out;
+  hipLaunchKernelGGL(k_cov_rowsums, dim3((R.nbx + COV_RNT - 1) / COV_RNT, R.nrp + R.nrt), dim3(COV_RNT), 0, c->stream, R);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// dssp on both vectors from the gathered parts: the combine (mean update, deviations), then the rank-1 update of the
+// rows this handle holds.  check: wait for the combine and fail when the parts do not tile the rows.
+static int cov_update(qgcm_hip_ctx *c, const double *gath, int nranks, bool check, const char *who) {
+  auto &v = c->cov;
+  const QgGeom &g = c->g;
+  QgCovCombParams Q;
+  memset(&Q, 0, sizeof(Q));
+  Q.gath = gath;
+  Q.part_len = v.part_len;
+  Q.nranks = nranks;
+  Q.nsi = v.nsi;
+  Q.nbx = v.nbx;
+  Q.nby = v.nby;
+  Q.nyp = g.nyg;
+  Q.nyt = g.nyg - 1;
+  Q.status = v.status;
+  const double wt = 1.0; // covocn / covatm call dssp with wt = 1.0d0
+  long nu[2];
+  double swt[2];
+  QgCovR1Params R;
+  memset(&R, 0, sizeof(R));
+  for (int w = 0; w < 2; ++w) {
+    nu[w] = v.nu[w] + 1;    // nunit = nunit+1
+    swt[w] = v.swt[w] + wt; // sumwt = sumwt+wt
+    Q.b[w] = wt / swt[w];   // b = wt/sumwt
+    Q.first[w] = nu[w] == 1;
+    Q.mean[w] = v.mean[w];
+    Q.dev[w] = v.dev[w];
+    R.m[w] = v.mat[w];
+    R.d[w] = v.dev[w];
+    R.c[w] = wt - Q.b[w] * wt; // c = wt - b*wt
+  }
+  KTimer t(c, KN_COV);
+  hipLaunchKernelGGL(k_cov_combine, dim3((2 * v.nvar + COV_NT - 1) / COV_NT), dim3(COV_NT), 0, c->stream, Q);
+  HIPCHECK(hipGetLastError());
+  if (check) {
+    int st = 0;
+    HIPCHECK(hipMemcpyAsync(&st, v.status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (st)
+      QG_FAIL("%s: the gathered row sums do not tile p rows 1..%d and T rows 1..%d (rank %d of %d does not continue them)",
+              who, g.nyg, g.nyg - 1, st - 1, nranks);
+  }
+  // nunit == 1: the matrix is zero (covini / reset) and stays so; later samples update the rows held here
+  R.k0 = v.k0;
+  R.n = v.k1 - v.k0;
+  if (nu[0] > 1 && R.n > 0) {
+    const dim3 grid((unsigned)((R.n + COV_TILE - 1) / COV_TILE));
+    if (v.nt) hipLaunchKernelGGL((k_cov_rank1<true>), grid, dim3(COV_NT), 0, c->stream, R);
+    else hipLaunchKernelGGL((k_cov_rank1<false>), grid, dim3(COV_NT), 0, c->stream, R);
+    HIPCHECK(hipGetLastError());
+  }
+  for (int w = 0; w < 2; ++w) {
+    v.nu[w] = nu[w];
+    v.swt[w] = swt[w];
+  }
+  return 0;
+}
+
+// one covocn / covatm from the device state (whole-domain handle; asynchronous)
+static int launch_cov(qgcm_hip_ctx *c, const char *who) {
+  if (cov_ready(c, who)) return 1;
+  if (!c->whole) QG_FAIL("%s: the handle is a y-slab (qgcm_hip_cov_part / _combine serve it)", who);
+  if (launch_cov_rowsums(c, c->cov.part, who)) return 1;
+  return cov_update(c, c->cov.part, 1, false, who);
+}
+
+extern "C" int qgcm_hip_cov_add(qgcm_hip_handle c) { return launch_cov(c, "qgcm_hip_cov_add"); }
+
+extern "C" long qgcm_hip_cov_part_len(qgcm_hip_handle c) {
+  if (cov_ready(c, "qgcm_hip_cov_part_len")) return -1;
+  return c->cov.part_len;
+}
+
+extern "C" int qgcm_hip_cov_part(qgcm_hip_handle c, double *send_dev) {
+  if (cov_ready(c, "qgcm_hip_cov_part")) return 1;
+  if (!send_dev) QG_FAIL("qgcm_hip_cov_part: null argument");
+  return launch_cov_rowsums(c, send_dev, "qgcm_hip_cov_part");
+}
+
+extern "C" int qgcm_hip_cov_combine(qgcm_hip_handle c, const double *gath_dev, int nranks) {
+  if (cov_ready(c, "qgcm_hip_cov_combine")) return 1;
+  if (!gath_dev || nranks < 1 || nranks > COV_MAXR)
+    QG_FAIL("qgcm_hip_cov_combine: need the gathered row sums and 1 <= nranks <= %d (not %d)", COV_MAXR, nranks);
+  return cov_update(c, gath_dev, nranks, true, "qgcm_hip_cov_combine");
+}
+
+extern "C" int qgcm_hip_cov_out(qgcm_hip_handle c, int which, double *avg, double *swt, long *nunit, long k0, long count,
+                                double *cov) {
+  if (cov_ready(c, "qgcm_hip_cov_out")) return 1;
+  const auto &v = c->cov;
+  if (which != 0 && which != 1) QG_FAIL("qgcm_hip_cov_out: which = %d (0 = p, 1 = T)", which);
+  if (cov && (count < 0 || k0 < v.k0 || k0 + count > v.k1))
+    QG_FAIL("qgcm_hip_cov_out: entries %ld..%ld outside the range %ld..%ld this handle holds", k0, k0 + count - 1, v.k0,
+            v.k1 - 1);
+  if (swt) *swt = v.swt[which];
+  if (nunit) *nunit = v.nu[which];
+  if (avg) HIPCHECK(hipMemcpyAsync(avg, v.mean[which], (size_t)v.nvar * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cov && count > 0)
+    HIPCHECK(hipMemcpyAsync(cov, v.mat[which] + (k0 - v.k0), (size_t)count * sizeof(double), hipMemcpyDeviceToHost,
+                            c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int qgcm_hip_cov_schedule(qgcm_hip_handle c, int every, int phase) {
+  if (check_ready(c, "qgcm_hip_cov_schedule")) return 1;
+  if (!c->whole)
+    QG_FAIL("qgcm_hip_cov_schedule: the handle is a y-slab; the scheduled contribution is whole-domain only (call "
+            "qgcm_hip_cov_part / _combine between slab steps)");
+  if (cov_ready(c, "qgcm_hip_cov_schedule")) return 1;
+  if (every < 0) QG_FAIL("qgcm_hip_cov_schedule: every = %d (need >= 0; 0 removes the schedule)", every);
+  if (every > 0 && (phase < 0 || phase >= every))
+    QG_FAIL("qgcm_hip_cov_schedule: phase = %d outside [0, %d)", phase, every);
+  c->cov.every = every;
+  c->cov.phase = every > 0 ? phase : 0;
+  return 0;
+}
+
 static int launch_poavg(qgcm_hip_ctx *c);
 
 static int one_step(qgcm_hip_ctx *c, int s) {
@@ -3283,7 +3593,8 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
   const long pn0 = c->poavg.n;
   if (qd_dumps(c, s0, B)) QG_FAIL("qgcm_hip_steps: internal: a graph block would hold a dump step"); // (steps_impl cuts)
-  if (at_count(c, s0, B - 1)) QG_FAIL("qgcm_hip_steps: internal: a graph block would hold an accumulation step");
+  if (at_count(c, s0, B - 1) || cv_count(c, s0, B - 1))
+    QG_FAIL("qgcm_hip_steps: internal: a graph block would hold an accumulation step");
   HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
   for (int s = s0; s < s0 + B && !rc; ++s) rc = one_step(c, s);
@@ -3310,7 +3621,8 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
 // a single step left before one) runs eagerly: the blocks of the other steps are the graphs of a run without one.
 // With an accumulation schedule (qgcm_hip_tavatm_schedule) the graph blocks end after every accumulation step, and the
 // contribution is launched on the stream between two replays (never captured); a single step left before one runs
-// eagerly.  The dry pass cuts in the same places.
+// eagerly.  The dry pass cuts in the same places.  A covariance schedule (qgcm_hip_cov_schedule) cuts the same way; its
+// contribution follows a tavatm contribution of the same step (src/q-gcm.F:1477-1488).
 static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
   int s = s0;
   if (!dry && c->qd.every > 0) {
@@ -3323,11 +3635,12 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
     QgTavParams P;
     if (atav_params(c, P, "qgcm_hip_steps (qgcm_hip_tavatm_schedule)")) return 1;
   }
+  if (!dry && cv_count(c, s0, n) > 0 && cov_inputs(c, "qgcm_hip_steps (qgcm_hip_cov_schedule)")) return 1;
   if (!dry) c->graph_call++; // (a dry pass belongs to the call that follows it: qgcm_hip_time_steps, prepare + steps)
   const int is0 = c->oml.is, ism0 = c->oml.ism, ip0 = c->ip, iq0 = c->iq;
   while (n > 0) {
     // steps before the next dump step; steps up to and including the next accumulation step
-    const int m = std::min(qd_run(c, s, n), at_run(c, s, n));
+    const int m = std::min(std::min(qd_run(c, s, n), at_run(c, s, n)), cv_run(c, s, n));
     if (!c->profiling && m >= 2) {
       const int B = m >= kGraphBlock50 ? kGraphBlock50 : (m & ~1);
       hipGraphExec_t ge;
@@ -3338,14 +3651,16 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       n -= B;
       if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
       if (!dry && at_due(c, s - 1) && launch_tavatm(c, "qgcm_hip_steps")) return 1; // tavatm after the block's last step
+      if (!dry && cv_due(c, s - 1) && launch_cov(c, "qgcm_hip_steps")) return 1;       // then covocn / covatm
       continue;
     }
-    if (c->qd.every <= 0 && c->atav.every <= 0) break; // no schedule: the tail below
+    if (c->qd.every <= 0 && c->atav.every <= 0 && c->cov.every <= 0) break; // no schedule: the tail below
     // a dump step, an accumulation step, or the single step before one: eagerly (a dry pass follows the rotations it
     // would make)
     if (!dry) {
       if (one_step(c, s)) return 1;
       if (at_due(c, s) && launch_tavatm(c, "qgcm_hip_steps")) return 1; // after the step's averaging (src/q-gcm.F:1477-1479)
+      if (cv_due(c, s) && launch_cov(c, "qgcm_hip_steps")) return 1;    // after tavatm (src/q-gcm.F:1484-1489)
     } else {
       c->ip ^= 1;
       c->iq ^= 1;
@@ -4158,7 +4473,8 @@ extern "C" int qgcm_hip_copy_bandwidth(qgcm_hip_handle c, size_t bytes, int reps
 }
 
 // Rate (GB/s of read + written bytes) of a pure streaming kernel that reads nr fields and writes nw fields of
-// field_bytes each (the mixes of the hot kernels: 15:6 tendency, 3:3 rows / sweep, 5:3 fused inverse rows).
+// field_bytes each (the mixes of the hot kernels: 15:6 tendency, 3:3 rows / sweep, 5:3 fused inverse rows, 1:1 the
+// covariances' rank-1 update).
 extern "C" int qgcm_hip_stream_mix_bandwidth(qgcm_hip_handle c, int nr, int nw, size_t field_bytes, int reps, double *gbps) {
   if (!c || !gbps) QG_FAIL("qgcm_hip_stream_mix_bandwidth: null argument");
   field_bytes = field_bytes / 4096 * 4096;
@@ -4177,6 +4493,7 @@ extern "C" int qgcm_hip_stream_mix_bandwidth(qgcm_hip_handle c, int nr, int nw, 
     if (nr == 15 && nw == 6) hipLaunchKernelGGL((k_stream_mix<15, 6>), grid, block, 0, c->stream, a, b, nper);
     else if (nr == 3 && nw == 3) hipLaunchKernelGGL((k_stream_mix<3, 3>), grid, block, 0, c->stream, a, b, nper);
     else if (nr == 5 && nw == 3) hipLaunchKernelGGL((k_stream_mix<5, 3>), grid, block, 0, c->stream, a, b, nper);
+    else if (nr == 1 && nw == 1) hipLaunchKernelGGL((k_stream_mix<1, 1>), grid, block, 0, c->stream, a, b, nper);
     else return 1;
     return 0;
   };
@@ -4195,7 +4512,7 @@ extern "C" int qgcm_hip_stream_mix_bandwidth(qgcm_hip_handle c, int nr, int nw, 
   hipEventDestroy(e1);
   hipFree(a);
   hipFree(b);
-  if (rc) QG_FAIL("qgcm_hip_stream_mix_bandwidth: supported mixes are 15:6, 3:3 and 5:3");
+  if (rc) QG_FAIL("qgcm_hip_stream_mix_bandwidth: supported mixes are 15:6, 3:3, 5:3 and 1:1");
   return 0;
 }
 

@@ -448,6 +448,52 @@ module qgcm_hip_iface
       integer(c_int), intent(in) :: outflat(7)
       real(c_double), intent(out) :: out(*)
     end function
+    ! covariance matrices (DESIGN 6j): covini / covocn / covatm; packed index k = i(i+1)/2 + j (0-based)
+    integer(c_int) function qgcm_hip_cov_init(h, nsi, rank, nranks) bind(C, name='qgcm_hip_cov_init')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: nsi, rank, nranks
+    end function
+    integer(c_int) function qgcm_hip_cov_size(h, nvar, nmat, k0, k1) bind(C, name='qgcm_hip_cov_size')
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: h
+      integer(c_long), intent(out) :: nvar, nmat, k0, k1
+    end function
+    integer(c_int) function qgcm_hip_cov_add(h) bind(C, name='qgcm_hip_cov_add')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_cov_reset(h) bind(C, name='qgcm_hip_cov_reset')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_cov_out(h, which, avg, swt, nunit, k0, count, cov) bind(C, name='qgcm_hip_cov_out')
+      import :: c_ptr, c_int, c_long, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: which
+      real(c_double), intent(out) :: avg(*), swt
+      integer(c_long), intent(out) :: nunit
+      integer(c_long), value :: k0, count
+      real(c_double), intent(out) :: cov(*)
+    end function
+    integer(c_int) function qgcm_hip_cov_schedule(h, every, phase) bind(C, name='qgcm_hip_cov_schedule')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: every, phase
+    end function
+    integer(c_long) function qgcm_hip_cov_part_len(h) bind(C, name='qgcm_hip_cov_part_len')
+      import :: c_ptr, c_long
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_cov_part(h, send_dev) bind(C, name='qgcm_hip_cov_part')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, send_dev
+    end function
+    integer(c_int) function qgcm_hip_cov_combine(h, gath_dev, nranks) bind(C, name='qgcm_hip_cov_combine')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, gath_dev
+      integer(c_int), value :: nranks
+    end function
   end interface
 
 contains

@@ -100,6 +100,8 @@ SYMBOLS = [
     "qgcm_hip_ocnc_sample_len", "qgcm_hip_ocnc_sample", "qgcm_hip_subsample_rows",
     "qgcm_hip_set_atm_tav_fields", "qgcm_hip_tavatm", "qgcm_hip_atm_tav_reset", "qgcm_hip_atm_tav_out",
     "qgcm_hip_tavatm_schedule", "qgcm_hip_atnc_sample_len", "qgcm_hip_atnc_sample",
+    "qgcm_hip_cov_init", "qgcm_hip_cov_size", "qgcm_hip_cov_add", "qgcm_hip_cov_reset", "qgcm_hip_cov_out",
+    "qgcm_hip_cov_schedule", "qgcm_hip_cov_part_len", "qgcm_hip_cov_part", "qgcm_hip_cov_combine",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -224,6 +226,17 @@ def load_library():
     L.qgcm_hip_atnc_sample_len.argtypes = [vp, C.c_int, ip]
     L.qgcm_hip_atnc_sample_len.restype = C.c_long
     L.qgcm_hip_atnc_sample.argtypes = [vp, C.c_int, ip, dp]
+    lp = C.POINTER(C.c_long)
+    L.qgcm_hip_cov_init.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.qgcm_hip_cov_size.argtypes = [vp, lp, lp, lp, lp]
+    L.qgcm_hip_cov_add.argtypes = [vp]
+    L.qgcm_hip_cov_reset.argtypes = [vp]
+    L.qgcm_hip_cov_out.argtypes = [vp, C.c_int, dp, dp, lp, C.c_long, C.c_long, dp]
+    L.qgcm_hip_cov_schedule.argtypes = [vp, C.c_int, C.c_int]
+    L.qgcm_hip_cov_part_len.argtypes = [vp]
+    L.qgcm_hip_cov_part_len.restype = C.c_long
+    L.qgcm_hip_cov_part.argtypes = [vp, vp]
+    L.qgcm_hip_cov_combine.argtypes = [vp, vp, C.c_int]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

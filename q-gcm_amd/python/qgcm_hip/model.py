@@ -279,6 +279,44 @@ def read_atnc(L, h, acfg, nska, outflat):
     return res
 
 
+# covariance matrices (qgcm_hip_cov_*): covout's arrays under the reference's names, p-grid vector first
+COV_NAMES_OCN = ("covpo", "avgpo", "swtpo", "nupo", "covto", "avgto", "swtto", "nuto")
+COV_NAMES_ATM = ("covpa", "avgpa", "swtpa", "nupa", "covta", "avgta", "swtta", "nuta")
+
+
+def cov_row_split(nvar, r, nranks):
+    """First packed matrix row of rank r of nranks (qgcm_hip_cov_init): the smallest i with i(i+1)/2 >= r*nmat//nranks."""
+    nmat = nvar * (nvar + 1) // 2
+    t = nmat * r // nranks
+    i = int((np.sqrt(8.0 * t + 1.0) - 1.0) * 0.5)
+    while i > 0 and (i - 1) * i // 2 >= t:
+        i -= 1
+    while i * (i + 1) // 2 < t:
+        i += 1
+    return i
+
+
+def cov_size(L, h):
+    """qgcm_hip_cov_size: dict nvar, nmat, k0, k1 (the packed range [k0, k1) the handle holds)."""
+    v = [C.c_long() for _ in range(4)]
+    check(L.qgcm_hip_cov_size(h, *[C.byref(x) for x in v]))
+    return dict(zip(("nvar", "nmat", "k0", "k1"), (x.value for x in v)))
+
+
+def read_covariance(L, h, names, k0=None, count=None):
+    """qgcm_hip_cov_out for both vectors: dict keyed by `names` (cov, avg, swt, nu of p, then of T).  The packed entries
+    k0 .. k0+count-1 (default: all the handle holds), 0-based k = i(i+1)/2 + j."""
+    sz = cov_size(L, h)
+    k0 = sz["k0"] if k0 is None else int(k0)
+    count = sz["k1"] - k0 if count is None else int(count)
+    out = {}
+    for w in (0, 1):
+        cov, avg, swt, nu = np.zeros(max(count, 0)), np.zeros(sz["nvar"]), C.c_double(), C.c_long()
+        check(L.qgcm_hip_cov_out(h, w, _dp(avg), C.byref(swt), C.byref(nu), k0, count, _dp(cov)))
+        out.update(zip(names[4 * w:4 * w + 4], (cov, avg, swt.value, nu.value)))
+    return out
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -657,6 +695,39 @@ class OceanModel:
         s0 = self.step_index if s0 is None else int(s0)
         check(self.L.qgcm_hip_prepare_steps(self.h, s0, int(n)))
 
+    # -- covariance matrices (covini / covocn and covout's arrays, src/covaria_diag.F) ---------------------
+    _COV_NAMES = COV_NAMES_OCN
+
+    def enable_covariance(self, nsi=16):
+        """covini: allocate and zero the p and T matrices (nvar(nvar+1)/2 entries each, nvar = (nxt/nsi)*(nyt/nsi)),
+        the means and the counts.  nsi = 0 frees them."""
+        check(self.L.qgcm_hip_cov_init(self.h, int(nsi), 0, 1))
+
+    def covocn(self):
+        """One covocn contribution from the device state (po layer 1; sst of the mixed layer, else of
+        set_monitor_fields)."""
+        check(self.L.qgcm_hip_cov_add(self.h))
+
+    def covariance(self, k0=None, count=None):
+        """covout's arrays keyed by the reference's names (covpo, avgpo, swtpo, nupo, covto, ...); the matrices as the
+        packed entries k0 .. k0+count-1 (default all; 0-based k = i(i+1)/2 + j, j <= i)."""
+        return read_covariance(self.L, self.h, self._COV_NAMES, k0, count)
+
+    def covariance_size(self):
+        """dict nvar, nmat, k0, k1."""
+        return cov_size(self.L, self.h)
+
+    def reset_covariance(self):
+        """covini again: matrices, means and counts to zero."""
+        check(self.L.qgcm_hip_cov_reset(self.h))
+
+    def schedule_covariance(self, every, phase=0):
+        """Add a contribution inside steps() / coupled_steps() after every step s with s % every == phase (after the
+        step's averaging and a scheduled tavatm).  Reference cadence: ocean every = ntcovoc // nstr,
+        phase = ((nsteps0 + nstr - 1) // nstr) % every; atmosphere every = ntcovat, phase = nsteps0 % ntcovat.
+        every = 0 removes the schedule."""
+        check(self.L.qgcm_hip_cov_schedule(self.h, int(every), int(phase)))
+
     def profile_steps(self, n, s0=None):
         """Per-kernel HIP-event totals over n eagerly launched steps:
         {name: (total_ms, launches)}."""
@@ -792,6 +863,20 @@ class AtmosModel(OceanModel):
         pa, qa (nla, jpwk, ipwk); ha = (pa(k)-pa(k+1))/gpat(k) (nla-1, jpwk, ipwk)."""
         r = read_atnc(self.L, self.h, self.cfg, nska, outflat)
         return {k: (v if k in ("pa", "qa", "ha") else v[0]) for k, v in r.items()}
+
+    # -- covariance matrices (covatm; DESIGN 6j): pa layer 1 and ast of set_atm_monitor_fields -------------------------
+    _COV_NAMES = COV_NAMES_ATM
+
+    def enable_covariance(self, nsi=2):
+        """covini's atmosphere half (nsi = nscvat)."""
+        OceanModel.enable_covariance(self, nsi)
+
+    def covatm(self):
+        """One covatm contribution from the device state (pa layer 1, ast)."""
+        check(self.L.qgcm_hip_cov_add(self.h))
+
+    def covocn(self):
+        raise QgcmHipError("covocn is the ocean's; an atmosphere handle accumulates with covatm()")
 
     pa = OceanModel.po
     pam = OceanModel.pom

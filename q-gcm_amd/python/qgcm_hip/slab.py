@@ -393,6 +393,39 @@ class HipSlab:
     def reset_time_means(self):
         check(self.L.qgcm_hip_tav_reset(self.h))
 
+    # covariance matrices: this rank's row sums, the combine, and the matrix rows this rank holds
+    def enable_covariance(self, nsi=16):
+        check(self.L.qgcm_hip_cov_init(self.h, int(nsi), int(self.rank), int(self.nranks)))
+
+    def cov_part_len(self):
+        n = self.L.qgcm_hip_cov_part_len(self.h)
+        if n < 0:
+            check(1)
+        return n
+
+    def cov_part(self, send):
+        """This rank's row sums -> send (device buffer of cov_part_len() doubles); asynchronous."""
+        check(self.L.qgcm_hip_cov_part(self.h, self._ptr(send)))
+        self._done()
+
+    def cov_combine(self, gath):
+        """All ranks' row sums (rank-major) -> the means everywhere and the update of the rows this rank holds."""
+        check(self.L.qgcm_hip_cov_combine(self.h, self._ptr(gath), int(self.nranks)))
+        self._done()
+
+    def covariance(self, k0=None, count=None):
+        """This rank's share: dict keyed by the reference's names (covpo .. nuto); the matrices hold packed entries
+        k0 .. k0+count-1 (default: covariance_size()'s [k0, k1))."""
+        from .model import COV_NAMES_OCN, read_covariance
+        return read_covariance(self.L, self.h, COV_NAMES_OCN, k0, count)
+
+    def covariance_size(self):
+        from .model import cov_size
+        return cov_size(self.L, self.h)
+
+    def reset_covariance(self):
+        check(self.L.qgcm_hip_cov_reset(self.h))
+
     # periodic ocean dumps (DESIGN 6g): the subsample rows this rank owns (subsample_rows)
     def subsample_rows(self, nsko):
         """(mp0, mp1, mt0, mt1): the p-grid subsample rows [mp0, mp1) and T-grid rows [mt0, mt1) this rank owns."""
@@ -753,6 +786,64 @@ class SlabOcean:
     def reset_time_means(self):
         for x in self.slabs:
             x.reset_time_means()
+
+    # covariance matrices, collective: row sums of every rank, one all-gather, the combine on every rank ----
+    def enable_covariance(self, nsi=16):
+        S = self.slabs
+        for x in S:
+            x.enable_covariance(nsi)
+        n = S[0].cov_part_len()
+        self._cov_bufs = ([x.new_buffer(n) for x in S], [x.new_buffer(n * self.P) for x in S])
+        self._settle()
+
+    def covocn(self):
+        """One covocn contribution: every rank's row sums, one all-gather, every rank forms the same vectors and means
+        and updates the matrix rows it holds."""
+        S = self.slabs
+        send, gath = self._cov_bufs
+        self._join()  # (the row sums read owned rows only; the pending halo stage belongs to the step)
+        for i, x in enumerate(S):
+            x.cov_part(send[i])
+        for x in S:
+            x.sync()
+        self._comm(self.comm.all_gather, gath, send)
+        for i, x in enumerate(S):
+            x.cov_combine(gath[i])
+
+    def covariance_parts(self, k0=None, count=None):
+        """The local slabs' shares (HipSlab.covariance), for matrices too large to assemble."""
+        return [x.covariance(k0, count) for x in self.slabs]
+
+    def covariance(self):
+        """As OceanModel.covariance(): the whole matrices, assembled from every rank's rows with one all-gather."""
+        from .model import COV_NAMES_OCN, cov_row_split
+        S = self.slabs
+        parts = self.covariance_parts()
+        sz = S[0].covariance_size()
+        nvar, P = sz["nvar"], self.P
+        ks = [cov_row_split(nvar, r, P) * (cov_row_split(nvar, r, P) + 1) // 2 for r in range(P + 1)]
+        m = max(ks[r + 1] - ks[r] for r in range(P))
+        send, gath = [], []
+        for x, d in zip(S, parts):
+            v = np.zeros(2 * m)
+            v[:len(d["covpo"])] = d["covpo"]
+            v[m:m + len(d["covto"])] = d["covto"]
+            t = x.new_buffer(2 * m)
+            t.copy_(x.torch.from_numpy(v))
+            send.append(t)
+            gath.append(x.new_buffer(2 * m * P))
+        self._settle()
+        self._comm(self.comm.all_gather, gath, send)
+        g = gath[0].cpu().numpy().reshape(P, 2 * m)
+        out = dict(parts[0])
+        out["covpo"] = np.concatenate([g[r, :ks[r + 1] - ks[r]] for r in range(P)])
+        out["covto"] = np.concatenate([g[r, m:m + ks[r + 1] - ks[r]] for r in range(P)])
+        assert len(out["covpo"]) == sz["nmat"]
+        return out
+
+    def reset_covariance(self):
+        for x in self.slabs:
+            x.reset_covariance()
 
     # periodic ocean dumps (DESIGN 6g), collective: the owned subsample rows of every rank, one all-gather -----------
     def _gather_subsample(self, parts, rows, nsko, tnames=()):
