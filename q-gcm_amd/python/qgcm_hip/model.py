@@ -145,20 +145,26 @@ def tav_params(oml=None, hmoc=None, ycexp=None, tsbdy=None, tnbdy=None, sb_hflux
     return p
 
 
+def _read_means(layout, entry, nout, h, shape, names):
+    """The means `entry` (qgcm_hip_tav_out / qgcm_hip_atm_tav_out, `nout` outputs in `layout`'s order) returns for the
+    given names (None = all): (dict name -> array, number of contributions).  shape: grid -> array shape."""
+    want = [n for n, _ in layout] if names is None else list(names)
+    out, ptrs = {}, (C.POINTER(C.c_double) * nout)()
+    for i, (name, grid) in enumerate(layout):
+        if name in want:
+            out[name] = np.zeros(shape[grid], order="F")
+            ptrs[i] = _dp(out[name])
+    n = C.c_int()
+    check(entry(h, ptrs, C.byref(n)))
+    return out, n.value
+
+
 def read_time_means(L, h, cfg, np_rows, nt_rows, names=None):
     """qgcm_hip_tav_out for the given names (None = all): (dict name -> array, nsumoc)."""
     from .lib import TAV_NOUT
     shape = dict(p=(cfg.nxpo, np_rows), t=(cfg.nxto, nt_rows), p3=(cfg.nxpo, np_rows, cfg.nlo), u=(cfg.nxpo, nt_rows),
                  v=(cfg.nxto, np_rows))
-    want = [n for n, _ in TAV_LAYOUT] if names is None else list(names)
-    out, ptrs = {}, (C.POINTER(C.c_double) * TAV_NOUT)()
-    for i, (name, grid) in enumerate(TAV_LAYOUT):
-        if name in want:
-            out[name] = np.zeros(shape[grid], order="F")
-            ptrs[i] = _dp(out[name])
-    n = C.c_int()
-    check(L.qgcm_hip_tav_out(h, ptrs, C.byref(n)))
-    return out, n.value
+    return _read_means(TAV_LAYOUT, L.qgcm_hip_tav_out, TAV_NOUT, h, shape, names)
 
 
 def read_po_mean(L, h, cfg, np_rows, reset):
@@ -171,7 +177,10 @@ def read_po_mean(L, h, cfg, np_rows, reset):
 
 # periodic ocean dumps (qgcm_hip_qocdiag / qgcm_hip_ocnc_sample)
 QOCDIAG_TERMS = ("dqdt", "qotjac", "qt2dif", "qt4dif", "qotent")
-OCNC_FIELDS = ("sst", "po", "qo", "wekto", "h", "tauxo", "tauyo")  # ocnc_out's order; tauxo, tauyo share outfloc(6)
+# ocnc_out's fields in its order: (name, grid, planes in units of nlo: 0 = one plane, 1 = nlo, -1 = nlo-1, flag index)
+# (tauxo and tauyo share outfloc(6))
+OCNC_FIELDS = (("sst", "t", 0, 0), ("po", "p", 1, 1), ("qo", "p", 1, 2), ("wekto", "t", 0, 3), ("h", "p", -1, 4),
+               ("tauxo", "p", 0, 5), ("tauyo", "p", 0, 5))
 
 
 def subsample_count(n, nsko):
@@ -202,27 +211,35 @@ def read_budget(L, h, cfg, nsko):
     return unpack_budget(out, cfg.nlo, subsample_count(cfg.nxpo, nsko))
 
 
-def read_ocnc(L, h, cfg, nsko, outfloc):
-    """ocnc_out's selected fields: dict name -> array (planes, rows, columns) (one plane for the 2-d fields)."""
-    fl = (C.c_int * 7)(*[int(x) for x in outfloc])
-    n = L.qgcm_hip_ocnc_sample_len(h, int(nsko), fl)
+def _read_dump(fields, length, sample, h, nsk, flags, nl, counts):
+    """The selected fields of `fields` (OCNC_FIELDS / ATNC_FIELDS) from the packed result of `sample`: dict name ->
+    (planes, rows, columns) array, (rows, columns) for the one-plane fields.  counts(): grid -> (rows, columns)."""
+    fl = (C.c_int * 7)(*[int(x) for x in flags])
+    n = length(h, int(nsk), fl)
     if n < 0:
         check(1)
     out = np.zeros(n)
-    check(L.qgcm_hip_ocnc_sample(h, int(nsko), fl, _dp(out)))
-    mp0, mp1, mt0, mt1 = subsample_rows(L, h, nsko)
-    ip, it = subsample_count(cfg.nxpo, nsko), subsample_count(cfg.nxto, nsko)
-    nl, res, o = cfg.nlo, {}, 0
-    shapes = dict(sst=(1, mt1 - mt0, it), po=(nl, mp1 - mp0, ip), qo=(nl, mp1 - mp0, ip), wekto=(1, mt1 - mt0, it),
-                  h=(nl - 1, mp1 - mp0, ip), tauxo=(1, mp1 - mp0, ip), tauyo=(1, mp1 - mp0, ip))
-    for f, name in enumerate(OCNC_FIELDS):
-        if int(outfloc[min(f, 5)]) != 1:
+    check(sample(h, int(nsk), fl, _dp(out)))
+    cnt, res, o = counts(), {}, 0
+    for name, grid, planes, flag in fields:
+        if int(flags[flag]) != 1:
             continue
-        m = int(np.prod(shapes[name]))
-        res[name] = out[o:o + m].reshape(shapes[name])
+        shp = ({0: 1, 1: nl, -1: nl - 1}[planes],) + cnt[grid]
+        m = int(np.prod(shp))
+        a = out[o:o + m].reshape(shp)
+        res[name] = a[0] if planes == 0 else a
         o += m
     assert o == n
     return res
+
+
+def read_ocnc(L, h, cfg, nsko, outfloc):
+    """ocnc_out's selected fields on the subsample rows the handle owns: sst, wekto (jtwk, itwk); po, qo
+    (nlo, jpwk, ipwk); h (nlo-1, jpwk, ipwk); tauxo, tauyo (jpwk, ipwk)."""
+    def counts():
+        mp0, mp1, mt0, mt1 = subsample_rows(L, h, nsko)
+        return dict(p=(mp1 - mp0, subsample_count(cfg.nxpo, nsko)), t=(mt1 - mt0, subsample_count(cfg.nxto, nsko)))
+    return _read_dump(OCNC_FIELDS, L.qgcm_hip_ocnc_sample_len, L.qgcm_hip_ocnc_sample, h, nsko, outfloc, cfg.nlo, counts)
 
 
 # the atmosphere's time averages and dump (qgcm_hip_atm_tav_out / qgcm_hip_atnc_sample; DESIGN 6i): outputs of
@@ -235,48 +252,6 @@ ATM_TAV_LAYOUT = (("txatav", "p"), ("tyatav", "p"), ("wtatav", "t"), ("fmatav", 
 # (tauxa and tauya share outflat(6))
 ATNC_FIELDS = (("ast", "t", 0, 0), ("pa", "p", 1, 1), ("qa", "p", 1, 2), ("wekta", "t", 0, 3), ("ha", "p", -1, 4),
                ("tauxa", "p", 0, 5), ("tauya", "p", 0, 5), ("hmixa", "t", 0, 6))
-
-
-def read_atm_time_means(L, h, acfg, names=None):
-    """qgcm_hip_atm_tav_out for the given names (None = all): (dict name -> array, nsumat)."""
-    from .lib import ATM_TAV_NOUT
-    nxp, nyp, nl = acfg.nxpa, acfg.nypa, acfg.nla
-    shape = dict(p=(nxp, nyp), t=(nxp - 1, nyp - 1), p3=(nxp, nyp, nl), u=(nxp, nyp - 1), v=(nxp - 1, nyp))
-    want = [n for n, _ in ATM_TAV_LAYOUT] if names is None else list(names)
-    unknown = set(want) - set(n for n, _ in ATM_TAV_LAYOUT)
-    if unknown:
-        raise QgcmHipError("unknown time means %s (ATM_TAV_LAYOUT)" % sorted(unknown))
-    out, ptrs = {}, (C.POINTER(C.c_double) * ATM_TAV_NOUT)()
-    for i, (name, grid) in enumerate(ATM_TAV_LAYOUT):
-        if name in want:
-            out[name] = np.zeros(shape[grid], order="F")
-            ptrs[i] = _dp(out[name])
-    n = C.c_int()
-    check(L.qgcm_hip_atm_tav_out(h, ptrs, C.byref(n)))
-    return out, n.value
-
-
-def read_atnc(L, h, acfg, nska, outflat):
-    """atnc_out's selected fields: dict name -> array (planes, rows, columns) (one plane for the 2-d fields)."""
-    fl = (C.c_int * 7)(*[int(x) for x in outflat])
-    n = L.qgcm_hip_atnc_sample_len(h, int(nska), fl)
-    if n < 0:
-        check(1)
-    out = np.zeros(n)
-    check(L.qgcm_hip_atnc_sample(h, int(nska), fl, _dp(out)))
-    nl = acfg.nla
-    cnt = dict(p=(subsample_count(acfg.nypa, nska), subsample_count(acfg.nxpa, nska)),
-               t=(subsample_count(acfg.nypa - 1, nska), subsample_count(acfg.nxpa - 1, nska)))
-    res, o = {}, 0
-    for name, grid, planes, flag in ATNC_FIELDS:
-        if int(outflat[flag]) != 1:
-            continue
-        shp = ({0: 1, 1: nl, -1: nl - 1}[planes],) + cnt[grid]
-        m = int(np.prod(shp))
-        res[name] = out[o:o + m].reshape(shp)
-        o += m
-    assert o == n
-    return res
 
 
 # covariance matrices (qgcm_hip_cov_*; DESIGN 6j): covout's arrays under the reference's names, p-grid vector first
@@ -620,8 +595,7 @@ class OceanModel:
     def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
         """ocnc_out's subsampled fields (the selected ones): sst, wekto (jtwk, itwk); po, qo (nlo, jpwk, ipwk);
         h (nlo-1, jpwk, ipwk); tauxo, tauyo (jpwk, ipwk)."""
-        r = read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
-        return {k: (v[0] if k in ("sst", "wekto", "tauxo", "tauyo") else v) for k, v in r.items()}
+        return read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
 
     # -- ocean mixed layer (`call oml`, src/q-gcm.F:1232; SURVEY 8 row f1) -------
     def oml_init(self, om):
@@ -844,7 +818,13 @@ class AtmosModel(OceanModel):
     def time_means(self, names=None):
         """tavout's atmosphere means (src/timavge.F:715-801) keyed by the reference's names (ATM_TAV_LAYOUT), plus
         "nsumat".  The sums are not changed.  names: the subset to compute and copy (None = all)."""
-        out, n = read_atm_time_means(self.L, self.h, self.cfg, names)
+        from .lib import ATM_TAV_NOUT
+        unknown = set(names or ()) - set(n for n, _ in ATM_TAV_LAYOUT)
+        if unknown:
+            raise QgcmHipError("unknown time means %s (ATM_TAV_LAYOUT)" % sorted(unknown))
+        nxp, nyp, nl = self.cfg.nxpa, self.cfg.nypa, self.cfg.nla
+        shape = dict(p=(nxp, nyp), t=(nxp - 1, nyp - 1), p3=(nxp, nyp, nl), u=(nxp, nyp - 1), v=(nxp - 1, nyp))
+        out, n = _read_means(ATM_TAV_LAYOUT, self.L.qgcm_hip_atm_tav_out, ATM_TAV_NOUT, self.h, shape, names)
         out["nsumat"] = n
         return out
 
@@ -861,8 +841,11 @@ class AtmosModel(OceanModel):
     def atmos_dump(self, nska=1, outflat=(1, 1, 1, 1, 1, 1, 1)):
         """atnc_out's subsampled fields (the selected ones): ast, wekta, hmixa (jtwk, itwk); tauxa, tauya (jpwk, ipwk);
         pa, qa (nla, jpwk, ipwk); ha = (pa(k)-pa(k+1))/gpat(k) (nla-1, jpwk, ipwk)."""
-        r = read_atnc(self.L, self.h, self.cfg, nska, outflat)
-        return {k: (v if k in ("pa", "qa", "ha") else v[0]) for k, v in r.items()}
+        c, L = self.cfg, self.L
+        counts = lambda: dict(p=(subsample_count(c.nypa, nska), subsample_count(c.nxpa, nska)),
+                              t=(subsample_count(c.nypa - 1, nska), subsample_count(c.nxpa - 1, nska)))
+        return _read_dump(ATNC_FIELDS, L.qgcm_hip_atnc_sample_len, L.qgcm_hip_atnc_sample, self.h, nska, outflat, c.nla,
+                          counts)
 
     # -- covariance matrices (covatm; DESIGN 6j): pa layer 1 and ast of set_atm_monitor_fields -------------------------
     _COV_NAMES = COV_NAMES_ATM

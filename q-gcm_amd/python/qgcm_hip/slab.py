@@ -440,8 +440,7 @@ class HipSlab:
     def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
         """As OceanModel.ocean_dump for the owned subsample rows."""
         from .model import read_ocnc
-        r = read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
-        return {k: (v[0] if k in ("sst", "wekto", "tauxo", "tauyo") else v) for k, v in r.items()}
+        return read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
 
     def set_dtopoc(self, dtopoc):
         """GLOBAL bottom topography (nxpo, nypo) for valids, None = flat."""
