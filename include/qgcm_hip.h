@@ -637,6 +637,55 @@ long qgcm_hip_cov_part_len(qgcm_hip_handle h);
 int qgcm_hip_cov_part(qgcm_hip_handle h, double *send_dev);
 int qgcm_hip_cov_combine(qgcm_hip_handle h, const double *gath_dev, int nranks);
 
+/* ---- momentum half of xforc -----------------------------------------------------------------------
+ * "call xforc" (src/q-gcm.F:1226) as far as the momentum goes (src/xfosubs.F:137-709): the atmosphere's geostrophic
+ * velocity from pam(:,:,1), its bicubic interpolation to ocean resolution (auvbcu), the optional shear against the
+ * ocean's geostrophic velocity from pom(:,:,1) (the cpp option tau_udiff as a run-time flag), the quadratic drag law,
+ * the Ekman velocities on both grids and the stress line integrals of the momentum constraints.  The thermodynamic
+ * half (:711-853: fnetoc, fnetat and the arlaav / slhfav / oradav / arocav sums) is NOT computed: fnetoc, fnetat,
+ * entoc, entat, xon, xan keep coming from the setters.
+ * qgcm_hip_xforc_init(oc, atm, p): oc = the whole-domain ocean handle, or NULL for the atmos_only half; atm = the
+ *   whole-domain atmosphere handle, which keeps the set-up.  dxa, fnot come from the atmosphere's qgcm_hip_params
+ *   (dxo), dxo from the ocean's (dxa / ndxr without one).  The five weight tables are host pointers laid out as
+ *   MODULE xfosubs holds them, (16, 0:ndxr, 0:ndxr) Fortran order (qgcm_hip.hostinit.bcuini restates bcuini).  Refuses,
+ *   naming the reason and changing nothing: a y-slab handle, an ocean whose T grid is not nxaooc*ndxr x nyaooc*ndxr,
+ *   an ocean that does not lie inside the atmosphere, a cyclic ocean with nxaooc != nxta, tau_udiff without an ocean.
+ *   Allocates the scratch (two fine p-grid stress arrays and the fine T-grid Ekman velocity; u1ator / v1ator are never
+ *   stored) and, where they do not exist yet, the buffers of qgcm_hip_set_atm_monitor_fields (wekta, tauxa, tauya,
+ *   uekat, vekat) and of qgcm_hip_set_monitor_fields (tauxo, tauyo, wekto).
+ * qgcm_hip_xforc(oc, atm): one call, asynchronous, on the atmosphere's stream; that stream first waits for what is
+ *   queued on the ocean's, and the ocean's stream afterwards waits for the results.  It reads the lagged time levels
+ *   (pam, pom: what qgcm_hip_get_state returns as pom) and writes
+ *     wekpa, txisat, txinat  where qgastep / atinvq read them (qgcm_hip_set_forcing / _set_cyc_forcing's places)
+ *     wekpo, txisoc, txinoc  likewise for the ocean (txis / txin: cyclic ocean only)
+ *     tauxo, tauyo, wekto    the buffers of qgcm_hip_set_monitor_fields and, after qgcm_hip_oml_init, the mixed layer's
+ *     tauxa, tauya, uekat, vekat, wekta   the buffers of qgcm_hip_set_atm_monitor_fields (they count as given)
+ *   Every field is bitwise the reference's (same operand order, contraction off); the four line integrals are
+ *   parallel sums with a fixed tree: reproducible from call to call, equal to the reference to rounding.
+ * qgcm_hip_xforc_get: synchronous copies, dense Fortran order: tauxa, tauya, wekpa (nxpa,nypa), uekat (nxpa,nyta),
+ *   vekat (nxta,nypa), wekta (nxta,nyta), tauxo, tauyo, wekpo (nxpo,nypo), wekto (nxto,nyto), txi[4] = txisat, txinat,
+ *   txisoc, txinoc (0 for a box ocean or none).  NULL skips a field.
+ * qgcm_hip_coupled_set_xforc(oc, atm, on): while on, qgcm_hip_coupled_steps(oc, atm, ...) runs the reference's order
+ *   (src/q-gcm.F:1222-1268): at every nt with mod(nt,nstr) == 1 xforc, then the ocean step, then the atmospheric
+ *   steps up to the next such nt.  Off (the default) a window's launches, streams and graphs are those without this
+ *   feature. */
+typedef struct qgcm_hip_xforc_params {
+  int ndxr;                 /* dxa/dxo                                       (MODULE parameters) */
+  int nx1, ny1;             /* first atmosphere T cell above the ocean */
+  int nxaooc, nyaooc;       /* atmosphere T cells above the ocean */
+  double cdat, raoro;       /* drag coefficient, density ratio rhoat/rhooc   (MODULE intrfac) */
+  double hmat, hmoc;        /* mixed layer thicknesses                       (MODULE intrfac) */
+  double bccoat, bccooc;    /* mixed boundary condition coefficients         (MODULE atconst / occonst) */
+  int tau_udiff;            /* the reference's cpp option tau_udiff as a run-time flag */
+  const double *stbbb, *stbus, *stbvs, *stbun, *stbvn; /* (16, 0:ndxr, 0:ndxr) each */
+} qgcm_hip_xforc_params;
+int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p);
+int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm);
+int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
+                       double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
+                       double *wekpo, double *txi);
+int qgcm_hip_coupled_set_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm, int on);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

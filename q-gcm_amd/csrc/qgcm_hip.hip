@@ -41,6 +41,7 @@
 #include "k_cov.h"
 #include "k_qocdiag.h"
 #include "k_setup.h"
+#include "k_xforc.h"
 #include "slab_comm.h"
 
 // kernels that are templates on the number of layers: instantiated for nlo = 2 .. QGCM_HIP_MAXL (8); the fused fast
@@ -247,6 +248,17 @@ struct qgcm_hip_ctx {
   // what qgcm_hip_steps does on its own at scheduled steps: the dump of qgcm_hip_qocdiag_schedule inside the step, the
   // contributions of qgcm_hip_tavatm_schedule and qgcm_hip_cov_schedule after it, in this order
   QgSched sched[SCH_COUNT];
+  // momentum half of xforc (qgcm_hip_xforc_init, k_xforc.h), held by the ATMOSPHERE handle: the constants, the ocean
+  // handle it was set up with (or nullptr: atmos_only), the scratch (coarse velocities, the fine stress and the fine
+  // Ekman velocity), the transposed weight tables and the two events that order the streams
+  struct {
+    bool on = false, coupled = false; // coupled: qgcm_hip_coupled_steps calls xforc before every ocean step
+    qgcm_hip_xforc_params prm;
+    qgcm_hip_ctx *oc = nullptr;
+    int ldf = 0, ldtf = 0;
+    double *u1at = nullptr, *v1at = nullptr, *txf = nullptr, *tyf = nullptr, *wf = nullptr, *tab = nullptr;
+    hipEvent_t ev_oc = nullptr, ev_atm = nullptr;
+  } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
   std::map<int, hipGraphExec_t> slab_graphs;
@@ -455,6 +467,11 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : tavp)
     if (p) hipFree(p);
   if (c->cov.status) hipFree(c->cov.status);
+  double *xfp[] = {c->xf.u1at, c->xf.v1at, c->xf.txf, c->xf.tyf, c->xf.wf, c->xf.tab};
+  for (double *p : xfp)
+    if (p) hipFree(p);
+  if (c->xf.ev_oc) hipEventDestroy(c->xf.ev_oc);
+  if (c->xf.ev_atm) hipEventDestroy(c->xf.ev_atm);
   double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
                    c->oml.taux, c->oml.tauy, c->oml.partA, c->oml.partB, c->oml.diag};
   for (double *p : omp)
@@ -2163,6 +2180,247 @@ extern "C" int qgcm_hip_get_bsums(qgcm_hip_handle c, double *b) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// momentum half of xforc: src/xfosubs.F:137-709 on the device, kernels in k_xforc.h
+// ---------------------------------------------------------------------------
+static void xf_free(qgcm_hip_ctx *a) {
+  auto &x = a->xf;
+  double **ps[] = {&x.u1at, &x.v1at, &x.txf, &x.tyf, &x.wf, &x.tab};
+  for (double **p : ps) {
+    if (*p) hipFree(*p);
+    *p = nullptr;
+  }
+  x.on = x.coupled = false;
+  x.oc = nullptr;
+}
+
+extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
+  const char *who = "qgcm_hip_xforc_init";
+  if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
+  if (check_atm(atm, who)) return 1;
+  if (!atm->whole) QG_FAIL("%s: the atmosphere handle is a y-slab (xforc needs the whole domain)", who);
+  if (oc) {
+    if (oc->g.atm) QG_FAIL("%s: the first handle is an atmosphere (pass the ocean, or NULL for atmos_only)", who);
+    if (!oc->whole) QG_FAIL("%s: the ocean handle is a y-slab (xforc needs the whole domain)", who);
+    if (check_ready(oc, who)) return 1;
+    if (oc->device != atm->device) QG_FAIL("%s: the two handles live on different devices (%d, %d)", who, oc->device, atm->device);
+  }
+  if (p->tau_udiff && !oc) QG_FAIL("%s: tau_udiff needs an ocean (the reference ignores it when atmos_only)", who);
+  if (!p->stbbb || !p->stbus || !p->stbvs || !p->stbun || !p->stbvn) QG_FAIL("%s: a weight table is NULL", who);
+  const int ndxr = p->ndxr, nxta = atm->g.nxt, nyta = atm->g.ny - 1;
+  if (ndxr < 1 || ndxr > 64) QG_FAIL("%s: ndxr = %d outside 1..64", who, ndxr);
+  if (nxta < 4 || nyta < 2) QG_FAIL("%s: atmosphere of %d x %d cells is too small", who, nxta, nyta);
+  if ((double)nxta * ndxr >= 1.0e6 || (long)nyta * ndxr >= 65535)
+    QG_FAIL("%s: the fine grid %d*%d x %d*%d exceeds the kernels' launch limits", who, nxta, ndxr, nyta, ndxr);
+  if (!(p->hmat > 0.0) || !(p->cdat > 0.0)) QG_FAIL("%s: need hmat > 0 and cdat > 0", who);
+  if (oc) {
+    const int nxto = oc->g.nxt, nyto = oc->g.ny - 1;
+    if (!(p->hmoc > 0.0)) QG_FAIL("%s: need hmoc > 0", who);
+    if (p->nxaooc < 1 || p->nyaooc < 1 || nxto != p->nxaooc * ndxr || nyto != p->nyaooc * ndxr)
+      QG_FAIL("%s: mismatched geometry: the ocean has %d x %d T cells, nxaooc*ndxr x nyaooc*ndxr = %d*%d x %d*%d", who, nxto,
+              nyto, p->nxaooc, ndxr, p->nyaooc, ndxr);
+    if (p->nx1 < 1 || p->ny1 < 1 || p->nx1 + p->nxaooc - 1 > nxta || p->ny1 + p->nyaooc - 1 > nyta)
+      QG_FAIL("%s: the ocean (nx1 = %d, ny1 = %d, nxaooc = %d, nyaooc = %d) does not lie inside the atmosphere's %d x %d cells",
+              who, p->nx1, p->ny1, p->nxaooc, p->nyaooc, nxta, nyta);
+    if (oc->g.cyc && (p->nxaooc != nxta || p->nx1 != 1))
+      QG_FAIL("%s: a zonally cyclic ocean needs nxaooc = nxta (%d, %d) and nx1 = 1", who, p->nxaooc, nxta);
+    if (oc->prm.fnot != atm->prm.fnot) QG_FAIL("%s: the handles differ in fnot", who);
+  }
+  auto &x = atm->xf;
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  xf_free(atm);
+  x.prm = *p;
+  x.prm.stbbb = x.prm.stbus = x.prm.stbvs = x.prm.stbun = x.prm.stbvn = nullptr; // (host pointers are not kept)
+  const QgGeom &g = atm->g;
+  const int nxpaor = nxta * ndxr + 1, nypaor = nyta * ndxr + 1;
+  x.ldf = round_up(nxpaor, 16);
+  x.ldtf = round_up(nxpaor - 1, 16);
+  const size_t nfine = (size_t)x.ldf * nypaor, npl = (size_t)(ndxr + 1) * ndxr;
+  if (dalloc(&x.u1at, (size_t)g.ldx * g.ny) || dalloc(&x.v1at, (size_t)g.ldx * g.ny) || dalloc(&x.txf, nfine) ||
+      dalloc(&x.tyf, nfine) || dalloc(&x.wf, (size_t)x.ldtf * (nypaor - 1)) || dalloc(&x.tab, 5 * 16 * npl)) {
+    xf_free(atm);
+    return 1;
+  }
+  {
+    // MODULE xfosubs holds stb**(16, 0:ndxr, 0:ndxr); the kernels read tab[k][jj][ii], ii = 0..ndxr-1 (k_xforc.h)
+    std::vector<double> t(5 * 16 * npl);
+    const double *src[5] = {p->stbbb, p->stbus, p->stbvs, p->stbun, p->stbvn};
+    for (int m = 0; m < 5; ++m)
+      for (int k = 0; k < 16; ++k)
+        for (int jj = 0; jj <= ndxr; ++jj)
+          for (int ii = 0; ii < ndxr; ++ii)
+            t[((size_t)m * 16 + k) * npl + (size_t)jj * ndxr + ii] = src[m][k + 16 * ((size_t)ii + (size_t)(ndxr + 1) * jj)];
+    HIPCHECK(hipMemcpy(x.tab, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  // the destinations beside wekpa / wekpo: the atmosphere's monitor fields and the ocean's (zero until the first call)
+  auto &m = atm->atmon;
+  if (!m.ldt) m.ldt = round_up(nxta, 16);
+  struct { double **ptr; size_t n; } dst[] = {{&m.wekta, (size_t)m.ldt * nyta}, {&m.tauxa, (size_t)g.ldx * g.ny},
+                                              {&m.tauya, (size_t)g.ldx * g.ny}, {&m.uekat, (size_t)g.ldx * nyta},
+                                              {&m.vekat, (size_t)m.ldt * g.ny}};
+  for (auto &d : dst)
+    if (!*d.ptr && dalloc(d.ptr, d.n)) return 1;
+  if (oc) {
+    auto &mo = oc->mon;
+    const QgGeom &go = oc->g;
+    if (!mo.ldt) mo.ldt = round_up(go.nxt, 16);
+    if (!mo.taux && dalloc(&mo.taux, (size_t)go.ldx * go.ny)) return 1;
+    if (!mo.tauy && dalloc(&mo.tauy, (size_t)go.ldx * go.ny)) return 1;
+    if (!mo.wekto && dalloc(&mo.wekto, (size_t)mo.ldt * (go.ny - 1))) return 1;
+  }
+  if (!x.ev_oc) HIPCHECK(hipEventCreateWithFlags(&x.ev_oc, hipEventDisableTiming));
+  if (!x.ev_atm) HIPCHECK(hipEventCreateWithFlags(&x.ev_atm, hipEventDisableTiming));
+  x.oc = oc;
+  x.on = true;
+  return 0;
+}
+
+static int xf_ready(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const char *who) {
+  if (!atm) QG_FAIL("%s: null atmosphere handle", who);
+  if (check_atm(atm, who)) return 1;
+  if (!atm->xf.on) QG_FAIL("%s: qgcm_hip_xforc_init has not been called for this atmosphere", who);
+  if (atm->xf.oc != oc) QG_FAIL("%s: the ocean handle is not the one qgcm_hip_xforc_init was called with", who);
+  return 0;
+}
+
+static void xf_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfParams &P) {
+  const auto &x = atm->xf;
+  const qgcm_hip_xforc_params &p = x.prm;
+  const QgGeom &g = atm->g;
+  memset(&P, 0, sizeof(P));
+  const int ndxr = p.ndxr;
+  P.ndxr = ndxr; P.nxta = g.nxt; P.nyta = g.ny - 1; P.nxpa = g.nx; P.nypa = g.ny;
+  P.nxtaor = P.nxta * ndxr; P.nytaor = P.nyta * ndxr; P.nxpaor = P.nxtaor + 1; P.nypaor = P.nytaor + 1;
+  P.ndxodd = ndxr % 2; P.nijwid = ndxr + ndxr % 2;
+  P.lda = g.ldx; P.ldta = atm->atmon.ldt; P.ldf = x.ldf; P.ldtf = x.ldtf;
+  P.pam = atm->p[atm->ip ^ 1];
+  P.u1at = x.u1at; P.v1at = x.v1at; P.txf = x.txf; P.tyf = x.tyf; P.wf = x.wf;
+  const size_t tn = (size_t)16 * (ndxr + 1) * ndxr;
+  P.tbb = x.tab; P.tus = x.tab + tn; P.tvs = x.tab + 2 * tn; P.tun = x.tab + 3 * tn; P.tvn = x.tab + 4 * tn;
+  const auto &m = atm->atmon;
+  P.tauxa = m.tauxa; P.tauya = m.tauya; P.uekat = m.uekat; P.vekat = m.vekat; P.wekta = m.wekta; P.wekpa = atm->wekpo;
+  P.sca = atm->sc;
+  // constants as src/xfosubs.F:137-155, 185, 249 with dxa = ndxr*dxo, rdxaf0, rdxof0 of src/q-gcm.F:380, 435-436
+  const double fnot = atm->prm.fnot, dxa = atm->prm.dxo, dxo = oc ? oc->prm.dxo : dxa / (double)ndxr;
+  const double rdxaf0 = 1.0 / (dxa * fnot), rdxof0 = 1.0 / (dxo * fnot);
+  P.dxo = dxo;
+  P.hxafac = 0.5 * rdxaf0; P.hxofac = 0.5 * rdxof0;
+  P.zbfcat = rdxaf0 / (0.5 * p.bccoat + 1.0);
+  P.zbfcoc = rdxof0 / (0.5 * p.bccooc + 1.0);
+  P.uvekfc = 1.0 / (p.hmat * fnot * (double)ndxr);
+  P.hmrdxa = p.hmat / dxa;
+  const double cdhfaa = (p.cdat / fnot) / p.hmat;
+  P.cdrfaa = p.cdat / fabs(cdhfaa);
+  P.qu2faa = 4.0 * cdhfaa * cdhfaa;
+  P.raoro = p.raoro;
+  P.udiff = p.tau_udiff ? 1 : 0;
+  if (oc) {
+    const double cdhfab = (p.cdat / fnot) * (1.0 / p.hmat + p.raoro / p.hmoc);
+    P.cdrfab = p.cdat / fabs(cdhfab);
+    P.qu2fab = 4.0 * cdhfab * cdhfab;
+    P.nxpo = oc->g.nx; P.nypo = oc->g.ny; P.ldo = oc->g.ldx; P.cyc_oc = oc->g.cyc;
+    P.iocoff = (p.nx1 - 1) * ndxr; P.jocoff = (p.ny1 - 1) * ndxr;
+    P.pom = oc->p[oc->ip ^ 1];
+    P.tauxo = oc->mon.taux; P.tauyo = oc->mon.tauy;
+    P.sco = oc->g.cyc ? oc->sc : nullptr;
+  }
+}
+
+// One `call xforc` (momentum half) on the atmosphere's stream, ordered against the ocean's stream by two events.
+extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
+  if (xf_ready(oc, atm, "qgcm_hip_xforc")) return 1;
+  auto &x = atm->xf;
+  hipStream_t st = atm->stream;
+  QgXfParams P;
+  xf_fill(oc, atm, P);
+  if (oc) { // pom and the ocean's forcing buffers: after everything queued on the ocean's stream
+    HIPCHECK(hipEventRecord(x.ev_oc, oc->stream));
+    HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
+  }
+  const dim3 b(XF_NT);
+  hipLaunchKernelGGL(k_xf_coarse, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_fine, dim3((P.nxta + XF_CX - 1) / XF_CX, P.nyta), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_atm, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_wekta, dim3((P.nxta + XF_NT - 1) / XF_NT, P.nyta), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_wektaor, dim3((P.nxtaor + XF_NT - 1) / XF_NT, P.nytaor), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_wekpa, dim3((P.nxpa + 63) / 64, P.nypa), dim3(64), 0, st, P);
+  if (oc) {
+    const QgGeom &go = oc->g;
+    auto &mo = oc->mon;
+    hipLaunchKernelGGL(k_xf_tauo, dim3((P.nxpo + XF_NT - 1) / XF_NT, P.nypo), b, 0, st, P);
+    QgWekParams W;
+    memset(&W, 0, sizeof(W));
+    W.g = go; W.taux = mo.taux; W.tauy = mo.tauy; W.wekto = mo.wekto; W.wekpo = oc->wekpo; W.ldt = mo.ldt;
+    W.hxofac = P.hxofac;
+    hipLaunchKernelGGL(k_wekto, dim3((go.nxt + 255) / 256, go.ny - 1), dim3(256), 0, st, W);
+    hipLaunchKernelGGL(k_wekpo, dim3((go.nx + 255) / 256, go.ny), dim3(256), 0, st, W);
+    if (oc->oml.on) { // the mixed layer's own forcing buffers (same pitches)
+      auto &o = oc->oml;
+      const size_t nP = (size_t)go.ldx * go.ny * sizeof(double), nT = (size_t)o.ldt * (go.ny - 1) * sizeof(double);
+      HIPCHECK(hipMemcpyAsync(o.taux, mo.taux, nP, hipMemcpyDeviceToDevice, st));
+      HIPCHECK(hipMemcpyAsync(o.tauy, mo.tauy, nP, hipMemcpyDeviceToDevice, st));
+      HIPCHECK(hipMemcpyAsync(o.wekto, mo.wekto, nT, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
+  HIPCHECK(hipGetLastError());
+  if (oc) { // the ocean's next step reads wekpo, the stress and the line integrals
+    HIPCHECK(hipEventRecord(x.ev_atm, st));
+    HIPCHECK(hipStreamWaitEvent(oc->stream, x.ev_atm, 0));
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
+                                  double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
+                                  double *wekpo, double *txi) {
+  if (xf_ready(oc, atm, "qgcm_hip_xforc_get")) return 1;
+  const QgGeom &g = atm->g;
+  const auto &m = atm->atmon;
+  const int nxt = g.nxt, nyt = g.ny - 1;
+  if (tauxa && download2d(atm, tauxa, m.tauxa, g.ldx, g.nx, g.ny)) return 1;
+  if (tauya && download2d(atm, tauya, m.tauya, g.ldx, g.nx, g.ny)) return 1;
+  if (uekat && download2d(atm, uekat, m.uekat, g.ldx, g.nx, nyt)) return 1;
+  if (vekat && download2d(atm, vekat, m.vekat, m.ldt, nxt, g.ny)) return 1;
+  if (wekta && download2d(atm, wekta, m.wekta, m.ldt, nxt, nyt)) return 1;
+  if (wekpa && download2d(atm, wekpa, atm->wekpo, g.ldx, g.nx, g.ny)) return 1;
+  if ((tauxo || tauyo || wekto || wekpo) && !oc) QG_FAIL("qgcm_hip_xforc_get: an ocean field was asked for without an ocean");
+  if (oc) {
+    const QgGeom &go = oc->g;
+    const auto &mo = oc->mon;
+    HIPCHECK(hipStreamSynchronize(atm->stream)); // (xforc ran on the atmosphere's stream)
+    if (tauxo && download2d(oc, tauxo, mo.taux, go.ldx, go.nx, go.ny)) return 1;
+    if (tauyo && download2d(oc, tauyo, mo.tauy, go.ldx, go.nx, go.ny)) return 1;
+    if (wekto && download2d(oc, wekto, mo.wekto, mo.ldt, go.nxt, go.ny - 1)) return 1;
+    if (wekpo && download2d(oc, wekpo, oc->wekpo, go.ldx, go.nx, go.ny)) return 1;
+  }
+  if (txi) {
+    QgScalars h;
+    HIPCHECK(hipMemcpyAsync(&h, atm->sc, sizeof(h), hipMemcpyDeviceToHost, atm->stream));
+    HIPCHECK(hipStreamSynchronize(atm->stream));
+    txi[0] = h.txisoc;
+    txi[1] = h.txinoc;
+    txi[2] = txi[3] = 0.0;
+    if (oc && oc->g.cyc) {
+      HIPCHECK(hipMemcpyAsync(&h, oc->sc, sizeof(h), hipMemcpyDeviceToHost, atm->stream));
+      HIPCHECK(hipStreamSynchronize(atm->stream));
+      txi[2] = h.txisoc;
+      txi[3] = h.txinoc;
+    }
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_coupled_set_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm, int on) {
+  if (!on) {
+    if (atm) atm->xf.coupled = false;
+    return 0;
+  }
+  if (xf_ready(oc, atm, "qgcm_hip_coupled_set_xforc")) return 1;
+  atm->xf.coupled = true;
+  return 0;
+}
+
 // Coupled run with the forcing held between calls: the main loop of src/q-gcm.F:1220-1268 without xforc / oml / aml.
 // The ocean steps of the window are queued on the ocean handle's stream and the atmospheric steps on the
 // atmosphere's: with the forcing frozen the two halves do not exchange data inside the window, so the streams need
@@ -2204,6 +2462,27 @@ extern "C" int qgcm_hip_coupled_steps(qgcm_hip_handle oc, qgcm_hip_handle atm, i
   if (oc && check_ready(oc, "qgcm_hip_coupled_steps")) return 1;
   if (atm && check_atm(atm, "qgcm_hip_coupled_steps")) return 1;
   if (oc && (oc->g.atm || !oc->whole)) QG_FAIL("qgcm_hip_coupled_steps: first handle must be a whole-domain ocean");
+  if (atm && atm->xf.coupled) {
+    // qgcm_hip_coupled_set_xforc: the reference's order (src/q-gcm.F:1222-1268) - at every nt with mod(nt,nstr) == 1
+    // xforc, then the ocean step, then the atmospheric steps up to the next such nt.  The events of qgcm_hip_xforc
+    // order the two streams; xforc is launched between the step graphs' replays.
+    if (xf_ready(oc, atm, "qgcm_hip_coupled_steps")) return 1;
+    const int end = nt0 + n; // one past the last step
+    for (int nt = nt0; nt < end;) {
+      int next = end;
+      if (nstr > 1) {
+        if (nt % nstr == 1) {
+          if (qgcm_hip_xforc(oc, atm)) return 1;
+          if (oc && steps_impl(oc, (nt - 1) / nstr + 1, 1, false)) return 1;
+        }
+        const int nn = nt + (nstr - (nt - 1) % nstr); // the next nt with mod(nt,nstr) == 1
+        if (nn < end) next = nn;
+      }
+      if (steps_impl(atm, nt, next - nt, false)) return 1;
+      nt = next;
+    }
+    return 0;
+  }
   if (oc && n > 0) {
     // ocean steps s with nt = 1 + (s-1)*nstr in [nt0, nt0+n-1]   (mod(nt,nstr) == 1, src/q-gcm.F:1222; nstr = 1 never
     // steps the ocean in the reference - SURVEY 8d caveat - and neither does this)

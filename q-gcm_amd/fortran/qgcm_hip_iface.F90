@@ -45,6 +45,15 @@ module qgcm_hip_iface
     integer(c_int) :: nx1, ny1, nxaooc, nyaooc
   end type qgcm_hip_atm_mon_params
 
+  ! struct qgcm_hip_xforc_params: constants and bicubic weight tables of the momentum half of xforc
+  ! (qgcm_hip_xforc_init); stb** = c_loc of MODULE xfosubs' tables (16, 0:ndxr, 0:ndxr)
+  type, bind(C) :: qgcm_hip_xforc_params
+    integer(c_int) :: ndxr, nx1, ny1, nxaooc, nyaooc
+    real(c_double) :: cdat, raoro, hmat, hmoc, bccoat, bccooc
+    integer(c_int) :: udiff_flag   ! tau_udiff of the C struct (that name is a cpp macro in reference builds)
+    type(c_ptr) :: stbbb, stbus, stbvs, stbun, stbvn
+  end type qgcm_hip_xforc_params
+
   interface
     integer(c_int) function qgcm_hip_create(h, prm, device) bind(C, name='qgcm_hip_create')
       import :: c_ptr, c_int, qgcm_hip_params
@@ -493,6 +502,27 @@ module qgcm_hip_iface
       import :: c_ptr, c_int
       type(c_ptr), value :: h, gath_dev
       integer(c_int), value :: nranks
+    end function
+    ! momentum half of xforc on the device (src/xfosubs.F:137-709); oc = c_null_ptr: the atmos_only half
+    integer(c_int) function qgcm_hip_xforc_init(oc, atm, prm) bind(C, name='qgcm_hip_xforc_init')
+      import :: c_ptr, c_int, qgcm_hip_xforc_params
+      type(c_ptr), value :: oc, atm
+      type(qgcm_hip_xforc_params), intent(in) :: prm
+    end function
+    integer(c_int) function qgcm_hip_xforc(oc, atm) bind(C, name='qgcm_hip_xforc')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: oc, atm
+    end function
+    ! every field is a c_ptr (c_loc of the host array, or c_null_ptr to skip it); txi: txisat, txinat, txisoc, txinoc
+    integer(c_int) function qgcm_hip_xforc_get(oc, atm, tauxa, tauya, uekat, vekat, wekta, wekpa, tauxo, tauyo, wekto, &
+                                               wekpo, txi) bind(C, name='qgcm_hip_xforc_get')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: oc, atm, tauxa, tauya, uekat, vekat, wekta, wekpa, tauxo, tauyo, wekto, wekpo, txi
+    end function
+    integer(c_int) function qgcm_hip_coupled_set_xforc(oc, atm, on) bind(C, name='qgcm_hip_coupled_set_xforc')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: oc, atm
+      integer(c_int), value :: on
     end function
   end interface
 

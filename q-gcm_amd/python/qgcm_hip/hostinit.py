@@ -10,6 +10,7 @@ restated with numpy for the host side (init-only, not on the per-step path):
   ocqbdy   src/vorsubs.F:245-388     (boundary q; numpy twin used only at init)
   homsol   src/conhoms.F:376-641     (homogeneous solutions; the Helmholtz solves
                                       go through the HIP solver, see OceanModel)
+  bcuini   src/xfosubs.F:1238-1728   (bicubic weight tables of auvbcu, with wts2bb)
 
 The atmospheric channel (cfg.atmos) shares all of it with the cyclic ocean; where the
 reference's atmosphere differs the functions branch on ``cfg.atmos``: eigmod without the Flierl normalisation
@@ -317,4 +318,105 @@ def helmholtz_box_host(cfg, rhs, boc):
         u[:, r] = u[:, r] - gam[:, r + 1] * u[:, r + 1]
     out = np.zeros((nx, ny), order="F")
     out[1:-1, 1:-1] = scipy.fft.dst(ftnorm * u, type=1, axis=0)
+    return out
+
+
+# stinv of wts2bb (src/xfosubs.F:1652-1667): the DATA statement fills the matrix column by column
+_STINV = np.array(
+    [1, 0, -3, 2] + 4 * [0] + [-3, 0, 9, -6, 2, 0, -6, 4]
+    + [0, 0, 3, -2] + 6 * [0] + [-9, 6, 0, 0, 6, -4]
+    + 8 * [0] + [3, 0, -9, 6, -2, 0, 6, -4]
+    + 10 * [0] + [9, -6, 0, 0, -6, 4]
+    + [0, 1, -2, 1] + 5 * [0] + [-3, 6, -3, 0, 2, -4, 2]
+    + [0, 0, -1, 1] + 6 * [0] + [3, -3, 0, 0, -2, 2]
+    + 9 * [0] + [3, -6, 3, 0, -2, 4, -2]
+    + 10 * [0] + [-3, 3, 0, 0, 2, -2]
+    + 4 * [0] + [1, 0, -3, 2, -2, 0, 6, -4, 1, 0, -3, 2]
+    + 6 * [0] + [3, -2, 0, 0, -6, 4, 0, 0, 3, -2]
+    + 8 * [0] + [-1, 0, 3, -2, 1, 0, -3, 2]
+    + 10 * [0] + [-3, 2, 0, 0, 3, -2]
+    + 5 * [0] + [1, -2, 1, 0, -2, 4, -2, 0, 1, -2, 1]
+    + 6 * [0] + [-1, 1, 0, 0, 2, -2, 0, 0, -1, 1]
+    + 9 * [0] + [-1, 2, -1, 0, 1, -2, 1]
+    + 10 * [0] + [1, -1, 0, 0, -1, 1], dtype=np.float64).reshape((16, 16), order="F")
+
+
+def _wts2bb(wfcn, wfnx, wfny, wfxy):
+    """wts2bb (src/xfosubs.F:1625-1728): the weights (id, jd, ip, jp), id / jd offset by one, -> B = stinv * u2f."""
+    u2f = np.zeros((16, 16))
+    kp = 0
+    for jp in range(2):
+        for ip in range(2):
+            kd = 0
+            for jd in range(4):
+                for i_d in range(4):
+                    u2f[kp, kd] = wfcn[i_d, jd, ip, jp]
+                    u2f[kp + 4, kd] = wfnx[i_d, jd, ip, jp]
+                    u2f[kp + 8, kd] = wfny[i_d, jd, ip, jp]
+                    u2f[kp + 12, kd] = wfxy[i_d, jd, ip, jp]
+                    kd += 1
+            kp += 1
+    bbb = np.zeros((16, 16))
+    for j in range(16):  # wfsum = wfsum + stinv(i,j)*u2f(j,kd), j ascending
+        bbb = bbb + _STINV[:, j][:, None] * u2f[j, :][None, :]
+    return bbb
+
+
+def bcuini(ndxr, bccoat, dya):
+    """The bicubic weight tables stbbb, stbus, stbvs, stbun, stbvn (16, 0:ndxr, 0:ndxr) of MODULE xfosubs, as bcuini
+    fills them (src/xfosubs.F:1238-1621): the general case, u and v next to the southern boundary, u and v next to
+    the northern one.  Like the reference it fills fine points 0..ndxr-1 only: row / column ndxr of the SAVEd module
+    storage is never written and stays zero, and auvbcu's northern cells read that row (jj = ndxr) of stbun / stbvn.
+    No LAPACK: sums in the reference's order."""
+    n1 = ndxr + 1
+    stfn = np.zeros((16, n1, n1))
+    s = np.arange(n1, dtype=np.float64) / float(ndxr)
+    pw = [np.ones(n1), s, s * s, s * s * s]  # (integer powers by multiplication, as the reference's run-time code)
+    m = 0
+    for j in range(4):
+        for i in range(4):
+            stfn[m] = pw[i][:, None] * pw[j][None, :]
+            m += 1
+    bc = bccoat / dya
+
+    def weights(case):
+        w = [np.zeros((4, 4, 2, 2)) for _ in range(4)]
+        fcn, fnx, fny, fxy = w
+        o = 1  # offset of id, jd = -1..2
+        for jp in range(2):
+            for ip in range(2):
+                fcn[ip + o, jp + o, ip, jp] = 1.0
+                fnx[ip + 1 + o, jp + o, ip, jp] = 0.5
+                fnx[ip - 1 + o, jp + o, ip, jp] = -0.5
+                special = (case in ("us", "vs") and jp == 0) or (case in ("un", "vn") and jp == 1)
+                if not special:
+                    fny[ip + o, jp + 1 + o, ip, jp] = 0.5
+                    fny[ip + o, jp - 1 + o, ip, jp] = -0.5
+                    fxy[ip + 1 + o, jp + 1 + o, ip, jp] = 0.25
+                    fxy[ip - 1 + o, jp + 1 + o, ip, jp] = -0.25
+                    fxy[ip + 1 + o, jp - 1 + o, ip, jp] = -0.25
+                    fxy[ip - 1 + o, jp - 1 + o, ip, jp] = 0.25
+                elif case in ("us", "un"):  # mixed pressure boundary condition
+                    sg = bc if case == "us" else -bc
+                    fny[ip + o, jp + o, ip, jp] = sg * fcn[ip + o, jp + o, ip, jp]
+                    fxy[ip + 1 + o, jp + o, ip, jp] = sg * fnx[ip + 1 + o, jp + o, ip, jp]
+                    fxy[ip - 1 + o, jp + o, ip, jp] = sg * fnx[ip - 1 + o, jp + o, ip, jp]
+                else:  # v: the u field on the boundary sits in the otherwise empty row (vy = -ux, vxy = -uxx)
+                    je = jp - 1 if case == "vs" else jp + 1
+                    fny[ip + 1 + o, je + o, ip, jp] = -fnx[ip + 1 + o, jp + o, ip, jp]
+                    fny[ip - 1 + o, je + o, ip, jp] = -fnx[ip - 1 + o, jp + o, ip, jp]
+                    fxy[ip + 1 + o, je + o, ip, jp] = -1.0
+                    fxy[ip + o, je + o, ip, jp] = 2.0
+                    fxy[ip - 1 + o, je + o, ip, jp] = -1.0
+        return w
+
+    out = {}
+    for case in ("bb", "us", "vs", "un", "vn"):
+        b = _wts2bb(*weights(case))
+        stb = np.zeros((16, n1, n1))
+        for mm in range(16):  # stbsum = stbsum + b(m,k)*stfn(m,ii,jj), m ascending
+            stb = stb + b[mm, :][:, None, None] * stfn[mm][None, :, :]
+        stb[:, ndxr, :] = 0.0
+        stb[:, :, ndxr] = 0.0
+        out["stb" + ("bb" if case == "bb" else case)] = np.asfortranarray(stb)
     return out

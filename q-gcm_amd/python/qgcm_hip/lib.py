@@ -66,6 +66,17 @@ class TavParams(C.Structure):
     ]
 
 
+class XforcParams(C.Structure):
+    """struct qgcm_hip_xforc_params (include/qgcm_hip.h)."""
+    _fields_ = [
+        ("ndxr", C.c_int), ("nx1", C.c_int), ("ny1", C.c_int), ("nxaooc", C.c_int), ("nyaooc", C.c_int),
+        ("cdat", C.c_double), ("raoro", C.c_double), ("hmat", C.c_double), ("hmoc", C.c_double),
+        ("bccoat", C.c_double), ("bccooc", C.c_double), ("tau_udiff", C.c_int),
+        ("stbbb", C.POINTER(C.c_double)), ("stbus", C.POINTER(C.c_double)), ("stbvs", C.POINTER(C.c_double)),
+        ("stbun", C.POINTER(C.c_double)), ("stbvn", C.POINTER(C.c_double)),
+    ]
+
+
 TAV_NOUT = 16  # QGCM_HIP_TAV_NOUT
 ATM_TAV_NOUT = 15  # QGCM_HIP_ATM_TAV_NOUT
 
@@ -102,6 +113,7 @@ SYMBOLS = [
     "qgcm_hip_tavatm_schedule", "qgcm_hip_atnc_sample_len", "qgcm_hip_atnc_sample",
     "qgcm_hip_cov_init", "qgcm_hip_cov_size", "qgcm_hip_cov_add", "qgcm_hip_cov_reset", "qgcm_hip_cov_out",
     "qgcm_hip_cov_schedule", "qgcm_hip_cov_part_len", "qgcm_hip_cov_part", "qgcm_hip_cov_combine",
+    "qgcm_hip_xforc_init", "qgcm_hip_xforc", "qgcm_hip_xforc_get", "qgcm_hip_coupled_set_xforc",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -237,6 +249,10 @@ def load_library():
     L.qgcm_hip_cov_part_len.restype = C.c_long
     L.qgcm_hip_cov_part.argtypes = [vp, vp]
     L.qgcm_hip_cov_combine.argtypes = [vp, vp, C.c_int]
+    L.qgcm_hip_xforc_init.argtypes = [vp, vp, C.POINTER(XforcParams)]
+    L.qgcm_hip_xforc.argtypes = [vp, vp]
+    L.qgcm_hip_xforc_get.argtypes = [vp, vp] + [dp] * 11
+    L.qgcm_hip_coupled_set_xforc.argtypes = [vp, vp, C.c_int]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

@@ -883,11 +883,82 @@ def share_gpu(ocean, atmos, atmos_cus=None):
     return acu
 
 
-def coupled_steps(ocean, atmos, nt0, n, nstr):
+XFORC_FIELDS = ("tauxa", "tauya", "uekat", "vekat", "wekta", "wekpa", "tauxo", "tauyo", "wekto", "wekpo")
+XFORC_INTEGRALS = ("txisat", "txinat", "txisoc", "txinoc")
+
+
+def xforc_setup(ocean, atmos, cdat=1.3e-3, rhoat=1.0, rhooc=1.0e3, hmat=1000.0, hmoc=100.0, tau_udiff=False,
+                tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None):
+    """Set up the momentum half of xforc on the device (qgcm_hip_xforc_init) for the whole-domain models
+    `ocean` (or None: the atmos_only half) and `atmos`.  cdat, hmat, hmoc and raoro = rhoat/rhooc default to the
+    double-gyre input.params; bccoat / bccooc come from the configurations.  tau_udiff: the reference's cpp option.
+    tables: the five bicubic weight tables {"stbbb", "stbus", "stbvs", "stbun", "stbvn"}, (16, ndxr+1, ndxr+1) each;
+    default hostinit.bcuini.  The position of the ocean defaults to MODULE parameters' centring,
+    nx1 = 1 + (nxta - nxaooc)/2 (likewise ny1)."""
+    from .lib import XforcParams
+    acfg = atmos.cfg
+    if ocean is not None:
+        oc = ocean.cfg
+        ndxr = oc.ndxr if ndxr is None else ndxr
+        nxaooc = oc.nxaooc if nxaooc is None else nxaooc
+        nyaooc = oc.nyaooc if nyaooc is None else nyaooc
+    elif ndxr is None:
+        raise QgcmHipError("xforc_setup: without an ocean give ndxr")
+    nxaooc = acfg.nxta if nxaooc is None else int(nxaooc)
+    nyaooc = acfg.nyta if nyaooc is None else int(nyaooc)
+    ndxr = int(ndxr)
+    if tables is None:
+        if ndxr < 1:
+            raise QgcmHipError("xforc_setup: ndxr = %d" % ndxr)
+        tables = hostinit.bcuini(ndxr, acfg.bccoat, acfg.dya)
+    keep = [np.asfortranarray(tables[k], dtype=np.float64) for k in ("stbbb", "stbus", "stbvs", "stbun", "stbvn")]
+    for t in keep:
+        if t.shape != (16, ndxr + 1, ndxr + 1):
+            raise QgcmHipError("xforc_setup: a weight table has shape %s, need (16, %d, %d)" % (t.shape, ndxr + 1, ndxr + 1))
+    p = XforcParams()
+    p.ndxr, p.nxaooc, p.nyaooc = ndxr, int(nxaooc), int(nyaooc)
+    p.nx1 = 1 + (acfg.nxta - p.nxaooc) // 2 if nx1 is None else int(nx1)
+    p.ny1 = 1 + (acfg.nyta - p.nyaooc) // 2 if ny1 is None else int(ny1)
+    p.cdat, p.raoro, p.hmat, p.hmoc = float(cdat), float(rhoat) / float(rhooc), float(hmat), float(hmoc)
+    p.bccoat = float(acfg.bccoat)
+    p.bccooc = float(ocean.cfg.bccooc) if ocean is not None else 0.0
+    p.tau_udiff = int(bool(tau_udiff))
+    p.stbbb, p.stbus, p.stbvs, p.stbun, p.stbvn = [_dp(t) for t in keep]
+    check(atmos.L.qgcm_hip_xforc_init(ocean.h if ocean is not None else None, atmos.h, C.byref(p)))
+
+
+def xforc(ocean, atmos):
+    """One `call xforc` (momentum half) from the lagged pressures on the device; asynchronous (qgcm_hip_xforc)."""
+    check(atmos.L.qgcm_hip_xforc(ocean.h if ocean is not None else None, atmos.h))
+
+
+def xforc_get(ocean, atmos, names=None):
+    """The outputs of the last xforc as a dict: XFORC_FIELDS (the ocean's only with an ocean) and XFORC_INTEGRALS."""
+    a = atmos.cfg
+    shapes = dict(tauxa=(a.nxpa, a.nypa), tauya=(a.nxpa, a.nypa), uekat=(a.nxpa, a.nyta), vekat=(a.nxta, a.nypa),
+                  wekta=(a.nxta, a.nyta), wekpa=(a.nxpa, a.nypa))
+    if ocean is not None:
+        o = ocean.cfg
+        shapes.update(tauxo=(o.nxpo, o.nypo), tauyo=(o.nxpo, o.nypo), wekto=(o.nxto, o.nyto), wekpo=(o.nxpo, o.nypo))
+    want = [n for n in XFORC_FIELDS if n in shapes and (names is None or n in names)]
+    out = {n: np.zeros(shapes[n], order="F") for n in want}
+    txi = np.zeros(4)
+    check(atmos.L.qgcm_hip_xforc_get(ocean.h if ocean is not None else None, atmos.h,
+                                     *[_dp(out.get(n)) for n in XFORC_FIELDS], _dp(txi)))
+    for k, n in enumerate(XFORC_INTEGRALS):
+        if names is None or n in names:
+            out[n] = float(txi[k])
+    return out
+
+
+def coupled_steps(ocean, atmos, nt0, n, nstr, xforc=False):
     """n atmospheric steps nt = nt0.. with one ocean step before every one with mod(nt,nstr) == 1
-    (src/q-gcm.F:1220-1268), forcing held; either model may be None."""
+    (src/q-gcm.F:1220-1268); either model may be None.  xforc = False: the forcing is held.  xforc = True (after
+    xforc_setup): the momentum half of xforc runs on the device before every ocean step, in the reference's order."""
     L = (ocean or atmos).L
-    check(L.qgcm_hip_coupled_steps(ocean.h if ocean is not None else None, atmos.h if atmos is not None else None,
-                                   int(nt0), int(n), int(nstr)))
+    oh, ah = ocean.h if ocean is not None else None, atmos.h if atmos is not None else None
+    if xforc or atmos is not None:
+        check(L.qgcm_hip_coupled_set_xforc(oh, ah, 1 if xforc else 0))
+    check(L.qgcm_hip_coupled_steps(oh, ah, int(nt0), int(n), int(nstr)))
     if atmos is not None:
         atmos.step_index = int(nt0) + int(n)
