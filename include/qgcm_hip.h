@@ -642,8 +642,8 @@ int qgcm_hip_cov_combine(qgcm_hip_handle h, const double *gath_dev, int nranks);
  * velocity from pam(:,:,1), its bicubic interpolation to ocean resolution (auvbcu), the optional shear against the
  * ocean's geostrophic velocity from pom(:,:,1) (the cpp option tau_udiff as a run-time flag), the quadratic drag law,
  * the Ekman velocities on both grids and the stress line integrals of the momentum constraints.  The thermodynamic
- * half (:711-853: fnetoc, fnetat and the arlaav / slhfav / oradav / arocav sums) is NOT computed: fnetoc, fnetat,
- * entoc, entat, xon, xan keep coming from the setters.
+ * half (:711-853: fnetoc, fnetat and the arlaav / slhfav / oradav / arocav sums) runs in the same call once
+ * qgcm_hip_xforc_heat_init has set it up (below); until then fnetoc and fnetat keep coming from the setters.
  * qgcm_hip_xforc_init(oc, atm, p): oc = the whole-domain ocean handle, or NULL for the atmos_only half; atm = the
  *   whole-domain atmosphere handle, which keeps the set-up.  dxa, fnot come from the atmosphere's qgcm_hip_params
  *   (dxo), dxo from the ocean's (dxa / ndxr without one).  The five weight tables are host pointers laid out as
@@ -685,6 +685,72 @@ int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *tauxa, d
                        double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
                        double *wekpo, double *txi);
 int qgcm_hip_coupled_set_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm, int on);
+
+/* ---- atmospheric mixed layer ------------------------------------------------------------------------
+ * "call aml" (src/q-gcm.F:1260; src/amlsubs.F) on the device, for a whole-domain atmosphere handle.
+ * qgcm_hip_aml_init(atm, p): from then on the handle owns ast, astm, hmixa, hmixam (nxta,nyta), in rotating buffers:
+ *   ast and hmixa ARE the buffers of qgcm_hip_set_atm_monitor_fields (what was given before is kept), so the
+ *   atmosphere monitors, qgcm_hip_atm_valids, tavatm, covatm and the periodic dump read the stepped fields; they count
+ *   as given.  The init also allocates, as zeros, the inputs nobody has given yet - fnetat (the buffer of
+ *   qgcm_hip_set_atm_tav_fields) and wekta, uekat, vekat (qgcm_hip_set_atm_monitor_fields) - so these count as given
+ *   too from then on: the diagnostics' "was never given" checks no longer catch a missing xforc / setter for them.
+ *   Every atmospheric step of qgcm_hip_steps / qgcm_hip_coupled_steps then runs aml immediately before
+ *   qgastep, on the handle's stream and inside the step's graph, and the averaging at mod(nt-1,100) == 0 also averages
+ *   ast and hmixa with their lagged levels (src/q-gcm.F:1388-1394).  Without it nothing changes.
+ *   tdta, dxa, dya, gpat, fnot come from the handle's qgcm_hip_params; radiat stays on the host and hands in its
+ *   coefficients.  xc1ast (nxta,nyta) and dtopat (nxpa,nypa) are host arrays, dense Fortran order; NULL = zeros.
+ * qgcm_hip_aml(atm): one call, asynchronous.  Reads fnetat (the buffer of qgcm_hip_set_atm_tav_fields), wekta, uekat,
+ *   vekat (qgcm_hip_set_atm_monitor_fields; xforc writes them), pa layer 1 (current level) and pam; writes the new
+ *   levels, entat, xan(1), enisat(1), eninat(1) where qgastep reads them (the places of qgcm_hip_set_forcing /
+ *   _set_cyc_forcing; later entries of xan, enisat, eninat are not touched) and the monitors cfraat, centat.
+ *   ast, astm, hmixa, hmixam, entat are bitwise the reference's; the sums are parallel with a fixed tree:
+ *   reproducible from call to call, equal to the reference to rounding; cfraat is exact.
+ * qgcm_hip_aml_set_state / _get_state: dense Fortran order, NULL = leave / skip, synchronous.
+ * qgcm_hip_aml_get_diag: entat (nxpa,nypa; NULL skips) and diag[3*(nla-1) + 2] = xan(1:nla-1), enisat(1:nla-1),
+ *   eninat(1:nla-1), cfraat, centat (aml writes the first entry of each vector; the others are what the setters gave). */
+typedef struct qgcm_hip_aml_params {
+  double hmat, hmamin, hmadmp;   /* mixed layer thickness, its floor, its damping constant   (MODULE intrfac) */
+  double rrcpat;                 /* 1/(rhoat*cpat)                                           (MODULE radiate) */
+  double tat1, tat2;             /* temperature anomalies of layers 1, 2                     (MODULE atconst) */
+  double xcexp;                  /* coupling coefficient x                                   (MODULE atconst) */
+  double at2d, at4d, ahmd;       /* diffusivities of ast (Del-sqd, Del-4th) and of hmixa     (MODULE intrfac) */
+  double aface[QGCM_HIP_MAXL - 1], bface, cface, dface; /* entrainment factors of radiat     (MODULE radiate) */
+  const double *xc1ast;          /* (nxta,nyta) or NULL */
+  const double *dtopat;          /* (nxpa,nypa) or NULL */
+} qgcm_hip_aml_params;
+int qgcm_hip_aml_init(qgcm_hip_handle atm, const qgcm_hip_aml_params *p);
+int qgcm_hip_aml_set_state(qgcm_hip_handle atm, const double *ast, const double *astm, const double *hmixa, const double *hmixam);
+int qgcm_hip_aml_get_state(qgcm_hip_handle atm, double *ast, double *astm, double *hmixa, double *hmixam);
+int qgcm_hip_aml(qgcm_hip_handle atm);
+int qgcm_hip_aml_get_diag(qgcm_hip_handle atm, double *entat, double *diag);
+
+/* ---- heat half of xforc -----------------------------------------------------------------------------
+ * src/xfosubs.F:711-853 with bilint (:891-993): fnetoc = -fsprim - atmrad - ocnrad - slhf at every ocean T point from
+ * the mixed layer's lagged sstm and asto, the bilinear interpolant of the atmosphere's lagged astm (computed where it
+ * is used, never stored); fnetat = the land value -fsprim - Dmup*astm, over the cells above the ocean the sum of
+ * ocfrac*(ocnrad + atmrad + slhf) over each cell's ndxr x ndxr ocean points (one wave per cell, fixed order, no
+ * atomics), plus the pointwise eta / topography / hmixam terms; the monitors arlaav, slhfav, oradav, arocav.
+ * qgcm_hip_xforc_heat_init(oc, atm, p): after qgcm_hip_xforc_init(oc, atm), qgcm_hip_aml_init(atm) and
+ *   qgcm_hip_oml_init(oc); refuses, naming the reason and changing nothing, when one of them is missing, when oc is
+ *   NULL or is not the handle qgcm_hip_xforc_init was given.  fsa[nyta] = fsprim(ytarel), fso[nyto] = fsprim(ytorel)
+ *   are host tables (sin is evaluated on the host, where the reference evaluates it); xta, yta, xto, yto are the
+ *   T-point coordinates of both grids, from which bilint's index and weight tables are built once, as the reference
+ *   computes them.  Adown11 = Adown(1,1); dtopat is the one given to qgcm_hip_aml_init.
+ * qgcm_hip_xforc(oc, atm) then runs the heat half after the momentum half, on the same stream and inside the same
+ *   waits, and writes fnetoc into the mixed layer's own forcing (the buffer of qgcm_hip_oml_set_forcing) and fnetat
+ *   into the buffer of qgcm_hip_set_atm_tav_fields (it counts as given), where aml reads it.  fnetoc is bitwise the
+ *   reference's, fnetat over land too; above the ocean and in the four monitors the sums run in a fixed tree:
+ *   reproducible, equal to the serial reference to rounding.
+ * qgcm_hip_xforc_heat_get: synchronous copies, dense Fortran order, NULL skips: fnetoc (nxto,nyto), fnetat
+ *   (nxta,nyta), scal[4] = arlaav, slhfav, oradav, arocav. */
+typedef struct qgcm_hip_xforc_heat_params {
+  double xlamda, D0up, Dmup, Dmdown, Adown11, Bmup, B1down, Cmup, C1down; /* MODULE radiate */
+  double hmadmp, hmat;                                                     /* MODULE intrfac */
+  const double *fsa, *fso;             /* fsprim(ytarel(1:nyta)), fsprim(ytorel(1:nyto)) */
+  const double *xta, *yta, *xto, *yto; /* T-point coordinates (nxta), (nyta), (nxto), (nyto) */
+} qgcm_hip_xforc_heat_params;
+int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p);
+int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *fnetoc, double *fnetat, double *scal);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of

@@ -33,6 +33,7 @@
 #include "k_rfft64.h"
 #include "k_fft3_unpack.h"
 #include "k_oml.h"
+#include "k_aml.h"
 #include "k_valids.h"
 #include "k_monitors.h"
 #include "k_atm_monitors.h"
@@ -73,11 +74,11 @@ static thread_local char g_err[512] = "";
     if (e_ != hipSuccess) QG_FAIL("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_TAVAT, KN_COV, KN_COUNT };
-// (k_oml = k_oml_step, the sst step + raw entrainment; k_oml_entoc = the entrainment on the p grid)
+enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_TAVAT, KN_COV, KN_AML, KN_AML_ENTAT, KN_COUNT };
+// (k_oml = k_oml_step, the sst step + raw entrainment; k_oml_entoc = the entrainment on the p grid; k_aml = k_aml_step)
 static const char *kKernelNames[KN_COUNT] = {"k_tend",   "k_cyc_bsums", "k_dst_fwd", "k_thomas", "k_dst_inv",
                                              "k_constr", "k_unpack",  "k_ocqbdy", "k_lf_average", "k_oml", "k_oml_entoc", "k_noop", "k_noop_train",
-                                             "k_poavg_add", "k_tavat_accum", "k_cov"};
+                                             "k_poavg_add", "k_tavat_accum", "k_cov", "k_aml", "k_aml_entat"};
 
 // Device copy of the Thomas pivot tables of one set of diagonals (see QgThomasParams / build_pivots).
 struct QgThomasTab {
@@ -182,6 +183,16 @@ struct qgcm_hip_ctx {
     double *fnet = nullptr, *wekto = nullptr, *xfo = nullptr, *taux = nullptr, *tauy = nullptr;
     double *partA = nullptr, *partB = nullptr, *diag = nullptr;
   } oml;
+  // atmospheric mixed layer (qgcm_hip_aml_init, k_aml.h; atmosphere handles): ast and hmixa in three rotating buffers
+  // each (ia = the current level, iam = the lagged one, spare = 3-ia-iam); atmon.ast / atmon.hmixa always point at the
+  // current ones, so every diagnostic reads the stepped fields.  fnetat is tav.fnet, wekta / uekat / vekat are atmon's.
+  struct {
+    bool on = false;
+    qgcm_hip_aml_params prm;
+    int ldt = 0, ia = 0, iam = 1, nblkA = 0, nblkB = 0;
+    double *ast[3] = {nullptr, nullptr, nullptr}, *hm[3] = {nullptr, nullptr, nullptr};
+    double *xfa = nullptr, *xc1 = nullptr, *dtop = nullptr, *partA = nullptr, *partB = nullptr, *diag = nullptr;
+  } aml;
   // validity scan (qgcm_hip_valids): partials, results, optional bottom topography
   double *val_part = nullptr, *val_out = nullptr, *dtopoc = nullptr;
   double *val_sum = nullptr, *prs_out = nullptr; // y-slab prsamp: this rank's valids summary (sst), combined result
@@ -258,6 +269,15 @@ struct qgcm_hip_ctx {
     int ldf = 0, ldtf = 0;
     double *u1at = nullptr, *v1at = nullptr, *txf = nullptr, *tyf = nullptr, *wf = nullptr, *tab = nullptr;
     hipEvent_t ev_oc = nullptr, ev_atm = nullptr;
+    // heat half (qgcm_hip_xforc_heat_init): constants, the two fsprim tables, bilint's index / weight tables, the
+    // per-cell sums above the ocean, the partial sums of the four monitors and their results
+    struct {
+      bool on = false;
+      qgcm_hip_xforc_heat_params prm;
+      double *fsa = nullptr, *fso = nullptr, *wx = nullptr, *wy = nullptr, *cell = nullptr, *part = nullptr, *scal = nullptr;
+      int *ix = nullptr, *iy = nullptr;
+      int nblkL = 0;
+    } heat;
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
@@ -456,6 +476,21 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : monp)
     if (p) hipFree(p);
   if (c->mon.hout) hipHostFree(c->mon.hout);
+  if (c->aml.ast[0]) { // the mixed layer owns what atmon.ast / atmon.hmixa point at
+    c->atmon.ast = c->atmon.hmixa = nullptr;
+    double *amp[] = {c->aml.ast[0], c->aml.ast[1], c->aml.ast[2], c->aml.hm[0], c->aml.hm[1], c->aml.hm[2], c->aml.xfa,
+                     c->aml.xc1, c->aml.dtop, c->aml.partA, c->aml.partB, c->aml.diag};
+    for (double *p : amp)
+      if (p) hipFree(p);
+  }
+  {
+    auto &hh = c->xf.heat;
+    double *hp[] = {hh.fsa, hh.fso, hh.wx, hh.wy, hh.cell, hh.part, hh.scal};
+    for (double *p : hp)
+      if (p) hipFree(p);
+    if (hh.ix) hipFree(hh.ix);
+    if (hh.iy) hipFree(hh.iy);
+  }
   double *atmp[] = {c->atmon.wekta, c->atmon.tauxa, c->atmon.tauya, c->atmon.ast, c->atmon.hmixa, c->atmon.uekat,
                     c->atmon.vekat, c->atmon.psum, c->atmon.pmin, c->atmon.chain, c->atmon.out};
   for (double *p : atmp)
@@ -1084,7 +1119,7 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
     S.dxo = pr.dxo; S.dyo = pr.dyo;
   }
   QgOmlFinal F;
-  fill_oml_final(c, F, oml_final && c->oml.on && part != TEND_OUTER);
+  fill_oml_final(c, F, oml_final && (c->oml.on || c->aml.on) && part != TEND_OUTER);
   const int nextra = part == TEND_INNER ? 0 : (g.cyc ? g.nl * 2 * BSUM_NB : T.nedge);
   dim3 grid(8 * ((ntiles + 7) / 8) + nextra); // 1-D: the kernel maps blockIdx -> tile per XCD band, then edge / line-sum work
   KTimer t(c, KN_TEND);
@@ -1740,6 +1775,9 @@ extern "C" int qgcm_hip_ocqbdy_host(qgcm_hip_handle c, double *q, const double *
 }
 
 static int launch_oml_average(qgcm_hip_ctx *c);
+static int launch_aml(qgcm_hip_ctx *c, bool with_final);
+static int launch_aml_average(qgcm_hip_ctx *c);
+static void aml_set_idx(qgcm_hip_ctx *c, int ia, int iam);
 
 // the whole ocean part of the averaging block src/q-gcm.F:1328-1366: po, qo, constraint scalars and - when the
 // mixed layer lives on the device - sst
@@ -1747,6 +1785,7 @@ extern "C" int qgcm_hip_lf_average(qgcm_hip_handle c) {
   if (check_ready(c, "qgcm_hip_lf_average")) return 1;
   if (launch_lfavg(c)) return 1;
   if (c->oml.on && launch_oml_average(c)) return 1;
+  if (c->aml.on && launch_aml_average(c)) return 1; // ast, hmixa: src/q-gcm.F:1388-1394
   return 0;
 }
 
@@ -1819,10 +1858,16 @@ extern "C" int qgcm_hip_oml_set_forcing(qgcm_hip_handle c, const double *fnetoc,
 }
 
 static void fill_oml_final(qgcm_hip_ctx *c, QgOmlFinal &F, bool on) {
-  const auto &o = c->oml;
   memset(&F, 0, sizeof(F));
-  F.partA = o.partA; F.partB = o.partB; F.nblkA = o.nblkA; F.nblkB = o.nblkB; F.cyc = c->g.cyc; F.on = on ? 1 : 0;
-  F.sc = c->sc; F.diag = o.diag;
+  if (c->aml.on) { // the atmosphere's mixed layer: the same sums under other names (xan, enisat / eninat, cfraat, centat)
+    const auto &a = c->aml;
+    F.partA = a.partA; F.partB = a.partB; F.nblkA = a.nblkA; F.nblkB = a.nblkB; F.diag = a.diag;
+  } else {
+    const auto &o = c->oml;
+    F.partA = o.partA; F.partB = o.partB; F.nblkA = o.nblkA; F.nblkB = o.nblkB; F.diag = o.diag;
+  }
+  F.cyc = c->g.cyc; F.on = on ? 1 : 0;
+  F.sc = c->sc;
   F.ocnorm = 1.0 / ((double)c->g.nxt * (double)(c->g.nyg - 1)); // src/parameters_data.F:88
   F.dxo = c->prm.dxo; F.dyo = c->prm.dyo;
 }
@@ -1972,6 +2017,7 @@ static int sched_block(const qgcm_hip_ctx *c, int s, int n) {
 
 static int one_step(qgcm_hip_ctx *c, int s) {
   if (c->oml.on && launch_oml(c, false)) return 1; // src/q-gcm.F:1232; its final reduction rides in launch_tend
+  if (c->aml.on && launch_aml(c, false)) return 1; // src/q-gcm.F:1260, immediately before qgastep; likewise
   if (sched_due(c->sched[SCH_DUMP], s) && qd_record(c, s)) return 1; // qocdiag_out after oml, before qgostep (src/q-gcm.F:1234-1239)
   const bool fused_constr = !c->g.cyc && can_fuse_dst_unpack(c) && !c->no_fused_constr; // see ocinvq_impl
   if (check_ready(c, "qgcm_hip_steps")) return 1;
@@ -1985,7 +2031,7 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   // (while the po sum is on, the averaging step runs unfused: the sum must see this step's po before it is averaged)
   c->avg_now = avg && (avg_box || avg_cyc) && !c->no_fused_avg && !c->poavg.on;
   const bool avg_fused = c->avg_now;
-  int rc = launch_tend(c, fused_constr, c->oml.on);
+  int rc = launch_tend(c, fused_constr, c->oml.on || c->aml.on);
   if (!rc) {
     c->iq ^= 1; // as qgcm_hip_qgostep
     rc = ocinvq_impl(c, true, true); // ocqbdy fused into the unpack kernel
@@ -1998,6 +2044,7 @@ static int one_step(qgcm_hip_ctx *c, int s) {
     hipLaunchKernelGGL(k_lf_average_scalars, dim3(1), dim3(64), 0, c->stream, c->sc, c->g.nl, c->g.cyc ? 1 : 0);
     HIPCHECK(hipGetLastError());
     if (c->oml.on && launch_oml_average(c)) return 1; // the mixed-layer temperature keeps its own (one-field) pass
+    if (c->aml.on && launch_aml_average(c)) return 1;
   } else if (avg) {
     if (qgcm_hip_lf_average(c)) return 1; // incl. sst when the mixed layer is on
   }
@@ -2018,6 +2065,10 @@ static void oml_rotate(qgcm_hip_ctx *c, int nsteps) {
     c->oml.is = spare;
   }
 }
+// ... and so do the atmosphere's ast / hmixa buffers
+static void aml_rotate(qgcm_hip_ctx *c, int nsteps) {
+  for (int r = 0; r < nsteps % 3; ++r) aml_set_idx(c, 3 - c->aml.ia - c->aml.iam, c->aml.ia);
+}
 
 // One captured block of B consecutive steps. B is even, so both buffer rotations are back where they started
 // after the block; the key carries everything else a captured step depends on: the position in the averaging
@@ -2031,7 +2082,8 @@ static const size_t kMaxGraphs = 96;
 
 static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   const int phase = (s0 - 1) % c->avg_period;
-  const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : 0; // mixed layer on/off and its buffer rotation
+  // mixed layer on/off and its buffer rotation (an ocean handle has the ocean's, an atmosphere handle the atmosphere's)
+  const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : c->aml.on ? 1 + 3 * c->aml.ia + c->aml.iam : 0;
   const long long key = ((long long)B << 32) | ((long long)c->poavg.on << 31) | (omk << 24) | (c->ip << 16) | (c->iq << 8) | phase;
   auto it = c->graphs.find(key);
   if (it != c->graphs.end()) {
@@ -2053,7 +2105,7 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
     }
   }
   hipGraph_t graph;
-  const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
+  const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism, ia0 = c->aml.ia, iam0 = c->aml.iam;
   const long pn0 = c->poavg.n;
   if (sched_block(c, s0, B) < B) // (steps_impl cuts)
     QG_FAIL("qgcm_hip_steps: internal: a graph block would hold a dump step or an accumulation step");
@@ -2066,6 +2118,7 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   c->iq = iq0;
   c->oml.is = is0;
   c->oml.ism = ism0;
+  if (c->aml.on) aml_set_idx(c, ia0, iam0);
   if (rc) return 1;
   HIPCHECK(e);
   hipGraphExec_t exec;
@@ -2096,7 +2149,7 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       if (sched_count(c->sched[a.sched], s0, n) > 0 && a.inputs(c, a.who)) return 1;
     c->graph_call++; // (a dry pass belongs to the call that follows it: qgcm_hip_time_steps, prepare + steps)
   }
-  const int is0 = c->oml.is, ism0 = c->oml.ism, ip0 = c->ip, iq0 = c->iq;
+  const int is0 = c->oml.is, ism0 = c->oml.ism, ip0 = c->ip, iq0 = c->iq, ia0 = c->aml.ia, iam0 = c->aml.iam;
   while (n > 0) {
     const int m = sched_block(c, s, n);
     if (!c->profiling && m >= 2) {
@@ -2108,6 +2161,7 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       s += B;
       n -= B;
       if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
+      if (c->aml.on) aml_rotate(c, B);
       if (!dry && launch_accums(c, s - 1)) return 1; // after the block's last step
       continue;
     }
@@ -2119,6 +2173,7 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       c->ip ^= 1;
       c->iq ^= 1;
       if (c->oml.on) oml_rotate(c, 1);
+      if (c->aml.on) aml_rotate(c, 1);
     }
     ++s;
     --n;
@@ -2126,6 +2181,7 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
   if (dry) {
     c->oml.is = is0;
     c->oml.ism = ism0;
+    if (c->aml.on) aml_set_idx(c, ia0, iam0);
     c->ip = ip0;
     c->iq = iq0;
   }
@@ -2181,6 +2237,203 @@ extern "C" int qgcm_hip_get_bsums(qgcm_hip_handle c, double *b) {
 }
 
 // ---------------------------------------------------------------------------
+// atmospheric mixed layer: src/amlsubs.F on the device, kernels in k_aml.h
+// ---------------------------------------------------------------------------
+// the handles the mixed layer's entry points serve: whole-domain atmosphere handles
+static int aml_handle(qgcm_hip_ctx *c, const char *who) {
+  if (!c) QG_FAIL("%s: null handle", who);
+  if (!c->g.atm) QG_FAIL("%s: the handle is an ocean (its mixed layer is qgcm_hip_oml_*)", who);
+  if (!c->whole) QG_FAIL("%s: the handle is a y-slab (the atmospheric mixed layer needs the whole domain)", who);
+  return check_ready(c, who);
+}
+
+static int aml_ready(qgcm_hip_ctx *c, const char *who) {
+  if (aml_handle(c, who)) return 1;
+  if (!c->aml.on) QG_FAIL("%s: qgcm_hip_aml_init has not been called", who);
+  return 0;
+}
+
+// the buffer rotation; atmon.ast / atmon.hmixa follow the current level
+static void aml_set_idx(qgcm_hip_ctx *c, int ia, int iam) {
+  c->aml.ia = ia;
+  c->aml.iam = iam;
+  c->atmon.ast = c->aml.ast[ia];
+  c->atmon.hmixa = c->aml.hm[ia];
+}
+
+extern "C" int qgcm_hip_aml_init(qgcm_hip_handle c, const qgcm_hip_aml_params *p) {
+  const char *who = "qgcm_hip_aml_init";
+  if (aml_handle(c, who)) return 1;
+  if (!p) QG_FAIL("%s: null parameters", who);
+  if (!(p->hmat > 0.0) || !(p->hmamin > 0.0) || p->tat1 == p->tat2) QG_FAIL("%s: need hmat > 0, hmamin > 0 and tat(1) != tat(2)", who);
+  const QgGeom &g = c->g;
+  const int nxt = g.nxt, nyt = g.ny - 1;
+  if (nxt < 3 || nyt < 3) QG_FAIL("%s: grid too small", who);
+  auto &a = c->aml;
+  auto &m = c->atmon;
+  drop_graphs(c);
+  if (!a.ast[0]) {
+    if (!m.ldt) m.ldt = round_up(nxt, 16);
+    a.ldt = m.ldt;
+    const size_t nT = (size_t)a.ldt * nyt, nP = (size_t)g.ldx * g.ny;
+    a.nblkA = ((nxt + OML_TX - 1) / OML_TX) * ((nyt + AML_SH - 1) / AML_SH);
+    a.nblkB = ((g.nx + OML_TX - 1) / OML_TX) * ((g.ny + OML_TY * OML_RPT - 1) / (OML_TY * OML_RPT));
+    struct { double **ptr; size_t n; } bufs[] = {{&a.ast[0], nT}, {&a.ast[1], nT}, {&a.ast[2], nT}, {&a.hm[0], nT}, {&a.hm[1], nT},
+                                                 {&a.hm[2], nT}, {&a.xfa, nT}, {&a.xc1, nT}, {&a.dtop, nP},
+                                                 {&a.partA, (size_t)3 * a.nblkA}, {&a.partB, (size_t)3 * a.nblkB}, {&a.diag, 2}};
+    bool failed = false;
+    for (auto &b : bufs)
+      if (!failed && dalloc(b.ptr, b.n)) failed = true;
+    // the inputs that others write: fnetat (xforc's heat half or qgcm_hip_set_atm_tav_fields), wekta, uekat, vekat
+    struct { double **ptr; size_t n; } in[] = {{&c->tav.fnet, nT}, {&m.wekta, nT}, {&m.uekat, (size_t)g.ldx * nyt},
+                                               {&m.vekat, (size_t)m.ldt * g.ny}};
+    for (auto &b : in)
+      if (!failed && !*b.ptr && dalloc(b.ptr, b.n)) failed = true;
+    if (failed) { // nothing of the mixed layer stays behind: a later init starts over
+      for (auto &b : bufs) {
+        if (*b.ptr) hipFree(*b.ptr);
+        *b.ptr = nullptr;
+      }
+      return 1;
+    }
+    // what qgcm_hip_set_atm_monitor_fields was given before becomes the current level
+    double *old[2] = {m.ast, m.hmixa}, *cur[2] = {a.ast[0], a.hm[0]};
+    for (int k = 0; k < 2; ++k)
+      if (old[k]) {
+        HIPCHECK(hipMemcpy(cur[k], old[k], nT * sizeof(double), hipMemcpyDeviceToDevice));
+        HIPCHECK(hipFree(old[k]));
+      }
+    aml_set_idx(c, 0, 1);
+  }
+  a.prm = *p;
+  a.prm.xc1ast = a.prm.dtopat = nullptr; // (host pointers are not kept)
+  const size_t nT = (size_t)a.ldt * nyt, nP = (size_t)g.ldx * g.ny;
+  if (p->xc1ast) { if (upload2d(c, a.xc1, a.ldt, p->xc1ast, nxt, nyt)) return 1; }
+  else HIPCHECK(hipMemset(a.xc1, 0, nT * sizeof(double)));
+  if (p->dtopat) { if (upload2d(c, a.dtop, g.ldx, p->dtopat, g.nx, g.ny)) return 1; }
+  else HIPCHECK(hipMemset(a.dtop, 0, nP * sizeof(double)));
+  HIPCHECK(hipDeviceSynchronize());
+  a.on = true;
+  return 0;
+}
+
+extern "C" int qgcm_hip_aml_set_state(qgcm_hip_handle c, const double *ast, const double *astm, const double *hmixa,
+                                      const double *hmixam) {
+  if (aml_ready(c, "qgcm_hip_aml_set_state")) return 1;
+  const auto &a = c->aml;
+  const int nxt = c->g.nxt, nyt = c->g.ny - 1;
+  if (ast && upload2d(c, a.ast[a.ia], a.ldt, ast, nxt, nyt)) return 1;
+  if (astm && upload2d(c, a.ast[a.iam], a.ldt, astm, nxt, nyt)) return 1;
+  if (hmixa && upload2d(c, a.hm[a.ia], a.ldt, hmixa, nxt, nyt)) return 1;
+  if (hmixam && upload2d(c, a.hm[a.iam], a.ldt, hmixam, nxt, nyt)) return 1;
+  return 0;
+}
+
+extern "C" int qgcm_hip_aml_get_state(qgcm_hip_handle c, double *ast, double *astm, double *hmixa, double *hmixam) {
+  if (aml_ready(c, "qgcm_hip_aml_get_state")) return 1;
+  const auto &a = c->aml;
+  const int nxt = c->g.nxt, nyt = c->g.ny - 1;
+  if (ast && download2d(c, ast, a.ast[a.ia], a.ldt, nxt, nyt)) return 1;
+  if (astm && download2d(c, astm, a.ast[a.iam], a.ldt, nxt, nyt)) return 1;
+  if (hmixa && download2d(c, hmixa, a.hm[a.ia], a.ldt, nxt, nyt)) return 1;
+  if (hmixam && download2d(c, hmixam, a.hm[a.iam], a.ldt, nxt, nyt)) return 1;
+  return 0;
+}
+
+static void fill_aml_params(qgcm_hip_ctx *c, QgAmlParams &P) {
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  const auto &a = c->aml;
+  const qgcm_hip_aml_params &q = a.prm;
+  memset(&P, 0, sizeof(P));
+  P.nxt = g.nxt; P.nyt = g.ny - 1; P.nx = g.nx; P.ny = g.ny; P.nl = g.nl;
+  P.ldt = a.ldt; P.ldx = g.ldx; P.fstride = g.fstride;
+  const int spare = 3 - a.ia - a.iam;
+  P.ast = a.ast[a.ia]; P.astm = a.ast[a.iam]; P.astn = a.ast[spare];
+  P.hm = a.hm[a.ia]; P.hmm = a.hm[a.iam]; P.hmn = a.hm[spare];
+  P.fnet = c->tav.fnet; P.wekta = c->atmon.wekta; P.xc1 = a.xc1; P.uekat = c->atmon.uekat; P.vekat = c->atmon.vekat;
+  P.pa = c->p[c->ip]; P.pam = c->p[c->ip ^ 1]; P.dtop = a.dtop;
+  P.xfa = a.xfa; P.entat = c->entoc;
+  P.partA = a.partA; P.partB = a.partB; P.nblkA = a.nblkA; P.nblkB = a.nblkB;
+  // MODULE atconst as src/q-gcm.F:392-441 derives it, then the scalar prologues of aml (src/amlsubs.F:78-90) and amladf (:277-279)
+  const double dxa = pr.dxo, dxam2 = 1.0 / (dxa * dxa);
+  P.rdxaf0 = 1.0 / (dxa * pr.fnot);
+  P.hdxam1 = 0.5 / dxa;
+  P.d2tfac = q.at2d * dxam2;
+  P.d4tfac = q.at4d * (dxam2 * dxam2);
+  P.hmdfac = q.ahmd * dxam2;
+  P.hmat = q.hmat; P.hmamin = q.hmamin;
+  P.hmainv = 1.0 / q.hmat;
+  P.hdrcdt = q.hmadmp * q.rrcpat * pr.tdto;
+  P.diabcr = q.tat1 - 2.0 * P.hdrcdt;
+  P.entfac = 1.0 / (pr.tdto * (q.tat2 - q.tat1));
+  P.xbfac = q.xcexp * q.bface;
+  for (int l = 0; l < g.nl - 1; ++l) P.afacdp[l] = q.aface[l] / pr.gpoc[l];
+  P.dface = q.dface; P.cface = q.cface; P.xcexp = q.xcexp; P.tat1 = q.tat1; P.tdta = pr.tdto; P.rrcpat = q.rrcpat;
+}
+
+// with_final = false: the final reduction rides in workgroup 0 of the tendency launch that follows (one_step)
+static int launch_aml(qgcm_hip_ctx *c, bool with_final) {
+  QgAmlParams P;
+  fill_aml_params(c, P);
+  dim3 gA((P.nxt + OML_TX - 1) / OML_TX, (P.nyt + AML_SH - 1) / AML_SH);
+  dim3 gB((P.nx + OML_TX - 1) / OML_TX, (P.ny + OML_TY * OML_RPT - 1) / (OML_TY * OML_RPT));
+  {
+    KTimer t(c, KN_AML);
+    hipLaunchKernelGGL(k_aml_step, gA, dim3(OML_NT), 0, c->stream, P);
+  }
+  {
+    KTimer t(c, KN_AML_ENTAT);
+    hipLaunchKernelGGL(k_aml_entat, gB, dim3(OML_NT), 0, c->stream, P);
+  }
+  if (with_final) {
+    QgOmlFinal F;
+    fill_oml_final(c, F, true);
+    hipLaunchKernelGGL(k_oml_final, dim3(1), dim3(OML_NT), 0, c->stream, F);
+  }
+  HIPCHECK(hipGetLastError());
+  // rotation: astm <- ast, ast <- new; likewise hmixa (src/amlsubs.F:161-164)
+  aml_set_idx(c, 3 - c->aml.ia - c->aml.iam, c->aml.ia);
+  return 0;
+}
+
+extern "C" int qgcm_hip_aml(qgcm_hip_handle c) {
+  if (aml_ready(c, "qgcm_hip_aml")) return 1;
+  return launch_aml(c, true);
+}
+
+static int launch_aml_average(qgcm_hip_ctx *c) {
+  const auto &a = c->aml;
+  const long n = (long)a.ldt * (c->g.ny - 1);
+  hipLaunchKernelGGL(k_aml_average, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, a.ast[a.ia],
+                     (const double *)a.ast[a.iam], a.hm[a.ia], (const double *)a.hm[a.iam], n);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_aml_get_diag(qgcm_hip_handle c, double *entat, double *diag) {
+  if (aml_ready(c, "qgcm_hip_aml_get_diag")) return 1;
+  const QgGeom &g = c->g;
+  if (entat && download2d(c, entat, c->entoc, g.ldx, g.nx, g.ny)) return 1;
+  if (diag) {
+    QgScalars h;
+    double d[2];
+    HIPCHECK(hipMemcpyAsync(&h, c->sc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipMemcpyAsync(d, c->aml.diag, sizeof(d), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    const int ni = g.nl - 1; // interfaces: the vectors whole, so that a host can see that only their first entries move
+    for (int k = 0; k < ni; ++k) {
+      diag[k] = h.xon[k];
+      diag[ni + k] = h.enisoc[k];
+      diag[2 * ni + k] = h.eninoc[k];
+    }
+    diag[3 * ni] = d[0];
+    diag[3 * ni + 1] = d[1];
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // momentum half of xforc: src/xfosubs.F:137-709 on the device, kernels in k_xforc.h
 // ---------------------------------------------------------------------------
 static void xf_free(qgcm_hip_ctx *a) {
@@ -2192,6 +2445,7 @@ static void xf_free(qgcm_hip_ctx *a) {
   }
   x.on = x.coupled = false;
   x.oc = nullptr;
+  x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
 }
 
 extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
@@ -2326,7 +2580,10 @@ static void xf_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfParams &P) {
   }
 }
 
-// One `call xforc` (momentum half) on the atmosphere's stream, ordered against the ocean's stream by two events.
+static int launch_xf_heat(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm);
+
+// One `call xforc` on the atmosphere's stream, ordered against the ocean's stream by two events: the momentum half and,
+// once qgcm_hip_xforc_heat_init has set it up, the heat half.
 extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
   if (xf_ready(oc, atm, "qgcm_hip_xforc")) return 1;
   auto &x = atm->xf;
@@ -2364,6 +2621,7 @@ extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
   }
   hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
   HIPCHECK(hipGetLastError());
+  if (x.heat.on && launch_xf_heat(oc, atm)) return 1; // the heat half, src/xfosubs.F:711-853
   if (oc) { // the ocean's next step reads wekpo, the stress and the line integrals
     HIPCHECK(hipEventRecord(x.ev_atm, st));
     HIPCHECK(hipStreamWaitEvent(oc->stream, x.ev_atm, 0));
@@ -2407,6 +2665,144 @@ extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, doubl
       txi[2] = h.txisoc;
       txi[3] = h.txinoc;
     }
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// heat half of xforc: src/xfosubs.F:711-853 on the device, kernels in k_xforc.h
+// ---------------------------------------------------------------------------
+static void xf_heat_free(qgcm_hip_ctx *a) {
+  auto &h = a->xf.heat;
+  double **ps[] = {&h.fsa, &h.fso, &h.wx, &h.wy, &h.cell, &h.part, &h.scal};
+  for (double **p : ps) {
+    if (*p) hipFree(*p);
+    *p = nullptr;
+  }
+  if (h.ix) hipFree(h.ix);
+  if (h.iy) hipFree(h.iy);
+  h.ix = h.iy = nullptr;
+  h.on = false;
+}
+
+extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p) {
+  const char *who = "qgcm_hip_xforc_heat_init";
+  if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
+  if (!oc) QG_FAIL("%s: the heat half needs an ocean (oc = NULL)", who);
+  if (!atm->g.atm) QG_FAIL("%s: the second handle is an ocean (pass the atmosphere)", who);
+  if (oc->g.atm) QG_FAIL("%s: the first handle is an atmosphere (pass the ocean)", who);
+  if (!atm->whole || !oc->whole) QG_FAIL("%s: the %s handle is a y-slab (xforc needs the whole domain)", who, atm->whole ? "ocean" : "atmosphere");
+  if (xf_ready(oc, atm, who)) return 1;
+  if (!atm->aml.on) QG_FAIL("%s: qgcm_hip_aml_init has not been called for this atmosphere", who);
+  if (!oc->oml.on) QG_FAIL("%s: qgcm_hip_oml_init has not been called for this ocean", who);
+  if (!p->fsa || !p->fso || !p->xta || !p->yta || !p->xto || !p->yto) QG_FAIL("%s: a table or a coordinate array is NULL", who);
+  const qgcm_hip_xforc_params &x = atm->xf.prm;
+  const int nxta = atm->g.nxt, nyta = atm->g.ny - 1, nxto = oc->g.nxt, nyto = oc->g.ny - 1;
+  // bilint's index and weight tables, as the reference computes them (src/xfosubs.F:916-980)
+  const double dxa = atm->prm.dxo, dya = atm->prm.dyo, dxainv = 1.0 / dxa, dyainv = 1.0 / dya;
+  std::vector<int> ix(2 * (size_t)nxto), iy(2 * (size_t)nyto);
+  std::vector<double> wx(2 * (size_t)nxto), wy(2 * (size_t)nyto);
+  for (int io = 0; io < nxto; ++io) {
+    int iam = (int)(1.0 + dxainv * (p->xto[io] - p->xta[0]));
+    int iap = iam + 1;
+    if (iam > nxta) QG_FAIL("%s: the atmosphere's xta does not cover ocean column %d", who, io + 1);
+    const double xam = iam >= 1 ? p->xta[iam - 1] : p->xta[0] - dxa;
+    wx[nxto + io] = dxainv * (p->xto[io] - xam);
+    wx[io] = 1.0 - wx[nxto + io];
+    iam = 1 + (iam + nxta - 1) % nxta; // (both pointers mended for the cyclic T grid)
+    iap = 1 + (iap + nxta - 1) % nxta;
+    if (iam < 1 || iap < 1) QG_FAIL("%s: the atmosphere's xta does not cover ocean column %d", who, io + 1);
+    ix[io] = iam;
+    ix[nxto + io] = iap;
+  }
+  for (int jo = 0; jo < nyto; ++jo) {
+    int jam = (int)(1.0 + dyainv * (p->yto[jo] - p->yta[0]));
+    int jap = jam + 1;
+    jam = std::max(jam, 1);
+    jap = std::min(jap, nyta);
+    if (jam > nyta || jap < 1) QG_FAIL("%s: the atmosphere's yta does not cover ocean row %d", who, jo + 1);
+    wy[nyto + jo] = dyainv * (p->yto[jo] - p->yta[jam - 1]);
+    wy[jo] = 1.0 - wy[nyto + jo];
+    iy[jo] = jam;
+    iy[nyto + jo] = jap;
+  }
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  xf_heat_free(atm);
+  auto &h = atm->xf.heat;
+  const int ncell = x.nxaooc * x.nyaooc;
+  h.nblkL = ((nxta + 63) / 64) * ((nyta + 3) / 4);
+  if (dalloc(&h.fsa, nyta) || dalloc(&h.fso, nyto) || dalloc(&h.wx, 2 * (size_t)nxto) || dalloc(&h.wy, 2 * (size_t)nyto) ||
+      dalloc(&h.cell, ncell) || dalloc(&h.part, 3 * (size_t)ncell + h.nblkL) || dalloc(&h.scal, 4)) {
+    xf_heat_free(atm);
+    return 1;
+  }
+  if (hipMalloc((void **)&h.ix, 2 * (size_t)nxto * sizeof(int)) != hipSuccess ||
+      hipMalloc((void **)&h.iy, 2 * (size_t)nyto * sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    xf_heat_free(atm);
+    QG_FAIL("%s: out of device memory for the index tables", who);
+  }
+  HIPCHECK(hipMemcpy(h.fsa, p->fsa, nyta * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.fso, p->fso, nyto * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.wx, wx.data(), wx.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.wy, wy.data(), wy.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.ix, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.iy, iy.data(), iy.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHECK(hipDeviceSynchronize());
+  h.prm = *p;
+  h.prm.fsa = h.prm.fso = h.prm.xta = h.prm.yta = h.prm.xto = h.prm.yto = nullptr; // (host pointers are not kept)
+  h.on = true;
+  return 0;
+}
+
+static void xf_heat_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfHeatParams &P) {
+  const auto &h = atm->xf.heat;
+  const qgcm_hip_xforc_heat_params &q = h.prm;
+  const qgcm_hip_xforc_params &x = atm->xf.prm;
+  const auto &a = atm->aml;
+  memset(&P, 0, sizeof(P));
+  P.nxta = atm->g.nxt; P.nyta = atm->g.ny - 1; P.nxto = oc->g.nxt; P.nyto = oc->g.ny - 1;
+  P.ndxr = x.ndxr; P.nx1 = x.nx1; P.ny1 = x.ny1; P.nxaooc = x.nxaooc; P.nyaooc = x.nyaooc;
+  P.ldta = a.ldt; P.lda = atm->g.ldx; P.ldto = oc->oml.ldt; P.fstride = atm->g.fstride;
+  P.astm = a.ast[a.iam]; P.hmm = a.hm[a.iam]; P.pam = atm->p[atm->ip ^ 1]; P.dtop = a.dtop;
+  P.sstm = oc->oml.sst[oc->oml.ism];
+  P.fsa = h.fsa; P.fso = h.fso; P.ix = h.ix; P.iy = h.iy; P.wx = h.wx; P.wy = h.wy;
+  P.fnetoc = oc->oml.fnet; P.fnetat = atm->tav.fnet;
+  P.cell = h.cell; P.part = h.part; P.scal = h.scal;
+  P.ncell = x.nxaooc * x.nyaooc; P.nblkL = h.nblkL; P.natlan = P.nxta * P.nyta - P.ncell;
+  // the scalar prologue, src/xfosubs.F:774-777
+  const double dxo = oc->prm.dxo, dyo = oc->prm.dyo, dxa = atm->prm.dxo, dya = atm->prm.dyo;
+  P.D0up = q.D0up; P.xlamda = q.xlamda; P.Dmdown = q.Dmdown; P.Dmup = q.Dmup; P.dmdu = q.Dmdown - q.Dmup;
+  P.ocfrac = dxo * dyo / (dxa * dya);
+  P.fmafac = q.Adown11 * 0.25 / atm->prm.gpoc[0];
+  P.fmatop = 0.25 * (q.Cmup + q.C1down);
+  P.hmafac = -q.hmadmp - q.Bmup - q.B1down;
+  P.hmat = q.hmat;
+  P.ocnorm = 1.0 / ((double)P.nxto * (double)P.nyto); // src/parameters_data.F:88
+}
+
+static int launch_xf_heat(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm) {
+  QgXfHeatParams P;
+  xf_heat_fill(oc, atm, P);
+  hipStream_t st = atm->stream;
+  hipLaunchKernelGGL(k_xf_heat_oc, dim3(P.nxaooc, P.nyaooc), dim3(64), 0, st, P);
+  hipLaunchKernelGGL(k_xf_heat_atm, dim3((P.nxta + 63) / 64, (P.nyta + 3) / 4), dim3(OML_NT), 0, st, P);
+  hipLaunchKernelGGL(k_xf_heat_final, dim3(1), dim3(OML_NT), 0, st, P);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *fnetoc, double *fnetat, double *scal) {
+  const char *who = "qgcm_hip_xforc_heat_get";
+  if (!oc) QG_FAIL("%s: the heat half needs an ocean (oc = NULL)", who);
+  if (xf_ready(oc, atm, who)) return 1;
+  if (!atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_init has not been called", who);
+  HIPCHECK(hipStreamSynchronize(atm->stream)); // (xforc ran on the atmosphere's stream)
+  if (fnetoc && download2d(oc, fnetoc, oc->oml.fnet, oc->oml.ldt, oc->g.nxt, oc->g.ny - 1)) return 1;
+  if (fnetat && download2d(atm, fnetat, atm->tav.fnet, atm->aml.ldt, atm->g.nxt, atm->g.ny - 1)) return 1;
+  if (scal) {
+    HIPCHECK(hipMemcpyAsync(scal, atm->xf.heat.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, atm->stream));
+    HIPCHECK(hipStreamSynchronize(atm->stream));
   }
   return 0;
 }

@@ -54,6 +54,22 @@ module qgcm_hip_iface
     type(c_ptr) :: stbbb, stbus, stbvs, stbun, stbvn
   end type qgcm_hip_xforc_params
 
+  ! struct qgcm_hip_aml_params: constants of the atmospheric mixed layer (qgcm_hip_aml_init); xc1ast, dtopat = c_loc
+  ! of MODULE atconst's arrays, or c_null_ptr for zeros
+  type, bind(C) :: qgcm_hip_aml_params
+    real(c_double) :: hmat, hmamin, hmadmp, rrcpat, tat1, tat2, xcexp, at2d, at4d, ahmd
+    real(c_double) :: aface(QGCM_HIP_MAXL-1)
+    real(c_double) :: bface, cface, dface
+    type(c_ptr) :: xc1ast, dtopat
+  end type qgcm_hip_aml_params
+
+  ! struct qgcm_hip_xforc_heat_params: constants of the heat half of xforc (qgcm_hip_xforc_heat_init); fsa, fso = c_loc
+  ! of the tables fsprim(ytarel), fsprim(ytorel); xta, yta, xto, yto = c_loc of MODULE atconst's / occonst's vectors
+  type, bind(C) :: qgcm_hip_xforc_heat_params
+    real(c_double) :: xlamda, D0up, Dmup, Dmdown, Adown11, Bmup, B1down, Cmup, C1down, hmadmp, hmat
+    type(c_ptr) :: fsa, fso, xta, yta, xto, yto
+  end type qgcm_hip_xforc_heat_params
+
   interface
     integer(c_int) function qgcm_hip_create(h, prm, device) bind(C, name='qgcm_hip_create')
       import :: c_ptr, c_int, qgcm_hip_params
@@ -523,6 +539,39 @@ module qgcm_hip_iface
       import :: c_ptr, c_int
       type(c_ptr), value :: oc, atm
       integer(c_int), value :: on
+    end function
+    ! atmospheric mixed layer on the device (src/amlsubs.F); every field is a c_ptr (c_loc of the host array, or
+    ! c_null_ptr to leave / skip it); diag(3*(nla-1)+2): xan(:), enisat(:), eninat(:), cfraat, centat
+    integer(c_int) function qgcm_hip_aml_init(atm, prm) bind(C, name='qgcm_hip_aml_init')
+      import :: c_ptr, c_int, qgcm_hip_aml_params
+      type(c_ptr), value :: atm
+      type(qgcm_hip_aml_params), intent(in) :: prm
+    end function
+    integer(c_int) function qgcm_hip_aml_set_state(atm, ast, astm, hmixa, hmixam) bind(C, name='qgcm_hip_aml_set_state')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: atm, ast, astm, hmixa, hmixam
+    end function
+    integer(c_int) function qgcm_hip_aml_get_state(atm, ast, astm, hmixa, hmixam) bind(C, name='qgcm_hip_aml_get_state')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: atm, ast, astm, hmixa, hmixam
+    end function
+    integer(c_int) function qgcm_hip_aml(atm) bind(C, name='qgcm_hip_aml')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: atm
+    end function
+    integer(c_int) function qgcm_hip_aml_get_diag(atm, entat, diag) bind(C, name='qgcm_hip_aml_get_diag')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: atm, entat, diag
+    end function
+    ! heat half of xforc on the device (src/xfosubs.F:711-853); scal: arlaav, slhfav, oradav, arocav
+    integer(c_int) function qgcm_hip_xforc_heat_init(oc, atm, prm) bind(C, name='qgcm_hip_xforc_heat_init')
+      import :: c_ptr, c_int, qgcm_hip_xforc_heat_params
+      type(c_ptr), value :: oc, atm
+      type(qgcm_hip_xforc_heat_params), intent(in) :: prm
+    end function
+    integer(c_int) function qgcm_hip_xforc_heat_get(oc, atm, fnetoc, fnetat, scal) bind(C, name='qgcm_hip_xforc_heat_get')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: oc, atm, fnetoc, fnetat, scal
     end function
   end interface
 

@@ -8,7 +8,8 @@ program performs before the time loop.  There is no CPU fallback: importing
 works anywhere, but constructing an :class:`OceanModel` without the built
 library or without a HIP device raises.
 """
-from .config import AtmosConfig, OceanConfig, OmlConfig, PRESETS, atmos_of, atmos_preset, oml_preset, preset  # noqa: F401
+from .config import AmlConfig, AtmosConfig, HeatConfig, OceanConfig, OmlConfig, PRESETS, atmos_of, atmos_preset, oml_preset, preset  # noqa: F401
 from .lib import QgcmHipError, check, load_library, library_path  # noqa: F401
-from .model import AtmosModel, OceanModel, coupled_steps, share_gpu, xforc, xforc_get, xforc_setup  # noqa: F401
+from .model import (AtmosModel, OceanModel, coupled_steps, share_gpu, xforc, xforc_get, xforc_heat_get,  # noqa: F401
+                    xforc_heat_setup, xforc_setup)
 from . import hostinit, synth  # noqa: F401

@@ -119,6 +119,50 @@ def oml_preset(cfg, sb_hflux=False, nb_hflux=False):
 
 
 @dataclass(frozen=True)
+class AmlConfig:
+    """Run-time parameters of the atmospheric mixed layer (aml / amladf, src/amlsubs.F).  tat(1:2), the layer
+    temperature anomalies, and the entrainment factors aface(1:nla-1), bface, cface, dface are products of the
+    reference's radiation set-up (radiat), which stays on the host: they have no defaults.  The others default to
+    the double-gyre input.params (hmat, hmamin, hmadmp, xcexp, rhoat, cpat, and the diffusivities of its 80 km grid)."""
+    tat: Tuple[float, float]
+    aface: Tuple[float, ...]
+    bface: float
+    cface: float
+    dface: float
+    hmat: float = 1000.0
+    hmamin: float = 100.0
+    hmadmp: float = 0.15
+    xcexp: float = 1.0
+    at2d: float = 2.5e4
+    at4d: float = 2.0e14
+    ahmd: float = 2.0e5
+    rhoat: float = 1.0
+    cpat: float = 1.0e3
+
+    @property
+    def rrcpat(self):  # src/q-gcm.F:437
+        return 1.0 / (self.rhoat * self.cpat)
+
+
+@dataclass(frozen=True)
+class HeatConfig:
+    """Run-time parameters of the heat half of xforc (src/xfosubs.F:711-853): the radiation coefficients of radiat
+    (no defaults: the host's radiation set-up hands them in; Adown11 = Adown(1,1)), the sensible + latent transfer
+    coefficient xlamda and the signed perturbation amplitude fspco of fsprim (double-gyre input.params: 35 and
+    fspamp = 80 with the sign of fnot)."""
+    D0up: float
+    Dmup: float
+    Dmdown: float
+    Adown11: float
+    Bmup: float
+    B1down: float
+    Cmup: float
+    C1down: float
+    xlamda: float = 35.0
+    fspco: float = 80.0
+
+
+@dataclass(frozen=True)
 class AtmosConfig:
     """The atmospheric channel of a coupled run: MODULE parameters nxta, nyta, nla, fnot, beta
     and the input.params entries dta, bccoat, ah4at, hat, gpat (src/in_param.f); dxa = ndxr*dxo (src/q-gcm.F:380).

@@ -420,3 +420,49 @@ def bcuini(ndxr, bccoat, dya):
         stb[:, :, ndxr] = 0.0
         out["stb" + ("bb" if case == "bb" else case)] = np.asfortranarray(stb)
     return out
+
+
+def fsprim(yrel, fspco, yla):
+    """The perturbative radiative forcing fsprim(yrel) of src/xfosubs.F:862-887 (yrel: y relative to the central
+    latitude; fspco: its signed peak-to-trough amplitude; yla: the atmosphere's y range)."""
+    pi = 3.14159265358979324
+    return fspco * 0.5 * np.sin(pi * np.asarray(yrel, dtype=np.float64) / yla)
+
+
+def grid_coordinates(acfg, ocfg, nx1=None, ny1=None):
+    """The T-point coordinates xta, yta, xto, yto of both grids and the relative latitudes ytarel, ytorel as the main
+    program derives them (src/q-gcm.F:394-431); nx1, ny1 default to MODULE parameters' centring."""
+    dxa, dxo = acfg.dxa, ocfg.dxo
+    nx1 = 1 + (acfg.nxta - ocfg.nxaooc) // 2 if nx1 is None else nx1
+    ny1 = 1 + (acfg.nyta - ocfg.nyaooc) // 2 if ny1 is None else ny1
+    yla = acfg.nyta * dxa
+    xta = np.arange(acfg.nxta, dtype=np.float64) * dxa + 0.5 * dxa
+    yta = np.arange(acfg.nyta, dtype=np.float64) * dxa + 0.5 * dxa
+    xto = (np.arange(ocfg.nxto, dtype=np.float64) * dxo + (nx1 - 1) * dxa) + 0.5 * dxo
+    yto = ((ny1 - 1) * dxa + np.arange(ocfg.nyto, dtype=np.float64) * dxo) + 0.5 * dxo
+    return dict(xta=xta, yta=yta, xto=xto, yto=yto, ytarel=yta - 0.5 * yla, ytorel=yto - 0.5 * yla, yla=yla)
+
+
+def bilint_tables(xta, yta, xto, yto, dxa, dya):
+    """The index and weight vectors bilint derives for interpolating an atmospheric T-grid field onto the ocean's T
+    points (src/xfosubs.F:916-980): per ocean column iam, iap (1-based, after the cyclic mending of both) and wmx, wpx
+    (from xam = xa(1) - dxa where the column lies west of the first atmospheric point); per ocean row jam, jap (clamped
+    to 1..nyta: no normal derivative) and wmy, wpy.  The interpolant is
+    wmx*wmy*a(iam,jam) + wpx*wmy*a(iap,jam) + wmx*wpy*a(iam,jap) + wpx*wpy*a(iap,jap)."""
+    xta, yta, xto, yto = (np.asarray(v, dtype=np.float64) for v in (xta, yta, xto, yto))
+    nxat, nyat = len(xta), len(yta)
+    dxainv, dyainv = 1.0 / dxa, 1.0 / dya
+    iam = np.trunc(1.0 + dxainv * (xto - xta[0])).astype(np.int64)  # int() truncates towards zero
+    iap = iam + 1
+    xam = np.where(iam >= 1, xta[np.clip(iam, 1, nxat) - 1], xta[0] - dxa)
+    wpx = dxainv * (xto - xam)
+    wmx = 1.0 - wpx
+    iam = 1 + np.mod(iam + nxat - 1, nxat)
+    iap = 1 + np.mod(iap + nxat - 1, nxat)
+    jam = np.trunc(1.0 + dyainv * (yto - yta[0])).astype(np.int64)
+    jap = np.minimum(jam + 1, nyat)
+    jam = np.maximum(jam, 1)
+    wpy = dyainv * (yto - yta[jam - 1])
+    wmy = 1.0 - wpy
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+    return dict(iam=i32(iam), iap=i32(iap), wmx=wmx, wpx=wpx, jam=i32(jam), jap=i32(jap), wmy=wmy, wpy=wpy)

@@ -77,6 +77,24 @@ class XforcParams(C.Structure):
     ]
 
 
+class AmlParams(C.Structure):
+    """struct qgcm_hip_aml_params (include/qgcm_hip.h)."""
+    _fields_ = [
+        ("hmat", C.c_double), ("hmamin", C.c_double), ("hmadmp", C.c_double), ("rrcpat", C.c_double),
+        ("tat1", C.c_double), ("tat2", C.c_double), ("xcexp", C.c_double),
+        ("at2d", C.c_double), ("at4d", C.c_double), ("ahmd", C.c_double),
+        ("aface", C.c_double * (MAXL - 1)), ("bface", C.c_double), ("cface", C.c_double), ("dface", C.c_double),
+        ("xc1ast", C.POINTER(C.c_double)), ("dtopat", C.POINTER(C.c_double)),
+    ]
+
+
+class XforcHeatParams(C.Structure):
+    """struct qgcm_hip_xforc_heat_params (include/qgcm_hip.h)."""
+    _fields_ = [(n, C.c_double) for n in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup",
+                                          "C1down", "hmadmp", "hmat")] + [
+        (n, C.POINTER(C.c_double)) for n in ("fsa", "fso", "xta", "yta", "xto", "yto")]
+
+
 TAV_NOUT = 16  # QGCM_HIP_TAV_NOUT
 ATM_TAV_NOUT = 15  # QGCM_HIP_ATM_TAV_NOUT
 
@@ -114,6 +132,8 @@ SYMBOLS = [
     "qgcm_hip_cov_init", "qgcm_hip_cov_size", "qgcm_hip_cov_add", "qgcm_hip_cov_reset", "qgcm_hip_cov_out",
     "qgcm_hip_cov_schedule", "qgcm_hip_cov_part_len", "qgcm_hip_cov_part", "qgcm_hip_cov_combine",
     "qgcm_hip_xforc_init", "qgcm_hip_xforc", "qgcm_hip_xforc_get", "qgcm_hip_coupled_set_xforc",
+    "qgcm_hip_aml_init", "qgcm_hip_aml_set_state", "qgcm_hip_aml_get_state", "qgcm_hip_aml", "qgcm_hip_aml_get_diag",
+    "qgcm_hip_xforc_heat_init", "qgcm_hip_xforc_heat_get",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
 ]
 
@@ -253,6 +273,13 @@ def load_library():
     L.qgcm_hip_xforc.argtypes = [vp, vp]
     L.qgcm_hip_xforc_get.argtypes = [vp, vp] + [dp] * 11
     L.qgcm_hip_coupled_set_xforc.argtypes = [vp, vp, C.c_int]
+    L.qgcm_hip_aml_init.argtypes = [vp, C.POINTER(AmlParams)]
+    L.qgcm_hip_aml_set_state.argtypes = [vp, dp, dp, dp, dp]
+    L.qgcm_hip_aml_get_state.argtypes = [vp, dp, dp, dp, dp]
+    L.qgcm_hip_aml.argtypes = [vp]
+    L.qgcm_hip_aml_get_diag.argtypes = [vp, dp, dp]
+    L.qgcm_hip_xforc_heat_init.argtypes = [vp, vp, C.POINTER(XforcHeatParams)]
+    L.qgcm_hip_xforc_heat_get.argtypes = [vp, vp, dp, dp, dp]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

@@ -861,6 +861,61 @@ class AtmosModel(OceanModel):
     def covocn(self):
         raise QgcmHipError("covocn is the ocean's; an atmosphere handle accumulates with covatm()")
 
+    # -- atmospheric mixed layer (`call aml`, src/q-gcm.F:1260) -----------------------------------------
+    def aml_init(self, am, xc1ast=None, dtopat=None):
+        """Switch the mixed layer on (am: qgcm_hip.config.AmlConfig; xc1ast (nxta,nyta), dtopat (nxpa,nypa): None =
+        zeros): the model then owns ast, astm, hmixa, hmixam; steps() / coupled_steps() run aml before qgastep in every
+        step and average ast, hmixa with the other fields; the monitors, atm_valids, tavatm, covatm and atmos_dump read
+        the stepped ast / hmixa (what set_atm_monitor_fields gave before is kept as the current level)."""
+        from .lib import AmlParams
+        c = self.cfg
+        p = AmlParams()
+        p.hmat, p.hmamin, p.hmadmp, p.rrcpat = am.hmat, am.hmamin, am.hmadmp, am.rrcpat
+        p.tat1, p.tat2, p.xcexp = am.tat[0], am.tat[1], am.xcexp
+        p.at2d, p.at4d, p.ahmd = am.at2d, am.at4d, am.ahmd
+        if len(am.aface) != c.nla - 1:
+            raise QgcmHipError("aml_init: aface has %d entries, need nla - 1 = %d" % (len(am.aface), c.nla - 1))
+        for l, v in enumerate(am.aface):
+            p.aface[l] = v
+        p.bface, p.cface, p.dface = am.bface, am.cface, am.dface
+        x, d = _f(xc1ast), _f(dtopat)
+        if x is not None and x.shape != (c.nxta, c.nyta):
+            raise QgcmHipError("aml_init: xc1ast has shape %s, need (%d, %d)" % (x.shape, c.nxta, c.nyta))
+        if d is not None and d.shape != (c.nxpa, c.nypa):
+            raise QgcmHipError("aml_init: dtopat has shape %s, need (%d, %d)" % (d.shape, c.nxpa, c.nypa))
+        p.xc1ast, p.dtopat = _dp(x), _dp(d)
+        check(self.L.qgcm_hip_aml_init(self.h, C.byref(p)))
+        self.aml_cfg = am
+
+    def aml_set_state(self, ast=None, astm=None, hmixa=None, hmixam=None):
+        a = [_f(x) for x in (ast, astm, hmixa, hmixam)]
+        for x in a:
+            assert x is None or x.shape == (self.cfg.nxta, self.cfg.nyta)
+        check(self.L.qgcm_hip_aml_set_state(self.h, *[_dp(x) for x in a]))
+
+    def aml_get_state(self):
+        """ast, astm, hmixa, hmixam (nxta, nyta)."""
+        a = [np.zeros((self.cfg.nxta, self.cfg.nyta), order="F") for _ in range(4)]
+        check(self.L.qgcm_hip_aml_get_state(self.h, *[_dp(x) for x in a]))
+        return a
+
+    def aml(self):
+        """One `call aml` from the device state; asynchronous."""
+        check(self.L.qgcm_hip_aml(self.h))
+
+    def aml_get_diag(self):
+        """entat (nxpa, nypa) and dict(xan, enisat, eninat, cfraat, centat): the first entries of xan, enisat, eninat
+        where qgastep reads them and the two monitors; xan_v, enisat_v, eninat_v: the whole vectors (nla-1) - aml
+        writes their first entries only."""
+        ni = self.cfg.nla - 1
+        e = np.zeros((self.cfg.nxpa, self.cfg.nypa), order="F")
+        d = np.zeros(3 * ni + 2)
+        check(self.L.qgcm_hip_aml_get_diag(self.h, _dp(e), _dp(d)))
+        out = dict(xan=float(d[0]), enisat=float(d[ni]), eninat=float(d[2 * ni]), cfraat=float(d[3 * ni]),
+                   centat=float(d[3 * ni + 1]))
+        out.update(xan_v=tuple(d[:ni]), enisat_v=tuple(d[ni:2 * ni]), eninat_v=tuple(d[2 * ni:3 * ni]))
+        return e, out
+
     pa = OceanModel.po
     pam = OceanModel.pom
     qa = OceanModel.qo
@@ -925,6 +980,7 @@ def xforc_setup(ocean, atmos, cdat=1.3e-3, rhoat=1.0, rhooc=1.0e3, hmat=1000.0, 
     p.tau_udiff = int(bool(tau_udiff))
     p.stbbb, p.stbus, p.stbvs, p.stbun, p.stbvn = [_dp(t) for t in keep]
     check(atmos.L.qgcm_hip_xforc_init(ocean.h if ocean is not None else None, atmos.h, C.byref(p)))
+    atmos.xforc_origin = (int(p.nx1), int(p.ny1))  # (where xforc_heat_setup finds the ocean)
 
 
 def xforc(ocean, atmos):
@@ -951,10 +1007,60 @@ def xforc_get(ocean, atmos, names=None):
     return out
 
 
+HEAT_SCALARS = ("arlaav", "slhfav", "oradav", "arocav")
+
+
+def xforc_heat_setup(ocean, atmos, heat, hmadmp=None, hmat=None, fsa=None, fso=None, coords=None):
+    """Set up the heat half of xforc on the device (qgcm_hip_xforc_heat_init) after xforc_setup(ocean,
+    atmos), atmos.aml_init and ocean.oml_init: xforc() and coupled_steps(..., xforc=True) then also compute fnetoc
+    (into the ocean mixed layer's forcing) and fnetat (where aml reads it).  heat: qgcm_hip.config.HeatConfig; hmadmp,
+    hmat default to the values aml_init was given.  fsa / fso: the tables fsprim(ytarel(1:nyta)) / fsprim(ytorel(1:nyto))
+    (default hostinit.fsprim); coords: dict(xta, yta, xto, yto), default hostinit.grid_coordinates with the ocean
+    placed where xforc_setup placed it (its nx1, ny1)."""
+    from .lib import XforcHeatParams
+    if ocean is None:  # (the library's own refusal: no coordinate can be derived without an ocean, so nothing else is passed)
+        check(atmos.L.qgcm_hip_xforc_heat_init(None, atmos.h, C.byref(XforcHeatParams())))
+    am = getattr(atmos, "aml_cfg", None)
+    if (hmadmp is None or hmat is None) and am is None:
+        raise QgcmHipError("xforc_heat_setup: call atmos.aml_init first (qgcm_hip_aml_init has not been called)")
+    nx1, ny1 = getattr(atmos, "xforc_origin", (None, None))  # the position xforc_setup was given
+    G = hostinit.grid_coordinates(atmos.cfg, ocean.cfg, nx1=nx1, ny1=ny1)
+    if coords is not None:
+        G = dict(G, **coords)
+    fsa = hostinit.fsprim(G["ytarel"], heat.fspco, G["yla"]) if fsa is None else fsa
+    fso = hostinit.fsprim(G["ytorel"], heat.fspco, G["yla"]) if fso is None else fso
+    keep = [np.ascontiguousarray(v, dtype=np.float64) for v in (fsa, fso, G["xta"], G["yta"], G["xto"], G["yto"])]
+    want = (atmos.cfg.nyta, ocean.cfg.nyto, atmos.cfg.nxta, atmos.cfg.nyta, ocean.cfg.nxto, ocean.cfg.nyto)
+    for v, n, name in zip(keep, want, ("fsa", "fso", "xta", "yta", "xto", "yto")):
+        if v.shape != (n,):
+            raise QgcmHipError("xforc_heat_setup: %s has shape %s, need (%d,)" % (name, v.shape, n))
+    p = XforcHeatParams()
+    for k in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup", "C1down"):
+        setattr(p, k, float(getattr(heat, k)))
+    p.hmadmp = float(am.hmadmp if hmadmp is None else hmadmp)
+    p.hmat = float(am.hmat if hmat is None else hmat)
+    p.fsa, p.fso, p.xta, p.yta, p.xto, p.yto = [_dp(v) for v in keep]
+    check(atmos.L.qgcm_hip_xforc_heat_init(ocean.h, atmos.h, C.byref(p)))
+
+
+def xforc_heat_get(ocean, atmos):
+    """The outputs of the heat half of the last xforc: dict(fnetoc (nxto,nyto), fnetat (nxta,nyta), arlaav, slhfav,
+    oradav, arocav)."""
+    o, a = ocean.cfg, atmos.cfg
+    fo, fa, sc = np.zeros((o.nxto, o.nyto), order="F"), np.zeros((a.nxta, a.nyta), order="F"), np.zeros(4)
+    check(atmos.L.qgcm_hip_xforc_heat_get(ocean.h if ocean is not None else None, atmos.h, _dp(fo), _dp(fa), _dp(sc)))
+    out = dict(fnetoc=fo, fnetat=fa)
+    out.update({k: float(v) for k, v in zip(HEAT_SCALARS, sc)})
+    return out
+
+
 def coupled_steps(ocean, atmos, nt0, n, nstr, xforc=False):
     """n atmospheric steps nt = nt0.. with one ocean step before every one with mod(nt,nstr) == 1
     (src/q-gcm.F:1220-1268); either model may be None.  xforc = False: the forcing is held.  xforc = True (after
-    xforc_setup): the momentum half of xforc runs on the device before every ocean step, in the reference's order."""
+    xforc_setup): xforc runs on the device before every ocean step, in the reference's order - the momentum half and,
+    after xforc_heat_setup, the heat half.  After atmos.aml_init every atmospheric step runs aml before qgastep, and
+    after ocean.oml_init every ocean step runs oml: with all of them the window is the reference's full sequence
+    xforc; oml; qgostep ...; (aml; qgastep ...) x nstr without a host transfer."""
     L = (ocean or atmos).L
     oh, ah = ocean.h if ocean is not None else None, atmos.h if atmos is not None else None
     if xforc or atmos is not None:
