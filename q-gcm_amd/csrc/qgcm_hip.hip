@@ -286,7 +286,7 @@ struct qgcm_hip_ctx {
   size_t dst_lds;
 };
 
-static const int kGraphBlock = 50; // y-slab step graphs (qgcm_hip_slab_steps)
+static const int kGraphBlock = 50; // steps per captured block (qgcm_hip_steps: get_graph; y-slabs: qgcm_hip_slab_steps)
 
 extern "C" const char *qgcm_hip_last_error(void) { return g_err; }
 extern "C" int qgcm_hip_abi_version(void) { return QGCM_HIP_ABI_VERSION; }
@@ -536,10 +536,13 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   return 0;
 }
 
+// rows per thread the Thomas kernel is instantiated for; 10 / 20: the 600- and 1200-row slabs of NAtl 1 km
+#define QG_TH_ROWS(X) X(1) X(2) X(4) X(8) X(10) X(12) X(16) X(20) X(24) X(32)
 static int thomas_rows_per_chunk(int nrows) {
   const int need = (nrows + TH_NC - 1) / TH_NC;
-  for (int r : {1, 2, 4, 8, 10, 12, 16, 20, 24, 32}) // rows per thread; 10 / 20: the 600- and 1200-row slabs of NAtl 1 km
-    if (need <= r) return r;
+#define QG_TH_FITS(RV) if (need <= RV) return RV;
+  QG_TH_ROWS(QG_TH_FITS)
+#undef QG_TH_FITS
   return -1;
 }
 
@@ -622,9 +625,23 @@ static int upload_pivots(qgcm_hip_ctx *c, QgThomasTab &D, const ThomasTabHost &T
 static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, int nlayers, int phase,
                          const double *gath, double *send, int rank, int nranks, int layer0, hipStream_t st,
                          bool cyc_part_a = false);
-static void fill_cyc_constr_params(qgcm_hip_ctx *c, QgCycConstrParams &Q);
 
-static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, double *wrk, const QgThomasTab &tab, int nlayers, int layer0);
+static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, double *wrk, const QgThomasTab &tab, int nlayers, int layer0) {
+  const QgGeom &g = c->g;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.gath_stride = (long)slab_msg_len_oml(c);
+  P.slabDE = c->slabDE;
+  P.ksum = c->ksum;
+  P.wrk = wrk;
+  P.binf = tab.binf; P.ptab = tab.ptab; P.rcb = tab.rcb; P.poff = tab.poff;
+  P.nblk = (g.nk + TH_KW - 1) / TH_KW;
+  P.aoc = c->prm.aoc;
+  P.ftnorm = g.cyc ? 1.0 / g.nxt : 0.5 / g.nxt; // src/ocisubs.F:440, 547
+  P.nlayers = nlayers;
+  P.layer0 = layer0;
+  P.nranks = 1;
+}
 
 // Set-up of the y-slab solve (k_thomas.h): PHASE 4 / 5 give the slab's gain and response sums (slabDE) and leave the
 // responses Pv / Qv to unit inflows in the work array; they are tabulated per block of TH_KW wavenumbers as far as
@@ -746,6 +763,7 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
       HIPCHECK(hipFuncSetAttribute((const void *)k_rfft_cyc<false, PL, FFT3_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->fft3_lds)); \
       HIPCHECK(hipFuncSetAttribute((const void *)k_rfft_cyc<true, PL, FFT3_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->fft3_lds)); \
       HIPCHECK(hipFuncSetAttribute((const void *)k_rfft3_unpack<PL, 3, FFT3_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->fft3_lds)); \
+      HIPCHECK(hipFuncSetAttribute((const void *)k_rfft3_unpack<PL, 3, FFT3_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->fft3_lds)); \
     }
     QG_FFT3_PLANS(QG_FFT3_SETUP)
 #undef QG_FFT3_SETUP
@@ -792,7 +810,63 @@ static int lu_factor(int n, double *a, int *piv) {
   return 0;
 }
 
-static void fill_constr_params(qgcm_hip_ctx *c, QgConstrParams &P);
+// what the box and the cyclic constraint parameters share (QgConstrParams, QgCycConstrParams)
+template <class T>
+static void fill_constr_common(const qgcm_hip_ctx *c, T &P) {
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.ksum = c->ksum;
+  P.wrk = c->wrk;
+  P.sc = c->sc;
+  P.cs = c->cs;
+  P.dxo = pr.dxo; P.dyo = pr.dyo; P.tdto = pr.tdto; P.fnot = pr.fnot;
+  for (int k = 0; k < g.nl; ++k) {
+    P.gpoc[k] = pr.gpoc[k];
+    P.hoc[k] = pr.hoc[k];
+  }
+  for (int i = 0; i < g.nl * g.nl; ++i) {
+    P.ctl2m[i] = pr.ctl2moc[i];
+    P.ctm2l[i] = pr.ctm2loc[i];
+  }
+}
+
+static void fill_constr_params(const qgcm_hip_ctx *c, QgConstrParams &P) {
+  fill_constr_common(c, P);
+  P.rowsum = c->rowsum;
+  P.wcot = c->wcot;
+}
+
+// ... packed for the extra wave of k_dst64_unpack (nlo <= 4, qgcm_dev.h)
+static void fill_constr_lite(const qgcm_hip_ctx *c, QgConstrLite &C) {
+  memset(&C, 0, sizeof(C));
+  C.g = c->g; C.ksum = c->ksum; C.wcot = c->wcot; C.sc = c->sc;
+  C.dxo = c->prm.dxo; C.dyo = c->prm.dyo;
+  for (int i = 0; i < 16; ++i) { C.cs.cdiffo[i] = c->cs.cdiffo[i]; C.cs.cdhoc[i] = c->cs.cdhoc[i]; C.cs.cdhlu[i] = c->cs.cdhlu[i]; }
+  for (int i = 0; i < 4; ++i) C.cs.ipiv[i] = c->cs.ipiv[i];
+}
+
+static void fill_cyc_constr_params(const qgcm_hip_ctx *c, QgCycConstrParams &Q) {
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  fill_constr_common(c, Q);
+  Q.bpart = Q.bpart_n = c->bpart;
+  Q.ybnd = c->ybnd; // k_thomas (PHASE 0 and PHASE 2 alike) leaves the zonal-mean rows next to the boundaries there
+  if (c->slab_gath) {
+    // y-slab stages: the boundary line sums travel at the end of the step messages (rank 0 owns the southern boundary,
+    // the last rank the northern one); the solution next to the boundaries comes from k_thomas PHASE 2
+    const size_t off = (size_t)TH_MSG * g.nl * g.ldw;
+    Q.bpart = c->slab_gath + off;
+    Q.bpart_n = c->slab_gath + (size_t)(c->slab_nranks - 1) * slab_msg_len_oml(c) + off;
+  }
+  Q.adfaco = 1.0 / (12.0 * pr.dxo * pr.dyo * pr.fnot);
+  Q.delek_sgn = 0.5 * (pr.fnot >= 0.0 ? 1.0 : -1.0) * pr.delek;
+  for (int k = 0; k < g.nl; ++k) {
+    Q.ah2oc[k] = pr.ah2oc[k];
+    Q.ah4oc[k] = pr.ah4oc[k];
+  }
+}
 
 extern "C" int qgcm_hip_set_homog_box(qgcm_hip_handle c, const double *ochom, const double *cdiffo, const double *cdhoc) {
   if (!c || !ochom || !cdiffo || !cdhoc) QG_FAIL("qgcm_hip_set_homog_box: null argument");
@@ -1050,7 +1124,20 @@ static void drain_timers(qgcm_hip_ctx *c) {
   c->evkid.clear();
 }
 
-static void fill_oml_final(qgcm_hip_ctx *c, QgOmlFinal &F, bool on);
+static void fill_oml_final(qgcm_hip_ctx *c, QgOmlFinal &F, bool on) {
+  memset(&F, 0, sizeof(F));
+  if (c->aml.on) { // the atmosphere's mixed layer: the same sums under other names (xan, enisat / eninat, cfraat, centat)
+    const auto &a = c->aml;
+    F.partA = a.partA; F.partB = a.partB; F.nblkA = a.nblkA; F.nblkB = a.nblkB; F.diag = a.diag;
+  } else {
+    const auto &o = c->oml;
+    F.partA = o.partA; F.partB = o.partB; F.nblkA = o.nblkA; F.nblkB = o.nblkB; F.diag = o.diag;
+  }
+  F.cyc = c->g.cyc; F.on = on ? 1 : 0;
+  F.sc = c->sc;
+  F.ocnorm = 1.0 / ((double)c->g.nxt * (double)(c->g.nyg - 1)); // src/parameters_data.F:88
+  F.dxo = c->prm.dxo; F.dyo = c->prm.dyo;
+}
 
 // part: TEND_ALL = the whole launch; TEND_INNER = the tile rows whose stencils stay inside the owned rows (they need no
 // halo row: y-slabs run them while the halo exchange of the previous step is still under way) plus the one-thread /
@@ -1062,10 +1149,70 @@ static bool tend_can_split(const qgcm_hip_ctx *c) {
   return T.gy >= 3;
 }
 
-// write-through pair stores of the new qo (and 16-wide tiles) while the fields fit the Infinity Cache; plain stores and
-// 32-wide tiles beyond (k_tend.h)
-static bool tend_wtq(const qgcm_hip_ctx *c) {
-  return (double)c->g.fstride * 8.0 * (7 * c->g.nl - 1) < 200.0e6 && !c->tend_wide;
+// The step plan: which launches one inversion makes, derived in ONE place from the geometry and the handle's switches
+// (DESIGN 3.5 has the table).  ocinvq_impl, one_step, launch_tend, launch_dst and the slab stages 1 / 2 read it.
+enum { ROWS_GENERIC = 0, ROWS_DST64, ROWS_RFFT64, ROWS_FFT3 };                    // the row kernels' family
+enum { INV_PLAIN = 0, INV_DST64_UNPACK, INV_RFFT64_UNPACK, INV_FFT3_UNPACK };      // inverse rows: alone, or fused with the unpack
+enum { CONSTR_OWN = 0, CONSTR_INV_WAVE, CONSTR_BOX_WG, CONSTR_AB };                // where the constraint solve runs
+struct QgStepPlan {
+  int rows;     // ROWS_GENERIC: k_dst_box / k_rfft_cyc (Stockham); ROWS_DST64 / ROWS_RFFT64: a wave per row pair (k_dst64.h,
+                // k_rfft64.h); ROWS_FFT3: the three-stage plans of k_fft3.h
+  int m64;      // wave-per-row-pair families: nxto = 64 * m64
+  int inv;      // INV_PLAIN: launch_dst + launch_unpack; else k_dst64_unpack / k_rfft64_unpack / k_rfft3_unpack
+  int constr;   // CONSTR_OWN: a launch of its own (k_constr_box / k_constr_cyc); CONSTR_INV_WAVE: the extra wave of
+                // k_dst64_unpack; CONSTR_BOX_WG: the extra workgroup of the generic box inverse rows; CONSTR_AB: part A in
+                // the Thomas launch, part B in the inverse launch (cyclic)
+  bool upd_dpi; // k_tend steps dpioc / dpiocp (the constraint solve of CONSTR_INV_WAVE starts from the stepped values)
+  bool wtq;     // k_tend: write-through pair stores of the new qo and 16-wide tiles
+  bool avg_ok;  // a leapfrog-averaging step may be fused into k_tend and the fused inverse kernel (avg_now)
+};
+
+// in_step: inside qgcm_hip_steps (k_tend has stepped dpioc where the plan says so, the boundary PV is fused into the
+// unpack); slab: the stages 1 / 2 of qgcm_hip_slab_stage
+static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool slab = false) {
+  const QgGeom &g = c->g;
+  QgStepPlan pl;
+  // the row lengths with a wave-per-row-pair kernel: an in-register M-point DFT exists for M = 3, 15 and (k_rfft64.h) 6
+  const int N = c->fftN;
+  pl.m64 = c->force_generic_dst ? 0 : (N == 64 * 3 ? 3 : N == 64 * 15 ? 15 : (g.cyc && N == 64 * 6) ? 6 : 0);
+  pl.rows = (c->fft3 && !c->force_generic_dst) ? ROWS_FFT3 : pl.m64 ? (g.cyc ? ROWS_RFFT64 : ROWS_DST64) : ROWS_GENERIC;
+  // inverse rows + homogeneous corrections + modes -> layers (+ boundary PV) in one launch, 2 .. 4 layers:
+  // box (k_dst64_unpack); cyclic / atmosphere, whole domain (k_rfft64_unpack; the slab stages keep the plain rows);
+  // long cyclic ocean rows of three layers (k_fft3_unpack.h: it reads the solved modes once, the boundary PV always fused)
+  pl.inv = INV_PLAIN;
+  if (!c->no_fused_unpack) {
+    if (pl.rows == ROWS_DST64 && g.nl <= 4) pl.inv = INV_DST64_UNPACK;
+    if (pl.rows == ROWS_RFFT64 && g.nl <= 4 && c->whole && !slab) pl.inv = INV_RFFT64_UNPACK;
+    if (pl.rows == ROWS_FFT3 && g.cyc && !g.atm && g.nl == 3 && g.ldx % 2 == 0) pl.inv = INV_FFT3_UNPACK;
+  }
+  pl.constr = CONSTR_OWN;
+  if (!c->no_fused_constr) {
+    if (g.cyc) {
+      // inside qgcm_hip_steps part A of the constraint algebra rides in the Thomas launch and part B in the inverse
+      // launch: the extra wave of k_rfft64_unpack, every workgroup of k_rfft3_unpack, the extra workgroup of the generic
+      // rows (SOcn 5 km; it reads ksum and ybnd, not wrk) - the riding parts exist for nlo <= 4.  (The wave-per-row-pair
+      // kernels of k_rfft64.h have no such extra workgroup: they are fused with the unpack unless that is switched off,
+      // and then keep the stand-alone constraint launch.)
+      if (in_step && !slab && g.nl <= 4 && (pl.inv == INV_RFFT64_UNPACK || pl.rows != ROWS_RFFT64)) pl.constr = CONSTR_AB;
+    } else if (pl.inv == INV_DST64_UNPACK) {
+      // (y-slabs with the mixed layer on: xon(1) is only complete after the all-gather of stage 2 - no riding solve)
+      if (in_step && !(slab && c->oml.on)) pl.constr = CONSTR_INV_WAVE;
+    } else if (pl.rows != ROWS_DST64 && g.nl <= 3) {
+      pl.constr = CONSTR_BOX_WG; // 2 or 3 layers, see k_dst_box
+    }
+  }
+  // whole-domain inversions use k_rfft3_unpack only where its workgroups evaluate part B themselves
+  if (pl.inv == INV_FFT3_UNPACK && !slab && pl.constr != CONSTR_AB) pl.inv = INV_PLAIN;
+  pl.upd_dpi = pl.constr == CONSTR_INV_WAVE;
+  // write-through pair stores of the new qo (and 16-wide tiles) while the fields fit the Infinity Cache; plain stores and
+  // 32-wide tiles beyond (k_tend.h)
+  pl.wtq = (double)g.fstride * 8.0 * (7 * g.nl - 1) < 200.0e6 && !c->tend_wide;
+  // the fused kernels that can store the averaged time level: k_tend<.., AVG> with k_dst64_unpack<.., AVG> (write-through
+  // tiles only) or with k_rfft3_unpack<.., AVG>.  (While the po sum is on, the averaging step runs unfused: the sum must
+  // see this step's po before it is averaged.)
+  pl.avg_ok = in_step && !slab && !c->no_fused_avg && !c->poavg.on &&
+              ((pl.constr == CONSTR_INV_WAVE && pl.wtq) || pl.inv == INV_FFT3_UNPACK);
+  return pl;
 }
 
 static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = false, int part = TEND_ALL) {
@@ -1100,8 +1247,9 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   // write-through pair stores of the new qo and 16-wide tiles while the step's working set (~ 7 nl - 1 fields) stays in the
   // 256 MiB Infinity Cache (NAtl 5 km: 150 MB: -1 us per step; SOcn 5 km's 425 MB: +8 us); plain stores and 32-wide
   // tiles at the HBM-bound sizes (k_tend.h)
-  const bool wtq = tend_wtq(c);
-  if (c->avg_now && (part != TEND_ALL || (g.cyc ? g.nl != 3 : (!wtq || g.nl > 4)))) QG_FAIL("k_tend: the fused leapfrog averaging belongs to whole-domain steps of the fused inverse-row kernels");
+  const QgStepPlan pl = step_plan(c, true);
+  const bool wtq = pl.wtq;
+  if (c->avg_now && (part != TEND_ALL || !pl.avg_ok)) QG_FAIL("k_tend: the fused leapfrog averaging belongs to whole-domain steps of the fused inverse-row kernels");
   const TendTiling T = g.cyc ? (wtq ? tend_tiling<true, TEND_TX>(g) : tend_tiling<true, TEND_TX_WIDE>(g))
                              : (wtq ? tend_tiling<false, TEND_TX>(g) : tend_tiling<false, TEND_TX_WIDE>(g));
   if (part != TEND_ALL && T.gy < 3) QG_FAIL("k_tend: a slab of fewer than three tile rows cannot be split");
@@ -1137,46 +1285,37 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
       case 3: hipLaunchKernelGGL((k_tend<3, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F); break;
       default: hipLaunchKernelGGL((k_tend<4, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F); break;
     }
-  } else
-  switch (g.nl) {
-    case 2: QG_TEND(2); break;
-    case 3: QG_TEND(3); break;
-    case 4: QG_TEND(4); break;
-    case 5: QG_TEND(5); break;
-    case 6: QG_TEND(6); break;
-    case 7: QG_TEND(7); break;
-    case 8: QG_TEND(8); break;
-    default: QG_FAIL("k_tend: unsupported nlo");
+  } else {
+    QG_SWITCH_NL(g.nl, QG_TEND, "k_tend");
   }
 #undef QG_TEND
   HIPCHECK(hipGetLastError());
   return 0;
 }
 
-// box rows that run k_dst_box (not the wave-per-row-pair kernels of k_dst64.h)
-static bool dst_box_generic(const qgcm_hip_ctx *c) {
-  return !c->g.cyc && (c->force_generic_dst || !(c->fftN == 64 * 15 || c->fftN == 64 * 3));
+// what the row kernels read, the fused inverse kernels included (they never look at the Stockham factor list)
+static void fill_dst_params(const qgcm_hip_ctx *c, QgDstParams &D, double *wrk, int nlayers, int layer0) {
+  memset(&D, 0, sizeof(D));
+  D.g = c->g;
+  D.wrk = wrk;
+  D.twid = c->twid;
+  D.sintab = c->sintab;
+  D.rowsum = nullptr; // area / line integrals come from k_thomas (ksum and the k = 0 column)
+  D.N = c->fftN;
+  D.nfac = c->nfac;
+  for (int f = 0; f < c->nfac; ++f) D.fac[f] = c->fac[f];
+  D.nlayers = nlayers;
+  D.layer0 = layer0;
+  D.single = c->dst_single ? 1 : 0;
 }
-// ... whose inverse launch can carry the box constraint solve as an extra workgroup (2 or 3 layers, see k_dst_box)
-static bool dst_box_rides_constr(const qgcm_hip_ctx *c) { return dst_box_generic(c) && c->g.nl <= 3 && !c->no_fused_constr; }
 
 static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, int layer0 = 0, hipStream_t st = nullptr,
                       bool cyc_part_b = false, bool box_constr = false) {
   if (!st) st = c->stream;
   const QgGeom &g = c->g;
+  const QgStepPlan pl = step_plan(c);
   QgDstParams P;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.wrk = wrk;
-  P.twid = c->twid;
-  P.sintab = c->sintab;
-  P.rowsum = nullptr; // area / line integrals come from k_thomas (ksum and the k = 0 column)
-  P.N = c->fftN;
-  P.nfac = c->nfac;
-  for (int f = 0; f < c->nfac; ++f) P.fac[f] = c->fac[f];
-  P.nlayers = nlayers;
-  P.layer0 = layer0;
-  P.single = c->dst_single ? 1 : 0;
+  fill_dst_params(c, P, wrk, nlayers, layer0);
   const int nrows = g.jr1 - g.jr0 + 1;
   const int npairs = (nrows + 1) / 2;
   dim3 grid(npairs, nlayers);
@@ -1187,12 +1326,12 @@ static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, i
     grid.x += 1;
   }
   if (box_constr) { // generic box inverse rows: one extra workgroup runs the constraint solve (k_constr_box's body)
-    if (!inverse || g.cyc || !c->d_boxq || !dst_box_generic(c) || g.nl > 3) QG_FAIL("launch_dst: the box constraint solve rides in the generic inverse rows of a box ocean with homogeneous solutions");
+    if (!inverse || g.cyc || !c->d_boxq || pl.rows == ROWS_DST64 || g.nl > 3) QG_FAIL("launch_dst: the box constraint solve rides in the generic inverse rows of a box ocean with homogeneous solutions");
     P.boxq = c->d_boxq;
     grid.x += 1;
   }
   KTimer t(c, inverse ? KN_DSTI : KN_DSTF, st);
-  if (c->fft3 && !c->force_generic_dst) {
+  if (pl.rows == ROWS_FFT3) {
     // long rows: three in-place register-radix stages (k_fft3.h)
 #define QG_FFT3_LAUNCH(ID, R1, R2, R3)                                                                                     \
     if (c->fft3 == ID) {                                                                                                   \
@@ -1208,7 +1347,7 @@ static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, i
   }
   if (g.cyc) {
     // wave-per-row-pair fast path when nxto = 64*M (k_rfft64.h); the generic Stockham kernel otherwise
-    const int M64 = (!c->force_generic_dst && c->fftN % 64 == 0) ? c->fftN / 64 : 0;
+    const int M64 = pl.m64;
 #define QG_RF(MV)                                                                           \
   if (inverse) hipLaunchKernelGGL((k_rfft64<MV, true>), grid64, dim3(D64_NT), 0, st, P);    \
   else hipLaunchKernelGGL((k_rfft64<MV, false>), grid64, dim3(D64_NT), 0, st, P)
@@ -1222,31 +1361,14 @@ static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, i
     return 0;
   }
   // wave-per-row-pair fast path when nxto = 64*M with an in-register M-point DFT available
-  if (c->fftN == 64 * 15 && !c->force_generic_dst) {
+  if (pl.m64 == 15) {
     hipLaunchKernelGGL((k_dst64<15, false>), grid64, dim3(D64_NT), 0, st, P);
-  } else if (c->fftN == 64 * 3 && !c->force_generic_dst) {
+  } else if (pl.m64 == 3) {
     hipLaunchKernelGGL((k_dst64<3, false>), grid64, dim3(D64_NT), 0, st, P);
   } else if (c->fftN >= DST_BIG_N) hipLaunchKernelGGL((k_dst_box<false, DST_NT_BIG>), grid, dim3(DST_NT_BIG), c->dst_lds, st, P);
   else hipLaunchKernelGGL((k_dst_box<false>), grid, dim3(DST_NT), c->dst_lds, st, P);
   HIPCHECK(hipGetLastError());
   return 0;
-}
-
-static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, double *wrk, const QgThomasTab &tab, int nlayers, int layer0) {
-  const QgGeom &g = c->g;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.gath_stride = (long)slab_msg_len_oml(c);
-  P.slabDE = c->slabDE;
-  P.ksum = c->ksum;
-  P.wrk = wrk;
-  P.binf = tab.binf; P.ptab = tab.ptab; P.rcb = tab.rcb; P.poff = tab.poff;
-  P.nblk = (g.nk + TH_KW - 1) / TH_KW;
-  P.aoc = c->prm.aoc;
-  P.ftnorm = g.cyc ? 1.0 / g.nxt : 0.5 / g.nxt; // src/ocisubs.F:440, 547
-  P.nlayers = nlayers;
-  P.layer0 = layer0;
-  P.nranks = 1;
 }
 
 // phase 0: whole column; 1: the slab's zero-inflow solution + its summary (send); 2: after the exchange - the inflows
@@ -1310,16 +1432,9 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   switch (c->thR) {
     // (short columns too: 1024-thread workgroups of 16 wavenumbers measured slower everywhere - atmosphere 22.1 -> 21.3 us
     //  per step, 27.9 -> 26.3 on the two XCDs of a coupled run: profiles/r4_coupled_cu_masks.log)
-    case 1: QG_TH(1, 8); break;
-    case 2: QG_TH(2, 8); break;
-    case 4: QG_TH(4, 8); break;
-    case 8: QG_TH(8, 8); break;
-    case 10: QG_TH(10, 8); break;
-    case 12: QG_TH(12, 8); break;
-    case 16: QG_TH(16, 8); break;
-    case 20: QG_TH(20, 8); break;
-    case 24: QG_TH(24, 8); break;
-    case 32: QG_TH(32, 8); break;
+#define QG_TH_CASE(RV) case RV: QG_TH(RV, 8); break;
+    QG_TH_ROWS(QG_TH_CASE)
+#undef QG_TH_CASE
     default: QG_FAIL("k_thomas: too many rows for the single-segment kernel");
   }
 #undef QG_TH
@@ -1327,311 +1442,24 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   return 0;
 }
 
-static void fill_constr_params(qgcm_hip_ctx *c, QgConstrParams &P);
-
 static int launch_constr(qgcm_hip_ctx *c) {
   const QgGeom &g = c->g;
-  QgConstrParams P;
-  fill_constr_params(c, P);
   if (g.cyc) {
     QgCycConstrParams Q;
     fill_cyc_constr_params(c, Q);
     KTimer t(c, KN_CONSTR);
-    switch (g.nl) {
-      case 2: hipLaunchKernelGGL((k_constr_cyc<2>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      case 3: hipLaunchKernelGGL((k_constr_cyc<3>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      case 4: hipLaunchKernelGGL((k_constr_cyc<4>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      case 5: hipLaunchKernelGGL((k_constr_cyc<5>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      case 6: hipLaunchKernelGGL((k_constr_cyc<6>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      case 7: hipLaunchKernelGGL((k_constr_cyc<7>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      case 8: hipLaunchKernelGGL((k_constr_cyc<8>), dim3(1), dim3(64), 0, c->stream, Q); break;
-      default: QG_FAIL("k_constr_cyc: unsupported nlo");
-    }
+#define QG_CONSTR_CYC(NLV) hipLaunchKernelGGL((k_constr_cyc<NLV>), dim3(1), dim3(64), 0, c->stream, Q)
+    QG_SWITCH_NL(g.nl, QG_CONSTR_CYC, "k_constr_cyc");
+#undef QG_CONSTR_CYC
     HIPCHECK(hipGetLastError());
     return 0;
   }
-  KTimer t(c, KN_CONSTR);
-  switch (g.nl) {
-    case 2: hipLaunchKernelGGL((k_constr_box<2>), dim3(1), dim3(64), 0, c->stream, P); break;
-    case 3: hipLaunchKernelGGL((k_constr_box<3>), dim3(1), dim3(64), 0, c->stream, P); break;
-    case 4: hipLaunchKernelGGL((k_constr_box<4>), dim3(1), dim3(64), 0, c->stream, P); break;
-    case 5: hipLaunchKernelGGL((k_constr_box<5>), dim3(1), dim3(64), 0, c->stream, P); break;
-    case 6: hipLaunchKernelGGL((k_constr_box<6>), dim3(1), dim3(64), 0, c->stream, P); break;
-    case 7: hipLaunchKernelGGL((k_constr_box<7>), dim3(1), dim3(64), 0, c->stream, P); break;
-    case 8: hipLaunchKernelGGL((k_constr_box<8>), dim3(1), dim3(64), 0, c->stream, P); break;
-    default: QG_FAIL("k_constr: unsupported nlo");
-  }
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-static void fill_cyc_constr_params(qgcm_hip_ctx *c, QgCycConstrParams &Q) {
-  const QgGeom &g = c->g;
-  const qgcm_hip_params &pr2 = c->prm;
   QgConstrParams P;
   fill_constr_params(c, P);
-  memset(&Q, 0, sizeof(Q));
-  Q.g = g; Q.ksum = c->ksum; Q.wrk = c->wrk; Q.sc = c->sc; Q.cs = c->cs;
-  Q.bpart = Q.bpart_n = c->bpart;
-  Q.ybnd = c->ybnd; // k_thomas (PHASE 0 and PHASE 2 alike) leaves the zonal-mean rows next to the boundaries there
-  if (c->slab_gath) {
-    // y-slab stages: the boundary line sums travel at the end of the step messages (rank 0 owns the southern boundary,
-    // the last rank the northern one); the solution next to the boundaries comes from k_thomas PHASE 2
-    const size_t off = (size_t)TH_MSG * g.nl * g.ldw;
-    Q.bpart = c->slab_gath + off;
-    Q.bpart_n = c->slab_gath + (size_t)(c->slab_nranks - 1) * slab_msg_len_oml(c) + off;
-    Q.ybnd = c->ybnd;
-  }
-  Q.adfaco = 1.0 / (12.0 * pr2.dxo * pr2.dyo * pr2.fnot);
-  Q.delek_sgn = 0.5 * (pr2.fnot >= 0.0 ? 1.0 : -1.0) * pr2.delek;
-  for (int k = 0; k < g.nl; ++k) {
-    Q.ah2oc[k] = pr2.ah2oc[k];
-    Q.ah4oc[k] = pr2.ah4oc[k];
-  }
-  Q.dxo = P.dxo; Q.dyo = P.dyo; Q.tdto = P.tdto; Q.fnot = P.fnot;
-  for (int k = 0; k < QG_MAXL; ++k) { Q.gpoc[k] = P.gpoc[k]; Q.hoc[k] = P.hoc[k]; }
-  for (int i = 0; i < QG_MAXL * QG_MAXL; ++i) { Q.ctl2m[i] = P.ctl2m[i]; Q.ctm2l[i] = P.ctm2l[i]; }
-}
-
-static void fill_constr_params(qgcm_hip_ctx *c, QgConstrParams &P) {
-  const QgGeom &g = c->g;
-  const qgcm_hip_params &pr = c->prm;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.rowsum = c->rowsum;
-  P.ksum = c->ksum;
-  P.wcot = c->wcot;
-  P.wrk = c->wrk;
-  P.sc = c->sc;
-  P.cs = c->cs;
-  P.dxo = pr.dxo; P.dyo = pr.dyo; P.tdto = pr.tdto; P.fnot = pr.fnot;
-  for (int k = 0; k < g.nl; ++k) {
-    P.gpoc[k] = pr.gpoc[k];
-    P.hoc[k] = pr.hoc[k];
-  }
-  for (int i = 0; i < g.nl * g.nl; ++i) {
-    P.ctl2m[i] = pr.ctl2moc[i];
-    P.ctm2l[i] = pr.ctm2loc[i];
-  }
-}
-
-static void fill_bdy_params(qgcm_hip_ctx *c, QgBdyParams &P);
-
-static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr) {
-  const QgGeom &g = c->g;
-  QgUnpackParams P;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.wrk = c->wrk;
-  P.ochom = c->ochom;
-  P.pnew = c->p[c->ip ^ 1];
-  P.sc = c->sc;
-  P.pch1 = c->pch1; P.pch2 = c->pch2; P.pbh = c->pbh;
-  for (int i = 0; i < g.nl * g.nl; ++i) P.ctm2l[i] = c->prm.ctm2loc[i];
-  if ((msg_lo || msg_hi) && (!fuse_bdy || g.jhi - g.jlo + 1 < 3)) QG_FAIL("k_unpack: halo messages need the fused boundary PV and three owned rows");
-  P.msg_lo = msg_lo; // y-slab halo messages written by the same threads (slab stage 2)
-  P.msg_hi = msg_hi;
-  QgBdyParams B;
-  fill_bdy_params(c, B); // B.qo = current qo; B.po unused by the fused kernel
-  dim3 grid((g.nx + 255) / 256, g.jhi - g.jlo + 1);
-  KTimer t(c, KN_UNPACK);
-#define QG_UNPACK(NLV)                                                                                   \
-  if (g.cyc && fuse_bdy) hipLaunchKernelGGL((k_unpack_cyc<NLV, true>), grid, dim3(256), 0, c->stream, P, B);       \
-  else if (g.cyc) hipLaunchKernelGGL((k_unpack_cyc<NLV, false>), grid, dim3(256), 0, c->stream, P, B);             \
-  else if (fuse_bdy) hipLaunchKernelGGL((k_unpack_box<NLV, true>), grid, dim3(256), 0, c->stream, P, B); \
-  else hipLaunchKernelGGL((k_unpack_box<NLV, false>), grid, dim3(256), 0, c->stream, P, B)
-  switch (g.nl) {
-    case 2: QG_UNPACK(2); break;
-    case 3: QG_UNPACK(3); break;
-    case 4: QG_UNPACK(4); break;
-    case 5: QG_UNPACK(5); break;
-    case 6: QG_UNPACK(6); break;
-    case 7: QG_UNPACK(7); break;
-    case 8: QG_UNPACK(8); break;
-    default: QG_FAIL("k_unpack: unsupported nlo");
-  }
-#undef QG_UNPACK
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// cyclic / atmosphere fast path: inverse rows + homogeneous corrections + modes -> layers (+ zonal-boundary PV) in
-// one launch (k_rfft64_unpack), nxto = 64 * {3, 6, 15}
-static bool can_fuse_rfft_unpack(const qgcm_hip_ctx *c) {
-  return c->g.cyc && c->whole && !c->force_generic_dst && !c->no_fused_unpack &&
-         (c->fftN == 64 * 3 || c->fftN == 64 * 6 || c->fftN == 64 * 15) && c->g.nl >= 2 && c->g.nl <= 4;
-}
-
-static int launch_rfft_unpack(qgcm_hip_ctx *c, bool fuse_bdy, bool constr) {
-  const QgGeom &g = c->g;
-  QgDstParams D;
-  memset(&D, 0, sizeof(D));
-  D.g = g;
-  D.wrk = c->wrk;
-  D.twid = c->twid;
-  D.N = c->fftN;
-  D.nlayers = g.nl;
-  QgUnpackParams P;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.wrk = c->wrk;
-  P.pnew = c->p[c->ip ^ 1];
-  P.sc = c->sc;
-  P.pch1 = c->pch1; P.pch2 = c->pch2; P.pbh = c->pbh;
-  for (int i = 0; i < g.nl * g.nl; ++i) P.ctm2l[i] = c->prm.ctm2loc[i];
-  QgBdyParams B;
-  fill_bdy_params(c, B);
-  if (constr && !c->d_cycq) QG_FAIL("k_rfft64_unpack: homogeneous solutions not set");
-  QgCycConstrParams Qv; // by value: kernel arguments (k_rfft64.h)
-  fill_cyc_constr_params(c, Qv);
-  const int nrows = g.jr1 - g.jr0 + 1;
-  dim3 grid((nrows + 1) / 2);
-  KTimer t(c, KN_DSTI);
-#define QG_RU(MV, NLV)                                                                                                        \
-  if (fuse_bdy && constr) hipLaunchKernelGGL((k_rfft64_unpack<MV, NLV, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, Qv); \
-  else if (fuse_bdy) hipLaunchKernelGGL((k_rfft64_unpack<MV, NLV, true, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, Qv); \
-  else hipLaunchKernelGGL((k_rfft64_unpack<MV, NLV, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, Qv)
-#define QG_RU_NL(MV)                 \
-  switch (g.nl) {                    \
-    case 2: QG_RU(MV, 2); break;     \
-    case 3: QG_RU(MV, 3); break;     \
-    default: QG_RU(MV, 4); break;    \
-  }
-  if (c->fftN == 64 * 15) {
-    QG_RU_NL(15)
-  } else if (c->fftN == 64 * 6) {
-    QG_RU_NL(6)
-  } else {
-    QG_RU_NL(3)
-  }
-#undef QG_RU_NL
-#undef QG_RU
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// long rows (three-stage plans): inverse rows + homogeneous corrections + modes -> layers + boundary PV in one launch
-// that reads the solved modes once (k_fft3_unpack.h); nlo = 3, the boundary PV always fused
-static bool can_fuse_fft3_unpack(const qgcm_hip_ctx *c) {
-  return c->fft3 && !c->force_generic_dst && !c->no_fused_unpack && c->g.nl == 3 && c->g.ldx % 2 == 0 && c->g.cyc && !c->g.atm;
-}
-
-static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo = nullptr, double *msg_hi = nullptr) {
-  const QgGeom &g = c->g;
-  if (!can_fuse_fft3_unpack(c)) QG_FAIL("k_fft3_unpack: not a long-row configuration of three layers");
-  if ((msg_lo || msg_hi) && g.jhi - g.jlo + 1 < 3) QG_FAIL("k_fft3_unpack: halo messages need three owned rows");
-  QgDstParams D;
-  memset(&D, 0, sizeof(D));
-  D.g = g;
-  D.wrk = c->wrk;
-  D.twid = c->twid;
-  D.sintab = c->sintab;
-  D.N = c->fftN;
-  D.nlayers = g.nl;
-  QgUnpackParams P;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.wrk = c->wrk;
-  P.ochom = c->ochom;
-  P.pnew = c->p[c->ip ^ 1];
-  P.sc = c->sc;
-  P.pch1 = c->pch1; P.pch2 = c->pch2; P.pbh = c->pbh;
-  P.msg_lo = msg_lo;
-  P.msg_hi = msg_hi;
-  for (int i = 0; i < g.nl * g.nl; ++i) P.ctm2l[i] = c->prm.ctm2loc[i];
-  if (c->avg_now) {
-    if (msg_lo || msg_hi || !own_constr) QG_FAIL("k_rfft3_unpack: the fused leapfrog averaging belongs to whole-domain steps");
-    P.pavg = c->p[c->ip];     // this step's po (the launch writes the old pom buffer)
-    P.qavg = c->q[c->iq ^ 1]; // this step's qo (iq already points at the new qo)
-  }
-  QgBdyParams B;
-  fill_bdy_params(c, B);
-  const int npairs = (g.jr1 - g.jr0 + 2) / 2;
-  dim3 grid(8 * ((npairs + 7) / 8) * g.nl);
-  KTimer t(c, KN_DSTI);
-  if (g.cyc) {
-    QgCycConstrParams Q;
-    fill_cyc_constr_params(c, Q);
-#define QG_FFT3U_LAUNCH(ID, R1, R2, R3)                                                                                   \
-    if (c->fft3 == ID) {                                                                                                  \
-      typedef Fft3Plan<R1, R2, R3> PL;                                                                                    \
-      if (c->avg_now) hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT, true>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, 1); \
-      else hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, own_constr ? 1 : 0); \
-    }
-    QG_FFT3_PLANS(QG_FFT3U_LAUNCH)
-#undef QG_FFT3U_LAUNCH
-  }
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// box fast path: inverse row transform + modes -> layers (+ boundary PV) in one launch (k_dst64_unpack)
-static bool can_fuse_dst_unpack(const qgcm_hip_ctx *c) {
-  return !c->g.cyc && !c->force_generic_dst && !c->no_fused_unpack && (c->fftN == 64 * 15 || c->fftN == 64 * 3) &&
-         c->g.nl >= 2 && c->g.nl <= 4;
-}
-
-static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr,
-                             bool constr = false) {
-  const QgGeom &g = c->g;
-  QgDstParams D;
-  memset(&D, 0, sizeof(D));
-  D.g = g;
-  D.wrk = c->wrk;
-  D.twid = c->twid;
-  D.sintab = c->sintab;
-  D.N = c->fftN;
-  D.nlayers = g.nl;
-  QgUnpackParams P;
-  memset(&P, 0, sizeof(P));
-  P.g = g;
-  P.wrk = c->wrk;
-  P.ochom = c->ochom;
-  P.pnew = c->p[c->ip ^ 1];
-  P.sc = c->sc;
-  P.msg_lo = msg_lo;
-  P.msg_hi = msg_hi;
-  if (c->avg_now) {
-    if (msg_lo || msg_hi || !fuse_bdy || !constr) QG_FAIL("k_dst64_unpack: the fused leapfrog averaging belongs to whole-domain steps");
-    P.pavg = c->p[c->ip];     // this step's po (the launch writes the old pom buffer)
-    P.qavg = c->q[c->iq ^ 1]; // this step's qo (iq already points at the new qo)
-  }
-  for (int i = 0; i < g.nl * g.nl; ++i) P.ctm2l[i] = c->prm.ctm2loc[i];
-  QgBdyParams B;
-  fill_bdy_params(c, B);
-  QgConstrLite C;
-  {
-    QgConstrParams F;
-    fill_constr_params(c, F);
-    memset(&C, 0, sizeof(C));
-    C.g = F.g; C.ksum = F.ksum; C.wcot = F.wcot; C.sc = F.sc;
-    C.dxo = F.dxo; C.dyo = F.dyo;
-    for (int i = 0; i < 16; ++i) { C.cs.cdiffo[i] = F.cs.cdiffo[i]; C.cs.cdhoc[i] = F.cs.cdhoc[i]; C.cs.cdhlu[i] = F.cs.cdhlu[i]; }
-    for (int i = 0; i < 4; ++i) C.cs.ipiv[i] = F.cs.ipiv[i];
-  }
-  const int nrows = g.jr1 - g.jr0 + 1;
-  dim3 grid((nrows + 1) / 2);
-  KTimer t(c, KN_DSTI);
-#define QG_DU(MV, NLV)                                                                                                  \
-  if (c->avg_now) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
-  else if ((msg_lo || msg_hi) && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
-  else if (msg_lo || msg_hi) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C); \
-  else if (fuse_bdy && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
-  else if (fuse_bdy) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C);  \
-  else hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, false, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C)
-#define QG_DU_NL(MV)                 \
-  switch (g.nl) {                    \
-    case 2: QG_DU(MV, 2); break;     \
-    case 3: QG_DU(MV, 3); break;     \
-    default: QG_DU(MV, 4); break;    \
-  }
-  if (c->fftN == 64 * 15) {
-    QG_DU_NL(15)
-  } else {
-    QG_DU_NL(3)
-  }
-#undef QG_DU_NL
-#undef QG_DU
+  KTimer t(c, KN_CONSTR);
+#define QG_CONSTR_BOX(NLV) hipLaunchKernelGGL((k_constr_box<NLV>), dim3(1), dim3(64), 0, c->stream, P)
+  QG_SWITCH_NL(g.nl, QG_CONSTR_BOX, "k_constr");
+#undef QG_CONSTR_BOX
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1650,6 +1478,158 @@ static void fill_bdy_params(qgcm_hip_ctx *c, QgBdyParams &P) {
   P.beta = pr.beta;
   for (int k = 0; k < g.nl; ++k)
     for (int l = 0; l < g.nl; ++l) P.f0A[k + g.nl * l] = pr.fnot * pr.amatoc[k + g.nl * l];
+}
+
+// what the unpack kernels read, stand-alone or fused with the inverse rows.  msg_lo / msg_hi: the y-slab halo messages
+// written by the same threads (slab stage 2).  In an averaging step of one_step (avg_now) the launch stores the
+// averaged level; avg_ok: this launch is the fused whole-domain kernel that can (`who` names it otherwise)
+static int fill_unpack_params(qgcm_hip_ctx *c, QgUnpackParams &P, double *msg_lo, double *msg_hi, const char *who, bool avg_ok) {
+  const QgGeom &g = c->g;
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.wrk = c->wrk;
+  P.ochom = c->ochom;
+  P.pnew = c->p[c->ip ^ 1];
+  P.sc = c->sc;
+  P.pch1 = c->pch1; P.pch2 = c->pch2; P.pbh = c->pbh;
+  P.msg_lo = msg_lo;
+  P.msg_hi = msg_hi;
+  for (int i = 0; i < g.nl * g.nl; ++i) P.ctm2l[i] = c->prm.ctm2loc[i];
+  if (c->avg_now) {
+    if (msg_lo || msg_hi || !avg_ok) QG_FAIL("%s: the fused leapfrog averaging belongs to whole-domain steps", who);
+    P.pavg = c->p[c->ip];     // this step's po (the launch writes the old pom buffer)
+    P.qavg = c->q[c->iq ^ 1]; // this step's qo (iq already points at the new qo)
+  }
+  return 0;
+}
+
+static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr) {
+  const QgGeom &g = c->g;
+  if ((msg_lo || msg_hi) && (!fuse_bdy || g.jhi - g.jlo + 1 < 3)) QG_FAIL("k_unpack: halo messages need the fused boundary PV and three owned rows");
+  QgUnpackParams P;
+  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_unpack", false)) return 1;
+  QgBdyParams B;
+  fill_bdy_params(c, B); // B.qo = current qo; B.po unused by the fused kernel
+  dim3 grid((g.nx + 255) / 256, g.jhi - g.jlo + 1);
+  KTimer t(c, KN_UNPACK);
+#define QG_UNPACK(NLV)                                                                                   \
+  if (g.cyc && fuse_bdy) hipLaunchKernelGGL((k_unpack_cyc<NLV, true>), grid, dim3(256), 0, c->stream, P, B);       \
+  else if (g.cyc) hipLaunchKernelGGL((k_unpack_cyc<NLV, false>), grid, dim3(256), 0, c->stream, P, B);             \
+  else if (fuse_bdy) hipLaunchKernelGGL((k_unpack_box<NLV, true>), grid, dim3(256), 0, c->stream, P, B); \
+  else hipLaunchKernelGGL((k_unpack_box<NLV, false>), grid, dim3(256), 0, c->stream, P, B)
+  QG_SWITCH_NL(g.nl, QG_UNPACK, "k_unpack");
+#undef QG_UNPACK
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// cyclic / atmosphere fast path: inverse rows + homogeneous corrections + modes -> layers (+ zonal-boundary PV) in
+// one launch (k_rfft64_unpack), nxto = 64 * {3, 6, 15}: step_plan's INV_RFFT64_UNPACK
+static int launch_rfft_unpack(qgcm_hip_ctx *c, bool fuse_bdy, bool constr) {
+  const QgGeom &g = c->g;
+  QgDstParams D;
+  fill_dst_params(c, D, c->wrk, g.nl, 0);
+  QgUnpackParams P;
+  if (fill_unpack_params(c, P, nullptr, nullptr, "k_rfft64_unpack", false)) return 1;
+  QgBdyParams B;
+  fill_bdy_params(c, B);
+  if (constr && !c->d_cycq) QG_FAIL("k_rfft64_unpack: homogeneous solutions not set");
+  QgCycConstrParams Qv; // by value: kernel arguments (k_rfft64.h)
+  fill_cyc_constr_params(c, Qv);
+  const int nrows = g.jr1 - g.jr0 + 1;
+  dim3 grid((nrows + 1) / 2);
+  KTimer t(c, KN_DSTI);
+#define QG_RU(MV, NLV)                                                                                                        \
+  if (fuse_bdy && constr) hipLaunchKernelGGL((k_rfft64_unpack<MV, NLV, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, Qv); \
+  else if (fuse_bdy) hipLaunchKernelGGL((k_rfft64_unpack<MV, NLV, true, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, Qv); \
+  else hipLaunchKernelGGL((k_rfft64_unpack<MV, NLV, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, Qv)
+#define QG_RU_NL(MV)                 \
+  switch (g.nl) {                    \
+    case 2: QG_RU(MV, 2); break;     \
+    case 3: QG_RU(MV, 3); break;     \
+    default: QG_RU(MV, 4); break;    \
+  }
+  switch (step_plan(c).m64) {
+    case 15: QG_RU_NL(15) break;
+    case 6: QG_RU_NL(6) break;
+    default: QG_RU_NL(3) break;
+  }
+#undef QG_RU_NL
+#undef QG_RU
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// long rows (three-stage plans): inverse rows + homogeneous corrections + modes -> layers + boundary PV in one launch
+// that reads the solved modes once (k_fft3_unpack.h); nlo = 3, the boundary PV always fused: step_plan's INV_FFT3_UNPACK
+// (own_constr: every workgroup evaluates part B of the constraint algebra for itself)
+static bool can_fuse_fft3_unpack(const qgcm_hip_ctx *c) { return step_plan(c, true, true).inv == INV_FFT3_UNPACK; } // (the slab stages' plan: wherever the kernel exists)
+
+static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo = nullptr, double *msg_hi = nullptr) {
+  const QgGeom &g = c->g;
+  if (!can_fuse_fft3_unpack(c)) QG_FAIL("k_fft3_unpack: not a long-row configuration of three layers");
+  if ((msg_lo || msg_hi) && g.jhi - g.jlo + 1 < 3) QG_FAIL("k_fft3_unpack: halo messages need three owned rows");
+  QgDstParams D;
+  fill_dst_params(c, D, c->wrk, g.nl, 0);
+  QgUnpackParams P;
+  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_rfft3_unpack", own_constr)) return 1;
+  QgBdyParams B;
+  fill_bdy_params(c, B);
+  const int npairs = (g.jr1 - g.jr0 + 2) / 2;
+  dim3 grid(8 * ((npairs + 7) / 8) * g.nl);
+  KTimer t(c, KN_DSTI);
+  QgCycConstrParams Q;
+  fill_cyc_constr_params(c, Q);
+#define QG_FFT3U_LAUNCH(ID, R1, R2, R3)                                                                                   \
+  if (c->fft3 == ID) {                                                                                                    \
+    typedef Fft3Plan<R1, R2, R3> PL;                                                                                      \
+    if (c->avg_now) hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT, true>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, 1); \
+    else hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, own_constr ? 1 : 0); \
+  }
+  QG_FFT3_PLANS(QG_FFT3U_LAUNCH)
+#undef QG_FFT3U_LAUNCH
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// box fast path: inverse row transform + modes -> layers (+ boundary PV) in one launch (k_dst64_unpack): step_plan's
+// INV_DST64_UNPACK
+static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr,
+                             bool constr = false) {
+  const QgGeom &g = c->g;
+  QgDstParams D;
+  fill_dst_params(c, D, c->wrk, g.nl, 0);
+  QgUnpackParams P;
+  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_dst64_unpack", fuse_bdy && constr)) return 1;
+  QgBdyParams B;
+  fill_bdy_params(c, B);
+  QgConstrLite C;
+  fill_constr_lite(c, C);
+  const int nrows = g.jr1 - g.jr0 + 1;
+  dim3 grid((nrows + 1) / 2);
+  KTimer t(c, KN_DSTI);
+#define QG_DU(MV, NLV)                                                                                                  \
+  if (c->avg_now) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
+  else if ((msg_lo || msg_hi) && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
+  else if (msg_lo || msg_hi) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C); \
+  else if (fuse_bdy && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
+  else if (fuse_bdy) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C);  \
+  else hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, false, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C)
+#define QG_DU_NL(MV)                 \
+  switch (g.nl) {                    \
+    case 2: QG_DU(MV, 2); break;     \
+    case 3: QG_DU(MV, 3); break;     \
+    default: QG_DU(MV, 4); break;    \
+  }
+  if (step_plan(c).m64 == 15) {
+    QG_DU_NL(15)
+  } else {
+    QG_DU_NL(3)
+  }
+#undef QG_DU_NL
+#undef QG_DU
+  HIPCHECK(hipGetLastError());
+  return 0;
 }
 
 static int launch_ocqbdy(qgcm_hip_ctx *c) {
@@ -1687,59 +1667,38 @@ extern "C" int qgcm_hip_qgostep(qgcm_hip_handle c) {
   return 0;
 }
 
-// in_step: called from qgcm_hip_steps, where k_tend has already stepped dpioc / dpiocp (launch_tend(c, true)) and
-// the box constraint solve can ride in the fused inverse-transform kernel
-static int ocinvq_impl(qgcm_hip_ctx *c, bool fuse_bdy, bool in_step = false) {
+// in_step: called from qgcm_hip_steps, where k_tend has already stepped dpioc / dpiocp where the plan says so
+// (launch_tend(c, pl.upd_dpi)) and ocqbdy is fused into the unpack; the launches are step_plan's
+static int ocinvq_impl(qgcm_hip_ctx *c, bool in_step = false) {
   if (check_ready(c, "qgcm_hip_ocinvq")) return 1;
   if (!c->whole) QG_FAIL("qgcm_hip_ocinvq: this handle is a y-slab; drive it with the slab building blocks");
   if (!c->homog_set) QG_FAIL("qgcm_hip_ocinvq: homogeneous solutions not set");
+  const QgStepPlan pl = step_plan(c, in_step);
+  const bool fuse_bdy = in_step;
   // (A per-mode side-stream variant of this chain was measured slower - 140 vs 116 us/step at 5 km - and removed.)
   if (launch_dst(c, c->wrk, c->g.nl, false)) return 1;
-  if (c->g.cyc && can_fuse_rfft_unpack(c)) {
-    // cyclic / atmosphere, nxto = 64*M: inside qgcm_hip_steps part A of the constraint algebra rides in the Thomas
-    // launch and part B in the fused inverse-transform kernel (3 launches after k_tend instead of 5)
-    const bool fc = in_step && fuse_bdy && !c->no_fused_constr;
-    if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr, fc)) return 1;
-    if (!fc && launch_constr(c)) return 1;
-    if (launch_rfft_unpack(c, fuse_bdy, fc)) return 1;
-    c->ip ^= 1;
-    return 0;
-  }
-  // (the wave-per-row-pair kernels of k_rfft64.h have no such extra workgroup: they are fused with the unpack step
-  //  above unless that is switched off, and then keep the stand-alone constraint launch)
-  const bool generic_rows = c->force_generic_dst || !(c->fftN == 64 * 3 || c->fftN == 64 * 6 || c->fftN == 64 * 15);
-  if (c->g.cyc && in_step && !c->no_fused_constr && generic_rows && c->g.nl <= 4) { // (the riding parts A / B: nlo <= 4)
-    // cyclic ocean with generic row sizes (SOcn 5 km), inside qgcm_hip_steps: part A of the constraint algebra rides in
-    // the Thomas launch, part B in the inverse-row launch (it reads ksum and ybnd, not wrk): no launch of its own
-    if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr, true)) return 1;
-    if (fuse_bdy && can_fuse_fft3_unpack(c)) { // long rows: one launch, every workgroup evaluates part B for itself
-      if (launch_fft3_unpack(c, true)) return 1;
-      c->ip ^= 1;
-      return 0;
-    }
-    if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, true)) return 1;
-    if (launch_unpack(c, fuse_bdy)) return 1;
-    c->ip ^= 1;
-    return 0;
-  }
-  if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr)) return 1;
-  const bool fused_constr = in_step && fuse_bdy && can_fuse_dst_unpack(c) && !c->no_fused_constr;
-  // generic box rows: the constraint solve rides as an extra workgroup of the inverse-row launch
-  const bool ride_constr = !fused_constr && dst_box_rides_constr(c);
+  if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr, pl.constr == CONSTR_AB)) return 1;
   // area (and, cyclic, line) integrals are a by-product of the y sweeps: the constraints precede the inverse transform
-  if (!fused_constr && !ride_constr && launch_constr(c)) return 1;
-  if (can_fuse_dst_unpack(c)) {
-    if (launch_dst_unpack(c, fuse_bdy, nullptr, nullptr, fused_constr)) return 1;
-    c->ip ^= 1; // new po sits in the old pom buffer; the old po is pom
-    return 0;
+  if (pl.constr == CONSTR_OWN && launch_constr(c)) return 1;
+  switch (pl.inv) {
+    case INV_DST64_UNPACK:
+      if (launch_dst_unpack(c, fuse_bdy, nullptr, nullptr, pl.constr == CONSTR_INV_WAVE)) return 1;
+      break;
+    case INV_RFFT64_UNPACK: // (3 launches after k_tend instead of 5)
+      if (launch_rfft_unpack(c, fuse_bdy, pl.constr == CONSTR_AB)) return 1;
+      break;
+    case INV_FFT3_UNPACK:
+      if (launch_fft3_unpack(c, true)) return 1;
+      break;
+    default:
+      if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, pl.constr == CONSTR_AB, pl.constr == CONSTR_BOX_WG)) return 1;
+      if (launch_unpack(c, fuse_bdy)) return 1;
   }
-  if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, false, ride_constr)) return 1;
-  if (launch_unpack(c, fuse_bdy)) return 1;
   c->ip ^= 1; // new po sits in the old pom buffer; the old po is pom
   return 0;
 }
 
-extern "C" int qgcm_hip_ocinvq(qgcm_hip_handle c) { return ocinvq_impl(c, false); }
+extern "C" int qgcm_hip_ocinvq(qgcm_hip_handle c) { return ocinvq_impl(c); }
 
 extern "C" int qgcm_hip_ocqbdy(qgcm_hip_handle c) {
   if (check_ready(c, "qgcm_hip_ocqbdy")) return 1;
@@ -1774,20 +1733,8 @@ extern "C" int qgcm_hip_ocqbdy_host(qgcm_hip_handle c, double *q, const double *
   return rc;
 }
 
-static int launch_oml_average(qgcm_hip_ctx *c);
 static int launch_aml(qgcm_hip_ctx *c, bool with_final);
 static int launch_aml_average(qgcm_hip_ctx *c);
-static void aml_set_idx(qgcm_hip_ctx *c, int ia, int iam);
-
-// the whole ocean part of the averaging block src/q-gcm.F:1328-1366: po, qo, constraint scalars and - when the
-// mixed layer lives on the device - sst
-extern "C" int qgcm_hip_lf_average(qgcm_hip_handle c) {
-  if (check_ready(c, "qgcm_hip_lf_average")) return 1;
-  if (launch_lfavg(c)) return 1;
-  if (c->oml.on && launch_oml_average(c)) return 1;
-  if (c->aml.on && launch_aml_average(c)) return 1; // ast, hmixa: src/q-gcm.F:1388-1394
-  return 0;
-}
 
 // ---------------------------------------------------------------------------
 // ocean mixed layer
@@ -1855,21 +1802,6 @@ extern "C" int qgcm_hip_oml_set_forcing(qgcm_hip_handle c, const double *fnetoc,
   if (tauxo && upload2d(c, c->oml.taux, g.ldx, tauxo, g.nx, g.ny)) return 1;
   if (tauyo && upload2d(c, c->oml.tauy, g.ldx, tauyo, g.nx, g.ny)) return 1;
   return 0;
-}
-
-static void fill_oml_final(qgcm_hip_ctx *c, QgOmlFinal &F, bool on) {
-  memset(&F, 0, sizeof(F));
-  if (c->aml.on) { // the atmosphere's mixed layer: the same sums under other names (xan, enisat / eninat, cfraat, centat)
-    const auto &a = c->aml;
-    F.partA = a.partA; F.partB = a.partB; F.nblkA = a.nblkA; F.nblkB = a.nblkB; F.diag = a.diag;
-  } else {
-    const auto &o = c->oml;
-    F.partA = o.partA; F.partB = o.partB; F.nblkA = o.nblkA; F.nblkB = o.nblkB; F.diag = o.diag;
-  }
-  F.cyc = c->g.cyc; F.on = on ? 1 : 0;
-  F.sc = c->sc;
-  F.ocnorm = 1.0 / ((double)c->g.nxt * (double)(c->g.nyg - 1)); // src/parameters_data.F:88
-  F.dxo = c->prm.dxo; F.dyo = c->prm.dyo;
 }
 
 static void fill_oml_params(qgcm_hip_ctx *c, QgOmlParams &P) {
@@ -1970,6 +1902,16 @@ static int launch_oml_average(qgcm_hip_ctx *c) {
   return 0;
 }
 
+// the whole ocean part of the averaging block src/q-gcm.F:1328-1366: po, qo, constraint scalars and - when the
+// mixed layer lives on the device - sst
+extern "C" int qgcm_hip_lf_average(qgcm_hip_handle c) {
+  if (check_ready(c, "qgcm_hip_lf_average")) return 1;
+  if (launch_lfavg(c)) return 1;
+  if (c->oml.on && launch_oml_average(c)) return 1;
+  if (c->aml.on && launch_aml_average(c)) return 1; // ast, hmixa: src/q-gcm.F:1388-1394
+  return 0;
+}
+
 extern "C" int qgcm_hip_oml_get_diag(qgcm_hip_handle c, double *entoc, double *diag) {
   if (oml_ready(c, "qgcm_hip_oml_get_diag")) return 1;
   const QgGeom &g = c->g;
@@ -2019,22 +1961,19 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   if (c->oml.on && launch_oml(c, false)) return 1; // src/q-gcm.F:1232; its final reduction rides in launch_tend
   if (c->aml.on && launch_aml(c, false)) return 1; // src/q-gcm.F:1260, immediately before qgastep; likewise
   if (sched_due(c->sched[SCH_DUMP], s) && qd_record(c, s)) return 1; // qocdiag_out after oml, before qgostep (src/q-gcm.F:1234-1239)
-  const bool fused_constr = !c->g.cyc && can_fuse_dst_unpack(c) && !c->no_fused_constr; // see ocinvq_impl
   if (check_ready(c, "qgcm_hip_steps")) return 1;
+  const QgStepPlan pl = step_plan(c, true);
   // Leapfrog averaging (src/q-gcm.F:1345-1351) after this step: where the box ocean's fused kernels run, they store the
   // averaged level themselves - k_tend the interior qo (both levels are in its registers), k_dst64_unpack the new po and
   // the boundary qo (one extra read of this step's po) - instead of a pass of its own over six fields (133 MB at 5 km,
   // 21 us every 25 steps); the integrals dpioc follow in a one-thread launch.  Same expressions: bitwise the same fields.
   const bool avg = (s - 1) % c->avg_period == 0;
-  const bool avg_box = fused_constr && c->g.nl <= 4 && tend_wtq(c);
-  const bool avg_cyc = c->g.cyc && can_fuse_fft3_unpack(c) && !c->no_fused_constr; // (ocinvq_impl: launch_fft3_unpack(c, true))
-  // (while the po sum is on, the averaging step runs unfused: the sum must see this step's po before it is averaged)
-  c->avg_now = avg && (avg_box || avg_cyc) && !c->no_fused_avg && !c->poavg.on;
+  c->avg_now = avg && pl.avg_ok; // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does what k_dst64_unpack does for the box)
   const bool avg_fused = c->avg_now;
-  int rc = launch_tend(c, fused_constr, c->oml.on || c->aml.on);
+  int rc = launch_tend(c, pl.upd_dpi, c->oml.on || c->aml.on);
   if (!rc) {
     c->iq ^= 1; // as qgcm_hip_qgostep
-    rc = ocinvq_impl(c, true, true); // ocqbdy fused into the unpack kernel
+    rc = ocinvq_impl(c, true); // ocqbdy fused into the unpack kernel
   }
   c->avg_now = false;
   if (rc) return 1;
@@ -2057,17 +1996,63 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   return 0;
 }
 
-// the sst buffers rotate with period 3 (sst -> sstm -> spare -> sst), one position per step
-static void oml_rotate(qgcm_hip_ctx *c, int nsteps) {
+// the buffer rotation; atmon.ast / atmon.hmixa follow the current level
+static void aml_set_idx(qgcm_hip_ctx *c, int ia, int iam) {
+  c->aml.ia = ia;
+  c->aml.iam = iam;
+  c->atmon.ast = c->aml.ast[ia];
+  c->atmon.hmixa = c->aml.hm[ia];
+}
+
+// three buffers rotate with period 3 (current -> lagged -> spare -> current), one position per step
+static void rotate3(int &cur, int &lag, int nsteps) {
   for (int r = 0; r < nsteps % 3; ++r) {
-    const int spare = 3 - c->oml.is - c->oml.ism;
-    c->oml.ism = c->oml.is;
-    c->oml.is = spare;
+    const int spare = 3 - cur - lag;
+    lag = cur;
+    cur = spare;
   }
 }
-// ... and so do the atmosphere's ast / hmixa buffers
-static void aml_rotate(qgcm_hip_ctx *c, int nsteps) {
-  for (int r = 0; r < nsteps % 3; ++r) aml_set_idx(c, 3 - c->aml.ia - c->aml.iam, c->aml.ia);
+// where the mixed layer's buffers (the ocean's sst; the atmosphere's ast / hmixa) stand nsteps later
+static void ml_rotate(qgcm_hip_ctx *c, int nsteps) {
+  if (c->oml.on) rotate3(c->oml.is, c->oml.ism, nsteps);
+  if (c->aml.on) {
+    int ia = c->aml.ia, iam = c->aml.iam;
+    rotate3(ia, iam, nsteps);
+    aml_set_idx(c, ia, iam);
+  }
+}
+
+// The rotation state a block of steps moves.  Capturing a block and the dry pass of steps_impl execute nothing: they
+// put it back to that of the block's first step.
+struct QgRotState {
+  int ip, iq, is, ism, ia, iam;
+  long pn;
+  void save(const qgcm_hip_ctx *c) {
+    ip = c->ip; iq = c->iq; is = c->oml.is; ism = c->oml.ism; ia = c->aml.ia; iam = c->aml.iam; pn = c->poavg.n;
+  }
+  void restore(qgcm_hip_ctx *c) const {
+    c->ip = ip; c->iq = iq; c->oml.is = is; c->oml.ism = ism; c->poavg.n = pn;
+    if (c->aml.on) aml_set_idx(c, ia, iam);
+  }
+};
+
+// What `body` launches on the handle's stream, captured and instantiated as an executable graph
+template <class Body>
+static int capture_block(qgcm_hip_ctx *c, bool upload, hipGraphExec_t *exec, Body body) {
+  QgRotState st;
+  st.save(c);
+  hipGraph_t graph;
+  HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  const int rc = body();
+  hipError_t e = hipStreamEndCapture(c->stream, &graph);
+  st.restore(c); // capture does not execute
+  if (rc) return 1;
+  HIPCHECK(e);
+  HIPCHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+  HIPCHECK(hipGraphDestroy(graph));
+  // (the first replay of a fresh executable graph otherwise pays for its upload inside the caller's window)
+  if (upload && hipGraphUpload(*exec, c->stream) != hipSuccess) (void)hipGetLastError();
+  return 0;
 }
 
 // One captured block of B consecutive steps. B is even, so both buffer rotations are back where they started
@@ -2077,7 +2062,6 @@ static void aml_rotate(qgcm_hip_ctx *c, int nsteps) {
 // launches and at most one eager step (round 2 cut the tail into 10-step blocks: two replays for the driver's
 // 20-step window, each paying the ~10-16 us host-side floor of a replay).  The cache is bounded: a caller
 // that asks for ever new block lengths / phases evicts everything once kMaxGraphs is reached.
-static const int kGraphBlock50 = 50;
 static const size_t kMaxGraphs = 96;
 
 static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
@@ -2104,28 +2088,15 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
       c->graphs.erase(old[i].second);
     }
   }
-  hipGraph_t graph;
-  const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism, ia0 = c->aml.ia, iam0 = c->aml.iam;
-  const long pn0 = c->poavg.n;
   if (sched_block(c, s0, B) < B) // (steps_impl cuts)
     QG_FAIL("qgcm_hip_steps: internal: a graph block would hold a dump step or an accumulation step");
-  HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int s = s0; s < s0 + B && !rc; ++s) rc = one_step(c, s);
-  hipError_t e = hipStreamEndCapture(c->stream, &graph);
-  c->poavg.n = pn0;
-  c->ip = ip0; // capture does not execute: restore the rotation state
-  c->iq = iq0;
-  c->oml.is = is0;
-  c->oml.ism = ism0;
-  if (c->aml.on) aml_set_idx(c, ia0, iam0);
-  if (rc) return 1;
-  HIPCHECK(e);
   hipGraphExec_t exec;
-  HIPCHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-  HIPCHECK(hipGraphDestroy(graph));
-  // (the first replay of a fresh executable graph otherwise pays for its upload inside the caller's window)
-  if (hipGraphUpload(exec, c->stream) != hipSuccess) (void)hipGetLastError();
+  if (capture_block(c, true, &exec, [&]() {
+        int rc = 0;
+        for (int s = s0; s < s0 + B && !rc; ++s) rc = one_step(c, s);
+        return rc;
+      }))
+    return 1;
   c->graphs[key] = {exec, c->graph_call};
   *out = exec;
   return 0;
@@ -2149,19 +2120,19 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
       if (sched_count(c->sched[a.sched], s0, n) > 0 && a.inputs(c, a.who)) return 1;
     c->graph_call++; // (a dry pass belongs to the call that follows it: qgcm_hip_time_steps, prepare + steps)
   }
-  const int is0 = c->oml.is, ism0 = c->oml.ism, ip0 = c->ip, iq0 = c->iq, ia0 = c->aml.ia, iam0 = c->aml.iam;
+  QgRotState st0;
+  st0.save(c);
   while (n > 0) {
     const int m = sched_block(c, s, n);
     if (!c->profiling && m >= 2) {
-      const int B = m >= kGraphBlock50 ? kGraphBlock50 : (m & ~1);
+      const int B = m >= kGraphBlock ? kGraphBlock : (m & ~1);
       hipGraphExec_t ge;
       if (get_graph(c, s, B, &ge)) return 1;
       if (!dry) HIPCHECK(hipGraphLaunch(ge, c->stream));
       if (!dry && c->poavg.on) c->poavg.n += B;
       s += B;
       n -= B;
-      if (c->oml.on) oml_rotate(c, B); // the p and q rotations are back where they started, sst has moved on
-      if (c->aml.on) aml_rotate(c, B);
+      ml_rotate(c, B); // the p and q rotations are back where they started, the mixed layer's has moved on
       if (!dry && launch_accums(c, s - 1)) return 1; // after the block's last step
       continue;
     }
@@ -2172,19 +2143,12 @@ static int steps_impl(qgcm_hip_ctx *c, int s0, int n, bool dry) {
     } else {
       c->ip ^= 1;
       c->iq ^= 1;
-      if (c->oml.on) oml_rotate(c, 1);
-      if (c->aml.on) aml_rotate(c, 1);
+      ml_rotate(c, 1);
     }
     ++s;
     --n;
   }
-  if (dry) {
-    c->oml.is = is0;
-    c->oml.ism = ism0;
-    if (c->aml.on) aml_set_idx(c, ia0, iam0);
-    c->ip = ip0;
-    c->iq = iq0;
-  }
+  if (dry) st0.restore(c);
   return 0;
 }
 
@@ -2211,7 +2175,7 @@ extern "C" int qgcm_hip_qgastep(qgcm_hip_handle c) {
 
 extern "C" int qgcm_hip_atinvq(qgcm_hip_handle c) {
   if (check_atm(c, "qgcm_hip_atinvq")) return 1;
-  return ocinvq_impl(c, false);
+  return ocinvq_impl(c);
 }
 
 extern "C" int qgcm_hip_atqzbd(qgcm_hip_handle c) {
@@ -2251,14 +2215,6 @@ static int aml_ready(qgcm_hip_ctx *c, const char *who) {
   if (aml_handle(c, who)) return 1;
   if (!c->aml.on) QG_FAIL("%s: qgcm_hip_aml_init has not been called", who);
   return 0;
-}
-
-// the buffer rotation; atmon.ast / atmon.hmixa follow the current level
-static void aml_set_idx(qgcm_hip_ctx *c, int ia, int iam) {
-  c->aml.ia = ia;
-  c->aml.iam = iam;
-  c->atmon.ast = c->aml.ast[ia];
-  c->atmon.hmixa = c->aml.hm[ia];
 }
 
 extern "C" int qgcm_hip_aml_init(qgcm_hip_handle c, const qgcm_hip_aml_params *p) {
@@ -3111,8 +3067,8 @@ extern "C" int qgcm_hip_slab_stage(qgcm_hip_handle c, int stage, double *a, doub
       // solve by the extra wave of the fused inverse-transform kernel of stage 2 (no k_constr_box launch)
       if (!c->homog_set) QG_FAIL("qgcm_hip_slab_stage: homogeneous solutions not set");
       // (with the mixed layer on, xon(1) is only complete after the all-gather: dpioc is stepped in stage 2 then)
-      const bool fused_constr = can_fuse_dst_unpack(c) && !c->no_fused_constr && !c->oml.on; // can_fuse: box ocean only
-      const int rc = stage == 7 ? 0 : launch_tend(c, fused_constr, false, stage == 1 ? TEND_ALL : stage == 4 ? TEND_INNER : TEND_OUTER);
+      const bool upd_dpi = step_plan(c, true, true).upd_dpi;
+      const int rc = stage == 7 ? 0 : launch_tend(c, upd_dpi, false, stage == 1 ? TEND_ALL : stage == 4 ? TEND_INNER : TEND_OUTER);
       c->bpart_out = nullptr;
       if (rc) return 1;
       if (stage == 4 || stage == 6) return 0;
@@ -3137,33 +3093,28 @@ extern "C" int qgcm_hip_slab_stage(qgcm_hip_handle c, int stage, double *a, doub
                            (long)slab_msg_len_oml(c), nranks, F);
         HIPCHECK(hipGetLastError());
       }
-      if (can_fuse_dst_unpack(c)) {
-        const bool fused_constr = !c->no_fused_constr && !c->oml.on;
-        if (!fused_constr && qgcm_hip_constr(c)) return 1; // area integrals of the whole basin came with the slab summaries
-        // the fused kernel also writes the halo messages (first / last three owned rows of po, edge row of qo)
-        if (launch_dst_unpack(c, true, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr, fused_constr)) return 1;
+      {
+        const QgStepPlan pl = step_plan(c, true, true);
+        double *to_lo = nranks > 1 ? b : nullptr, *to_hi = nranks > 1 ? cc : nullptr;
+        if (pl.constr == CONSTR_OWN && qgcm_hip_constr(c)) return 1; // area integrals of the whole basin came with the slab summaries
+        // the unpack launch, fused or not, also writes the halo messages (first / last three owned rows of po, edge row of qo)
+        switch (pl.inv) {
+          case INV_DST64_UNPACK:
+            if (launch_dst_unpack(c, true, to_lo, to_hi, pl.constr == CONSTR_INV_WAVE)) return 1;
+            break;
+          case INV_FFT3_UNPACK: // long rows: inverse rows + unpack + halo messages in one launch (k_fft3_unpack.h)
+            if (launch_fft3_unpack(c, false, to_lo, to_hi)) return 1;
+            break;
+          default:
+            if (pl.constr == CONSTR_BOX_WG) { // box: the constraint solve rides in the inverse-row launch
+              if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, false, true)) return 1;
+            } else if (qgcm_hip_row_transform(c, 1)) return 1;
+            if (check_ready(c, "qgcm_hip_slab_stage") || launch_unpack(c, true, to_lo, to_hi)) return 1;
+        }
         c->ip ^= 1;
-        if (launch_poavg(c)) return 1;
-        return oml_halo_pack(c, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr);
+        if (launch_poavg(c)) return 1; // the new po of the owned rows, before stage 3 averages it
+        return oml_halo_pack(c, to_lo, to_hi);
       }
-      if (can_fuse_fft3_unpack(c)) { // long rows: inverse rows + unpack + halo messages in one launch (k_fft3_unpack.h)
-        if (qgcm_hip_constr(c)) return 1;
-        if (launch_fft3_unpack(c, false, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr)) return 1;
-        c->ip ^= 1;
-        if (launch_poavg(c)) return 1;
-        return oml_halo_pack(c, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr);
-      }
-      if (dst_box_rides_constr(c)) { // box: the constraint solve rides in the inverse-row launch
-        if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, false, true)) return 1;
-      } else {
-        if (qgcm_hip_constr(c)) return 1;
-        if (qgcm_hip_row_transform(c, 1)) return 1;
-      }
-      // the unpack launch also writes the halo messages (first / last three owned rows of po, edge row of qo)
-      if (check_ready(c, "qgcm_hip_slab_stage") || launch_unpack(c, true, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr)) return 1;
-      c->ip ^= 1;
-      if (launch_poavg(c)) return 1; // the new po of the owned rows, before stage 3 averages it
-      return oml_halo_pack(c, nranks > 1 ? b : nullptr, nranks > 1 ? cc : nullptr);
     case 3:
       if (nranks > 1 && qgcm_hip_halo_unpack(c, a, b)) return 1;
       if (nranks > 1 && c->oml.on) { // the neighbours' edge rows of the new sst sit at the end of the halo messages
@@ -3439,25 +3390,15 @@ static int get_slab_graph(qgcm_hip_ctx *c, int s0, hipGraphExec_t *out) {
     *out = it->second;
     return 0;
   }
-  const int ip0 = c->ip, iq0 = c->iq, is0 = c->oml.is, ism0 = c->oml.ism;
-  const long pn0 = c->poavg.n;
-  hipGraph_t graph;
-  HIPCHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int k = 0; k < kGraphBlock && !rc; ++k) rc = slab_step(c, s0 + k, k + 1 < kGraphBlock);
-  if (!rc) rc = slab_join(c);
-  hipError_t e = hipStreamEndCapture(c->stream, &graph);
-  c->poavg.n = pn0;
-  if (rc && c->sc_comm) c->sc_comm->pending = c->sc_comm->outer_done = false;
-  c->ip = ip0; // nothing ran: the rotation state is that of the block's first step
-  c->iq = iq0;
-  c->oml.is = is0;
-  c->oml.ism = ism0;
-  if (rc) return 1;
-  HIPCHECK(e);
   hipGraphExec_t exec;
-  HIPCHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-  HIPCHECK(hipGraphDestroy(graph));
+  if (capture_block(c, false, &exec, [&]() {
+        int rc = 0;
+        for (int k = 0; k < kGraphBlock && !rc; ++k) rc = slab_step(c, s0 + k, k + 1 < kGraphBlock);
+        if (!rc) rc = slab_join(c);
+        if (rc && c->sc_comm) c->sc_comm->pending = c->sc_comm->outer_done = false;
+        return rc;
+      }))
+    return 1;
   c->slab_graphs[key] = exec;
   *out = exec;
   return 0;
@@ -3474,7 +3415,7 @@ extern "C" int qgcm_hip_slab_steps(qgcm_hip_handle c, int s0, int n) {
     if (get_slab_graph(c, s, &ge)) return 1;
     HIPCHECK(hipGraphLaunch(ge, c->stream));
     if (c->poavg.on) c->poavg.n += kGraphBlock;
-    if (c->oml.on) oml_rotate(c, kGraphBlock); // the p and q rotations are back where they started, sst has moved on
+    ml_rotate(c, kGraphBlock); // the p and q rotations are back where they started, sst has moved on
     s += kGraphBlock; // 50 steps: both rotations are back where they started
     n -= kGraphBlock;
   }
