@@ -64,6 +64,7 @@ def lib():
         L.qgo_oml_set.argtypes = [C.c_void_p] + [dp] * 6
         L.qgo_oml_get.argtypes = [C.c_void_p] + [dp] * 4
         L.qgo_oml.argtypes = [C.c_void_p]
+        L.qgo_oml_get_xfo.argtypes = [C.c_void_p, dp, dp]
         L.qgo_steps_oml.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.qgo_valids.argtypes = [C.c_void_p, dp, dp]
         _lib = L
@@ -271,6 +272,14 @@ class Oracle:
 
     def oml(self):
         self.L.qgo_oml(self.h)
+
+    def oml_get_xfo(self):
+        """(xfo, coneno) on the T grid of the last oml(): xfo before its mean was removed (the terms of the mean
+        entrainment) and the convective part (the terms of centoc)."""
+        x = np.zeros((self.nx - 1, self.ny - 1), order="F")
+        k = np.zeros_like(x)
+        self.L.qgo_oml_get_xfo(self.h, _dp(x), _dp(k))
+        return x, k
 
     def steps_oml(self, s0, n):
         self.L.qgo_steps_oml(self.h, int(s0), int(n))

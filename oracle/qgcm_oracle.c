@@ -54,6 +54,7 @@ struct qgo_ctx {
   double hmoc, toc1, toc2, st2d, st4d, ycexp, rrcpoc, tsbdy, tnbdy;
   double *sst, *sstm, *fnetoc, *wekto, *tauxo, *tauyo; /* T grid (nxto,nyto) x4, p grid x2 */
   double *omrhs, *omd2t, *omxfo;                        /* scratch */
+  double *omxfr, *omcon;                                /* last oml: xfo before its mean is removed, coneno */
   double cfraoc, centoc;
 };
 
@@ -771,7 +772,7 @@ void qgo_destroy(qgo_ctx *c) {
                     c->ocncs, c->ocncn, c->ocncsp, c->ocncnp, c->enisoc, c->eninoc, c->ajisoc, c->ajinoc,
                     c->ap3soc, c->ap3noc, c->ap5soc, c->ap5noc, c->xinhom, c->invcoef, c->d2p, c->d4p,
                     c->dqdt, c->wrk, c->sst, c->sstm, c->fnetoc, c->wekto, c->tauxo, c->tauyo,
-                    c->omrhs, c->omd2t, c->omxfo};
+                    c->omrhs, c->omd2t, c->omxfo, c->omxfr, c->omcon};
   for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) free(ptrs[i]);
   free(c->ipivch);
   free(c);
@@ -1503,7 +1504,7 @@ void qgo_oml_init(qgo_ctx *c, double hmoc, double toc1, double toc2, double st2d
   if (!c->sst) {
     c->sst = dalloc(nt); c->sstm = dalloc(nt); c->fnetoc = dalloc(nt); c->wekto = dalloc(nt);
     c->tauxo = dalloc(np); c->tauyo = dalloc(np);
-    c->omrhs = dalloc(nt); c->omd2t = dalloc(nt); c->omxfo = dalloc(nt);
+    c->omrhs = dalloc(nt); c->omd2t = dalloc(nt); c->omxfo = dalloc(nt); c->omxfr = dalloc(nt); c->omcon = dalloc(nt);
   }
 }
 
@@ -1528,6 +1529,15 @@ void qgo_oml_get(qgo_ctx *c, double *sst, double *sstm, double *entoc, double *s
     scal[0] = c->xon[0]; scal[1] = c->cfraoc; scal[2] = c->centoc;
     scal[3] = c->cyclic ? c->enisoc[0] : 0.0; scal[4] = c->cyclic ? c->eninoc[0] : 0.0;
   }
+}
+
+/* The terms of the two sums of the last qgo_oml whose order the device changes (the tests derive their bounds from
+ * them): xfo(nxto,nyto) as formed at src/omlsubs.F:109-117, before the mean is removed (:147-155), and coneno (:116),
+ * the terms of centsm.  Either pointer may be NULL. */
+void qgo_oml_get_xfo(qgo_ctx *c, double *xfo, double *coneno) {
+  const size_t nb = sizeof(double) * (size_t)c->nxt * (c->ny - 1);
+  if (xfo) memcpy(xfo, c->omxfr, nb);
+  if (coneno) memcpy(coneno, c->omcon, nb);
 }
 
 /* del2t(i,j) of the lagged sst with the boundary variants of src/omlsubs.F:297-300 (W), 331-346 (E),
@@ -1651,6 +1661,7 @@ void qgo_oml(qgo_ctx *c) {
       sstnew = sstnew + fmax(0.0, dtonew);
       cfrasm = cfrasm + (0.5 - copysign(0.5, -dtonew));
       centsm = centsm - coneno;
+      c->omcon[o] = coneno;
       c->sstm[o] = c->sst[o];
       c->sst[o] = sstnew;
     }
@@ -1660,6 +1671,7 @@ void qgo_oml(qgo_ctx *c) {
     for (int i = 1; i <= nxt; ++i) xfsi = xfsi + xfo[(size_t)(i - 1) + (size_t)nxt * (j - 1)];
     xfosum = xfosum + xfsi;
   }
+  memcpy(c->omxfr, xfo, sizeof(double) * (size_t)nxt * nyt);
   for (size_t o = 0; o < (size_t)nxt * nyt; ++o) xfo[o] = xfo[o] - xfosum * ocnorm;
 #define XF(ii, jj) xfo[(size_t)((ii)-1) + (size_t)nxt * ((jj)-1)]
 #define EN(ii, jj) ent[(size_t)((ii)-1) + (size_t)nx * ((jj)-1)]

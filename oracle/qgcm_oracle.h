@@ -11,7 +11,7 @@
  * /root/reference/src (oracle/build_ref.sh -> oracle/_ref/) and against the
  * golden vectors under tests/golden/ that were generated from that build
  * (tests/golden/make_golden.py).  See tests/test_oracle_vs_golden.py.
- * The mixed layer (qgo_oml) is pinned bitwise by three reference builds (tests/golden/make_golden_oml.py,
+ * The mixed layer (qgo_oml) is pinned bitwise by nine reference builds (tests/golden/make_golden_oml.py,
  * tests/test_oml_oracle.py), the validity scan (qgo_valids) by the reference's verdicts on 16 crafted states
  * (tests/golden/make_golden_valids.py, tests/test_valids_oracle.py).
  *
@@ -101,6 +101,7 @@ void qgo_oml_set(qgo_ctx *c, const double *sst, const double *sstm, const double
                  const double *tauxo, const double *tauyo);
 void qgo_oml_get(qgo_ctx *c, double *sst, double *sstm, double *entoc, double *scal);
 void qgo_oml(qgo_ctx *c);
+void qgo_oml_get_xfo(qgo_ctx *c, double *xfo, double *coneno); /* last qgo_oml: xfo before its mean was removed, coneno */
 void qgo_steps_oml(qgo_ctx *c, int s0, int n); /* oml, qgostep, ocinvq, ocqbdy (+ averaging incl. sst) */
 
 /* valids, ocean part (src/valsubs.F:272-527): out = min/max of po, qo, sst, wekto, full layer thickness

@@ -38,6 +38,14 @@ CONFIGS = {
     #  qo(nxpo,j) != qo(1,j))
     "cyc_tiny_spl": (4, 8, "nxta", 3, 12, 3, "-1.19467D-04", "1.31301D-11", 1, "-Dsponge_layer_k247 -Dnospl_in_ewbdy_k247"),
     "cyc_tiny": (4, 8, "nxta", 3, 12, 3, "-1.19467D-04", "1.31301D-11", 1),
+    # mixed-layer grids wider / taller than one tile of the device kernels (tests/golden/make_golden_oml.py): T grid
+    # 65 x 25 with each wall option of a box, 128 x 16 (exact multiples of the tiles), channels of 128 and 72 columns
+    "box_seam": (16, 8, 13, 5, 5, 3, "9.37456D-05", "1.75360D-11", 0),
+    "box_seam_nb": (16, 8, 13, 5, 5, 3, "9.37456D-05", "1.75360D-11", 0, "-Dnb_hflux"),
+    "box_seam_sbnb": (16, 8, 13, 5, 5, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux -Dnb_hflux"),
+    "box_128_sbnb": (36, 8, 32, 4, 4, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux -Dnb_hflux"),
+    "cyc_128": (32, 8, "nxta", 5, 4, 3, "-1.19467D-04", "1.31301D-11", 1),
+    "cyc_72_sbnb": (18, 8, "nxta", 5, 4, 3, "-1.19467D-04", "1.31301D-11", 1, "-Dsb_hflux"),
     "cyc_small": (6, 10, "nxta", 4, 16, 3, "-1.19467D-04", "1.31301D-11", 1),
     "box_natl5": (384, 96, 60, 60, 16, 3, "9.37456D-05", "1.75360D-11", 0),
     "cyc_socn5": (288, 108, "nxta", 36, 16, 3, "-1.19467D-04", "1.31301D-11", 1),

@@ -22,7 +22,7 @@
 //                before it steps dpioc with the new xon (a device-wide completion counter instead would need
 //                device-scope fences - an L2 write-back per workgroup on this multi-XCD part: measured 84 us)
 // The reference's sums run over j then i (and thread-dependent under OpenMP); here the order is fixed but
-// different, so the mean entrainment agrees to rounding (tests: 1e-13 of max|xfo|), everything else bitwise.
+// different, so the mean entrainment agrees to rounding (tests: 2 N 2^-53 sum|xfo| / N), everything else bitwise.
 // Algorithmic traffic: read sstm, sst, po(1), tauxo, tauyo, fnetoc, wekto (7) + write sst, xfo (2) in the first
 // kernel, read xfo + write entoc (2) in the second: 11 N * 8 B = 81 MB at 5 km.
 #pragma once

@@ -257,6 +257,14 @@ PRESETS = {
                                 ah2oc=(240.0, 160.0, 80.0), ah4oc=(3.2e12,) * 3, **_NATL),
     "cyc_tiny_ah2": OceanConfig("cyc_tiny_ah2", 4, 8, 4, 3, 12, 3, dxo=1.0e5, dta=720.0,
                                 ah2oc=(240.0, 160.0, 80.0), ah4oc=(3.2e12,) * 3, **_SOCN),
+    # mixed-layer grids around the 64 x 8 tiles of k_oml_step and the 64 x 16 tiles of k_oml_entoc (own reference builds,
+    # tests/golden/make_golden_oml.py), constants of box_tiny / cyc_tiny.  T grid 65 x 25: one seam, a last tile of one
+    # column and one row; 128 x 16: exact multiples of the tile; channels of 128 and 72 columns: the zonal wrap reaches
+    # into another tile, the last tile full resp. 8 columns wide
+    "box_seam": OceanConfig("box_seam", 16, 8, 13, 5, 5, 3, dxo=1.0e5, dta=720.0, ah4oc=(3.2e12,) * 3, **_NATL),
+    "box_128": OceanConfig("box_128", 36, 8, 32, 4, 4, 3, dxo=1.0e5, dta=720.0, ah4oc=(3.2e12,) * 3, **_NATL),
+    "cyc_128": OceanConfig("cyc_128", 32, 8, 32, 5, 4, 3, dxo=1.0e5, dta=720.0, ah4oc=(3.2e12,) * 3, **_SOCN),
+    "cyc_72": OceanConfig("cyc_72", 18, 8, 18, 5, 4, 3, dxo=1.0e5, dta=720.0, ah4oc=(3.2e12,) * 3, **_SOCN),
     # nxto = 192 = 64*3 and 960 = 64*15: exercise the wave-per-row-pair real-FFT kernels (k_rfft64.h) of the cyclic path
     "cyc_med": OceanConfig("cyc_med", 12, 10, 12, 4, 16, 3, dxo=2.5e4, dta=240.0, ah4oc=(1.2e10,) * 3, **_SOCN),
     "cyc_960": OceanConfig("cyc_960", 60, 12, 60, 3, 16, 3, dxo=5.0e3, **_SOCN),

@@ -81,6 +81,11 @@ def preset(name):
 # ---- ocean mixed layer fixtures (tests/golden/make_golden_oml.py) -----------------------------
 OML_CASES = (("oml_box_tiny", "box_tiny"), ("oml_box_tiny_sb", "box_tiny"), ("oml_cyc_tiny", "cyc_tiny"))
 OML_SNAPS = (1, 2, 26, 40)
+# ... and the short fixtures on grids that cross the seams of the device kernels' tiles (k_oml_step: 64 x 8 T points,
+# k_oml_entoc: 64 x 16 p points): one call and two coupled steps each
+OML_SEAM_CASES = (("oml_box_seam", "box_seam"), ("oml_box_seam_nb", "box_seam"), ("oml_box_seam_sbnb", "box_seam"),
+                  ("oml_box_128_sbnb", "box_128"), ("oml_cyc_128", "cyc_128"), ("oml_cyc_72_sbnb", "cyc_72"))
+OML_SEAM_SNAPS = (1, 2)
 
 
 def oml_config(g):
@@ -102,6 +107,133 @@ def oml_load(model, g, cfg, is_oracle):
     else:
         model.oml_set_state(g["in_sst"], g["in_sstm"])
         model.oml_set_forcing(g["in_fnetoc"], g["in_wekto"], g["in_tauxo"], g["in_tauyo"])
+
+
+def oml_init_oracle(o, om):
+    o.oml_init(om.hmoc, om.toc[0], om.toc[1], om.st2d, om.st4d, om.ycexp, om.rrcpoc, om.sb_hflux, om.tsbdy,
+               om.nb_hflux, om.tnbdy)
+
+
+def bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64)
+
+
+def same_bits(a, b, what):
+    """Equality by integer view; the message counts and locates the points that differ (0-based indices)."""
+    assert np.shape(a) == np.shape(b), (what, np.shape(a), np.shape(b))
+    ne = np.asarray(bits(a) != bits(b))
+    if ne.any():
+        where = np.argwhere(ne)
+        raise AssertionError("%s: %d points differ, max |diff| %.3e, first at %s, columns %d..%d, rows %s" % (
+            what, int(ne.sum()), np.abs(np.asarray(a) - np.asarray(b)).max(), where[:8].tolist(),
+            where[:, 0].min(), where[:, 0].max(), sorted(set(where[:, -1].tolist()))[:12]))
+
+
+def oml_weights(cfg):
+    """Trapezoidal weights of xintp on the p grid (src/intsubs.f:78-133) and of the boundary line sums."""
+    wx, wy = np.ones(cfg.nxpo), np.ones(cfg.nypo)
+    wx[0] = wx[-1] = wy[0] = wy[-1] = 0.5
+    return wx, wy
+
+
+def oml_bounds(cfg, xfo, coneno, entoc):
+    """How far the mixed layer's reordered sums may lie from the reference's.  Everything pointwise in oml is bitwise;
+    only the ORDER of four kinds of sums differs on the device.  With u = 2^-53, a sum of n terms formed with r
+    roundings in any order lies within r u sum|terms| of the exact sum (to first order in u), so two orders differ by at
+    most 2 r u sum|terms|; a scaling of the sum is one more rounding of the chain.
+
+      mean   xmean = (sum of the N = nxto nyto values of xfo) * ocnorm: N - 1 additions and the scaling, r = N:
+             B_mean = 2 N u sum|xfo| ocnorm
+      entoc  0.25 ((x0 - m) + (x1 - m) + (x2 - m) + (x3 - m)) of identical x with means that differ by d <= B_mean: each
+             difference carries d and is rounded (u X each side, X = max|xfo| + |mean| bounds every |x - m|), the three
+             additions round partial sums of at most 4 X: 4 d + 2 u (4 X + 3 * 4 X) = 4 d + 32 u X before the exact
+             factor 0.25 (the two-cell and one-cell forms on the walls come out smaller):
+             B_entoc = B_mean + 8 u X
+      xon(1) dxo dyo sum(w entoc) over the n = nxpo nypo points of the p grid: n - 1 additions and two scalings
+             (r = n + 1) of terms that themselves differ by at most w B_entoc (sum(w) = N < n):
+             B_xon = dxo dyo (2 (n + 1) u sum|w entoc| + n B_entoc)
+      line sums  dxo sum(wx entoc(:, row)), nxpo terms, one scaling (r = nxpo), terms within wx B_entoc:
+             B_line = dxo (2 nxpo u sum|wx entoc| + nxpo B_entoc)
+      centoc dxo dyo sum(-coneno): N identical terms, two scalings (r = N + 1): B_centoc = 2 (N + 1) u sum|coneno| dxo dyo
+    xfo, coneno: the reference algorithm's terms (oracle.oml_get_xfo()); entoc: the reference's result."""
+    u = 2.0 ** -53
+    N, n = cfg.nxto * cfg.nyto, cfg.nxpo * cfg.nypo
+    ocnorm = 1.0 / (float(cfg.nxto) * float(cfg.nyto))
+    wx, wy = oml_weights(cfg)
+    mean = float(xfo.sum()) * ocnorm
+    b = dict(mean=2.0 * N * u * float(np.abs(xfo).sum()) * ocnorm)
+    b["entoc"] = b["mean"] + 8.0 * u * (float(np.abs(xfo).max()) + abs(mean))
+    b["xon"] = cfg.dxo * cfg.dyo * (2.0 * (n + 1) * u * float(np.abs(wx[:, None] * wy[None, :] * entoc).sum()) + n * b["entoc"])
+    b["centoc"] = 2.0 * (N + 1) * u * float(np.abs(coneno).sum()) * cfg.dxo * cfg.dyo
+    for k, row in (("enis", 0), ("enin", -1)):
+        b[k] = cfg.dxo * (2.0 * cfg.nxpo * u * float(np.abs(wx * entoc[:, row]).sum()) + cfg.nxpo * b["entoc"])
+    return b
+
+
+def oml_check_sums(tag, cfg, bound, ent, scal, ref_ent, ref_scal):
+    """entoc and the scalars (xon(1), cfraoc, centoc, enisoc(1), eninoc(1)) of one call against the reference's within
+    oml_bounds; every figure is printed before it is asserted.  Returns the largest |diff| / bound per quantity."""
+    ratios = {}
+    d = np.abs(np.asarray(ent) - ref_ent)
+    ij = np.unravel_index(int(d.argmax()), d.shape)
+    print("%s entoc: max |diff| %.3e at %s, bound %.3e" % (tag, d.max(), ij, bound["entoc"]))
+    assert d.max() <= bound["entoc"], (tag, "entoc", float(d.max()), ij, bound["entoc"])
+    ratios["entoc"] = float(d.max() / bound["entoc"])
+    assert scal[1] == ref_scal[1], (tag, "cfraoc", scal[1], ref_scal[1])  # the convecting fraction: an exact count
+    names = (("xon", 0), ("centoc", 2)) + ((("enis", 3), ("enin", 4)) if cfg.cyclic else ())
+    for f, k in names:
+        diff = abs(float(scal[k]) - float(ref_scal[k]))
+        print("%s %s: got %.17e reference %.17e |diff| %.3e bound %.3e" % (tag, f, scal[k], ref_scal[k], diff, bound[f]))
+        assert diff <= bound[f], (tag, f, float(scal[k]), float(ref_scal[k]), bound[f])
+        ratios[f] = diff / bound[f]
+    return ratios
+
+
+def oml_numpy_sums(cfg, xfo, coneno):
+    """The reordered part of oml (src/omlsubs.F:131-233) again with numpy's pairwise sums: mean removal, averaging onto
+    the p grid in the reference's operand order, xon(1), centoc and the line sums.  Returns entoc and the five scalars
+    (cfraoc left 0: it is a count)."""
+    nx, ny = cfg.nxpo, cfg.nypo
+    ocnorm = 1.0 / (float(cfg.nxto) * float(cfg.nyto))
+    x = xfo - float(np.sum(xfo)) * ocnorm
+    e = np.zeros((nx, ny), order="F")
+    e[1:-1, 1:-1] = 0.25 * (x[:-1, :-1] + x[1:, :-1] + x[:-1, 1:] + x[1:, 1:])
+    e[1:-1, 0] = 0.5 * (x[:-1, 0] + x[1:, 0])
+    e[1:-1, -1] = 0.5 * (x[:-1, -1] + x[1:, -1])
+    if cfg.cyclic:
+        e[0, 1:-1] = 0.25 * (x[-1, :-1] + x[0, :-1] + x[-1, 1:] + x[0, 1:])
+        e[0, 0] = 0.5 * (x[-1, 0] + x[0, 0])
+        e[0, -1] = 0.5 * (x[-1, -1] + x[0, -1])
+        e[-1, :] = e[0, :]
+    else:
+        e[0, 1:-1] = 0.5 * (x[0, :-1] + x[0, 1:])
+        e[-1, 1:-1] = 0.5 * (x[-1, :-1] + x[-1, 1:])
+        e[0, 0], e[-1, 0], e[0, -1], e[-1, -1] = x[0, 0], x[-1, 0], x[0, -1], x[-1, -1]
+    wx, wy = oml_weights(cfg)
+    scal = np.zeros(5)
+    scal[0] = float(np.sum(wx[:, None] * wy[None, :] * e)) * cfg.dxo * cfg.dyo
+    scal[2] = float(np.sum(-coneno)) * cfg.dxo * cfg.dyo
+    if cfg.cyclic:
+        scal[3] = cfg.dxo * float(np.sum(wx * e[:, 0]))
+        scal[4] = cfg.dxo * float(np.sum(wx * e[:, -1]))
+    return e, scal
+
+
+def oml_convecting(call_sst, toc1):
+    """Points that convected in a call: the adjustment (7.13, src/omlsubs.F:116-119) leaves them at toc(1), to the
+    rounding of one addition; every other point ends above it."""
+    return call_sst <= toc1 * (1.0 + 4.0 * np.finfo(float).eps)
+
+
+def oml_seam_columns(nxto, cyclic):
+    """0-based T columns next to an x seam of the 64-wide tiles, two on either side where the grid has them; a
+    channel's wrap is a seam between its last and its first tile."""
+    cols = set()
+    for s in range(64, nxto, 64):
+        cols.update(c for c in (s - 2, s - 1, s, s + 1) if c < nxto)
+    if cyclic and nxto > 64:
+        cols.update((nxto - 2, nxto - 1, 0, 1))
+    return sorted(cols)
 
 
 # ---- atmosphere fixtures (tests/golden/make_golden_atmos.py), SURVEY 8 row f3 ------------------------------
