@@ -23,9 +23,23 @@ and in y.  The temperature fields carry a warm patch on the zonal seam next to t
 above the ocean), where astm passes tat(1): every branch of the step is taken there, at the wall, at the seam and in
 the interior, and the assertions at the end of this script check that on the reference's own outputs.
 
+The cases and what each is for:
+  heat_cpl_tiny    the smallest coupled grid, plain (xcexp = 1, xc1ast = dtopat = 0), ndxr = 12
+  heat_odd5        odd ndxr
+  heat_cyc4        cyclic ocean as wide as the atmosphere (bilint's wrapped columns)
+  heat_wide        (96, 24): two aml tile columns and three tile rows
+  heat_cpl_small   ndxr = 16, the production refinement: k_xf_heat_oc's loop over the ndxr^2 ocean points of a cell
+                   takes four rounds of 64
+  heat_cyc72       cyclic, 288 cells above the ocean: a second round of k_xf_heat_final's loops of stride 256; the
+                   last aml tile is 8 columns wide
+  heat_300         320 cells above the ocean; five aml tile columns with a tail of 44; nxpa = 301, so aml reads uekat,
+                   vekat and wekta that the momentum kernels produced in more than one block
+
   python tests/golden/make_golden_heat.py           # writes tests/golden/heat_*.npz
+  python tests/golden/make_golden_heat.py NAME ...  # writes only the named cases
   python tests/golden/make_golden_heat.py time [N]  # the reference's xforc (N = 16 threads) and aml (one) at cpl_natl5
 """
+import io
 import os
 import re
 import shutil
@@ -170,7 +184,10 @@ end program heat_driver
 CASES = [("heat_cpl_tiny", (16, 12, 4, 3, 12), False, True),
          ("heat_odd5", (16, 12, 6, 4, 5), False, False),
          ("heat_cyc4", (16, 12, 16, 4, 4), True, False),
-         ("heat_wide", (96, 24, 6, 5, 4), False, False)]
+         ("heat_wide", (96, 24, 6, 5, 4), False, False),
+         ("heat_cpl_small", (32, 20, 6, 5, 16), False, False),
+         ("heat_cyc72", (72, 12, 72, 4, 4), True, False),
+         ("heat_300", (300, 12, 80, 4, 4), False, False)]
 NATL5 = (384, 96, 60, 60, 16)
 
 
@@ -376,6 +393,13 @@ def check_branches(name, dims, cyc, C, F, res):
     assert all(got.values()) and any(0.0 < v < 1.0 for v in cf), (name, got, cf)
 
 
+def packed_size(d):
+    """The size of the compressed file that np.savez_compressed would write for d."""
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **d)
+    return buf.getbuffer().nbytes
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "time":
         n = int(sys.argv[2]) if len(sys.argv) > 2 else 16
@@ -383,7 +407,11 @@ if __name__ == "__main__":
         print("reference at cpl_natl5 (385x97 / 961x961, ndxr 16): xforc (both halves) %.2f ms per call on %d threads, "
               "aml %.3f ms per call on one thread (built without OpenMP)" % (1e3 * t["xforc"], n, 1e3 * t["aml"]))
         sys.exit(0)
+    only = sys.argv[1:]
+    assert all(n in [c[0] for c in CASES] for n in only), only
     for ic, (name, dims, cyc, plain) in enumerate(CASES):
+        if only and name not in only:
+            continue
         C = constants(dims, plain)
         F = inputs(dims, cyc, plain, C, 300 + ic)
         wrk = tempfile.mkdtemp(prefix="heat_")
@@ -403,12 +431,21 @@ if __name__ == "__main__":
         out.update({"c_" + k: np.float64(v) for k, v in C.items()})
         out.update({"in_" + k: np.asfortranarray(v) for k, v in F.items()})
         out.update(res)
-        # (one file per case, or two where the nine aml records would push it past the size limit of a committed file:
-        #  <case>.npz with everything else and <case>_aml.npz with the a<c><s>_* records)
+        # (one file per case, or several where the nine aml records would push it past the size limit of a committed
+        #  file: <case>.npz with everything else and <case>_aml.npz, <case>_aml2.npz, ... with the a<c><s>_* records,
+        #  cut call by call into as few parts as stay under the limit)
         parts = {name: out}
         if sum(np.asarray(v).nbytes for v in out.values()) > 900000:
-            parts = {name: {k: v for k, v in out.items() if not re.match(r"a\d\d_", k)},
-                     name + "_aml": {k: v for k, v in out.items() if re.match(r"a\d\d_", k)}}
+            parts = {name: {k: v for k, v in out.items() if not re.match(r"a\d\d_", k)}}
+            calls = ["a%d%d_" % (c, s) for c in range(K) for s in range(NSTR)]
+            for n in range(1, len(calls) + 1):
+                cut = [calls[len(calls) * i // n:len(calls) * (i + 1) // n] for i in range(n)]
+                aml = {name + "_aml" + (str(i + 1) if i else ""): {k: v for k, v in out.items() if k[:4] in grp}
+                       for i, grp in enumerate(cut)}
+                if all(packed_size(d) < (1 << 20) for d in aml.values()):
+                    break
+            parts.update(aml)
+            assert sum(len(d) for d in parts.values()) == len(out)
         for fn, d in parts.items():
             path = os.path.join(HERE, "%s.npz" % fn)
             np.savez_compressed(path, **d)

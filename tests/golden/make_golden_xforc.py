@@ -11,7 +11,22 @@ of spun-up magnitude, calls xforc on each and writes the twelve momentum fields,
 the five weight tables.  Every thermodynamic input is zero (fnetoc / fnetat are not recorded).  All reference sources,
 objects and .mod files stay in the temporary directory, which is deleted.
 
+The cases and what each is for (the launch geometry is that of qgcm_hip_xforc: 256 threads along a row for the
+pointwise kernels, 64 for k_xf_wekpa, XF_CX = 8 atmosphere cells per workgroup in k_xf_fine, one workgroup striding by
+256 in k_xf_lines):
+  xf_cpl_tiny / _ud   the smallest coupled grid, without and with the shear term (tau_udiff)
+  xf_cpl_small_ud     ndxr = 16, the production refinement
+  xf_odd5_ud          odd ndxr (half weights on both edges of a cell)
+  xf_cyc4_ud          cyclic ocean as wide as the atmosphere (the ocean's own line integrals)
+  xf_wide_ud          nxpa = 301: two blocks of 256 and five of 64 along the atmosphere's rows; nxta % 8 = 4: a tail
+                      workgroup of k_xf_fine that holds column nxta and its wrap; nxpo = 321: two blocks along the
+                      ocean's rows (k_xf_tauo, k_wekto, k_wekpo)
+  xf_edge_ud          nxpa = nxpo = 257: the second block holds exactly one live thread, on the atmosphere the copy
+                      column ia = nxpa
+  xf_cycwide_ud       cyclic ocean with nxpo = 361: two rounds of k_xf_lines' loop over the ocean; nxta % 8 = 2
+
   python tests/golden/make_golden_xforc.py           # writes tests/golden/xf_*.npz
+  python tests/golden/make_golden_xforc.py NAME ...  # writes only the named cases
   python tests/golden/make_golden_xforc.py time [N]  # the reference's xforc at cpl_natl5 on N (16) threads
 """
 import os
@@ -94,7 +109,10 @@ CASES = [("xf_cpl_tiny", (16, 12, 4, 3, 12), False, False),
          ("xf_cpl_tiny_ud", (16, 12, 4, 3, 12), False, True),
          ("xf_cpl_small_ud", (32, 20, 6, 5, 16), False, True),
          ("xf_odd5_ud", (16, 12, 6, 4, 5), False, True),
-         ("xf_cyc4_ud", (16, 12, 16, 4, 4), True, True)]
+         ("xf_cyc4_ud", (16, 12, 16, 4, 4), True, True),
+         ("xf_wide_ud", (300, 12, 80, 4, 4), False, True),
+         ("xf_edge_ud", (256, 12, 64, 4, 4), False, True),
+         ("xf_cycwide_ud", (90, 12, 90, 4, 4), True, True)]
 NATL5 = (384, 96, 60, 60, 16)
 
 
@@ -227,8 +245,12 @@ if __name__ == "__main__":
         print("reference xforc at cpl_natl5 (385x97 / 961x961, ndxr 16, tau_udiff): %.1f ms per call on %d threads"
               % (1e3 * time_xforc(n), n))
         sys.exit(0)
+    only = sys.argv[1:]
+    assert all(n in [c[0] for c in CASES] for n in only), only
     done = {}
     for name, dims, cyc, udiff in CASES:
+        if only and name not in only:
+            continue
         pairs = [smooth_pair(dims, cyc, 100 + s) for s in range(2)]
         wrk = tempfile.mkdtemp(prefix="xf_")
         try:
@@ -252,4 +274,5 @@ if __name__ == "__main__":
         sys.stderr.write("wrote %s.npz (%d bytes)\n" % (name, size))
         done[name] = out
     # the shear term must be visible in the fixtures, else tau_udiff would not be tested
-    assert not np.array_equal(done["xf_cpl_tiny"]["out0_tauxo"], done["xf_cpl_tiny_ud"]["out0_tauxo"])
+    if "xf_cpl_tiny" in done and "xf_cpl_tiny_ud" in done:
+        assert not np.array_equal(done["xf_cpl_tiny"]["out0_tauxo"], done["xf_cpl_tiny_ud"]["out0_tauxo"])

@@ -2,12 +2,13 @@
 (src/xfosubs.F:711-853 with bilint, :891-993): every expression in the reference's operand order, every sum in its
 serial order, so that IEEE arithmetic reproduces the reference bit for bit.  Arrays are indexed [i-1, j-1] (Fortran
 order).  The fixtures are tests/golden/heat_*.npz (tests/golden/make_golden_heat.py)."""
+import glob
 import os
 
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = ("heat_cpl_tiny", "heat_odd5", "heat_cyc4", "heat_wide")
+CASES = ("heat_cpl_tiny", "heat_odd5", "heat_cyc4", "heat_wide", "heat_cpl_small", "heat_cyc72", "heat_300")
 AML_FIELDS = ("ast", "astm", "hmixa", "hmixam", "entat")
 AML_SUMS = ("xan", "enisat", "eninat", "centat")  # (cfraat is an exact count)
 HEAT_SCALARS = ("arlaav", "slhfav", "oradav", "arocav")
@@ -19,15 +20,14 @@ _cache = {}
 
 
 def load(case):
-    """The fixture as a dict (loaded once, shared, never modified by the tests); <case>_aml.npz, where the generator
-    had to split a case, is merged in."""
+    """The fixture as a dict (loaded once, shared, never modified by the tests); every part <case>_aml*.npz, where the
+    generator had to split a case, is merged in."""
     if case not in _cache:
         d = {}
-        for fn in (case + ".npz", case + "_aml.npz"):
-            path = os.path.join(GOLDEN, fn)
-            if os.path.exists(path):
-                with np.load(path) as g:
-                    d.update({k: g[k] for k in g.files})
+        for path in [os.path.join(GOLDEN, case + ".npz")] + sorted(glob.glob(os.path.join(GOLDEN, case + "_aml*.npz"))):
+            with np.load(path) as g:
+                assert not set(g.files) & set(d), path
+                d.update({k: g[k] for k in g.files})
         _cache[case] = d
     return _cache[case]
 

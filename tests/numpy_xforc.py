@@ -6,7 +6,8 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = ("xf_cpl_tiny", "xf_cpl_tiny_ud", "xf_cpl_small_ud", "xf_odd5_ud", "xf_cyc4_ud")
+CASES = ("xf_cpl_tiny", "xf_cpl_tiny_ud", "xf_cpl_small_ud", "xf_odd5_ud", "xf_cyc4_ud", "xf_wide_ud", "xf_edge_ud",
+         "xf_cycwide_ud")
 POINTWISE = ("tauxa", "tauya", "uekat", "vekat", "wekta", "wekpa", "tauxo", "tauyo", "wekto", "wekpo")
 INTEGRALS = ("txisat", "txinat", "txisoc", "txinoc")
 TABLES = ("stbbb", "stbus", "stbvs", "stbun", "stbvn")

@@ -79,7 +79,7 @@ def test_golden(case):
         a.close()
 
 
-@pytest.mark.parametrize("case", ["xf_cpl_tiny_ud", "xf_cyc4_ud"])
+@pytest.mark.parametrize("case", ["xf_cpl_tiny_ud", "xf_cyc4_ud", "xf_cycwide_ud"])
 def test_destinations(case):
     """After xforc the consumers' own buffers hold what xforc_get reports: wekpa / wekpo where the steppers read them
     (the buffers of set_forcing), the scalars behind set_cyc_forcing, the mixed layer's wekto and stress (after

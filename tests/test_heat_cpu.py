@@ -99,3 +99,20 @@ def test_fixtures_exercise_their_branches():
     assert any(np.abs(nh.load(c)["in_xc1ast"]).max() > 0 and np.abs(nh.load(c)["in_dtopat"]).max() > 0 for c in nh.CASES)
     assert any(p["ndxr"] % 2 == 1 for p in P) and any(p["cyclic"] and p["nxaooc"] == p["nxta"] for p in P)
     assert any(p["nxta"] > 64 and p["nyta"] > 8 for p in P)
+    # The launch geometry (k_xforc.h, k_aml.h), from the fixtures' dimensions alone; each line is one path that some
+    # fixture must reach.
+    blocks = lambda n, w: -(-n // w)
+    # k_xf_heat_oc: a wave strides by 64 over the ndxr^2 ocean points of a cell; the production refinement takes four rounds
+    assert any(p["ndxr"] == 16 for p in P)
+    # k_xf_heat_final: one workgroup strides by 256 over the cells above the ocean; a second round, box and cyclic
+    assert any(p["nxaooc"] * p["nyaooc"] > 256 and not p["cyclic"] for p in P)
+    assert any(p["nxaooc"] * p["nyaooc"] > 256 and p["cyclic"] for p in P)
+    # k_aml_step, k_aml_entat: 64-wide tiles; more than two tile columns and a last one that is neither full nor half
+    assert any(blocks(p["nxta"], 64) >= 3 and p["nxta"] % 64 not in (0, 32) for p in P)
+    # ... and a last tile of at most 8 columns (most of its threads idle, the zonal wrap right behind its few columns)
+    assert any(0 < p["nxta"] % 64 <= 8 for p in P)
+    # aml fed by uekat, vekat, wekta of multi-block momentum kernels: 256 threads along nxpa = nxta + 1
+    assert any(blocks(p["nxta"] + 1, 256) >= 2 for p in P)
+    # a<c><s>_* records cut into more than one extra part are all merged back
+    g = nh.load("heat_300")
+    assert all("a%d%d_%s" % (c, s, f) in g for c in range(3) for s in range(3) for f in nh.AML_FIELDS + nh.AML_SUMS)

@@ -36,6 +36,28 @@ def test_fixtures_exercise_their_branches():
         g = nx.load(case)
         for s in range(2):
             assert np.abs(g["out%d_wekpa" % s]).max() > 0 and np.abs(g["out%d_wekpo" % s]).max() > 0
+    # The launch geometry of qgcm_hip_xforc (k_xforc.h), from the fixtures' dimensions alone: 256 threads along a row
+    # of nxpa, nxta, nxpo or nxto points, 64 along nxpa in k_xf_wekpa, XF_CX = 8 cells per workgroup of k_xf_fine, one
+    # workgroup striding by 256 in k_xf_lines.  Each line is one path that some fixture must reach.
+    P = [nx.params(nx.load(c)) for c in nx.CASES]
+    for p in P:
+        p.update(nxpa=p["nxta"] + 1, nxto=p["nxaooc"] * p["ndxr"], nxpo=p["nxaooc"] * p["ndxr"] + 1)
+    blocks = lambda n, w: -(-n // w)
+    # k_xf_coarse, k_xf_atm: a second block along nxpa; k_xf_wekta: along nxta
+    assert any(blocks(p["nxpa"], 256) >= 2 for p in P) and any(blocks(p["nxta"], 256) >= 2 for p in P)
+    # ... and a second block that holds the copy column ia = nxpa alone
+    assert any(p["nxpa"] % 256 == 1 and p["nxpo"] % 256 == 1 for p in P)
+    # k_xf_wekpa: more than two blocks of 64, the cyclic wrap of `it` reached from the first and from the last
+    assert any(blocks(p["nxpa"], 64) >= 3 for p in P)
+    # k_xf_fine: a tail workgroup of fewer than 8 cells (it holds column nxta, whose icp2 wraps), with a full one before
+    assert any(p["nxta"] % 8 != 0 and p["nxta"] > 8 for p in P)
+    # k_xf_tauo, k_wekto, k_wekpo: a second block along the ocean's rows, for a box and for a cyclic ocean
+    assert any(blocks(p["nxpo"], 256) >= 2 and blocks(p["nxto"], 256) >= 2 and not p["cyclic"] for p in P)
+    assert any(blocks(p["nxpo"], 256) >= 2 and blocks(p["nxto"], 256) >= 2 and p["cyclic"] for p in P)
+    # k_xf_lines: a second round of the cyclic ocean's loop (the atmosphere's loop over nxpaor takes several in every case)
+    assert any(p["cyclic"] and p["nxpo"] > 256 for p in P)
+    assert all(float(nx.load(c)["out0_txisoc"]) != 0.0 and float(nx.load(c)["out0_txinoc"]) != 0.0
+               for c, p in zip(nx.CASES, P) if p["cyclic"])
 
 
 # hostinit.bcuini against the tables the reference built.  Bitwise for ndxr = 4, 12 and 16.  At ndxr = 5 the reference
