@@ -22,7 +22,7 @@ m.set_p(po, po); m.set_forcing(wek, np.zeros_like(wek), np.zeros(cfg.nlo - 1))
 if cfg.cyclic:
     m.set_cyc_forcing(*synth.tau_line_integrals(cfg, tx))
 m.steps(60, s0=1); m.sync()
-buf = np.zeros((4, 4096, 10), dtype=np.int64)
+buf = np.zeros((4, 4096, 12), dtype=np.int64)
 for rep in range(3):
     m.steps(20); m.sync()
     m.L.qgcm_hip_debug_stamps(buf.ctypes.data_as(C.c_void_p), C.c_size_t(buf.nbytes))

@@ -159,8 +159,8 @@ __device__ __forceinline__ void d64_wave_scan2(double &a, double &b) {
 // Split in two so that a caller can issue its own prefetches BETWEEN the halves: the front half (row loads,
 // pre-twiddle, M-point DFTs) peaks at ~230 VGPRs, all dead when it returns.
 template <int M>
-__device__ __forceinline__ void dst64_front(const QgDstParams &P, const double *rowa, const double *rowb, bool has_b,
-                                            cplx *F, cplx *W64, int lane) {
+__device__ __forceinline__ void dst64_front(const double2 *twid, const double *sintab, const double *rowa, const double *rowb,
+                                            bool has_b, cplx *F, cplx *W64, int lane) {
   constexpr int N = 64 * M, n = N - 1, NS2 = n / 2; // n odd: NS2 = N/2 - 1 = K
 
   // Everything this lane will need from global tables is requested up front so
@@ -168,13 +168,13 @@ __device__ __forceinline__ void dst64_front(const QgDstParams &P, const double *
   // factors, and this wave's copy of the 64-point twiddles.
   cplx tw1[M]; // W_N^(lane*k1) as powers of W_N^lane (one coalesced load; depth-4 product tree)
   {
-    double2 w = P.twid[lane];
+    double2 w = twid[lane];
     tw1[1 % M] = {w.x, w.y};
 #pragma unroll
     for (int k1 = 2; k1 < M; ++k1) tw1[k1] = cmul(tw1[k1 / 2], tw1[k1 - k1 / 2]);
   }
   {
-    double2 w = P.twid[M * lane];
+    double2 w = twid[M * lane];
     W64[lane] = {w.x, w.y};
   }
 
@@ -197,7 +197,7 @@ __device__ __forceinline__ void dst64_front(const QgDstParams &P, const double *
       const int j = 64 * n1 + lane;
       const int k = (j <= NS2 + 1) ? j : 0;                    // (lanes past the middle of register MH: clamped, unused)
       const int i1 = k > 0 ? k - 1 : 0, i2 = k > 0 ? n - k : 0; // j = 0: z = 0, loads clamped
-      snv[n1] = P.sintab[(k <= NS2) ? k : 0];
+      snv[n1] = sintab[(k <= NS2) ? k : 0];
       xav[n1] = rowa[i1];
       xac[n1] = rowa[i2];
       xbv[n1] = rb[i1];
@@ -383,13 +383,19 @@ __device__ __forceinline__ void dst64_back(cplx *F, const cplx *W64, int lane, d
 template <int M>
 __device__ __forceinline__ void dst64_core(const QgDstParams &P, const double *rowa, const double *rowb, bool has_b,
                                            cplx *F, cplx *W64, int lane, double &rsa, double &rsb) {
-  dst64_front<M>(P, rowa, rowb, has_b, F, W64, lane);
+  dst64_front<M>(P.twid, P.sintab, rowa, rowb, has_b, F, W64, lane);
   dst64_back<M>(F, W64, lane, rsa, rsb);
 }
 
+// Leading scalar arguments (QG_ROW_ARGS, qgcm_dev.h): what a wave needs to take its early exit and to form the addresses
+// of its first loads.  The compiler preloads them into SGPRs at wave launch (Makefile: kernarg preload), so the row and
+// table loads are issued without a scalar round trip to the kernarg segment - every wave of these one-generation
+// kernels is the first on its SIMD and finds those lines cold.  The struct behind them is unchanged; the host passes
+// QG_ROW_VALS of that very struct.
 // grid: (ceil(npairs / 4), nlayers), block 64*D64_WAVES = independent waves
 template <int M, bool ROWSUM>
-__global__ __launch_bounds__(D64_NT) void k_dst64(const QgDstParams P) {
+__global__ __launch_bounds__(D64_NT) void k_dst64(QG_ROW_ARGS, const QgDstParams P) {
+  QG_STAMP(0, 10);
   constexpr int N = 64 * M;
   __shared__ __align__(16) cplx Fsh[D64_WAVES][M * D64_ROW];
   __shared__ __align__(16) cplx W64sh[D64_WAVES][64]; // exp(-2 pi i t / 64), per wave copy
@@ -397,17 +403,17 @@ __global__ __launch_bounds__(D64_NT) void k_dst64(const QgDstParams P) {
   // (the wave's number as a scalar: the row pointers below are then uniform - one SGPR pair plus 32-bit lane offsets
   //  per load / store instead of a 64-bit address computed in VGPRs for each)
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ny = P.g.ny, ldw = P.g.ldw;
-  const int m = blockIdx.y + P.layer0;
+  const int m = blockIdx.y + layer0;
   const int pair = blockIdx.x * D64_WAVES + wv;
-  const int ja = P.g.jr0 + 2 * pair;
-  if (ja > P.g.jr1) return; // whole wave leaves; no workgroup barrier is ever used
-  const bool has_b = (ja + 1 <= P.g.jr1);
-  double *rowa = P.wrk + P.g.wstride * m + (long)(ja - 1) * ldw;
+  const int ja = jr0 + 2 * pair;
+  if (ja > jr1) return; // whole wave leaves; no workgroup barrier is ever used
+  const bool has_b = (ja + 1 <= jr1);
+  double *rowa = wrk + wstride * m + (long)(ja - 1) * ldw;
   double *rowb = rowa + ldw;
   double rsa, rsb;
   QG_STAMP(0, 0);
-  dst64_front<M>(P, rowa, rowb, has_b, Fsh[wv], W64sh[wv], lane);
+  QG_STAMP(0, 11);
+  dst64_front<M>(twid, sintab, rowa, rowb, has_b, Fsh[wv], W64sh[wv], lane);
   QG_STAMP(0, 1);
   dst64_back<M>(Fsh[wv], W64sh[wv], lane, rsa, rsb);
   QG_STAMP(0, 2);
@@ -444,6 +450,7 @@ __global__ __launch_bounds__(D64_NT) void k_dst64(const QgDstParams P) {
       rsb += __shfl_down(rsb, off);
     }
     if (lane == 0) {
+      const int ny = P.g.ny;
       P.rowsum[(long)m * ny + (ja - 1)] = rsa;
       if (has_b) P.rowsum[(long)m * ny + ja] = rsb;
     }
@@ -473,8 +480,9 @@ __global__ __launch_bounds__(D64_NT) void k_dst64(const QgDstParams P) {
 // AVG: the leapfrog averaging that follows the step (src/q-gcm.F:1345-1351) folded into the stores (QgUnpackParams.pavg /
 // qavg) - a template flag, instantiated for the whole-domain step only: the other 24 steps of 25 run the plain code.
 template <int M, int NL, bool BDY, bool HALO, bool CONSTR, bool AVG = false>
-__global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_dst64_unpack(const QgDstParams P, const QgUnpackParams U,
+__global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_dst64_unpack(QG_ROW_ARGS, const QgUnpackParams U,
                                                                                       const QgBdyParams B, const QgConstrLite C) {
+  QG_STAMP(2, 10);
   constexpr int N = 64 * M, NP = N + N / 16;
   __shared__ __align__(16) cplx Fsh[NL][M * D64_ROW];
   __shared__ __align__(16) cplx W64sh[NL][64];
@@ -482,9 +490,8 @@ __global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_dst64_unpack(c
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6); // = mode (NL: the constraint wave); scalar: uniform row pointers
-  const int ldw = P.g.ldw;
-  const int ja = P.g.jr0 + 2 * blockIdx.x;     // local rows ja, ja+1 (grid is exactly the pairs)
-  const bool has_b = (ja + 1 <= P.g.jr1);
+  const int ja = jr0 + 2 * blockIdx.x;         // local rows ja, ja+1 (grid is exactly the pairs)
+  const bool has_b = (ja + 1 <= jr1);
   const long fs = U.g.fstride;
   const int nx = U.g.nx, nyg = U.g.nyg, joff = U.g.joff;
   constexpr int NX = N + 1;
@@ -626,9 +633,10 @@ __global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_dst64_unpack(c
   // Everything the combine step reads from global memory is requested before the back half of the transform - after
   // the front half, whose row loads need the registers (one wave per mode), so that the kernel keeps two waves per SIMD.
   constexpr int NT = 64 * NL, NPAIR = (NX - 3) / 2, NIT = (NPAIR + NT - 1) / NT;
-  const double *rowa = P.wrk + P.g.wstride * wv + (long)(ja - 1) * ldw;
+  const double *rowa = wrk + wstride * wv + (long)(ja - 1) * ldw; // (all modes: layer0 is not used)
   QG_STAMP(2, 0);
-  dst64_front<M>(P, rowa, rowa + ldw, has_b, Fsh[wv], W64sh[wv], lane);
+  QG_STAMP(2, 11);
+  dst64_front<M>(twid, sintab, rowa, rowa + ldw, has_b, Fsh[wv], W64sh[wv], lane);
   QG_STAMP(2, 1);
   asm volatile("" ::: "memory"); // keep the prefetch below the front half
   // (column pairs (3,4), (5,6) .. (nx-2, nx-1): 16-byte aligned in the field arrays - 16-byte loads of ochom and

@@ -204,8 +204,9 @@ template <int NL, bool CYC, bool WTQ, bool AVG = false>
 #ifndef TEND_WAVES_WTQ
 #define TEND_WAVES_WTQ 4
 #endif
-__global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_WAVES_PER_EU) void k_tend(const QgTendParams P, const QgCycSumParams S,
-                                                                     const QgOmlFinal F) {
+__global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_WAVES_PER_EU) void k_tend(QG_TEND_ARGS, const QgTendParams P,
+                                                                     const QgCycSumParams S, const QgOmlFinal F) {
+  QG_STAMP(3, 10);
 #ifndef TEND_EXPERIMENT // (tile-shape A/B builds without the mixed layer: profiles/r4_tend_shapes_socn5.log)
   static_assert(TEND_NT == OML_NT, "oml_final_block runs in workgroup 0 of this kernel");
 #endif
@@ -225,25 +226,28 @@ __global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_W
   __shared__ double spo[H1 * W1];
   __shared__ double sqo[H1 * W1];
 
-  const int nx = P.g.nx, ny = P.g.ny, nxt = P.g.nxt, ldx = P.g.ldx;
-  const int nyg = P.g.nyg, joff = P.g.joff, jlo = P.g.jlo, jhi = P.g.jhi; // slab view (global row = local + joff)
+  // nx .. jhi (slab view: global row = local + joff), the row window and `side` are leading scalar arguments, preloaded
+  // into SGPRs (QG_TEND_ARGS, qgcm_dev.h): the tile mapping and the staging offsets below wait for no scalar load
+  const double *po0 = P.po, *qo0 = P.qo; // (requested here: they arrive while the offsets are formed)
   const long fs = P.g.fstride;
   const int tid = threadIdx.x;
   // ---- XCD-aware tile numbering ------------------------------------------
   // Box grids have nx = 64*g + 1 columns and (whole basin) 8*h + 1 rows: the last column and the last
   // row are walls whose update is point-wise (no stencil), so they are peeled off into a few "edge"
   // workgroups instead of a whole extra column / row of nearly empty tiles (tend_edge below).
-  const TendTiling T = tend_tiling<CYC, TX>(P.g);
+  QgGeom gt; // what tend_tiling reads
+  gt.nx = nx; gt.jlo = jlo; gt.jhi = jhi; gt.joff = joff; gt.nyg = nyg;
+  const TendTiling T = tend_tiling<CYC, TX>(gt);
   const int gx = T.gx;
-  const int ntiles = gx * (P.trows ? P.trows : T.gy); // (a window of the tile rows, or all of them)
+  const int ntiles = gx * (trows ? trows : T.gy); // (a window of the tile rows, or all of them)
   const int per_xcd = (ntiles + 7) / 8;
-  if (F.on && blockIdx.x == 0) {
+  if ((side & 1) && blockIdx.x == 0) {
     // mixed layer on, inside qgcm_hip_steps: the last reduction of `oml` (xon(1), enisoc(1) / eninoc(1), monitors) is
     // done here instead of in a one-workgroup launch; xon must be final before dpioc is stepped below
     __shared__ double redf[20];
     oml_final_block(F, redf, tid);
   }
-  if (!CYC && P.upd_dpi && blockIdx.x == 0 && tid == 0) constr_dpi_update<NL>(P.sc, P.tdto, P.gpoc); // see QgTendParams
+  if (!CYC && (side & 2) && blockIdx.x == 0 && tid == 0) constr_dpi_update<NL>(P.sc, P.tdto, P.gpoc); // see QgTendParams
   if ((int)blockIdx.x >= 8 * per_xcd) {
     // cyclic / atmosphere: the boundary line sums for the momentum constraints (k_cyclic.h); box: the wall edges
     if (CYC) cyc_bsums_block(S, (int)blockIdx.x - 8 * per_xcd);
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_W
   if (tile >= ntiles) return;
   QG_STAMP(3, 0);
   const int i0 = (tile % gx) * TX + 1; // first global i of the tile (1-based)
-  const int trow = P.trows ? P.trow0 + (tile / gx) * P.tstride : tile / gx;
+  const int trow = trows ? trow0 + (tile / gx) * tstride : tile / gx;
   const int j0 = trow * TY + jlo; // first local row of the tile
   const int tx = tid % TX;
   const int ty0 = tid / TX; // 0..3
@@ -286,12 +290,13 @@ __global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_W
     o1[e] = v1[e] ? (gj - 1) * ldx + (tend_wrap<CYC>(gi, nxt) - 1) : 0;
   }
   double r3[N3], rp[N1], rq[N1];
+  QG_STAMP(3, 11);
 #pragma unroll
-  for (int e = 0; e < N3; ++e) r3[e] = P.pom[o3[e]];
+  for (int e = 0; e < N3; ++e) r3[e] = pom[o3[e]];
 #pragma unroll
   for (int e = 0; e < N1; ++e) {
-    rp[e] = P.po[o1[e]];
-    rq[e] = P.qo[o1[e]];
+    rp[e] = po0[o1[e]];
+    rq[e] = qo0[o1[e]];
   }
   // ---- the Del^2 / Del^4 passes of this thread (elements tid, tid + 256, ... of the halo-2 / halo-1 region): the LDS
   // read base, the position of the ONE inner neighbour the wall rule uses (N of a S-wall point, ...) and whether the
@@ -353,11 +358,11 @@ __global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_W
     QG_STAMP(3, 1 + 2 * k);
     // ---- issue the loads of layer k+1 (they fly while layer k is computed)
     if (k + 1 < NL) {
-      const double *pom = P.pom + fs * (k + 1);
-      const double *po = P.po + fs * (k + 1);
-      const double *qo = P.qo + fs * (k + 1);
+      const double *pomk = pom + fs * (k + 1);
+      const double *po = po0 + fs * (k + 1);
+      const double *qo = qo0 + fs * (k + 1);
 #pragma unroll
-      for (int e = 0; e < N3; ++e) r3[e] = pom[o3[e]];
+      for (int e = 0; e < N3; ++e) r3[e] = pomk[o3[e]];
 #pragma unroll
       for (int e = 0; e < N1; ++e) {
         rp[e] = po[o1[e]];

@@ -114,7 +114,8 @@ __device__ __forceinline__ void affine_scan(double &Cs, double &Ds, int lane) {
 // registers and spilled 100-800 B per lane under the 128-VGPR limit.
 template <int R, int PHASE, bool CYCA = false, int KW = TH_KW>
 // (second launch bound = waves per SIMD: 512-thread workgroups of 8 wavenumbers share a CU in pairs at 128 VGPRs)
-__global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_thomas(const QgThomasParams P) {
+__global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_thomas(QG_TH_ARGS, const QgThomasParams P) {
+  QG_STAMP(1, 10);
   static_assert(TH_KW % KW == 0, "a workgroup's wavenumbers lie inside one block of the pivot tables");
   static_assert(KW % 2 == 0, "the write-through stores pair the lanes of neighbouring wavenumbers");
   // pitch TH_KW + 1: the scans read / write these arrays transposed ([lane][wv]: 64 lanes at a stride of one row);
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
   // grid's x extent is a multiple of 8 then) - so that one L2 fetches each line once.
   int bxl = (int)blockIdx.x;
   if (KW == 8) {
-    const int nfull = ((int)gridDim.x - (CYCA ? 1 : 0)) / 16 * 16;
+    const int nfull = (nk + KW - 1) / KW / 16 * 16; // (the grid's x extent less CYCA's extra workgroup, from a preloaded argument)
     if (bxl < nfull) bxl = (bxl & ~15) + 2 * (bxl & 7) + ((bxl >> 3) & 1);
   }
   const int kk = tid % KW;
@@ -150,18 +151,17 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
   const int lane = tid & 63, wv = tid >> 6;
   const int k = bxl * KW + kk;
   const int kq = bxl * KW + wv; // wavenumber whose chunk maps this wave scans
-  const int m = blockIdx.y + P.layer0;
-  const int nr = P.g.jr1 - P.g.jr0 + 1; // local rows jr0..jr1  <->  r = 0..nr-1
-  const int ldw = P.g.ldw;
-  const bool kok = k < P.g.nk;
-  const double a = P.aoc;
+  // (leading scalar arguments, preloaded into SGPRs: QG_TH_ARGS in qgcm_dev.h - the row loads below and the loads of
+  //  rcb / binf are issued without waiting for the kernarg segment; aoc, ftnorm, poff and ptab are used after them)
+  const int m = blockIdx.y + layer0;
+  const int nr = jr1 - jr0 + 1; // local rows jr0..jr1  <->  r = 0..nr-1
+  const bool kok = k < nk;
   const int r0 = c * R;
   const long mk = TH_MSG * ((long)m * ldw + kq);
-  const double ft = P.ftnorm;
+  const double a = P.aoc, ft = P.ftnorm;
 
   // 32-bit element offsets from a uniform base (one scalar pointer + one VGPR per address)
-  const double *wbase_c = P.wrk + P.g.wstride * m + (long)(P.g.jr0 - 1) * ldw + bxl * KW;
-  double *wbase = const_cast<double *>(wbase_c);
+  double *wbase = wrk + wstride * m + (long)(jr0 - 1) * ldw + bxl * KW;
   const unsigned off0 = (unsigned)(r0 * ldw + kk);
   // rows past the end of the slab: PHASE 0 (whole column, zero inflow at both ends) pads them with w = 0, b = 0 - the
   // forward values and the backward values of such rows are exactly 0, nothing of them is stored, and the sweeps need
@@ -169,6 +169,7 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
   // identity map: they keep the predicate.
   constexpr bool PRED = (PHASE != 0);
   double w[R], b[R];
+  QG_STAMP(1, 11);
 #pragma unroll
   for (int t = 0; t < R; ++t) {
     int r = r0 + t;
@@ -178,19 +179,19 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
   // pivots of this chunk (src/ocisubs.F:472-477, tabulated by the host): rows below rcb from the block's table,
   // the stationary value after that
   {
-    const int tb = m * P.nblk + (bxl * KW) / TH_KW; // the tables are per block of TH_KW wavenumbers
-    const int rcb = P.rcb[tb];
-    const double binf = kok ? P.binf[(long)m * ldw + k] : 0.0;
+    const int tb = m * nblk + (bxl * KW) / TH_KW; // the tables are per block of TH_KW wavenumbers
+    const int rcb_b = rcb[tb];
+    const double binf_k = kok ? binf[(long)m * ldw + k] : 0.0;
 #pragma unroll
-    for (int t = 0; t < R; ++t) b[t] = binf;
-    if (r0 < rcb) {
+    for (int t = 0; t < R; ++t) b[t] = binf_k;
+    if (r0 < rcb_b) {
       const double *tab = P.ptab + (long)P.poff[tb] * TH_KW + (bxl * KW) % TH_KW + kk;
 #pragma unroll
       for (int t = 0; t < R; ++t) {
         const int r = r0 + t;
-        const int rc = r < rcb ? r : rcb - 1;
+        const int rc = r < rcb_b ? r : rcb_b - 1;
         const double v = tab[rc * TH_KW];
-        b[t] = (r < rcb && kok) ? v : binf;
+        b[t] = (r < rcb_b && kok) ? v : binf_k;
       }
     }
     if (r0 + R > nr) {
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
       // neighbouring wavenumbers swap one value per pair of rows, the even lane then stores row t for both, the odd
       // lane row t + 1 (columns k - 1, k).  A column past nk is a padding column of the row (ldw = nk rounded up).
       const bool odd = (kk & 1) != 0;
-      const bool pok = odd ? (k - 1 < P.g.nk) : kok; // the pair's first column exists
+      const bool pok = odd ? (k - 1 < nk) : kok; // the pair's first column exists
       double *cbase = wbase + (odd ? off0 - 1 : off0);
 #pragma unroll
       for (int t = 0; t < R; t += 2) {
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
   double tot = sC[lane][wv];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
-  if (lane != 0 || kq >= P.g.nk) return;
+  if (lane != 0 || kq >= nk) return;
   double *cst = P.slabDE + 4 * ((long)m * ldw + kq); // D, E, SP, SQ of this slab
   if (PHASE == 0) {
     P.ksum[(long)m * ldw + kq] = ft * tot;

@@ -19,7 +19,7 @@
 // In-kernel phase stamps (development builds only, -DQG_STAMPS: scratch/stamps.py): thread 0 of every workgroup
 // records the constant 100 MHz wall clock at phase boundaries; never compiled into the product library.
 #ifdef QG_STAMPS
-#define QG_NSTAMP 10
+#define QG_NSTAMP 12 // 0..9: phases; 10: kernel entry, before any kernarg use; 11: just before the first vector load
 #define QG_STAMP_BLOCKS 4096
 __device__ long long qg_stamps[4][QG_STAMP_BLOCKS][QG_NSTAMP];
 #define QG_STAMP(kern, i)                                                                   \
@@ -152,6 +152,22 @@ struct QgDstParams {
   // (k_constr_box's body, k_misc.h) instead of a launch of its own; nullptr otherwise
   const struct QgConstrParams *boxq;
 };
+
+// Leading scalar kernel arguments of the wave-per-row-pair kernels (k_dst64.h) and of k_thomas: copies of the struct
+// fields a wave needs for its early exit and the addresses of its first loads, placed first so that the compiler can
+// preload them into SGPRs at wave launch (Makefile: -amdgpu-kernarg-preload-count; by-value structs are never
+// preloaded).  At most 14 SGPRs (16 user SGPRs less the kernarg pointer), 8-byte values first (no padding).  The
+// launch sites pass QG_ROW_VALS / QG_TH_VALS / QG_TEND_VALS of the very struct that follows, so a scalar cannot disagree
+// with its field.
+#define QG_ROW_ARGS double *wrk, const double2 *twid, const double *sintab, long wstride, int ldw, int jr0, int jr1, int layer0
+#define QG_ROW_VALS(D) (D).wrk, (D).twid, (D).sintab, (D).g.wstride, (D).g.ldw, (D).g.jr0, (D).g.jr1, (D).layer0
+#define QG_TH_ARGS double *wrk, const double *binf, const int *rcb, long wstride, int ldw, int jr0, int jr1, int nk, int layer0, int nblk
+#define QG_TH_VALS(T) (T).wrk, (T).binf, (T).rcb, (T).g.wstride, (T).g.ldw, (T).g.jr0, (T).g.jr1, (T).g.nk, (T).layer0, (T).nblk
+// k_tend: the integers of the tile mapping (tend_tiling, the row window), the side-job flags of workgroup 0 (bit 0:
+// QgOmlFinal.on, bit 1: upd_dpi) and the first field pointer; po / qo follow from the struct while the offsets are formed
+#define QG_TEND_ARGS const double *pom, int nx, int ny, int nxt, int ldx, int nyg, int joff, int jlo, int jhi, int trows, int trow0, int tstride, int side
+#define QG_TEND_VALS(T, F) (T).pom, (T).g.nx, (T).g.ny, (T).g.nxt, (T).g.ldx, (T).g.nyg, (T).g.joff, (T).g.jlo, (T).g.jhi, (T).trows, (T).trow0, (T).tstride, \
+                           ((F).on ? 1 : 0) | ((T).upd_dpi ? 2 : 0)
 
 struct QgThomasParams {
   QgGeom g;

@@ -1272,18 +1272,18 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   dim3 grid(8 * ((ntiles + 7) / 8) + nextra); // 1-D: the kernel maps blockIdx -> tile per XCD band, then edge / line-sum work
   KTimer t(c, KN_TEND);
 #define QG_TEND(NLV)                                                                                       \
-  if (g.cyc && wtq) hipLaunchKernelGGL((k_tend<NLV, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F);    \
-  else if (g.cyc) hipLaunchKernelGGL((k_tend<NLV, true, false>), grid, dim3(TEND_NT), 0, c->stream, P, S, F);     \
-  else if (wtq) hipLaunchKernelGGL((k_tend<NLV, false, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F);       \
-  else hipLaunchKernelGGL((k_tend<NLV, false, false>), grid, dim3(TEND_NT), 0, c->stream, P, S, F)
+  if (g.cyc && wtq) hipLaunchKernelGGL((k_tend<NLV, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
+  else if (g.cyc) hipLaunchKernelGGL((k_tend<NLV, true, false>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
+  else if (wtq) hipLaunchKernelGGL((k_tend<NLV, false, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
+  else hipLaunchKernelGGL((k_tend<NLV, false, false>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F)
   if (c->avg_now && g.cyc) { // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does the rest)
-    if (wtq) hipLaunchKernelGGL((k_tend<3, true, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F);
-    else hipLaunchKernelGGL((k_tend<3, true, false, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F);
+    if (wtq) hipLaunchKernelGGL((k_tend<3, true, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F);
+    else hipLaunchKernelGGL((k_tend<3, true, false, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F);
   } else if (c->avg_now) { // the step before a leapfrog averaging stores the averaged qo itself (one_step)
     switch (g.nl) {
-      case 2: hipLaunchKernelGGL((k_tend<2, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F); break;
-      case 3: hipLaunchKernelGGL((k_tend<3, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F); break;
-      default: hipLaunchKernelGGL((k_tend<4, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, P, S, F); break;
+      case 2: hipLaunchKernelGGL((k_tend<2, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); break;
+      case 3: hipLaunchKernelGGL((k_tend<3, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); break;
+      default: hipLaunchKernelGGL((k_tend<4, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); break;
     }
   } else {
     QG_SWITCH_NL(g.nl, QG_TEND, "k_tend");
@@ -1362,9 +1362,9 @@ static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, i
   }
   // wave-per-row-pair fast path when nxto = 64*M with an in-register M-point DFT available
   if (pl.m64 == 15) {
-    hipLaunchKernelGGL((k_dst64<15, false>), grid64, dim3(D64_NT), 0, st, P);
+    hipLaunchKernelGGL((k_dst64<15, false>), grid64, dim3(D64_NT), 0, st, QG_ROW_VALS(P), P);
   } else if (pl.m64 == 3) {
-    hipLaunchKernelGGL((k_dst64<3, false>), grid64, dim3(D64_NT), 0, st, P);
+    hipLaunchKernelGGL((k_dst64<3, false>), grid64, dim3(D64_NT), 0, st, QG_ROW_VALS(P), P);
   } else if (c->fftN >= DST_BIG_N) hipLaunchKernelGGL((k_dst_box<false, DST_NT_BIG>), grid, dim3(DST_NT_BIG), c->dst_lds, st, P);
   else hipLaunchKernelGGL((k_dst_box<false>), grid, dim3(DST_NT), c->dst_lds, st, P);
   HIPCHECK(hipGetLastError());
@@ -1418,12 +1418,12 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
     dim3 gridk((g.nk + KWV - 1) / KWV + (cyca ? 1 : 0), nlayers);                                                        \
     switch (phase) {                                                                                                     \
       case 0:                                                                                                            \
-        if (cyca) hipLaunchKernelGGL((k_thomas<RV, 0, true, KWV>), gridk, dim3(KWV * TH_NC), 0, st, P);                  \
-        else hipLaunchKernelGGL((k_thomas<RV, 0, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, P);                      \
+        if (cyca) hipLaunchKernelGGL((k_thomas<RV, 0, true, KWV>), gridk, dim3(KWV * TH_NC), 0, st, QG_TH_VALS(P), P); \
+        else hipLaunchKernelGGL((k_thomas<RV, 0, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, QG_TH_VALS(P), P); \
         break;                                                                                                           \
-      case 1: hipLaunchKernelGGL((k_thomas<RV, 1, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, P); break;              \
-      case 4: hipLaunchKernelGGL((k_thomas<RV, 4, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, P); break;              \
-      default: hipLaunchKernelGGL((k_thomas<RV, 5, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, P); break;             \
+      case 1: hipLaunchKernelGGL((k_thomas<RV, 1, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, QG_TH_VALS(P), P); break; \
+      case 4: hipLaunchKernelGGL((k_thomas<RV, 4, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, QG_TH_VALS(P), P); break; \
+      default: hipLaunchKernelGGL((k_thomas<RV, 5, false, KWV>), gridk, dim3(KWV * TH_NC), 0, st, QG_TH_VALS(P), P); break; \
     }                                                                                                                    \
   }
   // 8 .. 16 rows per thread: 512-thread workgroups of 8 wavenumbers, two per CU (128 VGPRs), the pair that shares the
@@ -1609,12 +1609,12 @@ static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nu
   dim3 grid((nrows + 1) / 2);
   KTimer t(c, KN_DSTI);
 #define QG_DU(MV, NLV)                                                                                                  \
-  if (c->avg_now) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
-  else if ((msg_lo || msg_hi) && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
-  else if (msg_lo || msg_hi) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C); \
-  else if (fuse_bdy && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, D, P, B, C); \
-  else if (fuse_bdy) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C);  \
-  else hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, false, false, false>), grid, dim3(64 * NLV), 0, c->stream, D, P, B, C)
+  if (c->avg_now) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
+  else if ((msg_lo || msg_hi) && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
+  else if (msg_lo || msg_hi) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, false>), grid, dim3(64 * NLV), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
+  else if (fuse_bdy && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
+  else if (fuse_bdy) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, false>), grid, dim3(64 * NLV), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
+  else hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, false, false, false>), grid, dim3(64 * NLV), 0, c->stream, QG_ROW_VALS(D), P, B, C)
 #define QG_DU_NL(MV)                 \
   switch (g.nl) {                    \
     case 2: QG_DU(MV, 2); break;     \
