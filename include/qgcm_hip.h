@@ -93,9 +93,33 @@ const char *qgcm_hip_last_error(void);
 int qgcm_hip_abi_version(void);
 
 /* yporel(nypo), bd2oc(nxto) [reference/FFTPACK ordering, q-gcm.F:933-954],
- * ddynoc(nxpo,nypo).  Builds the device-side Thomas tables. */
+ * ddynoc(nxpo,nypo).  Builds the device-side Thomas tables.
+ *
+ * Column height.  The whole-column tridiagonal kernel holds a column of at most QGCM_HIP_THOMAS_MAX_ROWS = 2048 interior
+ * rows (nypo - 2).  A WHOLE-DOMAIN OCEAN handle, box or zonally cyclic, with a taller column (NAtl 2 km: 2401 rows,
+ * NAtl 1 km: 4801) cuts it into balanced segments - qgcm_hip_thomas_segments gives the plan - and solves it in two
+ * launches per inversion instead of one.  Every entry point that wants a whole-domain handle accepts such a handle;
+ * run on one so far (README): qgcm_hip_steps and its graphs, the three stand-alone calls, helmholtz, oml, valids, prsamp;
+ * accepted but not yet run on one: qgcm_hip_coupled_steps, xforc, the monitors, time averages, dumps and covariances.
+ * A y-slab of more than 2048 rows and an atmosphere handle of more than 2048 rows are refused by this call.
+ * QGCM_HIP_THOMAS_SEG_ROWS=<n> (environment, read by this call): the longest segment, 2 * QGCM_HIP_THOMAS_SEG_MIN - 1
+ * <= n; columns of ANY height longer than n are then cut (n > 2048 counts as 2048) - tests force segments on small
+ * basins with it.  Anything but a positive integer is refused.  Unset, columns of up to 2048 rows take the single
+ * launch. */
 int qgcm_hip_set_grid(qgcm_hip_handle h, const double *yporel, const double *bd2oc,
                       const double *ddynoc);
+#define QGCM_HIP_THOMAS_MAX_ROWS 2048 /* rows of one segment = of a column solved by the single-segment kernel */
+#define QGCM_HIP_THOMAS_SEG_MIN 4     /* no segment is shorter (the minimum of a y-slab, qgcm_hip_create) */
+#define QGCM_HIP_THOMAS_MAX_SEG 64    /* segments per column */
+#define QGCM_HIP_THOMAS_SEG_DEFAULT 1024 /* longest segment of a column of more than 2048 rows when no maximum is given */
+/* The segment plan of a column of nrows interior rows; pure host code, no handle and no device needed.
+ * max_rows > 0: no segment is longer than min(max_rows, 2048); max_rows <= 0: one segment up to 2048 rows, segments
+ * of at most QGCM_HIP_THOMAS_SEG_DEFAULT = 1024 rows beyond.  *nseg = S = the fewest segments that respect the maximum; segment s covers the interior rows
+ * first[s] .. first[s] + count[s] - 1 (0-based, in order, each row once); the lengths differ by at most one (the longer
+ * ones first).  first / count (QGCM_HIP_THOMAS_MAX_SEG ints each) may be NULL.  Fails (non-zero) for nrows < 1, for a
+ * maximum below 2 * QGCM_HIP_THOMAS_SEG_MIN - 1 (it could leave a segment shorter than the minimum) and for more than
+ * QGCM_HIP_THOMAS_MAX_SEG segments. */
+int qgcm_hip_thomas_segments(int nrows, int max_rows, int *nseg, int *first, int *count);
 /* The part of set_grid that does not need bd2oc: yporel and ddynoc only.  The main program calls ocqbdy / atqzbd on
  * host arrays (src/q-gcm.F:724-725, 743-744) before it computes bd2oc (:932-972); qgcm_hip_ocqbdy_host needs no more
  * than this.  The stepping entry points still require qgcm_hip_set_grid. */
@@ -192,7 +216,9 @@ int qgcm_hip_coupled_steps(qgcm_hip_handle oc, qgcm_hip_handle atm, int nt0, int
 int qgcm_hip_set_cu_range(qgcm_hip_handle h, int first, int count);
 
 /* Helmholtz solve for homsol: wrk(nxpo,nypo) in/out, boc(nxto)
- * (replaces hsbxoc / hscyoc, src/ocisubs.F:415-618). Synchronous. */
+ * (replaces hsbxoc / hscyoc, src/ocisubs.F:415-618). Synchronous.  Any diagonal, not only the modal ones: a handle
+ * whose column is cut into segments (see qgcm_hip_set_grid) builds the segments' response tables for this boc on the
+ * call and keeps them until another boc arrives. */
 int qgcm_hip_helmholtz(qgcm_hip_handle h, double *wrk, const double *boc);
 
 /* ---- y-slab building blocks (multi-GPU; one handle per slab) -------------

@@ -126,6 +126,21 @@ struct qgcm_hip_ctx {
   const double *oml_gath = nullptr;        // y-slabs: the gathered sums of the mixed layer's stage 10 (3, nranks)
   double *bpart_out = nullptr;             // where k_tend's extra workgroups put the boundary line sums (bpart, or the tail of the step message)
   QgThomasTab tt, tt_tmp;                  // Thomas pivot tables of the modal solves / of the last qgcm_hip_helmholtz
+  // whole-domain oceans whose column is cut into segments (k_thomas.h: k_thomas_seg, k_thomas_corr_seg): the plan, and
+  // per set of diagonals - [0] the modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot
+  // tables (tt / tt_tmp, segment-major), response tables and constants
+  struct {
+    int S = 1, R = 0, maxlen = 0;           // segments (1: the single-segment kernel), rows per chunk, longest segment
+    int seg_rows = 0;                       // QGCM_HIP_THOMAS_SEG_ROWS as set_grid read it (0: unset)
+    std::vector<int> first, count;          // interior rows [first, first + count) of each segment
+    double *msg = nullptr;                  // (Cf, Cb, S0) of every segment, segment-major: the gathered slab messages' layout
+    struct Set {
+      QgThomasSegRec *recs = nullptr;
+      double *ptab = nullptr, *qtab = nullptr, *cst = nullptr; // responses; (D, E, SP, SQ) segment-major (cgath's layout)
+      int *meta = nullptr;                  // np, nq, poff, qoff: (nblk, layers, S) each
+      std::vector<double> boc;              // [1]: the diagonal the tables were built for
+    } set[2];
+  } seg;
   // y-slabs: the slab's responses to unit inflows from below / above, tabulated as far as they reach (k_thomas_corr)
   struct {
     double *ptab = nullptr, *qtab = nullptr;
@@ -522,6 +537,14 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   if (c->corr.ptab) hipFree(c->corr.ptab);
   if (c->corr.qtab) hipFree(c->corr.qtab);
   if (c->corr.meta) hipFree(c->corr.meta);
+  if (c->seg.msg) hipFree(c->seg.msg);
+  for (auto &ss : c->seg.set) {
+    if (ss.recs) hipFree(ss.recs);
+    if (ss.ptab) hipFree(ss.ptab);
+    if (ss.qtab) hipFree(ss.qtab);
+    if (ss.cst) hipFree(ss.cst);
+    if (ss.meta) hipFree(ss.meta);
+  }
   for (QgThomasTab *t : {&c->tt, &c->tt_tmp}) {
     if (t->binf) hipFree(t->binf);
     if (t->ptab) hipFree(t->ptab);
@@ -544,6 +567,35 @@ static int thomas_rows_per_chunk(int nrows) {
   QG_TH_ROWS(QG_TH_FITS)
 #undef QG_TH_FITS
   return -1;
+}
+
+// The segment plan of a column of nrows interior rows (pure host code): S = ceil(nrows / max) balanced segments, the
+// first nrows % S one row longer.  max_rows <= 0: no maximum given - one segment up to QGCM_HIP_THOMAS_MAX_ROWS rows (the
+// single-segment kernel), segments of at most QGCM_HIP_THOMAS_SEG_DEFAULT rows beyond (1024: 16 rows per thread, the
+// 128-VGPR form - measured on NAtl 1 km against 2048 and 640).  A maximum below 2 * MIN - 1 could leave a
+// segment shorter than the slab minimum (nrows = max + 1 gives two halves): refused.
+extern "C" int qgcm_hip_thomas_segments(int nrows, int max_rows, int *nseg, int *first, int *count) {
+  if (!nseg) QG_FAIL("qgcm_hip_thomas_segments: null argument");
+  if (nrows < 1) QG_FAIL("qgcm_hip_thomas_segments: nrows = %d", nrows);
+  int cap = QGCM_HIP_THOMAS_SEG_DEFAULT;
+  if (max_rows > 0) {
+    if (max_rows < 2 * QGCM_HIP_THOMAS_SEG_MIN - 1)
+      QG_FAIL("qgcm_hip_thomas_segments: a maximum of %d rows per segment is below %d (segments of at least %d rows)", max_rows,
+              2 * QGCM_HIP_THOMAS_SEG_MIN - 1, QGCM_HIP_THOMAS_SEG_MIN);
+    cap = max_rows < QGCM_HIP_THOMAS_MAX_ROWS ? max_rows : QGCM_HIP_THOMAS_MAX_ROWS;
+  }
+  const int S = (max_rows <= 0 && nrows <= QGCM_HIP_THOMAS_MAX_ROWS) ? 1 : (nrows + cap - 1) / cap;
+  if (S > QGCM_HIP_THOMAS_MAX_SEG)
+    QG_FAIL("qgcm_hip_thomas_segments: %d rows in segments of at most %d rows are more than %d segments", nrows, cap, QGCM_HIP_THOMAS_MAX_SEG);
+  *nseg = S;
+  const int base = nrows / S, extra = nrows % S;
+  for (int s = 0, at = 0; s < S; ++s) {
+    const int n = base + (s < extra ? 1 : 0);
+    if (first) first[s] = at;
+    if (count) count[s] = n;
+    at += n;
+  }
+  return 0;
 }
 
 // per-step message of one slab: the summaries of the two y sweeps; a cyclic ocean appends its boundary line sums
@@ -626,6 +678,9 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
                          const double *gath, double *send, int rank, int nranks, int layer0, hipStream_t st,
                          bool cyc_part_a = false);
 
+static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, int phase, bool cyca, int nlayers, hipStream_t st);
+static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int nlayers, hipStream_t st);
+
 static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, double *wrk, const QgThomasTab &tab, int nlayers, int layer0) {
   const QgGeom &g = c->g;
   memset(&P, 0, sizeof(P));
@@ -686,6 +741,80 @@ static int build_slab_responses(qgcm_hip_ctx *c) {
   return 0;
 }
 
+// Set-up of the segmented whole-column solve for one set of diagonals (which = 0: the modal solves, boc = nlo diagonals;
+// 1: qgcm_hip_helmholtz's, one diagonal): every segment's pivots - the recurrence depends on its first global row - go
+// segment-major into tt / tt_tmp; PHASE 4 / 5 run once per segment (they leave the unit responses in the segment's own
+// rows of the work array, which is overwritten), then the responses are tabulated as far as they reach, as
+// build_slab_responses does for a slab: a segment's neighbours are the segments next to it.
+static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vector<double>> &boc) {
+  const QgGeom &g = c->g;
+  auto &sg = c->seg;
+  auto &ss = sg.set[which];
+  QgThomasTab &tab = which ? c->tt_tmp : c->tt;
+  const int S = sg.S, nlt = (int)boc.size(), nblk = (g.nk + TH_KW - 1) / TH_KW, nmt = nblk * nlt;
+  std::vector<QgThomasSegRec> recs(S);
+  {
+    ThomasTabHost T;
+    for (int s = 0; s < S; ++s) {
+      QgGeom gs = g;
+      gs.jr0 = g.jr0 + sg.first[s];
+      gs.jr1 = gs.jr0 + sg.count[s] - 1;
+      recs[s] = QgThomasSegRec{gs.jr0, gs.jr1, s * nmt, 0, (long)s * nlt * g.ldw, (long)s * TH_MSG * nlt * g.ldw, (long)s * TH_CST * g.nl * g.ldw};
+      for (int m = 0; m < nlt; ++m) build_pivots(gs, c->prm.aoc, boc[m].data(), T);
+    }
+    if (upload_pivots(c, tab, T)) return 1; // (waits for the stream: nothing reads the old tables any more)
+  }
+  if (!sg.msg && dalloc(&sg.msg, (size_t)TH_MSG * g.nl * g.ldw * S)) return 1;
+  if (!ss.cst && dalloc(&ss.cst, (size_t)TH_CST * g.nl * g.ldw * S)) return 1;
+  if (!ss.recs) HIPCHECK(hipMalloc((void **)&ss.recs, sizeof(QgThomasSegRec) * S));
+  if (!ss.meta) HIPCHECK(hipMalloc((void **)&ss.meta, sizeof(int) * 4 * S * nmt));
+  HIPCHECK(hipMemcpy(ss.recs, recs.data(), sizeof(QgThomasSegRec) * S, hipMemcpyHostToDevice));
+  std::vector<int> meta((size_t)4 * S * nmt, 0);
+  HIPCHECK(hipMemcpy(ss.meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice)); // (ends without a neighbour: reach 0)
+  QgThomasParams P0;
+  fill_thomas_params(c, P0, c->wrk, tab, nlt, 0);
+  auto seg_params = [&](int s) {
+    QgThomasParams P = P0;
+    P.g.jr0 = recs[s].jr0; P.g.jr1 = recs[s].jr1;
+    P.binf += recs[s].b0; P.rcb += recs[s].tb0; P.poff += recs[s].tb0;
+    P.slabDE = ss.cst + recs[s].cst0;
+    return P;
+  };
+  const double tol = 1.0e-19 * P0.ftnorm; // (build_slab_responses)
+  for (int side = 0; side < 2; ++side) { // 0: inflow from below (PHASE 4, Pv), 1: from above (PHASE 5, Qv)
+    double *&rtab = side ? ss.qtab : ss.ptab;
+    if (rtab) HIPCHECK(hipFree(rtab));
+    rtab = nullptr;
+    int *d_reach = ss.meta + side * S * nmt, *d_off = ss.meta + (2 + side) * S * nmt;
+    int *h_reach = meta.data() + side * S * nmt, *h_off = meta.data() + (2 + side) * S * nmt;
+    for (int s = 0; s < S; ++s) {
+      const QgThomasParams P = seg_params(s);
+      if (launch_thomas_rows(c, P, sg.R, 4 + side, false, nlt, c->stream)) return 1;
+      if (side ? s == S - 1 : s == 0) continue; // the column's end: nothing ever enters there
+      hipLaunchKernelGGL(k_thomas_reach, dim3(nblk, nlt), dim3(256), 0, c->stream, P, side, tol, d_reach + s * nmt);
+      HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipMemcpyAsync(h_reach, d_reach, sizeof(int) * S * nmt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    size_t off = 0;
+    for (int i = 0; i < S * nmt; ++i) {
+      h_off[i] = (int)off;
+      off += h_reach[i];
+    }
+    if ((double)off * TH_KW >= 2147483647.0) QG_FAIL("qgcm_hip_set_grid: the segments' response tables exceed 32-bit offsets");
+    HIPCHECK(hipMalloc((void **)&rtab, sizeof(double) * TH_KW * (off ? off : 1)));
+    HIPCHECK(hipMemcpyAsync(d_off, h_off, sizeof(int) * S * nmt, hipMemcpyHostToDevice, c->stream));
+    for (int s = side ? 0 : 1; s < (side ? S - 1 : S); ++s) {
+      const QgThomasParams P = seg_params(s);
+      hipLaunchKernelGGL(k_thomas_pack, dim3(nblk, nlt), dim3(256), 0, c->stream, P, side, (const int *)(d_reach + s * nmt),
+                         (const int *)(d_off + s * nmt), rtab);
+      HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
 extern "C" int qgcm_hip_set_geometry(qgcm_hip_handle c, const double *yporel, const double *ddynoc) {
   if (!c || !yporel) QG_FAIL("qgcm_hip_set_geometry: null argument");
   const QgGeom &g = c->g;
@@ -704,15 +833,55 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   if (qgcm_hip_set_geometry(c, yporel, ddynoc)) return 1;
   c->bd2oc.assign(bd2oc, bd2oc + g.nxt);
   // Thomas diagonal + chunk-entry pivots per mode: boc = bd2oc - rdm2oc(m)   (src/ocisubs.F:148-150)
-  c->thR = thomas_rows_per_chunk(g.jr1 - g.jr0 + 1);
-  if (c->thR < 0) QG_FAIL("qgcm_hip_set_grid: %d rows per slab exceed the single-segment Thomas kernel (<= 2048)", g.jr1 - g.jr0 + 1);
+  // a whole-domain ocean cuts a column of more than 2048 rows (or, with QGCM_HIP_THOMAS_SEG_ROWS set, any column longer
+  // than that) into segments; y-slabs and the atmosphere keep the single-segment kernel
   {
-    ThomasTabHost T;
-    std::vector<double> boc(g.nk);
-    for (int m = 0; m < g.nl; ++m) {
-      for (int k = 0; k < g.nk; ++k) boc[k] = bd2oc[k] - c->prm.rdm2oc[m];
-      build_pivots(g, c->prm.aoc, boc.data(), T);
+    const int nrows = g.jr1 - g.jr0 + 1;
+    auto &sg = c->seg;
+    int S = 1;
+    if (c->whole && !g.atm) {
+      // QGCM_HIP_THOMAS_SEG_ROWS: the longest segment; read here, at every set_grid.  Anything but a positive integer is
+      // refused: a typing error must not silently mean "unset"
+      sg.seg_rows = 0;
+      if (const char *sr = getenv("QGCM_HIP_THOMAS_SEG_ROWS")) {
+        char *end = nullptr;
+        const long v = strtol(sr, &end, 10);
+        if (end == sr || *end != '\0' || v < 1 || v > 1000000) QG_FAIL("qgcm_hip_set_grid: QGCM_HIP_THOMAS_SEG_ROWS=\"%s\" is not a positive number of rows", sr);
+        sg.seg_rows = (int)v;
+      }
+      int first[QGCM_HIP_THOMAS_MAX_SEG], count[QGCM_HIP_THOMAS_MAX_SEG];
+      if (qgcm_hip_thomas_segments(nrows, sg.seg_rows, &S, first, count)) return 1;
+      sg.first.assign(first, first + S);
+      sg.count.assign(count, count + S);
+      sg.maxlen = count[0];
     }
+    if (S != sg.S) { // (a second set_grid under another plan: the per-segment buffers are sized by S)
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      if (sg.msg) hipFree(sg.msg);
+      sg.msg = nullptr;
+      for (auto &ss : sg.set) {
+        void **ps[] = {(void **)&ss.recs, (void **)&ss.ptab, (void **)&ss.qtab, (void **)&ss.cst, (void **)&ss.meta};
+        for (void **q : ps) {
+          if (*q) hipFree(*q);
+          *q = nullptr;
+        }
+      }
+    }
+    sg.set[1].boc.clear();
+    sg.S = S;
+    c->thR = thomas_rows_per_chunk(S > 1 ? sg.maxlen : nrows);
+    sg.R = c->thR;
+    if (c->thR < 0) {
+      if (g.atm) QG_FAIL("qgcm_hip_set_grid: %d rows of an atmosphere handle exceed the single-segment Thomas kernel (<= 2048); only whole-domain ocean handles solve taller columns", nrows);
+      QG_FAIL("qgcm_hip_set_grid: %d rows per slab exceed the single-segment Thomas kernel (<= 2048); only whole-domain ocean handles solve taller columns", nrows);
+    }
+  }
+  std::vector<std::vector<double>> bocs(g.nl, std::vector<double>(g.nk));
+  for (int m = 0; m < g.nl; ++m)
+    for (int k = 0; k < g.nk; ++k) bocs[m][k] = bd2oc[k] - c->prm.rdm2oc[m];
+  if (c->seg.S == 1) {
+    ThomasTabHost T;
+    for (int m = 0; m < g.nl; ++m) build_pivots(g, c->prm.aoc, bocs[m].data(), T);
     if (upload_pivots(c, c->tt, T)) return 1;
   }
   // FFT tables: complex length N = nxto (box DST-I of length nxto-1)
@@ -770,7 +939,7 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   }
   c->grid_set = true;
   // slab summary constants (gain, backward image and column sums of the unit responses), once
-  if (build_slab_responses(c)) return 1;
+  if (c->seg.S > 1 ? build_segments(c, 0, bocs) : build_slab_responses(c)) return 1;
   {
     // weights of the spectral area integral (k_thomas.h): sum_{i=1}^{n-1} 2 sin(k i pi/n) = 2 cot(k pi/2n), k odd
     std::vector<double> wc((size_t)g.ldw, 0.0);
@@ -1193,7 +1362,9 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
       // rows (SOcn 5 km; it reads ksum and ybnd, not wrk) - the riding parts exist for nlo <= 4.  (The wave-per-row-pair
       // kernels of k_rfft64.h have no such extra workgroup: they are fused with the unpack unless that is switched off,
       // and then keep the stand-alone constraint launch.)
-      if (in_step && !slab && g.nl <= 4 && (pl.inv == INV_RFFT64_UNPACK || pl.rows != ROWS_RFFT64)) pl.constr = CONSTR_AB;
+      // (a column cut into segments launches no k_thomas<R, 0, true>, whose extra workgroup part A rides in: the
+      //  stand-alone k_constr_cyc there)
+      if (in_step && !slab && g.nl <= 4 && c->seg.S == 1 && (pl.inv == INV_RFFT64_UNPACK || pl.rows != ROWS_RFFT64)) pl.constr = CONSTR_AB;
     } else if (pl.inv == INV_DST64_UNPACK) {
       // (y-slabs with the mixed layer on: xon(1) is only complete after the all-gather of stage 2 - no riding solve)
       if (in_step && !(slab && c->oml.on)) pl.constr = CONSTR_INV_WAVE;
@@ -1382,6 +1553,11 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   QgThomasParams P;
   fill_thomas_params(c, P, wrk, tab, nlayers, layer0);
   P.gath = gath; P.send = send; P.rank = rank; P.nranks = nranks;
+  if (c->seg.S > 1) {
+    if (phase != 0) QG_FAIL("qgcm_hip_thomas_phase: this handle solves its column in %d segments; the slab phases belong to y-slabs", c->seg.S);
+    if (cyc_part_a) QG_FAIL("k_thomas: part A of the constraint algebra does not ride in the segmented solve");
+    return launch_thomas_seg(c, P, &tab == &c->tt ? 0 : 1, nlayers, st);
+  }
   if (phase == 2) {
     if (g.cyc) P.ybnd = c->ybnd;
     c->slab_gath = gath; // (the cyclic constraint algebra reads the boundary line sums at the end of the step messages)
@@ -1412,6 +1588,12 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   const bool cyca = (phase == 0 && g.cyc);
   if (cyc_part_a && (phase != 0 || !c->d_cycq || g.nl > 4)) QG_FAIL("k_thomas: part A of the constraint algebra needs the homogeneous solutions and nlo <= 4");
   if (cyca) P.cycq = cyc_part_a ? c->d_cycq : nullptr; // (its extra workgroup is added to the grid below)
+  return launch_thomas_rows(c, P, c->thR, phase, cyca, nlayers, st);
+}
+
+// the k_thomas instantiation of R rows per thread for the rows P.g.jr0 .. jr1
+static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, int phase, bool cyca, int nlayers, hipStream_t st) {
+  const QgGeom &g = c->g;
   KTimer t(c, KN_THOMAS, st);
 #define QG_TH(RV, KWV)                                                                                                  \
   {                                                                                                                      \
@@ -1429,7 +1611,7 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   // 8 .. 16 rows per thread: 512-thread workgroups of 8 wavenumbers, two per CU (128 VGPRs), the pair that shares the
   // 128-byte lines of a 16-wavenumber block on ONE XCD (k_thomas.h; r3: NAtl 5 km 10.6 -> 9.9 us against 1024-thread
   // workgroups); long columns (>= 20 rows per thread): 512 threads, 256 VGPRs
-  switch (c->thR) {
+  switch (R) {
     // (short columns too: 1024-thread workgroups of 16 wavenumbers measured slower everywhere - atmosphere 22.1 -> 21.3 us
     //  per step, 27.9 -> 26.3 on the two XCDs of a coupled run: profiles/r4_coupled_cu_masks.log)
 #define QG_TH_CASE(RV) case RV: QG_TH(RV, 8); break;
@@ -1439,6 +1621,47 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   }
 #undef QG_TH
   HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The whole column of a handle whose plan has S > 1 segments, two launches with nothing of the host in between:
+// k_thomas_seg (PHASE 1 of every segment, summaries into seg.msg) and k_thomas_corr_seg (inflows composed from seg.msg
+// and the set-up constants, responses added, ksum / ybnd published).  P: launch_thomas's; which: the set of diagonals
+static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int nlayers, hipStream_t st) {
+  const QgGeom &g = c->g;
+  const auto &sg = c->seg;
+  const auto &ss = sg.set[which];
+  const int nlt = which ? 1 : g.nl, S = sg.S;
+  if (!ss.recs || !ss.meta || !ss.ptab || !ss.qtab) QG_FAIL("k_thomas_seg: the segments' tables have not been built for these diagonals");
+  if (nlayers > nlt) QG_FAIL("k_thomas_seg: %d layers asked of tables of %d", nlayers, nlt);
+  P.send = sg.msg; P.gath = sg.msg; P.gath_stride = (long)TH_MSG * nlt * g.ldw;
+  P.slabDE = ss.cst; P.cgath = ss.cst;
+  P.rank = 0; P.nranks = S;
+  c->slab_gath = nullptr; // whole-column solve: the constraint algebra reads bpart
+  if (g.cyc && nlayers == g.nl) P.ybnd = c->ybnd;
+  {
+    KTimer t(c, KN_THOMAS, st);
+    dim3 gridk((g.nk + 7) / 8, nlayers, S);
+    switch (sg.R) {
+#define QG_TH_CASE(RV) case RV: hipLaunchKernelGGL((k_thomas_seg<RV, 1, 8>), gridk, dim3(8 * TH_NC), 0, st, P.wrk, (const QgThomasSegRec *)ss.recs, g.wstride, g.ldw, g.nk, P.layer0, P.nblk, P); break;
+      QG_TH_ROWS(QG_TH_CASE)
+#undef QG_TH_CASE
+      default: QG_FAIL("k_thomas_seg: no instantiation for %d rows per thread", sg.R);
+    }
+    HIPCHECK(hipGetLastError());
+  }
+  {
+    const int nm = P.nblk * nlt * S;
+    QgThomasCorr T;
+    T.ptab = ss.ptab; T.qtab = ss.qtab;
+    T.np = ss.meta; T.nq = ss.meta + nm; T.poff = ss.meta + 2 * nm; T.qoff = ss.meta + 3 * nm;
+    KTimer t(c, KN_THOMAS, st);
+    const size_t lds = sizeof(double) * THC_LDS * S;
+    if (lds > 32 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_thomas_corr_seg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int per = THC_UNR * (THC_NT / 8), nslice = (sg.maxlen + per - 1) / per; // rows per slice
+    hipLaunchKernelGGL(k_thomas_corr_seg, dim3(P.nblk, nlayers, S * nslice), dim3(THC_NT), lds, st, P, T, (const QgThomasSegRec *)ss.recs, nslice);
+    HIPCHECK(hipGetLastError());
+  }
   return 0;
 }
 
@@ -2860,7 +3083,15 @@ extern "C" int qgcm_hip_helmholtz(qgcm_hip_handle c, double *wrk, const double *
   if (!c->whole) QG_FAIL("qgcm_hip_helmholtz: only for a handle that owns the whole domain");
   const QgGeom &g = c->g;
   // pivots for this boc (box: boc(i-1) multiplies sine wavenumber i-1, src/ocisubs.F:470-478)
-  {
+  if (c->seg.S > 1) {
+    // a column in segments: the responses of every segment for THIS diagonal too (the last one is kept)
+    auto &ss = c->seg.set[1];
+    if (ss.boc.size() != (size_t)g.nk || memcmp(ss.boc.data(), boc, sizeof(double) * g.nk)) {
+      ss.boc.clear();
+      if (build_segments(c, 1, {std::vector<double>(boc, boc + g.nk)})) return 1;
+      ss.boc.assign(boc, boc + g.nk);
+    }
+  } else {
     ThomasTabHost T;
     build_pivots(g, c->prm.aoc, boc, T);
     if (upload_pivots(c, c->tt_tmp, T)) return 1;

@@ -110,7 +110,7 @@ SYMBOLS = [
     "qgcm_hip_qgastep", "qgcm_hip_atinvq", "qgcm_hip_atqzbd", "qgcm_hip_get_bsums", "qgcm_hip_coupled_steps", "qgcm_hip_set_cu_range",
     "qgcm_hip_wrk_fill", "qgcm_hip_wrk_get", "qgcm_hip_wrk_set", "qgcm_hip_area_integrals",
     "qgcm_hip_local_rows", "qgcm_hip_row_transform", "qgcm_hip_thomas_msg_len", "qgcm_hip_thomas_phase",
-    "qgcm_hip_thomas_const_len", "qgcm_hip_thomas_consts", "qgcm_hip_set_thomas_consts",
+    "qgcm_hip_thomas_const_len", "qgcm_hip_thomas_consts", "qgcm_hip_set_thomas_consts", "qgcm_hip_thomas_segments",
     "qgcm_hip_constr", "qgcm_hip_unpack",
     "qgcm_hip_halo_msg_len", "qgcm_hip_halo_pack", "qgcm_hip_halo_unpack", "qgcm_hip_slab_stage", "qgcm_hip_oml_msg_len",
     "qgcm_hip_comm_unique_id", "qgcm_hip_comm_init", "qgcm_hip_slab_steps", "qgcm_hip_comm_set_halo_p2p", "qgcm_hip_comm_set_overlap", "qgcm_hip_comm_probe",
@@ -193,6 +193,7 @@ def load_library():
     L.qgcm_hip_thomas_consts.argtypes = [vp, vp]
     L.qgcm_hip_set_thomas_consts.argtypes = [vp, vp, C.c_int]
     L.qgcm_hip_thomas_phase.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
+    L.qgcm_hip_thomas_segments.argtypes = [C.c_int, C.c_int, ip, ip, ip]
     L.qgcm_hip_constr.argtypes = [vp]
     L.qgcm_hip_unpack.argtypes = [vp, C.c_int]
     L.qgcm_hip_halo_msg_len.argtypes = [vp]
@@ -295,3 +296,18 @@ def load_library():
 def check(rc):
     if rc != 0:
         raise QgcmHipError(load_library().qgcm_hip_last_error().decode())
+
+
+THOMAS_MAX_ROWS = 2048  # QGCM_HIP_THOMAS_MAX_ROWS
+THOMAS_SEG_MIN = 4      # QGCM_HIP_THOMAS_SEG_MIN
+THOMAS_MAX_SEG = 64     # QGCM_HIP_THOMAS_MAX_SEG
+THOMAS_SEG_DEFAULT = 1024  # QGCM_HIP_THOMAS_SEG_DEFAULT
+
+
+def thomas_segments(nrows, max_rows=0):
+    """The segment plan of a column of `nrows` interior rows (qgcm_hip_thomas_segments; host code, no device):
+    [(first, count)] per segment.  max_rows = 0: no maximum given (QGCM_HIP_THOMAS_SEG_ROWS unset)."""
+    n = C.c_int(0)
+    first, count = (C.c_int * THOMAS_MAX_SEG)(), (C.c_int * THOMAS_MAX_SEG)()
+    check(load_library().qgcm_hip_thomas_segments(nrows, max_rows, C.byref(n), first, count))
+    return [(first[s], count[s]) for s in range(n.value)]

@@ -454,6 +454,13 @@ class OceanModel:
         check(self.L.qgcm_hip_get_monitors(self.h, _dp(e), _dp(f)))
         return e, f
 
+    def get_bsums(self):
+        """ajisoc, ajinoc, ap5soc, ap5noc (nlo each): the boundary line sums of the last qgostep of a zonally cyclic
+        ocean (valid after the following ocinvq)."""
+        b = np.zeros(4 * self.cfg.nlo)
+        check(self.L.qgcm_hip_get_bsums(self.h, _dp(b)))
+        return b
+
     def get_inv_diag(self):
         nl = self.cfg.nlo
         x = np.zeros(nl)
