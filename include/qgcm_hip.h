@@ -663,6 +663,64 @@ long qgcm_hip_cov_part_len(qgcm_hip_handle h);
 int qgcm_hip_cov_part(qgcm_hip_handle h, double *send_dev);
 int qgcm_hip_cov_combine(qgcm_hip_handle h, const double *gath_dev, int nranks);
 
+/* ---- area averages and the CFL check: areavg and cfltry ------------------------------------------
+ * "call areavg" (src/areasubs_diag.F:50-677, cpp option get_areav) and "call cfltry" (src/q-gcm.F:2121-2440) on the
+ * device, for an ocean handle (sst; po, tauxo, tauyo, hmoc) or a whole-domain atmosphere handle (ast; pa, uekat,
+ * vekat).  Both read the levels qgcm_hip_get_state / _oml_get_state / _aml_get_state would return at that point (after
+ * an averaging step the averaged ones) and change no state; a handle that never calls them runs exactly as before.
+ * The fields are the ones the monitors read: the mixed layer's own sst / ast and stress when it is on, else what
+ * qgcm_hip_set_monitor_fields / qgcm_hip_set_atm_monitor_fields gave; uekat, vekat are those xforc writes.
+ *
+ * qgcm_hip_areavg_init(h, n, i1, i2, j1, j2, facw, face, facs, facn): the finished tables of areavg's first call for
+ *   the T grid - 1-based subscripts (global rows, also on a y-slab) and the four boundary weights of n <= 9 areas
+ *   (namxoc = namxat = 9); qgcm_hip.hostinit.area_limits restates the reference's arithmetic from the limits in
+ *   metres.  Areas may overlap.  Refuses, naming the area and changing nothing: n outside 1..9, a subscript outside
+ *   the T grid (the reference's own check), i1 > i2, j1 > j2.  i1 == i2 and j1 == j2 follow areint's formula as
+ *   written (west and east weight on the one column, south and north row both contribute).  The denominator of
+ *   areint depends on the tables alone: it is formed here, on the host, in the reference's serial order - bitwise
+ *   the reference's.  May be called again with other tables.  qgcm_hip_areavg_count(h): n (0 before the set-up).
+ * qgcm_hip_areavg(h, avg, num, den): tavoc / tavat (n) of one call of areavg; num, den (n each, may be NULL) are
+ *   areint's numerator and denominator.  One pass over the areas' rows, no atomics and a fixed order: bitwise the
+ *   same from call to call; the numerator is a sum in another order than areint's and agrees with it to rounding
+ *   (2 N 2^-53 sum|terms| for an area of N points).  Fails, naming the field, if sst / ast was never given.
+ *   Whole-domain handles; synchronous.
+ * qgcm_hip_cfl_len(h) = 2*(nl+1) quantities, in this order: the mixed layer's |u|, |v|, then |u|(k), k = 1..nl, then
+ *   |v|(k).  qgcm_hip_cfl(h, cflcrit, maxima, nbad, loc): per quantity the maximum (uabmax / vabmax, uamaxo / vamaxo
+ *   and the atmosphere's), the number of lines "Bad ...; CFL, i, j[, k]" the reference would print - the points with
+ *   (dt/dx)*|.| >= cflcrit where max*dt/dx >= cflcrit, else 0 - and loc[2q], loc[2q+1] = (i, j) of the maximum, its
+ *   first occurrence in the reference's scan order (j outer, i inner).  nbad, loc may be NULL.  cflcrit: the
+ *   reference's parameter is 0.8.  The expressions keep the reference's operand order, uncontracted, and maxima,
+ *   counts and first locations do not depend on the order of a reduction: all are exact.  The Courant numbers
+ *   max*dt/dx are the caller's to form (dt = tdto/2, dx = dxo).  There is no cyclic special case, as in the
+ *   reference.  The point-by-point listing itself stays with the host, which pulls the state for a failing run as it
+ *   does for valids.  Fails, naming it, if a stress, uekat / vekat or hmoc (qgcm_hip_set_mon_params, else
+ *   qgcm_hip_oml_init) was never given.  Whole-domain handles; synchronous.
+ * Y-slabs (ocean): the triples of the other diagnostics - _part_len(h) doubles per summary, _part(h, .., send_dev)
+ *   asynchronous on the handle's stream, _combine(h, gath_dev, nranks, ..) synchronous, failing when the gathered rows
+ *   do not tile the domain in rank order; they also serve a whole-domain ocean with nranks = 1 and refuse an
+ *   atmosphere, as the whole-domain calls refuse a y-slab.
+ *   areavg  per area the raw sums of rows j1 and j2 (0 on the ranks that do not own them) and the sum of the owned
+ *           interior rows (3*9) | the owned global T rows t0, t1  = 29 doubles.  Ownership as above: T rows g0..g1,
+ *           g1-1 on the rank that owns row nypo.  The combine adds in rank order, then applies facs / facn and
+ *           divides: bitwise the same on every rank, within the reordering bound of the whole-domain value.
+ *   cfl     maxima | keys (j-1)*nxpo + (i-1) of their first points, global rows | counts (2*(nl+1) each) | the owned
+ *           p rows g0, g1  = 6*(nl+1) + 2 doubles.  The |u| forms read row j+1: a halo row, current between the slab
+ *           step calls; the rank that owns row nypo stops at nypo-1.  The combine keeps the largest maximum and among
+ *           equal ones the earliest key, and adds the counts: bitwise the whole-domain result. */
+int qgcm_hip_areavg_init(qgcm_hip_handle h, int n, const int *i1, const int *i2, const int *j1, const int *j2,
+                         const double *facw, const double *face, const double *facs, const double *facn);
+int qgcm_hip_areavg_count(qgcm_hip_handle h);
+int qgcm_hip_areavg(qgcm_hip_handle h, double *avg, double *num, double *den);
+int qgcm_hip_areavg_part_len(qgcm_hip_handle h);
+int qgcm_hip_areavg_part(qgcm_hip_handle h, double *send_dev);
+int qgcm_hip_areavg_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, double *avg, double *num, double *den);
+int qgcm_hip_cfl_len(qgcm_hip_handle h);
+int qgcm_hip_cfl(qgcm_hip_handle h, double cflcrit, double *maxima, int *nbad, int *loc);
+int qgcm_hip_cfl_part_len(qgcm_hip_handle h);
+int qgcm_hip_cfl_part(qgcm_hip_handle h, double cflcrit, double *send_dev);
+int qgcm_hip_cfl_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, double cflcrit, double *maxima, int *nbad,
+                         int *loc);
+
 /* ---- momentum half of xforc -----------------------------------------------------------------------
  * "call xforc" (src/q-gcm.F:1226) as far as the momentum goes (src/xfosubs.F:137-709): the atmosphere's geostrophic
  * velocity from pam(:,:,1), its bicubic interpolation to ocean resolution (auvbcu), the optional shear against the

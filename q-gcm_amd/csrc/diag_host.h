@@ -1,5 +1,6 @@
 // Host side of the on-device diagnostics: the validity scan, the ocean and atmosphere monitors, the start-up / restart
-// arithmetic, the time averages, the periodic dumps and the covariance matrices.  Parameter fillers,
+// arithmetic, the time averages, the periodic dumps, the covariance matrices, the area averages and the CFL check
+// (DESIGN 6e-6j, 6m).  Parameter fillers,
 // launches and C ABI entry points only; the kernels are in the k_*.h headers.  Part of qgcm_hip.hip's translation unit:
 // included there once, after the handle and the step's building blocks and before one_step.
 #pragma once
@@ -1483,4 +1484,272 @@ extern "C" int qgcm_hip_cov_schedule(qgcm_hip_handle c, int every, int phase) {
             "qgcm_hip_cov_part / _combine between slab steps)");
   if (cov_ready(c, "qgcm_hip_cov_schedule")) return 1;
   return sched_set(c->sched[SCH_COV], every, phase, "qgcm_hip_cov_schedule");
+}
+
+// ---------------------------------------------------------------------------
+// area averages and the CFL check: areavg and cfltry
+// ---------------------------------------------------------------------------
+// The handles these entry points serve.  part: the y-slab triple (_part / _combine), which an atmosphere does not
+// have; else the whole-domain call, which a y-slab cannot answer.  `other`: the calls that serve the refused handle.
+static int ac_handle(qgcm_hip_ctx *c, bool part, const char *who, const char *other) {
+  if (!c) QG_FAIL("%s: null handle", who);
+  if (part && c->g.atm) QG_FAIL("%s: the handle is an atmosphere, which has no y-slabs (%s serves it)", who, other);
+  if (!part && !c->whole) QG_FAIL("%s: the handle is a y-slab (%s serve it)", who, other);
+  return check_ready(c, who);
+}
+
+extern "C" int qgcm_hip_areavg_init(qgcm_hip_handle c, int n, const int *i1, const int *i2, const int *j1, const int *j2,
+                                    const double *facw, const double *face, const double *facs, const double *facn) {
+  const char *who = "qgcm_hip_areavg_init";
+  if (check_ready(c, who)) return 1;
+  if (c->g.atm && !c->whole) QG_FAIL("%s: the handle is an atmosphere's y-slab (the atmosphere's diagnostics need the whole domain)", who);
+  if (n < 1 || n > ARAV_MAXN)
+    QG_FAIL("%s: %d areas (need 1 .. %d = namxoc, namxat of src/areasubs_diag.F)", who, n, ARAV_MAXN);
+  if (!i1 || !i2 || !j1 || !j2 || !facw || !face || !facs || !facn) QG_FAIL("%s: null argument", who);
+  const QgGeom &g = c->g;
+  const int nxt = g.nx - 1, nyt = g.nyg - 1;
+  const char *fluid = g.atm ? "atmos." : "ocean";
+  QgAravParams T = {};
+  T.n = n;
+  for (int a = 0; a < n; ++a) {
+    // the reference's subscript checks (src/areasubs_diag.F:312-325), then what areint's loops assume
+    if (i1[a] < 1 || i1[a] > nxt || i2[a] < 1 || i2[a] > nxt)
+      QG_FAIL("%s: invalid subscript for %s area m = %d: i1t, i2t = %d, %d outside 1..%d", who, fluid, a + 1, i1[a], i2[a], nxt);
+    if (j1[a] < 1 || j1[a] > nyt || j2[a] < 1 || j2[a] > nyt)
+      QG_FAIL("%s: invalid subscript for %s area m = %d: j1t, j2t = %d, %d outside 1..%d", who, fluid, a + 1, j1[a], j2[a], nyt);
+    if (i1[a] > i2[a]) QG_FAIL("%s: %s area m = %d has i1t = %d > i2t = %d", who, fluid, a + 1, i1[a], i2[a]);
+    if (j1[a] > j2[a]) QG_FAIL("%s: %s area m = %d has j1t = %d > j2t = %d", who, fluid, a + 1, j1[a], j2[a]);
+    T.i1[a] = i1[a]; T.i2[a] = i2[a]; T.j1[a] = j1[a]; T.j2[a] = j2[a];
+    T.facw[a] = facw[a]; T.face[a] = face[a]; T.facs[a] = facs[a]; T.facn[a] = facn[a];
+    // areint's weight sums in its serial order (:621-675): the same wsumi for every row
+    double wsumi = facw[a];
+    for (int i = i1[a] + 1; i <= i2[a] - 1; ++i) wsumi = wsumi + 1.0;
+    wsumi = wsumi + face[a];
+    double wtsum = 0.0;
+    for (int j = j1[a] + 1; j <= j2[a] - 1; ++j) wtsum = wtsum + wsumi;
+    T.den[a] = facs[a] * wsumi + facn[a] * wsumi + wtsum;
+  }
+  auto &m = c->ac;
+  const int rowcap = owned_t1(g) - g.jlo + 1;
+  if (!m.rows && (dalloc(&m.rows, (size_t)ARAV_MAXN * rowcap) || dalloc(&m.out, ARAV_PART_LEN))) return 1;
+  HIPCHECK(hipStreamSynchronize(c->stream)); // (no call that reads the old tables is still in flight)
+  m.tab = T;
+  return 0;
+}
+
+// the kernel parameters: the tables, the field at its current level, the owned T rows
+static int arav_params(qgcm_hip_ctx *c, QgAravParams &P, const char *who) {
+  auto &m = c->ac;
+  if (m.tab.n == 0) QG_FAIL("%s: qgcm_hip_areavg_init has not been called", who);
+  const QgGeom &g = c->g;
+  P = m.tab;
+  if (g.atm) {
+    if (!c->atmon.ast)
+      QG_FAIL("%s: ast was never given (qgcm_hip_set_atm_monitor_fields) and the mixed layer is off", who);
+    P.f = c->atmon.ast;
+    P.ld = c->atmon.ldt;
+  } else {
+    static const int need[] = {SF_SST, SF_END};
+    QgSurf S;
+    if (surf_fields(c, need, S, who)) return 1;
+    P.f = S.sst;
+    P.ld = S.ldt;
+  }
+  P.t0 = g.jlo + g.joff;
+  P.t1 = owned_t1(g) + g.joff;
+  P.joff = g.joff;
+  P.nyt = g.nyg - 1;
+  P.rowcap = P.t1 - P.t0 + 1;
+  P.rows = m.rows;
+  P.out = m.out;
+  return 0;
+}
+
+// the row sums of every area over the owned rows, then the handle's part of the sums (FINAL: the averages)
+static int launch_arav(qgcm_hip_ctx *c, const QgAravParams &P, bool final) {
+  int maxrows = 0;
+  for (int a = 0; a < P.n; ++a)
+    maxrows = std::max(maxrows, std::min(P.j2[a], P.t1) - std::max(P.j1[a], P.t0) + 1);
+  if (maxrows > 0) hipLaunchKernelGGL(k_arav_rows, dim3(maxrows, P.n), dim3(64), 0, c->stream, P);
+  if (final) hipLaunchKernelGGL(k_arav_part<true>, dim3(1), dim3(64 * ARAV_MAXN), 0, c->stream, P);
+  else hipLaunchKernelGGL(k_arav_part<false>, dim3(1), dim3(64 * ARAV_MAXN), 0, c->stream, P);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// avg, num, den (each may be null) from the device vector at c->ac.out; *status = the combine's
+static int arav_fetch(qgcm_hip_ctx *c, int n, double *avg, double *num, double *den, double *status) {
+  double h[ARAV_OUT_LEN];
+  HIPCHECK(hipMemcpyAsync(h, c->ac.out, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  if (status) {
+    *status = h[3 * ARAV_MAXN];
+    if (*status != 0.0) return 0;
+  }
+  for (int a = 0; a < n; ++a) {
+    if (avg) avg[a] = h[a];
+    if (num) num[a] = h[ARAV_MAXN + a];
+    if (den) den[a] = h[2 * ARAV_MAXN + a];
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_areavg_count(qgcm_hip_handle c) { return c ? c->ac.tab.n : -1; }
+
+extern "C" int qgcm_hip_areavg(qgcm_hip_handle c, double *avg, double *num, double *den) {
+  const char *who = "qgcm_hip_areavg";
+  if (ac_handle(c, false, who, "qgcm_hip_areavg_part / _combine")) return 1;
+  if (!avg) QG_FAIL("%s: null argument", who);
+  QgAravParams P;
+  if (arav_params(c, P, who) || launch_arav(c, P, true)) return 1;
+  return arav_fetch(c, P.n, avg, num, den, nullptr);
+}
+
+extern "C" int qgcm_hip_areavg_part_len(qgcm_hip_handle c) { return c ? ARAV_PART_LEN : -1; }
+
+extern "C" int qgcm_hip_areavg_part(qgcm_hip_handle c, double *send_dev) {
+  const char *who = "qgcm_hip_areavg_part";
+  if (ac_handle(c, true, who, "qgcm_hip_areavg")) return 1;
+  if (!send_dev) QG_FAIL("%s: null argument", who);
+  QgAravParams P;
+  if (arav_params(c, P, who)) return 1;
+  P.out = send_dev;
+  return launch_arav(c, P, false);
+}
+
+extern "C" int qgcm_hip_areavg_combine(qgcm_hip_handle c, const double *gath_dev, int nranks, double *avg, double *num,
+                                       double *den) {
+  const char *who = "qgcm_hip_areavg_combine";
+  if (ac_handle(c, true, who, "qgcm_hip_areavg")) return 1;
+  if (!gath_dev || !avg || nranks < 1) QG_FAIL("%s: need the gathered summaries, avg and nranks >= 1", who);
+  auto &m = c->ac;
+  if (m.tab.n == 0) QG_FAIL("%s: qgcm_hip_areavg_init has not been called", who);
+  QgAravParams P = m.tab;
+  P.nyt = c->g.nyg - 1;
+  P.out = m.out;
+  P.gath = gath_dev;
+  P.nranks = nranks;
+  hipLaunchKernelGGL(k_arav_combine, dim3(1), dim3(64), 0, c->stream, P);
+  HIPCHECK(hipGetLastError());
+  double st = 0.0;
+  if (arav_fetch(c, P.n, avg, num, den, &st)) return 1;
+  if (st != 0.0)
+    QG_FAIL("%s: the gathered summaries do not tile T rows 1..%d (rank %d of %d does not continue them)", who, P.nyt,
+            (int)st - 1, nranks);
+  return 0;
+}
+
+// the parameters of the CFL kernels (partials over this handle's owned rows); allocates on first use
+static int cfl_params(qgcm_hip_ctx *c, QgCflParams &P, double cflcrit, const char *who) {
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("%s: unsupported number of layers", who);
+  if (!(cflcrit == cflcrit)) QG_FAIL("%s: cflcrit is not a number", who);
+  memset(&P, 0, sizeof(P));
+  P.g = g;
+  P.p = c->p[c->ip]; // the level qgcm_hip_get_state hands out as po / pa
+  if (g.atm) {
+    const auto &m = c->atmon;
+    const char *miss = !m.uekat ? "uekat" : !m.vekat ? "vekat" : nullptr;
+    if (miss) QG_FAIL("%s: %s was never given (qgcm_hip_set_atm_monitor_fields, qgcm_hip_xforc)", who, miss);
+    P.sx = m.uekat; P.sy = m.vekat; P.ldt = m.ldt;
+  } else {
+    static const int need[] = {SF_TAUX, SF_TAUY, SF_END};
+    QgSurf S;
+    if (surf_fields(c, need, S, who)) return 1;
+    P.sx = S.taux; P.sy = S.tauy; P.ldt = S.ldt;
+    // hmoc where the monitors take it (qgcm_hip_set_mon_params), else the mixed layer's own
+    if (!c->mon.prm_set && !c->oml.on)
+      QG_FAIL("%s: hmoc was never given (qgcm_hip_set_mon_params or qgcm_hip_oml_init)", who);
+    const double hmoc = c->mon.prm_set ? c->mon.prm.hmoc : c->oml.prm.hmoc;
+    P.rhf0hm = 0.5 / (pr.fnot * hmoc); // src/q-gcm.F:2174
+  }
+  P.jlo = g.jlo; P.jhi = g.jhi;
+  P.ntx = (g.nx + CFL_TX - 1) / CFL_TX;
+  P.nblk = P.ntx * ((g.jhi - g.jlo + 1 + CFL_TY - 1) / CFL_TY);
+  auto &m = c->ac;
+  if (!m.cfl_part && (dalloc(&m.cfl_part, (size_t)CFL_LEN(QG_MAXL) * P.nblk) || dalloc(&m.cfl_out, CFL_PART_LEN(QG_MAXL))))
+    return 1;
+  P.part = m.cfl_part;
+  P.out = m.cfl_out;
+  // MODULE occonst / atconst as src/q-gcm.F derives them; dto = tdto/2 exactly
+  P.rdxf0 = 1.0 / (pr.dxo * pr.fnot);
+  P.dtdx = (0.5 * pr.tdto) / pr.dxo;
+  P.cflcrit = cflcrit;
+  return 0;
+}
+
+static int launch_cfl(qgcm_hip_ctx *c, const QgCflParams &P, bool part) {
+#define QG_CFL(NLV)                                                                                      \
+  if (c->g.atm) hipLaunchKernelGGL((k_cfl_scan<NLV, true>), dim3(P.nblk), dim3(CFL_NT), 0, c->stream, P); \
+  else hipLaunchKernelGGL((k_cfl_scan<NLV, false>), dim3(P.nblk), dim3(CFL_NT), 0, c->stream, P)
+  QG_SWITCH_NL(c->g.nl, QG_CFL, "k_cfl");
+#undef QG_CFL
+  if (part) hipLaunchKernelGGL(k_cfl_final<true>, dim3(1), dim3(CFL_FT), 0, c->stream, P);
+  else hipLaunchKernelGGL(k_cfl_final<false>, dim3(1), dim3(CFL_FT), 0, c->stream, P);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// maxima, nbad (nq each) and loc (i, j per quantity) from the device vector at c->ac.cfl_out.  The count is the
+// reference's: its second scan runs only where the printed Courant number max*dt/dx reaches cflcrit.
+static int cfl_fetch(qgcm_hip_ctx *c, const QgCflParams &P, double *maxima, int *nbad, int *loc, double *status) {
+  const int nq = CFL_NQ(c->g.nl);
+  double h[CFL_PART_LEN(QG_MAXL)];
+  HIPCHECK(hipMemcpyAsync(h, c->ac.cfl_out, sizeof(double) * (3 * nq + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  if (status) {
+    *status = h[3 * nq];
+    if (*status != 0.0) return 0;
+  }
+  const double dt = 0.5 * c->prm.tdto, dx = c->prm.dxo;
+  for (int q = 0; q < nq; ++q) {
+    const int key = (int)h[nq + q];
+    if (maxima) maxima[q] = h[q];
+    if (nbad) nbad[q] = h[q] * dt / dx >= P.cflcrit ? (int)h[2 * nq + q] : 0;
+    if (loc) { loc[2 * q] = key % c->g.nx + 1; loc[2 * q + 1] = key / c->g.nx + 1; }
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_cfl_len(qgcm_hip_handle c) { return c ? CFL_NQ(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_cfl(qgcm_hip_handle c, double cflcrit, double *maxima, int *nbad, int *loc) {
+  const char *who = "qgcm_hip_cfl";
+  if (ac_handle(c, false, who, "qgcm_hip_cfl_part / _combine")) return 1;
+  if (!maxima) QG_FAIL("%s: null argument", who);
+  QgCflParams P;
+  if (cfl_params(c, P, cflcrit, who) || launch_cfl(c, P, false)) return 1;
+  return cfl_fetch(c, P, maxima, nbad, loc, nullptr);
+}
+
+extern "C" int qgcm_hip_cfl_part_len(qgcm_hip_handle c) { return c ? CFL_PART_LEN(c->g.nl) : -1; }
+
+extern "C" int qgcm_hip_cfl_part(qgcm_hip_handle c, double cflcrit, double *send_dev) {
+  const char *who = "qgcm_hip_cfl_part";
+  if (ac_handle(c, true, who, "qgcm_hip_cfl")) return 1;
+  if (!send_dev) QG_FAIL("%s: null argument", who);
+  QgCflParams P;
+  if (cfl_params(c, P, cflcrit, who)) return 1;
+  P.out = send_dev;
+  return launch_cfl(c, P, true);
+}
+
+extern "C" int qgcm_hip_cfl_combine(qgcm_hip_handle c, const double *gath_dev, int nranks, double cflcrit, double *maxima,
+                                    int *nbad, int *loc) {
+  const char *who = "qgcm_hip_cfl_combine";
+  if (ac_handle(c, true, who, "qgcm_hip_cfl")) return 1;
+  if (!gath_dev || !maxima || nranks < 1) QG_FAIL("%s: need the gathered summaries, maxima and nranks >= 1", who);
+  QgCflParams P;
+  if (cfl_params(c, P, cflcrit, who)) return 1;
+  P.gath = gath_dev;
+  P.nranks = nranks;
+  hipLaunchKernelGGL(k_cfl_combine, dim3(1), dim3(64), 0, c->stream, P);
+  HIPCHECK(hipGetLastError());
+  double st = 0.0;
+  if (cfl_fetch(c, P, maxima, nbad, loc, &st)) return 1;
+  if (st != 0.0)
+    QG_FAIL("%s: the gathered summaries do not tile rows 1..%d (rank %d of %d does not continue them)", who, c->g.nyg,
+            (int)st - 1, nranks);
+  return 0;
 }

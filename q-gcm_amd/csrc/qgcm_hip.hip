@@ -40,6 +40,7 @@
 #include "k_tavg.h"
 #include "k_atm_tavg.h"
 #include "k_cov.h"
+#include "k_areacfl.h"
 #include "k_qocdiag.h"
 #include "k_setup.h"
 #include "k_xforc.h"
@@ -261,6 +262,13 @@ struct qgcm_hip_ctx {
     long nu[2] = {0, 0};
     double swt[2] = {0.0, 0.0};
   } cov;
+  // area averages and CFL check (qgcm_hip_areavg* / qgcm_hip_cfl*, k_areacfl.h): the tables of qgcm_hip_areavg_init
+  // (tab.n = 0: not set up), the row sums and the result; the CFL partials and result, allocated on first use
+  struct {
+    QgAravParams tab = {};
+    double *rows = nullptr, *out = nullptr;
+    double *cfl_part = nullptr, *cfl_out = nullptr;
+  } ac;
   // periodic dumps (qgcm_hip_qocdiag / _ocnc_sample / _atnc_sample, k_qocdiag.h): device result buffer (grown on
   // demand); the scheduled dump of qgcm_hip_qocdiag_schedule: a ring of `cap` snapshots of `len` doubles, oldest at `head`
   struct {
@@ -517,6 +525,9 @@ extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
   for (double *p : tavp)
     if (p) hipFree(p);
   if (c->cov.status) hipFree(c->cov.status);
+  double *acp[] = {c->ac.rows, c->ac.out, c->ac.cfl_part, c->ac.cfl_out};
+  for (double *p : acp)
+    if (p) hipFree(p);
   double *xfp[] = {c->xf.u1at, c->xf.v1at, c->xf.txf, c->xf.tyf, c->xf.wf, c->xf.tab};
   for (double *p : xfp)
     if (p) hipFree(p);

@@ -434,6 +434,73 @@ module qgcm_hip_iface
       real(c_double), intent(out) :: out(12)
       integer(c_int), intent(out) :: solnok
     end function
+    ! area averages and the CFL check (areavg, cfltry; DESIGN 6m).  Not called by the drop-in, which still pulls the
+    ! state before areavg / cfltry (INTEGRATION.md)
+    integer(c_int) function qgcm_hip_areavg_init(h, n, i1, i2, j1, j2, facw, face, facs, facn) &
+        bind(C, name='qgcm_hip_areavg_init')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: n
+      integer(c_int), intent(in) :: i1(*), i2(*), j1(*), j2(*)
+      real(c_double), intent(in) :: facw(*), face(*), facs(*), facn(*)
+    end function
+    integer(c_int) function qgcm_hip_areavg_count(h) bind(C, name='qgcm_hip_areavg_count')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    ! c_loc of num(n), den(n), or c_null_ptr
+    integer(c_int) function qgcm_hip_areavg(h, avg, num, den) bind(C, name='qgcm_hip_areavg')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: avg(*)
+      type(c_ptr), value :: num, den
+    end function
+    integer(c_int) function qgcm_hip_areavg_part_len(h) bind(C, name='qgcm_hip_areavg_part_len')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_areavg_part(h, send_dev) bind(C, name='qgcm_hip_areavg_part')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, send_dev
+    end function
+    integer(c_int) function qgcm_hip_areavg_combine(h, gath_dev, nranks, avg, num, den) &
+        bind(C, name='qgcm_hip_areavg_combine')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h, gath_dev
+      integer(c_int), value :: nranks
+      real(c_double), intent(out) :: avg(*)
+      type(c_ptr), value :: num, den
+    end function
+    integer(c_int) function qgcm_hip_cfl_len(h) bind(C, name='qgcm_hip_cfl_len')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    ! maxima(2*(nl+1)), nbad(2*(nl+1)), loc(2, 2*(nl+1)) = (i, j) of every maximum
+    integer(c_int) function qgcm_hip_cfl(h, cflcrit, maxima, nbad, loc) bind(C, name='qgcm_hip_cfl')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), value :: cflcrit
+      real(c_double), intent(out) :: maxima(*)
+      integer(c_int), intent(out) :: nbad(*), loc(2,*)
+    end function
+    integer(c_int) function qgcm_hip_cfl_part_len(h) bind(C, name='qgcm_hip_cfl_part_len')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function qgcm_hip_cfl_part(h, cflcrit, send_dev) bind(C, name='qgcm_hip_cfl_part')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h, send_dev
+      real(c_double), value :: cflcrit
+    end function
+    integer(c_int) function qgcm_hip_cfl_combine(h, gath_dev, nranks, cflcrit, maxima, nbad, loc) &
+        bind(C, name='qgcm_hip_cfl_combine')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h, gath_dev
+      integer(c_int), value :: nranks
+      real(c_double), value :: cflcrit
+      real(c_double), intent(out) :: maxima(*)
+      integer(c_int), intent(out) :: nbad(*), loc(2,*)
+    end function
     ! time averages and periodic dump of the atmosphere (tavatm / tavout, atnc_out; DESIGN 6i).  Not called by the
     ! drop-in, which still pulls the state before tavatm / atnc_out (INTEGRATION.md)
     integer(c_int) function qgcm_hip_set_atm_tav_fields(h, fnetat) bind(C, name='qgcm_hip_set_atm_tav_fields')

@@ -11,6 +11,7 @@ restated with numpy for the host side (init-only, not on the per-step path):
   homsol   src/conhoms.F:376-641     (homogeneous solutions; the Helmholtz solves
                                       go through the HIP solver, see OceanModel)
   bcuini   src/xfosubs.F:1238-1728   (bicubic weight tables of auvbcu, with wts2bb)
+  areavg   src/areasubs_diag.F:123-448 (the `first` block: areas.limits, subscripts and weights of the areas)
 
 The atmospheric channel (cfg.atmos) shares all of it with the cyclic ocean; where the
 reference's atmosphere differs the functions branch on ``cfg.atmos``: eigmod without the Flierl normalisation
@@ -466,3 +467,93 @@ def bilint_tables(xta, yta, xto, yto, dxa, dya):
     wmy = 1.0 - wpy
     i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
     return dict(iam=i32(iam), iap=i32(iap), wmx=wmx, wpx=wpx, jam=i32(jam), jap=i32(jap), wmy=wmy, wpy=wpy)
+
+
+# ---------------------------------------------------------------------------
+# areavg's set-up (src/areasubs_diag.F:123-448)
+# ---------------------------------------------------------------------------
+AREAS_MAX = 9  # namxoc = namxat
+
+
+def _fortran_values(lines, pos, n):
+    """One list-directed READ of n values (`read (unit, *) (x(ia), ia=1,n)`): values separated by blanks or commas,
+    a D exponent (400.0d3), records taken until n values are in; the rest of the last record is ignored (the sample
+    file keeps its `!!name` comments there).  Returns (values, next record)."""
+    vals = []
+    while len(vals) < n:
+        if pos >= len(lines):
+            raise ValueError("areas.limits ends inside a record of %d values" % n)
+        for tok in lines[pos].replace(",", " ").split():
+            if len(vals) == n:
+                break
+            try:
+                vals.append(float(tok.lower().replace("d", "e")))
+            except ValueError:
+                raise ValueError("areas.limits: record %d: %r is not a number" % (pos + 1, tok))
+        pos += 1
+    return vals, pos
+
+
+def read_areas_limits(path):
+    """The file `areas.limits` as areavg reads it (src/areasubs_diag.F:131-193): the ocean block, then the atmosphere
+    block; each is the number of areas, xlo, xhi, ylo, yhi in metres (list-directed records) and a line of names in
+    the format (9(8x,a3)).  Returns {"ocean": block, "atmos": block}, block = dict(n, xlo, xhi, ylo, yhi, names)."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    out, pos = {}, 0
+    for fluid in ("ocean", "atmos"):
+        (n,), pos = _fortran_values(lines, pos, 1)
+        if n != int(n) or not 0 <= n <= AREAS_MAX:
+            raise ValueError("areas.limits: %s block has %r areas (0 .. %d = namxoc, namxat)" % (fluid, n, AREAS_MAX))
+        n = int(n)
+        blk = {"n": n}
+        for k in ("xlo", "xhi", "ylo", "yhi"):
+            v, pos = _fortran_values(lines, pos, n)
+            blk[k] = np.array(v, dtype=np.float64)
+        if pos >= len(lines):
+            raise ValueError("areas.limits: the names of the %s areas are missing" % fluid)
+        blk["names"] = [lines[pos][11 * a + 8:11 * a + 11] for a in range(n)]
+        pos += 1
+        out[fluid] = blk
+    return out
+
+
+def area_limits(xlo, xhi, ylo, yhi, dx, dy, nx, ny, fluid="ocean"):
+    """T subscripts and boundary weights of areavg's areas on a grid of nx x ny T cells of dx x dy metres
+    (src/areasubs_diag.F:204-238 / :345-379), from the limits in metres measured from the domain's south-west corner.
+    (The p-point subscripts the reference prints next to them are never used.)  Returns dict(i1, i2, j1, j2 (1-based),
+    facw, face, facs, facn).  Raises ValueError with the reference's range checks, naming the area (1-based)."""
+    lim = [np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (xlo, xhi, ylo, yhi)]
+    n = len(lim[0])
+    if any(len(a) != n for a in lim):
+        raise ValueError("area_limits: xlo, xhi, ylo, yhi differ in length")
+    if n > AREAS_MAX:
+        raise ValueError("area_limits: %d areas > %d (namxoc, namxat of src/areasubs_diag.F)" % (n, AREAS_MAX))
+
+    def side(v, d, lower):
+        # rilo = 1 + (xlo - dx/2)/dx; frlo = mod(rilo, 1); i1 = int(rilo); frlo >= 0.5 bumps i1, frhi > 0.5 bumps i2
+        r = 1.0 + (v - 0.5 * d) / d
+        fr = float(np.fmod(r, 1.0))
+        i = int(r)
+        if (fr >= 0.5) if lower else (fr > 0.5):
+            fr = fr - 1.0
+            i += 1
+        return i, (0.5 - fr if lower else 0.5 + fr)
+
+    out = {k: np.zeros(n, dtype=np.int32) for k in ("i1", "i2", "j1", "j2")}
+    out.update({k: np.zeros(n) for k in ("facw", "face", "facs", "facn")})
+    for m in range(n):
+        x0, x1, y0, y1 = (float(a[m]) for a in lim)
+        for lo, hi, length, ax in ((x0, x1, nx * dx, "x"), (y0, y1, ny * dy, "y")):
+            if lo < 0.0 or lo > length or hi < 0.0 or hi > length:
+                raise ValueError("limits outside %s range for %s area m = %d: %r, %r; limits are 0, %r"
+                                 % (ax, fluid, m + 1, lo, hi, length))
+        out["i1"][m], out["facw"][m] = side(x0, dx, True)
+        out["i2"][m], out["face"][m] = side(x1, dx, False)
+        out["j1"][m], out["facs"][m] = side(y0, dy, True)
+        out["j2"][m], out["facn"][m] = side(y1, dy, False)
+        if not (1 <= out["i1"][m] <= nx and 1 <= out["i2"][m] <= nx):
+            raise ValueError("invalid subscript for %s area m = %d: i1, i2 = %d, %d" % (fluid, m + 1, out["i1"][m], out["i2"][m]))
+        if not (1 <= out["j1"][m] <= ny and 1 <= out["j2"][m] <= ny):
+            raise ValueError("invalid subscript for %s area m = %d: j1, j2 = %d, %d" % (fluid, m + 1, out["j1"][m], out["j2"][m]))
+    return out

@@ -131,6 +131,9 @@ SYMBOLS = [
     "qgcm_hip_tavatm_schedule", "qgcm_hip_atnc_sample_len", "qgcm_hip_atnc_sample",
     "qgcm_hip_cov_init", "qgcm_hip_cov_size", "qgcm_hip_cov_add", "qgcm_hip_cov_reset", "qgcm_hip_cov_out",
     "qgcm_hip_cov_schedule", "qgcm_hip_cov_part_len", "qgcm_hip_cov_part", "qgcm_hip_cov_combine",
+    "qgcm_hip_areavg_init", "qgcm_hip_areavg_count", "qgcm_hip_areavg", "qgcm_hip_areavg_part_len", "qgcm_hip_areavg_part",
+    "qgcm_hip_areavg_combine", "qgcm_hip_cfl_len", "qgcm_hip_cfl", "qgcm_hip_cfl_part_len", "qgcm_hip_cfl_part",
+    "qgcm_hip_cfl_combine",
     "qgcm_hip_xforc_init", "qgcm_hip_xforc", "qgcm_hip_xforc_get", "qgcm_hip_coupled_set_xforc",
     "qgcm_hip_aml_init", "qgcm_hip_aml_set_state", "qgcm_hip_aml_get_state", "qgcm_hip_aml", "qgcm_hip_aml_get_diag",
     "qgcm_hip_xforc_heat_init", "qgcm_hip_xforc_heat_get",
@@ -270,6 +273,15 @@ def load_library():
     L.qgcm_hip_cov_part_len.restype = C.c_long
     L.qgcm_hip_cov_part.argtypes = [vp, vp]
     L.qgcm_hip_cov_combine.argtypes = [vp, vp, C.c_int]
+    L.qgcm_hip_areavg_init.argtypes = [vp, C.c_int] + [ip] * 4 + [dp] * 4
+    L.qgcm_hip_areavg.argtypes = [vp, dp, dp, dp]
+    for n in ("qgcm_hip_areavg_count", "qgcm_hip_areavg_part_len", "qgcm_hip_cfl_len", "qgcm_hip_cfl_part_len"):
+        getattr(L, n).argtypes = [vp]
+    L.qgcm_hip_areavg_part.argtypes = [vp, vp]
+    L.qgcm_hip_areavg_combine.argtypes = [vp, vp, C.c_int, dp, dp, dp]
+    L.qgcm_hip_cfl.argtypes = [vp, C.c_double, dp, ip, ip]
+    L.qgcm_hip_cfl_part.argtypes = [vp, C.c_double, vp]
+    L.qgcm_hip_cfl_combine.argtypes = [vp, vp, C.c_int, C.c_double, dp, ip, ip]
     L.qgcm_hip_xforc_init.argtypes = [vp, vp, C.POINTER(XforcParams)]
     L.qgcm_hip_xforc.argtypes = [vp, vp]
     L.qgcm_hip_xforc_get.argtypes = [vp, vp] + [dp] * 11

@@ -292,6 +292,29 @@ def read_covariance(L, h, names, k0=None, count=None):
     return out
 
 
+def set_area_tables(L, h, tables):
+    """qgcm_hip_areavg_init from the dict qgcm_hip.hostinit.area_limits returns."""
+    ii = [np.ascontiguousarray(tables[k], dtype=np.int32) for k in ("i1", "i2", "j1", "j2")]
+    ww = [np.ascontiguousarray(tables[k], dtype=np.float64) for k in ("facw", "face", "facs", "facn")]
+    n = len(ii[0])
+    if any(len(a) != n for a in ii + ww):
+        raise ValueError("set_area_tables: the tables differ in length")
+    ip = C.POINTER(C.c_int)
+    check(L.qgcm_hip_areavg_init(h, n, *[a.ctypes.data_as(ip) for a in ii], *[_dp(a) for a in ww]))
+
+
+def cfl_names(nl):
+    """The quantities of qgcm_hip_cfl in its order: ml_u, ml_v, u1..u<nl>, v1..v<nl>."""
+    return ["ml_u", "ml_v"] + ["u%d" % (k + 1) for k in range(nl)] + ["v%d" % (k + 1) for k in range(nl)]
+
+
+def cfl_dict(cfg, maxima, nbad, loc):
+    """What cfl() returns: maxima, Courant numbers max*dt/dx (formed here, as the reference prints them), the counts
+    of points at or above cflcrit and the 1-based (i, j) of every maximum, arrays over cfl_names(nl)."""
+    return {"names": cfl_names(len(maxima) // 2 - 1), "maxima": maxima, "courant": maxima * cfg.dto / cfg.dxo,
+            "nbad": nbad, "loc": loc.reshape(-1, 2)}
+
+
 class OceanModel:
     """One ocean configuration on one MI355X.
 
@@ -534,6 +557,37 @@ class OceanModel:
         """The ocean variables of MODULE monitor that monnc_comp / couroc compute (src/monitor_data.F:50-71), from
         the device state without pulling it: dict of scalars and per-layer / per-interface numpy arrays."""
         return unpack_monitors(self.monitor_vector(), self.cfg.nlo)
+
+    # -- area averages and the CFL check (`call areavg`, `call cfltry`; DESIGN 6m) ---------------------------------
+    def set_areas(self, xlo=None, xhi=None, ylo=None, yhi=None, tables=None):
+        """The areas of areavg: their limits in metres from the domain's south-west corner, as `areas.limits` gives
+        them (hostinit.read_areas_limits; at most nine), or the finished `tables` of hostinit.area_limits.  Returns
+        the tables (subscripts 1-based, weights)."""
+        if tables is None:
+            from .hostinit import area_limits
+            cfg = self.cfg
+            tables = area_limits(xlo, xhi, ylo, yhi, cfg.dxo, cfg.dyo, cfg.nxto, cfg.nyto,
+                                 fluid="atmos." if getattr(cfg, "atmos", False) else "ocean")
+        set_area_tables(self.L, self.h, tables)
+        return tables
+
+    def area_averages(self, parts=False):
+        """tavoc (tavat on an atmosphere) of one `call areavg`: the weighted averages of sst (ast) at its current
+        level over the areas of set_areas, from the device.  parts: (averages, numerators, denominators) of areint."""
+        n = self.L.qgcm_hip_areavg_count(self.h)
+        avg, num, den = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        check(self.L.qgcm_hip_areavg(self.h, _dp(avg), _dp(num), _dp(den)))
+        return (avg[:n], num[:n], den[:n]) if parts else avg[:n]
+
+    def cfl(self, cflcrit=0.8):
+        """`call cfltry` without its print-out: dict of names, maxima (the largest |u|, |v| of the mixed layer with its
+        Ekman part, then the geostrophic ones per layer), courant = maxima*dt/dx, nbad (the points the reference would
+        list as Bad: Courant number >= cflcrit) and loc (1-based i, j of each maximum, first in scan order)."""
+        nq = self.L.qgcm_hip_cfl_len(self.h)
+        mx, nb, loc = np.zeros(nq), np.zeros(nq, dtype=np.int32), np.zeros(2 * nq, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        check(self.L.qgcm_hip_cfl(self.h, float(cflcrit), _dp(mx), nb.ctypes.data_as(ip), loc.ctypes.data_as(ip)))
+        return cfl_dict(self.cfg, mx, nb, loc)
 
     # -- time averages (avg_ocn_k247 / ocnc_avgout_k247, tavocn / tavout; DESIGN 6f) --------------------------
     def enable_po_mean(self, on=True):

@@ -448,20 +448,49 @@ class HipSlab:
         d = None if dtopoc is None else np.asfortranarray(np.asarray(dtopoc, dtype=np.float64)[:, sl])
         check(self.L.qgcm_hip_set_dtopoc(self.h, _dp(d)))
 
+    def set_areas(self, xlo=None, xhi=None, ylo=None, yhi=None, tables=None):
+        """As OceanModel.set_areas: the areas of the whole basin (global rows), the same on every rank."""
+        from .model import set_area_tables
+        if tables is None:
+            from .hostinit import area_limits
+            cfg = self.cfg
+            tables = area_limits(xlo, xhi, ylo, yhi, cfg.dxo, cfg.dyo, cfg.nxto, cfg.nyto)
+        set_area_tables(self.L, self.h, tables)
+        return tables
+
     def diag_part_len(self, kind):
         return {"monitors": self.L.qgcm_hip_monitor_part_len, "valids": self.L.qgcm_hip_valids_part_len,
-                "prsamp": self.L.qgcm_hip_prsamp_part_len}[kind](self.h)
+                "prsamp": self.L.qgcm_hip_prsamp_part_len, "areavg": self.L.qgcm_hip_areavg_part_len,
+                "cfl": self.L.qgcm_hip_cfl_part_len}[kind](self.h)
 
-    def diag_part(self, kind, send):
+    def diag_part(self, kind, send, cflcrit=0.8):
         """This rank's summary of `kind` -> send (device buffer of diag_part_len(kind) doubles); asynchronous."""
+        if kind == "cfl":
+            check(self.L.qgcm_hip_cfl_part(self.h, float(cflcrit), self._ptr(send)))
+            self._done()
+            return
         fn = {"monitors": self.L.qgcm_hip_monitors_part, "valids": self.L.qgcm_hip_valids_part,
-              "prsamp": self.L.qgcm_hip_prsamp_part}[kind]
+              "prsamp": self.L.qgcm_hip_prsamp_part, "areavg": self.L.qgcm_hip_areavg_part}[kind]
         check(fn(self.h, self._ptr(send)))
         self._done()
 
-    def diag_combine(self, kind, gath):
-        """All ranks' summaries (rank-major) -> the whole-domain call's packed result (valids: (solnok, out))."""
+    def diag_combine(self, kind, gath, cflcrit=0.8):
+        """All ranks' summaries (rank-major) -> the whole-domain call's packed result (valids: (solnok, out); areavg:
+        (averages, numerators, denominators); cfl: the dict of OceanModel.cfl)."""
         nl, P = self.cfg.nlo, self.nranks
+        if kind == "areavg":
+            n = self.L.qgcm_hip_areavg_count(self.h)
+            avg, num, den = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+            check(self.L.qgcm_hip_areavg_combine(self.h, self._ptr(gath), P, _dp(avg), _dp(num), _dp(den)))
+            return avg[:n], num[:n], den[:n]
+        if kind == "cfl":
+            from .model import cfl_dict
+            nq = self.L.qgcm_hip_cfl_len(self.h)
+            mx, nb, loc = np.zeros(nq), np.zeros(nq, dtype=np.int32), np.zeros(2 * nq, dtype=np.int32)
+            ip = C.POINTER(C.c_int)
+            check(self.L.qgcm_hip_cfl_combine(self.h, self._ptr(gath), P, float(cflcrit), _dp(mx), nb.ctypes.data_as(ip),
+                                              loc.ctypes.data_as(ip)))
+            return cfl_dict(self.cfg, mx, nb, loc)
         if kind == "monitors":
             out = np.zeros(self.L.qgcm_hip_monitor_len(self.h))
             check(self.L.qgcm_hip_monitors_combine(self.h, self._ptr(gath), P, _dp(out)))
@@ -670,9 +699,10 @@ class SlabOcean:
             self._halo_pending = False
 
     # diagnostics, collective: every rank calls them between steps() calls and gets the same result --------------
-    def diagnostic(self, kind):
-        """kind = "monitors", "valids" or "prsamp": every local slab writes its summary, one all-gather, every local
-        slab combines the gathered buffer.  Returns the list of the local slabs' results (bitwise the same)."""
+    def diagnostic(self, kind, **kw):
+        """kind = "monitors", "valids", "prsamp", "areavg" or "cfl" (kw: cflcrit): every local slab writes its summary,
+        one all-gather, every local slab combines the gathered buffer.  Returns the list of the local slabs' results
+        (bitwise the same)."""
         S = self.slabs
         bufs = getattr(self, "_diag_bufs", None)
         if bufs is None:
@@ -684,11 +714,11 @@ class SlabOcean:
         send, gath = bufs[kind]
         self._join()  # the halo rows the scans read must be current
         for i, x in enumerate(S):
-            x.diag_part(kind, send[i])
+            x.diag_part(kind, send[i], **kw)
         for x in S:  # the summaries are complete before a transport reads them (LocalComm copies on torch's stream)
             x.sync()
         self._comm(self.comm.all_gather, gath, send)
-        return [x.diag_combine(kind, gath[i]) for i, x in enumerate(S)]
+        return [x.diag_combine(kind, gath[i], **kw) for i, x in enumerate(S)]
 
     def monitors(self):
         """As OceanModel.monitors(): the ocean half of monnc_comp and couroc over the whole basin."""
@@ -703,6 +733,19 @@ class SlabOcean:
         """As OceanModel.prsamp()."""
         from .model import prsamp_dict
         return prsamp_dict(self.diagnostic("prsamp")[0], self.cfg.nlo)
+
+    def set_areas(self, xlo=None, xhi=None, ylo=None, yhi=None, tables=None):
+        """As OceanModel.set_areas, on every local slab."""
+        return [x.set_areas(xlo, xhi, ylo, yhi, tables) for x in self.slabs][0]
+
+    def area_averages(self, parts=False):
+        """As OceanModel.area_averages(): one all-gather of 29 doubles per rank."""
+        r = self.diagnostic("areavg")[0]
+        return r if parts else r[0]
+
+    def cfl(self, cflcrit=0.8):
+        """As OceanModel.cfl(): bitwise the whole-domain result."""
+        return self.diagnostic("cfl", cflcrit=cflcrit)[0]
 
     # time averages (DESIGN 6f): every rank sums its owned rows; a readout assembles the basin with one all-gather
     def _assemble(self, parts):

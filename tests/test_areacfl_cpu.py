@@ -1,0 +1,166 @@
+"""The numpy restatement of areavg and cfltry (tests/numpy_areacfl.py) and hostinit's set-up arithmetic against the
+reference's own results (tests/golden/areacfl_*.npz, written by tests/golden/make_golden_areacfl.py), the geometry the
+cases were shaped for, the new symbols and the new kernels' resources.  No GPU."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import numpy_areacfl as na
+from qgcm_hip import hostinit, lib
+
+FLUIDS = ("oc", "at")
+NEW = ("qgcm_hip_areavg_init", "qgcm_hip_areavg_count", "qgcm_hip_areavg", "qgcm_hip_areavg_part_len",
+       "qgcm_hip_areavg_part", "qgcm_hip_areavg_combine", "qgcm_hip_cfl_len", "qgcm_hip_cfl", "qgcm_hip_cfl_part_len",
+       "qgcm_hip_cfl_part", "qgcm_hip_cfl_combine")
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64)
+
+
+@pytest.mark.parametrize("fluid", FLUIDS)
+@pytest.mark.parametrize("case", na.CASES)
+def test_areavg_restatement_is_bitwise(case, fluid):
+    g = na.load(case)
+    T = na.tables(g, fluid)
+    avg = na.areavg(g["in_sst" if fluid == "oc" else "in_ast"], T)[0]
+    ref = g[fluid + "_tav"]
+    assert np.all(np.isfinite(ref)) and avg.shape == ref.shape
+    assert np.array_equal(_bits(avg), _bits(ref)), (case, fluid, avg - ref)
+
+
+@pytest.mark.parametrize("fluid", FLUIDS)
+@pytest.mark.parametrize("case", na.CASES)
+def test_area_tables_match_the_print_out(case, fluid):
+    """The T subscripts exactly, the weights at the three decimals the reference prints."""
+    g = na.load(case)
+    T = na.tables(g, fluid)
+    got = np.stack([T[k] for k in ("i1", "i2", "j1", "j2")], axis=1)
+    assert np.array_equal(got, g[fluid + "_it"]), (case, fluid)
+    w = np.stack([T[k] for k in ("facw", "face", "facs", "facn")], axis=1)
+    assert np.all(np.abs(w - g[fluid + "_wt"]) <= 0.5e-3 + 1e-12), (case, fluid, w, g[fluid + "_wt"])
+
+
+@pytest.mark.parametrize("fluid", FLUIDS)
+@pytest.mark.parametrize("case", na.CASES)
+def test_cfltry_restatement(case, fluid):
+    """Maxima and Courant numbers to half a unit of the eighth significant digit (what `1p,9d15.7` prints, so a
+    contraction in the reference build could not be told from it); the Bad lines exactly: quantity, i, j in print order,
+    their values at printed precision."""
+    g = na.load(case)
+    R = na.cfl_of_fixture(g, fluid)
+    for got, ref in ((R["maxima"], g[fluid + "_max"]), (R["courant"], g[fluid + "_cfl"])):
+        assert np.all(np.abs(got - ref) <= 0.5e-7 * 10.0 ** np.floor(np.log10(np.abs(ref))) * (1 + 1e-9)), (case, fluid, got, ref)
+    bad = g[fluid + "_bad"]
+    assert np.array_equal(R["bad"][:, :3], bad[:, :3]), (case, fluid)
+    assert np.all(np.abs(R["bad"][:, 3] - bad[:, 3]) <= 0.5e-7 * 10.0 ** np.floor(np.log10(bad[:, 3])) * (1 + 1e-9))
+    assert np.array_equal(R["nbad"], [(bad[:, 0] == q).sum() for q in range(len(R["nbad"]))])
+    # the location of every maximum that has Bad lines: the first of them with the largest value
+    for q in np.nonzero(R["nbad"])[0]:
+        rows = R["bad"][R["bad"][:, 0] == q]
+        assert tuple(rows[np.argmax(rows[:, 3]), 1:3]) == tuple(R["loc"][q])
+
+
+def test_case_geometry():
+    """What the shapes were chosen for: one wave strides an area's row segment in rounds of 64 columns; the CFL scan
+    uses 64 x 16 tiles (k_areacfl.h)."""
+    g = na.load("area_box")
+    T = na.tables(g, "oc")
+    nxto, nyto = g["in_sst"].shape
+    assert (nxto, nyto) == (300, 40) and len(T["i1"]) == 9 == hostinit.AREAS_MAX
+    assert (T["i1"][0], T["i2"][0], T["j1"][0], T["j2"][0]) == (1, nxto, 1, nyto)
+    assert all(T[k][m] == 1.0 for k in ("facw", "face", "facs", "facn") for m in (0, 1))  # edges: >= bumps i1, > keeps i2
+    w = [T[k][2] for k in ("facw", "face", "facs", "facn")]
+    assert len(set(w)) == 4 and all(0.0 < v < 1.0 for v in w)
+    assert T["j1"][3] == T["j2"][3] and T["i1"][4] == T["i2"][4]
+    assert T["i2"][5] - T["i1"][5] + 1 > 256 and T["i2"][6] - T["i1"][6] + 1 == 3
+    assert T["i1"][7] < T["i1"][8] <= T["i2"][7] and T["j1"][7] < T["j1"][8] <= T["j2"][7]  # overlap
+    g = na.load("area_atm")
+    assert g["in_ast"].shape == (72, 24) and len(g["at_tav"]) == 5 and len(g["oc_tav"]) == 1
+    T = na.tables(g, "at")
+    assert T["i1"][3] == T["i2"][3] and T["j1"][3] == T["j2"][3]  # one cell: both weights on it, both rows contribute
+    for case, fluid, shape in (("cfl_box", "oc", (97, 41, 3)), ("cfl_cyc", "oc", (129, 25, 3)), ("cfl_atm", "at", (33, 13, 3))):
+        g = na.load(case)
+        assert g["in_po" if fluid == "oc" else "in_pa"].shape == shape
+    g = na.load("cfl_box")
+    R = na.cfl_of_fixture(g, "oc")
+    cnt = R["nbad"]
+    assert all(1 <= c <= 50 for c in cnt[cnt > 0]) and (cnt[:2] > 0).any() and (cnt[2:] > 0).any() and (cnt == 0).any()
+    names = R["names"]
+    assert R["loc"][names.index("v2")][1] == 41 and R["loc"][names.index("u2")][1] == 40  # the last scanned rows
+    i, j = R["loc"][names.index("u1")]
+    assert i in (64, 65) and j in (16, 17)  # at the seam of the first tiles
+    p = na.load("cfl_cyc")["in_po"]
+    assert np.array_equal(p[0], p[-1])
+    bad = na.cfl_of_fixture(na.load("cfl_cyc"), "oc")["bad"]
+    assert 128 in bad[bad[:, 0] == names.index("v1"), 1]  # an offender whose +i neighbour is the one-point third tile
+    assert 129 in bad[bad[:, 0] == names.index("u1"), 1]  # and one inside it
+
+
+def test_read_areas_limits(tmp_path):
+    g = na.load("area_atm")
+    A = hostinit.read_areas_limits(os.path.join(na.GOLDEN, "areas_limits_area_atm.txt"))
+    assert A["ocean"]["n"] == 1 and A["atmos"]["n"] == 5
+    assert A["ocean"]["names"] == ["oc1"] and A["atmos"]["names"] == ["at%d" % m for m in range(1, 6)]
+    for fluid, key in (("ocean", "oc_lim"), ("atmos", "at_lim")):
+        got = np.stack([A[fluid][k] for k in ("xlo", "xhi", "ylo", "yhi")], axis=1)
+        assert np.array_equal(got, g[key])
+    # the reference's sample: D exponents, trailing !! comments, text after the last record
+    p = tmp_path / "areas.limits"
+    p.write_text("   2                     !!nareoc\n      0.0d3    400.0d3  !!xlooc (m)\n 400.0d3, 8.0D5\n"
+                 "  0.0d3\n 0.0d3\n   400.0d3    400.0d3    !!yhioc\n        oc1        abc    !!areaoc\n"
+                 "   1\n 0.0\n 7680.0d3\n 1440.0d3\n 6240.0d3\n        at1\nSpecify NAREOC ocean subareas\n")
+    A = hostinit.read_areas_limits(str(p))
+    assert list(A["ocean"]["xlo"]) == [0.0, 400.0e3] and list(A["ocean"]["xhi"]) == [400.0e3, 800.0e3]
+    assert list(A["ocean"]["ylo"]) == [0.0, 0.0] and A["ocean"]["names"] == ["oc1", "abc"]
+    assert A["atmos"]["yhi"][0] == 6240.0e3
+    p.write_text("  10\n")
+    with pytest.raises(ValueError, match="10"):
+        hostinit.read_areas_limits(str(p))
+
+
+def test_area_limits_refusals():
+    with pytest.raises(ValueError, match="outside x range for ocean area m = 2"):
+        hostinit.area_limits([0.0, 10.0], [50.0, 101.0], [0.0, 0.0], [50.0, 50.0], 10.0, 10.0, 10, 5)
+    with pytest.raises(ValueError, match="outside y range for atmos. area m = 1"):
+        hostinit.area_limits([0.0], [50.0], [-1.0], [50.0], 10.0, 10.0, 10, 5, fluid="atmos.")
+    with pytest.raises(ValueError, match="10 areas"):
+        hostinit.area_limits(*[[0.0] * 10] * 4, 10.0, 10.0, 10, 5)
+
+
+def test_symbols_declared_bound_and_exported(repo_root):
+    hdr = open(os.path.join(repo_root, "include", "qgcm_hip.h")).read()
+    f90 = open(os.path.join(repo_root, "q-gcm_amd", "fortran", "qgcm_hip_iface.F90")).read()
+    path = lib.library_path()
+    assert os.path.exists(path), "libqgcm_hip.so not built"
+    L = ctypes.CDLL(path)
+    for s in NEW:
+        assert re.search(r"\b%s\s*\(" % s, hdr), s
+        assert s in lib.SYMBOLS, s
+        assert "bind(C, name='%s')" % s in f90, s
+        assert hasattr(L, s), s
+    assert "#define QGCM_HIP_ABI_VERSION 3" in hdr and lib.ABI_VERSION == 3
+
+
+def test_new_kernels_use_no_scratch(repo_root):
+    path = os.path.join(repo_root, "q-gcm_amd", "lib", "kernel_resources.txt")
+    assert os.path.exists(path), "kernel_resources.txt missing - rebuild with `make -C q-gcm_amd/csrc`"
+    res, cur = {}, None
+    for line in open(path):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and cur:
+            res[cur] = int(m.group(1))
+    want = ["_Z11k_arav_rows", "_Z11k_arav_partILb0E", "_Z11k_arav_partILb1E", "_Z14k_arav_combine", "_Z11k_cfl_finalILb0E",
+            "_Z11k_cfl_finalILb1E", "_Z13k_cfl_combine"]
+    want += ["_Z10k_cfl_scanILi%dELb%dE" % (nl, a) for nl in range(2, 9) for a in (0, 1)]
+    for w in want:
+        hits = [k for k in res if k.startswith(w)]
+        assert hits, "kernel %s not in the report" % w
+        for k in hits:
+            assert res[k] == 0, "%s uses %d B of scratch per lane" % (k, res[k])
