@@ -145,6 +145,13 @@ int qgcm_hip_get_state(qgcm_hip_handle h, double *po, double *pom, double *qo, d
 /* wekpo(nxpo,nypo), entoc(nxpo,nypo), xon(nlo-1)  (written by xforc / oml) */
 int qgcm_hip_set_forcing(qgcm_hip_handle h, const double *wekpo, const double *entoc,
                          const double *xon);
+/* Which fields the next tendency launch of the handle leaves out because the library knows them to hold +0.0
+ * everywhere: bit 0 = entoc (entat), bit 1 = ddynoc; 0 = both are read; -1 for a NULL handle.  The library scans the
+ * host arrays of qgcm_hip_set_forcing / _set_geometry / _set_grid (bit patterns: a -0.0 counts as non-zero) and knows
+ * that a fresh handle's buffers are zero; a mixed layer on the device (qgcm_hip_oml_init / _aml_init) writes entoc
+ * every step, which clears bit 0 for good.  The results do not depend on the mask, bit for bit;
+ * QGCM_HIP_READ_ZERO_FIELDS=1 (read by qgcm_hip_create) keeps it at 0, as does nlo > 4. */
+int qgcm_hip_tend_zero_mask(qgcm_hip_handle h);
 /* The fork's sponge layer (cpp option sponge_layer_k247): the leapfrog step of qgostep gains
  *   + tdto*c1_spl*r_spl(i,j)*(qom(i,j,k) - beta*yporel(j))            src/qgosubs.F:203-205
  * r_spl(nxpo,nypo): the ramp of MODULE occonst (src/occonst_data.F:100-105) as the main program sets it

@@ -26,7 +26,10 @@
 // Algorithmic HBM traffic: read pom,po,qo,qom (4 nl) + wekpo,entoc,ddynoc (3),
 // write qo (nl) + wrk (nl)  ->  (6 nl + 3) N doubles = 21 N for nl = 3
 // (SURVEY 8d counts 24 N because the reference also rewrites qom; here the
-// q buffers rotate instead).
+// q buffers rotate instead).  Where the host knows entoc and / or ddynoc to be
+// all zero, k_tend_z does not read them: 19 N with both zero (flat bottom,
+// mixed layer off - the flagship), 20 N with one.
+// The kernels' body is k_tend_body.inc (shared by k_tend and k_tend_z).
 #pragma once
 #include "qgcm_dev.h"
 #include "k_misc.h" // constr_dpi_update
@@ -157,7 +160,8 @@ __device__ __forceinline__ void tend_point(const QgTendParams &P, int gi, int gj
 
 // Edge work of the box ocean: the E wall column (dqdt = 0, qgosubs.F:371,397; Del^2 of the bottom layer by
 // the wall rule :112,125) and the N wall row (not stepped), one point per thread.
-template <int NL, bool AVG = false>
+// ZM: the zero-field mask of k_tend_z below (bit 0: entoc, bit 1: ddynoc are all zero and not read).
+template <int NL, bool AVG = false, int ZM = 0>
 __device__ __forceinline__ void tend_edge(const QgTendParams &P, const TendTiling &T, int eblock) {
   const QgGeom &g = P.g;
   const int rows = g.jhi - g.jlo + 1;
@@ -187,8 +191,8 @@ __device__ __forceinline__ void tend_edge(const QgTendParams &P, const TendTilin
     const double *pb = P.pom + fs * (NL - 1) + o;
     d2bot = P.bcfaco * (pb[-1] - pb[0]);
     wek = P.wekpo[o];
-    ent = P.entoc[o];
-    ddy = P.ddynoc[o];
+    if (!(ZM & 1)) ent = P.entoc[o];
+    if (!(ZM & 2)) ddy = P.ddynoc[o];
   }
   tend_point<NL, false, false, AVG>(P, gi, gj, dq, d2bot, qm, qo, wek, ent, ddy);
 }
@@ -206,275 +210,18 @@ template <int NL, bool CYC, bool WTQ, bool AVG = false>
 #endif
 __global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_WAVES_PER_EU) void k_tend(QG_TEND_ARGS, const QgTendParams P,
                                                                      const QgCycSumParams S, const QgOmlFinal F) {
-  QG_STAMP(3, 10);
-#ifndef TEND_EXPERIMENT // (tile-shape A/B builds without the mixed layer: profiles/r4_tend_shapes_socn5.log)
-  static_assert(TEND_NT == OML_NT, "oml_final_block runs in workgroup 0 of this kernel");
-#endif
-  constexpr int TX = WTQ ? TEND_TX : TEND_TX_WIDE, TY = TEND_TY;
-  static_assert(TEND_NT % TX == 0 && TY % (TEND_NT / TX) == 0, "whole rows of threads, whole rows per thread");
-  constexpr int W3 = TX + 6, H3 = TY + 6; // pom tile, halo 3
-  constexpr int W2 = TX + 4, H2 = TY + 4; // d2 tile, halo 2
-  constexpr int W1 = TX + 2, H1 = TY + 2; // d4 / po / qo tiles, halo 1
-  constexpr int N3 = (H3 * W3 + TEND_NT - 1) / TEND_NT; // staged elements per thread
-  constexpr int N1 = (H1 * W1 + TEND_NT - 1) / TEND_NT;
-  __shared__ double sp[H3 * W3];
-  __shared__ double sd2[H2 * W2];
-  // Del^4 tile: lives in the pom tile's storage (dead once Del^2 is formed; refilled only after the layer's
-  // last barrier), which keeps the workgroup at 4 x 30 KB (TY = 8) resp. 3 x 51 KB (TY = 20) per CU
-  double *sd4 = sp;
-  static_assert(H1 * W1 <= H3 * W3, "Del^4 tile must fit into the pom tile");
-  __shared__ double spo[H1 * W1];
-  __shared__ double sqo[H1 * W1];
+  constexpr int ZM = 0; // reads entoc and ddynoc
+#include "k_tend_body.inc"
+}
 
-  // nx .. jhi (slab view: global row = local + joff), the row window and `side` are leading scalar arguments, preloaded
-  // into SGPRs (QG_TEND_ARGS, qgcm_dev.h): the tile mapping and the staging offsets below wait for no scalar load
-  const double *po0 = P.po, *qo0 = P.qo; // (requested here: they arrive while the offsets are formed)
-  const long fs = P.g.fstride;
-  const int tid = threadIdx.x;
-  // ---- XCD-aware tile numbering ------------------------------------------
-  // Box grids have nx = 64*g + 1 columns and (whole basin) 8*h + 1 rows: the last column and the last
-  // row are walls whose update is point-wise (no stencil), so they are peeled off into a few "edge"
-  // workgroups instead of a whole extra column / row of nearly empty tiles (tend_edge below).
-  QgGeom gt; // what tend_tiling reads
-  gt.nx = nx; gt.jlo = jlo; gt.jhi = jhi; gt.joff = joff; gt.nyg = nyg;
-  const TendTiling T = tend_tiling<CYC, TX>(gt);
-  const int gx = T.gx;
-  const int ntiles = gx * (trows ? trows : T.gy); // (a window of the tile rows, or all of them)
-  const int per_xcd = (ntiles + 7) / 8;
-  if ((side & 1) && blockIdx.x == 0) {
-    // mixed layer on, inside qgcm_hip_steps: the last reduction of `oml` (xon(1), enisoc(1) / eninoc(1), monitors) is
-    // done here instead of in a one-workgroup launch; xon must be final before dpioc is stepped below
-    __shared__ double redf[20];
-    oml_final_block(F, redf, tid);
-  }
-  if (!CYC && (side & 2) && blockIdx.x == 0 && tid == 0) constr_dpi_update<NL>(P.sc, P.tdto, P.gpoc); // see QgTendParams
-  if ((int)blockIdx.x >= 8 * per_xcd) {
-    // cyclic / atmosphere: the boundary line sums for the momentum constraints (k_cyclic.h); box: the wall edges
-    if (CYC) cyc_bsums_block(S, (int)blockIdx.x - 8 * per_xcd);
-    else tend_edge<NL, AVG>(P, T, (int)blockIdx.x - 8 * per_xcd);
-    return;
-  }
-  const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  if (tile >= ntiles) return;
-  QG_STAMP(3, 0);
-  const int i0 = (tile % gx) * TX + 1; // first global i of the tile (1-based)
-  const int trow = trows ? trow0 + (tile / gx) * tstride : tile / gx;
-  const int j0 = trow * TY + jlo; // first local row of the tile
-  const int tx = tid % TX;
-  const int ty0 = tid / TX; // 0..3
-  constexpr int RPT = TY / (TEND_NT / TX); // rows per thread
-  const double bcf = P.bcfaco, dxom2 = P.dxom2;
-
-  // ---- global offsets of the elements this thread stages (same for every layer), computed ONCE: 32-bit element
-  // offsets (the host checks ldx*ny*nl < 2^31) clamped to 0 where the element lies outside the array, plus a
-  // validity bit. Every staging load is then unconditional: a "load or zero" conditional makes hipcc branch around
-  // each load (exec-mask save / restore, s_cbranch_execz: ~560 of the kernel's 1900 instructions were that
-  // bookkeeping, and the kernel is instruction-issue bound). Elements outside the array receive element 0 of the
-  // field - a finite value that no point inside the domain ever reads.
-  int o3[N3], o1[N1];
-  bool v3[N3], v1[N1];
-#pragma unroll
-  for (int e = 0; e < N3; ++e) {
-    int idx = tid + e * TEND_NT;
-    int lx = idx % W3, ly = idx / W3;
-    int gi = i0 - 3 + lx, gj = j0 - 3 + ly;
-    v3[e] = idx < H3 * W3 && gj >= 1 && gj <= ny && (CYC ? (gi >= -2 && gi <= nx + 3) : (gi >= 1 && gi <= nx));
-    o3[e] = v3[e] ? (gj - 1) * ldx + (tend_wrap<CYC>(gi, nxt) - 1) : 0;
-  }
-#pragma unroll
-  for (int e = 0; e < N1; ++e) {
-    int idx = tid + e * TEND_NT;
-    int lx = idx % W1, ly = idx / W1;
-    int gi = i0 - 1 + lx, gj = j0 - 1 + ly;
-    v1[e] = idx < H1 * W1 && gj >= 1 && gj <= ny && (CYC ? (gi >= 0 && gi <= nx + 1) : (gi >= 1 && gi <= nx));
-    o1[e] = v1[e] ? (gj - 1) * ldx + (tend_wrap<CYC>(gi, nxt) - 1) : 0;
-  }
-  double r3[N3], rp[N1], rq[N1];
-  QG_STAMP(3, 11);
-#pragma unroll
-  for (int e = 0; e < N3; ++e) r3[e] = pom[o3[e]];
-#pragma unroll
-  for (int e = 0; e < N1; ++e) {
-    rp[e] = po0[o1[e]];
-    rq[e] = qo0[o1[e]];
-  }
-  // ---- the Del^2 / Del^4 passes of this thread (elements tid, tid + 256, ... of the halo-2 / halo-1 region): the LDS
-  // read base, the position of the ONE inner neighbour the wall rule uses (N of a S-wall point, ...) and whether the
-  // point is a wall point do not depend on the layer - computed once.  Points outside the domain are computed from
-  // whatever the (clamped) loads delivered: no point inside the domain ever reads them (interior points have all five
-  // neighbours inside, wall points read their inner neighbour only), so they need neither a predicate nor a select.
-  constexpr int N2 = (H2 * W2 + TEND_NT - 1) / TEND_NT;
-  int b2[N2], b4[N1], i2[N2], i4[N1];
-  bool w2[N2], w4[N1];
-#pragma unroll
-  for (int e = 0; e < N2; ++e) {
-    const int idx = tid + e * TEND_NT;
-    const int lx = idx % W2, ly = idx / W2;
-    const int gi = i0 - 2 + lx, gj = j0 - 2 + ly;
-    const bool inx = CYC ? (gi >= -1 && gi <= nx + 2) : (gi >= 1 && gi <= nx);
-    (void)inx;
-    b2[e] = (idx < H2 * W2) ? (ly + 1) * W3 + (lx + 1) : W3 + 1; // clamped: the extra pass reads valid LDS, stores nothing
-    const bool wS = (gj + joff == 1), wN = (gj + joff == nyg), wW = (!CYC && gi == 1), wE = (!CYC && gi == nx);
-    w2[e] = wS || wN || wW || wE;
-    i2[e] = b2[e] + (wS ? W3 : (wN ? -W3 : (wW ? 1 : -1)));
-  }
-#pragma unroll
-  for (int e = 0; e < N1; ++e) {
-    const int idx = tid + e * TEND_NT;
-    const int lx = idx % W1, ly = idx / W1;
-    const int gi = i0 - 1 + lx, gj = j0 - 1 + ly;
-    const bool inx = CYC ? (gi >= 0 && gi <= nx + 1) : (gi >= 1 && gi <= nx);
-    (void)inx;
-    b4[e] = (idx < H1 * W1) ? (ly + 1) * W2 + (lx + 1) : W2 + 1;
-    const bool wS = (gj + joff == 1), wN = (gj + joff == nyg), wW = (!CYC && gi == 1), wE = (!CYC && gi == nx);
-    w4[e] = wS || wN || wW || wE;
-    i4[e] = b4[e] + (wS ? W2 : (wN ? -W2 : (wW ? 1 : -1)));
-  }
-  // ---- epilogue operands of this thread's own points: requested while the LAST layer is computed (the
-  // registers of the layer prefetch are free by then); the old qo of the wall rows is read in the epilogue
-  double e_qm[NL][RPT], e_wek[RPT], e_ent[RPT], e_ddy[RPT];
-  double e_qo[AVG ? NL : 1][RPT]; // AVG: this step's qo of the thread's own points
-
-  double dq[NL][RPT];
-  double d2bot[RPT];
-
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    // ---- registers -> LDS tiles of layer k --------------------------------
-#pragma unroll
-    for (int e = 0; e < N3; ++e) {
-      int idx = tid + e * TEND_NT;
-      if (idx < H3 * W3) sp[idx] = r3[e];
-    }
-#pragma unroll
-    for (int e = 0; e < N1; ++e) {
-      int idx = tid + e * TEND_NT;
-      if (idx < H1 * W1) {
-        spo[idx] = rp[e];
-        sqo[idx] = rq[e];
-      }
-    }
-    __syncthreads();
-    QG_STAMP(3, 1 + 2 * k);
-    // ---- issue the loads of layer k+1 (they fly while layer k is computed)
-    if (k + 1 < NL) {
-      const double *pomk = pom + fs * (k + 1);
-      const double *po = po0 + fs * (k + 1);
-      const double *qo = qo0 + fs * (k + 1);
-#pragma unroll
-      for (int e = 0; e < N3; ++e) r3[e] = pomk[o3[e]];
-#pragma unroll
-      for (int e = 0; e < N1; ++e) {
-        rp[e] = po[o1[e]];
-        rq[e] = qo[o1[e]];
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-        int ly = ty0 + r * (TEND_NT / TX);
-        int gi = i0 + tx, gj = j0 + ly;
-        bool in = gi <= T.imax && gj <= T.jmax;
-        const int o = in ? (gj - 1) * ldx + (gi - 1) : 0; // clamped: unconditional loads, values unused when !in
-        e_wek[r] = P.wekpo[o];
-        e_ent[r] = P.entoc[o];
-        e_ddy[r] = P.ddynoc[o];
-#pragma unroll
-        for (int kk = 0; kk < NL; ++kk) e_qm[kk][r] = P.qnew[fs * kk + o];
-        if (AVG) {
-#pragma unroll
-          for (int kk = 0; kk < NL; ++kk) e_qo[kk][r] = P.qo[fs * kk + o];
-        }
-      }
-    }
-    // ---- Del^2(pom) on the halo-2 region (qgosubs.F:94-127) ----------
-#pragma unroll
-    for (int e = 0; e < N2; ++e) {
-      const int idx = tid + e * TEND_NT;
-      const double *c = &sp[b2[e]];
-      // branch-free: the wall rule picks ONE inner neighbour (N, S, E or W of a wall point), the interior rule is
-      // evaluated alongside and the result selected - same expressions, same rounding, no exec-mask bookkeeping
-      const double cS = c[-W3], cW = c[-1], c0 = c[0], cE = c[1], cN = c[W3];
-      const double vw = bcf * (sp[i2[e]] - c0);
-      const double vi = (cS + cW + cE + cN - 4.0 * c0) * dxom2;
-      if (idx < H2 * W2) sd2[idx] = w2[e] ? vw : vi;
-    }
-    __syncthreads();
-    // ---- Del^4 on the halo-1 region (qgosubs.F:310-341) ---------------
-#pragma unroll
-    for (int e = 0; e < N1; ++e) {
-      const int idx = tid + e * TEND_NT;
-      const double *c = &sd2[b4[e]];
-      const double cS = c[-W2], cW = c[-1], c0 = c[0], cE = c[1], cN = c[W2];
-      const double vw = bcf * (sd2[i4[e]] - c0);
-      const double vi = dxom2 * (cS + cW + cE + cN - 4.0 * c0);
-      if (idx < H1 * W1) sd4[idx] = w4[e] ? vw : vi;
-    }
-    __syncthreads();
-    // ---- Del^6 + Jacobian at the tile's own points (qgosubs.F:349-399)
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-      int ly = ty0 + r * (TEND_NT / TX);
-      int gi = i0 + tx, gj = j0 + ly;
-      double val = 0.0;
-      bool interior = (gj <= jhi && gj + joff >= 2 && gj + joff <= nyg - 1) && (CYC ? (gi >= 1 && gi <= nx) : (gi >= 2 && gi <= nx - 1));
-      if (interior) {
-        const double *d4 = &sd4[(ly + 1) * W1 + (tx + 1)];
-        const double *p = &spo[(ly + 1) * W1 + (tx + 1)];
-        const double *q = &sqo[(ly + 1) * W1 + (tx + 1)];
-        double d6p = dxom2 * (d4[-W1] + d4[-1] + d4[1] + d4[W1] - 4.0 * d4[0]);
-        double diffus = P.ah2fac[k] * d4[0] - P.ah4fac[k] * d6p;
-        double jac = (q[1] - q[-1]) * (p[W1] - p[-W1]) + (q[-W1] - q[W1]) * (p[1] - p[-1]) +
-                     q[1] * (p[W1 + 1] - p[-W1 + 1]) - q[-1] * (p[W1 - 1] - p[-W1 - 1]) -
-                     q[W1] * (p[W1 + 1] - p[W1 - 1]) + q[-W1] * (p[-W1 + 1] - p[-W1 - 1]) +
-                     p[W1] * (q[W1 + 1] - q[W1 - 1]) - p[-W1] * (q[-W1 + 1] - q[-W1 - 1]) -
-                     p[1] * (q[W1 + 1] - q[-W1 + 1]) + p[-1] * (q[W1 - 1] - q[-W1 - 1]);
-        val = P.adfaco * jac + diffus;
-      }
-      dq[k][r] = val;
-      if (k == NL - 1) d2bot[r] = sd2[(ly + 2) * W2 + (tx + 2)];
-    }
-    QG_STAMP(3, 2 + 2 * k);
-    if (k + 1 < NL) __syncthreads();
-  }
-
-  // ---- forcing, bottom drag, leapfrog, projection ----------------------
-  if (WTQ) {
-    // (every lane goes through: the stores are pairs of neighbouring lanes; points outside the tile's part of the
-    //  domain compute on clamped operands and store nothing)
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-      int ly = ty0 + r * (TEND_NT / TX);
-      const int gi0 = i0 + tx, gj0 = j0 + ly;
-      const bool valid = gi0 <= T.imax && gj0 <= T.jmax;
-      const int gi = valid ? gi0 : (gi0 <= T.imax ? gi0 : T.imax), gj = gj0 <= T.jmax ? gj0 : T.jmax;
-      double dqp[NL], qmp[NL], qop[NL];
-      const bool wallrow = (gj + joff == 1 || gj + joff == nyg);
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        dqp[k] = dq[k][r];
-        qmp[k] = e_qm[k][r];
-        qop[k] = AVG ? e_qo[AVG ? k : 0][r] : (wallrow ? P.qo[fs * k + (long)(gj - 1) * ldx + (gi - 1)] : 0.0);
-      }
-      tend_point<NL, CYC, true, AVG>(P, gi0, gj, dqp, d2bot[r], qmp, qop, e_wek[r], e_ent[r], e_ddy[r], valid);
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-      int ly = ty0 + r * (TEND_NT / TX);
-      int gi = i0 + tx, gj = j0 + ly;
-      if (gi > T.imax || gj > T.jmax) continue;
-      double dqp[NL], qmp[NL], qop[NL];
-      const bool wallrow = (gj + joff == 1 || gj + joff == nyg);
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        dqp[k] = dq[k][r];
-        qmp[k] = e_qm[k][r];
-        qop[k] = AVG ? e_qo[AVG ? k : 0][r] : (wallrow ? P.qo[fs * k + (long)(gj - 1) * ldx + (gi - 1)] : 0.0);
-      }
-      tend_point<NL, CYC, false, AVG>(P, gi, gj, dqp, d2bot[r], qmp, qop, e_wek[r], e_ent[r], e_ddy[r]);
-    }
-  }
-  QG_STAMP(3, 7);
-  QG_STAMP_DRAIN();
-  QG_STAMP(3, 8);
+// Zero-field variants: the same kernel for a handle whose entoc (ZM bit 0) and / or ddynoc (ZM bit 1) is known on the
+// host to be all +0.0 (qgcm_hip.hip: tend_zmask).  A field whose bit is set is neither loaded nor given a prefetch
+// register; the epilogue computes with a literal 0.0 in its place, expression by expression as written in tend_point,
+// so signed zeros and rounding are the reading kernel's.  A second kernel name: k_tend<NL, CYC, WTQ, AVG> keeps its
+// name, its template list and its code (ZM = 0).  Instantiated for NL = 2, 3, 4; NL > 4 keeps reading the fields.
+template <int NL, bool CYC, bool WTQ, bool AVG, int ZM>
+__global__ __launch_bounds__(TEND_NT, (WTQ && NL <= 4) ? TEND_WAVES_WTQ : TEND_WAVES_PER_EU) void k_tend_z(QG_TEND_ARGS, const QgTendParams P,
+                                                                       const QgCycSumParams S, const QgOmlFinal F) {
+  static_assert(ZM >= 1 && ZM <= 3 && NL <= 4, "ZM = 0 is k_tend");
+#include "k_tend_body.inc"
 }

@@ -175,6 +175,11 @@ struct qgcm_hip_ctx {
   bool avg_now = false;   // one_step: this step's kernels store the averaged time level (k_tend, k_dst64_unpack)
   bool no_fused_constr;   // QGCM_HIP_NO_FUSED_CONSTR=1: keep the k_constr_box launch inside qgcm_hip_steps (A/B + tests)
   bool tend_wide;         // QGCM_HIP_TEND_WIDE=1: the tendency kernel's HBM-bound instantiation (32-wide tiles, plain stores) at any size (tests)
+  // The device buffer holds +0.0 everywhere (bit patterns: -0.0 does not count), known on the host: set by the zero fill
+  // of the allocation and by the scan of every host array handed in (set_forcing; set_geometry / set_grid), cleared by
+  // every device-side writer of entoc (the mixed layers).  tend_zmask turns them into k_tend_z's ZM.
+  bool entoc_zero = false, ddynoc_zero = false;
+  bool read_zero_fields;  // QGCM_HIP_READ_ZERO_FIELDS=1: the tendency kernel reads entoc and ddynoc whatever they hold (A/B + tests)
   std::vector<double> bd2oc;
   // profiling
   hipError_t timer_err = hipSuccess;
@@ -360,6 +365,24 @@ static int download2d(qgcm_hip_ctx *c, double *dst, const double *src, int ld, i
   return 0;
 }
 
+// every element of a host array is +0.0 (bit patterns: -0.0 is not, the kernels' arithmetic tells the two apart)
+static bool all_plus_zero(const double *a, size_t n) {
+  unsigned long long any = 0;
+  for (size_t i = 0; i < n; ++i) {
+    unsigned long long b;
+    memcpy(&b, a + i, sizeof(b));
+    any |= b;
+  }
+  return any == 0;
+}
+
+// k_tend_z's mask for the next tendency launch: bit 0 = entoc, bit 1 = ddynoc need not be read (k_tend.h).  Every
+// launch goes through launch_tend, which asks here; the graph keys carry the mask (get_graph, get_slab_graph).
+static int tend_zmask(const qgcm_hip_ctx *c) {
+  if (c->read_zero_fields || c->g.nl > 4) return 0;
+  return (c->entoc_zero && !c->oml.on && !c->aml.on ? 1 : 0) | (c->ddynoc_zero ? 2 : 0);
+}
+
 static int dalloc(double **p, size_t n) {
   HIPCHECK(hipMalloc((void **)p, n * sizeof(double)));
   // The zero fill runs on the NULL stream, and a device memset need not have finished when hipMemset returns; the
@@ -439,6 +462,7 @@ extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, i
   }
   c->ip = c->iq = 0;
   if (dalloc(&c->wekpo, F) || dalloc(&c->entoc, F) || dalloc(&c->ddynoc, F)) return 1;
+  c->entoc_zero = c->ddynoc_zero = true; // (dalloc fills with zeros)
   if (dalloc(&c->ochom, F * (g.nl - 1))) return 1;
   if (dalloc(&c->yporel, g.ny)) return 1;
   if (dalloc(&c->wrk, W * g.nl)) return 1;
@@ -465,6 +489,8 @@ extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, i
     c->tend_wide = tw && tw[0] == '1';
     const char *fa = getenv("QGCM_HIP_NO_FUSED_AVG");
     c->no_fused_avg = fa && fa[0] == '1';
+    const char *rz = getenv("QGCM_HIP_READ_ZERO_FIELDS");
+    c->read_zero_fields = rz && rz[0] == '1';
   }
   c->profiling = false;
   HIPCHECK(hipEventCreate(&c->ev0));
@@ -832,7 +858,9 @@ extern "C" int qgcm_hip_set_geometry(qgcm_hip_handle c, const double *yporel, co
   drop_graphs(c);
   HIPCHECK(hipMemcpy(c->yporel, yporel, sizeof(double) * g.ny, hipMemcpyHostToDevice));
   if (ddynoc) {
+    c->ddynoc_zero = false; // (a failed copy leaves the buffer unknown)
     if (upload2d(c, c->ddynoc, g.ldx, ddynoc, g.nx, g.ny)) return 1;
+    c->ddynoc_zero = all_plus_zero(ddynoc, (size_t)g.nx * g.ny); // (the row padding keeps the allocation's zeros; nothing reads it)
   }
   c->geom_set = true;
   return 0;
@@ -1129,13 +1157,20 @@ extern "C" int qgcm_hip_set_forcing(qgcm_hip_handle c, const double *wekpo, cons
   if (!c) QG_FAIL("qgcm_hip_set_forcing: null handle");
   const QgGeom &g = c->g;
   if (wekpo && upload2d(c, c->wekpo, g.ldx, wekpo, g.nx, g.ny)) return 1;
-  if (entoc && upload2d(c, c->entoc, g.ldx, entoc, g.nx, g.ny)) return 1;
+  if (entoc) { // (NULL leaves the buffer and what is known about it as they were)
+    c->entoc_zero = false;
+    if (upload2d(c, c->entoc, g.ldx, entoc, g.nx, g.ny)) return 1;
+    // no drop_graphs: the graph keys carry the mask, a captured block of the other variant stays valid for its mask
+    c->entoc_zero = all_plus_zero(entoc, (size_t)g.nx * g.ny);
+  }
   if (xon) {
     HIPCHECK(hipMemcpyAsync((char *)c->sc + offsetof(QgScalars, xon), xon, sizeof(double) * (g.nl - 1), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
   }
   return 0;
 }
+
+extern "C" int qgcm_hip_tend_zero_mask(qgcm_hip_handle c) { return c ? tend_zmask(c) : -1; }
 
 // The fork's sponge layer (-Dsponge_layer_k247): r_spl(nxpo,nypo) of MODULE occonst (set by the main program,
 // src/q-gcm.F:1154-1168) and the compile-time constant c1_spl (src/parameters_data.F:144).  NULL switches the term off.
@@ -1397,6 +1432,13 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
   return pl;
 }
 
+// The zero-field variants of the tendency kernel (k_tend.h: k_tend_z; zm = 1, 2, 3, nl <= 4).  Defined at the END of this
+// file, and on purpose: kernels land in the code object in the order of their first use in this translation unit, so the
+// variants follow every kernel the parent library had, which keep their code AND their place (where a kernel lies moves
+// the 5 km step by +-0.7 us).
+static void launch_tend_z(int zm, int nl, bool cyc, bool wtq, bool avg, dim3 grid, hipStream_t stream, const QgTendParams &P,
+                          const QgCycSumParams &S, const QgOmlFinal &F);
+
 static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = false, int part = TEND_ALL) {
   const QgGeom &g = c->g;
   const qgcm_hip_params &pr = c->prm;
@@ -1453,12 +1495,17 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   const int nextra = part == TEND_INNER ? 0 : (g.cyc ? g.nl * 2 * BSUM_NB : T.nedge);
   dim3 grid(8 * ((ntiles + 7) / 8) + nextra); // 1-D: the kernel maps blockIdx -> tile per XCD band, then edge / line-sum work
   KTimer t(c, KN_TEND);
+  // the ONE place that picks between k_tend and its zero-field variants: qgostep, one_step, the slab stages (whole,
+  // inner and outer tile windows) and qgastep all launch from here
+  const int zm = tend_zmask(c);
 #define QG_TEND(NLV)                                                                                       \
   if (g.cyc && wtq) hipLaunchKernelGGL((k_tend<NLV, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
   else if (g.cyc) hipLaunchKernelGGL((k_tend<NLV, true, false>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
   else if (wtq) hipLaunchKernelGGL((k_tend<NLV, false, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
   else hipLaunchKernelGGL((k_tend<NLV, false, false>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F)
-  if (c->avg_now && g.cyc) { // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does the rest)
+  if (zm) { // (tend_zmask: nl <= 4) the same choice of NL, CYC, WTQ, AVG as below, among the variants
+    launch_tend_z(zm, g.nl, g.cyc, wtq, c->avg_now, grid, c->stream, P, S, F);
+  } else if (c->avg_now && g.cyc) { // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does the rest)
     if (wtq) hipLaunchKernelGGL((k_tend<3, true, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F);
     else hipLaunchKernelGGL((k_tend<3, true, false, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F);
   } else if (c->avg_now) { // the step before a leapfrog averaging stores the averaged qo itself (one_step)
@@ -2001,6 +2048,7 @@ extern "C" int qgcm_hip_oml_init(qgcm_hip_handle c, const qgcm_hip_oml_params *p
     o.ism = 1;
   }
   o.on = true;
+  c->entoc_zero = false; // the mixed layer writes entoc every step from now on (tend_zmask: never skipped again)
   return 0;
 }
 
@@ -2094,6 +2142,7 @@ static int launch_oml_b(qgcm_hip_ctx *c, const double *gath3, int nranks) {
   P.mean_gath = gath3;
   P.nranks = nranks;
   dim3 gB((P.nx + OML_TX - 1) / OML_TX, (P.jP1 - P.jP0 + 1 + OML_TY * OML_RPT * OML_ERR - 1) / (OML_TY * OML_RPT * OML_ERR));
+  c->entoc_zero = false; // (k_oml_entoc writes entoc)
   hipLaunchKernelGGL(k_oml_entoc, gB, dim3(OML_NT), 0, c->stream, P);
   HIPCHECK(hipGetLastError());
   // rotation: sstm <- sst, sst <- new (src/omlsubs.F:125-126)
@@ -2302,7 +2351,10 @@ static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
   const int phase = (s0 - 1) % c->avg_period;
   // mixed layer on/off and its buffer rotation (an ocean handle has the ocean's, an atmosphere handle the atmosphere's)
   const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : c->aml.on ? 1 + 3 * c->aml.ia + c->aml.iam : 0;
-  const long long key = ((long long)B << 32) | ((long long)c->poavg.on << 31) | (omk << 24) | (c->ip << 16) | (c->iq << 8) | phase;
+  // ... and which tendency kernel the block launches (tend_zmask: set_forcing changes it without dropping the graphs;
+  // omk < 16, so bits 28-29 are free)
+  const long long key = ((long long)B << 32) | ((long long)c->poavg.on << 31) | ((long long)tend_zmask(c) << 28) | (omk << 24) |
+                        (c->ip << 16) | (c->iq << 8) | phase;
   auto it = c->graphs.find(key);
   if (it != c->graphs.end()) {
     it->second.used = c->graph_call;
@@ -2504,6 +2556,7 @@ extern "C" int qgcm_hip_aml_init(qgcm_hip_handle c, const qgcm_hip_aml_params *p
   else HIPCHECK(hipMemset(a.dtop, 0, nP * sizeof(double)));
   HIPCHECK(hipDeviceSynchronize());
   a.on = true;
+  c->entoc_zero = false; // the mixed layer writes entat (the handle's entoc buffer) every step from now on
   return 0;
 }
 
@@ -2574,6 +2627,7 @@ static int launch_aml(qgcm_hip_ctx *c, bool with_final) {
   }
   {
     KTimer t(c, KN_AML_ENTAT);
+    c->entoc_zero = false; // (k_aml_entat writes entat, the handle's entoc buffer)
     hipLaunchKernelGGL(k_aml_entat, gB, dim3(OML_NT), 0, c->stream, P);
   }
   if (with_final) {
@@ -3626,7 +3680,7 @@ static int slab_join(qgcm_hip_ctx *c) {
 static int get_slab_graph(qgcm_hip_ctx *c, int s0, hipGraphExec_t *out) {
   const int phase = (s0 - 1) % 25;
   const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : 0; // mixed layer on/off and its buffer rotation
-  const int key = ((int)c->poavg.on << 28) | (omk << 20) | (c->ip << 16) | (c->iq << 8) | phase;
+  const int key = ((int)c->poavg.on << 28) | (tend_zmask(c) << 24) | (omk << 20) | (c->ip << 16) | (c->iq << 8) | phase; // (omk < 16)
   auto it = c->slab_graphs.find(key);
   if (it != c->slab_graphs.end()) {
     *out = it->second;
@@ -3819,3 +3873,45 @@ extern "C" int qgcm_hip_debug_stamps(long long *out, size_t nbytes) {
   return 0;
 }
 #endif
+
+// ---------------------------------------------------------------------------
+// The zero-field variants of the tendency kernel.  LAST in the file: see the declaration in front of launch_tend.
+// ---------------------------------------------------------------------------
+template <int NL, bool CYC, bool WTQ, bool AVG>
+static void tend_z_go(int zm, dim3 grid, hipStream_t stream, const QgTendParams &P, const QgCycSumParams &S, const QgOmlFinal &F) {
+  switch (zm) {
+    case 3: hipLaunchKernelGGL((k_tend_z<NL, CYC, WTQ, AVG, 3>), grid, dim3(TEND_NT), 0, stream, QG_TEND_VALS(P, F), P, S, F); break;
+    case 2: hipLaunchKernelGGL((k_tend_z<NL, CYC, WTQ, AVG, 2>), grid, dim3(TEND_NT), 0, stream, QG_TEND_VALS(P, F), P, S, F); break;
+    default: hipLaunchKernelGGL((k_tend_z<NL, CYC, WTQ, AVG, 1>), grid, dim3(TEND_NT), 0, stream, QG_TEND_VALS(P, F), P, S, F); break;
+  }
+}
+
+// launch_tend's choice of NL, CYC, WTQ, AVG, mirrored (the 5 km box ocean first: its variants lead the group)
+static void launch_tend_z(int zm, int nl, bool cyc, bool wtq, bool avg, dim3 grid, hipStream_t stream, const QgTendParams &P,
+                          const QgCycSumParams &S, const QgOmlFinal &F) {
+#define QG_TEND_Z(NLV)                                                         \
+  if (cyc && wtq) tend_z_go<NLV, true, true, false>(zm, grid, stream, P, S, F); \
+  else if (cyc) tend_z_go<NLV, true, false, false>(zm, grid, stream, P, S, F);  \
+  else if (wtq) tend_z_go<NLV, false, true, false>(zm, grid, stream, P, S, F);  \
+  else tend_z_go<NLV, false, false, false>(zm, grid, stream, P, S, F)
+  if (!cyc && wtq && nl == 3) { // (first in the group whatever happens to the other variants: its place stays put)
+    if (avg) tend_z_go<3, false, true, true>(zm, grid, stream, P, S, F);
+    else tend_z_go<3, false, true, false>(zm, grid, stream, P, S, F);
+  } else if (avg && cyc) {
+    if (wtq) tend_z_go<3, true, true, true>(zm, grid, stream, P, S, F);
+    else tend_z_go<3, true, false, true>(zm, grid, stream, P, S, F);
+  } else if (avg) {
+    switch (nl) {
+      case 3: tend_z_go<3, false, true, true>(zm, grid, stream, P, S, F); break;
+      case 2: tend_z_go<2, false, true, true>(zm, grid, stream, P, S, F); break;
+      default: tend_z_go<4, false, true, true>(zm, grid, stream, P, S, F); break;
+    }
+  } else {
+    switch (nl) {
+      case 3: QG_TEND_Z(3); break;
+      case 2: QG_TEND_Z(2); break;
+      default: QG_TEND_Z(4); break;
+    }
+  }
+#undef QG_TEND_Z
+}

@@ -103,7 +103,7 @@ ATM_TAV_NOUT = 15  # QGCM_HIP_ATM_TAV_NOUT
 SYMBOLS = [
     "qgcm_hip_create", "qgcm_hip_destroy", "qgcm_hip_last_error", "qgcm_hip_abi_version",
     "qgcm_hip_set_grid", "qgcm_hip_set_geometry", "qgcm_hip_set_homog_box", "qgcm_hip_set_homog_cyc",
-    "qgcm_hip_set_state", "qgcm_hip_get_state", "qgcm_hip_set_forcing", "qgcm_hip_set_cyc_forcing", "qgcm_hip_set_sponge",
+    "qgcm_hip_set_state", "qgcm_hip_get_state", "qgcm_hip_set_forcing", "qgcm_hip_tend_zero_mask", "qgcm_hip_set_cyc_forcing", "qgcm_hip_set_sponge",
     "qgcm_hip_set_scalars", "qgcm_hip_get_scalars", "qgcm_hip_get_inv_diag", "qgcm_hip_get_monitors",
     "qgcm_hip_qgostep", "qgcm_hip_ocinvq", "qgcm_hip_ocqbdy", "qgcm_hip_lf_average", "qgcm_hip_ocqbdy_host",
     "qgcm_hip_steps", "qgcm_hip_sync", "qgcm_hip_helmholtz",
@@ -168,6 +168,8 @@ def load_library():
     L.qgcm_hip_set_state.argtypes = [vp, dp, dp, dp, dp]
     L.qgcm_hip_get_state.argtypes = [vp, dp, dp, dp, dp]
     L.qgcm_hip_set_forcing.argtypes = [vp, dp, dp, dp]
+    if hasattr(L, "qgcm_hip_tend_zero_mask"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_tend_zero_mask.argtypes = [vp]
     L.qgcm_hip_set_cyc_forcing.argtypes = [vp, C.c_double, C.c_double, dp, dp]
     L.qgcm_hip_set_sponge.argtypes = [vp, dp, C.c_double]
     L.qgcm_hip_set_scalars.argtypes = [vp, dp]

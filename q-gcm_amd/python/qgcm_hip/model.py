@@ -444,6 +444,11 @@ class OceanModel:
         x = None if xon is None else np.ascontiguousarray(xon, dtype=np.float64)
         check(self.L.qgcm_hip_set_forcing(self.h, _dp(w), _dp(e), _dp(x)))
 
+    def tend_zero_mask(self):
+        """Which of entoc (bit 0) and ddynoc (bit 1) the next tendency launch leaves out because the library knows
+        them to be all zero (qgcm_hip_tend_zero_mask); the results do not depend on it."""
+        return int(self.L.qgcm_hip_tend_zero_mask(self.h))
+
     def set_cyc_forcing(self, txisoc, txinoc, enisoc=None, eninoc=None):
         nl = self.cfg.nlo
         es = np.zeros(nl - 1) if enisoc is None else np.ascontiguousarray(enisoc, dtype=np.float64)
