@@ -865,6 +865,11 @@ int qgcm_hip_copy_bandwidth(qgcm_hip_handle h, size_t bytes, int reps, double *g
 int qgcm_hip_stream_mix_bandwidth(qgcm_hip_handle h, int nr, int nw, size_t field_bytes, int reps, double *gbps);
 /* HIP stream of the handle as an opaque pointer (hipStream_t). */
 void *qgcm_hip_stream(qgcm_hip_handle h);
+/* Debug aid: the device allocations the library holds in this process at the moment, over all handles and scratch -
+ * their number and their bytes (either pointer may be NULL).  Every allocation of the library is counted where it is
+ * made and where it is freed, so a handle that has been destroyed leaves both figures where they were before it was
+ * created.  Process-local and exact, unlike the device's free memory, which other work on the GPU moves. */
+int qgcm_hip_debug_live_allocs(long *blocks, size_t *bytes);
 
 #ifdef __cplusplus
 }

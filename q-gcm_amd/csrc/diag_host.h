@@ -12,11 +12,10 @@ extern "C" int qgcm_hip_set_dtopoc(qgcm_hip_handle c, const double *dtopoc) {
   if (check_ready(c, "qgcm_hip_set_dtopoc")) return 1;
   const QgGeom &g = c->g;
   if (!dtopoc) {
-    if (c->dtopoc) hipFree(c->dtopoc);
-    c->dtopoc = nullptr;
+    c->dtopoc.reset();
     return 0;
   }
-  return upload_field(c, &c->dtopoc, g.ldx, dtopoc, g.nx, g.ny);
+  return upload_field(c, c->dtopoc, g.ldx, dtopoc, g.nx, g.ny);
 }
 
 // last owned T row (local): the T rows of a slab are jlo..jhi, and jlo..jhi-1 on the rank that owns row nypo
@@ -27,10 +26,9 @@ static int launch_valids_scan(qgcm_hip_ctx *c, QgValidsParams &P, const char *wh
   if (check_ready(c, who)) return 1;
   const QgGeom &g = c->g;
   if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("%s: unsupported nlo", who);
-  if (!c->val_part) {
-    if (dalloc(&c->val_part, (size_t)(2 * VAL_NMM + QG_MAXL) * VAL_NB)) return 1;
-    if (dalloc(&c->val_out, (size_t)2 * VAL_NMM + QG_MAXL + 2)) return 1;
-  }
+  if (c->val_part.ensure((size_t)(2 * VAL_NMM + QG_MAXL) * VAL_NB, "the validity scan's partials") ||
+      c->val_out.ensure((size_t)2 * VAL_NMM + QG_MAXL + 2, "the validity scan's result"))
+    return 1;
   memset(&P, 0, sizeof(P));
   P.g = g;
   P.po = c->p[c->ip];
@@ -103,7 +101,7 @@ extern "C" int qgcm_hip_valids_combine(qgcm_hip_handle c, const double *gath_dev
   if (!gath_dev || nranks < 1) QG_FAIL("qgcm_hip_valids_combine: need the gathered summaries and nranks >= 1");
   const QgGeom &g = c->g;
   if (g.nl < 2 || g.nl > QG_MAXL) QG_FAIL("qgcm_hip_valids_combine: unsupported nlo");
-  if (!c->val_out && dalloc(&c->val_out, (size_t)2 * VAL_NMM + QG_MAXL + 2)) return 1;
+  if (c->val_out.ensure((size_t)2 * VAL_NMM + QG_MAXL + 2, "the validity scan's result")) return 1;
   QgValidsParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
@@ -143,8 +141,8 @@ extern "C" int qgcm_hip_set_monitor_fields(qgcm_hip_handle c, const double *taux
   const int nyt = g.ny - 1;
   auto &m = c->mon;
   if (!m.ldt) m.ldt = round_up(g.nxt, 16);
-  return upload_field(c, &m.taux, g.ldx, tauxo, g.nx, g.ny) || upload_field(c, &m.tauy, g.ldx, tauyo, g.nx, g.ny) ||
-         upload_field(c, &m.wekto, m.ldt, wekto, g.nxt, nyt) || upload_field(c, &m.sst, m.ldt, sst, g.nxt, nyt);
+  return upload_field(c, m.taux, g.ldx, tauxo, g.nx, g.ny) || upload_field(c, m.tauy, g.ldx, tauyo, g.nx, g.ny) ||
+         upload_field(c, m.wekto, m.ldt, wekto, g.nxt, nyt) || upload_field(c, m.sst, m.ldt, sst, g.nxt, nyt);
 }
 
 // The surface fields the ocean's diagnostics read: the mixed layer's own stress, wekto and sst when it is on, else the
@@ -189,12 +187,11 @@ static int mon_params(qgcm_hip_ctx *c, QgMonParams &P, const char *who) {
   P.jlo = g.jlo; P.jhi = g.jhi; P.njet = owned_t1(g) - g.jlo + 1;
   P.ntx = (g.nx + MON_TX - 1) / MON_TX;
   P.nblk = P.ntx * ((g.jhi - g.jlo + 1 + MON_TY - 1) / MON_TY);
-  if (!m.psum) {
-    if (dalloc(&m.psum, (size_t)MON_NS(nl) * P.nblk) || dalloc(&m.pmin, (size_t)MON_NM(nl) * P.nblk) ||
-        dalloc(&m.ujet, (size_t)P.njet * nl) || dalloc(&m.out, MON_LEN(nl) + 1))
-      return 1;
-    HIPCHECK(hipHostMalloc((void **)&m.hout, sizeof(double) * (MON_LEN(nl) + 1), hipHostMallocDefault));
-  }
+  if (m.psum.ensure((size_t)MON_NS(nl) * P.nblk, "the monitors' partial sums") ||
+      m.pmin.ensure((size_t)MON_NM(nl) * P.nblk, "the monitors' partial extrema") ||
+      m.ujet.ensure((size_t)P.njet * nl, "the monitors' jet rows") || m.out.ensure(MON_LEN(nl) + 1, "the monitors' result") ||
+      m.hout.ensure(MON_LEN(nl) + 1, "the monitors' pinned result"))
+    return 1;
   P.psum = m.psum; P.pmin = m.pmin; P.ujet = m.ujet; P.out = m.out;
   P.sb = m.prm.sb_hflux; P.nb = m.prm.nb_hflux;
   // MODULE occonst as src/q-gcm.F:414-436 derives it; dto = tdto/2 exactly
@@ -314,12 +311,17 @@ extern "C" int qgcm_hip_set_atm_monitor_fields(qgcm_hip_handle c, const double *
   auto &m = c->atmon;
   if (!m.ldt) m.ldt = round_up(nxt, 16);
   // (field, device buffer, pitch, width, rows)
-  struct F { const double *src; double **dst; int ld, nx, ny; } fs[] = {
+  struct F { const double *src; QgDbl *dst; int ld, nx, ny; } fs[] = {
       {wekta, &m.wekta, m.ldt, nxt, nyt}, {tauxa, &m.tauxa, g.ldx, g.nx, g.ny}, {tauya, &m.tauya, g.ldx, g.nx, g.ny},
-      {ast, &m.ast, m.ldt, nxt, nyt},     {hmixa, &m.hmixa, m.ldt, nxt, nyt},   {uekat, &m.uekat, g.ldx, g.nx, nyt},
-      {vekat, &m.vekat, m.ldt, nxt, g.ny}};
+      {uekat, &m.uekat, g.ldx, g.nx, nyt}, {vekat, &m.vekat, m.ldt, nxt, g.ny}};
   for (const F &f : fs)
-    if (upload_field(c, f.dst, f.ld, f.src, f.nx, f.ny)) return 1;
+    if (upload_field(c, *f.dst, f.ld, f.src, f.nx, f.ny)) return 1;
+  // ast and hmixa: with the mixed layer on the device they go into its current level (what m.ast / m.hmixa point at),
+  // without it into buffers of the monitors' own
+  if (c->aml.diag) return (ast && upload2d(c, m.ast, m.ldt, ast, nxt, nyt)) || (hmixa && upload2d(c, m.hmixa, m.ldt, hmixa, nxt, nyt));
+  if (upload_field(c, m.ast_own, m.ldt, ast, nxt, nyt) || upload_field(c, m.hmixa_own, m.ldt, hmixa, nxt, nyt)) return 1;
+  m.ast = m.ast_own;
+  m.hmixa = m.hmixa_own;
   return 0;
 }
 
@@ -347,12 +349,11 @@ static int atmon_params(qgcm_hip_ctx *c, QgAtmonParams &P, bool mon, const char 
   P.ldt = m.ldt;
   P.ntx = (g.nx + MON_TX - 1) / MON_TX;
   P.nblk = P.ntx * ((g.ny + MON_TY - 1) / MON_TY);
-  if (!m.out) {
-    if (dalloc(&m.psum, (size_t)MON_NS(nl) * P.nblk) || dalloc(&m.pmin, (size_t)MON_NM(nl) * P.nblk) ||
-        dalloc(&m.chain, (size_t)nyt * nl + 1) || dalloc(&m.out, ATMON_LEN(nl)))
-      return 1;
-    HIPCHECK(hipHostMalloc((void **)&m.hout, sizeof(double) * ATMON_LEN(nl), hipHostMallocDefault));
-  }
+  if (m.psum.ensure((size_t)MON_NS(nl) * P.nblk, "the monitors' partial sums") ||
+      m.pmin.ensure((size_t)MON_NM(nl) * P.nblk, "the monitors' partial extrema") ||
+      m.chain.ensure((size_t)nyt * nl + 1, "the monitors' chain") || m.out.ensure(ATMON_LEN(nl), "the monitors' result") ||
+      m.hout.ensure(ATMON_LEN(nl), "the monitors' pinned result"))
+    return 1;
   P.psum = m.psum; P.pmin = m.pmin; P.chain = m.chain; P.out = m.out;
   // MODULE atconst as src/q-gcm.F:392-441 derives it; dta = tdta/2 exactly; atnorm: src/parameters_data.F:87
   P.dta = 0.5 * pr.tdto;
@@ -417,9 +418,9 @@ extern "C" int qgcm_hip_atm_valids(qgcm_hip_handle c, double *out, int *solnok) 
 // the trapezoid sums over the owned rows (k_area_partial); with `final` also their reduction into c->area_out
 static int launch_area_sums(qgcm_hip_ctx *c, bool final = true) {
   const QgGeom &g = c->g;
-  if (!c->area_part) {
-    if (dalloc(&c->area_part, (size_t)AREA_NB * 3 * QG_MAXL) || dalloc(&c->area_out, (size_t)3 * QG_MAXL)) return 1;
-  }
+  if (c->area_part.ensure((size_t)AREA_NB * 3 * QG_MAXL, "the area integrals' partials") ||
+      c->area_out.ensure((size_t)3 * QG_MAXL, "the area integrals"))
+    return 1;
   QgAreaParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
@@ -487,11 +488,14 @@ extern "C" int qgcm_hip_wekpo_from_tau(qgcm_hip_handle c, const double *tauxo, c
   QgWekParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
-  double *tx = nullptr, *ty = nullptr, *wt = nullptr;
-  const bool own = !c->oml.on; // with the device mixed layer the stress and wekto live in its arrays
-  if (own) {
+  QgDbl stx, sty, swt; // scratch without the device mixed layer: with it the stress and wekto live in its arrays
+  double *tx, *ty, *wt;
+  if (!c->oml.on) {
     P.ldt = round_up(g.nxt, 16);
-    if (dalloc(&tx, (size_t)g.ldx * g.ny) || dalloc(&ty, (size_t)g.ldx * g.ny) || dalloc(&wt, (size_t)P.ldt * nyt)) return 1;
+    if (stx.alloc((size_t)g.ldx * g.ny, "the scratch stress") || sty.alloc((size_t)g.ldx * g.ny, "the scratch stress") ||
+        swt.alloc((size_t)P.ldt * nyt, "the scratch wekto"))
+      return 1;
+    tx = stx; ty = sty; wt = swt;
   } else {
     tx = c->oml.taux; ty = c->oml.tauy; wt = c->oml.wekto;
     P.ldt = c->oml.ldt;
@@ -505,9 +509,6 @@ extern "C" int qgcm_hip_wekpo_from_tau(qgcm_hip_handle c, const double *tauxo, c
     rc = hipGetLastError() != hipSuccess;
     if (rc) snprintf(g_err, sizeof(g_err), "qgcm_hip_wekpo_from_tau: launch failed");
     if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
-  }
-  if (own) {
-    hipFree(tx); hipFree(ty); hipFree(wt);
   }
   return rc;
 }
@@ -558,7 +559,7 @@ extern "C" int qgcm_hip_prsamp_part(qgcm_hip_handle c, double *send_dev) {
   if (c->oml.on) { // min, max of sst: this rank's valids summary
     QgValidsParams V;
     if (launch_valids_scan(c, V, "qgcm_hip_prsamp_part")) return 1;
-    if (!c->val_sum && dalloc(&c->val_sum, (size_t)VAL_PART_LEN(QG_MAXL))) return 1;
+    if (c->val_sum.ensure((size_t)VAL_PART_LEN(QG_MAXL), "the valids summary")) return 1;
     V.out = c->val_sum;
 #define QG_VALIDS(NLV) hipLaunchKernelGGL((k_valids_part<NLV>), dim3(1), dim3(VAL_NT), 0, c->stream, V)
     QG_SWITCH_NL(g.nl, QG_VALIDS, "k_valids");
@@ -584,7 +585,7 @@ extern "C" int qgcm_hip_prsamp_combine(qgcm_hip_handle c, const double *gath_dev
   const QgGeom &g = c->g;
   const int nl = g.nl;
   if (nl < 2 || nl > QG_MAXL) QG_FAIL("qgcm_hip_prsamp_combine: unsupported nlo");
-  if (!c->prs_out && dalloc(&c->prs_out, (size_t)4 * QG_MAXL + 3)) return 1;
+  if (c->prs_out.ensure((size_t)4 * QG_MAXL + 3, "prsamp's result")) return 1;
   QgPrsampParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
@@ -635,7 +636,7 @@ extern "C" int qgcm_hip_poavg_enable(qgcm_hip_handle c, int on) {
   auto &a = c->poavg;
   if (on && !a.on) { // the sum starts at zero
     const size_t n = (size_t)c->g.fstride * c->g.nl;
-    if (!a.sum && dalloc(&a.sum, n)) return 1;
+    if (a.sum.ensure(n, "the running sum of po")) return 1;
     HIPCHECK(hipMemsetAsync(a.sum, 0, n * sizeof(double), c->stream));
     a.n = 0;
   }
@@ -684,7 +685,7 @@ extern "C" int qgcm_hip_set_tav_params(qgcm_hip_handle c, const qgcm_hip_tav_par
 
 // fnetoc / fnetat (T grid) for a handle whose fluid has no mixed layer on the device
 static int tav_set_fnet(qgcm_hip_ctx *c, const double *fnet, int ldt) {
-  return upload_field(c, &c->tav.fnet, ldt, fnet, c->g.nxt, c->g.ny - 1);
+  return upload_field(c, c->tav.fnet, ldt, fnet, c->g.nxt, c->g.ny - 1);
 }
 
 extern "C" int qgcm_hip_set_tav_fields(qgcm_hip_handle c, const double *fnetoc) {
@@ -699,7 +700,7 @@ static int tav_accum_params(qgcm_hip_ctx *c, QgTavParams &P) {
   P.po = c->p[c->ip]; P.qo = c->q[c->iq];
   P.jlo = g.jlo; P.jhi = g.jhi; P.jt1 = owned_t1(g); // (a whole-domain handle: 1, ny, ny - 1)
   if (!c->tav.sum) {
-    if (dalloc(&c->tav.sum, (size_t)TAV_NSUM(g.nl) * g.fstride)) return 1;
+    if (c->tav.sum.alloc((size_t)TAV_NSUM(g.nl) * g.fstride, "the time averages' sums")) return 1;
     c->tav.n = 0;
   }
   P.sum = c->tav.sum;
@@ -797,8 +798,8 @@ static int tav_out(qgcm_hip_ctx *c, double *const *fields, int *nsum) {
     if (fields[o])
       for (int k = 0; k < map[o].nf; ++k) mask |= 1u << (map[o].f + k);
   if (!mask) return 0;
-  if (!c->tav.mean && dalloc(&c->tav.mean, (size_t)TAV_NMEAN(nl) * g.fstride)) return 1;
-  if (!c->tav.sum && dalloc(&c->tav.sum, (size_t)TAV_NSUM(nl) * g.fstride)) return 1;
+  if (c->tav.mean.ensure((size_t)TAV_NMEAN(nl) * g.fstride, "the time averages' means")) return 1;
+  if (c->tav.sum.ensure((size_t)TAV_NSUM(nl) * g.fstride, "the time averages' sums")) return 1;
   QgTavParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
@@ -852,18 +853,10 @@ static size_t qd_len(const qgcm_hip_ctx *c, int nsko) {
   return (size_t)QD_NTERM * g.nl * (m1 - m0) * qd_count(g.nx, nsko);
 }
 
+// the dumps' result buffer, grown on demand (the stream is drained first: a dump in flight may still write the old one)
 static int qd_grow(qgcm_hip_ctx *c, size_t n) {
-  auto &q = c->qd;
-  if (q.nbuf >= n) return 0;
-  if (q.buf) {
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    HIPCHECK(hipFree(q.buf));
-    q.buf = nullptr;
-    q.nbuf = 0;
-  }
-  if (dalloc(&q.buf, n)) return 1;
-  q.nbuf = n;
-  return 0;
+  if (c->qd.buf.size() < n) HIPCHECK(hipStreamSynchronize(c->stream));
+  return c->qd.buf.grow(n, "the dumps' result buffer");
 }
 
 // the budget of the state on the device into out (device, qd_len doubles); asynchronous
@@ -944,24 +937,23 @@ static int qd_record(qgcm_hip_ctx *c, int s) {
 extern "C" int qgcm_hip_qocdiag_schedule(qgcm_hip_handle c, int nsko, int every, int capacity) {
   if (check_ready(c, "qgcm_hip_qocdiag_schedule")) return 1;
   auto &q = c->qd;
+  if (every != 0) {
+    if (qd_ready(c, nsko, "qgcm_hip_qocdiag_schedule")) return 1;
+    if (!c->whole) QG_FAIL("qgcm_hip_qocdiag_schedule: this handle is a y-slab; the scheduled dump is whole-domain only (call qgcm_hip_qocdiag between slab steps)");
+    if (every < 0 || capacity < 1) QG_FAIL("qgcm_hip_qocdiag_schedule: need every >= 0 and capacity >= 1");
+  }
+  // the old schedule goes, with what its ring still holds (a dump in flight may still write the ring: drained first)
+  if (q.ring) HIPCHECK(hipStreamSynchronize(c->stream));
+  c->sched[SCH_DUMP] = {};
+  q.cap = q.head = q.count = q.nsko = 0;
+  q.len = 0;
+  q.steps.clear();
   if (every == 0) {
-    if (q.ring) {
-      HIPCHECK(hipStreamSynchronize(c->stream));
-      HIPCHECK(hipFree(q.ring));
-    }
-    q.ring = nullptr;
-    c->sched[SCH_DUMP] = {};
-    q.cap = q.head = q.count = q.nsko = 0;
-    q.len = 0;
-    q.steps.clear();
+    q.ring.reset();
     return 0;
   }
-  if (qd_ready(c, nsko, "qgcm_hip_qocdiag_schedule")) return 1;
-  if (!c->whole) QG_FAIL("qgcm_hip_qocdiag_schedule: this handle is a y-slab; the scheduled dump is whole-domain only (call qgcm_hip_qocdiag between slab steps)");
-  if (every < 0 || capacity < 1) QG_FAIL("qgcm_hip_qocdiag_schedule: need every >= 0 and capacity >= 1");
-  if (qgcm_hip_qocdiag_schedule(c, 0, 0, 0)) return 1;
   const size_t len = qd_len(c, nsko);
-  if (dalloc(&q.ring, len * (size_t)capacity)) return 1;
+  if (q.ring.grow(len * (size_t)capacity, "the dump ring")) return 1;
   q.nsko = nsko; q.cap = capacity; q.len = len;
   c->sched[SCH_DUMP] = {every, 1 % every}; // after every step s with (s - 1) % every == 0
   q.steps.assign(capacity, 0);
@@ -1212,27 +1204,10 @@ extern "C" int qgcm_hip_atnc_sample(qgcm_hip_handle c, int nska, const int *outf
 // (an ocean handle: po and sst, covocn; an atmosphere handle: pa and ast, covatm).  The matrices are split across
 // y-slab ranks by whole matrix rows; a whole-domain handle holds them all.
 // ---------------------------------------------------------------------------
-static void cov_free(qgcm_hip_ctx *c) {
-  auto &v = c->cov;
-  double *f[] = {v.mat[0], v.mat[1], v.mean[0], v.mean[1], v.dev[0], v.dev[1], v.part};
-  for (double *p : f)
-    if (p) hipFree(p);
-  if (v.status) hipFree(v.status);
-  v = {};
+// the covariances off: the state back to its defaults (which gives the memory back)
+static void cov_off(qgcm_hip_ctx *c) {
+  c->cov = {};
   c->sched[SCH_COV] = {}; // (the schedule goes with the matrices)
-}
-
-// n doubles, zeroed; a failure names the bytes
-static int cov_alloc(double **p, size_t n, const char *what) {
-  const size_t bytes = n * sizeof(double);
-  if (hipMalloc((void **)p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    QG_FAIL("qgcm_hip_cov_init: allocating %s (%zu bytes, %.2f GB) failed", what, bytes, bytes / 1e9);
-  }
-  HIPCHECK(hipMemset(*p, 0, bytes));
-  HIPCHECK(hipStreamSynchronize(nullptr)); // (the fill runs on the null stream: see dalloc)
-  return 0;
 }
 
 static int cov_ready(qgcm_hip_ctx *c, const char *who) {
@@ -1257,7 +1232,7 @@ extern "C" int qgcm_hip_cov_init(qgcm_hip_handle c, int nsi, int rank, int nrank
   const QgGeom &g = c->g;
   if (nsi == 0) {
     HIPCHECK(hipStreamSynchronize(c->stream));
-    cov_free(c);
+    cov_off(c);
     return 0;
   }
   const int nyt = g.nyg - 1;
@@ -1269,7 +1244,7 @@ extern "C" int qgcm_hip_cov_init(qgcm_hip_handle c, int nsi, int rank, int nrank
   if (c->whole && nranks != 1)
     QG_FAIL("qgcm_hip_cov_init: a whole-domain handle holds the whole matrices (rank 0 of 1, not %d of %d)", rank, nranks);
   HIPCHECK(hipStreamSynchronize(c->stream));
-  cov_free(c);
+  cov_off(c);
   auto &v = c->cov;
   v.nbx = g.nxt / nsi;
   v.nby = nyt / nsi;
@@ -1286,20 +1261,11 @@ extern "C" int qgcm_hip_cov_init(qgcm_hip_handle c, int nsi, int rank, int nrank
   v.nt = (env && (env[0] == '0' || env[0] == '1')) ? env[0] == '1' : 2.0 * 8.0 * (double)(v.k1 - v.k0) > 256.0 * (1 << 20);
   int rc = 0;
   for (int w = 0; w < 2 && !rc; ++w)
-    rc = (nm && cov_alloc(&v.mat[w], nm, w ? "the T covariance matrix" : "the p covariance matrix")) ||
-         cov_alloc(&v.mean[w], v.nvar, "a mean") || cov_alloc(&v.dev[w], v.nvar, "a deviation vector");
-  if (!rc) rc = cov_alloc(&v.part, v.part_len, "the row sums");
-  if (!rc && hipMalloc((void **)&v.status, sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    v.status = nullptr;
-    snprintf(g_err, sizeof(g_err), "qgcm_hip_cov_init: allocating the status word failed");
-    rc = 1;
-  }
-  if (rc) {
-    char keep[sizeof(g_err)];
-    memcpy(keep, g_err, sizeof(keep));
-    cov_free(c);
-    memcpy(g_err, keep, sizeof(keep));
+    rc = (nm && v.mat[w].alloc(nm, w ? "the T covariance matrix" : "the p covariance matrix")) ||
+         v.mean[w].alloc(v.nvar, "a covariance mean") || v.dev[w].alloc(v.nvar, "a covariance deviation vector");
+  if (!rc) rc = v.part.alloc(v.part_len, "the covariances' row sums") || v.status.alloc(1, "the covariances' status word");
+  if (rc) { // (nothing of a multi-gigabyte attempt stays behind; the message is alloc's)
+    cov_off(c);
     return 1;
   }
   v.nsi = nsi;
@@ -1531,7 +1497,8 @@ extern "C" int qgcm_hip_areavg_init(qgcm_hip_handle c, int n, const int *i1, con
   }
   auto &m = c->ac;
   const int rowcap = owned_t1(g) - g.jlo + 1;
-  if (!m.rows && (dalloc(&m.rows, (size_t)ARAV_MAXN * rowcap) || dalloc(&m.out, ARAV_PART_LEN))) return 1;
+  if (m.rows.ensure((size_t)ARAV_MAXN * rowcap, "the area averages' row sums") || m.out.ensure(ARAV_PART_LEN, "the area averages"))
+    return 1;
   HIPCHECK(hipStreamSynchronize(c->stream)); // (no call that reads the old tables is still in flight)
   m.tab = T;
   return 0;
@@ -1668,7 +1635,8 @@ static int cfl_params(qgcm_hip_ctx *c, QgCflParams &P, double cflcrit, const cha
   P.ntx = (g.nx + CFL_TX - 1) / CFL_TX;
   P.nblk = P.ntx * ((g.jhi - g.jlo + 1 + CFL_TY - 1) / CFL_TY);
   auto &m = c->ac;
-  if (!m.cfl_part && (dalloc(&m.cfl_part, (size_t)CFL_LEN(QG_MAXL) * P.nblk) || dalloc(&m.cfl_out, CFL_PART_LEN(QG_MAXL))))
+  if (m.cfl_part.ensure((size_t)CFL_LEN(QG_MAXL) * P.nblk, "the CFL check's partials") ||
+      m.cfl_out.ensure(CFL_PART_LEN(QG_MAXL), "the CFL check's result"))
     return 1;
   P.part = m.cfl_part;
   P.out = m.cfl_out;

@@ -9,7 +9,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "qgcm_dev.h"
@@ -44,7 +46,6 @@
 #include "k_qocdiag.h"
 #include "k_setup.h"
 #include "k_xforc.h"
-#include "slab_comm.h"
 
 // kernels that are templates on the number of layers: instantiated for nlo = 2 .. QGCM_HIP_MAXL (8); the fused fast
 // paths (k_dst64_unpack, k_rfft64_unpack, k_rfft3_unpack, the riding constraint solves) stay with nlo <= 4
@@ -75,6 +76,88 @@ static thread_local char g_err[512] = "";
     if (e_ != hipSuccess) QG_FAIL("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// Device allocations held through QgBuf in this process (qgcm_hip_debug_live_allocs).
+static std::atomic<long> g_live_blocks{0};
+static std::atomic<size_t> g_live_bytes{0};
+
+// Move-only owner of n elements of device memory (PINNED: of page-locked host memory, which is not counted above).
+// Converts to T *, so kernel-parameter fills and launches read as with a raw pointer.  Every device or pinned
+// allocation of the library is one of these: a member of the handle, or a local for scratch.  Members that point into
+// memory owned elsewhere stay raw pointers and say so.
+template <typename T, bool PINNED = false>
+class QgBuf {
+  T *p_ = nullptr;
+  size_t n_ = 0;
+
+ public:
+  QgBuf() = default;
+  QgBuf(QgBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+  QgBuf &operator=(QgBuf &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, n_ = o.n_;
+      o.p_ = nullptr, o.n_ = 0;
+    }
+    return *this;
+  }
+  ~QgBuf() { reset(); }
+  operator T *() const { return p_; }
+  size_t size() const { return n_; }
+  // frees; the caller has made sure that no launch still uses the memory
+  void reset() {
+    if (!p_) return;
+    if (PINNED) (void)hipHostFree(p_);
+    else {
+      (void)hipFree(p_);
+      g_live_blocks -= 1;
+      g_live_bytes -= n_ * sizeof(T);
+    }
+    p_ = nullptr, n_ = 0;
+  }
+  // n elements in place of what was held, device memory zeroed; a failure names `what` and the bytes
+  int alloc(size_t n, const char *what) {
+    reset();
+    const size_t bytes = n * sizeof(T);
+    const hipError_t e = PINNED ? hipHostMalloc((void **)&p_, bytes, hipHostMallocDefault) : hipMalloc((void **)&p_, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError(); // (the runtime's sticky error: later calls must not report it)
+      p_ = nullptr;
+      QG_FAIL("allocating %s (%zu bytes, %.2f GB) failed", what, bytes, bytes / 1e9);
+    }
+    if (!p_) return 0; // (nothing asked for)
+    n_ = n;
+    if (PINNED) return 0;
+    g_live_blocks += 1;
+    g_live_bytes += bytes;
+    // The zero fill runs on the NULL stream, and a device memset need not have finished when hipMemset returns; the
+    // handle's stream is non-blocking (not ordered against the null stream), so work queued on it right after an
+    // allocation - the copy in qgcm_hip_set_thomas_consts, the all-gather in qgcm_hip_comm_init - could be overtaken
+    // by the fill and zeroed. Seen as wrong slab constants with three one-process-per-slab ranks. Wait for the fill.
+    HIPCHECK(hipMemset(p_, 0, bytes));
+    HIPCHECK(hipStreamSynchronize(nullptr));
+    return 0;
+  }
+  int ensure(size_t n, const char *what) { return p_ ? 0 : alloc(n, what); }           // allocated on first use
+  int grow(size_t n, const char *what) { return p_ && n <= n_ ? 0 : alloc(n, what); }  // reallocated when too small
+};
+typedef QgBuf<double> QgDbl;
+
+// a pair of scratch events of one call, destroyed at scope exit
+struct QgEventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  int create() {
+    HIPCHECK(hipEventCreate(&a));
+    HIPCHECK(hipEventCreate(&b));
+    return 0;
+  }
+  ~QgEventPair() {
+    if (a) hipEventDestroy(a);
+    if (b) hipEventDestroy(b);
+  }
+};
+
+#include "slab_comm.h"
+
 enum { KN_TEND = 0, KN_BSUMS, KN_DSTF, KN_THOMAS, KN_DSTI, KN_CONSTR, KN_UNPACK, KN_OCQBDY, KN_LFAVG, KN_OML, KN_OML_ENTOC, KN_NOOP, KN_NOOP_TRAIN, KN_POAVG, KN_TAVAT, KN_COV, KN_AML, KN_AML_ENTAT, KN_COUNT };
 // (k_oml = k_oml_step, the sst step + raw entrainment; k_oml_entoc = the entrainment on the p grid; k_aml = k_aml_step)
 static const char *kKernelNames[KN_COUNT] = {"k_tend",   "k_cyc_bsums", "k_dst_fwd", "k_thomas", "k_dst_inv",
@@ -83,9 +166,8 @@ static const char *kKernelNames[KN_COUNT] = {"k_tend",   "k_cyc_bsums", "k_dst_f
 
 // Device copy of the Thomas pivot tables of one set of diagonals (see QgThomasParams / build_pivots).
 struct QgThomasTab {
-  double *binf = nullptr, *ptab = nullptr;
-  int *rcb = nullptr, *poff = nullptr;
-  size_t binf_n = 0, ptab_n = 0, rcb_n = 0, poff_n = 0; // capacities (elements)
+  QgDbl binf, ptab;
+  QgBuf<int> rcb, poff;
 };
 
 // A schedule: step s is due when every > 0 and s % every == phase.
@@ -114,18 +196,18 @@ struct qgcm_hip_ctx {
   qgcm_hip_params prm;
   QgGeom g;
   int device;
-  hipStream_t stream;
-  double *p[2], *q[2];
+  hipStream_t stream = nullptr;
+  QgDbl p[2], q[2];
   int ip, iq; // p[ip] = po, p[ip^1] = pom ; q[iq] = qo, q[iq^1] = qom
-  double *wekpo, *entoc, *ddynoc, *ochom, *yporel;
-  double *rspl = nullptr; // sponge-layer ramp r_spl (qgcm_hip_set_sponge), or nullptr
+  QgDbl wekpo, entoc, ddynoc, ochom, yporel;
+  QgDbl rspl; // sponge-layer ramp r_spl (qgcm_hip_set_sponge), or empty
   double c1_spl = 0.0;
-  double *wrk, *rowsum;
-  double *ybnd = nullptr;                  // cyclic y-slabs: (2, nl) zonal-mean solution next to the zonal boundaries (k_thomas PHASE 2)
-  const double *slab_gath = nullptr;       // cyclic y-slabs: the gathered step messages of the last thomas phase 2
+  QgDbl wrk, rowsum;
+  QgDbl ybnd;                              // cyclic y-slabs: (2, nl) zonal-mean solution next to the zonal boundaries (k_thomas PHASE 2)
+  const double *slab_gath = nullptr;       // not owned - cyclic y-slabs: the gathered step messages of the last thomas phase 2
   int slab_nranks = 1;
-  const double *oml_gath = nullptr;        // y-slabs: the gathered sums of the mixed layer's stage 10 (3, nranks)
-  double *bpart_out = nullptr;             // where k_tend's extra workgroups put the boundary line sums (bpart, or the tail of the step message)
+  const double *oml_gath = nullptr;        // not owned - y-slabs: the gathered sums of the mixed layer's stage 10 (3, nranks)
+  double *bpart_out = nullptr;             // not owned - where k_tend's extra workgroups put the boundary line sums (bpart, or the tail of the step message)
   QgThomasTab tt, tt_tmp;                  // Thomas pivot tables of the modal solves / of the last qgcm_hip_helmholtz
   // whole-domain oceans whose column is cut into segments (k_thomas.h: k_thomas_seg, k_thomas_corr_seg): the plan, and
   // per set of diagonals - [0] the modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot
@@ -134,32 +216,32 @@ struct qgcm_hip_ctx {
     int S = 1, R = 0, maxlen = 0;           // segments (1: the single-segment kernel), rows per chunk, longest segment
     int seg_rows = 0;                       // QGCM_HIP_THOMAS_SEG_ROWS as set_grid read it (0: unset)
     std::vector<int> first, count;          // interior rows [first, first + count) of each segment
-    double *msg = nullptr;                  // (Cf, Cb, S0) of every segment, segment-major: the gathered slab messages' layout
+    QgDbl msg;                              // (Cf, Cb, S0) of every segment, segment-major: the gathered slab messages' layout
     struct Set {
-      QgThomasSegRec *recs = nullptr;
-      double *ptab = nullptr, *qtab = nullptr, *cst = nullptr; // responses; (D, E, SP, SQ) segment-major (cgath's layout)
-      int *meta = nullptr;                  // np, nq, poff, qoff: (nblk, layers, S) each
+      QgBuf<QgThomasSegRec> recs;
+      QgDbl ptab, qtab, cst;                // responses; (D, E, SP, SQ) segment-major (cgath's layout)
+      QgBuf<int> meta;                      // np, nq, poff, qoff: (nblk, layers, S) each
       std::vector<double> boc;              // [1]: the diagonal the tables were built for
     } set[2];
   } seg;
   // y-slabs: the slab's responses to unit inflows from below / above, tabulated as far as they reach (k_thomas_corr)
   struct {
-    double *ptab = nullptr, *qtab = nullptr;
-    int *meta = nullptr; // np, nq, poff, qoff: (nblk, nl) each
+    QgDbl ptab, qtab;
+    QgBuf<int> meta; // np, nq, poff, qoff: (nblk, nl) each
     size_t prows = 0, qrows = 0;
   } corr;
-  double *slabDE;                          // y-slab summary constants (D, E, SP, SQ) per (mode, wavenumber)
-  double *th_cgath = nullptr;              // all ranks' slabDE (rank-major), exchanged once (qgcm_hip_set_thomas_consts)
+  QgDbl slabDE;                            // y-slab summary constants (D, E, SP, SQ) per (mode, wavenumber)
+  QgDbl th_cgath;                          // all ranks' slabDE (rank-major), exchanged once (qgcm_hip_set_thomas_consts)
   int th_cgath_ranks = 0;
-  double *ksum, *wcot;                     // spectral column sums of the solution and their cot weights (k_thomas.h)
-  double *bpart;                           // cyclic: partial boundary line sums (k_tend's extra workgroups -> constraint algebra)
-  QgConstrParams *d_boxq = nullptr;        // box: device copy of the constraint parameters (generic inverse rows' extra workgroup)
-  QgCycConstrParams *d_cycq = nullptr;     // cyclic: device copy of the constraint parameters (fused step path)
+  QgDbl ksum, wcot;                        // spectral column sums of the solution and their cot weights (k_thomas.h)
+  QgDbl bpart;                             // cyclic: partial boundary line sums (k_tend's extra workgroups -> constraint algebra)
+  QgBuf<QgConstrParams> d_boxq;            // box: device copy of the constraint parameters (generic inverse rows' extra workgroup)
+  QgBuf<QgCycConstrParams> d_cycq;         // cyclic: device copy of the constraint parameters (fused step path)
   int thR;                                 // rows per chunk of the Thomas kernel
-  double *pch1, *pch2, *pbh;
-  QgScalars *sc;
-  double2 *twid;
-  double *sintab;
+  QgDbl pch1, pch2, pbh;
+  QgBuf<QgScalars> sc;
+  QgBuf<double2> twid;
+  QgDbl sintab;
   int fftN, nfac, fac[QG_MAXFAC];
   QgConstr cs;
   bool grid_set, homog_set;
@@ -185,7 +267,7 @@ struct qgcm_hip_ctx {
   hipError_t timer_err = hipSuccess;
   int timer_err_at = 0;
   bool profiling;
-  hipEvent_t ev0, ev1;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> evpool; // pairs, drained once per step (no host sync between kernels)
   std::vector<int> evkid;
   double kms[KN_COUNT];
@@ -200,9 +282,9 @@ struct qgcm_hip_ctx {
     bool on = false;
     qgcm_hip_oml_params prm;
     int ldt = 0, is = 0, ism = 1, nblkA = 0, nblkB = 0;
-    double *sst[3] = {nullptr, nullptr, nullptr};
-    double *fnet = nullptr, *wekto = nullptr, *xfo = nullptr, *taux = nullptr, *tauy = nullptr;
-    double *partA = nullptr, *partB = nullptr, *diag = nullptr;
+    QgDbl sst[3];
+    QgDbl fnet, wekto, xfo, taux, tauy;
+    QgDbl partA, partB, diag;
   } oml;
   // atmospheric mixed layer (qgcm_hip_aml_init, k_aml.h; atmosphere handles): ast and hmixa in three rotating buffers
   // each (ia = the current level, iam = the lagged one, spare = 3-ia-iam); atmon.ast / atmon.hmixa always point at the
@@ -211,22 +293,22 @@ struct qgcm_hip_ctx {
     bool on = false;
     qgcm_hip_aml_params prm;
     int ldt = 0, ia = 0, iam = 1, nblkA = 0, nblkB = 0;
-    double *ast[3] = {nullptr, nullptr, nullptr}, *hm[3] = {nullptr, nullptr, nullptr};
-    double *xfa = nullptr, *xc1 = nullptr, *dtop = nullptr, *partA = nullptr, *partB = nullptr, *diag = nullptr;
+    QgDbl ast[3], hm[3];
+    QgDbl xfa, xc1, dtop, partA, partB, diag;
   } aml;
   // validity scan (qgcm_hip_valids): partials, results, optional bottom topography
-  double *val_part = nullptr, *val_out = nullptr, *dtopoc = nullptr;
-  double *val_sum = nullptr, *prs_out = nullptr; // y-slab prsamp: this rank's valids summary (sst), combined result
-  double *area_part = nullptr, *area_out = nullptr; // trapezoid area integrals of po, pom, qo (k_setup.h)
+  QgDbl val_part, val_out, dtopoc;
+  QgDbl val_sum, prs_out; // y-slab prsamp: this rank's valids summary (sst), combined result
+  QgDbl area_part, area_out; // trapezoid area integrals of po, pom, qo (k_setup.h)
   // ocean monitors (qgcm_hip_monitors, k_monitors.h): constants, the fields that do not evolve on the device without
   // the mixed layer (qgcm_hip_set_monitor_fields), partials and the pinned result, all allocated on first use
   struct {
     bool prm_set = false;
     qgcm_hip_mon_params prm;
     int ldt = 0;
-    double *taux = nullptr, *tauy = nullptr, *wekto = nullptr, *sst = nullptr;
-    double *psum = nullptr, *pmin = nullptr, *ujet = nullptr, *out = nullptr;
-    double *hout = nullptr; // pinned host copy of out
+    QgDbl taux, tauy, wekto, sst;
+    QgDbl psum, pmin, ujet, out;
+    QgBuf<double, true> hout; // pinned host copy of out
   } mon;
   // atmosphere monitors and valids (qgcm_hip_atm_monitors / _atm_valids, k_atm_monitors.h): constants, the fields
   // xforc / aml leave on the host (qgcm_hip_set_atm_monitor_fields), partials and the pinned result
@@ -234,16 +316,19 @@ struct qgcm_hip_ctx {
     bool prm_set = false;
     qgcm_hip_atm_mon_params prm;
     int ldt = 0;
-    double *wekta = nullptr, *tauxa = nullptr, *tauya = nullptr, *ast = nullptr, *hmixa = nullptr, *uekat = nullptr,
-           *vekat = nullptr;
-    double *psum = nullptr, *pmin = nullptr, *chain = nullptr, *out = nullptr;
-    double *hout = nullptr; // pinned host copy of out
+    QgDbl wekta, tauxa, tauya, uekat, vekat;
+    // what every diagnostic reads, not owned: ast_own / hmixa_own (the fields of qgcm_hip_set_atm_monitor_fields) until
+    // qgcm_hip_aml_init, the mixed layer's current level from then on (aml_set_idx)
+    double *ast = nullptr, *hmixa = nullptr;
+    QgDbl ast_own, hmixa_own;
+    QgDbl psum, pmin, chain, out;
+    QgBuf<double, true> hout; // pinned host copy of out
   } atmon;
   // running mean of po (qgcm_hip_poavg_enable, k_tavg.h): the sum over the owned rows and its count; while `on`
   // every step of qgcm_hip_steps / the slab stage 2 adds its po before the leapfrog averaging
   struct {
     bool on = false;
-    double *sum = nullptr;
+    QgDbl sum;
     long n = 0;
   } poavg;
   // tavocn / tavatm and tavout (qgcm_hip_tavocn / _tavatm, k_tavg.h, k_atm_tavg.h) for the handle's fluid: sums (the
@@ -251,7 +336,7 @@ struct qgcm_hip_ctx {
   struct {
     bool prm_set = false;
     qgcm_hip_tav_params prm; // (ocean only: the atmosphere's hmat comes with qgcm_hip_set_atm_mon_params)
-    double *sum = nullptr, *mean = nullptr, *fnet = nullptr;
+    QgDbl sum, mean, fnet;
     long n = 0;
   } tav;
   // covariance matrices (qgcm_hip_cov_*, k_cov.h): covini's state for the handle's fluid - the packed rows [k0, k1)
@@ -261,9 +346,9 @@ struct qgcm_hip_ctx {
     int nsi = 0, nbx = 0, nby = 0, nvar = 0;
     bool nt = false; // non-temporal loads / stores in k_cov_rank1 (matrices past the Infinity Cache, QGCM_HIP_COV_NT)
     long nmat = 0, k0 = 0, k1 = 0, part_len = 0;
-    double *mat[2] = {nullptr, nullptr}, *mean[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};
-    double *part = nullptr;
-    int *status = nullptr;
+    QgDbl mat[2], mean[2], dev[2];
+    QgDbl part;
+    QgBuf<int> status;
     long nu[2] = {0, 0};
     double swt[2] = {0.0, 0.0};
   } cov;
@@ -271,17 +356,16 @@ struct qgcm_hip_ctx {
   // (tab.n = 0: not set up), the row sums and the result; the CFL partials and result, allocated on first use
   struct {
     QgAravParams tab = {};
-    double *rows = nullptr, *out = nullptr;
-    double *cfl_part = nullptr, *cfl_out = nullptr;
+    QgDbl rows, out;
+    QgDbl cfl_part, cfl_out;
   } ac;
   // periodic dumps (qgcm_hip_qocdiag / _ocnc_sample / _atnc_sample, k_qocdiag.h): device result buffer (grown on
   // demand); the scheduled dump of qgcm_hip_qocdiag_schedule: a ring of `cap` snapshots of `len` doubles, oldest at `head`
   struct {
-    double *buf = nullptr;
-    size_t nbuf = 0;
+    QgDbl buf;
     int nsko = 0, cap = 0, head = 0, count = 0;
     size_t len = 0;
-    double *ring = nullptr;
+    QgDbl ring;
     std::vector<int> steps; // step number of each ring slot
   } qd;
   // what qgcm_hip_steps does on its own at scheduled steps: the dump of qgcm_hip_qocdiag_schedule inside the step, the
@@ -293,17 +377,17 @@ struct qgcm_hip_ctx {
   struct {
     bool on = false, coupled = false; // coupled: qgcm_hip_coupled_steps calls xforc before every ocean step
     qgcm_hip_xforc_params prm;
-    qgcm_hip_ctx *oc = nullptr;
+    qgcm_hip_ctx *oc = nullptr; // not owned
     int ldf = 0, ldtf = 0;
-    double *u1at = nullptr, *v1at = nullptr, *txf = nullptr, *tyf = nullptr, *wf = nullptr, *tab = nullptr;
+    QgDbl u1at, v1at, txf, tyf, wf, tab;
     hipEvent_t ev_oc = nullptr, ev_atm = nullptr;
     // heat half (qgcm_hip_xforc_heat_init): constants, the two fsprim tables, bilint's index / weight tables, the
     // per-cell sums above the ocean, the partial sums of the four monitors and their results
     struct {
       bool on = false;
       qgcm_hip_xforc_heat_params prm;
-      double *fsa = nullptr, *fso = nullptr, *wx = nullptr, *wy = nullptr, *cell = nullptr, *part = nullptr, *scal = nullptr;
-      int *ix = nullptr, *iy = nullptr;
+      QgDbl fsa, fso, wx, wy, cell, part, scal;
+      QgBuf<int> ix, iy;
       int nblkL = 0;
     } heat;
   } xf;
@@ -312,6 +396,23 @@ struct qgcm_hip_ctx {
   std::map<int, hipGraphExec_t> slab_graphs;
   bool slab_graph_mode = false; // QGCM_HIP_SLAB_GRAPH=1: capture 50 distributed steps (collectives included)
   size_t dst_lds;
+
+  qgcm_hip_ctx() = default;
+  qgcm_hip_ctx(const qgcm_hip_ctx &) = delete;
+  // What is not memory.  The stream is drained first and the communicator goes before its buffers (~QgSlabComm); the
+  // members then free the memory, after the stream has gone idle.
+  ~qgcm_hip_ctx() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (auto &kv : graphs) hipGraphExecDestroy(kv.second.exec);
+    for (auto &kv : slab_graphs) hipGraphExecDestroy(kv.second);
+    delete sc_comm;
+    if (xf.ev_oc) hipEventDestroy(xf.ev_oc);
+    if (xf.ev_atm) hipEventDestroy(xf.ev_atm);
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    for (hipEvent_t e : evpool) hipEventDestroy(e);
+    if (stream) hipStreamDestroy(stream);
+  }
 };
 
 static const int kGraphBlock = 50; // steps per captured block (qgcm_hip_steps: get_graph; y-slabs: qgcm_hip_slab_steps)
@@ -383,22 +484,11 @@ static int tend_zmask(const qgcm_hip_ctx *c) {
   return (c->entoc_zero && !c->oml.on && !c->aml.on ? 1 : 0) | (c->ddynoc_zero ? 2 : 0);
 }
 
-static int dalloc(double **p, size_t n) {
-  HIPCHECK(hipMalloc((void **)p, n * sizeof(double)));
-  // The zero fill runs on the NULL stream, and a device memset need not have finished when hipMemset returns; the
-  // handle's stream is non-blocking (not ordered against the null stream), so work queued on it right after an
-  // allocation - the copy in qgcm_hip_set_thomas_consts, the all-gather in qgcm_hip_comm_init - could be overtaken
-  // by the fill and zeroed. Seen as wrong slab constants with three one-process-per-slab ranks. Wait for the fill.
-  HIPCHECK(hipMemset(*p, 0, n * sizeof(double)));
-  HIPCHECK(hipStreamSynchronize(nullptr));
-  return 0;
-}
-
-// a host field a set_* call hands over (nullptr: not this time) into *dst, allocated (ld, rows) on first use
-static int upload_field(qgcm_hip_ctx *c, double **dst, int ld, const double *src, int nx, long rows) {
+// a host field a set_* call hands over (nullptr: not this time) into dst, allocated (ld, rows) on first use
+static int upload_field(qgcm_hip_ctx *c, QgDbl &dst, int ld, const double *src, int nx, long rows) {
   if (!src) return 0;
-  if (!*dst && dalloc(dst, (size_t)ld * rows)) return 1;
-  return upload2d(c, *dst, ld, src, nx, rows);
+  if (dst.ensure((size_t)ld * rows, "a field handed over by the host")) return 1;
+  return upload2d(c, dst, ld, src, nx, rows);
 }
 
 extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, int device) {
@@ -410,7 +500,7 @@ extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, i
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev == 0) QG_FAIL("qgcm_hip_create: no HIP device (%s) - there is no CPU fallback", hipGetErrorString(e));
   if (device >= 0) HIPCHECK(hipSetDevice(device));
-  qgcm_hip_ctx *c = new qgcm_hip_ctx();
+  std::unique_ptr<qgcm_hip_ctx> c(new qgcm_hip_ctx()); // (a failure below leaves nothing behind, and *h null)
   memset(&c->prm, 0, sizeof(c->prm));
   c->prm = *prm;
   HIPCHECK(hipGetDevice(&c->device));
@@ -457,26 +547,23 @@ extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, i
   HIPCHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   const size_t F = (size_t)g.fstride, W = (size_t)g.wstride;
   for (int i = 0; i < 2; ++i) {
-    if (dalloc(&c->p[i], F * g.nl)) return 1;
-    if (dalloc(&c->q[i], F * g.nl)) return 1;
+    if (c->p[i].alloc(F * g.nl, "a time level of p")) return 1;
+    if (c->q[i].alloc(F * g.nl, "a time level of q")) return 1;
   }
   c->ip = c->iq = 0;
-  if (dalloc(&c->wekpo, F) || dalloc(&c->entoc, F) || dalloc(&c->ddynoc, F)) return 1;
-  c->entoc_zero = c->ddynoc_zero = true; // (dalloc fills with zeros)
-  if (dalloc(&c->ochom, F * (g.nl - 1))) return 1;
-  if (dalloc(&c->yporel, g.ny)) return 1;
-  if (dalloc(&c->wrk, W * g.nl)) return 1;
-  if (dalloc(&c->slabDE, (size_t)4 * g.ldw * g.nl)) return 1;
-  if (g.cyc && dalloc(&c->ybnd, 2 * QG_MAXL)) return 1;
-  if (dalloc(&c->ksum, (size_t)g.ldw * g.nl)) return 1;
-  if (dalloc(&c->wcot, (size_t)g.ldw)) return 1;
-  if (dalloc(&c->bpart, (size_t)5 * BSUM_NB * 2 * g.nl)) return 1;
-  if (dalloc(&c->rowsum, (size_t)g.ny * g.nl)) return 1;
-  if (dalloc(&c->pch1, (size_t)g.ny * g.nl) || dalloc(&c->pch2, (size_t)g.ny * g.nl) || dalloc(&c->pbh, g.ny)) return 1;
-  HIPCHECK(hipMalloc((void **)&c->sc, sizeof(QgScalars)));
-  HIPCHECK(hipMemset(c->sc, 0, sizeof(QgScalars)));
-  c->twid = nullptr;
-  c->sintab = nullptr;
+  if (c->wekpo.alloc(F, "wekpo") || c->entoc.alloc(F, "entoc") || c->ddynoc.alloc(F, "ddynoc")) return 1;
+  c->entoc_zero = c->ddynoc_zero = true; // (alloc fills with zeros)
+  if (c->ochom.alloc(F * (g.nl - 1), "the homogeneous solutions")) return 1;
+  if (c->yporel.alloc(g.ny, "yporel")) return 1;
+  if (c->wrk.alloc(W * g.nl, "the spectral work array")) return 1;
+  if (c->slabDE.alloc((size_t)4 * g.ldw * g.nl, "the slab constants")) return 1;
+  if (g.cyc && c->ybnd.alloc(2 * QG_MAXL, "ybnd")) return 1;
+  if (c->ksum.alloc((size_t)g.ldw * g.nl, "ksum")) return 1;
+  if (c->wcot.alloc((size_t)g.ldw, "wcot")) return 1;
+  if (c->bpart.alloc((size_t)5 * BSUM_NB * 2 * g.nl, "the boundary line sums")) return 1;
+  if (c->rowsum.alloc((size_t)g.ny * g.nl, "the row sums")) return 1;
+  if (c->pch1.alloc((size_t)g.ny * g.nl, "pch1") || c->pch2.alloc((size_t)g.ny * g.nl, "pch2") || c->pbh.alloc(g.ny, "pbh")) return 1;
+  if (c->sc.alloc(1, "the step's scalars")) return 1;
   c->grid_set = c->homog_set = false;
   {
     const char *e = getenv("QGCM_HIP_GENERIC_DST");
@@ -497,102 +584,18 @@ extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, i
   HIPCHECK(hipEventCreate(&c->ev1));
   memset(&c->cs, 0, sizeof(c->cs));
   HIPCHECK(hipDeviceSynchronize()); // the zero fills above ran on the null stream
-  *h = c;
+  *h = c.release();
   return 0;
 }
 
 extern "C" int qgcm_hip_destroy(qgcm_hip_handle c) {
-  if (!c) return 0;
-  hipStreamSynchronize(c->stream);
-  for (auto &kv : c->graphs) hipGraphExecDestroy(kv.second.exec);
-  for (auto &kv : c->slab_graphs) hipGraphExecDestroy(kv.second);
-  if (c->sc_comm) {
-    QgSlabComm *m = c->sc_comm;
-    if (m->comm) m->api->CommDestroy(m->comm);
-    if (m->ev_fork) hipEventDestroy(m->ev_fork);
-    if (m->ev_halo) hipEventDestroy(m->ev_halo);
-    if (m->cstream) hipStreamDestroy(m->cstream);
-    double *cb[] = {m->th_send, m->th_gath, m->h_send, m->h_gath, m->oml_send, m->oml_gath};
-    for (double *p : cb)
-      if (p) hipFree(p);
-    delete m;
-  }
-  double *vp[] = {c->val_part, c->val_out, c->dtopoc, c->th_cgath, c->area_part, c->area_out, c->ybnd, c->rspl,
-                  c->val_sum, c->prs_out};
-  for (double *p : vp)
-    if (p) hipFree(p);
-  double *monp[] = {c->mon.taux, c->mon.tauy, c->mon.wekto, c->mon.sst, c->mon.psum, c->mon.pmin, c->mon.ujet, c->mon.out};
-  for (double *p : monp)
-    if (p) hipFree(p);
-  if (c->mon.hout) hipHostFree(c->mon.hout);
-  if (c->aml.ast[0]) { // the mixed layer owns what atmon.ast / atmon.hmixa point at
-    c->atmon.ast = c->atmon.hmixa = nullptr;
-    double *amp[] = {c->aml.ast[0], c->aml.ast[1], c->aml.ast[2], c->aml.hm[0], c->aml.hm[1], c->aml.hm[2], c->aml.xfa,
-                     c->aml.xc1, c->aml.dtop, c->aml.partA, c->aml.partB, c->aml.diag};
-    for (double *p : amp)
-      if (p) hipFree(p);
-  }
-  {
-    auto &hh = c->xf.heat;
-    double *hp[] = {hh.fsa, hh.fso, hh.wx, hh.wy, hh.cell, hh.part, hh.scal};
-    for (double *p : hp)
-      if (p) hipFree(p);
-    if (hh.ix) hipFree(hh.ix);
-    if (hh.iy) hipFree(hh.iy);
-  }
-  double *atmp[] = {c->atmon.wekta, c->atmon.tauxa, c->atmon.tauya, c->atmon.ast, c->atmon.hmixa, c->atmon.uekat,
-                    c->atmon.vekat, c->atmon.psum, c->atmon.pmin, c->atmon.chain, c->atmon.out};
-  for (double *p : atmp)
-    if (p) hipFree(p);
-  if (c->atmon.hout) hipHostFree(c->atmon.hout);
-  double *tavp[] = {c->poavg.sum, c->tav.sum, c->tav.mean, c->tav.fnet, c->qd.buf, c->qd.ring,
-                    c->cov.mat[0], c->cov.mat[1], c->cov.mean[0], c->cov.mean[1], c->cov.dev[0], c->cov.dev[1],
-                    c->cov.part};
-  for (double *p : tavp)
-    if (p) hipFree(p);
-  if (c->cov.status) hipFree(c->cov.status);
-  double *acp[] = {c->ac.rows, c->ac.out, c->ac.cfl_part, c->ac.cfl_out};
-  for (double *p : acp)
-    if (p) hipFree(p);
-  double *xfp[] = {c->xf.u1at, c->xf.v1at, c->xf.txf, c->xf.tyf, c->xf.wf, c->xf.tab};
-  for (double *p : xfp)
-    if (p) hipFree(p);
-  if (c->xf.ev_oc) hipEventDestroy(c->xf.ev_oc);
-  if (c->xf.ev_atm) hipEventDestroy(c->xf.ev_atm);
-  double *omp[] = {c->oml.sst[0], c->oml.sst[1], c->oml.sst[2], c->oml.fnet, c->oml.wekto, c->oml.xfo,
-                   c->oml.taux, c->oml.tauy, c->oml.partA, c->oml.partB, c->oml.diag};
-  for (double *p : omp)
-    if (p) hipFree(p);
-  double *ptrs[] = {c->p[0], c->p[1], c->q[0], c->q[1], c->wekpo, c->entoc, c->ddynoc, c->ochom, c->yporel,
-                    c->wrk,  c->slabDE, c->ksum, c->wcot, c->bpart, c->rowsum, c->pch1, c->pch2, c->pbh, c->sintab};
-  for (double *p : ptrs)
-    if (p) hipFree(p);
-  if (c->twid) hipFree(c->twid);
-  hipFree(c->sc);
-  if (c->d_cycq) hipFree(c->d_cycq);
-  if (c->d_boxq) hipFree(c->d_boxq);
-  if (c->corr.ptab) hipFree(c->corr.ptab);
-  if (c->corr.qtab) hipFree(c->corr.qtab);
-  if (c->corr.meta) hipFree(c->corr.meta);
-  if (c->seg.msg) hipFree(c->seg.msg);
-  for (auto &ss : c->seg.set) {
-    if (ss.recs) hipFree(ss.recs);
-    if (ss.ptab) hipFree(ss.ptab);
-    if (ss.qtab) hipFree(ss.qtab);
-    if (ss.cst) hipFree(ss.cst);
-    if (ss.meta) hipFree(ss.meta);
-  }
-  for (QgThomasTab *t : {&c->tt, &c->tt_tmp}) {
-    if (t->binf) hipFree(t->binf);
-    if (t->ptab) hipFree(t->ptab);
-    if (t->rcb) hipFree(t->rcb);
-    if (t->poff) hipFree(t->poff);
-  }
-  hipEventDestroy(c->ev0);
-  hipEventDestroy(c->ev1);
-  for (hipEvent_t e : c->evpool) hipEventDestroy(e);
-  hipStreamDestroy(c->stream);
-  delete c;
+  delete c; // (~qgcm_hip_ctx; a null handle is fine)
+  return 0;
+}
+
+extern "C" int qgcm_hip_debug_live_allocs(long *blocks, size_t *bytes) {
+  if (blocks) *blocks = g_live_blocks.load();
+  if (bytes) *bytes = g_live_bytes.load();
   return 0;
 }
 
@@ -691,19 +694,10 @@ static void build_pivots(const QgGeom &g, double aoc, const double *boc /* per s
 
 // (re)allocates the device tables as needed and uploads T (blocking copies: T may die at the caller's scope exit)
 static int upload_pivots(qgcm_hip_ctx *c, QgThomasTab &D, const ThomasTabHost &T) {
-  auto fit = [&](void **p, size_t &cap, size_t n, size_t el) -> int {
-    if (n <= cap && *p) return 0;
-    if (*p) HIPCHECK(hipFree(*p));
-    *p = nullptr;
-    HIPCHECK(hipMalloc(p, n * el));
-    cap = n;
-    return 0;
-  };
   HIPCHECK(hipStreamSynchronize(c->stream)); // no launch may still be reading the old tables
-  if (fit((void **)&D.binf, D.binf_n, T.binf.size(), sizeof(double))) return 1;
-  if (fit((void **)&D.ptab, D.ptab_n, T.ptab.size(), sizeof(double))) return 1;
-  if (fit((void **)&D.rcb, D.rcb_n, T.rcb.size(), sizeof(int))) return 1;
-  if (fit((void **)&D.poff, D.poff_n, T.poff.size(), sizeof(int))) return 1;
+  if (D.binf.grow(T.binf.size(), "the stationary pivots") || D.ptab.grow(T.ptab.size(), "the pivot tables") ||
+      D.rcb.grow(T.rcb.size(), "the pivot tables' row counts") || D.poff.grow(T.poff.size(), "the pivot tables' offsets"))
+    return 1;
   HIPCHECK(hipMemcpy(D.binf, T.binf.data(), T.binf.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(D.ptab, T.ptab.data(), T.ptab.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(D.rcb, T.rcb.data(), T.rcb.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -742,17 +736,16 @@ static int build_slab_responses(qgcm_hip_ctx *c) {
   const QgGeom &g = c->g;
   const int nblk = (g.nk + TH_KW - 1) / TH_KW, nm = nblk * g.nl;
   const bool nb_lo = g.joff + g.jlo > 1, nb_hi = g.joff + g.jhi < g.nyg;
-  if (!c->corr.meta) HIPCHECK(hipMalloc((void **)&c->corr.meta, sizeof(int) * 4 * nm));
+  if (c->corr.meta.ensure((size_t)4 * nm, "the slab responses' reach")) return 1;
   std::vector<int> meta((size_t)4 * nm, 0);
   QgThomasParams P;
   fill_thomas_params(c, P, c->wrk, c->tt, g.nl, 0);
   const double tol = 1.0e-19 * P.ftnorm; // three orders below the rounding of the inflow itself
   for (int side = 0; side < 2; ++side) { // 0: inflow from below (PHASE 4, Pv), 1: from above (PHASE 5, Qv)
     if (launch_thomas(c, c->wrk, c->tt, g.nl, 4 + side, nullptr, nullptr, 0, 1, 0, nullptr)) return 1;
-    double *&tab = side ? c->corr.qtab : c->corr.ptab;
+    QgDbl &tab = side ? c->corr.qtab : c->corr.ptab;
     size_t &rows = side ? c->corr.qrows : c->corr.prows;
-    if (tab) HIPCHECK(hipFree(tab));
-    tab = nullptr;
+    tab.reset();
     rows = 0;
     int *d_reach = c->corr.meta + side * nm, *d_off = c->corr.meta + (2 + side) * nm;
     if (!(side ? nb_hi : nb_lo)) continue; // reach 0 everywhere
@@ -766,7 +759,7 @@ static int build_slab_responses(qgcm_hip_ctx *c) {
       off += meta[side * nm + i];
     }
     rows = off;
-    HIPCHECK(hipMalloc((void **)&tab, sizeof(double) * TH_KW * (off ? off : 1)));
+    if (tab.alloc((size_t)TH_KW * (off ? off : 1), "the slab's response table")) return 1;
     HIPCHECK(hipMemcpyAsync(d_off, meta.data() + (2 + side) * nm, sizeof(int) * nm, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_thomas_pack, dim3(nblk, g.nl), dim3(256), 0, c->stream, P, side, (const int *)d_reach, (const int *)d_off, tab);
     HIPCHECK(hipGetLastError());
@@ -801,10 +794,9 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
     }
     if (upload_pivots(c, tab, T)) return 1; // (waits for the stream: nothing reads the old tables any more)
   }
-  if (!sg.msg && dalloc(&sg.msg, (size_t)TH_MSG * g.nl * g.ldw * S)) return 1;
-  if (!ss.cst && dalloc(&ss.cst, (size_t)TH_CST * g.nl * g.ldw * S)) return 1;
-  if (!ss.recs) HIPCHECK(hipMalloc((void **)&ss.recs, sizeof(QgThomasSegRec) * S));
-  if (!ss.meta) HIPCHECK(hipMalloc((void **)&ss.meta, sizeof(int) * 4 * S * nmt));
+  if (sg.msg.ensure((size_t)TH_MSG * g.nl * g.ldw * S, "the segments' messages")) return 1;
+  if (ss.cst.ensure((size_t)TH_CST * g.nl * g.ldw * S, "the segments' constants")) return 1;
+  if (ss.recs.ensure(S, "the segment records") || ss.meta.ensure((size_t)4 * S * nmt, "the segments' reach")) return 1;
   HIPCHECK(hipMemcpy(ss.recs, recs.data(), sizeof(QgThomasSegRec) * S, hipMemcpyHostToDevice));
   std::vector<int> meta((size_t)4 * S * nmt, 0);
   HIPCHECK(hipMemcpy(ss.meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice)); // (ends without a neighbour: reach 0)
@@ -819,9 +811,8 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
   };
   const double tol = 1.0e-19 * P0.ftnorm; // (build_slab_responses)
   for (int side = 0; side < 2; ++side) { // 0: inflow from below (PHASE 4, Pv), 1: from above (PHASE 5, Qv)
-    double *&rtab = side ? ss.qtab : ss.ptab;
-    if (rtab) HIPCHECK(hipFree(rtab));
-    rtab = nullptr;
+    QgDbl &rtab = side ? ss.qtab : ss.ptab;
+    rtab.reset();
     int *d_reach = ss.meta + side * S * nmt, *d_off = ss.meta + (2 + side) * S * nmt;
     int *h_reach = meta.data() + side * S * nmt, *h_off = meta.data() + (2 + side) * S * nmt;
     for (int s = 0; s < S; ++s) {
@@ -839,7 +830,7 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
       off += h_reach[i];
     }
     if ((double)off * TH_KW >= 2147483647.0) QG_FAIL("qgcm_hip_set_grid: the segments' response tables exceed 32-bit offsets");
-    HIPCHECK(hipMalloc((void **)&rtab, sizeof(double) * TH_KW * (off ? off : 1)));
+    if (rtab.alloc((size_t)TH_KW * (off ? off : 1), "the segments' response table")) return 1;
     HIPCHECK(hipMemcpyAsync(d_off, h_off, sizeof(int) * S * nmt, hipMemcpyHostToDevice, c->stream));
     for (int s = side ? 0 : 1; s < (side ? S - 1 : S); ++s) {
       const QgThomasParams P = seg_params(s);
@@ -896,15 +887,8 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
     }
     if (S != sg.S) { // (a second set_grid under another plan: the per-segment buffers are sized by S)
       HIPCHECK(hipStreamSynchronize(c->stream));
-      if (sg.msg) hipFree(sg.msg);
-      sg.msg = nullptr;
-      for (auto &ss : sg.set) {
-        void **ps[] = {(void **)&ss.recs, (void **)&ss.ptab, (void **)&ss.qtab, (void **)&ss.cst, (void **)&ss.meta};
-        for (void **q : ps) {
-          if (*q) hipFree(*q);
-          *q = nullptr;
-        }
-      }
+      sg.msg.reset();
+      for (auto &ss : sg.set) ss = {};
     }
     sg.set[1].boc.clear();
     sg.S = S;
@@ -938,10 +922,7 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   std::vector<double> st(N / 2 + 2);
   const double pi = 3.14159265358979323846264338327950288;
   for (int k = 0; k <= N / 2 + 1; ++k) st[k] = 2.0 * sin((double)k * (pi / (double)N)); // dsinti.f:20-24
-  if (c->twid) hipFree(c->twid);
-  if (c->sintab) hipFree(c->sintab);
-  HIPCHECK(hipMalloc((void **)&c->twid, sizeof(double2) * N));
-  HIPCHECK(hipMalloc((void **)&c->sintab, sizeof(double) * st.size()));
+  if (c->twid.alloc(N, "the twiddle factors") || c->sintab.alloc(st.size(), "the sine table")) return 1;
   HIPCHECK(hipMemcpy(c->twid, tw.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(c->sintab, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice));
   // generic row kernels: two ping-pong buffers, or ONE buffer with in-place stages for long rows
@@ -1093,7 +1074,7 @@ extern "C" int qgcm_hip_set_homog_box(qgcm_hip_handle c, const double *ochom, co
     // device copy of the constraint parameters for the extra workgroup of the generic inverse rows
     QgConstrParams Q;
     fill_constr_params(c, Q);
-    if (!c->d_boxq) HIPCHECK(hipMalloc((void **)&c->d_boxq, sizeof(Q)));
+    if (c->d_boxq.ensure(1, "the constraint parameters")) return 1;
     HIPCHECK(hipMemcpy(c->d_boxq, &Q, sizeof(Q), hipMemcpyHostToDevice));
   }
   return 0;
@@ -1125,7 +1106,7 @@ extern "C" int qgcm_hip_set_homog_cyc(qgcm_hip_handle c, const double *pch1oc, c
     // device copy of the constraint parameters for the fused step path (k_thomas's extra workgroup, k_rfft64_unpack)
     QgCycConstrParams Q;
     fill_cyc_constr_params(c, Q);
-    if (!c->d_cycq) HIPCHECK(hipMalloc((void **)&c->d_cycq, sizeof(Q)));
+    if (c->d_cycq.ensure(1, "the constraint parameters")) return 1;
     HIPCHECK(hipMemcpy(c->d_cycq, &Q, sizeof(Q), hipMemcpyHostToDevice));
   }
   return 0;
@@ -1164,7 +1145,7 @@ extern "C" int qgcm_hip_set_forcing(qgcm_hip_handle c, const double *wekpo, cons
     c->entoc_zero = all_plus_zero(entoc, (size_t)g.nx * g.ny);
   }
   if (xon) {
-    HIPCHECK(hipMemcpyAsync((char *)c->sc + offsetof(QgScalars, xon), xon, sizeof(double) * (g.nl - 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipMemcpyAsync((char *)(QgScalars *)c->sc + offsetof(QgScalars, xon), xon, sizeof(double) * (g.nl - 1), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
   }
   return 0;
@@ -1180,8 +1161,7 @@ extern "C" int qgcm_hip_set_sponge(qgcm_hip_handle c, const double *r_spl, doubl
   drop_graphs(c); // captured steps hold the kernel parameters by value
   const QgGeom &g = c->g;
   if (!r_spl) {
-    if (c->rspl) HIPCHECK(hipFree(c->rspl));
-    c->rspl = nullptr;
+    c->rspl.reset();
     c->c1_spl = 0.0;
     return 0;
   }
@@ -1194,7 +1174,7 @@ extern "C" int qgcm_hip_set_sponge(qgcm_hip_handle c, const double *r_spl, doubl
       if (r_spl[(size_t)j * g.nx] != r_spl[(size_t)j * g.nx + g.nx - 1])
         QG_FAIL("qgcm_hip_set_sponge: r_spl(1,%d) != r_spl(nxpo,%d) - a zonally cyclic ocean needs a ramp that is periodic in x (build with -Dnospl_in_ewbdy_k247)", j + 1, j + 1);
   }
-  if (!c->rspl && dalloc(&c->rspl, (size_t)g.fstride)) return 1;
+  if (c->rspl.ensure((size_t)g.fstride, "the sponge ramp")) return 1;
   c->c1_spl = c1_spl;
   return upload2d(c, c->rspl, g.ldx, r_spl, g.nx, g.ny);
 }
@@ -1994,8 +1974,8 @@ extern "C" int qgcm_hip_ocqbdy_host(qgcm_hip_handle c, double *q, const double *
   if (!c->whole) QG_FAIL("qgcm_hip_ocqbdy_host: only for a handle that owns the whole domain");
   const QgGeom &g = c->g;
   const size_t n = (size_t)g.fstride * g.nl;
-  double *dp = nullptr, *dq = nullptr;
-  if (dalloc(&dp, n) || dalloc(&dq, n)) return 1;
+  QgDbl dp, dq; // scratch
+  if (dp.alloc(n, "the scratch copy of p") || dq.alloc(n, "the scratch copy of q")) return 1;
   const long rows = (long)g.ny * g.nl;
   int rc = upload2d(c, dp, g.ldx, p, g.nx, rows) || upload2d(c, dq, g.ldx, q, g.nx, rows);
   if (!rc) {
@@ -2009,8 +1989,6 @@ extern "C" int qgcm_hip_ocqbdy_host(qgcm_hip_handle c, double *q, const double *
     if (rc) snprintf(g_err, sizeof(g_err), "qgcm_hip_ocqbdy_host: launch failed");
   }
   if (!rc) rc = download2d(c, q, dq, g.ldx, g.nx, rows);
-  hipFree(dp);
-  hipFree(dq);
   return rc;
 }
 
@@ -2031,19 +2009,16 @@ extern "C" int qgcm_hip_oml_init(qgcm_hip_handle c, const qgcm_hip_oml_params *p
   auto &o = c->oml;
   drop_graphs(c);
   o.prm = *p;
-  if (!o.sst[0]) {
+  if (!o.diag) { // (the last of the buffers: a call that failed half-way is made good by the next)
     o.ldt = round_up(nxt, 16);
     const size_t nT = (size_t)o.ldt * nyt, nP = (size_t)g.ldx * g.ny;
     o.nblkA = ((nxt + OML_TX - 1) / OML_TX) * ((nyt + OML_SH - 1) / OML_SH);
     o.nblkB = ((g.nx + OML_TX - 1) / OML_TX) * ((g.ny + OML_TY * OML_RPT * OML_ERR - 1) / (OML_TY * OML_RPT * OML_ERR));
-    struct { double **ptr; size_t n; } bufs[] = {{&o.sst[0], nT}, {&o.sst[1], nT}, {&o.sst[2], nT}, {&o.fnet, nT}, {&o.wekto, nT},
-                                                 {&o.xfo, nT}, {&o.taux, nP}, {&o.tauy, nP}, {&o.partA, (size_t)3 * o.nblkA},
-                                                 {&o.partB, (size_t)3 * o.nblkB}, {&o.diag, 2}};
-    for (auto &b : bufs) {
-      HIPCHECK(hipMalloc((void **)b.ptr, b.n * sizeof(double)));
-      HIPCHECK(hipMemsetAsync(*b.ptr, 0, b.n * sizeof(double), c->stream));
-    }
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    struct { QgDbl *buf; size_t n; } bufs[] = {{&o.sst[0], nT}, {&o.sst[1], nT}, {&o.sst[2], nT}, {&o.fnet, nT}, {&o.wekto, nT},
+                                               {&o.xfo, nT}, {&o.taux, nP}, {&o.tauy, nP}, {&o.partA, (size_t)3 * o.nblkA},
+                                               {&o.partB, (size_t)3 * o.nblkB}, {&o.diag, 2}};
+    for (auto &b : bufs)
+      if (b.buf->ensure(b.n, "a buffer of the ocean mixed layer")) return 1;
     o.is = 0;
     o.ism = 1;
   }
@@ -2514,37 +2489,27 @@ extern "C" int qgcm_hip_aml_init(qgcm_hip_handle c, const qgcm_hip_aml_params *p
   auto &a = c->aml;
   auto &m = c->atmon;
   drop_graphs(c);
-  if (!a.ast[0]) {
+  if (!a.diag) { // (the last of the buffers: a call that failed half-way is made good by the next)
     if (!m.ldt) m.ldt = round_up(nxt, 16);
     a.ldt = m.ldt;
     const size_t nT = (size_t)a.ldt * nyt, nP = (size_t)g.ldx * g.ny;
     a.nblkA = ((nxt + OML_TX - 1) / OML_TX) * ((nyt + AML_SH - 1) / AML_SH);
     a.nblkB = ((g.nx + OML_TX - 1) / OML_TX) * ((g.ny + OML_TY * OML_RPT - 1) / (OML_TY * OML_RPT));
-    struct { double **ptr; size_t n; } bufs[] = {{&a.ast[0], nT}, {&a.ast[1], nT}, {&a.ast[2], nT}, {&a.hm[0], nT}, {&a.hm[1], nT},
-                                                 {&a.hm[2], nT}, {&a.xfa, nT}, {&a.xc1, nT}, {&a.dtop, nP},
-                                                 {&a.partA, (size_t)3 * a.nblkA}, {&a.partB, (size_t)3 * a.nblkB}, {&a.diag, 2}};
-    bool failed = false;
+    // the mixed layer's own buffers, then the inputs that others write: fnetat (xforc's heat half or
+    // qgcm_hip_set_atm_tav_fields), wekta, uekat, vekat
+    struct { QgDbl *buf; size_t n; } bufs[] = {{&a.ast[0], nT}, {&a.ast[1], nT}, {&a.ast[2], nT}, {&a.hm[0], nT}, {&a.hm[1], nT},
+                                               {&a.hm[2], nT}, {&a.xfa, nT}, {&a.xc1, nT}, {&a.dtop, nP},
+                                               {&a.partA, (size_t)3 * a.nblkA}, {&a.partB, (size_t)3 * a.nblkB},
+                                               {&c->tav.fnet, nT}, {&m.wekta, nT}, {&m.uekat, (size_t)g.ldx * nyt},
+                                               {&m.vekat, (size_t)m.ldt * g.ny}, {&a.diag, 2}};
     for (auto &b : bufs)
-      if (!failed && dalloc(b.ptr, b.n)) failed = true;
-    // the inputs that others write: fnetat (xforc's heat half or qgcm_hip_set_atm_tav_fields), wekta, uekat, vekat
-    struct { double **ptr; size_t n; } in[] = {{&c->tav.fnet, nT}, {&m.wekta, nT}, {&m.uekat, (size_t)g.ldx * nyt},
-                                               {&m.vekat, (size_t)m.ldt * g.ny}};
-    for (auto &b : in)
-      if (!failed && !*b.ptr && dalloc(b.ptr, b.n)) failed = true;
-    if (failed) { // nothing of the mixed layer stays behind: a later init starts over
-      for (auto &b : bufs) {
-        if (*b.ptr) hipFree(*b.ptr);
-        *b.ptr = nullptr;
-      }
-      return 1;
-    }
-    // what qgcm_hip_set_atm_monitor_fields was given before becomes the current level
-    double *old[2] = {m.ast, m.hmixa}, *cur[2] = {a.ast[0], a.hm[0]};
-    for (int k = 0; k < 2; ++k)
-      if (old[k]) {
-        HIPCHECK(hipMemcpy(cur[k], old[k], nT * sizeof(double), hipMemcpyDeviceToDevice));
-        HIPCHECK(hipFree(old[k]));
-      }
+      if (b.buf->ensure(b.n, "a buffer of the atmospheric mixed layer")) return 1;
+    // what qgcm_hip_set_atm_monitor_fields was given before becomes the current level: copy, give the old owners'
+    // memory back, point atmon.ast / atmon.hmixa at the rotating buffers
+    if (m.ast_own) HIPCHECK(hipMemcpy(a.ast[0], m.ast_own, nT * sizeof(double), hipMemcpyDeviceToDevice));
+    if (m.hmixa_own) HIPCHECK(hipMemcpy(a.hm[0], m.hmixa_own, nT * sizeof(double), hipMemcpyDeviceToDevice));
+    m.ast_own.reset();
+    m.hmixa_own.reset();
     aml_set_idx(c, 0, 1);
   }
   a.prm = *p;
@@ -2680,13 +2645,9 @@ extern "C" int qgcm_hip_aml_get_diag(qgcm_hip_handle c, double *entat, double *d
 // ---------------------------------------------------------------------------
 // momentum half of xforc: src/xfosubs.F:137-709 on the device, kernels in k_xforc.h
 // ---------------------------------------------------------------------------
-static void xf_free(qgcm_hip_ctx *a) {
+// xforc is off until qgcm_hip_xforc_init has gone through (it replaces the buffers)
+static void xf_off(qgcm_hip_ctx *a) {
   auto &x = a->xf;
-  double **ps[] = {&x.u1at, &x.v1at, &x.txf, &x.tyf, &x.wf, &x.tab};
-  for (double **p : ps) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-  }
   x.on = x.coupled = false;
   x.oc = nullptr;
   x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
@@ -2726,7 +2687,7 @@ extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, cons
   }
   auto &x = atm->xf;
   HIPCHECK(hipStreamSynchronize(atm->stream));
-  xf_free(atm);
+  xf_off(atm);
   x.prm = *p;
   x.prm.stbbb = x.prm.stbus = x.prm.stbvs = x.prm.stbun = x.prm.stbvn = nullptr; // (host pointers are not kept)
   const QgGeom &g = atm->g;
@@ -2734,11 +2695,10 @@ extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, cons
   x.ldf = round_up(nxpaor, 16);
   x.ldtf = round_up(nxpaor - 1, 16);
   const size_t nfine = (size_t)x.ldf * nypaor, npl = (size_t)(ndxr + 1) * ndxr;
-  if (dalloc(&x.u1at, (size_t)g.ldx * g.ny) || dalloc(&x.v1at, (size_t)g.ldx * g.ny) || dalloc(&x.txf, nfine) ||
-      dalloc(&x.tyf, nfine) || dalloc(&x.wf, (size_t)x.ldtf * (nypaor - 1)) || dalloc(&x.tab, 5 * 16 * npl)) {
-    xf_free(atm);
+  if (x.u1at.alloc((size_t)g.ldx * g.ny, "xforc's u1at") || x.v1at.alloc((size_t)g.ldx * g.ny, "xforc's v1at") ||
+      x.txf.alloc(nfine, "xforc's fine stress") || x.tyf.alloc(nfine, "xforc's fine stress") ||
+      x.wf.alloc((size_t)x.ldtf * (nypaor - 1), "xforc's fine Ekman velocity") || x.tab.alloc(5 * 16 * npl, "xforc's weight tables"))
     return 1;
-  }
   {
     // MODULE xfosubs holds stb**(16, 0:ndxr, 0:ndxr); the kernels read tab[k][jj][ii], ii = 0..ndxr-1 (k_xforc.h)
     std::vector<double> t(5 * 16 * npl);
@@ -2753,18 +2713,19 @@ extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, cons
   // the destinations beside wekpa / wekpo: the atmosphere's monitor fields and the ocean's (zero until the first call)
   auto &m = atm->atmon;
   if (!m.ldt) m.ldt = round_up(nxta, 16);
-  struct { double **ptr; size_t n; } dst[] = {{&m.wekta, (size_t)m.ldt * nyta}, {&m.tauxa, (size_t)g.ldx * g.ny},
-                                              {&m.tauya, (size_t)g.ldx * g.ny}, {&m.uekat, (size_t)g.ldx * nyta},
-                                              {&m.vekat, (size_t)m.ldt * g.ny}};
+  struct { QgDbl *buf; size_t n; } dst[] = {{&m.wekta, (size_t)m.ldt * nyta}, {&m.tauxa, (size_t)g.ldx * g.ny},
+                                            {&m.tauya, (size_t)g.ldx * g.ny}, {&m.uekat, (size_t)g.ldx * nyta},
+                                            {&m.vekat, (size_t)m.ldt * g.ny}};
   for (auto &d : dst)
-    if (!*d.ptr && dalloc(d.ptr, d.n)) return 1;
+    if (d.buf->ensure(d.n, "an atmosphere monitor field")) return 1;
   if (oc) {
     auto &mo = oc->mon;
     const QgGeom &go = oc->g;
     if (!mo.ldt) mo.ldt = round_up(go.nxt, 16);
-    if (!mo.taux && dalloc(&mo.taux, (size_t)go.ldx * go.ny)) return 1;
-    if (!mo.tauy && dalloc(&mo.tauy, (size_t)go.ldx * go.ny)) return 1;
-    if (!mo.wekto && dalloc(&mo.wekto, (size_t)mo.ldt * (go.ny - 1))) return 1;
+    if (mo.taux.ensure((size_t)go.ldx * go.ny, "an ocean monitor field") ||
+        mo.tauy.ensure((size_t)go.ldx * go.ny, "an ocean monitor field") ||
+        mo.wekto.ensure((size_t)mo.ldt * (go.ny - 1), "an ocean monitor field"))
+      return 1;
   }
   if (!x.ev_oc) HIPCHECK(hipEventCreateWithFlags(&x.ev_oc, hipEventDisableTiming));
   if (!x.ev_atm) HIPCHECK(hipEventCreateWithFlags(&x.ev_atm, hipEventDisableTiming));
@@ -2916,19 +2877,6 @@ extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, doubl
 // ---------------------------------------------------------------------------
 // heat half of xforc: src/xfosubs.F:711-853 on the device, kernels in k_xforc.h
 // ---------------------------------------------------------------------------
-static void xf_heat_free(qgcm_hip_ctx *a) {
-  auto &h = a->xf.heat;
-  double **ps[] = {&h.fsa, &h.fso, &h.wx, &h.wy, &h.cell, &h.part, &h.scal};
-  for (double **p : ps) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-  }
-  if (h.ix) hipFree(h.ix);
-  if (h.iy) hipFree(h.iy);
-  h.ix = h.iy = nullptr;
-  h.on = false;
-}
-
 extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p) {
   const char *who = "qgcm_hip_xforc_heat_init";
   if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
@@ -2971,21 +2919,16 @@ extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm,
     iy[nyto + jo] = jap;
   }
   HIPCHECK(hipStreamSynchronize(atm->stream));
-  xf_heat_free(atm);
   auto &h = atm->xf.heat;
+  h.on = false; // (until this call has gone through: it replaces the buffers)
   const int ncell = x.nxaooc * x.nyaooc;
   h.nblkL = ((nxta + 63) / 64) * ((nyta + 3) / 4);
-  if (dalloc(&h.fsa, nyta) || dalloc(&h.fso, nyto) || dalloc(&h.wx, 2 * (size_t)nxto) || dalloc(&h.wy, 2 * (size_t)nyto) ||
-      dalloc(&h.cell, ncell) || dalloc(&h.part, 3 * (size_t)ncell + h.nblkL) || dalloc(&h.scal, 4)) {
-    xf_heat_free(atm);
+  if (h.fsa.alloc(nyta, "fsprim of the atmosphere") || h.fso.alloc(nyto, "fsprim of the ocean") ||
+      h.wx.alloc(2 * (size_t)nxto, "bilint's x weights") || h.wy.alloc(2 * (size_t)nyto, "bilint's y weights") ||
+      h.cell.alloc(ncell, "the per-cell sums") || h.part.alloc(3 * (size_t)ncell + h.nblkL, "the heat half's partial sums") ||
+      h.scal.alloc(4, "the heat half's results") || h.ix.alloc(2 * (size_t)nxto, "bilint's x indices") ||
+      h.iy.alloc(2 * (size_t)nyto, "bilint's y indices"))
     return 1;
-  }
-  if (hipMalloc((void **)&h.ix, 2 * (size_t)nxto * sizeof(int)) != hipSuccess ||
-      hipMalloc((void **)&h.iy, 2 * (size_t)nyto * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    xf_heat_free(atm);
-    QG_FAIL("%s: out of device memory for the index tables", who);
-  }
   HIPCHECK(hipMemcpy(h.fsa, p->fsa, nyta * sizeof(double), hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(h.fso, p->fso, nyto * sizeof(double), hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(h.wx, wx.data(), wx.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -3279,9 +3222,8 @@ extern "C" int qgcm_hip_set_thomas_consts(qgcm_hip_handle c, const double *gath_
   drop_graphs(c);
   if (c->th_cgath_ranks != nranks) {
     HIPCHECK(hipStreamSynchronize(c->stream));
-    if (c->th_cgath) hipFree(c->th_cgath);
-    c->th_cgath = nullptr;
-    if (dalloc(&c->th_cgath, n)) return 1;
+    c->th_cgath_ranks = 0;
+    if (c->th_cgath.alloc(n, "all ranks' slab constants")) return 1;
     c->th_cgath_ranks = nranks;
   }
   HIPCHECK(hipMemcpyAsync(c->th_cgath, gath_dev, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -3469,7 +3411,7 @@ extern "C" int qgcm_hip_comm_init(qgcm_hip_handle c, const char *id, int nbytes,
   QgRccl *api = qg_rccl(g_err, sizeof(g_err));
   if (!api) return 1;
   HIPCHECK(hipSetDevice(c->device));
-  QgSlabComm *m = new QgSlabComm;
+  std::unique_ptr<QgSlabComm> m(new QgSlabComm); // (a failure below leaves the handle without a communicator)
   m->api = api;
   m->rank = rank;
   m->nranks = nranks;
@@ -3477,29 +3419,26 @@ extern "C" int qgcm_hip_comm_init(qgcm_hip_handle c, const char *id, int nbytes,
   m->halo_p2p = hp ? atoi(hp) != 0 : true; // default: the two neighbours only (an all-gather moves nranks x the bytes)
   m->th_len = slab_msg_len_oml(c);
   m->halo_len = halo_msg_len(c);
-  c->sc_comm = m; // owned by the handle from here on (freed in qgcm_hip_destroy)
   ncclUniqueId u;
   memcpy(&u, id, sizeof(u));
   NCCLCHECK(api, api->CommInitRank(&m->comm, nranks, u, rank));
-  struct { double **p; size_t n; } bufs[] = {{&m->th_send, m->th_len}, {&m->th_gath, m->th_len * nranks},
+  struct { QgDbl *buf; size_t n; } bufs[] = {{&m->th_send, m->th_len}, {&m->th_gath, m->th_len * nranks},
                                              {&m->h_send, 2 * m->halo_len}, {&m->h_gath, 2 * m->halo_len * nranks},
                                              {&m->oml_send, 4}, {&m->oml_gath, (size_t)4 * nranks}};
-  for (auto &b : bufs) {
-    HIPCHECK(hipMalloc((void **)b.p, b.n * sizeof(double)));
-    HIPCHECK(hipMemsetAsync(*b.p, 0, b.n * sizeof(double), c->stream));
-  }
+  for (auto &b : bufs)
+    if (b.buf->alloc(b.n, "an exchange buffer")) return 1;
   // the right-hand-side independent part of the slab summaries (D, E, SP, SQ) is exchanged once
   if (nranks > 1) {
     const size_t nc = (size_t)TH_CST * g.nl * g.ldw;
-    if (c->th_cgath) hipFree(c->th_cgath);
-    c->th_cgath = nullptr;
-    if (dalloc(&c->th_cgath, nc * nranks)) return 1;
+    c->th_cgath_ranks = 0;
+    if (c->th_cgath.alloc(nc * nranks, "all ranks' slab constants")) return 1;
     c->th_cgath_ranks = nranks;
     NCCLCHECK(api, api->AllGather(c->slabDE, c->th_cgath, nc, ncclDouble, m->comm, c->stream));
   }
   HIPCHECK(hipStreamSynchronize(c->stream));
   const char *gm = getenv("QGCM_HIP_SLAB_GRAPH");
   c->slab_graph_mode = gm && atoi(gm) != 0;
+  c->sc_comm = m.release(); // owned by the handle from here on (~qgcm_hip_ctx)
   return 0;
 }
 
@@ -3540,9 +3479,9 @@ extern "C" int qgcm_hip_comm_probe(qgcm_hip_handle c, int reps, double *us) {
   QgSlabComm *m = c->sc_comm;
   const int r = m->rank, P = m->nranks;
   const size_t n = m->halo_len;
-  hipEvent_t a, b;
-  HIPCHECK(hipEventCreate(&a));
-  HIPCHECK(hipEventCreate(&b));
+  QgEventPair ev;
+  if (ev.create()) return 1;
+  const hipEvent_t a = ev.a, b = ev.b;
   for (int which = 0; which < 3; ++which) {
     for (int pass = 0; pass < 2; ++pass) { // pass 0 warms the algorithm / channel set-up
       const int nrep = pass ? reps : 3;
@@ -3573,8 +3512,6 @@ extern "C" int qgcm_hip_comm_probe(qgcm_hip_handle c, int reps, double *us) {
       if (pass) us[which] = 1e3 * ms / nrep;
     }
   }
-  hipEventDestroy(a);
-  hipEventDestroy(b);
   return 0;
 }
 
@@ -3733,9 +3670,9 @@ extern "C" int qgcm_hip_prepare_steps(qgcm_hip_handle c, int s0, int n) {
 
 extern "C" int qgcm_hip_time_steps(qgcm_hip_handle c, int s0, int n, float *ms) {
   if (check_ready(c, "qgcm_hip_time_steps")) return 1;
-  hipEvent_t a, b;
-  HIPCHECK(hipEventCreate(&a));
-  HIPCHECK(hipEventCreate(&b));
+  QgEventPair ev;
+  if (ev.create()) return 1;
+  const hipEvent_t a = ev.a, b = ev.b;
   // instantiate the graphs the run replays outside the timed region
   if (steps_impl(c, s0, n, true)) return 1;
   HIPCHECK(hipEventRecord(a, c->stream));
@@ -3752,8 +3689,6 @@ extern "C" int qgcm_hip_time_steps(qgcm_hip_handle c, int s0, int n, float *ms) 
   float t = 0.f;
   HIPCHECK(hipEventElapsedTime(&t, a, b));
   if (ms) *ms = t;
-  hipEventDestroy(a);
-  hipEventDestroy(b);
   return 0;
 }
 
@@ -3795,14 +3730,13 @@ extern "C" int qgcm_hip_profile_steps(qgcm_hip_handle c, int s0, int n, double *
 
 extern "C" int qgcm_hip_copy_bandwidth(qgcm_hip_handle c, size_t bytes, int reps, double *gbps) {
   if (!c || !gbps) QG_FAIL("qgcm_hip_copy_bandwidth: null argument");
-  double2 *a = nullptr, *b = nullptr;
+  QgBuf<double2> a, b; // scratch
   const long n = (long)(bytes / sizeof(double2));
-  HIPCHECK(hipMalloc((void **)&a, n * sizeof(double2)));
-  HIPCHECK(hipMalloc((void **)&b, n * sizeof(double2)));
+  if (a.alloc(n, "the probe's source") || b.alloc(n, "the probe's destination")) return 1;
   HIPCHECK(hipMemset(a, 1, n * sizeof(double2)));
-  hipEvent_t e0, e1;
-  HIPCHECK(hipEventCreate(&e0));
-  HIPCHECK(hipEventCreate(&e1));
+  QgEventPair ev;
+  if (ev.create()) return 1;
+  const hipEvent_t e0 = ev.a, e1 = ev.b;
   hipLaunchKernelGGL(k_copy, dim3(2048), dim3(256), 0, c->stream, a, b, n);
   HIPCHECK(hipEventRecord(e0, c->stream));
   for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_copy, dim3(2048), dim3(256), 0, c->stream, a, b, n);
@@ -3811,10 +3745,6 @@ extern "C" int qgcm_hip_copy_bandwidth(qgcm_hip_handle c, size_t bytes, int reps
   float ms = 0.f;
   HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
   *gbps = 2.0 * (double)n * sizeof(double2) * reps / (ms * 1e-3) / 1e9;
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipFree(a);
-  hipFree(b);
   return 0;
 }
 
@@ -3825,15 +3755,13 @@ extern "C" int qgcm_hip_stream_mix_bandwidth(qgcm_hip_handle c, int nr, int nw, 
   if (!c || !gbps) QG_FAIL("qgcm_hip_stream_mix_bandwidth: null argument");
   field_bytes = field_bytes / 4096 * 4096;
   if (field_bytes == 0 || reps < 1) QG_FAIL("qgcm_hip_stream_mix_bandwidth: bad size / repetitions");
-  double2 *a = nullptr, *b = nullptr;
+  QgBuf<double2> a, b; // scratch
   const long nper = (long)(field_bytes / sizeof(double2));
-  HIPCHECK(hipMalloc((void **)&a, field_bytes * nr));
-  HIPCHECK(hipMalloc((void **)&b, field_bytes * (nw > 0 ? nw : 1)));
-  HIPCHECK(hipMemsetAsync(a, 0, field_bytes * nr, c->stream));
-  HIPCHECK(hipMemsetAsync(b, 0, field_bytes * (nw > 0 ? nw : 1), c->stream));
-  hipEvent_t e0, e1;
-  HIPCHECK(hipEventCreate(&e0));
-  HIPCHECK(hipEventCreate(&e1));
+  if (a.alloc((size_t)nper * nr, "the probe's sources") || b.alloc((size_t)nper * (nw > 0 ? nw : 1), "the probe's destinations"))
+    return 1;
+  QgEventPair ev;
+  if (ev.create()) return 1;
+  const hipEvent_t e0 = ev.a, e1 = ev.b;
   auto launch = [&]() -> int {
     const dim3 grid(2048), block(256);
     if (nr == 15 && nw == 6) hipLaunchKernelGGL((k_stream_mix<15, 6>), grid, block, 0, c->stream, a, b, nper);
@@ -3854,10 +3782,6 @@ extern "C" int qgcm_hip_stream_mix_bandwidth(qgcm_hip_handle c, int nr, int nw, 
     HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
     *gbps = (double)field_bytes * (nr + nw) * reps / (ms * 1e-3) / 1e9;
   }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipFree(a);
-  hipFree(b);
   if (rc) QG_FAIL("qgcm_hip_stream_mix_bandwidth: supported mixes are 15:6, 3:3, 5:3 and 1:1");
   return 0;
 }

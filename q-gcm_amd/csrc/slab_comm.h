@@ -60,13 +60,23 @@ struct QgSlabComm {
   int rank = 0, nranks = 1;
   bool halo_p2p = true; // halo rows by grouped send/recv with the two neighbours (false: one all-gather of all edge rows)
   size_t th_len = 0, halo_len = 0;
-  double *th_send = nullptr, *th_gath = nullptr; // slab summaries of the y sweeps (k_thomas.h, TH_MSG per mode and wavenumber)
-  double *h_send = nullptr, *h_gath = nullptr;   // edge rows: [to lower | to upper] per rank
-  double *oml_send = nullptr, *oml_gath = nullptr; // mixed layer: the three sums of a slab's k_oml_step (3 per rank)
+  QgDbl th_send, th_gath;   // slab summaries of the y sweeps (k_thomas.h, TH_MSG per mode and wavenumber)
+  QgDbl h_send, h_gath;     // edge rows: [to lower | to upper] per rank
+  QgDbl oml_send, oml_gath; // mixed layer: the three sums of a slab's k_oml_step (3 per rank)
   // halo exchange overlapped with the inner tile rows of the next step's tendency launch (qgcm_hip_comm_set_overlap):
   // the exchange and the halo unpack run on cstream, forked from / joined to the handle's stream by events
   bool overlap = false, pending = false;
   bool outer_done = false; // the pending exchange's stream has also run the outer tile rows of the next step's tendency
   hipStream_t cstream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_halo = nullptr;
+
+  QgSlabComm() = default;
+  QgSlabComm(const QgSlabComm &) = delete;
+  // the communicator goes before its buffers (the members free them afterwards)
+  ~QgSlabComm() {
+    if (comm) api->CommDestroy(comm);
+    if (ev_fork) hipEventDestroy(ev_fork);
+    if (ev_halo) hipEventDestroy(ev_halo);
+    if (cstream) hipStreamDestroy(cstream);
+  }
 };

@@ -138,6 +138,7 @@ SYMBOLS = [
     "qgcm_hip_aml_init", "qgcm_hip_aml_set_state", "qgcm_hip_aml_get_state", "qgcm_hip_aml", "qgcm_hip_aml_get_diag",
     "qgcm_hip_xforc_heat_init", "qgcm_hip_xforc_heat_get",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
+    "qgcm_hip_debug_live_allocs",
 ]
 
 _lib = None
@@ -303,6 +304,8 @@ def load_library():
     L.qgcm_hip_stream_mix_bandwidth.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_int, dp]
     L.qgcm_hip_stream.argtypes = [vp]
     L.qgcm_hip_stream.restype = vp
+    if hasattr(L, "qgcm_hip_debug_live_allocs"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_debug_live_allocs.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -310,6 +313,14 @@ def load_library():
 def check(rc):
     if rc != 0:
         raise QgcmHipError(load_library().qgcm_hip_last_error().decode())
+
+
+def live_allocs():
+    """(blocks, bytes) of device memory the library holds in this process right now, over all handles
+    (qgcm_hip_debug_live_allocs): exact and process-local, for tests of what a handle gives back."""
+    blocks, nbytes = C.c_long(0), C.c_size_t(0)
+    check(load_library().qgcm_hip_debug_live_allocs(C.byref(blocks), C.byref(nbytes)))
+    return blocks.value, nbytes.value
 
 
 THOMAS_MAX_ROWS = 2048  # QGCM_HIP_THOMAS_MAX_ROWS
