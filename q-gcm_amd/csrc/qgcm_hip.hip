@@ -207,7 +207,6 @@ struct qgcm_hip_ctx {
   const double *slab_gath = nullptr;       // not owned - cyclic y-slabs: the gathered step messages of the last thomas phase 2
   int slab_nranks = 1;
   const double *oml_gath = nullptr;        // not owned - y-slabs: the gathered sums of the mixed layer's stage 10 (3, nranks)
-  double *bpart_out = nullptr;             // not owned - where k_tend's extra workgroups put the boundary line sums (bpart, or the tail of the step message)
   QgThomasTab tt, tt_tmp;                  // Thomas pivot tables of the modal solves / of the last qgcm_hip_helmholtz
   // whole-domain oceans whose column is cut into segments (k_thomas.h: k_thomas_seg, k_thomas_corr_seg): the plan, and
   // per set of diagonals - [0] the modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot
@@ -254,7 +253,6 @@ struct qgcm_hip_ctx {
   bool no_fused_unpack;   // QGCM_HIP_NO_FUSED_UNPACK=1: separate inverse transform and unpack launches (A/B + tests)
   int cu_first = 0, cu_count = 0; // qgcm_hip_set_cu_range: the CUs this handle's stream may use (0: all)
   bool no_fused_avg;      // QGCM_HIP_NO_FUSED_AVG=1: leapfrog averaging as a launch of its own inside qgcm_hip_steps (A/B + tests)
-  bool avg_now = false;   // one_step: this step's kernels store the averaged time level (k_tend, k_dst64_unpack)
   bool no_fused_constr;   // QGCM_HIP_NO_FUSED_CONSTR=1: keep the k_constr_box launch inside qgcm_hip_steps (A/B + tests)
   bool tend_wide;         // QGCM_HIP_TEND_WIDE=1: the tendency kernel's HBM-bound instantiation (32-wide tiles, plain stores) at any size (tests)
   // The device buffer holds +0.0 everywhere (bit patterns: -0.0 does not count), known on the host: set by the zero fill
@@ -393,7 +391,7 @@ struct qgcm_hip_ctx {
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
-  std::map<int, hipGraphExec_t> slab_graphs;
+  std::map<long long, hipGraphExec_t> slab_graphs;
   bool slab_graph_mode = false; // QGCM_HIP_SLAB_GRAPH=1: capture 50 distributed steps (collectives included)
   size_t dst_lds;
 
@@ -1359,7 +1357,7 @@ struct QgStepPlan {
                 // the Thomas launch, part B in the inverse launch (cyclic)
   bool upd_dpi; // k_tend steps dpioc / dpiocp (the constraint solve of CONSTR_INV_WAVE starts from the stepped values)
   bool wtq;     // k_tend: write-through pair stores of the new qo and 16-wide tiles
-  bool avg_ok;  // a leapfrog-averaging step may be fused into k_tend and the fused inverse kernel (avg_now)
+  bool avg_ok;  // a leapfrog-averaging step may be fused into k_tend and the fused inverse kernel
 };
 
 // in_step: inside qgcm_hip_steps (k_tend has stepped dpioc where the plan says so, the boundary PV is fused into the
@@ -1419,7 +1417,11 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
 static void launch_tend_z(int zm, int nl, bool cyc, bool wtq, bool avg, dim3 grid, hipStream_t stream, const QgTendParams &P,
                           const QgCycSumParams &S, const QgOmlFinal &F);
 
-static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = false, int part = TEND_ALL) {
+// avg: the launch stores the averaged time level (one_step); bpart: where the extra workgroups put the boundary line
+// sums (nullptr: c->bpart; y-slabs: the tail of the step message); st: nullptr = the handle's stream
+static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = false, int part = TEND_ALL, bool avg = false,
+                       double *bpart = nullptr, hipStream_t st = nullptr) {
+  if (!st) st = c->stream;
   const QgGeom &g = c->g;
   const qgcm_hip_params &pr = c->prm;
   QgTendParams P;
@@ -1453,7 +1455,7 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   // tiles at the HBM-bound sizes (k_tend.h)
   const QgStepPlan pl = step_plan(c, true);
   const bool wtq = pl.wtq;
-  if (c->avg_now && (part != TEND_ALL || !pl.avg_ok)) QG_FAIL("k_tend: the fused leapfrog averaging belongs to whole-domain steps of the fused inverse-row kernels");
+  if (avg && (part != TEND_ALL || !pl.avg_ok)) QG_FAIL("k_tend: the fused leapfrog averaging belongs to whole-domain steps of the fused inverse-row kernels");
   const TendTiling T = g.cyc ? (wtq ? tend_tiling<true, TEND_TX>(g) : tend_tiling<true, TEND_TX_WIDE>(g))
                              : (wtq ? tend_tiling<false, TEND_TX>(g) : tend_tiling<false, TEND_TX_WIDE>(g));
   if (part != TEND_ALL && T.gy < 3) QG_FAIL("k_tend: a slab of fewer than three tile rows cannot be split");
@@ -1466,7 +1468,7 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   if (g.cyc) {
     S.g = g;
     S.pom = P.pom; S.po = P.po; S.qo = P.qo;
-    S.part = c->bpart_out ? c->bpart_out : c->bpart;
+    S.part = bpart ? bpart : c->bpart;
     S.bcfaco = P.bcfaco; S.dxom2 = P.dxom2; S.adfaco = P.adfaco; S.fnot = pr.fnot;
     S.dxo = pr.dxo; S.dyo = pr.dyo;
   }
@@ -1474,25 +1476,25 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   fill_oml_final(c, F, oml_final && (c->oml.on || c->aml.on) && part != TEND_OUTER);
   const int nextra = part == TEND_INNER ? 0 : (g.cyc ? g.nl * 2 * BSUM_NB : T.nedge);
   dim3 grid(8 * ((ntiles + 7) / 8) + nextra); // 1-D: the kernel maps blockIdx -> tile per XCD band, then edge / line-sum work
-  KTimer t(c, KN_TEND);
+  KTimer t(c, KN_TEND, st);
   // the ONE place that picks between k_tend and its zero-field variants: qgostep, one_step, the slab stages (whole,
   // inner and outer tile windows) and qgastep all launch from here
   const int zm = tend_zmask(c);
 #define QG_TEND(NLV)                                                                                       \
-  if (g.cyc && wtq) hipLaunchKernelGGL((k_tend<NLV, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
-  else if (g.cyc) hipLaunchKernelGGL((k_tend<NLV, true, false>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
-  else if (wtq) hipLaunchKernelGGL((k_tend<NLV, false, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); \
-  else hipLaunchKernelGGL((k_tend<NLV, false, false>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F)
+  if (g.cyc && wtq) hipLaunchKernelGGL((k_tend<NLV, true, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F); \
+  else if (g.cyc) hipLaunchKernelGGL((k_tend<NLV, true, false>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F); \
+  else if (wtq) hipLaunchKernelGGL((k_tend<NLV, false, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F); \
+  else hipLaunchKernelGGL((k_tend<NLV, false, false>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F)
   if (zm) { // (tend_zmask: nl <= 4) the same choice of NL, CYC, WTQ, AVG as below, among the variants
-    launch_tend_z(zm, g.nl, g.cyc, wtq, c->avg_now, grid, c->stream, P, S, F);
-  } else if (c->avg_now && g.cyc) { // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does the rest)
-    if (wtq) hipLaunchKernelGGL((k_tend<3, true, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F);
-    else hipLaunchKernelGGL((k_tend<3, true, false, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F);
-  } else if (c->avg_now) { // the step before a leapfrog averaging stores the averaged qo itself (one_step)
+    launch_tend_z(zm, g.nl, g.cyc, wtq, avg, grid, st, P, S, F);
+  } else if (avg && g.cyc) { // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does the rest)
+    if (wtq) hipLaunchKernelGGL((k_tend<3, true, true, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F);
+    else hipLaunchKernelGGL((k_tend<3, true, false, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F);
+  } else if (avg) { // the step before a leapfrog averaging stores the averaged qo itself (one_step)
     switch (g.nl) {
-      case 2: hipLaunchKernelGGL((k_tend<2, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); break;
-      case 3: hipLaunchKernelGGL((k_tend<3, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); break;
-      default: hipLaunchKernelGGL((k_tend<4, false, true, true>), grid, dim3(TEND_NT), 0, c->stream, QG_TEND_VALS(P, F), P, S, F); break;
+      case 2: hipLaunchKernelGGL((k_tend<2, false, true, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F); break;
+      case 3: hipLaunchKernelGGL((k_tend<3, false, true, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F); break;
+      default: hipLaunchKernelGGL((k_tend<4, false, true, true>), grid, dim3(TEND_NT), 0, st, QG_TEND_VALS(P, F), P, S, F); break;
     }
   } else {
     QG_SWITCH_NL(g.nl, QG_TEND, "k_tend");
@@ -1742,9 +1744,9 @@ static void fill_bdy_params(qgcm_hip_ctx *c, QgBdyParams &P) {
 }
 
 // what the unpack kernels read, stand-alone or fused with the inverse rows.  msg_lo / msg_hi: the y-slab halo messages
-// written by the same threads (slab stage 2).  In an averaging step of one_step (avg_now) the launch stores the
+// written by the same threads (the slab's solve and unpack).  avg: an averaging step of one_step, the launch stores the
 // averaged level; avg_ok: this launch is the fused whole-domain kernel that can (`who` names it otherwise)
-static int fill_unpack_params(qgcm_hip_ctx *c, QgUnpackParams &P, double *msg_lo, double *msg_hi, const char *who, bool avg_ok) {
+static int fill_unpack_params(qgcm_hip_ctx *c, QgUnpackParams &P, double *msg_lo, double *msg_hi, const char *who, bool avg, bool avg_ok) {
   const QgGeom &g = c->g;
   memset(&P, 0, sizeof(P));
   P.g = g;
@@ -1756,7 +1758,7 @@ static int fill_unpack_params(qgcm_hip_ctx *c, QgUnpackParams &P, double *msg_lo
   P.msg_lo = msg_lo;
   P.msg_hi = msg_hi;
   for (int i = 0; i < g.nl * g.nl; ++i) P.ctm2l[i] = c->prm.ctm2loc[i];
-  if (c->avg_now) {
+  if (avg) {
     if (msg_lo || msg_hi || !avg_ok) QG_FAIL("%s: the fused leapfrog averaging belongs to whole-domain steps", who);
     P.pavg = c->p[c->ip];     // this step's po (the launch writes the old pom buffer)
     P.qavg = c->q[c->iq ^ 1]; // this step's qo (iq already points at the new qo)
@@ -1764,11 +1766,11 @@ static int fill_unpack_params(qgcm_hip_ctx *c, QgUnpackParams &P, double *msg_lo
   return 0;
 }
 
-static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr) {
+static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr, bool avg = false) {
   const QgGeom &g = c->g;
   if ((msg_lo || msg_hi) && (!fuse_bdy || g.jhi - g.jlo + 1 < 3)) QG_FAIL("k_unpack: halo messages need the fused boundary PV and three owned rows");
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_unpack", false)) return 1;
+  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_unpack", avg, false)) return 1;
   QgBdyParams B;
   fill_bdy_params(c, B); // B.qo = current qo; B.po unused by the fused kernel
   dim3 grid((g.nx + 255) / 256, g.jhi - g.jlo + 1);
@@ -1786,12 +1788,12 @@ static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullpt
 
 // cyclic / atmosphere fast path: inverse rows + homogeneous corrections + modes -> layers (+ zonal-boundary PV) in
 // one launch (k_rfft64_unpack), nxto = 64 * {3, 6, 15}: step_plan's INV_RFFT64_UNPACK
-static int launch_rfft_unpack(qgcm_hip_ctx *c, bool fuse_bdy, bool constr) {
+static int launch_rfft_unpack(qgcm_hip_ctx *c, bool fuse_bdy, bool constr, bool avg = false) {
   const QgGeom &g = c->g;
   QgDstParams D;
   fill_dst_params(c, D, c->wrk, g.nl, 0);
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, nullptr, nullptr, "k_rfft64_unpack", false)) return 1;
+  if (fill_unpack_params(c, P, nullptr, nullptr, "k_rfft64_unpack", avg, false)) return 1;
   QgBdyParams B;
   fill_bdy_params(c, B);
   if (constr && !c->d_cycq) QG_FAIL("k_rfft64_unpack: homogeneous solutions not set");
@@ -1826,14 +1828,14 @@ static int launch_rfft_unpack(qgcm_hip_ctx *c, bool fuse_bdy, bool constr) {
 // (own_constr: every workgroup evaluates part B of the constraint algebra for itself)
 static bool can_fuse_fft3_unpack(const qgcm_hip_ctx *c) { return step_plan(c, true, true).inv == INV_FFT3_UNPACK; } // (the slab stages' plan: wherever the kernel exists)
 
-static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo = nullptr, double *msg_hi = nullptr) {
+static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo = nullptr, double *msg_hi = nullptr, bool avg = false) {
   const QgGeom &g = c->g;
   if (!can_fuse_fft3_unpack(c)) QG_FAIL("k_fft3_unpack: not a long-row configuration of three layers");
   if ((msg_lo || msg_hi) && g.jhi - g.jlo + 1 < 3) QG_FAIL("k_fft3_unpack: halo messages need three owned rows");
   QgDstParams D;
   fill_dst_params(c, D, c->wrk, g.nl, 0);
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_rfft3_unpack", own_constr)) return 1;
+  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_rfft3_unpack", avg, own_constr)) return 1;
   QgBdyParams B;
   fill_bdy_params(c, B);
   const int npairs = (g.jr1 - g.jr0 + 2) / 2;
@@ -1844,7 +1846,7 @@ static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo =
 #define QG_FFT3U_LAUNCH(ID, R1, R2, R3)                                                                                   \
   if (c->fft3 == ID) {                                                                                                    \
     typedef Fft3Plan<R1, R2, R3> PL;                                                                                      \
-    if (c->avg_now) hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT, true>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, 1); \
+    if (avg) hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT, true>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, 1); \
     else hipLaunchKernelGGL((k_rfft3_unpack<PL, 3, FFT3_NT>), grid, dim3(FFT3_NT), c->fft3_lds, c->stream, D, P, B, Q, own_constr ? 1 : 0); \
   }
   QG_FFT3_PLANS(QG_FFT3U_LAUNCH)
@@ -1856,12 +1858,12 @@ static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo =
 // box fast path: inverse row transform + modes -> layers (+ boundary PV) in one launch (k_dst64_unpack): step_plan's
 // INV_DST64_UNPACK
 static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullptr, double *msg_hi = nullptr,
-                             bool constr = false) {
+                             bool constr = false, bool avg = false) {
   const QgGeom &g = c->g;
   QgDstParams D;
   fill_dst_params(c, D, c->wrk, g.nl, 0);
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_dst64_unpack", fuse_bdy && constr)) return 1;
+  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_dst64_unpack", avg, fuse_bdy && constr)) return 1;
   QgBdyParams B;
   fill_bdy_params(c, B);
   QgConstrLite C;
@@ -1870,7 +1872,7 @@ static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nu
   dim3 grid((nrows + 1) / 2);
   KTimer t(c, KN_DSTI);
 #define QG_DU(MV, NLV)                                                                                                  \
-  if (c->avg_now) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
+  if (avg) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
   else if ((msg_lo || msg_hi) && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
   else if (msg_lo || msg_hi) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, true, false>), grid, dim3(64 * NLV), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
   else if (fuse_bdy && constr) hipLaunchKernelGGL((k_dst64_unpack<MV, NLV, true, false, true>), grid, dim3(64 * (NLV + 1)), 0, c->stream, QG_ROW_VALS(D), P, B, C); \
@@ -1928,33 +1930,34 @@ extern "C" int qgcm_hip_qgostep(qgcm_hip_handle c) {
   return 0;
 }
 
+// The plan's inverse rows and unpack, fused or not, with the constraint parts the plan lets ride in them.  A whole-domain
+// inversion (ocinvq_impl) has no halo messages and lets every workgroup of k_rfft3_unpack evaluate part B for itself
+// (own_constr); a slab's solve and unpack (slab_solve_unpack) passes the messages the unpack threads also write.
+static int launch_inverse(qgcm_hip_ctx *c, const QgStepPlan &pl, bool fuse_bdy, double *msg_lo, double *msg_hi, bool own_constr, bool avg) {
+  switch (pl.inv) {
+    case INV_DST64_UNPACK: return launch_dst_unpack(c, fuse_bdy, msg_lo, msg_hi, pl.constr == CONSTR_INV_WAVE, avg);
+    case INV_RFFT64_UNPACK: return launch_rfft_unpack(c, fuse_bdy, pl.constr == CONSTR_AB, avg); // (3 launches after k_tend instead of 5)
+    case INV_FFT3_UNPACK: return launch_fft3_unpack(c, own_constr, msg_lo, msg_hi, avg);
+    default:
+      if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, pl.constr == CONSTR_AB, pl.constr == CONSTR_BOX_WG)) return 1;
+      return launch_unpack(c, fuse_bdy, msg_lo, msg_hi, avg);
+  }
+}
+
 // in_step: called from qgcm_hip_steps, where k_tend has already stepped dpioc / dpiocp where the plan says so
-// (launch_tend(c, pl.upd_dpi)) and ocqbdy is fused into the unpack; the launches are step_plan's
-static int ocinvq_impl(qgcm_hip_ctx *c, bool in_step = false) {
+// (launch_tend(c, pl.upd_dpi)) and ocqbdy is fused into the unpack; the launches are step_plan's.  avg: one_step's
+// averaging step, the fused inverse kernel stores the averaged level
+static int ocinvq_impl(qgcm_hip_ctx *c, bool in_step = false, bool avg = false) {
   if (check_ready(c, "qgcm_hip_ocinvq")) return 1;
   if (!c->whole) QG_FAIL("qgcm_hip_ocinvq: this handle is a y-slab; drive it with the slab building blocks");
   if (!c->homog_set) QG_FAIL("qgcm_hip_ocinvq: homogeneous solutions not set");
   const QgStepPlan pl = step_plan(c, in_step);
-  const bool fuse_bdy = in_step;
   // (A per-mode side-stream variant of this chain was measured slower - 140 vs 116 us/step at 5 km - and removed.)
   if (launch_dst(c, c->wrk, c->g.nl, false)) return 1;
   if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr, pl.constr == CONSTR_AB)) return 1;
   // area (and, cyclic, line) integrals are a by-product of the y sweeps: the constraints precede the inverse transform
   if (pl.constr == CONSTR_OWN && launch_constr(c)) return 1;
-  switch (pl.inv) {
-    case INV_DST64_UNPACK:
-      if (launch_dst_unpack(c, fuse_bdy, nullptr, nullptr, pl.constr == CONSTR_INV_WAVE)) return 1;
-      break;
-    case INV_RFFT64_UNPACK: // (3 launches after k_tend instead of 5)
-      if (launch_rfft_unpack(c, fuse_bdy, pl.constr == CONSTR_AB)) return 1;
-      break;
-    case INV_FFT3_UNPACK:
-      if (launch_fft3_unpack(c, true)) return 1;
-      break;
-    default:
-      if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, pl.constr == CONSTR_AB, pl.constr == CONSTR_BOX_WG)) return 1;
-      if (launch_unpack(c, fuse_bdy)) return 1;
-  }
+  if (launch_inverse(c, pl, in_step, nullptr, nullptr, true, avg)) return 1; // (fuse_bdy = in_step)
   c->ip ^= 1; // new po sits in the old pom buffer; the old po is pom
   return 0;
 }
@@ -2215,6 +2218,9 @@ static int sched_block(const qgcm_hip_ctx *c, int s, int n) {
   return n;
 }
 
+static int avg_phase(const qgcm_hip_ctx *c, int s) { return (s - 1) % c->avg_period; }
+static bool avg_after(const qgcm_hip_ctx *c, int s) { return avg_phase(c, s) == 0; } // step s ends with a leapfrog averaging
+
 static int one_step(qgcm_hip_ctx *c, int s) {
   if (c->oml.on && launch_oml(c, false)) return 1; // src/q-gcm.F:1232; its final reduction rides in launch_tend
   if (c->aml.on && launch_aml(c, false)) return 1; // src/q-gcm.F:1260, immediately before qgastep; likewise
@@ -2225,16 +2231,11 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   // averaged level themselves - k_tend the interior qo (both levels are in its registers), k_dst64_unpack the new po and
   // the boundary qo (one extra read of this step's po) - instead of a pass of its own over six fields (133 MB at 5 km,
   // 21 us every 25 steps); the integrals dpioc follow in a one-thread launch.  Same expressions: bitwise the same fields.
-  const bool avg = (s - 1) % c->avg_period == 0;
-  c->avg_now = avg && pl.avg_ok; // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does what k_dst64_unpack does for the box)
-  const bool avg_fused = c->avg_now;
-  int rc = launch_tend(c, pl.upd_dpi, c->oml.on || c->aml.on);
-  if (!rc) {
-    c->iq ^= 1; // as qgcm_hip_qgostep
-    rc = ocinvq_impl(c, true); // ocqbdy fused into the unpack kernel
-  }
-  c->avg_now = false;
-  if (rc) return 1;
+  const bool avg = avg_after(c, s);
+  const bool avg_fused = avg && pl.avg_ok; // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does what k_dst64_unpack does for the box)
+  if (launch_tend(c, pl.upd_dpi, c->oml.on || c->aml.on, TEND_ALL, avg_fused)) return 1;
+  c->iq ^= 1; // as qgcm_hip_qgostep
+  if (ocinvq_impl(c, true, avg_fused)) return 1; // ocqbdy fused into the unpack kernel
   if (c->poavg.on && launch_poavg(c)) return 1; // avg_ocn_k247 right after ocqbdy, src/q-gcm.F:1250-1252
   if (avg_fused) {
     KTimer t(c, KN_LFAVG);
@@ -2322,14 +2323,18 @@ static int capture_block(qgcm_hip_ctx *c, bool upload, hipGraphExec_t *exec, Bod
 // that asks for ever new block lengths / phases evicts everything once kMaxGraphs is reached.
 static const size_t kMaxGraphs = 96;
 
-static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
-  const int phase = (s0 - 1) % c->avg_period;
+// the key of a captured block of B steps from s0, in both caches (graphs, slab_graphs)
+static long long graph_key(const qgcm_hip_ctx *c, int s0, int B) {
   // mixed layer on/off and its buffer rotation (an ocean handle has the ocean's, an atmosphere handle the atmosphere's)
   const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : c->aml.on ? 1 + 3 * c->aml.ia + c->aml.iam : 0;
   // ... and which tendency kernel the block launches (tend_zmask: set_forcing changes it without dropping the graphs;
   // omk < 16, so bits 28-29 are free)
-  const long long key = ((long long)B << 32) | ((long long)c->poavg.on << 31) | ((long long)tend_zmask(c) << 28) | (omk << 24) |
-                        (c->ip << 16) | (c->iq << 8) | phase;
+  return ((long long)B << 32) | ((long long)c->poavg.on << 31) | ((long long)tend_zmask(c) << 28) | (omk << 24) | (c->ip << 16) |
+         (c->iq << 8) | avg_phase(c, s0);
+}
+
+static int get_graph(qgcm_hip_ctx *c, int s0, int B, hipGraphExec_t *out) {
+  const long long key = graph_key(c, s0, B);
   auto it = c->graphs.find(key);
   if (it != c->graphs.end()) {
     it->second.used = c->graph_call;
@@ -3264,107 +3269,100 @@ extern "C" int qgcm_hip_halo_pack(qgcm_hip_handle c, double *to_lower_dev, doubl
   return 0;
 }
 
-extern "C" int qgcm_hip_halo_unpack(qgcm_hip_handle c, const double *from_lower_dev, const double *from_upper_dev) {
+// st (here and below): the stream of the launches, nullptr = the handle's
+static int launch_halo_unpack(qgcm_hip_ctx *c, const double *from_lo, const double *from_hi, hipStream_t st = nullptr) {
   if (check_ready(c, "qgcm_hip_halo_unpack")) return 1;
   const QgGeom &g = c->g;
-  if ((from_lower_dev && g.jlo < 4) || (from_upper_dev && g.ny - g.jhi < 3)) QG_FAIL("qgcm_hip_halo_unpack: no halo rows on that side");
+  if ((from_lo && g.jlo < 4) || (from_hi && g.ny - g.jhi < 3)) QG_FAIL("qgcm_hip_halo_unpack: no halo rows on that side");
   dim3 grid((g.ldx + 255) / 256, 4 * g.nl, 2);
-  hipLaunchKernelGGL(k_halo_unpack, grid, dim3(256), 0, c->stream, g, c->p[c->ip], c->q[c->iq], from_lower_dev,
-                     from_upper_dev);
+  hipLaunchKernelGGL(k_halo_unpack, grid, dim3(256), 0, st ? st : c->stream, g, c->p[c->ip], c->q[c->iq], from_lo, from_hi);
   HIPCHECK(hipGetLastError());
   return 0;
 }
 
-// edge rows of the new sst (first / last three owned T rows) appended to the halo messages
-static int oml_halo_pack(qgcm_hip_ctx *c, double *to_lo, double *to_hi) {
-  if (!c->oml.on || (!to_lo && !to_hi)) return 0;
+extern "C" int qgcm_hip_halo_unpack(qgcm_hip_handle c, const double *from_lo, const double *from_hi) { return launch_halo_unpack(c, from_lo, from_hi); }
+
+// edge rows of the new sst, appended to the halo messages: the first / last three owned T rows out (to_lo / to_hi), or
+// the neighbours' rows in (from_lo / from_hi)
+static int launch_oml_halo(qgcm_hip_ctx *c, double *to_lo, double *to_hi, const double *from_lo, const double *from_hi, hipStream_t st = nullptr) {
+  if (!c->oml.on || (!to_lo && !to_hi && !from_lo && !from_hi)) return 0;
   const size_t off = (size_t)4 * c->g.nl * c->g.ldx;
   const int jT1 = (c->g.jhi + c->g.joff == c->g.nyg) ? c->g.jhi - 1 : c->g.jhi;
-  hipLaunchKernelGGL(k_oml_halo, dim3((c->g.nxt + 255) / 256, 3, 2), dim3(256), 0, c->stream, c->oml.sst[c->oml.is], c->oml.ldt, c->g.nxt,
-                     c->g.ny - 1, c->g.jlo, jT1, to_lo ? to_lo + off : nullptr, to_hi ? to_hi + off : nullptr, (const double *)nullptr,
-                     (const double *)nullptr, 0);
+  hipLaunchKernelGGL(k_oml_halo, dim3((c->g.nxt + 255) / 256, 3, 2), dim3(256), 0, st ? st : c->stream, c->oml.sst[c->oml.is],
+                     c->oml.ldt, c->g.nxt, c->g.ny - 1, c->g.jlo, jT1, to_lo ? to_lo + off : nullptr, to_hi ? to_hi + off : nullptr,
+                     from_lo ? from_lo + off : nullptr, from_hi ? from_hi + off : nullptr, from_lo || from_hi ? 1 : 0);
   HIPCHECK(hipGetLastError());
   return 0;
 }
 
+// The communication-free pieces of a y-slab step: qgcm_hip_slab_stage runs them by stage number (the Python driver
+// SlabOcean.step), slab_step calls them between its exchanges.  First the tendency tiles of a slab: all of them, or the
+// inner / the outer tile rows (launch_tend's part); send: the step message (cyclic: the boundary line sums go into its tail)
+static int slab_tend(qgcm_hip_ctx *c, int part, double *send, hipStream_t st = nullptr) {
+  // box fast path: as in qgcm_hip_steps the leapfrog of dpioc is done by the tendency launch and the constraint
+  // solve by the extra wave of the fused inverse-transform kernel of slab_solve_unpack (no k_constr_box launch)
+  // (with the mixed layer on, xon(1) is only complete after the all-gather: dpioc is stepped in slab_solve_unpack then)
+  const bool upd_dpi = step_plan(c, true, true).upd_dpi;
+  double *bpart = c->g.cyc && part != TEND_INNER ? send + (size_t)TH_MSG * c->g.nl * c->g.ldw : nullptr;
+  return launch_tend(c, upd_dpi, false, part, false, bpart, st);
+}
+
+// forward rows and the slab summary of the two y sweeps into the step message (after all the tendency tiles)
+static int slab_forward(qgcm_hip_ctx *c, double *send, int rank, int nranks) {
+  c->iq ^= 1; // as qgcm_hip_qgostep
+  if (qgcm_hip_row_transform(c, 0) || qgcm_hip_thomas_phase(c, 1, nullptr, send, rank, nranks)) return 1;
+  if (c->oml.on) { // the three sums of this slab's entoc pass (launch_oml_b) ride at the end of the step message
+    QgOmlParams OP;
+    fill_oml_params(c, OP);
+    hipLaunchKernelGGL(k_oml_sum3, dim3(1), dim3(OML_NT), 0, c->stream, (const double *)OP.partB, OP.nblkB, send + slab_msg_len(c->g));
+    HIPCHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// both sweeps from the gathered step messages, constraints, inverse rows, modes -> layers + boundary PV; the unpack
+// launch, fused or not, also writes the halo messages (first / last three owned rows of po, edge row of qo)
+static int slab_solve_unpack(qgcm_hip_ctx *c, double *gath, double *to_lo, double *to_hi, int rank, int nranks) {
+  if (qgcm_hip_thomas_phase(c, 2, gath, nullptr, rank, nranks)) return 1;
+  if (c->oml.on) { // xon(1), enisoc(1) / eninoc(1), monitors from every rank's sums, before the constraints use them
+    if (!c->oml_gath) QG_FAIL("qgcm_hip_slab_stage: the mixed layer's stages 10 / 11 have not run this step");
+    QgOmlFinal F;
+    fill_oml_final(c, F, true);
+    hipLaunchKernelGGL(k_oml_final_slab, dim3(1), dim3(64), 0, c->stream, c->oml_gath, (const double *)(gath + slab_msg_len(c->g)),
+                       (long)slab_msg_len_oml(c), nranks, F);
+    HIPCHECK(hipGetLastError());
+  }
+  const QgStepPlan pl = step_plan(c, true, true);
+  if (nranks == 1) to_lo = to_hi = nullptr;
+  if (pl.constr == CONSTR_OWN && qgcm_hip_constr(c)) return 1; // area integrals of the whole basin came with the slab summaries
+  if (launch_inverse(c, pl, true, to_lo, to_hi, false, false)) return 1;
+  c->ip ^= 1;
+  if (launch_poavg(c)) return 1; // the new po of the owned rows, before slab_halo_in averages it
+  return launch_oml_halo(c, to_lo, to_hi, nullptr, nullptr);
+}
+
+// the neighbours' edge rows in (with the mixed layer on, those of the new sst sit at the end of the halo messages),
+// then the leapfrog averaging where the step ends with one (always on the handle's stream)
+static int slab_halo_in(qgcm_hip_ctx *c, const double *from_lo, const double *from_hi, int nranks, bool avg, hipStream_t st = nullptr) {
+  if (nranks > 1 && (launch_halo_unpack(c, from_lo, from_hi, st) || launch_oml_halo(c, nullptr, nullptr, from_lo, from_hi, st))) return 1;
+  return avg ? qgcm_hip_lf_average(c) : 0;
+}
+
+// Stages 4 - 7 are stage 1 in pieces: 4 = the inner tile rows of the tendency launch (they need no halo row), 6 = the
+// outer tile rows + edge work, 7 = forward rows and summary sweep (after 4 AND 6), 5 = 6 + 7.
 extern "C" int qgcm_hip_slab_stage(qgcm_hip_handle c, int stage, double *a, double *b, double *cc, int rank, int nranks,
                                    int flags) {
   switch (stage) {
-    case 1:
-    case 4:   // the part of stage 1 that needs no halo row: the inner tile rows of the tendency launch
-    case 5:   // the rest of stage 1: outer tile rows + edge work, forward rows, summary sweep
-    case 6:   // ... its first half alone: the outer tile rows + edge work of the tendency launch
-    case 7: { // ... and its second half: forward rows, summary sweep (after stages 4 AND 6)
+    case 1: case 4: case 5: case 6: case 7:
       if (stage != 4 && !a) QG_FAIL("qgcm_hip_slab_stage: stage %d needs the send buffer", stage);
       if (check_ready(c, "qgcm_hip_slab_stage")) return 1;
       if (stage != 1 && (c->oml.on || !tend_can_split(c)))
         QG_FAIL("qgcm_hip_slab_stage: stages 4 - 7 need a slab of at least three tile rows (%d rows each) and the mixed layer off", TEND_TY);
-      // cyclic: the boundary line sums of the tendency launch go straight into the tail of the step message
-      if (c->g.cyc && stage != 4 && stage != 7) c->bpart_out = a + (size_t)TH_MSG * c->g.nl * c->g.ldw;
-      // box fast path: as in qgcm_hip_steps the leapfrog of dpioc is done by the tendency launch and the constraint
-      // solve by the extra wave of the fused inverse-transform kernel of stage 2 (no k_constr_box launch)
       if (!c->homog_set) QG_FAIL("qgcm_hip_slab_stage: homogeneous solutions not set");
-      // (with the mixed layer on, xon(1) is only complete after the all-gather: dpioc is stepped in stage 2 then)
-      const bool upd_dpi = step_plan(c, true, true).upd_dpi;
-      const int rc = stage == 7 ? 0 : launch_tend(c, upd_dpi, false, stage == 1 ? TEND_ALL : stage == 4 ? TEND_INNER : TEND_OUTER);
-      c->bpart_out = nullptr;
-      if (rc) return 1;
-      if (stage == 4 || stage == 6) return 0;
-      c->iq ^= 1; // as qgcm_hip_qgostep
-      if (qgcm_hip_row_transform(c, 0)) return 1;
-      if (qgcm_hip_thomas_phase(c, 1, nullptr, a, rank, nranks)) return 1;
-      if (c->oml.on) { // the three sums of this slab's entoc pass (stage 11) ride at the end of the step message
-        QgOmlParams OP;
-        fill_oml_params(c, OP);
-        hipLaunchKernelGGL(k_oml_sum3, dim3(1), dim3(OML_NT), 0, c->stream, (const double *)OP.partB, OP.nblkB, a + slab_msg_len(c->g));
-        HIPCHECK(hipGetLastError());
-      }
-      return 0;
-    }
-    case 2:
-      if (qgcm_hip_thomas_phase(c, 2, a, nullptr, rank, nranks)) return 1;
-      if (c->oml.on) { // xon(1), enisoc(1) / eninoc(1), monitors from every rank's sums, before the constraints use them
-        if (!c->oml_gath) QG_FAIL("qgcm_hip_slab_stage: the mixed layer's stages 10 / 11 have not run this step");
-        QgOmlFinal F;
-        fill_oml_final(c, F, true);
-        hipLaunchKernelGGL(k_oml_final_slab, dim3(1), dim3(64), 0, c->stream, c->oml_gath, (const double *)(a + slab_msg_len(c->g)),
-                           (long)slab_msg_len_oml(c), nranks, F);
-        HIPCHECK(hipGetLastError());
-      }
-      {
-        const QgStepPlan pl = step_plan(c, true, true);
-        double *to_lo = nranks > 1 ? b : nullptr, *to_hi = nranks > 1 ? cc : nullptr;
-        if (pl.constr == CONSTR_OWN && qgcm_hip_constr(c)) return 1; // area integrals of the whole basin came with the slab summaries
-        // the unpack launch, fused or not, also writes the halo messages (first / last three owned rows of po, edge row of qo)
-        switch (pl.inv) {
-          case INV_DST64_UNPACK:
-            if (launch_dst_unpack(c, true, to_lo, to_hi, pl.constr == CONSTR_INV_WAVE)) return 1;
-            break;
-          case INV_FFT3_UNPACK: // long rows: inverse rows + unpack + halo messages in one launch (k_fft3_unpack.h)
-            if (launch_fft3_unpack(c, false, to_lo, to_hi)) return 1;
-            break;
-          default:
-            if (pl.constr == CONSTR_BOX_WG) { // box: the constraint solve rides in the inverse-row launch
-              if (launch_dst(c, c->wrk, c->g.nl, true, 0, nullptr, false, true)) return 1;
-            } else if (qgcm_hip_row_transform(c, 1)) return 1;
-            if (check_ready(c, "qgcm_hip_slab_stage") || launch_unpack(c, true, to_lo, to_hi)) return 1;
-        }
-        c->ip ^= 1;
-        if (launch_poavg(c)) return 1; // the new po of the owned rows, before stage 3 averages it
-        return oml_halo_pack(c, to_lo, to_hi);
-      }
-    case 3:
-      if (nranks > 1 && qgcm_hip_halo_unpack(c, a, b)) return 1;
-      if (nranks > 1 && c->oml.on) { // the neighbours' edge rows of the new sst sit at the end of the halo messages
-        const size_t off = (size_t)4 * c->g.nl * c->g.ldx;
-        const int jT1 = (c->g.jhi + c->g.joff == c->g.nyg) ? c->g.jhi - 1 : c->g.jhi;
-        hipLaunchKernelGGL(k_oml_halo, dim3((c->g.nxt + 255) / 256, 3, 2), dim3(256), 0, c->stream, c->oml.sst[c->oml.is], c->oml.ldt,
-                           c->g.nxt, c->g.ny - 1, c->g.jlo, jT1, (double *)nullptr, (double *)nullptr,
-                           a ? (const double *)(a + off) : nullptr, b ? (const double *)(b + off) : nullptr, 1);
-        HIPCHECK(hipGetLastError());
-      }
-      if (flags & 1) return qgcm_hip_lf_average(c);
-      return 0;
+      if (stage != 7 && slab_tend(c, stage == 1 ? TEND_ALL : stage == 4 ? TEND_INNER : TEND_OUTER, a)) return 1;
+      return stage == 4 || stage == 6 ? 0 : slab_forward(c, a, rank, nranks);
+    case 2: return slab_solve_unpack(c, a, b, cc, rank, nranks); // a = the gathered step messages, b / cc = the halo messages out
+    case 3: return slab_halo_in(c, a, b, nranks, (flags & 1) != 0); // a / b = the halo messages in; flags & 1: leapfrog averaging
     // ---- ocean mixed layer on y-slabs: `call oml` (src/q-gcm.F:1232) comes before qgostep and needs the basin-wide
     // mean entrainment half way through - one more (three numbers per rank) all-gather per step
     case 10: // new sst, raw entrainment; a = this slab's three sums (send buffer of the mixed layer's all-gather)
@@ -3515,10 +3513,11 @@ extern "C" int qgcm_hip_comm_probe(qgcm_hip_handle c, int reps, double *us) {
   return 0;
 }
 
-// one distributed ocean step: three communication-free stages (the same calls SlabOcean.step makes through
+// one distributed ocean step: the communication-free pieces above (what SlabOcean.step runs through
 // qgcm_hip_slab_stage) and two exchanges, all ordered on c->stream; no host synchronisation
-// next_follows: step s + 1 is executed by the same qgcm_hip_slab_steps call / captured block (its tendency may be started)
-static int slab_step(qgcm_hip_ctx *c, int s, bool next_follows) {
+// next_follows: step s + 1 is executed by the same qgcm_hip_slab_steps call / captured block (its tendency may be started);
+// forked: set once this step has sent work to the exchange's stream (slab_step joins it if the step fails)
+static int slab_step_issue(qgcm_hip_ctx *c, int s, bool next_follows, bool &forked) {
   QgSlabComm *m = c->sc_comm;
   const int r = m->rank, P = m->nranks;
   const size_t n = m->halo_len;
@@ -3526,31 +3525,34 @@ static int slab_step(qgcm_hip_ctx *c, int s, bool next_follows) {
     QG_FAIL("qgcm_hip_slab_steps: the mixed layer was switched on after qgcm_hip_comm_init (message sizes differ)");
   // 0. mixed layer (`call oml` precedes qgostep): new sst + raw entrainment, every slab's sums, entoc
   if (c->oml.on) {
-    if (qgcm_hip_slab_stage(c, 10, m->oml_send, nullptr, nullptr, r, P, 0)) return 1;
+    if (launch_oml_a(c, m->oml_send)) return 1;
     NCCLCHECK(m->api, m->api->AllGather(m->oml_send, m->oml_gath, 3, ncclDouble, m->comm, c->stream));
-    if (qgcm_hip_slab_stage(c, 11, m->oml_gath, nullptr, nullptr, r, P, 0)) return 1;
+    c->oml_gath = m->oml_gath; // (slab_solve_unpack reads it)
+    if (launch_oml_b(c, m->oml_gath, P)) return 1;
   }
   // 1. tendency, forward row transform, slab summary of the two y sweeps
   if (m->pending) {
     // the halo rows of the previous step are still on their way (second stream): inner tile rows first
-    if (qgcm_hip_slab_stage(c, 4, nullptr, nullptr, nullptr, r, P, 0)) return 1;
+    if (slab_tend(c, TEND_INNER, nullptr)) return 1;
     HIPCHECK(hipStreamWaitEvent(c->stream, m->ev_halo, 0));
     m->pending = false;
     // the outer tile rows have run on the exchange's stream right behind the halo rows, beside the inner ones (below)
-    if (qgcm_hip_slab_stage(c, m->outer_done ? 7 : 5, m->th_send, nullptr, nullptr, r, P, 0)) return 1;
+    if (!m->outer_done && slab_tend(c, TEND_OUTER, m->th_send)) return 1;
     m->outer_done = false;
-  } else if (qgcm_hip_slab_stage(c, 1, m->th_send, nullptr, nullptr, r, P, 0)) return 1;
+  } else if (slab_tend(c, TEND_ALL, m->th_send)) return 1;
+  if (slab_forward(c, m->th_send, r, P)) return 1;
   NCCLCHECK(m->api, m->api->AllGather(m->th_send, m->th_gath, m->th_len, ncclDouble, m->comm, c->stream));
   // 2. both sweeps from the composed inflows (+ basin-wide area integrals), constraints, inverse row transform,
   //    modes -> layers + boundary PV, edge rows out
   double *to_lo = r > 0 ? m->h_send : nullptr, *to_hi = r < P - 1 ? m->h_send + n : nullptr;
-  if (qgcm_hip_slab_stage(c, 2, m->th_gath, to_lo, to_hi, r, P, 0)) return 1;
-  const int avg = (s - 1) % 25 == 0 ? 1 : 0; // leapfrog averaging after steps s with (s-1) mod 25 == 0
-  // overlapped: the exchange and the halo unpack on the second stream; the next step's stage 4 does not wait for them
+  if (slab_solve_unpack(c, m->th_gath, to_lo, to_hi, r, P)) return 1;
+  const bool avg = avg_after(c, s);
+  // overlapped: the exchange and the halo unpack on the second stream; the next step's inner tile rows do not wait for them
   const bool ov = m->overlap && !avg && !c->oml.on && tend_can_split(c);
   hipStream_t xs = c->stream;
   if (ov) {
     HIPCHECK(hipEventRecord(m->ev_fork, c->stream));
+    forked = true;
     HIPCHECK(hipStreamWaitEvent(m->cstream, m->ev_fork, 0));
     xs = m->cstream;
   }
@@ -3575,14 +3577,8 @@ static int slab_step(qgcm_hip_ctx *c, int s, bool next_follows) {
     if (r > 0) from_lo = m->h_gath + (size_t)(2 * (r - 1) + 1) * n;  // what the lower neighbour sent upwards
     if (r < P - 1) from_hi = m->h_gath + (size_t)(2 * (r + 1)) * n;  // what the upper neighbour sent downwards
   }
-  // 3. edge rows in (+ leapfrog averaging)
-  if (P > 1 || avg) {
-    hipStream_t main_stream = c->stream;
-    c->stream = xs; // (the stage's launches follow the exchange on its stream)
-    const int rc = qgcm_hip_slab_stage(c, 3, (double *)from_lo, (double *)from_hi, nullptr, r, P, avg);
-    c->stream = main_stream;
-    if (rc) return 1;
-  }
+  // 3. edge rows in, behind the exchange on its stream (+ leapfrog averaging: never overlapped, xs is the handle's stream)
+  if ((P > 1 || avg) && slab_halo_in(c, from_lo, from_hi, P, avg, xs)) return 1;
   if (ov) {
     // The outer tile rows of step s + 1's tendency launch go out on the exchange's stream, right behind the halo rows
     // they need: they run BESIDE the inner tile rows the handle's stream is computing (disjoint tiles of the same
@@ -3591,11 +3587,7 @@ static int slab_step(qgcm_hip_ctx *c, int s, bool next_follows) {
     // read the state, and the outer rows write into the buffer that holds qom.
     m->outer_done = false;
     if (next_follows) {
-      hipStream_t main_stream = c->stream;
-      c->stream = xs;
-      const int rc = qgcm_hip_slab_stage(c, 6, m->th_send, nullptr, nullptr, r, P, 0);
-      c->stream = main_stream;
-      if (rc) return 1;
+      if (slab_tend(c, TEND_OUTER, m->th_send, xs)) return 1;
       m->outer_done = true;
     }
     HIPCHECK(hipEventRecord(m->ev_halo, m->cstream));
@@ -3604,20 +3596,30 @@ static int slab_step(qgcm_hip_ctx *c, int s, bool next_follows) {
   return 0;
 }
 
+// The one exit of a step.  A step that fails leaves nothing forked and no overlap state behind: the handle's stream
+// waits for what the exchange's stream was given, by this step or (still pending) by the one before.
+static int slab_step(qgcm_hip_ctx *c, int s, bool next_follows) {
+  QgSlabComm *m = c->sc_comm;
+  bool forked = false;
+  if (!slab_step_issue(c, s, next_follows, forked)) return 0;
+  if (forked && !m->pending) (void)hipEventRecord(m->ev_halo, m->cstream); // (failed before the step recorded it)
+  if (forked || m->pending) (void)hipStreamWaitEvent(c->stream, m->ev_halo, 0);
+  m->pending = m->outer_done = false;
+  return 1;
+}
+
 // the second stream joins the handle's stream (end of a qgcm_hip_slab_steps call, end of a captured block)
 static int slab_join(qgcm_hip_ctx *c) {
   QgSlabComm *m = c->sc_comm;
   if (m && m->pending) {
-    HIPCHECK(hipStreamWaitEvent(c->stream, m->ev_halo, 0));
     m->pending = false;
+    HIPCHECK(hipStreamWaitEvent(c->stream, m->ev_halo, 0));
   }
   return 0;
 }
 
 static int get_slab_graph(qgcm_hip_ctx *c, int s0, hipGraphExec_t *out) {
-  const int phase = (s0 - 1) % 25;
-  const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : 0; // mixed layer on/off and its buffer rotation
-  const int key = ((int)c->poavg.on << 28) | (tend_zmask(c) << 24) | (omk << 20) | (c->ip << 16) | (c->iq << 8) | phase; // (omk < 16)
+  const long long key = graph_key(c, s0, kGraphBlock); // (no eviction here, and 50-step blocks only)
   auto it = c->slab_graphs.find(key);
   if (it != c->slab_graphs.end()) {
     *out = it->second;
@@ -3627,9 +3629,7 @@ static int get_slab_graph(qgcm_hip_ctx *c, int s0, hipGraphExec_t *out) {
   if (capture_block(c, false, &exec, [&]() {
         int rc = 0;
         for (int k = 0; k < kGraphBlock && !rc; ++k) rc = slab_step(c, s0 + k, k + 1 < kGraphBlock);
-        if (!rc) rc = slab_join(c);
-        if (rc && c->sc_comm) c->sc_comm->pending = c->sc_comm->outer_done = false;
-        return rc;
+        return rc ? rc : slab_join(c);
       }))
     return 1;
   c->slab_graphs[key] = exec;
