@@ -1,0 +1,309 @@
+// k_tend_rows.h - K1 + K3 (forward) in one launch for the 5 km box ocean (nxto = 960): PV tendency, leapfrog and
+// layer->mode projection by ROW BANDS, whose epilogue runs the forward DST-I of the band's rows.
+//
+// k_tend writes the modal right-hand side to wrk and k_dst64 reads it straight back (6 of the 25 fields the two
+// launches move), across the longest kernel boundary of the step.  A workgroup that steps whole rows needs nothing from
+// any other workgroup to transform them, so here
+//
+//   * one workgroup owns a band of B consecutive interior rows over the full width and all layers;
+//   * phase 1 (tendency): each WAVE takes strips of TR_SW = 56 columns, lane = column with 4 halo lanes on either side
+//     (the cascade Del^2 -> Del^4 -> Del^6 has radius 3; 4 keeps the owned columns starting on an odd column, so that the
+//     even lane of a lane pair is 16-byte aligned for qg_pair_store_wt).  East / west neighbours come from DPP wave
+//     shifts, north / south neighbours are the rows the lane holds in registers.  The wave walks the layers of its strip
+//     one after the other (the loads of layer k+1 are requested before layer k is computed), keeps dqdt of all layers in
+//     registers and finishes with the point-wise part (forcing, drag, leapfrog, projection) - the expressions, the
+//     association order and the wall rules are those of k_tend_body.inc and tend_point, contraction off.  The new qo
+//     leaves in 16-byte write-through pairs; the modal right-hand side fnot * qmm goes to LDS, one row per (row, mode);
+//   * ONE workgroup barrier;
+//   * phase 2 (forward rows): B/2 x NL of the waves run dst64_front / dst64_back (k_dst64.h, unchanged) on one (row
+//     pair, mode) each, reading the rows from LDS, and store the spectral rows to wrk as k_dst64 does.  The transform
+//     buffer F of a wave lies over the two right-hand-side rows that this wave alone reads: dst64_front has all its row
+//     loads in registers before it writes F.
+// No workgroup waits for another one: no flags, no counters.
+// The wall rows (not stepped: the new-qo buffer keeps qo) are copied by the first and the last band.
+#pragma once
+#include "k_tend.h"
+#include "k_dst64.h"
+
+#define TR_SW 56 // columns owned by a strip (64 lanes - 2 x 4 halo lanes)
+#define TR_HL 4  // halo lanes on either side
+
+// value of the lane to the west (lane - 1) / east (lane + 1); lanes 0 / 63 receive 0 (halo lanes)
+template <int CTRL>
+__device__ __forceinline__ double tr_dpp(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+#define TR_WEST(v) tr_dpp<0x138>(v) // wave_shr:1
+#define TR_EAST(v) tr_dpp<0x130>(v) // wave_shl:1
+
+// element at byte offset `off` (32-bit, per lane) behind the wave-uniform pointer `base`: keeps the address in the "scalar
+// base + 32-bit lane offset" form of global_load (no 64-bit address arithmetic in VGPRs).  `base` is the pointer of ONE
+// layer: the launcher refuses grids whose layer reaches 2^32 bytes (ny * ldx >= 2^29)
+__device__ __forceinline__ double tr_ld(const double *base, unsigned off) {
+  return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + off);
+}
+
+struct TrRules {
+  bool isW, isE; // this lane is the W / E wall column
+  int nyg;
+  int vz; // 0, in a VGPR the compiler cannot see through
+  double bcf, dxom2;
+};
+
+// Five-point operator of one row with the reference's mixed boundary rule (qgosubs.F:94-127 for Del^2, :310-341 for
+// Del^4): interior points (cS + cW + cE + cN - 4 c0) * dxom2; a wall point takes bcf * (inner neighbour - itself), the
+// inner neighbour being N on the S wall row, S on the N wall row, E on the W wall column, W on the E wall column (rows
+// first: the corners follow the row rule, as the i2 / i4 offsets of k_tend_body.inc).  gj: row of c0 - the same in every
+// lane, but held in a VGPR (TrRules.vz): on a scalar row number the compiler branches around each rule, and the web of
+// blocks that makes of the unrolled cascade ends in scratch; on a vector one both rules are evaluated and selected, as
+// k_tend_body.inc does.
+__device__ __forceinline__ double tr_lap(const TrRules &R, double cS, double c0, double cN, int gj) {
+  const double cW = TR_WEST(c0), cE = TR_EAST(c0);
+  const double vi = (cS + cW + cE + cN - 4.0 * c0) * R.dxom2;
+  const bool wS = gj == 1, wN = gj == R.nyg;
+  double in = cW; // (a flat chain of selects, the last one wins: rows before columns, S before N)
+  in = R.isW ? cE : in;
+  in = wN ? cS : in;
+  in = wS ? cN : in;
+  const double vw = R.bcf * (in - c0);
+  const bool wall = wS | wN | R.isW | R.isE;
+  return wall ? vw : vi;
+}
+
+#define TR_WAVES_PER_EU 3 // the transform waves need ~146 VGPRs (k_dst64): three waves per SIMD
+// rows per band.  Measured at NAtl 5 km: 2 (two six-wave workgroups per CU): 71.9 us per step, 4 (one
+// twelve-wave workgroup per CU): 59.4; the parent 61.9.
+constexpr int TR_BAND = 4;
+template <int B>
+struct TrCfg {
+  static constexpr int NW = 3 * B;                 // waves per workgroup: three per SIMD at two (B = 2) / one (B = 4) workgroups per CU
+  static constexpr int NT = 64 * NW;
+  static constexpr int REG = 15 * D64_ROW * 2 + 128; // doubles per (row pair, mode): F (over the two rows), then W64
+  static_assert(B % 2 == 0 && NT <= 1024, "whole row pairs; a workgroup has at most 1024 threads");
+  static_assert((B / 2) * 3 * REG * 8 <= 160 * 1024, "three modes per row pair: the band's rows must fit the CU's 160 KB of LDS");
+};
+
+// grid: 8 * ceil(nbands / 8) workgroups of 64 * 3 B threads; whole-domain handle (joff = 0, rows 1..ny), NL = 3
+template <int NL, int B, int ZM>
+__global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(const double *pom, const double2 *twid, const double *sintab,
+                                                                  int nx, int ny, int ldx, int side, const QgTendParams P) {
+  constexpr int M = 15, N = 64 * M, NW = TrCfg<B>::NW, REG = TrCfg<B>::REG, NPW = B / 2;
+  static_assert(B % 2 == 0 && NPW * NL <= NW, "a wave per (row pair, mode)");
+  static_assert(2 * N <= M * D64_ROW * 2, "the two right-hand-side rows lie inside the transform buffer");
+  constexpr bool ENT = !(ZM & 1), DDY = !(ZM & 2); // the field is read
+  __shared__ __align__(16) double lds[NPW * NL * REG];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const long fs = P.g.fstride;
+  const int jr1 = ny - 1; // interior rows 2 .. ny - 1
+  const int nbands = (jr1 - 1 + B - 1) / B;
+  const int per_xcd = (nbands + 7) / 8;
+  if ((side & 2) && blockIdx.x == 0 && tid == 0) constr_dpi_update<NL>(P.sc, P.tdto, P.gpoc); // see QgTendParams
+  // XCD-aware numbering: each XCD (blockIdx mod 8) sweeps a contiguous run of bands, neighbours in time and in rows
+  const int band = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  if (band >= nbands) return;
+  const int j0 = 2 + band * B; // first row of the band
+  const double *po0 = P.po, *qo0 = P.qo;
+
+  // ---- wall rows (not stepped): the new-qo buffer keeps qo (qgosubs.F:214-219) -----------------------------------
+  if (band == 0 || band == nbands - 1) {
+#pragma unroll 1
+    for (int w = 0; w < 2; ++w) {
+      if ((w == 0 && band != 0) || (w == 1 && band != nbands - 1)) continue;
+      const long ow = (long)(w == 0 ? 0 : ny - 1) * ldx;
+      for (int i = tid; i < nx; i += TrCfg<B>::NT) {
+#pragma unroll
+        for (int k = 0; k < NL; ++k) P.qnew[fs * k + ow + i] = qo0[fs * k + ow + i];
+      }
+    }
+  }
+
+  TrRules R;
+  R.nyg = ny; R.bcf = P.bcfaco; R.dxom2 = P.dxom2;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(R.vz));
+  const double dxom2 = P.dxom2;
+  // row offset inside a field layer, clamped: rows outside the array are never used by a point inside
+  auto rowoff = [&](int gj) {
+    const int rj = gj < 1 ? 1 : (gj > ny ? ny : gj);
+    return (unsigned)((rj - 1) * ldx) * 8u;
+  };
+
+  // ---- phase 1: the tendency of the band, strip by strip ----------------------------------------------------------
+  const int nstrips = (nx + TR_SW - 1) / TR_SW;
+#pragma unroll 1
+  for (int strip = wv; strip < nstrips; strip += NW) {
+    const int i0 = strip * TR_SW + 1;          // first column the strip owns (odd)
+    const int gi = i0 - TR_HL + lane;          // this lane's column
+    const int gc = gi < 1 ? 1 : (gi > nx ? nx : gi); // clamped: lanes outside the basin load finite values no point inside reads
+    const unsigned lcol = (unsigned)(gc - 1) * 8u;
+    const bool own = lane >= TR_HL && lane < TR_HL + TR_SW && gi <= nx; // (gi >= 1 then)
+    const bool cint = gi >= 2 && gi <= nx - 1;
+    R.isW = gi == 1;
+    R.isE = gi == nx;
+
+    double w[B + 6], pr[B + 2], qr[B + 2]; // pom rows j0-3 .. j0+B+2, po / qo rows j0-1 .. j0+B of the layer in flight
+#pragma unroll
+    for (int r = 0; r < B + 6; ++r) w[r] = tr_ld(pom, rowoff(j0 - 3 + r) + lcol);
+#pragma unroll
+    for (int r = 0; r < B + 2; ++r) {
+      pr[r] = tr_ld(po0, rowoff(j0 - 1 + r) + lcol);
+      qr[r] = tr_ld(qo0, rowoff(j0 - 1 + r) + lcol);
+    }
+    double dq[NL][B], d2bot[B];
+    double e_qm[NL][B], e_wek[B], e_ent[ENT ? B : 1], e_ddy[DDY ? B : 1];
+    // (TR_FENCE: a scheduling fence.  Left to itself the compiler requests the rows of all layers at once and forms every
+    //  DPP shift of the Jacobian before the first product: 600 bytes of scratch per lane.  Between the fences the order is
+    //  the one written here: the pom rows of layer k + 1 are requested once Del^2 of layer k has consumed those of layer
+    //  k, its po / qo rows once the Jacobian has - so each request flies during the arithmetic that follows it, and a lane
+    //  never holds more than one layer's rows.  TR_PIN: the value exists HERE - pure arithmetic is otherwise sunk past
+    //  the fences to its use in the epilogue, and the DPP shifts it reads, which cannot move, stay live until then.)
+#define TR_PIN(x) asm volatile("" : "+v"(x))
+#define TR_FENCE()                       \
+  do {                                   \
+    asm volatile("" ::: "memory");       \
+    __builtin_amdgcn_sched_barrier(0);   \
+  } while (0)
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+      // Del^2 of rows j0-2 .. j0+B+1
+      double d2[B + 4], d4[B + 2];
+#pragma unroll
+      for (int r = 0; r < B + 4; ++r) {
+        d2[r] = tr_lap(R, w[r], w[r + 1], w[r + 2], j0 - 2 + r + R.vz);
+        TR_PIN(d2[r]);
+      }
+      TR_FENCE();
+      if (k + 1 < NL) {
+        const double *pomk = pom + fs * (k + 1);
+#pragma unroll
+        for (int r = 0; r < B + 6; ++r) w[r] = tr_ld(pomk, rowoff(j0 - 3 + r) + lcol);
+      } else { // the operands of the point-wise epilogue
+#pragma unroll
+        for (int t = 0; t < B; ++t) {
+          const unsigned o = rowoff(j0 + t) + lcol;
+          e_wek[t] = tr_ld(P.wekpo, o);
+          if (ENT) e_ent[ENT ? t : 0] = tr_ld(P.entoc, o);
+          if (DDY) e_ddy[DDY ? t : 0] = tr_ld(P.ddynoc, o);
+#pragma unroll
+          for (int kk = 0; kk < NL; ++kk) e_qm[kk][t] = tr_ld(P.qnew + fs * kk, o);
+        }
+      }
+      TR_FENCE();
+      // Del^4 of rows j0-1 .. j0+B
+#pragma unroll
+      for (int r = 0; r < B + 2; ++r) {
+        d4[r] = tr_lap(R, d2[r], d2[r + 1], d2[r + 2], j0 - 1 + r + R.vz);
+        TR_PIN(d4[r]);
+      }
+      TR_FENCE();
+      // Del^6 + Arakawa Jacobian (qgosubs.F:349-399); S / C / N rows gj-1 / gj / gj+1, w / e columns i-1 / i+1
+#pragma unroll
+      for (int t = 0; t < B; ++t) {
+        const double d4A = d4[t], d4B = d4[t + 1], d4C = d4[t + 2];
+        const double d4w = TR_WEST(d4B), d4e = TR_EAST(d4B);
+        const double pS = pr[t], pC = pr[t + 1], pN = pr[t + 2];
+        const double qS = qr[t], qC = qr[t + 1], qN = qr[t + 2];
+        const double pSw = TR_WEST(pS), pSe = TR_EAST(pS), pCw = TR_WEST(pC), pCe = TR_EAST(pC), pNw = TR_WEST(pN), pNe = TR_EAST(pN);
+        const double qSw = TR_WEST(qS), qSe = TR_EAST(qS), qCw = TR_WEST(qC), qCe = TR_EAST(qC), qNw = TR_WEST(qN), qNe = TR_EAST(qN);
+        const double d6p = dxom2 * (d4A + d4w + d4e + d4C - 4.0 * d4B);
+        const double diffus = P.ah2fac[k] * d4B - P.ah4fac[k] * d6p;
+        double jac = (qCe - qCw) * (pN - pS) + (qS - qN) * (pCe - pCw) +
+                     qCe * (pNe - pSe) - qCw * (pNw - pSw) -
+                     qN * (pNe - pNw) + qS * (pSe - pSw);
+        jac = jac + pN * (qNe - qNw) - pS * (qSe - qSw) -
+              pCe * (qNe - qSe) + pCw * (qNw - qSw);
+        const double val = P.adfaco * jac + diffus;
+        dq[k][t] = cint ? val : 0.0; // dqdt = 0 on the wall columns (qgosubs.F:371,397)
+        if (k == NL - 1) d2bot[t] = d2[t + 2];
+        TR_PIN(dq[k][t]);
+        TR_FENCE();
+      }
+      if (k + 1 < NL) {
+        const double *pok = po0 + fs * (k + 1), *qok = qo0 + fs * (k + 1);
+#pragma unroll
+        for (int r = 0; r < B + 2; ++r) {
+          pr[r] = tr_ld(pok, rowoff(j0 - 1 + r) + lcol);
+          qr[r] = tr_ld(qok, rowoff(j0 - 1 + r) + lcol);
+        }
+        TR_FENCE();
+      }
+    }
+#undef TR_FENCE
+#undef TR_PIN
+    // ---- forcing, bottom drag, leapfrog, projection: tend_point's expressions (k_tend.h), every lane goes through ----
+#pragma unroll
+    for (int t = 0; t < B; ++t) {
+      const int gj = j0 + t;
+      if (gj > jr1) break; // (wave-uniform: the partial last band)
+      const long o = (long)(gj - 1) * ldx + (gc - 1);
+      // (a field the host knows to be all zero enters as a literal 0.0: the same expressions, the same bits)
+      const double wek = e_wek[t], ent = ENT ? e_ent[ENT ? t : 0] : 0.0, ddy = DDY ? e_ddy[DDY ? t : 0] : 0.0;
+      double qdot[NL];
+#pragma unroll
+      for (int k = 0; k < NL; ++k) qdot[k] = dq[k][t];
+      qdot[0] = dq[0][t] + P.fohfac[0] * (wek - ent);
+      qdot[1] = dq[1][t] + P.fohfac[1] * ent;
+      qdot[NL - 1] = qdot[NL - 1] - P.bdrfac * d2bot[t];
+      double ql[NL];
+      const double betay = P.beta * P.yporel[gj - 1];
+#pragma unroll
+      for (int k = 0; k < NL; ++k) {
+        const double qn = e_qm[k][t] + P.tdto * qdot[k]; // qom + tdto*qdot
+        qg_pair_store_wt(P.qnew + fs * k + o, qn, own && gi <= nx - 1);
+        if (own && gi == nx) P.qnew[fs * k + o] = qn; // (the E wall column has no partner: the odd one out of 961)
+        ql[k] = qn - betay;
+      }
+      ql[NL - 1] = ql[NL - 1] - ddy;
+      double *dst = lds + ((t >> 1) * NL) * REG + (t & 1) * N + (gi - 2);
+#pragma unroll
+      for (int m = 0; m < NL; ++m) {
+        double qmm = 0.0;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) qmm = qmm + P.ctl2m[k + NL * m] * ql[k];
+        if (own && cint) dst[m * REG] = P.fnot * qmm;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: forward DST-I of the band's rows, a wave per (row pair, mode), as k_dst64 --------------------------
+  if (wv >= NPW * NL) return;
+  const int pair = wv / NL, m = wv - pair * NL;
+  const int ja = j0 + 2 * pair;
+  if (ja > jr1) return;
+  const bool has_b = (ja + 1 <= jr1);
+  double *reg = lds + wv * REG; // (wv = pair * NL + m)
+  cplx *F = reinterpret_cast<cplx *>(reg);
+  cplx *W64 = reinterpret_cast<cplx *>(reg + M * D64_ROW * 2);
+  double *rowa = P.wrk + P.g.wstride * m + (long)(ja - 1) * P.g.ldw;
+  double *rowb = rowa + P.g.ldw;
+  double rsa, rsb;
+  dst64_front<M>(twid, sintab, reg, reg + N, has_b, F, W64, lane);
+  dst64_back<M>(F, W64, lane, rsa, rsb);
+  const double *raw = reg;
+  constexpr int NP = N + N / 16;
+  {
+    constexpr int NU = (N / 2 + 63) / 64;
+    double2 oa[NU], ob[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int t = lane + 64 * u;
+      const int tc = t < N / 2 ? t : N / 2 - 1;
+      const int i = 2 * tc + ((2 * tc) >> 4);
+      oa[u] = double2{raw[i], raw[i + 1]};
+      ob[u] = double2{raw[NP + i], raw[NP + i + 1]};
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int t = lane + 64 * u;
+      if (t < N / 2) { // (write-through: qgcm_dev.h)
+        qg_store16_wt(rowa + 2 * t, oa[u].x, oa[u].y);
+        if (has_b) qg_store16_wt(rowb + 2 * t, ob[u].x, ob[u].y);
+      }
+    }
+  }
+}

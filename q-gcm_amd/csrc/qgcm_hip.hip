@@ -259,6 +259,8 @@ struct qgcm_hip_ctx {
   // of the allocation and by the scan of every host array handed in (set_forcing; set_geometry / set_grid), cleared by
   // every device-side writer of entoc (the mixed layers).  tend_zmask turns them into k_tend_z's ZM.
   bool entoc_zero = false, ddynoc_zero = false;
+  bool no_band_rows;      // QGCM_HIP_NO_BAND_ROWS=1: the 5 km step keeps k_tend + k_dst64 instead of the row-band kernel k_tend_rows (A/B + tests)
+  bool beside = false;    // qgcm_hip_coupled_steps: an atmosphere handle steps beside this ocean on the same GPU (step_plan: band_rows)
   bool read_zero_fields;  // QGCM_HIP_READ_ZERO_FIELDS=1: the tendency kernel reads entoc and ddynoc whatever they hold (A/B + tests)
   std::vector<double> bd2oc;
   // profiling
@@ -576,6 +578,8 @@ extern "C" int qgcm_hip_create(qgcm_hip_handle *h, const qgcm_hip_params *prm, i
     c->no_fused_avg = fa && fa[0] == '1';
     const char *rz = getenv("QGCM_HIP_READ_ZERO_FIELDS");
     c->read_zero_fields = rz && rz[0] == '1';
+    const char *br = getenv("QGCM_HIP_NO_BAND_ROWS");
+    c->no_band_rows = br && br[0] == '1';
   }
   c->profiling = false;
   HIPCHECK(hipEventCreate(&c->ev0));
@@ -1358,6 +1362,8 @@ struct QgStepPlan {
   bool upd_dpi; // k_tend steps dpioc / dpiocp (the constraint solve of CONSTR_INV_WAVE starts from the stepped values)
   bool wtq;     // k_tend: write-through pair stores of the new qo and 16-wide tiles
   bool avg_ok;  // a leapfrog-averaging step may be fused into k_tend and the fused inverse kernel
+  bool band_rows; // one_step's plain steps run k_tend_rows (k_tend_rows.h: tendency by bands of so many rows, whose
+                // epilogue is the forward row transform) in place of launch_tend + the forward launch_dst
 };
 
 // in_step: inside qgcm_hip_steps (k_tend has stepped dpioc where the plan says so, the boundary PV is fused into the
@@ -1407,6 +1413,16 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
   // see this step's po before it is averaged.)
   pl.avg_ok = in_step && !slab && !c->no_fused_avg && !c->poavg.on &&
               ((pl.constr == CONSTR_INV_WAVE && pl.wtq) || pl.inv == INV_FFT3_UNPACK);
+  // the 5 km box ocean inside qgcm_hip_steps: tendency and forward rows in one launch.  The kernel exists for three
+  // layers, 960-point rows, entoc and ddynoc both read or both all zero; it carries neither the mixed layers' riders nor
+  // the sponge term.  (The running mean of po adds its launch after the step either way: the same plan on or off.)
+  // Not where the ocean shares the GPU with an atmosphere (qgcm_hip_coupled_steps) or has a CU range: the kernel's 240
+  // workgroups want a whole CU each (768 threads, 110 KB of LDS) and one generation of them - with 192 CUs, or with CUs
+  // that hold the atmosphere's waves, the coupled ocean step was 4.5 us slower than with the two launches.
+  const int zm = tend_zmask(c);
+  pl.band_rows = (!c->no_band_rows && !g.cyc && pl.rows == ROWS_DST64 && pl.m64 == 15 && g.nl == 3 && in_step && !slab &&
+                  c->whole && c->seg.S == 1 && pl.wtq && pl.constr == CONSTR_INV_WAVE && (zm == 0 || zm == 3) &&
+                  !c->oml.on && !c->aml.on && !(const double *)c->rspl && !c->beside && c->cu_count == 0);
   return pl;
 }
 
@@ -1416,15 +1432,15 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
 // the 5 km step by +-0.7 us).
 static void launch_tend_z(int zm, int nl, bool cyc, bool wtq, bool avg, dim3 grid, hipStream_t stream, const QgTendParams &P,
                           const QgCycSumParams &S, const QgOmlFinal &F);
+// The row-band kernel of the 5 km box ocean (k_tend_rows.h; step_plan's band_rows).  The kernel and its launch live in
+// k_tend_rows.hip, a device code object of its own: this file compiles to the device code it had without the kernel.
+void qg_launch_tend_rows(int zm, hipStream_t st, const QgTendParams &P, const double2 *twid, const double *sintab);
+static int launch_tend_rows(qgcm_hip_ctx *c, bool upd_dpi);
 
-// avg: the launch stores the averaged time level (one_step); bpart: where the extra workgroups put the boundary line
-// sums (nullptr: c->bpart; y-slabs: the tail of the step message); st: nullptr = the handle's stream
-static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = false, int part = TEND_ALL, bool avg = false,
-                       double *bpart = nullptr, hipStream_t st = nullptr) {
-  if (!st) st = c->stream;
+// what the tendency kernels read (launch_tend, launch_tend_rows)
+static void fill_tend_params(const qgcm_hip_ctx *c, QgTendParams &P, bool upd_dpi) {
   const QgGeom &g = c->g;
   const qgcm_hip_params &pr = c->prm;
-  QgTendParams P;
   memset(&P, 0, sizeof(P));
   P.g = g;
   P.pom = c->p[c->ip ^ 1];
@@ -1450,6 +1466,17 @@ static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = f
   P.rspl = c->rspl;
   P.tdc1 = pr.tdto * c->c1_spl; // tdto*c1_spl, src/qgosubs.F:204
   for (int k = 0; k < g.nl; ++k) P.gpoc[k] = pr.gpoc[k];
+}
+
+// avg: the launch stores the averaged time level (one_step); bpart: where the extra workgroups put the boundary line
+// sums (nullptr: c->bpart; y-slabs: the tail of the step message); st: nullptr = the handle's stream
+static int launch_tend(qgcm_hip_ctx *c, bool upd_dpi = false, bool oml_final = false, int part = TEND_ALL, bool avg = false,
+                       double *bpart = nullptr, hipStream_t st = nullptr) {
+  if (!st) st = c->stream;
+  const QgGeom &g = c->g;
+  const qgcm_hip_params &pr = c->prm;
+  QgTendParams P;
+  fill_tend_params(c, P, upd_dpi);
   // write-through pair stores of the new qo and 16-wide tiles while the step's working set (~ 7 nl - 1 fields) stays in the
   // 256 MiB Infinity Cache (NAtl 5 km: 150 MB: -1 us per step; SOcn 5 km's 425 MB: +8 us); plain stores and 32-wide
   // tiles at the HBM-bound sizes (k_tend.h)
@@ -1947,13 +1974,13 @@ static int launch_inverse(qgcm_hip_ctx *c, const QgStepPlan &pl, bool fuse_bdy, 
 // in_step: called from qgcm_hip_steps, where k_tend has already stepped dpioc / dpiocp where the plan says so
 // (launch_tend(c, pl.upd_dpi)) and ocqbdy is fused into the unpack; the launches are step_plan's.  avg: one_step's
 // averaging step, the fused inverse kernel stores the averaged level
-static int ocinvq_impl(qgcm_hip_ctx *c, bool in_step = false, bool avg = false) {
+static int ocinvq_impl(qgcm_hip_ctx *c, bool in_step = false, bool avg = false, bool fwd_done = false) {
   if (check_ready(c, "qgcm_hip_ocinvq")) return 1;
   if (!c->whole) QG_FAIL("qgcm_hip_ocinvq: this handle is a y-slab; drive it with the slab building blocks");
   if (!c->homog_set) QG_FAIL("qgcm_hip_ocinvq: homogeneous solutions not set");
   const QgStepPlan pl = step_plan(c, in_step);
   // (A per-mode side-stream variant of this chain was measured slower - 140 vs 116 us/step at 5 km - and removed.)
-  if (launch_dst(c, c->wrk, c->g.nl, false)) return 1;
+  if (!fwd_done && launch_dst(c, c->wrk, c->g.nl, false)) return 1; // (fwd_done: k_tend_rows has left the spectral rows in wrk)
   if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr, pl.constr == CONSTR_AB)) return 1;
   // area (and, cyclic, line) integrals are a by-product of the y sweeps: the constraints precede the inverse transform
   if (pl.constr == CONSTR_OWN && launch_constr(c)) return 1;
@@ -2233,9 +2260,11 @@ static int one_step(qgcm_hip_ctx *c, int s) {
   // 21 us every 25 steps); the integrals dpioc follow in a one-thread launch.  Same expressions: bitwise the same fields.
   const bool avg = avg_after(c, s);
   const bool avg_fused = avg && pl.avg_ok; // (long-row cyclic oceans: k_rfft3_unpack<.., AVG> does what k_dst64_unpack does for the box)
-  if (launch_tend(c, pl.upd_dpi, c->oml.on || c->aml.on, TEND_ALL, avg_fused)) return 1;
+  // (the 5 km box ocean's plain steps: tendency and forward rows in one launch; averaging steps keep the two)
+  const bool rows_fused = pl.band_rows && !avg;
+  if (rows_fused ? launch_tend_rows(c, pl.upd_dpi) : launch_tend(c, pl.upd_dpi, c->oml.on || c->aml.on, TEND_ALL, avg_fused)) return 1;
   c->iq ^= 1; // as qgcm_hip_qgostep
-  if (ocinvq_impl(c, true, avg_fused)) return 1; // ocqbdy fused into the unpack kernel
+  if (ocinvq_impl(c, true, avg_fused, rows_fused)) return 1; // ocqbdy fused into the unpack kernel
   if (c->poavg.on && launch_poavg(c)) return 1; // avg_ocn_k247 right after ocqbdy, src/q-gcm.F:1250-1252
   if (avg_fused) {
     KTimer t(c, KN_LFAVG);
@@ -2329,7 +2358,8 @@ static long long graph_key(const qgcm_hip_ctx *c, int s0, int B) {
   const int omk = c->oml.on ? 1 + 3 * c->oml.is + c->oml.ism : c->aml.on ? 1 + 3 * c->aml.ia + c->aml.iam : 0;
   // ... and which tendency kernel the block launches (tend_zmask: set_forcing changes it without dropping the graphs;
   // omk < 16, so bits 28-29 are free)
-  return ((long long)B << 32) | ((long long)c->poavg.on << 31) | ((long long)tend_zmask(c) << 28) | (omk << 24) | (c->ip << 16) |
+  // (bit 30: step_plan's band_rows depends on whether an atmosphere steps beside the ocean)
+  return ((long long)B << 32) | ((long long)c->poavg.on << 31) | ((long long)c->beside << 30) | ((long long)tend_zmask(c) << 28) | (omk << 24) | (c->ip << 16) |
          (c->iq << 8) | avg_phase(c, s0);
 }
 
@@ -3050,6 +3080,7 @@ extern "C" int qgcm_hip_coupled_steps(qgcm_hip_handle oc, qgcm_hip_handle atm, i
   if (oc && check_ready(oc, "qgcm_hip_coupled_steps")) return 1;
   if (atm && check_atm(atm, "qgcm_hip_coupled_steps")) return 1;
   if (oc && (oc->g.atm || !oc->whole)) QG_FAIL("qgcm_hip_coupled_steps: first handle must be a whole-domain ocean");
+  if (oc) oc->beside = atm != nullptr; // (part of the graph key)
   if (atm && atm->xf.coupled) {
     // qgcm_hip_coupled_set_xforc: the reference's order (src/q-gcm.F:1222-1268) - at every nt with mod(nt,nstr) == 1
     // xforc, then the ocean step, then the atmospheric steps up to the next such nt.  The events of qgcm_hip_xforc
@@ -3838,4 +3869,22 @@ static void launch_tend_z(int zm, int nl, bool cyc, bool wtq, bool avg, dim3 gri
     }
   }
 #undef QG_TEND_Z
+}
+
+// ---------------------------------------------------------------------------
+// The row-band kernel: tendency + forward rows of the 5 km box ocean in one launch (k_tend_rows.h, k_tend_rows.hip).
+// ---------------------------------------------------------------------------
+static int launch_tend_rows(qgcm_hip_ctx *c, bool upd_dpi) {
+  const QgGeom &g = c->g;
+  QgTendParams P;
+  fill_tend_params(c, P, upd_dpi);
+  const int zm = tend_zmask(c);
+  // (ny * ldx < 2^29: the kernel forms 32-bit byte offsets inside a layer)
+  if (g.cyc || g.nl != 3 || g.nxt != 960 || !c->whole || g.joff != 0 || g.jlo != 1 || g.jhi != g.ny || g.nyg != g.ny || g.ny < 3 ||
+      (long)g.ny * g.ldx >= (1L << 29) || (zm != 0 && zm != 3) || P.rspl)
+    QG_FAIL("k_tend_rows: the row-band kernel belongs to whole-domain steps of the three-layer box ocean with 960-point rows");
+  KTimer t(c, KN_TEND, c->stream);
+  qg_launch_tend_rows(zm, c->stream, P, c->twid, c->sintab);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }
