@@ -18,6 +18,7 @@
 //                optionally fused with ocqbdy (zonal boundaries only).
 #pragma once
 #include "qgcm_dev.h"
+#include "qg_ref_expr.h"
 
 struct QgCycSumParams {
   QgGeom g;
@@ -58,14 +59,14 @@ __device__ __forceinline__ void cyc_bsums_block(const QgCycSumParams &P, int bid
   // rows counted from the boundary inwards: r = 0 boundary row, 1, 2, 3
   auto row = [&](int r) { return north ? (P.g.jhi - 1 - r) : (P.g.jlo - 1 + r); }; // 0-based local row
   auto PM = [&](int i, int r) { return pom[(long)row(r) * ldx + (cyc_col(i, nxt) - 1)]; };
-  // Del^2 of pom on rows r = 0 (boundary, mixed BC), 1, 2 (interior 5-point, cyclic in x)
+  // Del^2 of pom on rows r = 0 (boundary, mixed BC), 1, 2 (interior 5-point, cyclic in x): qg_ref_expr.h
   auto D2 = [&](int i, int r) {
-    if (r == 0) return bcf * (PM(i, 1) - PM(i, 0));
-    return (PM(i, r - 1) + PM(i - 1, r) + PM(i + 1, r) + PM(i, r + 1) - 4.0 * PM(i, r)) * dxom2;
+    if (r == 0) return QG_WALL_RULE(bcf, PM(i, 1), PM(i, 0));
+    return QG_FIVE_POINT(PM(i, r - 1), PM(i - 1, r), PM(i + 1, r), PM(i, r + 1), PM(i, r)) * dxom2;
   };
   auto D4 = [&](int i, int r) { // r = 0 or 1
-    if (r == 0) return bcf * (D2(i, 1) - D2(i, 0));
-    return dxom2 * (D2(i, 0) + D2(i - 1, 1) + D2(i + 1, 1) + D2(i, 2) - 4.0 * D2(i, 1));
+    if (r == 0) return QG_WALL_RULE(bcf, D2(i, 1), D2(i, 0));
+    return dxom2 * QG_FIVE_POINT(D2(i, 0), D2(i - 1, 1), D2(i + 1, 1), D2(i, 2), D2(i, 1));
   };
   // note: for the northern boundary "r-1" is the row to the north, "r+1" to the south; the
   // 5-point operator is symmetric so the value is the same, only the summation order of the

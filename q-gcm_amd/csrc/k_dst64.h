@@ -418,28 +418,7 @@ __global__ __launch_bounds__(D64_NT) void k_dst64(QG_ROW_ARGS, const QgDstParams
   dst64_back<M>(Fsh[wv], W64sh[wv], lane, rsa, rsb);
   QG_STAMP(0, 2);
   const double *raw = reinterpret_cast<const double *>(Fsh[wv]);
-  constexpr int NP = N + N / 16;
-  {
-    constexpr int NU = (N / 2 + 63) / 64;
-    // all LDS reads of the two output rows first, then the global stores (one exposed LDS round trip instead of 2 NU)
-    double2 oa[NU], ob[NU];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const int t = lane + 64 * u;
-      const int tc = t < N / 2 ? t : N / 2 - 1;
-      const int i = 2 * tc + ((2 * tc) >> 4); // 2t and 2t+1 share a 16-group: consecutive after padding
-      oa[u] = double2{raw[i], raw[i + 1]};
-      ob[u] = double2{raw[NP + i], raw[NP + i + 1]};
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const int t = lane + 64 * u;
-      if (t < N / 2) { // (write-through: qgcm_dev.h)
-        qg_store16_wt(rowa + 2 * t, oa[u].x, oa[u].y);
-        if (has_b) qg_store16_wt(rowb + 2 * t, ob[u].x, ob[u].y);
-      }
-    }
-  }
+#include "k_dst64_store.inc"
   QG_STAMP(0, 3);
   QG_STAMP_DRAIN();
   QG_STAMP(0, 4);

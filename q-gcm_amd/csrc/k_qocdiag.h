@@ -24,6 +24,7 @@
 // j+3, po / qo on rows j-1 .. j+1: the three halo rows that k_monslab_scan relies on.
 #pragma once
 #include "qgcm_dev.h"
+#include "qg_ref_expr.h" // what qocdiag_out shares with qgostep: the five-point sum, the wall rule, the Jacobian
 
 #define QD_TX 64 // tile width = one wave: lane = column
 #define QD_TY 16
@@ -79,14 +80,13 @@ __global__ __launch_bounds__(QD_NT) void k_qocdiag(const QgQocdiagParams P) {
     const int c = qd_col<CYC>(i0 - 2 + a, nx), lj = j0 - 2 + b, gj = lj + joff;
     double v = 0.0;
     if (c >= 1 && gj >= 1 && gj <= ny && lj >= P.jlo - 2 && lj <= P.jhi + 2) {
-      if (gj == 1) v = bcfaco * (QD_AT(pmk, c, lj + 1) - QD_AT(pmk, c, lj));
-      else if (gj == ny) v = bcfaco * (QD_AT(pmk, c, lj - 1) - QD_AT(pmk, c, lj));
-      else if (!CYC && c == 1) v = bcfaco * (QD_AT(pmk, 2, lj) - QD_AT(pmk, 1, lj));
-      else if (!CYC && c == nx) v = bcfaco * (QD_AT(pmk, nx - 1, lj) - QD_AT(pmk, nx, lj));
+      if (gj == 1) v = QG_WALL_RULE(bcfaco, QD_AT(pmk, c, lj + 1), QD_AT(pmk, c, lj));
+      else if (gj == ny) v = QG_WALL_RULE(bcfaco, QD_AT(pmk, c, lj - 1), QD_AT(pmk, c, lj));
+      else if (!CYC && c == 1) v = QG_WALL_RULE(bcfaco, QD_AT(pmk, 2, lj), QD_AT(pmk, 1, lj));
+      else if (!CYC && c == nx) v = QG_WALL_RULE(bcfaco, QD_AT(pmk, nx - 1, lj), QD_AT(pmk, nx, lj));
       else {
         const int il = (CYC && c == 1) ? nx - 1 : c - 1;
-        v = (QD_AT(pmk, c, lj - 1) + QD_AT(pmk, il, lj) + QD_AT(pmk, c + 1, lj) + QD_AT(pmk, c, lj + 1) -
-             4.0 * QD_AT(pmk, c, lj)) * dxom2;
+        v = QG_FIVE_POINT(QD_AT(pmk, c, lj - 1), QD_AT(pmk, il, lj), QD_AT(pmk, c + 1, lj), QD_AT(pmk, c, lj + 1), QD_AT(pmk, c, lj)) * dxom2;
       }
     }
     d2[b][a] = v;
@@ -99,11 +99,11 @@ __global__ __launch_bounds__(QD_NT) void k_qocdiag(const QgQocdiagParams P) {
     double v = 0.0;
     if (c >= 1 && gj >= 1 && gj <= ny && lj >= P.jlo - 1 && lj <= P.jhi + 1) {
       const int A = a + 1, B = b + 1;
-      if (gj == 1) v = bcfaco * (d2[B + 1][A] - d2[B][A]);
-      else if (gj == ny) v = bcfaco * (d2[B - 1][A] - d2[B][A]);
-      else if (!CYC && c == 1) v = bcfaco * (d2[B][A + 1] - d2[B][A]);
-      else if (!CYC && c == nx) v = bcfaco * (d2[B][A - 1] - d2[B][A]);
-      else v = (d2[B - 1][A] + d2[B][A - 1] + d2[B][A + 1] + d2[B + 1][A] - 4.0 * d2[B][A]) * dxom2;
+      if (gj == 1) v = QG_WALL_RULE(bcfaco, d2[B + 1][A], d2[B][A]);
+      else if (gj == ny) v = QG_WALL_RULE(bcfaco, d2[B - 1][A], d2[B][A]);
+      else if (!CYC && c == 1) v = QG_WALL_RULE(bcfaco, d2[B][A + 1], d2[B][A]);
+      else if (!CYC && c == nx) v = QG_WALL_RULE(bcfaco, d2[B][A - 1], d2[B][A]);
+      else v = QG_FIVE_POINT(d2[B - 1][A], d2[B][A - 1], d2[B][A + 1], d2[B + 1][A], d2[B][A]) * dxom2;
     }
     d4[b][a] = v;
   }
@@ -125,20 +125,15 @@ __global__ __launch_bounds__(QD_NT) void k_qocdiag(const QgQocdiagParams P) {
       dqdt = P.rdto * (QD_AT(qk, gi, j) - QD_AT(P.qom + fs * k, gi, j));
     } else {
       const int A = lane + 1, B = r + 1; // d4 centre; d2 centre (B + 1, A + 1)
-      const double d6p = dxom2 * (d4[B - 1][A] + d4[B][A - 1] + d4[B][A + 1] + d4[B + 1][A] - 4.0 * d4[B][A]);
+      const double d6p = dxom2 * QG_FIVE_POINT(d4[B - 1][A], d4[B][A - 1], d4[B][A + 1], d4[B + 1][A], d4[B][A]);
       qt2 = P.ah2fac[k] * d4[B][A];
       qt4 = -(P.ah4fac[k] * d6p);
-      jac = P.adfaco *
-            ((QD_AT(qk, ir, j) - QD_AT(qk, il, j)) * (QD_AT(pk, c, j + 1) - QD_AT(pk, c, j - 1))
-             + (QD_AT(qk, c, j - 1) - QD_AT(qk, c, j + 1)) * (QD_AT(pk, ir, j) - QD_AT(pk, il, j))
-             + QD_AT(qk, ir, j) * (QD_AT(pk, ir, j + 1) - QD_AT(pk, ir, j - 1))
-             - QD_AT(qk, il, j) * (QD_AT(pk, il, j + 1) - QD_AT(pk, il, j - 1))
-             - QD_AT(qk, c, j + 1) * (QD_AT(pk, ir, j + 1) - QD_AT(pk, il, j + 1))
-             + QD_AT(qk, c, j - 1) * (QD_AT(pk, ir, j - 1) - QD_AT(pk, il, j - 1))
-             + QD_AT(pk, c, j + 1) * (QD_AT(qk, ir, j + 1) - QD_AT(qk, il, j + 1))
-             - QD_AT(pk, c, j - 1) * (QD_AT(qk, ir, j - 1) - QD_AT(qk, il, j - 1))
-             - QD_AT(pk, ir, j) * (QD_AT(qk, ir, j + 1) - QD_AT(qk, ir, j - 1))
-             + QD_AT(pk, il, j) * (QD_AT(qk, il, j + 1) - QD_AT(qk, il, j - 1)));
+      jac = P.adfaco * QG_JAC_TAIL(
+                QG_JAC_HEAD(QD_AT(qk, c, j - 1), QD_AT(qk, il, j), QD_AT(qk, ir, j), QD_AT(qk, c, j + 1),
+                            QD_AT(pk, c, j - 1), QD_AT(pk, il, j), QD_AT(pk, ir, j), QD_AT(pk, c, j + 1),
+                            QD_AT(pk, il, j - 1), QD_AT(pk, ir, j - 1), QD_AT(pk, il, j + 1), QD_AT(pk, ir, j + 1)),
+                QD_AT(pk, c, j - 1), QD_AT(pk, il, j), QD_AT(pk, ir, j), QD_AT(pk, c, j + 1),
+                QD_AT(qk, il, j - 1), QD_AT(qk, ir, j - 1), QD_AT(qk, il, j + 1), QD_AT(qk, ir, j + 1));
       if (k == 0) ent = P.fohfac[0] * (QD_AT(P.wekpo, c, j) - QD_AT(P.entoc, c, j));
       else if (k == 1) ent = P.fohfac[1] * QD_AT(P.entoc, c, j);
       else ent = 0.0;

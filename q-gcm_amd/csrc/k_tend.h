@@ -32,6 +32,7 @@
 // The kernels' body is k_tend_body.inc (shared by k_tend and k_tend_z).
 #pragma once
 #include "qgcm_dev.h"
+#include "qg_ref_expr.h" // the five-point sum, the wall rule, the Jacobian
 #include "k_misc.h" // constr_dpi_update
 #include "k_cyclic.h" // cyc_bsums_block
 #include "k_oml.h" // oml_final_block
@@ -189,7 +190,7 @@ __device__ __forceinline__ void tend_edge(const QgTendParams &P, const TendTilin
   double d2bot = 0.0, wek = 0.0, ent = 0.0, ddy = 0.0;
   if (!wallrow) { // then gi == nx: E wall column of a stepped row
     const double *pb = P.pom + fs * (NL - 1) + o;
-    d2bot = P.bcfaco * (pb[-1] - pb[0]);
+    d2bot = QG_WALL_RULE(P.bcfaco, pb[-1], pb[0]);
     wek = P.wekpo[o];
     if (!(ZM & 1)) ent = P.entoc[o];
     if (!(ZM & 2)) ddy = P.ddynoc[o];

@@ -108,8 +108,6 @@
     const int idx = tid + e * TEND_NT;
     const int lx = idx % W2, ly = idx / W2;
     const int gi = i0 - 2 + lx, gj = j0 - 2 + ly;
-    const bool inx = CYC ? (gi >= -1 && gi <= nx + 2) : (gi >= 1 && gi <= nx);
-    (void)inx;
     b2[e] = (idx < H2 * W2) ? (ly + 1) * W3 + (lx + 1) : W3 + 1; // clamped: the extra pass reads valid LDS, stores nothing
     const bool wS = (gj + joff == 1), wN = (gj + joff == nyg), wW = (!CYC && gi == 1), wE = (!CYC && gi == nx);
     w2[e] = wS || wN || wW || wE;
@@ -120,8 +118,6 @@
     const int idx = tid + e * TEND_NT;
     const int lx = idx % W1, ly = idx / W1;
     const int gi = i0 - 1 + lx, gj = j0 - 1 + ly;
-    const bool inx = CYC ? (gi >= 0 && gi <= nx + 1) : (gi >= 1 && gi <= nx);
-    (void)inx;
     b4[e] = (idx < H1 * W1) ? (ly + 1) * W2 + (lx + 1) : W2 + 1;
     const bool wS = (gj + joff == 1), wN = (gj + joff == nyg), wW = (!CYC && gi == 1), wE = (!CYC && gi == nx);
     w4[e] = wS || wN || wW || wE;
@@ -190,10 +186,10 @@
       const int idx = tid + e * TEND_NT;
       const double *c = &sp[b2[e]];
       // branch-free: the wall rule picks ONE inner neighbour (N, S, E or W of a wall point), the interior rule is
-      // evaluated alongside and the result selected - same expressions, same rounding, no exec-mask bookkeeping
+      // evaluated alongside and the result selected - qg_ref_expr.h's expressions, no exec-mask bookkeeping
       const double cS = c[-W3], cW = c[-1], c0 = c[0], cE = c[1], cN = c[W3];
-      const double vw = bcf * (sp[i2[e]] - c0);
-      const double vi = (cS + cW + cE + cN - 4.0 * c0) * dxom2;
+      const double vw = QG_WALL_RULE(bcf, sp[i2[e]], c0);
+      const double vi = QG_FIVE_POINT(cS, cW, cE, cN, c0) * dxom2;
       if (idx < H2 * W2) sd2[idx] = w2[e] ? vw : vi;
     }
     __syncthreads();
@@ -203,8 +199,8 @@
       const int idx = tid + e * TEND_NT;
       const double *c = &sd2[b4[e]];
       const double cS = c[-W2], cW = c[-1], c0 = c[0], cE = c[1], cN = c[W2];
-      const double vw = bcf * (sd2[i4[e]] - c0);
-      const double vi = dxom2 * (cS + cW + cE + cN - 4.0 * c0);
+      const double vw = QG_WALL_RULE(bcf, sd2[i4[e]], c0);
+      const double vi = dxom2 * QG_FIVE_POINT(cS, cW, cE, cN, c0);
       if (idx < H1 * W1) sd4[idx] = w4[e] ? vw : vi;
     }
     __syncthreads();
@@ -219,18 +215,16 @@
         const double *d4 = &sd4[(ly + 1) * W1 + (tx + 1)];
         const double *p = &spo[(ly + 1) * W1 + (tx + 1)];
         const double *q = &sqo[(ly + 1) * W1 + (tx + 1)];
-        double d6p = dxom2 * (d4[-W1] + d4[-1] + d4[1] + d4[W1] - 4.0 * d4[0]);
+        double d6p = dxom2 * QG_FIVE_POINT(d4[-W1], d4[-1], d4[1], d4[W1], d4[0]);
         double diffus = P.ah2fac[k] * d4[0] - P.ah4fac[k] * d6p;
-        // (the sum is formed left to right, as one expression would be: the same bits.  The compiler barrier between its
-        //  halves exists in the wide-tile variants only: there the LDS reads of all twelve terms in flight at once left
+        // (the halves of qg_ref_expr.h's Jacobian chain to the one left-to-right sum: the same bits.  The compiler barrier
+        //  between them exists in the wide-tile variants only: there the LDS reads of all twelve terms in flight at once left
         //  k_tend_z<2, true, false, false, 3> with 84 VGPRs against its twin's 82; with it the wide variants take 72 / 86 / 90
         //  VGPRs for 2 / 3 / 4 layers instead of 82 / 96 / 100.  k_tend and the 16-wide variants compile as without it.)
-        double jac = (q[1] - q[-1]) * (p[W1] - p[-W1]) + (q[-W1] - q[W1]) * (p[1] - p[-1]) +
-                     q[1] * (p[W1 + 1] - p[-W1 + 1]) - q[-1] * (p[W1 - 1] - p[-W1 - 1]) -
-                     q[W1] * (p[W1 + 1] - p[W1 - 1]) + q[-W1] * (p[-W1 + 1] - p[-W1 - 1]);
+        double jac = QG_JAC_HEAD(q[-W1], q[-1], q[1], q[W1], p[-W1], p[-1], p[1], p[W1],
+                                 p[-W1 - 1], p[-W1 + 1], p[W1 - 1], p[W1 + 1]);
         if (ZM && !WTQ) asm volatile("" ::: "memory");
-        jac = jac + p[W1] * (q[W1 + 1] - q[W1 - 1]) - p[-W1] * (q[-W1 + 1] - q[-W1 - 1]) -
-              p[1] * (q[W1 + 1] - q[-W1 + 1]) + p[-1] * (q[W1 - 1] - q[-W1 - 1]);
+        jac = QG_JAC_TAIL(jac, p[-W1], p[-1], p[1], p[W1], q[-W1 - 1], q[-W1 + 1], q[W1 - 1], q[W1 + 1]);
         val = P.adfaco * jac + diffus;
       }
       dq[k][r] = val;

@@ -11,8 +11,8 @@
 //     even lane of a lane pair is 16-byte aligned for qg_pair_store_wt).  East / west neighbours come from DPP wave
 //     shifts, north / south neighbours are the rows the lane holds in registers.  The wave walks the layers of its strip
 //     one after the other (the loads of layer k+1 are requested before layer k is computed), keeps dqdt of all layers in
-//     registers and finishes with the point-wise part (forcing, drag, leapfrog, projection) - the expressions, the
-//     association order and the wall rules are those of k_tend_body.inc and tend_point, contraction off.  The new qo
+//     registers and finishes with the point-wise part (forcing, drag, leapfrog, projection) - the five-point sum, the
+//     wall rule and the Jacobian are qg_ref_expr.h's, the point-wise expressions tend_point's, contraction off.  The new qo
 //     leaves in 16-byte write-through pairs; the modal right-hand side fnot * qmm goes to LDS, one row per (row, mode);
 //   * ONE workgroup barrier;
 //   * phase 2 (forward rows): B/2 x NL of the waves run dst64_front / dst64_back (k_dst64.h, unchanged) on one (row
@@ -53,22 +53,20 @@ struct TrRules {
   double bcf, dxom2;
 };
 
-// Five-point operator of one row with the reference's mixed boundary rule (qgosubs.F:94-127 for Del^2, :310-341 for
-// Del^4): interior points (cS + cW + cE + cN - 4 c0) * dxom2; a wall point takes bcf * (inner neighbour - itself), the
-// inner neighbour being N on the S wall row, S on the N wall row, E on the W wall column, W on the E wall column (rows
-// first: the corners follow the row rule, as the i2 / i4 offsets of k_tend_body.inc).  gj: row of c0 - the same in every
-// lane, but held in a VGPR (TrRules.vz): on a scalar row number the compiler branches around each rule, and the web of
-// blocks that makes of the unrolled cascade ends in scratch; on a vector one both rules are evaluated and selected, as
-// k_tend_body.inc does.
+// Five-point operator of one row with the reference's mixed boundary rule (qg_ref_expr.h: interior sum, wall rule and
+// which neighbour is the inner one; the corners follow the row rule, as the i2 / i4 offsets of k_tend_body.inc).  gj: row
+// of c0 - the same in every lane, but held in a VGPR (TrRules.vz): on a scalar row number the compiler branches around
+// each rule, and the web of blocks that makes of the unrolled cascade ends in scratch; on a vector one both rules are
+// evaluated and selected, as k_tend_body.inc does.
 __device__ __forceinline__ double tr_lap(const TrRules &R, double cS, double c0, double cN, int gj) {
   const double cW = TR_WEST(c0), cE = TR_EAST(c0);
-  const double vi = (cS + cW + cE + cN - 4.0 * c0) * R.dxom2;
+  const double vi = qg_five_point(cS, cW, cE, cN, c0) * R.dxom2;
   const bool wS = gj == 1, wN = gj == R.nyg;
   double in = cW; // (a flat chain of selects, the last one wins: rows before columns, S before N)
   in = R.isW ? cE : in;
   in = wN ? cS : in;
   in = wS ? cN : in;
-  const double vw = R.bcf * (in - c0);
+  const double vw = qg_wall_rule(R.bcf, in, c0);
   const bool wall = wS | wN | R.isW | R.isE;
   return wall ? vw : vi;
 }
@@ -209,13 +207,10 @@ __global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(con
         const double qS = qr[t], qC = qr[t + 1], qN = qr[t + 2];
         const double pSw = TR_WEST(pS), pSe = TR_EAST(pS), pCw = TR_WEST(pC), pCe = TR_EAST(pC), pNw = TR_WEST(pN), pNe = TR_EAST(pN);
         const double qSw = TR_WEST(qS), qSe = TR_EAST(qS), qCw = TR_WEST(qC), qCe = TR_EAST(qC), qNw = TR_WEST(qN), qNe = TR_EAST(qN);
-        const double d6p = dxom2 * (d4A + d4w + d4e + d4C - 4.0 * d4B);
+        const double d6p = dxom2 * qg_five_point(d4A, d4w, d4e, d4C, d4B);
         const double diffus = P.ah2fac[k] * d4B - P.ah4fac[k] * d6p;
-        double jac = (qCe - qCw) * (pN - pS) + (qS - qN) * (pCe - pCw) +
-                     qCe * (pNe - pSe) - qCw * (pNw - pSw) -
-                     qN * (pNe - pNw) + qS * (pSe - pSw);
-        jac = jac + pN * (qNe - qNw) - pS * (qSe - qSw) -
-              pCe * (qNe - qSe) + pCw * (qNw - qSw);
+        double jac = qg_jac_head(qS, qCw, qCe, qN, pS, pCw, pCe, pN, pSw, pSe, pNw, pNe);
+        jac = qg_jac_tail(jac, pS, pCw, pCe, pN, qSw, qSe, qNw, qNe);
         const double val = P.adfaco * jac + diffus;
         dq[k][t] = cint ? val : 0.0; // dqdt = 0 on the wall columns (qgosubs.F:371,397)
         if (k == NL - 1) d2bot[t] = d2[t + 2];
@@ -285,25 +280,5 @@ __global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(con
   dst64_front<M>(twid, sintab, reg, reg + N, has_b, F, W64, lane);
   dst64_back<M>(F, W64, lane, rsa, rsb);
   const double *raw = reg;
-  constexpr int NP = N + N / 16;
-  {
-    constexpr int NU = (N / 2 + 63) / 64;
-    double2 oa[NU], ob[NU];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const int t = lane + 64 * u;
-      const int tc = t < N / 2 ? t : N / 2 - 1;
-      const int i = 2 * tc + ((2 * tc) >> 4);
-      oa[u] = double2{raw[i], raw[i + 1]};
-      ob[u] = double2{raw[NP + i], raw[NP + i + 1]};
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const int t = lane + 64 * u;
-      if (t < N / 2) { // (write-through: qgcm_dev.h)
-        qg_store16_wt(rowa + 2 * t, oa[u].x, oa[u].y);
-        if (has_b) qg_store16_wt(rowb + 2 * t, ob[u].x, ob[u].y);
-      }
-    }
-  }
+#include "k_dst64_store.inc"
 }
