@@ -38,8 +38,8 @@ def entoc_field(cfg):
 
 def setup(cfgname, mixed_layer):
     """A model with an eddy state, wind, a non-zero entrainment and (with or without the mixed layer) the fields the
-    monitors read; returns (model, fields the state does not carry)."""
-    cfg = preset(cfgname)
+    monitors read; returns (model, fields the state does not carry).  cfgname: a preset's name or a configuration."""
+    cfg = preset(cfgname) if isinstance(cfgname, str) else cfgname
     om = oml_preset(cfg, sb_hflux=mixed_layer, nb_hflux=mixed_layer)
     m = OceanModel(cfg)
     po = synth.gaussian_eddy(cfg, noise=1e-3)

@@ -65,7 +65,7 @@ def test_golden_time_means(case, mixed_layer):
 
 # 2. the running mean of po across steps ------------------------------------------------------------------------------
 def ocean(cfgname, mixed_layer):
-    cfg = preset(cfgname)
+    cfg = preset(cfgname) if isinstance(cfgname, str) else cfgname  # a preset's name or a configuration
     om = oml_preset(cfg, sb_hflux=mixed_layer, nb_hflux=mixed_layer)
     m = OceanModel(cfg)
     po = synth.gaussian_eddy(cfg, noise=1e-3)
