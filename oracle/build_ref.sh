@@ -18,14 +18,15 @@
 #    the reference (src/lasubs.f INCLUDEs an absent lapack/ dir); the
 #    image's MKL (/opt/conda/lib/libmkl_rt.so) provides it.
 #
-# usage: build_ref.sh <cfg> <nxta> <nyta> <nxaooc|nxta> <nyaooc> <ndxr> <nlo> <fnot> <beta> <cyclic 0|1> [extra cpp options] [coupled 0|1]
+# usage: build_ref.sh <cfg> <nxta> <nyta> <nxaooc|nxta> <nyaooc> <ndxr> <nlo> <fnot> <beta> <cyclic 0|1> [extra cpp options] [coupled 0|1] [nla]
 #   extra cpp options: e.g. -Dsb_hflux (mixed-layer boundary variants, src/omlsubs.F:405-422,437-454);
 #   the cyclic builds carry -Dnb_hflux as examples/southern_ocean_ocean_only does
 #   coupled = 1: a coupled build (no -Docean_only, as examples/double_gyre_coupled/make.config.coupled):
 #   adds the atmosphere path qgasubs.F / atisubs.F / atqzbd and oracle/ref/qgcm_ref_atmos.F90
+#   nla: atmospheric layers (default 3; a compile-time PARAMETER like nlo, src/parameters_data.F:41-63)
 set -euo pipefail
 
-CFG=$1; NXTA=$2; NYTA=$3; NXAOOC=$4; NYAOOC=$5; NDXR=$6; NLO=$7; FNOT=$8; BETA=$9; CYC=${10}; EXTRA=${11:-}; CPL=${12:-0}
+CFG=$1; NXTA=$2; NYTA=$3; NXAOOC=$4; NYAOOC=$5; NDXR=$6; NLO=$7; FNOT=$8; BETA=$9; CYC=${10}; EXTRA=${11:-}; CPL=${12:-0}; NLA=${13:-3}
 
 REF=${QGCM_REFERENCE:-/root/reference}
 SRC=$REF/src
@@ -45,7 +46,7 @@ cd "$WRK"
 
 # per-config dimension module: the example file with its three active
 # PARAMETER lines (grid, ocean, rotation) rewritten
-sed -e "s|^      PARAMETER ( nxta = .*|      PARAMETER ( nxta = $NXTA, nyta = $NYTA, nla = 3 )|" \
+sed -e "s|^      PARAMETER ( nxta = .*|      PARAMETER ( nxta = $NXTA, nyta = $NYTA, nla = $NLA )|" \
     -e "s|^      PARAMETER ( nxaooc = .*|      PARAMETER ( nxaooc = $NXAOOC, nyaooc = $NYAOOC, ndxr = $NDXR, nlo = $NLO )|" \
     -e "s|^      PARAMETER ( fnot = .*|      PARAMETER ( fnot = $FNOT, beta = $BETA )|" \
     "$REF/examples/double_gyre_ocean_only/parameters_data.F.dg_oo" > parameters_data.F

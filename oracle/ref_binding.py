@@ -17,7 +17,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REFDIR = os.path.join(HERE, "_ref")
 
-# name -> (nxta, nyta, nxaooc, nyaooc, ndxr, nlo, fnot, beta, cyclic)
+# name -> (nxta, nyta, nxaooc, nyaooc, ndxr, nlo, fnot, beta, cyclic[, cpp options[, coupled[, nla]]])
 # box_natl5 / cyc_socn5 are exactly examples/double_gyre_ocean_only/parameters_data.F.dg_oo
 # and examples/southern_ocean_ocean_only/parameters_data.F.so_oo.
 CONFIGS = {
@@ -58,6 +58,11 @@ CONFIGS = {
     "cpl_tiny": (16, 12, 4, 3, 12, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux", 1),
     "cpl_small": (32, 20, 6, 5, 16, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux", 1),
     "cpl_natl5": (384, 96, 60, 60, 16, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux", 1),
+    # cpl_tiny with two, four and five atmospheric layers over the unchanged three-layer ocean (nla is a compile-time
+    # PARAMETER like nlo): one more entry, the layer count, which build_ref.sh takes as its last argument
+    "cpl_tiny_a2": (16, 12, 4, 3, 12, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux", 1, 2),
+    "cpl_tiny_a4": (16, 12, 4, 3, 12, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux", 1, 4),
+    "cpl_tiny_a5": (16, 12, 4, 3, 12, 3, "9.37456D-05", "1.75360D-11", 0, "-Dsb_hflux", 1, 5),
 }
 
 

@@ -4,7 +4,7 @@ Mirrors what the reference takes from MODULE parameters (compile-time,
 src/parameters_data.F:23-147) and from input.params (run-time, order fixed by
 src/in_param.f:31-142); only the entries the ocean hot path reads are kept.
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Tuple
 
 import numpy as np
@@ -287,13 +287,38 @@ PRESETS["cpl_small"] = OceanConfig("cpl_small", 32, 20, 6, 5, 16, 3, dxo=5.0e3, 
 PRESETS["cpl_natl5"] = OceanConfig("cpl_natl5", 384, 96, 60, 60, 16, 3, dxo=5.0e3, **_NATL)
 
 
+# cpl_tiny with two, four and five atmospheric layers (oracle/ref_binding.CONFIGS "cpl_tiny_a<nla>"): the same ocean
+for _n in (2, 4, 5):
+    PRESETS["cpl_tiny_a%d" % _n] = PRESETS["cpl_tiny"]
+
+# atmospheres with other layer counts than the examples' three: nla -> (hat, gpat, factors on ah4at).  Layer
+# thicknesses sum to 9000 m as the examples' do; the factors give every layer a Del-6th coefficient of its own, no two
+# neighbours alike.  On cpl_tiny's atmosphere (dxa = 1.2e5, dta = 360; rows of 16, 192 and 384 points) the CPU oracle
+# runs 230 steps of synth.atmos_fields with each of them and max|pa| grows by less than 1.9 times.
+ATMOS_LAYERS = {
+    2: ((3000.0, 6000.0), (1.0,), (1.2, 0.8)),
+    4: ((1500.0, 2000.0, 2500.0, 3000.0), (1.2, 0.6, 0.3), (0.8, 1.1, 1.2, 0.9)),
+    5: ((1000.0, 1500.0, 2000.0, 2000.0, 2500.0), (1.2, 0.7, 0.4, 0.25), (1.2, 0.8, 1.1, 0.9, 1.0)),
+    8: ((800.0, 900.0, 1000.0, 1100.0, 1200.0, 1300.0, 1300.0, 1400.0), (1.2, 0.9, 0.7, 0.55, 0.4, 0.3, 0.2),
+        (0.8, 1.15, 0.9, 1.2, 0.85, 1.05, 0.95, 1.1)),
+}
+
+
 def preset(name):
     return PRESETS[name]
 
 
-def atmos_preset(name):
+def atmos_preset(name, nla=3):
     """Atmosphere of the coupled preset `name`; Del-6th coefficient scaled from the 80 km grid of
-    examples/double_gyre_coupled (ah4at = 1.5e14) to the grid spacing (same grid-scale damping rate per second)."""
+    examples/double_gyre_coupled (ah4at = 1.5e14) to the grid spacing (same grid-scale damping rate per second).
+    nla != 3 (or a name ending in _a<nla>): the layers of ATMOS_LAYERS, ah4at different in every layer."""
+    base, _, tail = name.rpartition("_a")
+    if base and tail.isdigit():
+        name, nla = base, int(tail)
     oc = PRESETS[name]
     r = oc.ndxr * oc.dxo / 8.0e4
-    return atmos_of(oc, ah4at=(1.5e14 * r ** 4,) * 3)
+    if nla == 3:
+        return atmos_of(oc, ah4at=(1.5e14 * r ** 4,) * 3)
+    hat, gpat, fac = ATMOS_LAYERS[nla]
+    at = atmos_of(oc, nla=nla, hat=hat, gpat=gpat, ah4at=tuple(1.5e14 * r ** 4 * x for x in fac))
+    return replace(at, name="%s_a%d" % (at.name, nla))

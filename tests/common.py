@@ -237,8 +237,15 @@ def oml_seam_columns(nxto, cyclic):
 
 
 # ---- atmosphere fixtures (tests/golden/make_golden_atmos.py), SURVEY 8 row f3 ------------------------------
-ATM_CASES = (("atm_tiny", "cpl_tiny"), ("atm_small", "cpl_small"), ("atm_natl5", "cpl_natl5"))
-ATM_SNAPS = {"atm_tiny": (1, 2, 100, 101, 130), "atm_small": (1, 40), "atm_natl5": (1, 6, 101)}
+# atm_tiny_a<n>: cpl_tiny's atmosphere with n = 2, 4, 5 layers and a different ah4at in every layer (reference builds
+# cpl_tiny_a<n>; config.atmos_preset reads the layer count from the name)
+ATM_CASES = (("atm_tiny", "cpl_tiny"), ("atm_small", "cpl_small"), ("atm_natl5", "cpl_natl5"),
+             ("atm_tiny_a2", "cpl_tiny_a2"), ("atm_tiny_a4", "cpl_tiny_a4"), ("atm_tiny_a5", "cpl_tiny_a5"))
+ATM_SNAPS = {"atm_tiny": (1, 2, 100, 101, 130), "atm_small": (1, 40), "atm_natl5": (1, 6, 101),
+             "atm_tiny_a2": (1, 2, 100, 101, 130), "atm_tiny_a4": (1, 2, 100, 101, 130),
+             "atm_tiny_a5": (1, 2, 100, 101, 130)}
+ATM_LAYER_CASES = ("atm_tiny_a2", "atm_tiny_a4", "atm_tiny_a5")
+CPL_CASES = ("cpl_tiny", "cpl_tiny_a4")  # coupled main loop fixtures (make_golden_atmos.py coupled)
 ATM_FIELDS = ("pa", "pam", "qa", "qam")
 
 
@@ -260,6 +267,35 @@ def atm_inputs(g, acfg):
 def make_atm_oracle(acfg, g, f):
     return ob.AtmosOracle(acfg.nxpa, acfg.nypa, acfg.nla, acfg.fnot, acfg.beta, acfg.dxa, acfg.dta, acfg.bccoat,
                           acfg.ah4at, acfg.hat, acfg.gpat, g["c_yparel"], f["ddynat"])
+
+
+def atm_wide(nxta, nla):
+    """cpl_tiny's atmosphere (dxa, dta, nyta = 12) with nla layers on rows of nxta points: 192 and 384 take the
+    wave-per-row-pair kernels.  No reference build exists at these shapes: the CPU oracle is the yardstick."""
+    import dataclasses
+    at = config.atmos_preset("cpl_tiny", nla)
+    return dataclasses.replace(at, nxta=nxta, name="%s_w%d" % (at.name, nxta + 1))
+
+
+def make_atm_oracle_of(acfg, f):
+    """AtmosOracle with the configuration's own yparel (no fixture)."""
+    return ob.AtmosOracle(acfg.nxpa, acfg.nypa, acfg.nla, acfg.fnot, acfg.beta, acfg.dxa, acfg.dta, acfg.bccoat,
+                          acfg.ah4at, acfg.hat, acfg.gpat, acfg.yporel(), f["ddynat"])
+
+
+def atm_mode_errs(name, ctl2m, ctm2l, g):
+    """relerr of the mode matrices ctl2m[k, m], ctm2l[m, k] against the reference's.  The reference's atmospheric
+    eigenvectors keep the sign LAPACK's Schur vectors happen to have (eigmode.f:283-296; no rule restates it), and no
+    result depends on it as long as both matrices carry the same one (cm2l * cl2m = 1).  For the three-layer fixtures
+    "positive in layer 1" reproduces it and the comparison is as it always was; with four and five layers some modes
+    come out negated, so for ATM_LAYER_CASES each mode is compared under the sign that its layer-1 component has in
+    the reference's ctl2m - one sign per mode, applied to its column of ctl2m and its row of ctm2l alike."""
+    rl, rm = g["c_ctl2mat"], g["c_ctm2lat"]
+    if name in ATM_LAYER_CASES:
+        sg = np.sign(rl[0, :]) * np.sign(np.asarray(ctl2m)[0, :])
+        assert np.all(np.abs(sg) == 1.0)
+        ctl2m, ctm2l = np.asarray(ctl2m) * sg[None, :], np.asarray(ctm2l) * sg[:, None]
+    return relerr(ctl2m, rl), relerr(ctm2l, rm)
 
 
 def atm_apply(model, f):

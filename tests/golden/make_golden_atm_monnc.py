@@ -13,7 +13,7 @@ prints its extrema only when they fail, so the driver takes the twelve extrema w
 reference's solnok with them, for the inputs and for the inputs with ast = 95 at one point.  All reference sources,
 objects and .mod files stay in the temporary directory, which is deleted.
 
-  python tests/golden/make_golden_atm_monnc.py           # the golden files (build machine only)
+  python tests/golden/make_golden_atm_monnc.py [case ...] # the golden files, or the named ones (build machine only)
   python tests/golden/make_golden_atm_monnc.py time [N]  # time the host atmosphere half at 385 x 97 x 3 on N threads
 """
 import os
@@ -94,14 +94,14 @@ end program atmon_driver
 """
 
 
-def build(wrk, dims):
+def build(wrk, dims, nla=3):
     nxta, nyta, nxaooc, nyaooc, ndxr, nlo, fnot, beta = dims
     src = os.path.join(REF, "src")
     with open(os.path.join(REF, "examples", "double_gyre_ocean_only", "parameters_data.F.dg_oo")) as f:
         lines = f.read().split("\n")
     for i, ln in enumerate(lines):
         if ln.startswith("      PARAMETER ( nxta = "):
-            lines[i] = "      PARAMETER ( nxta = %s, nyta = %s, nla = 3 )" % (nxta, nyta)
+            lines[i] = "      PARAMETER ( nxta = %s, nyta = %s, nla = %d )" % (nxta, nyta, nla)
         elif ln.startswith("      PARAMETER ( nxaooc = "):
             lines[i] = "      PARAMETER ( nxaooc = %s, nyaooc = %s, ndxr = %s, nlo = %s )" % (nxaooc, nyaooc, ndxr, nlo)
         elif ln.startswith("      PARAMETER ( fnot = "):
@@ -154,14 +154,18 @@ if __name__ == "__main__":
     import ref_binding
     from qgcm_hip import atmos_preset, preset, synth
     timing = len(sys.argv) > 1 and sys.argv[1] == "time"
+    # (cpl_tiny_a4: four layers, so that the layer loops run over more than two interfaces)
     cases = [("cpl_natl5", None, None)] if timing else [("cpl_tiny", "atm_tiny", "steps130"),
-                                                       ("cpl_small", "atm_small", "steps40")]
+                                                       ("cpl_small", "atm_small", "steps40"),
+                                                       ("cpl_tiny_a4", "atm_tiny_a4", "steps130")]
+    if not timing and len(sys.argv) > 1:  # only the named cases
+        cases = [c for c in cases if c[0] in sys.argv[1:]]
     for name, fixture, step in cases:
         a = ref_binding.CONFIGS[name]
         acfg, ocfg = atmos_preset(name), preset(name)
         wrk = tempfile.mkdtemp(prefix="atmonnc_")
         try:
-            build(wrk, a[:8])
+            build(wrk, a[:8], acfg.nla)
             if timing:
                 s = synth.atmos_fields(acfg)
                 g = dict(x_pa=s["pa"], x_pam=s["pam"], x_qa=1e-6 * s["pa"], in_wekpa=s["wekpa"], in_entat=s["entat"])
@@ -173,7 +177,7 @@ if __name__ == "__main__":
                                  "%.3f ms per call\n" % (acfg.nxpa, acfg.nypa, acfg.nla, nth, 1e3 * t))
                 continue
             g = np.load(os.path.join(HERE, fixture + ".npz"))
-            f, c = inputs(acfg, ocfg, g, step, 7 if fixture == "atm_tiny" else 8)
+            f, c = inputs(acfg, ocfg, g, step, {"atm_tiny": 7, "atm_small": 8, "atm_tiny_a4": 9}[fixture])
             vec, val, ok, _, _ = run(wrk, f, c)
             out = {"in_" + k: np.asarray(v) for k, v in f.items()}
             out.update({"c_" + k: np.asarray(v) for k, v in c.items()})

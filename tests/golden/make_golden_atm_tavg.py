@@ -13,7 +13,8 @@ tavout, and writes the scaled sums; tavout's eddy fluxes uptpat / vptpat are loc
 here from the reference's scaled arrays with tavout's own expression.  Then atnc_init / atnc_out for nska = 1, 2, 5 on
 the last state.  All reference sources, objects and .mod files stay in the temporary directory, which is deleted.
 
-  python tests/golden/make_golden_atm_tavg.py           # writes tests/golden/atav_cpl_{tiny,small}.npz
+  python tests/golden/make_golden_atm_tavg.py           # writes tests/golden/atav_cpl_{tiny,small,tiny_a4}.npz
+  python tests/golden/make_golden_atm_tavg.py cpl_tiny_a4  # only the named cases
   python tests/golden/make_golden_atm_tavg.py time [N]  # the reference's tavatm at 385 x 97 x 3 on N (16) threads
 """
 import os
@@ -38,7 +39,8 @@ SUMS = ("txatav", "tyatav", "wtatav", "fmatav", "astav", "patav", "qatav", "uufa
         "vtvfa")
 # (golden file, fixture, the three stepped states tavatm reads)
 CASES = [("cpl_tiny", "atm_tiny", ("steps100", "steps101", "steps130")),
-         ("cpl_small", "atm_small", ("steps1", "atqzbd", "steps40"))]
+         ("cpl_small", "atm_small", ("steps1", "atqzbd", "steps40")),
+         ("cpl_tiny_a4", "atm_tiny_a4", ("steps100", "steps101", "steps130"))]
 
 DRIVER = r"""
 program atav_driver
@@ -96,7 +98,7 @@ end program atav_driver
 """
 
 
-def build(wrk, dims, timing=False):
+def build(wrk, dims, timing=False, nla=3):
     from make_golden_qocdiag import NETCDF_INC, NETCDF_STUBS
     nxta, nyta, nxaooc, nyaooc, ndxr, nlo, fnot, beta = dims
     src = os.path.join(REF, "src")
@@ -104,7 +106,7 @@ def build(wrk, dims, timing=False):
         lines = f.read().split("\n")
     for i, ln in enumerate(lines):
         if ln.startswith("      PARAMETER ( nxta = "):
-            lines[i] = "      PARAMETER ( nxta = %s, nyta = %s, nla = 3 )" % (nxta, nyta)
+            lines[i] = "      PARAMETER ( nxta = %s, nyta = %s, nla = %d )" % (nxta, nyta, nla)
         elif ln.startswith("      PARAMETER ( nxaooc = "):
             lines[i] = "      PARAMETER ( nxaooc = %s, nyaooc = %s, ndxr = %s, nlo = %s )" % (nxaooc, nyaooc, ndxr, nlo)
         elif ln.startswith("      PARAMETER ( fnot = "):
@@ -220,13 +222,13 @@ if __name__ == "__main__":
     import ref_binding
     from qgcm_hip import atmos_preset
     hmat = 1000.0  # examples/double_gyre_coupled's input.params
-    for name, fixture, states in CASES:
+    for name, fixture, states in [c for c in CASES if len(sys.argv) == 1 or c[0] in sys.argv[1:]]:
         acfg = atmos_preset(name)
         g = np.load(os.path.join(HERE, fixture + ".npz"))
         calls = [dict(forcing(acfg, 21 + n), pa=g[st + "_pa"], qa=g[st + "_qa"]) for n, st in enumerate(states)]
         wrk = tempfile.mkdtemp(prefix="atav_")
         try:
-            build(wrk, ref_binding.CONFIGS[name][:8])
+            build(wrk, ref_binding.CONFIGS[name][:8], nla=acfg.nla)
             res = unpack(run(wrk, acfg, hmat, calls), acfg)
             rec = dumps(wrk, acfg.nla)
         finally:

@@ -125,7 +125,11 @@ def aml(S, fnetat, wekta, uekat, vekat, pa, pam, xc1ast, dtopat, P):
     diabcr = tat1 - 2.0 * hdrcdt
     entfac = 1.0 / (tdta * (P["tat2"] - tat1))
     xbfac = xcexp * P["bface"]
-    afacdp = (P["aface1"] / P["gpat1"], P["aface2"] / P["gpat2"])
+    # aface(l) / gpat(l) over the nla - 1 interfaces (src/amlsubs.F:88-90); the fixtures carry the two of three layers
+    aface, gpat = P.get("aface", (P["aface1"], P["aface2"])), P.get("gpat", (P["gpat1"], P["gpat2"]))
+    nla = pam.shape[2]
+    assert len(aface) >= nla - 1 and len(gpat) >= nla - 1
+    afacdp = [aface[l] / gpat[l] for l in range(nla - 1)]
     tmrhs, hmrhs = amladf(ast, astm, hmixa, hmixam, uekat, vekat, pa[:, :, 0], P)
     cold = astm <= diabcr
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -153,8 +157,9 @@ def aml(S, fnetat, wekta, uekat, vekat, pa, pam, xc1ast, dtopat, P):
     ent[:-1, 0] = 0.5 * (Wx[:, 0] + xfa[:, 0])
     ent[:-1, -1] = 0.5 * (Wx[:, -1] + xfa[:, -1])
     ent[-1, :] = ent[0, :]
-    adpsum = 0.0 + afacdp[0] * (pam[:, :, 0] - pam[:, :, 1])
-    adpsum = adpsum + afacdp[1] * (pam[:, :, 1] - pam[:, :, 2])
+    adpsum = 0.0
+    for l in range(nla - 1):  # src/amlsubs.F:203-209
+        adpsum = adpsum + afacdp[l] * (pam[:, :, l] - pam[:, :, l + 1])
     ent = ent + adpsum + P["cface"] * dtopat
     xi, axi = xintp(ent)
     ens, aens = _serial(list(ent[1:-1, 0]), 0.5 * ent[0, 0])

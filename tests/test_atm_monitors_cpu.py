@@ -19,7 +19,7 @@ NEW = ["qgcm_hip_set_atm_mon_params", "qgcm_hip_set_atm_monitor_fields", "qgcm_h
 # bitwise against the reference: extrema, Courant numbers, jet position and value, tmaooc
 EXACT = ("astmin", "astmax", "tmaooc", "umminat", "ummaxat", "vmminat", "vmmaxat", "cnmlat", "ugminat", "ugmaxat",
          "vgminat", "vgmaxat", "cnqgat", "atstpos", "atstval")
-GOLDEN = ["cpl_tiny", "cpl_small"]
+GOLDEN = ["cpl_tiny", "cpl_small", "cpl_tiny_a4"]  # (the last: four layers, ah4at different in each)
 
 
 def golden_case(name):

@@ -16,7 +16,7 @@ from qgcm_hip import lib, model
 
 NEW = ["qgcm_hip_set_atm_tav_fields", "qgcm_hip_tavatm", "qgcm_hip_atm_tav_reset", "qgcm_hip_atm_tav_out",
        "qgcm_hip_tavatm_schedule", "qgcm_hip_atnc_sample_len", "qgcm_hip_atnc_sample"]
-GOLDEN = ["cpl_tiny", "cpl_small"]
+GOLDEN = ["cpl_tiny", "cpl_small", "cpl_tiny_a4"]  # (the last: four layers, ah4at different in each)
 NSKA = (1, 2, 5)
 
 

@@ -62,7 +62,7 @@ def restated(m, fl, c):
     return na.monitors(dict(fl, pa=pa, pam=pam, qa=qa), c)
 
 
-@pytest.mark.parametrize("name", ["cpl_tiny", "cpl_small"])
+@pytest.mark.parametrize("name", ["cpl_tiny", "cpl_small", "cpl_tiny_a4"])
 def test_against_the_reference(name):
     f, c, want, val, ok = golden_case(name)
     _, scales = na.monitors(f, c)

@@ -45,7 +45,7 @@ def restated_sum(S, m, fl, c):
     return na.tavatm(S, dict(fl, pa=pa, qa=qa), c)
 
 
-@pytest.mark.parametrize("name", ["cpl_tiny", "cpl_small"])
+@pytest.mark.parametrize("name", ["cpl_tiny", "cpl_small", "cpl_tiny_a4"])
 def test_against_the_reference(name):
     g, c, calls, last = golden_case(name)
     acfg = atmos_preset(name)

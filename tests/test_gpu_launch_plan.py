@@ -11,7 +11,7 @@ that closes each profiled step, k_noop_train the 512 empty launches of the calib
 import pytest
 import torch  # noqa: F401  (before the library: torch brings its own HIP runtime, see qgcm_hip/slab.py)
 
-from common import atm_apply
+from common import atm_apply, atm_wide
 from qgcm_hip import AtmosModel, config, synth
 from test_gpu_tavg import ocean
 
@@ -27,6 +27,8 @@ CASES = {
     "cyc_med": ("cyc_med", None, None),              # k_rfft64_unpack
     "cyc_2880": ("cyc_2880", None, None),            # k_rfft3_unpack
     "atm_cpl_tiny": ("cpl_tiny", "atmos", None),     # the smallest atmosphere the tests step
+    "atm_385_a4": ((384, 4), "atmos_wide", None),    # 385 x 13, four layers: k_rfft64_unpack with the constraint riding
+    "atm_385_a5": ((384, 5), "atmos_wide", None),    # ... five: plain inverse rows + k_constr_cyc + k_unpack_cyc
     "box_med_oml": ("box_med", "oml", None),
     "box_med_po_mean": ("box_med", "po_mean", None),
     "box_med_no_fused_constr": ("box_med", None, "QGCM_HIP_NO_FUSED_CONSTR"),
@@ -54,6 +56,12 @@ EXPECTED = {
                  "k_noop_train": 512},
     "atm_cpl_tiny": {"k_tend": 30, "k_dst_fwd": 30, "k_thomas": 30, "k_dst_inv": 30, "k_unpack": 30,
                      "k_lf_average": 1, "k_noop": 30, "k_noop_train": 512},
+    # (not recorded but required: the atmosphere's layer count must pick the launches the cyclic ocean's does - four
+    #  layers as cyc_med, five as cyc_tiny6 - with the atmosphere's single averaging at step 1)
+    "atm_385_a4": {"k_tend": 30, "k_dst_fwd": 30, "k_thomas": 30, "k_dst_inv": 30, "k_lf_average": 1, "k_noop": 30,
+                   "k_noop_train": 512},
+    "atm_385_a5": {"k_tend": 30, "k_dst_fwd": 30, "k_thomas": 30, "k_dst_inv": 30, "k_constr": 30, "k_unpack": 30,
+                   "k_lf_average": 1, "k_noop": 30, "k_noop_train": 512},
     "box_med_oml": {"k_tend": 30, "k_dst_fwd": 30, "k_thomas": 30, "k_dst_inv": 30, "k_lf_average": 2,
                     "k_oml": 30, "k_oml_entoc": 30, "k_noop": 30, "k_noop_train": 512},
     "box_med_po_mean": {"k_tend": 30, "k_dst_fwd": 30, "k_thomas": 30, "k_dst_inv": 30, "k_lf_average": 2,
@@ -76,8 +84,8 @@ EXPECTED = {
 def launches(case):
     """{kernel class: launches} of steps 1 .. 30 of a fresh model of `case` (classes that never launch left out)."""
     name, variant, _ = CASES[case]
-    if variant == "atmos":
-        acfg = config.atmos_preset(name)
+    if variant in ("atmos", "atmos_wide"):
+        acfg = config.atmos_preset(name) if variant == "atmos" else atm_wide(*name)
         f = synth.atmos_fields(acfg)
         m = AtmosModel(acfg, ddynat=f["ddynat"])
         atm_apply(m, f)
