@@ -13,7 +13,9 @@
 //     one after the other (the loads of layer k+1 are requested before layer k is computed), keeps dqdt of all layers in
 //     registers and finishes with the point-wise part (forcing, drag, leapfrog, projection) - the five-point sum, the
 //     wall rule and the Jacobian are qg_ref_expr.h's, the point-wise expressions tend_point's, contraction off.  The new qo
-//     leaves in 16-byte write-through pairs; the modal right-hand side fnot * qmm goes to LDS, one row per (row, mode);
+//     leaves in 16-byte write-through pairs; the modal right-hand side fnot * qmm goes to LDS, one row per (row, mode).
+//     A strip out of reach of every wall - all but 2 of 240 bands, all but 2 of 18 strips at NAtl 5 km - takes a body
+//     without the wall rule, the clamps and the wall-column masks (k_tend_rows_strip.inc, one text included twice);
 //   * ONE workgroup barrier;
 //   * phase 2 (forward rows): B/2 x NL of the waves run dst64_front / dst64_back (k_dst64.h, unchanged) on one (row
 //     pair, mode) each, reading the rows from LDS, and store the spectral rows to wrk as k_dst64 does.  The transform
@@ -70,6 +72,22 @@ __device__ __forceinline__ double tr_lap(const TrRules &R, double cS, double c0,
   const bool wall = wS | wN | R.isW | R.isE;
   return wall ? vw : vi;
 }
+// the same operator where no wall is in reach: tr_lap's `vi`, which its last select returns there
+__device__ __forceinline__ double tr_lap_interior(double dxom2, double cS, double c0, double cN) {
+  const double cW = TR_WEST(c0), cE = TR_EAST(c0);
+  return qg_five_point(cS, cW, cE, cN, c0) * dxom2;
+}
+
+// The kernel's arguments as the kernarg segment lays them out: where the by-value P lies in it.  A strip reads P's
+// scalars and pointers from there (scalar loads, under its own arithmetic) instead of holding them in SGPRs from the
+// kernel's head on: held, they and the band's row offsets are ~200 SGPRs the compiler spills to VGPR lanes before the first
+// load is requested and moves back lane by lane inside every strip.
+struct TrKernArgs {
+  const double *pom; const double2 *twid; const double *sintab;
+  int nx, ny, ldx, side;
+  QgTendParams P;
+};
+typedef const __attribute__((address_space(4))) QgTendParams *TrParamPtr;
 
 #define TR_WAVES_PER_EU 3 // the transform waves need ~146 VGPRs (k_dst64): three waves per SIMD
 // rows per band.  Measured at NAtl 5 km: 2 (two six-wave workgroups per CU): 71.9 us per step, 4 (one
@@ -124,145 +142,53 @@ __global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(con
   R.nyg = ny; R.bcf = P.bcfaco; R.dxom2 = P.dxom2;
   asm volatile("v_mov_b32 %0, 0" : "=v"(R.vz));
   const double dxom2 = P.dxom2;
-  // row offset inside a field layer, clamped: rows outside the array are never used by a point inside
-  auto rowoff = [&](int gj) {
-    const int rj = gj < 1 ? 1 : (gj > ny ? ny : gj);
-    return (unsigned)((rj - 1) * ldx) * 8u;
-  };
 
   // ---- phase 1: the tendency of the band, strip by strip ----------------------------------------------------------
+  // Two bodies of one text (k_tend_rows_strip.inc), chosen per strip by a scalar branch.  A band is out of reach of the
+  // wall ROWS iff every row on which the cascade forms the five-point operator is an interior row: the widest level,
+  // Del^2, covers rows j0-2 .. j0+B+1 (with B = 4: band >= 1 && ny >= 4 band + 8; not "neither first nor last" - the band
+  // before a short last band reaches row ny; a partial band never is).  A strip is out of reach of the wall COLUMNS iff
+  // no lane of it is column 1 or nx.  At NAtl 5 km 2 of 240 bands and 2 of 18 strips take the body with the wall rule.
+  const bool band_free = j0 - 2 >= 2 && j0 + B + 1 <= ny - 1;
   const int nstrips = (nx + TR_SW - 1) / TR_SW;
-#pragma unroll 1
-  for (int strip = wv; strip < nstrips; strip += NW) {
-    const int i0 = strip * TR_SW + 1;          // first column the strip owns (odd)
-    const int gi = i0 - TR_HL + lane;          // this lane's column
-    const int gc = gi < 1 ? 1 : (gi > nx ? nx : gi); // clamped: lanes outside the basin load finite values no point inside reads
-    const unsigned lcol = (unsigned)(gc - 1) * 8u;
-    const bool own = lane >= TR_HL && lane < TR_HL + TR_SW && gi <= nx; // (gi >= 1 then)
-    const bool cint = gi >= 2 && gi <= nx - 1;
-    R.isW = gi == 1;
-    R.isE = gi == nx;
-
-    double w[B + 6], pr[B + 2], qr[B + 2]; // pom rows j0-3 .. j0+B+2, po / qo rows j0-1 .. j0+B of the layer in flight
-#pragma unroll
-    for (int r = 0; r < B + 6; ++r) w[r] = tr_ld(pom, rowoff(j0 - 3 + r) + lcol);
-#pragma unroll
-    for (int r = 0; r < B + 2; ++r) {
-      pr[r] = tr_ld(po0, rowoff(j0 - 1 + r) + lcol);
-      qr[r] = tr_ld(qo0, rowoff(j0 - 1 + r) + lcol);
-    }
-    double dq[NL][B], d2bot[B];
-    double e_qm[NL][B], e_wek[B], e_ent[ENT ? B : 1], e_ddy[DDY ? B : 1];
-    // (TR_FENCE: a scheduling fence.  Left to itself the compiler requests the rows of all layers at once and forms every
-    //  DPP shift of the Jacobian before the first product: 600 bytes of scratch per lane.  Between the fences the order is
-    //  the one written here: the pom rows of layer k + 1 are requested once Del^2 of layer k has consumed those of layer
-    //  k, its po / qo rows once the Jacobian has - so each request flies during the arithmetic that follows it, and a lane
-    //  never holds more than one layer's rows.  TR_PIN: the value exists HERE - pure arithmetic is otherwise sunk past
-    //  the fences to its use in the epilogue, and the DPP shifts it reads, which cannot move, stay live until then.)
+  // (TR_FENCE: a scheduling fence.  Left to itself the compiler requests the rows of all layers at once and forms every
+  //  DPP shift of the Jacobian before the first product: 600 bytes of scratch per lane.  Between the fences the order is
+  //  the one written in the strip body: the pom rows of layer k + 1 are requested once Del^2 of layer k has consumed those
+  //  of layer k, its po / qo rows once the Jacobian has - so each request flies during the arithmetic that follows it,
+  //  and a lane never holds more than one layer's rows.  TR_PIN: the value exists HERE - pure arithmetic is otherwise
+  //  sunk past the fences to its use in the epilogue, and the DPP shifts it reads, which cannot move, stay live until then.)
 #define TR_PIN(x) asm volatile("" : "+v"(x))
 #define TR_FENCE()                       \
   do {                                   \
     asm volatile("" ::: "memory");       \
     __builtin_amdgcn_sched_barrier(0);   \
   } while (0)
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      // Del^2 of rows j0-2 .. j0+B+1
-      double d2[B + 4], d4[B + 2];
-#pragma unroll
-      for (int r = 0; r < B + 4; ++r) {
-        d2[r] = tr_lap(R, w[r], w[r + 1], w[r + 2], j0 - 2 + r + R.vz);
-        TR_PIN(d2[r]);
-      }
-      TR_FENCE();
-      if (k + 1 < NL) {
-        const double *pomk = pom + fs * (k + 1);
-#pragma unroll
-        for (int r = 0; r < B + 6; ++r) w[r] = tr_ld(pomk, rowoff(j0 - 3 + r) + lcol);
-      } else { // the operands of the point-wise epilogue
-#pragma unroll
-        for (int t = 0; t < B; ++t) {
-          const unsigned o = rowoff(j0 + t) + lcol;
-          e_wek[t] = tr_ld(P.wekpo, o);
-          if (ENT) e_ent[ENT ? t : 0] = tr_ld(P.entoc, o);
-          if (DDY) e_ddy[DDY ? t : 0] = tr_ld(P.ddynoc, o);
-#pragma unroll
-          for (int kk = 0; kk < NL; ++kk) e_qm[kk][t] = tr_ld(P.qnew + fs * kk, o);
-        }
-      }
-      TR_FENCE();
-      // Del^4 of rows j0-1 .. j0+B
-#pragma unroll
-      for (int r = 0; r < B + 2; ++r) {
-        d4[r] = tr_lap(R, d2[r], d2[r + 1], d2[r + 2], j0 - 1 + r + R.vz);
-        TR_PIN(d4[r]);
-      }
-      TR_FENCE();
-      // Del^6 + Arakawa Jacobian (qgosubs.F:349-399); S / C / N rows gj-1 / gj / gj+1, w / e columns i-1 / i+1
-#pragma unroll
-      for (int t = 0; t < B; ++t) {
-        const double d4A = d4[t], d4B = d4[t + 1], d4C = d4[t + 2];
-        const double d4w = TR_WEST(d4B), d4e = TR_EAST(d4B);
-        const double pS = pr[t], pC = pr[t + 1], pN = pr[t + 2];
-        const double qS = qr[t], qC = qr[t + 1], qN = qr[t + 2];
-        const double pSw = TR_WEST(pS), pSe = TR_EAST(pS), pCw = TR_WEST(pC), pCe = TR_EAST(pC), pNw = TR_WEST(pN), pNe = TR_EAST(pN);
-        const double qSw = TR_WEST(qS), qSe = TR_EAST(qS), qCw = TR_WEST(qC), qCe = TR_EAST(qC), qNw = TR_WEST(qN), qNe = TR_EAST(qN);
-        const double d6p = dxom2 * qg_five_point(d4A, d4w, d4e, d4C, d4B);
-        const double diffus = P.ah2fac[k] * d4B - P.ah4fac[k] * d6p;
-        double jac = qg_jac_head(qS, qCw, qCe, qN, pS, pCw, pCe, pN, pSw, pSe, pNw, pNe);
-        jac = qg_jac_tail(jac, pS, pCw, pCe, pN, qSw, qSe, qNw, qNe);
-        const double val = P.adfaco * jac + diffus;
-        dq[k][t] = cint ? val : 0.0; // dqdt = 0 on the wall columns (qgosubs.F:371,397)
-        if (k == NL - 1) d2bot[t] = d2[t + 2];
-        TR_PIN(dq[k][t]);
-        TR_FENCE();
-      }
-      if (k + 1 < NL) {
-        const double *pok = po0 + fs * (k + 1), *qok = qo0 + fs * (k + 1);
-#pragma unroll
-        for (int r = 0; r < B + 2; ++r) {
-          pr[r] = tr_ld(pok, rowoff(j0 - 1 + r) + lcol);
-          qr[r] = tr_ld(qok, rowoff(j0 - 1 + r) + lcol);
-        }
-        TR_FENCE();
-      }
+#pragma unroll 1
+  for (int strip = wv; strip < nstrips; strip += NW) {
+    // What does not change from strip to strip is made to look as if it did (an empty asm the compiler cannot see
+    // through): the band's first row - the row offsets are then formed on the scalar unit inside the strip instead of
+    // being held, and spilled, across the loop - and the address of P in the kernarg segment (TrKernArgs above).
+    int jb = j0;
+    asm volatile("" : "+s"(jb));
+    TrParamPtr pe = (TrParamPtr)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
+                                 offsetof(TrKernArgs, P));
+    asm volatile("" : "+s"(pe));
+#define PE (*pe)
+    const int g0 = strip * TR_SW + 1 - TR_HL; // column of lane 0
+    const bool strip_free = g0 >= 2 && g0 + 63 <= nx - 1;
+    if (band_free && strip_free) {
+#define TR_WALLS 0
+#include "k_tend_rows_strip.inc"
+#undef TR_WALLS
+    } else {
+#define TR_WALLS 1
+#include "k_tend_rows_strip.inc"
+#undef TR_WALLS
     }
+#undef PE
+  }
 #undef TR_FENCE
 #undef TR_PIN
-    // ---- forcing, bottom drag, leapfrog, projection: tend_point's expressions (k_tend.h), every lane goes through ----
-#pragma unroll
-    for (int t = 0; t < B; ++t) {
-      const int gj = j0 + t;
-      if (gj > jr1) break; // (wave-uniform: the partial last band)
-      const long o = (long)(gj - 1) * ldx + (gc - 1);
-      // (a field the host knows to be all zero enters as a literal 0.0: the same expressions, the same bits)
-      const double wek = e_wek[t], ent = ENT ? e_ent[ENT ? t : 0] : 0.0, ddy = DDY ? e_ddy[DDY ? t : 0] : 0.0;
-      double qdot[NL];
-#pragma unroll
-      for (int k = 0; k < NL; ++k) qdot[k] = dq[k][t];
-      qdot[0] = dq[0][t] + P.fohfac[0] * (wek - ent);
-      qdot[1] = dq[1][t] + P.fohfac[1] * ent;
-      qdot[NL - 1] = qdot[NL - 1] - P.bdrfac * d2bot[t];
-      double ql[NL];
-      const double betay = P.beta * P.yporel[gj - 1];
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const double qn = e_qm[k][t] + P.tdto * qdot[k]; // qom + tdto*qdot
-        qg_pair_store_wt(P.qnew + fs * k + o, qn, own && gi <= nx - 1);
-        if (own && gi == nx) P.qnew[fs * k + o] = qn; // (the E wall column has no partner: the odd one out of 961)
-        ql[k] = qn - betay;
-      }
-      ql[NL - 1] = ql[NL - 1] - ddy;
-      double *dst = lds + ((t >> 1) * NL) * REG + (t & 1) * N + (gi - 2);
-#pragma unroll
-      for (int m = 0; m < NL; ++m) {
-        double qmm = 0.0;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) qmm = qmm + P.ctl2m[k + NL * m] * ql[k];
-        if (own && cint) dst[m * REG] = P.fnot * qmm;
-      }
-    }
-  }
   __syncthreads();
 
   // ---- phase 2: forward DST-I of the band's rows, a wave per (row pair, mode), as k_dst64 --------------------------
