@@ -101,11 +101,17 @@ int qgcm_hip_abi_version(void);
  * launches per inversion instead of one.  Every entry point that wants a whole-domain handle accepts such a handle;
  * run on one so far (README): qgcm_hip_steps and its graphs, the three stand-alone calls, helmholtz, oml, valids, prsamp;
  * accepted but not yet run on one: qgcm_hip_coupled_steps, xforc, the monitors, time averages, dumps and covariances.
- * A y-slab of more than 2048 rows and an atmosphere handle of more than 2048 rows are refused by this call.
- * QGCM_HIP_THOMAS_SEG_ROWS=<n> (environment, read by this call): the longest segment, 2 * QGCM_HIP_THOMAS_SEG_MIN - 1
- * <= n; columns of ANY height longer than n are then cut (n > 2048 counts as 2048) - tests force segments on small
- * basins with it.  Anything but a positive integer is refused.  Unset, columns of up to 2048 rows take the single
- * launch. */
+ * A Y-SLAB of an ocean with more than 2048 interior rows takes a plan by the same rule.  It solves its segments in two
+ * launches before the exchange of the slab summaries and one after it, and still publishes ONE summary per step and
+ * ONE set of set-up constants, in the layout and lengths of every other slab (qgcm_hip_thomas_msg_len / _const_len):
+ * the other ranks cannot tell, and ranks with different plans mix freely.  Every slab entry point drives such a handle
+ * unchanged.  A whole-domain handle in segments is a lone slab (nranks = 1) to qgcm_hip_thomas_phase and
+ * qgcm_hip_slab_steps.  An atmosphere handle of more than 2048 rows is refused by this call.
+ * QGCM_HIP_THOMAS_SEG_ROWS=<n> (environment, read by this call for WHOLE-DOMAIN handles) and
+ * QGCM_HIP_THOMAS_SLAB_SEG_ROWS=<n> (read for Y-SLABS, i.e. handles that own part of the rows): the longest segment,
+ * 2 * QGCM_HIP_THOMAS_SEG_MIN - 1 <= n; columns of ANY height longer than n are then cut (n > 2048 counts as 2048) -
+ * tests force segments on small basins with them.  Anything but a positive integer is refused.  Unset, columns of up
+ * to 2048 rows take the single launch.  Neither variable is read for the other kind of handle. */
 int qgcm_hip_set_grid(qgcm_hip_handle h, const double *yporel, const double *bd2oc,
                       const double *ddynoc);
 #define QGCM_HIP_THOMAS_MAX_ROWS 2048 /* rows of one segment = of a column solved by the single-segment kernel */
@@ -120,6 +126,10 @@ int qgcm_hip_set_grid(qgcm_hip_handle h, const double *yporel, const double *bd2
  * maximum below 2 * QGCM_HIP_THOMAS_SEG_MIN - 1 (it could leave a segment shorter than the minimum) and for more than
  * QGCM_HIP_THOMAS_MAX_SEG segments. */
 int qgcm_hip_thomas_segments(int nrows, int max_rows, int *nseg, int *first, int *count);
+/* The plan the handle actually uses (after qgcm_hip_set_grid): *nseg segments, segment s = the handle's interior rows
+ * first[s] .. first[s] + count[s] - 1 (0-based from its first interior row; QGCM_HIP_THOMAS_MAX_SEG ints each, may be
+ * NULL).  One segment of all interior rows for a handle on the single-segment kernel, the atmosphere included. */
+int qgcm_hip_thomas_plan(qgcm_hip_handle h, int *nseg, int *first, int *count);
 /* The part of set_grid that does not need bd2oc: yporel and ddynoc only.  The main program calls ocqbdy / atqzbd on
  * host arrays (src/q-gcm.F:724-725, 743-744) before it computes bd2oc (:932-972); qgcm_hip_ocqbdy_host needs no more
  * than this.  The stepping entry points still require qgcm_hip_set_grid. */

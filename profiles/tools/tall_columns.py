@@ -12,7 +12,16 @@
   python3 profiles/tools/tall_columns.py slabs          the same basin as eight y-slabs: bench.py's figure of one middle
                                                         slab stepping alone; x 8 is an EXTRAPOLATION to the eight slabs one
                                                         after the other on one GPU, without the two exchanges (the basin
-                                                        stepped as eight virtual slabs is not timed here)"""
+                                                        stepped as eight virtual slabs is not timed here)
+  python3 profiles/tools/tall_columns.py slab [P:N,.. ...] the same basin as P y-slabs (2: 2400-row slabs, in segments; 3 / 4:
+                                                        1600 / 1200 rows), ONE middle slab stepping alone as run_workload.py
+                                                        natl1_one_slab sets it up (the other ranks' summaries and halo rows
+                                                        held at the last real step), for every QGCM_HIP_THOMAS_SLAB_SEG_ROWS
+                                                        = N (0: unset): 20-step windows replayed from a graph, HIP events,
+                                                        the state restored before every replay; then HIP-event brackets
+                                                        around the launches of each Thomas phase, eager (profiles/tall_slabs.log).
+                                                        One GPU: what one rank computes per step, no exchange - not a scaling
+                                                        measurement"""
 import json
 import os
 import sys
@@ -121,6 +130,82 @@ def slabs():
     return 0
 
 
+def one_slab(groups):
+    from qgcm_hip import hostinit, preset, synth
+    from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, global_consts, partition
+    cfg = preset("natl1")
+    consts = global_consts(cfg)
+    po = synth.gaussian_eddy(cfg)
+    tx, ty = synth.wind_stress(cfg)
+    _, wek = synth.wekpo_from_tau(cfg, tx, ty)
+    qo = hostinit.q_from_p(cfg, consts["amatoc"], consts["yporel"], consts["ddynoc"], po)
+    scal = hostinit.constr(cfg, consts["amatoc"], po, po)
+    z2 = np.zeros_like(wek)
+    for nranks, n in ((p, n) for p, lengths in groups for n in lengths):
+        r = nranks // 2
+        if n:
+            os.environ["QGCM_HIP_THOMAS_SLAB_SEG_ROWS"] = str(n)  # read by qgcm_hip_set_grid
+        else:
+            os.environ.pop("QGCM_HIP_THOMAS_SLAB_SEG_ROWS", None)
+        slabs = [HipSlab(cfg, consts, g0, g1, k, nranks, sync_each_call=True) for k, (g0, g1) in enumerate(partition(cfg.nypo, nranks))]
+        try:
+            x = slabs[r]
+            plan = [c for _, c in x.thomas_plan()]
+            so = SlabOcean(cfg, slabs, LocalComm(nranks, after=torch.cuda.synchronize))
+            so.homsol()
+            so.scatter_state(po, po, qo, qo, wek, z2, np.zeros(cfg.nlo - 1), scal)
+            so.steps(4, s0=1)          # real steps of all slabs: the exchange buffers hold consistent values
+            torch.cuda.synchronize()
+            x.sync_each_call = False
+            st = torch.cuda.ExternalStream(x.stream_ptr)
+            mine = so.th_gath[r][r * x.th_len:(r + 1) * x.th_len]
+            state0, scal0 = x.get_state(), x.get_scalars()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr, stream=st):
+                for _ in range(20):    # the stages of SlabOcean.step for this slab alone (steps without an averaging)
+                    x.stage(1, so.th_send[r])
+                    mine.copy_(so.th_send[r])   # its own summary is current, the other ranks' stay at the last real step
+                    x.stage(2, so.th_gath[r], so.h_to_lo[r], so.h_to_hi[r])
+                    x.stage(3, so.h_from_lo[r], so.h_from_hi[r], None, 0)
+            e0, e1, wins = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), []
+            for rep in range(6):       # the first replay is a rehearsal
+                x.set_state(*state0)
+                x.set_scalars(scal0)
+                with torch.cuda.stream(st):
+                    e0.record()
+                    gr.replay()
+                    e1.record()
+                e1.synchronize()
+                if rep:
+                    wins.append(1e3 * e0.elapsed_time(e1) / 20)
+            # the solve alone, eager: HIP events around the launches of each phase (what the work array holds does not
+            # change what the launches do)
+            x.set_state(*state0)
+            x.set_scalars(scal0)
+            ph = {1: [], 2: []}
+            with torch.cuda.stream(st):
+                for rep in range(21):
+                    for phase in (1, 2):
+                        e0.record()
+                        x.thomas_phase(phase, so.th_gath[r] if phase == 2 else None, so.th_send[r] if phase == 1 else None)
+                        e1.record()
+                        e1.synchronize()
+                        if rep:
+                            ph[phase].append(1e3 * e0.elapsed_time(e1))
+            print("%d slabs, slab %d (rows %d..%d) alone, max segment %s -> %d segment(s) of %d..%d rows: us per step, 5 windows "
+                  "of 20 graph-replayed steps: %s  median %.1f" % (nranks, r, x.g0, x.g1, n or "unset", len(plan), min(plan), max(plan),
+                                                                  " ".join("%.1f" % w for w in wins), float(np.median(wins))), flush=True)
+            print("   eager HIP-event brackets (bracket cost included), median of 20: phase 1 (%s) %.1f us, phase 2 (%s) %.1f us" % (
+                "k_thomas_seg + k_thomas_fold" if len(plan) > 1 else "k_thomas<R, 1>", float(np.median(ph[1])),
+                "k_thomas_corr_slab" if len(plan) > 1 else "k_thomas_corr", float(np.median(ph[2]))), flush=True)
+        finally:
+            torch.cuda.synchronize()
+            torch.cuda.set_stream(torch.cuda.default_stream())
+            for sl in slabs:
+                sl.close()
+    return 0
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "check"
     if what == "check":
@@ -129,4 +214,7 @@ if __name__ == "__main__":
         sys.exit(timing([int(a) for a in sys.argv[2:]] or [2048, 1024, 640]))
     if what == "slabs":
         sys.exit(slabs())
-    sys.exit("usage: tall_columns.py check | time [N ...] | slabs")
+    if what == "slab":
+        groups = [(int(a.split(":")[0]), [int(n) for n in a.split(":")[1].split(",")]) for a in sys.argv[2:]]
+        sys.exit(one_slab(groups or [(2, [2048, 1024, 640])]))
+    sys.exit("usage: tall_columns.py check | time [N ...] | slabs | slab [P:N,N,... ...]")

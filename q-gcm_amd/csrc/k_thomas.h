@@ -135,6 +135,16 @@ struct QgThomasSegRec {
   long msg0;    // ... of its TH_MSG * (ldw, nlayers) summaries (the layout of the gathered slab messages)
   long cst0;    // ... of its TH_CST * (ldw, nlayers) constants (the layout of cgath)
 };
+// ... and of a y-slab cut into segments (k_thomas_slab.h): what folds the segments' summaries into the slab's own
+struct QgThomasFold {
+  const double *msg; // (Cf, Cb, S0) of every segment, segment-major (k_thomas_seg's output)
+  const double *cst; // (D, E, SP, SQ) of every segment, segment-major
+  double *coef;      // (3, S, nl, ldw): delta_s, eps_s, gamma_s (set-up)
+  double *ab;        // (2, S, nl, ldw): alpha_s, beta_s (every solve)
+  double *send;      // the slab's message: TH_MSG doubles per (mode, wavenumber)
+  double *slabDE;    // the slab's constants: TH_CST doubles per (mode, wavenumber)
+  int S, nl, ldw, nk;
+};
 template <int R, int PHASE, int KW>
 __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_thomas_seg(double *wrk, const QgThomasSegRec *segs, long wstride,
                                                                                          int ldw, int nk, int layer0, int nblk,

@@ -1,8 +1,11 @@
 // k_thomas_corr.inc - the body of the correction pass (see k_thomas.h), included into k_thomas_corr (this handle is slab
-// P.rank of P.nranks) and k_thomas_corr_seg (segment `rank` of the P.nranks segments of one column); textual inclusion
-// for the reason given in k_thomas_solve.inc.  The including kernel provides: the kernel argument P; T (its
-// QgThomasCorr, or a segment's); rank, jr0, jr1 (the rows corrected); slice (of THC_UNR * STEP rows); owner: this
-// workgroup publishes the basin-wide ksum / ybnd.
+// P.rank of P.nranks), k_thomas_corr_seg (segment `rank` of the P.nranks segments of one column) and k_thomas_corr_slab
+// (k_thomas_slab.h: one segment of slab P.rank); textual inclusion for the reason given in k_thomas_solve.inc.  The
+// including kernel provides: the kernel argument P; T (its QgThomasCorr, or a segment's); rank, jr0, jr1 (the rows
+// corrected); slice (of THC_UNR * STEP rows); owner: this workgroup publishes the basin-wide ksum / ybnd;
+// and, where the rows corrected are not all of `rank`, the macro THC_INFLOWS(u, v), which turns the inflows composed
+// for `rank` into theirs (a macro, not a callable: an empty lambda reordered a few instructions of the two kernels that
+// have nothing to turn, and they are to compile to what they compiled to).
   // 256 threads: four workgroups share a CU (the pass is all memory latency).  Every thread first requests its first
   // rows and table entries, then the workgroup fetches all ranks' summaries of the block's 16 wavenumbers into LDS in
   // one round trip - the two latencies overlap instead of adding - and 16 lanes run the two short chains of
@@ -96,6 +99,9 @@
       v = __builtin_fma(gc[0], v, gs[1] + gc[1] * us);
       vfirst = v;
     }
+#ifdef THC_INFLOWS
+    THC_INFLOWS(mine_u, mine_v);
+#endif
     sU[tid] = ft * mine_u;
     sV[tid] = ft * mine_v;
     if (kq < P.g.nk && owner) P.ksum[(long)m * ldw + kq] = ft * term;

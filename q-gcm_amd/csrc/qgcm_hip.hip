@@ -208,14 +208,17 @@ struct qgcm_hip_ctx {
   int slab_nranks = 1;
   const double *oml_gath = nullptr;        // not owned - y-slabs: the gathered sums of the mixed layer's stage 10 (3, nranks)
   QgThomasTab tt, tt_tmp;                  // Thomas pivot tables of the modal solves / of the last qgcm_hip_helmholtz
-  // whole-domain oceans whose column is cut into segments (k_thomas.h: k_thomas_seg, k_thomas_corr_seg): the plan, and
-  // per set of diagonals - [0] the modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot
+  // oceans whose column is cut into segments: a whole-domain handle's (k_thomas.h: k_thomas_seg, k_thomas_corr_seg) or a
+  // y-slab's (k_thomas_slab.h: the segments folded into the slab's one summary).  The plan, and per set of diagonals -
+  // [0] the modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot
   // tables (tt / tt_tmp, segment-major), response tables and constants
   struct {
     int S = 1, R = 0, maxlen = 0;           // segments (1: the single-segment kernel), rows per chunk, longest segment
-    int seg_rows = 0;                       // QGCM_HIP_THOMAS_SEG_ROWS as set_grid read it (0: unset)
+    int seg_rows = 0;                       // QGCM_HIP_THOMAS_SEG_ROWS (a y-slab: .._SLAB_SEG_ROWS) as set_grid read it (0: unset)
     std::vector<int> first, count;          // interior rows [first, first + count) of each segment
     QgDbl msg;                              // (Cf, Cb, S0) of every segment, segment-major: the gathered slab messages' layout
+    QgDbl coef, ab;                         // the slab phases of the modal solves (QgThomasFold): (delta, eps, gamma) of the
+                                            // set-up and (alpha, beta) of the last phase 1, (S, nl, ldw) each
     struct Set {
       QgBuf<QgThomasSegRec> recs;
       QgDbl ptab, qtab, cst;                // responses; (D, E, SP, SQ) segment-major (cgath's layout)
@@ -640,6 +643,18 @@ extern "C" int qgcm_hip_thomas_segments(int nrows, int max_rows, int *nseg, int 
   return 0;
 }
 
+extern "C" int qgcm_hip_thomas_plan(qgcm_hip_handle c, int *nseg, int *first, int *count) {
+  if (!c || !nseg) QG_FAIL("qgcm_hip_thomas_plan: null argument");
+  if (!c->grid_set) QG_FAIL("qgcm_hip_thomas_plan: the plan is made by qgcm_hip_set_grid");
+  const int S = c->seg.S;
+  *nseg = S;
+  for (int s = 0; s < S; ++s) {
+    if (first) first[s] = S > 1 ? c->seg.first[s] : 0;
+    if (count) count[s] = S > 1 ? c->seg.count[s] : c->g.jr1 - c->g.jr0 + 1;
+  }
+  return 0;
+}
+
 // per-step message of one slab: the summaries of the two y sweeps; a cyclic ocean appends its boundary line sums
 static inline size_t slab_msg_len(const QgGeom &g) {
   return (size_t)TH_MSG * g.nl * g.ldw + (g.cyc ? (size_t)5 * BSUM_NB * 2 * g.nl : 0);
@@ -712,7 +727,15 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
                          bool cyc_part_a = false);
 
 static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, int phase, bool cyca, int nlayers, hipStream_t st);
+static int launch_thomas_seg_rows(qgcm_hip_ctx *c, const QgThomasParams &P, const QgThomasSegRec *recs, int nlayers, hipStream_t st);
 static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int nlayers, hipStream_t st);
+static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int phase, int nlayers, hipStream_t st);
+// The kernels of a y-slab cut into segments and their launches live in k_thomas_slab.hip, a device code object of its
+// own (as k_tend_rows.hip): this file compiles to the device code it had without them.
+hipError_t qg_launch_thomas_fold(bool setup, hipStream_t st, const QgThomasFold &F);
+hipError_t qg_launch_thomas_corr_slab(hipStream_t st, const QgThomasParams &P, const QgThomasCorr &T, const QgThomasSegRec *segs,
+                                      const QgThomasFold &F, int nslice, int nlayers);
+static QgThomasFold thomas_fold_params(const qgcm_hip_ctx *c, double *send);
 
 static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, double *wrk, const QgThomasTab &tab, int nlayers, int layer0) {
   const QgGeom &g = c->g;
@@ -773,11 +796,15 @@ static int build_slab_responses(qgcm_hip_ctx *c) {
   return 0;
 }
 
-// Set-up of the segmented whole-column solve for one set of diagonals (which = 0: the modal solves, boc = nlo diagonals;
+// Set-up of the segmented solve of a whole column or of a y-slab for one set of diagonals (which = 0: the modal solves,
+// boc = nlo diagonals;
 // 1: qgcm_hip_helmholtz's, one diagonal): every segment's pivots - the recurrence depends on its first global row - go
 // segment-major into tt / tt_tmp; PHASE 4 / 5 run once per segment (they leave the unit responses in the segment's own
 // rows of the work array, which is overwritten), then the responses are tabulated as far as they reach, as
-// build_slab_responses does for a slab: a segment's neighbours are the segments next to it.
+// build_slab_responses does for a slab: a segment's neighbours are the segments next to it, and at the slab's two ends the
+// neighbouring ranks, where there are any.  The modal set then folds the segments' constants into the slab's own
+// (k_thomas_slab.h): slabDE and the per-segment coefficients of the slab phases - on a whole-domain handle too, which
+// is a lone slab (nranks = 1) to qgcm_hip_thomas_phase.
 static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vector<double>> &boc) {
   const QgGeom &g = c->g;
   auto &sg = c->seg;
@@ -812,6 +839,8 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
     return P;
   };
   const double tol = 1.0e-19 * P0.ftnorm; // (build_slab_responses)
+  const bool nb_lo = g.joff + g.jlo > 1, nb_hi = g.joff + g.jhi < g.nyg; // a neighbouring rank below / above
+  auto closed = [&](int side, int s) { return side ? (s == S - 1 && !nb_hi) : (s == 0 && !nb_lo); }; // nothing ever enters there
   for (int side = 0; side < 2; ++side) { // 0: inflow from below (PHASE 4, Pv), 1: from above (PHASE 5, Qv)
     QgDbl &rtab = side ? ss.qtab : ss.ptab;
     rtab.reset();
@@ -820,7 +849,7 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
     for (int s = 0; s < S; ++s) {
       const QgThomasParams P = seg_params(s);
       if (launch_thomas_rows(c, P, sg.R, 4 + side, false, nlt, c->stream)) return 1;
-      if (side ? s == S - 1 : s == 0) continue; // the column's end: nothing ever enters there
+      if (closed(side, s)) continue;
       hipLaunchKernelGGL(k_thomas_reach, dim3(nblk, nlt), dim3(256), 0, c->stream, P, side, tol, d_reach + s * nmt);
       HIPCHECK(hipGetLastError());
     }
@@ -834,12 +863,19 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
     if ((double)off * TH_KW >= 2147483647.0) QG_FAIL("qgcm_hip_set_grid: the segments' response tables exceed 32-bit offsets");
     if (rtab.alloc((size_t)TH_KW * (off ? off : 1), "the segments' response table")) return 1;
     HIPCHECK(hipMemcpyAsync(d_off, h_off, sizeof(int) * S * nmt, hipMemcpyHostToDevice, c->stream));
-    for (int s = side ? 0 : 1; s < (side ? S - 1 : S); ++s) {
+    for (int s = 0; s < S; ++s) {
+      if (closed(side, s)) continue;
       const QgThomasParams P = seg_params(s);
       hipLaunchKernelGGL(k_thomas_pack, dim3(nblk, nlt), dim3(256), 0, c->stream, P, side, (const int *)(d_reach + s * nmt),
                          (const int *)(d_off + s * nmt), rtab);
       HIPCHECK(hipGetLastError());
     }
+    HIPCHECK(hipStreamSynchronize(c->stream));
+  }
+  if (which == 0) {
+    const size_t per = (size_t)S * g.nl * g.ldw;
+    if (sg.coef.ensure(3 * per, "the segments' fold coefficients") || sg.ab.ensure(2 * per, "the segments' inflows")) return 1;
+    HIPCHECK(qg_launch_thomas_fold(true, c->stream, thomas_fold_params(c, nullptr)));
     HIPCHECK(hipStreamSynchronize(c->stream));
   }
   return 0;
@@ -865,20 +901,22 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   if (qgcm_hip_set_geometry(c, yporel, ddynoc)) return 1;
   c->bd2oc.assign(bd2oc, bd2oc + g.nxt);
   // Thomas diagonal + chunk-entry pivots per mode: boc = bd2oc - rdm2oc(m)   (src/ocisubs.F:148-150)
-  // a whole-domain ocean cuts a column of more than 2048 rows (or, with QGCM_HIP_THOMAS_SEG_ROWS set, any column longer
-  // than that) into segments; y-slabs and the atmosphere keep the single-segment kernel
+  // an ocean cuts a column of more than 2048 rows (or, with QGCM_HIP_THOMAS_SEG_ROWS - a y-slab: with
+  // QGCM_HIP_THOMAS_SLAB_SEG_ROWS - set, any column longer than that) into segments; the atmosphere keeps the
+  // single-segment kernel
   {
     const int nrows = g.jr1 - g.jr0 + 1;
     auto &sg = c->seg;
     int S = 1;
-    if (c->whole && !g.atm) {
-      // QGCM_HIP_THOMAS_SEG_ROWS: the longest segment; read here, at every set_grid.  Anything but a positive integer is
-      // refused: a typing error must not silently mean "unset"
+    if (!g.atm) {
+      // QGCM_HIP_THOMAS_SEG_ROWS (whole-domain handles) / QGCM_HIP_THOMAS_SLAB_SEG_ROWS (y-slabs): the longest segment; read
+      // here, at every set_grid.  Anything but a positive integer is refused: a typing error must not silently mean "unset"
+      const char *var = c->whole ? "QGCM_HIP_THOMAS_SEG_ROWS" : "QGCM_HIP_THOMAS_SLAB_SEG_ROWS";
       sg.seg_rows = 0;
-      if (const char *sr = getenv("QGCM_HIP_THOMAS_SEG_ROWS")) {
+      if (const char *sr = getenv(var)) {
         char *end = nullptr;
         const long v = strtol(sr, &end, 10);
-        if (end == sr || *end != '\0' || v < 1 || v > 1000000) QG_FAIL("qgcm_hip_set_grid: QGCM_HIP_THOMAS_SEG_ROWS=\"%s\" is not a positive number of rows", sr);
+        if (end == sr || *end != '\0' || v < 1 || v > 1000000) QG_FAIL("qgcm_hip_set_grid: %s=\"%s\" is not a positive number of rows", var, sr);
         sg.seg_rows = (int)v;
       }
       int first[QGCM_HIP_THOMAS_MAX_SEG], count[QGCM_HIP_THOMAS_MAX_SEG];
@@ -890,16 +928,16 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
     if (S != sg.S) { // (a second set_grid under another plan: the per-segment buffers are sized by S)
       HIPCHECK(hipStreamSynchronize(c->stream));
       sg.msg.reset();
+      sg.coef.reset();
+      sg.ab.reset();
       for (auto &ss : sg.set) ss = {};
     }
     sg.set[1].boc.clear();
     sg.S = S;
     c->thR = thomas_rows_per_chunk(S > 1 ? sg.maxlen : nrows);
     sg.R = c->thR;
-    if (c->thR < 0) {
-      if (g.atm) QG_FAIL("qgcm_hip_set_grid: %d rows of an atmosphere handle exceed the single-segment Thomas kernel (<= 2048); only whole-domain ocean handles solve taller columns", nrows);
-      QG_FAIL("qgcm_hip_set_grid: %d rows per slab exceed the single-segment Thomas kernel (<= 2048); only whole-domain ocean handles solve taller columns", nrows);
-    }
+    if (c->thR < 0) // (an ocean of that height has a segment plan: the atmosphere only)
+      QG_FAIL("qgcm_hip_set_grid: %d rows of an atmosphere handle exceed the single-segment Thomas kernel (<= 2048); only ocean handles solve taller columns", nrows);
   }
   std::vector<std::vector<double>> bocs(g.nl, std::vector<double>(g.nk));
   for (int m = 0; m < g.nl; ++m)
@@ -1620,11 +1658,6 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   QgThomasParams P;
   fill_thomas_params(c, P, wrk, tab, nlayers, layer0);
   P.gath = gath; P.send = send; P.rank = rank; P.nranks = nranks;
-  if (c->seg.S > 1) {
-    if (phase != 0) QG_FAIL("qgcm_hip_thomas_phase: this handle solves its column in %d segments; the slab phases belong to y-slabs", c->seg.S);
-    if (cyc_part_a) QG_FAIL("k_thomas: part A of the constraint algebra does not ride in the segmented solve");
-    return launch_thomas_seg(c, P, &tab == &c->tt ? 0 : 1, nlayers, st);
-  }
   if (phase == 2) {
     if (g.cyc) P.ybnd = c->ybnd;
     c->slab_gath = gath; // (the cyclic constraint algebra reads the boundary line sums at the end of the step messages)
@@ -1632,6 +1665,14 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
     P.cgath = (nranks == 1) ? c->slabDE : c->th_cgath; // a lone slab is its own rank 0
     if (nranks > 1 && (!c->th_cgath || c->th_cgath_ranks != nranks))
       QG_FAIL("qgcm_hip_thomas_phase: the set-up constants of the %d slabs have not been exchanged (qgcm_hip_set_thomas_consts)", nranks);
+  }
+  if (c->seg.S > 1) {
+    if (phase == 1 || phase == 2) return launch_thomas_slab_seg(c, P, phase, nlayers, st);
+    if (phase != 0 || !c->whole) QG_FAIL("k_thomas: phase %d on a column in %d segments", phase, c->seg.S);
+    if (cyc_part_a) QG_FAIL("k_thomas: part A of the constraint algebra does not ride in the segmented solve");
+    return launch_thomas_seg(c, P, &tab == &c->tt ? 0 : 1, nlayers, st);
+  }
+  if (phase == 2) {
     if (&tab != &c->tt || !c->corr.meta) QG_FAIL("k_thomas_corr: the response tables belong to the modal solves of qgcm_hip_set_grid");
     const int nm = P.nblk * g.nl;
     QgThomasCorr T;
@@ -1691,6 +1732,21 @@ static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, i
   return 0;
 }
 
+// PHASE 1 of every segment at once (k_thomas_seg): P.send = the segments' summaries, the tables P's
+static int launch_thomas_seg_rows(qgcm_hip_ctx *c, const QgThomasParams &P, const QgThomasSegRec *recs, int nlayers, hipStream_t st) {
+  const QgGeom &g = c->g;
+  KTimer t(c, KN_THOMAS, st);
+  dim3 gridk((g.nk + 7) / 8, nlayers, c->seg.S);
+  switch (c->seg.R) {
+#define QG_TH_CASE(RV) case RV: hipLaunchKernelGGL((k_thomas_seg<RV, 1, 8>), gridk, dim3(8 * TH_NC), 0, st, P.wrk, recs, g.wstride, g.ldw, g.nk, P.layer0, P.nblk, P); break;
+    QG_TH_ROWS(QG_TH_CASE)
+#undef QG_TH_CASE
+    default: QG_FAIL("k_thomas_seg: no instantiation for %d rows per thread", c->seg.R);
+  }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 // The whole column of a handle whose plan has S > 1 segments, two launches with nothing of the host in between:
 // k_thomas_seg (PHASE 1 of every segment, summaries into seg.msg) and k_thomas_corr_seg (inflows composed from seg.msg
 // and the set-up constants, responses added, ksum / ybnd published).  P: launch_thomas's; which: the set of diagonals
@@ -1706,17 +1762,7 @@ static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int 
   P.rank = 0; P.nranks = S;
   c->slab_gath = nullptr; // whole-column solve: the constraint algebra reads bpart
   if (g.cyc && nlayers == g.nl) P.ybnd = c->ybnd;
-  {
-    KTimer t(c, KN_THOMAS, st);
-    dim3 gridk((g.nk + 7) / 8, nlayers, S);
-    switch (sg.R) {
-#define QG_TH_CASE(RV) case RV: hipLaunchKernelGGL((k_thomas_seg<RV, 1, 8>), gridk, dim3(8 * TH_NC), 0, st, P.wrk, (const QgThomasSegRec *)ss.recs, g.wstride, g.ldw, g.nk, P.layer0, P.nblk, P); break;
-      QG_TH_ROWS(QG_TH_CASE)
-#undef QG_TH_CASE
-      default: QG_FAIL("k_thomas_seg: no instantiation for %d rows per thread", sg.R);
-    }
-    HIPCHECK(hipGetLastError());
-  }
+  if (launch_thomas_seg_rows(c, P, ss.recs, nlayers, st)) return 1;
   {
     const int nm = P.nblk * nlt * S;
     QgThomasCorr T;
@@ -1729,6 +1775,42 @@ static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int 
     hipLaunchKernelGGL(k_thomas_corr_seg, dim3(P.nblk, nlayers, S * nslice), dim3(THC_NT), lds, st, P, T, (const QgThomasSegRec *)ss.recs, nslice);
     HIPCHECK(hipGetLastError());
   }
+  return 0;
+}
+
+// The slab phases of a handle whose plan has S > 1 segments (k_thomas_slab.h), two launches each with nothing of the host
+// in between.  1: k_thomas_seg (the segments' summaries into seg.msg) and k_thomas_fold (the slab's ONE summary into
+// P.send, every segment's zero-inflow inflows into seg.ab); 2: k_thomas_corr_slab.  P: launch_thomas's, for phase 2
+// with the ranks' summaries and constants in place
+static QgThomasFold thomas_fold_params(const qgcm_hip_ctx *c, double *send) {
+  const auto &sg = c->seg;
+  QgThomasFold F;
+  F.msg = sg.msg; F.cst = sg.set[0].cst; F.coef = sg.coef; F.ab = sg.ab;
+  F.send = send; F.slabDE = c->slabDE;
+  F.S = sg.S; F.nl = c->g.nl; F.ldw = c->g.ldw; F.nk = c->g.nk;
+  return F;
+}
+static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int phase, int nlayers, hipStream_t st) {
+  const QgGeom &g = c->g;
+  const auto &sg = c->seg;
+  const auto &ss = sg.set[0];
+  if (P.binf != c->tt.binf || nlayers != g.nl || P.layer0 != 0) QG_FAIL("qgcm_hip_thomas_phase: a column in segments folds all modal solves at once");
+  if (!ss.recs || !ss.meta || !sg.coef || !sg.ab) QG_FAIL("qgcm_hip_thomas_phase: the segments' tables have not been built (qgcm_hip_set_grid)");
+  const QgThomasFold F = thomas_fold_params(c, P.send);
+  if (phase == 1) {
+    P.send = sg.msg; P.slabDE = ss.cst;
+    if (launch_thomas_seg_rows(c, P, ss.recs, nlayers, st)) return 1;
+    KTimer t(c, KN_THOMAS, st);
+    HIPCHECK(qg_launch_thomas_fold(false, st, F));
+    return 0;
+  }
+  const int nm = P.nblk * g.nl * sg.S;
+  QgThomasCorr T;
+  T.ptab = ss.ptab; T.qtab = ss.qtab;
+  T.np = ss.meta; T.nq = ss.meta + nm; T.poff = ss.meta + 2 * nm; T.qoff = ss.meta + 3 * nm;
+  KTimer t(c, KN_THOMAS, st);
+  const int per = THC_UNR * (THC_NT / 8), nslice = (sg.maxlen + per - 1) / per; // rows per slice
+  HIPCHECK(qg_launch_thomas_corr_slab(st, P, T, ss.recs, F, nslice, nlayers));
   return 0;
 }
 

@@ -110,7 +110,7 @@ SYMBOLS = [
     "qgcm_hip_qgastep", "qgcm_hip_atinvq", "qgcm_hip_atqzbd", "qgcm_hip_get_bsums", "qgcm_hip_coupled_steps", "qgcm_hip_set_cu_range",
     "qgcm_hip_wrk_fill", "qgcm_hip_wrk_get", "qgcm_hip_wrk_set", "qgcm_hip_area_integrals",
     "qgcm_hip_local_rows", "qgcm_hip_row_transform", "qgcm_hip_thomas_msg_len", "qgcm_hip_thomas_phase",
-    "qgcm_hip_thomas_const_len", "qgcm_hip_thomas_consts", "qgcm_hip_set_thomas_consts", "qgcm_hip_thomas_segments",
+    "qgcm_hip_thomas_const_len", "qgcm_hip_thomas_consts", "qgcm_hip_set_thomas_consts", "qgcm_hip_thomas_segments", "qgcm_hip_thomas_plan",
     "qgcm_hip_constr", "qgcm_hip_unpack",
     "qgcm_hip_halo_msg_len", "qgcm_hip_halo_pack", "qgcm_hip_halo_unpack", "qgcm_hip_slab_stage", "qgcm_hip_oml_msg_len",
     "qgcm_hip_comm_unique_id", "qgcm_hip_comm_init", "qgcm_hip_slab_steps", "qgcm_hip_comm_set_halo_p2p", "qgcm_hip_comm_set_overlap", "qgcm_hip_comm_probe",
@@ -200,6 +200,7 @@ def load_library():
     L.qgcm_hip_set_thomas_consts.argtypes = [vp, vp, C.c_int]
     L.qgcm_hip_thomas_phase.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
     L.qgcm_hip_thomas_segments.argtypes = [C.c_int, C.c_int, ip, ip, ip]
+    L.qgcm_hip_thomas_plan.argtypes = [vp, ip, ip, ip]
     L.qgcm_hip_constr.argtypes = [vp]
     L.qgcm_hip_unpack.argtypes = [vp, C.c_int]
     L.qgcm_hip_halo_msg_len.argtypes = [vp]
@@ -335,4 +336,13 @@ def thomas_segments(nrows, max_rows=0):
     n = C.c_int(0)
     first, count = (C.c_int * THOMAS_MAX_SEG)(), (C.c_int * THOMAS_MAX_SEG)()
     check(load_library().qgcm_hip_thomas_segments(nrows, max_rows, C.byref(n), first, count))
+    return [(first[s], count[s]) for s in range(n.value)]
+
+
+def thomas_plan(handle):
+    """The segment plan a handle uses (qgcm_hip_thomas_plan): [(first, count)] per segment, rows counted from the
+    handle's first interior row; one entry for a handle on the single-segment kernel."""
+    n = C.c_int(0)
+    first, count = (C.c_int * THOMAS_MAX_SEG)(), (C.c_int * THOMAS_MAX_SEG)()
+    check(load_library().qgcm_hip_thomas_plan(handle, C.byref(n), first, count))
     return [(first[s], count[s]) for s in range(n.value)]

@@ -389,6 +389,11 @@ class OceanModel:
         except Exception:
             pass
 
+    def thomas_plan(self):
+        """[(first, count)] per segment of the column's interior rows (lib.thomas_plan); one entry: the single launch."""
+        from .lib import thomas_plan
+        return thomas_plan(self.h)
+
     def _f3(self):
         c = self.cfg
         return np.zeros((c.nxpo, c.nypo, c.nlo), order="F")

@@ -538,6 +538,11 @@ class HipSlab:
         check(self.L.qgcm_hip_thomas_phase(self.h, int(phase), self._ptr(gath), self._ptr(send), self.rank, self.nranks))
         self._done()
 
+    def thomas_plan(self):
+        """[(first, count)] per segment of this slab's interior rows (lib.thomas_plan); one entry: the single launch."""
+        from .lib import thomas_plan
+        return thomas_plan(self.h)
+
     def thomas_consts(self, dst):
         """This slab's right-hand-side independent summary constants -> dst (device buffer of cst_len doubles)."""
         check(self.L.qgcm_hip_thomas_consts(self.h, self._ptr(dst))); self._done()
