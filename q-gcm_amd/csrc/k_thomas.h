@@ -125,8 +125,9 @@ __global__ __launch_bounds__(KW * TH_NC, (KW == 8 && R <= 16) ? 4 : 1) void k_th
 // "slab" of the y-slab algebra above that lives in the same work array.  k_thomas_seg runs PHASE 1 over all segments
 // at once - the segment is the grid's z index, its rows and the origins of its tables, of its summary and of its
 // constants come from a device table - and k_thomas_corr_seg below composes all segments' inflows and adds the
-// responses.  (Set-up: the plain k_thomas<R, 4 / 5> once per segment, build_segments in qgcm_hip.hip.)  Two launches, 2 reads + 2 writes of the rows within reach against 1 + 1
-// of PHASE 0; the summaries never leave the device.  grid: (ceil(nk/KW), nlayers, S)
+// responses.  (Set-up: the plain k_thomas<R, 4 / 5> once per segment, build_thomas_tables in qgcm_hip.hip - the set-up
+// of the column that is not cut too, which is a plan of one segment.)  Two launches, 2 reads + 2 writes of the rows
+// within reach against 1 + 1 of PHASE 0; the summaries never leave the device.  grid: (ceil(nk/KW), nlayers, S)
 struct QgThomasSegRec {
   int jr0, jr1; // the segment's first / last local row (1-based, as QgGeom::jr0 / jr1)
   int tb0;      // offset of its (nblk, nlayers) entries in rcb / poff and in the response tables' np / nq / poff / qoff

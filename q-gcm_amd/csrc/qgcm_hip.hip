@@ -207,31 +207,28 @@ struct qgcm_hip_ctx {
   const double *slab_gath = nullptr;       // not owned - cyclic y-slabs: the gathered step messages of the last thomas phase 2
   int slab_nranks = 1;
   const double *oml_gath = nullptr;        // not owned - y-slabs: the gathered sums of the mixed layer's stage 10 (3, nranks)
-  QgThomasTab tt, tt_tmp;                  // Thomas pivot tables of the modal solves / of the last qgcm_hip_helmholtz
-  // oceans whose column is cut into segments: a whole-domain handle's (k_thomas.h: k_thomas_seg, k_thomas_corr_seg) or a
-  // y-slab's (k_thomas_slab.h: the segments folded into the slab's one summary).  The plan, and per set of diagonals -
-  // [0] the modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot
-  // tables (tt / tt_tmp, segment-major), response tables and constants
+  // The Thomas solve's plan and tables (build_thomas_tables).  The plan cuts the interior rows into S >= 1 segments: one
+  // for every column up to 2048 rows (the single-segment kernels k_thomas / k_thomas_corr; the plan of one segment is
+  // the slab itself), more for a taller ocean - a whole-domain handle's (k_thomas.h: k_thomas_seg, k_thomas_corr_seg)
+  // or a y-slab's (k_thomas_slab.h: the segments folded into the slab's one summary).  Per set of diagonals - [0] the
+  // modal solves of set_grid, [1] the last qgcm_hip_helmholtz - every segment's pivot tables, response tables and
+  // constants, segment-major.  With S = 1 a set holds its pivots and, in [0], meta and the two response tables (a
+  // single row towards a side without a neighbour); the slab's constants are slabDE itself.
   struct {
-    int S = 1, R = 0, maxlen = 0;           // segments (1: the single-segment kernel), rows per chunk, longest segment
+    int S = 1, R = 0, maxlen = 0;           // segments, rows per thread of the Thomas kernel (its chunk), longest segment
     int seg_rows = 0;                       // QGCM_HIP_THOMAS_SEG_ROWS (a y-slab: .._SLAB_SEG_ROWS) as set_grid read it (0: unset)
     std::vector<int> first, count;          // interior rows [first, first + count) of each segment
-    QgDbl msg;                              // (Cf, Cb, S0) of every segment, segment-major: the gathered slab messages' layout
-    QgDbl coef, ab;                         // the slab phases of the modal solves (QgThomasFold): (delta, eps, gamma) of the
-                                            // set-up and (alpha, beta) of the last phase 1, (S, nl, ldw) each
+    QgDbl msg;                              // S > 1: (Cf, Cb, S0) of every segment, segment-major: the gathered slab messages' layout
+    QgDbl coef, ab;                         // S > 1: the slab phases of the modal solves (QgThomasFold): (delta, eps, gamma) of
+                                            // the set-up and (alpha, beta) of the last phase 1, (S, nl, ldw) each
     struct Set {
-      QgBuf<QgThomasSegRec> recs;
-      QgDbl ptab, qtab, cst;                // responses; (D, E, SP, SQ) segment-major (cgath's layout)
+      QgThomasTab tab;                      // pivots
+      QgBuf<QgThomasSegRec> recs;           // S > 1
+      QgDbl ptab, qtab, cst;                // responses; S > 1: (D, E, SP, SQ) segment-major (cgath's layout)
       QgBuf<int> meta;                      // np, nq, poff, qoff: (nblk, layers, S) each
-      std::vector<double> boc;              // [1]: the diagonal the tables were built for
+      std::vector<double> boc;              // [1], S > 1: the diagonal the tables were built for
     } set[2];
   } seg;
-  // y-slabs: the slab's responses to unit inflows from below / above, tabulated as far as they reach (k_thomas_corr)
-  struct {
-    QgDbl ptab, qtab;
-    QgBuf<int> meta; // np, nq, poff, qoff: (nblk, nl) each
-    size_t prows = 0, qrows = 0;
-  } corr;
   QgDbl slabDE;                            // y-slab summary constants (D, E, SP, SQ) per (mode, wavenumber)
   QgDbl th_cgath;                          // all ranks' slabDE (rank-major), exchanged once (qgcm_hip_set_thomas_consts)
   int th_cgath_ranks = 0;
@@ -239,7 +236,6 @@ struct qgcm_hip_ctx {
   QgDbl bpart;                             // cyclic: partial boundary line sums (k_tend's extra workgroups -> constraint algebra)
   QgBuf<QgConstrParams> d_boxq;            // box: device copy of the constraint parameters (generic inverse rows' extra workgroup)
   QgBuf<QgCycConstrParams> d_cycq;         // cyclic: device copy of the constraint parameters (fused step path)
-  int thR;                                 // rows per chunk of the Thomas kernel
   QgDbl pch1, pch2, pbh;
   QgBuf<QgScalars> sc;
   QgBuf<double2> twid;
@@ -649,8 +645,8 @@ extern "C" int qgcm_hip_thomas_plan(qgcm_hip_handle c, int *nseg, int *first, in
   const int S = c->seg.S;
   *nseg = S;
   for (int s = 0; s < S; ++s) {
-    if (first) first[s] = S > 1 ? c->seg.first[s] : 0;
-    if (count) count[s] = S > 1 ? c->seg.count[s] : c->g.jr1 - c->g.jr0 + 1;
+    if (first) first[s] = c->seg.first[s];
+    if (count) count[s] = c->seg.count[s];
   }
   return 0;
 }
@@ -722,14 +718,18 @@ static int upload_pivots(qgcm_hip_ctx *c, QgThomasTab &D, const ThomasTabHost &T
   return 0;
 }
 
-static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, int nlayers, int phase,
-                         const double *gath, double *send, int rank, int nranks, int layer0, hipStream_t st,
-                         bool cyc_part_a = false);
+// the y-slab arguments of a Thomas phase (qgcm_hip_thomas_phase); the default is a lone slab
+struct QgThomasSlabArgs {
+  const double *gath = nullptr; // phase 2: all ranks' gathered step messages
+  double *send = nullptr;       // phase 1: this slab's message
+  int rank = 0, nranks = 1;
+};
+static int launch_thomas(qgcm_hip_ctx *c, int which, int nlayers, int phase, const QgThomasSlabArgs &slab = {}, bool cyc_part_a = false);
 
-static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, int phase, bool cyca, int nlayers, hipStream_t st);
+static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int phase, bool cyca, int nlayers, hipStream_t st);
 static int launch_thomas_seg_rows(qgcm_hip_ctx *c, const QgThomasParams &P, const QgThomasSegRec *recs, int nlayers, hipStream_t st);
 static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int nlayers, hipStream_t st);
-static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int phase, int nlayers, hipStream_t st);
+static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int phase, int nlayers, hipStream_t st);
 // The kernels of a y-slab cut into segments and their launches live in k_thomas_slab.hip, a device code object of its
 // own (as k_tend_rows.hip): this file compiles to the device code it had without them.
 hipError_t qg_launch_thomas_fold(bool setup, hipStream_t st, const QgThomasFold &F);
@@ -737,79 +737,41 @@ hipError_t qg_launch_thomas_corr_slab(hipStream_t st, const QgThomasParams &P, c
                                       const QgThomasFold &F, int nslice, int nlayers);
 static QgThomasFold thomas_fold_params(const qgcm_hip_ctx *c, double *send);
 
-static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, double *wrk, const QgThomasTab &tab, int nlayers, int layer0) {
+// which: the set of diagonals (seg.set) whose pivots the solve reads; always the whole work array from its first layer
+static void fill_thomas_params(qgcm_hip_ctx *c, QgThomasParams &P, int which, int nlayers) {
   const QgGeom &g = c->g;
+  const QgThomasTab &tab = c->seg.set[which].tab;
   memset(&P, 0, sizeof(P));
   P.g = g;
   P.gath_stride = (long)slab_msg_len_oml(c);
   P.slabDE = c->slabDE;
   P.ksum = c->ksum;
-  P.wrk = wrk;
+  P.wrk = c->wrk;
   P.binf = tab.binf; P.ptab = tab.ptab; P.rcb = tab.rcb; P.poff = tab.poff;
   P.nblk = (g.nk + TH_KW - 1) / TH_KW;
   P.aoc = c->prm.aoc;
   P.ftnorm = g.cyc ? 1.0 / g.nxt : 0.5 / g.nxt; // src/ocisubs.F:440, 547
   P.nlayers = nlayers;
-  P.layer0 = layer0;
+  P.layer0 = 0;
   P.nranks = 1;
 }
 
-// Set-up of the y-slab solve (k_thomas.h): PHASE 4 / 5 give the slab's gain and response sums (slabDE) and leave the
-// responses Pv / Qv to unit inflows in the work array; they are tabulated per block of TH_KW wavenumbers as far as
-// they reach (above 1e-19 of the inflow) - towards a side without a neighbour nothing ever enters: no table.
-static int build_slab_responses(qgcm_hip_ctx *c) {
-  const QgGeom &g = c->g;
-  const int nblk = (g.nk + TH_KW - 1) / TH_KW, nm = nblk * g.nl;
-  const bool nb_lo = g.joff + g.jlo > 1, nb_hi = g.joff + g.jhi < g.nyg;
-  if (c->corr.meta.ensure((size_t)4 * nm, "the slab responses' reach")) return 1;
-  std::vector<int> meta((size_t)4 * nm, 0);
-  QgThomasParams P;
-  fill_thomas_params(c, P, c->wrk, c->tt, g.nl, 0);
-  const double tol = 1.0e-19 * P.ftnorm; // three orders below the rounding of the inflow itself
-  for (int side = 0; side < 2; ++side) { // 0: inflow from below (PHASE 4, Pv), 1: from above (PHASE 5, Qv)
-    if (launch_thomas(c, c->wrk, c->tt, g.nl, 4 + side, nullptr, nullptr, 0, 1, 0, nullptr)) return 1;
-    QgDbl &tab = side ? c->corr.qtab : c->corr.ptab;
-    size_t &rows = side ? c->corr.qrows : c->corr.prows;
-    tab.reset();
-    rows = 0;
-    int *d_reach = c->corr.meta + side * nm, *d_off = c->corr.meta + (2 + side) * nm;
-    if (!(side ? nb_hi : nb_lo)) continue; // reach 0 everywhere
-    hipLaunchKernelGGL(k_thomas_reach, dim3(nblk, g.nl), dim3(256), 0, c->stream, P, side, tol, d_reach);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(meta.data() + side * nm, d_reach, sizeof(int) * nm, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    size_t off = 0;
-    for (int i = 0; i < nm; ++i) {
-      meta[(2 + side) * nm + i] = (int)off;
-      off += meta[side * nm + i];
-    }
-    rows = off;
-    if (tab.alloc((size_t)TH_KW * (off ? off : 1), "the slab's response table")) return 1;
-    HIPCHECK(hipMemcpyAsync(d_off, meta.data() + (2 + side) * nm, sizeof(int) * nm, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_thomas_pack, dim3(nblk, g.nl), dim3(256), 0, c->stream, P, side, (const int *)d_reach, (const int *)d_off, tab);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(c->stream));
-  }
-  // (the sides without a neighbour: zero reach, zero offsets)
-  HIPCHECK(hipMemcpyAsync(c->corr.meta, meta.data(), sizeof(int) * 4 * nm, hipMemcpyHostToDevice, c->stream));
-  HIPCHECK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-// Set-up of the segmented solve of a whole column or of a y-slab for one set of diagonals (which = 0: the modal solves,
-// boc = nlo diagonals;
-// 1: qgcm_hip_helmholtz's, one diagonal): every segment's pivots - the recurrence depends on its first global row - go
-// segment-major into tt / tt_tmp; PHASE 4 / 5 run once per segment (they leave the unit responses in the segment's own
-// rows of the work array, which is overwritten), then the responses are tabulated as far as they reach, as
-// build_slab_responses does for a slab: a segment's neighbours are the segments next to it, and at the slab's two ends the
-// neighbouring ranks, where there are any.  The modal set then folds the segments' constants into the slab's own
-// (k_thomas_slab.h): slabDE and the per-segment coefficients of the slab phases - on a whole-domain handle too, which
-// is a lone slab (nranks = 1) to qgcm_hip_thomas_phase.
-static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vector<double>> &boc) {
+// Set-up of the Thomas solve for one set of diagonals (which = 0: the modal solves, boc = nlo diagonals; 1:
+// qgcm_hip_helmholtz's, one diagonal) under the handle's plan of S >= 1 segments; a plan of one segment is the slab
+// itself.  Every segment's pivots - the recurrence depends on its first global row - go segment-major into the set's
+// pivot tables.  A whole column solved in one piece with another diagonal (which = 1, S = 1) needs nothing else: PHASE 0
+// has no inflows.  Otherwise PHASE 4 / 5 run once per segment (k_thomas.h: they give the segment's gain and response
+// sums - with S = 1 straight into slabDE - and leave the responses Pv / Qv to unit inflows in the segment's own rows of
+// the work array, which is overwritten), then the responses are tabulated per block of TH_KW wavenumbers as far as they
+// reach (above 1e-19 of the inflow).  A segment's neighbours are the segments next to it, and at the slab's two ends the
+// neighbouring ranks, where there are any; towards a side without a neighbour nothing ever enters: reach 0.  The modal
+// set of S > 1 segments then folds the segments' constants into the slab's own (k_thomas_slab.h): slabDE and the
+// per-segment coefficients of the slab phases - on a whole-domain handle too, which is a lone slab (nranks = 1) to
+// qgcm_hip_thomas_phase.  (One segment is not folded: the fold of one is not bound to give PHASE 4 / 5's bits.)
+static int build_thomas_tables(qgcm_hip_ctx *c, int which, const std::vector<std::vector<double>> &boc) {
   const QgGeom &g = c->g;
   auto &sg = c->seg;
   auto &ss = sg.set[which];
-  QgThomasTab &tab = which ? c->tt_tmp : c->tt;
   const int S = sg.S, nlt = (int)boc.size(), nblk = (g.nk + TH_KW - 1) / TH_KW, nmt = nblk * nlt;
   std::vector<QgThomasSegRec> recs(S);
   {
@@ -821,24 +783,28 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
       recs[s] = QgThomasSegRec{gs.jr0, gs.jr1, s * nmt, 0, (long)s * nlt * g.ldw, (long)s * TH_MSG * nlt * g.ldw, (long)s * TH_CST * g.nl * g.ldw};
       for (int m = 0; m < nlt; ++m) build_pivots(gs, c->prm.aoc, boc[m].data(), T);
     }
-    if (upload_pivots(c, tab, T)) return 1; // (waits for the stream: nothing reads the old tables any more)
+    if (upload_pivots(c, ss.tab, T)) return 1; // (waits for the stream: nothing reads the old tables any more)
   }
-  if (sg.msg.ensure((size_t)TH_MSG * g.nl * g.ldw * S, "the segments' messages")) return 1;
-  if (ss.cst.ensure((size_t)TH_CST * g.nl * g.ldw * S, "the segments' constants")) return 1;
-  if (ss.recs.ensure(S, "the segment records") || ss.meta.ensure((size_t)4 * S * nmt, "the segments' reach")) return 1;
-  HIPCHECK(hipMemcpy(ss.recs, recs.data(), sizeof(QgThomasSegRec) * S, hipMemcpyHostToDevice));
+  if (which != 0 && S == 1) return 0;
+  if (S > 1) { // (one segment: no device records, its summary is the slab's message and its constants are slabDE)
+    if (sg.msg.ensure((size_t)TH_MSG * g.nl * g.ldw * S, "the segments' messages")) return 1;
+    if (ss.cst.ensure((size_t)TH_CST * g.nl * g.ldw * S, "the segments' constants")) return 1;
+    if (ss.recs.ensure(S, "the segment records")) return 1;
+    HIPCHECK(hipMemcpy(ss.recs, recs.data(), sizeof(QgThomasSegRec) * S, hipMemcpyHostToDevice));
+  }
+  if (ss.meta.ensure((size_t)4 * S * nmt, "the segments' reach")) return 1;
   std::vector<int> meta((size_t)4 * S * nmt, 0);
   HIPCHECK(hipMemcpy(ss.meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice)); // (ends without a neighbour: reach 0)
   QgThomasParams P0;
-  fill_thomas_params(c, P0, c->wrk, tab, nlt, 0);
+  fill_thomas_params(c, P0, which, nlt);
   auto seg_params = [&](int s) {
     QgThomasParams P = P0;
     P.g.jr0 = recs[s].jr0; P.g.jr1 = recs[s].jr1;
     P.binf += recs[s].b0; P.rcb += recs[s].tb0; P.poff += recs[s].tb0;
-    P.slabDE = ss.cst + recs[s].cst0;
+    if (S > 1) P.slabDE = ss.cst + recs[s].cst0;
     return P;
   };
-  const double tol = 1.0e-19 * P0.ftnorm; // (build_slab_responses)
+  const double tol = 1.0e-19 * P0.ftnorm; // three orders below the rounding of the inflow itself
   const bool nb_lo = g.joff + g.jlo > 1, nb_hi = g.joff + g.jhi < g.nyg; // a neighbouring rank below / above
   auto closed = [&](int side, int s) { return side ? (s == S - 1 && !nb_hi) : (s == 0 && !nb_lo); }; // nothing ever enters there
   for (int side = 0; side < 2; ++side) { // 0: inflow from below (PHASE 4, Pv), 1: from above (PHASE 5, Qv)
@@ -848,7 +814,7 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
     int *h_reach = meta.data() + side * S * nmt, *h_off = meta.data() + (2 + side) * S * nmt;
     for (int s = 0; s < S; ++s) {
       const QgThomasParams P = seg_params(s);
-      if (launch_thomas_rows(c, P, sg.R, 4 + side, false, nlt, c->stream)) return 1;
+      if (launch_thomas_rows(c, P, 4 + side, false, nlt, c->stream)) return 1;
       if (closed(side, s)) continue;
       hipLaunchKernelGGL(k_thomas_reach, dim3(nblk, nlt), dim3(256), 0, c->stream, P, side, tol, d_reach + s * nmt);
       HIPCHECK(hipGetLastError());
@@ -860,6 +826,10 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
       h_off[i] = (int)off;
       off += h_reach[i];
     }
+    // The kernels index the table with 32-bit offsets.  A block's reach is at most its segment's rows, so the table has
+    // at most nblk * nlt * nrows rows of TH_KW doubles, and TH_KW * nblk <= ldw, nlt <= nlo, nrows < ny: fewer elements
+    // than the ldw * ny * nlo of the work array, which qgcm_hip_create keeps below 2^31 - for one segment as for many,
+    // this cannot trip on a grid the library accepts.
     if ((double)off * TH_KW >= 2147483647.0) QG_FAIL("qgcm_hip_set_grid: the segments' response tables exceed 32-bit offsets");
     if (rtab.alloc((size_t)TH_KW * (off ? off : 1), "the segments' response table")) return 1;
     HIPCHECK(hipMemcpyAsync(d_off, h_off, sizeof(int) * S * nmt, hipMemcpyHostToDevice, c->stream));
@@ -872,7 +842,7 @@ static int build_segments(qgcm_hip_ctx *c, int which, const std::vector<std::vec
     }
     HIPCHECK(hipStreamSynchronize(c->stream));
   }
-  if (which == 0) {
+  if (which == 0 && S > 1) {
     const size_t per = (size_t)S * g.nl * g.ldw;
     if (sg.coef.ensure(3 * per, "the segments' fold coefficients") || sg.ab.ensure(2 * per, "the segments' inflows")) return 1;
     HIPCHECK(qg_launch_thomas_fold(true, c->stream, thomas_fold_params(c, nullptr)));
@@ -907,7 +877,7 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   {
     const int nrows = g.jr1 - g.jr0 + 1;
     auto &sg = c->seg;
-    int S = 1;
+    int S = 1, first[QGCM_HIP_THOMAS_MAX_SEG] = {0}, count[QGCM_HIP_THOMAS_MAX_SEG] = {nrows}; // (the atmosphere's plan)
     if (!g.atm) {
       // QGCM_HIP_THOMAS_SEG_ROWS (whole-domain handles) / QGCM_HIP_THOMAS_SLAB_SEG_ROWS (y-slabs): the longest segment; read
       // here, at every set_grid.  Anything but a positive integer is refused: a typing error must not silently mean "unset"
@@ -919,34 +889,33 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
         if (end == sr || *end != '\0' || v < 1 || v > 1000000) QG_FAIL("qgcm_hip_set_grid: %s=\"%s\" is not a positive number of rows", var, sr);
         sg.seg_rows = (int)v;
       }
-      int first[QGCM_HIP_THOMAS_MAX_SEG], count[QGCM_HIP_THOMAS_MAX_SEG];
       if (qgcm_hip_thomas_segments(nrows, sg.seg_rows, &S, first, count)) return 1;
-      sg.first.assign(first, first + S);
-      sg.count.assign(count, count + S);
-      sg.maxlen = count[0];
     }
+    sg.first.assign(first, first + S);
+    sg.count.assign(count, count + S);
+    sg.maxlen = count[0];
     if (S != sg.S) { // (a second set_grid under another plan: the per-segment buffers are sized by S)
       HIPCHECK(hipStreamSynchronize(c->stream));
       sg.msg.reset();
       sg.coef.reset();
       sg.ab.reset();
-      for (auto &ss : sg.set) ss = {};
+      for (auto &ss : sg.set) { // (the pivot tables stay: upload_pivots grows them where the new plan needs more)
+        ss.recs.reset();
+        ss.ptab.reset();
+        ss.qtab.reset();
+        ss.cst.reset();
+        ss.meta.reset();
+      }
     }
     sg.set[1].boc.clear();
     sg.S = S;
-    c->thR = thomas_rows_per_chunk(S > 1 ? sg.maxlen : nrows);
-    sg.R = c->thR;
-    if (c->thR < 0) // (an ocean of that height has a segment plan: the atmosphere only)
+    sg.R = thomas_rows_per_chunk(sg.maxlen);
+    if (sg.R < 0) // (an ocean of that height has a segment plan: the atmosphere only)
       QG_FAIL("qgcm_hip_set_grid: %d rows of an atmosphere handle exceed the single-segment Thomas kernel (<= 2048); only ocean handles solve taller columns", nrows);
   }
   std::vector<std::vector<double>> bocs(g.nl, std::vector<double>(g.nk));
   for (int m = 0; m < g.nl; ++m)
     for (int k = 0; k < g.nk; ++k) bocs[m][k] = bd2oc[k] - c->prm.rdm2oc[m];
-  if (c->seg.S == 1) {
-    ThomasTabHost T;
-    for (int m = 0; m < g.nl; ++m) build_pivots(g, c->prm.aoc, bocs[m].data(), T);
-    if (upload_pivots(c, c->tt, T)) return 1;
-  }
   // FFT tables: complex length N = nxto (box DST-I of length nxto-1)
   const int N = g.nxt;
   c->fftN = N;
@@ -998,8 +967,8 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
 #undef QG_FFT3_SETUP
   }
   c->grid_set = true;
-  // slab summary constants (gain, backward image and column sums of the unit responses), once
-  if (c->seg.S > 1 ? build_segments(c, 0, bocs) : build_slab_responses(c)) return 1;
+  // the pivots, and the slab summary constants (gain, backward image and column sums of the unit responses), once
+  if (build_thomas_tables(c, 0, bocs)) return 1;
   {
     // weights of the spectral area integral (k_thomas.h): sum_{i=1}^{n-1} 2 sin(k i pi/n) = 2 cot(k pi/2n), k odd
     std::vector<double> wc((size_t)g.ldw, 0.0);
@@ -1647,43 +1616,59 @@ static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, i
   return 0;
 }
 
-// phase 0: whole column; 1: the slab's zero-inflow solution + its summary (send); 2: after the exchange - the inflows
-// composed from all ranks' summaries (gath) and their responses added (k_thomas_corr); 4 / 5: set-up (k_thomas.h)
-static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, int nlayers, int phase,
-                         const double *gath, double *send, int rank, int nranks, int layer0, hipStream_t st,
-                         bool cyc_part_a) {
-  if (!st) st = c->stream;
+// the response tables of set `which` as the three correction kernels read them: np, nq, poff, qoff are the quarters of meta
+static QgThomasCorr thomas_corr_tables(const qgcm_hip_ctx *c, int which) {
+  const auto &ss = c->seg.set[which];
+  const int nm = (c->g.nk + TH_KW - 1) / TH_KW * (which ? 1 : c->g.nl) * c->seg.S;
+  QgThomasCorr T;
+  T.ptab = ss.ptab; T.qtab = ss.qtab;
+  T.np = ss.meta; T.nq = ss.meta + nm; T.poff = ss.meta + 2 * nm; T.qoff = ss.meta + 3 * nm;
+  return T;
+}
+// slices (blockIdx.z) the correction kernels cut a slab or segment of nrows rows into
+static int thomas_corr_slices(int nrows) {
+  const int per = THC_UNR * (THC_NT / 8); // rows per slice
+  return (nrows + per - 1) / per;
+}
+// a correction kernel of this file with lds bytes for its ranks' or segments' inflows: more than 31 of them are beyond
+// the default dynamic-LDS limit of a launch
+static int thomas_corr_allow_lds(const void *kernel, size_t lds) {
+  if (lds > 32 * 1024) HIPCHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return 0;
+}
+
+// The solve of set `which` of diagonals (seg.set) over the whole work array.  phase 0: whole column; 1: the slab's
+// zero-inflow solution + its summary (slab.send); 2: after the exchange - the inflows composed from all ranks' summaries
+// (slab.gath) and their responses added (k_thomas_corr)
+static int launch_thomas(qgcm_hip_ctx *c, int which, int nlayers, int phase, const QgThomasSlabArgs &slab, bool cyc_part_a) {
+  hipStream_t st = c->stream;
   const QgGeom &g = c->g;
-  if (!tab.binf) QG_FAIL("k_thomas: the pivot tables have not been built (qgcm_hip_set_grid)");
+  const int nranks = slab.nranks;
+  if (!c->seg.set[which].tab.binf) QG_FAIL("k_thomas: the pivot tables have not been built (qgcm_hip_set_grid)");
   QgThomasParams P;
-  fill_thomas_params(c, P, wrk, tab, nlayers, layer0);
-  P.gath = gath; P.send = send; P.rank = rank; P.nranks = nranks;
+  fill_thomas_params(c, P, which, nlayers);
+  P.gath = slab.gath; P.send = slab.send; P.rank = slab.rank; P.nranks = nranks;
   if (phase == 2) {
     if (g.cyc) P.ybnd = c->ybnd;
-    c->slab_gath = gath; // (the cyclic constraint algebra reads the boundary line sums at the end of the step messages)
+    c->slab_gath = slab.gath; // (the cyclic constraint algebra reads the boundary line sums at the end of the step messages)
     c->slab_nranks = nranks;
     P.cgath = (nranks == 1) ? c->slabDE : c->th_cgath; // a lone slab is its own rank 0
     if (nranks > 1 && (!c->th_cgath || c->th_cgath_ranks != nranks))
       QG_FAIL("qgcm_hip_thomas_phase: the set-up constants of the %d slabs have not been exchanged (qgcm_hip_set_thomas_consts)", nranks);
   }
   if (c->seg.S > 1) {
-    if (phase == 1 || phase == 2) return launch_thomas_slab_seg(c, P, phase, nlayers, st);
+    if (phase == 1 || phase == 2) return launch_thomas_slab_seg(c, P, which, phase, nlayers, st);
     if (phase != 0 || !c->whole) QG_FAIL("k_thomas: phase %d on a column in %d segments", phase, c->seg.S);
     if (cyc_part_a) QG_FAIL("k_thomas: part A of the constraint algebra does not ride in the segmented solve");
-    return launch_thomas_seg(c, P, &tab == &c->tt ? 0 : 1, nlayers, st);
+    return launch_thomas_seg(c, P, which, nlayers, st);
   }
   if (phase == 2) {
-    if (&tab != &c->tt || !c->corr.meta) QG_FAIL("k_thomas_corr: the response tables belong to the modal solves of qgcm_hip_set_grid");
-    const int nm = P.nblk * g.nl;
-    QgThomasCorr T;
-    T.ptab = c->corr.ptab; T.qtab = c->corr.qtab;
-    T.np = c->corr.meta; T.nq = c->corr.meta + nm; T.poff = c->corr.meta + 2 * nm; T.qoff = c->corr.meta + 3 * nm;
+    if (which != 0 || !c->seg.set[0].meta) QG_FAIL("k_thomas_corr: the response tables belong to the modal solves of qgcm_hip_set_grid");
+    const QgThomasCorr T = thomas_corr_tables(c, 0);
     KTimer t(c, KN_THOMAS, st);
     const size_t lds = sizeof(double) * THC_LDS * nranks;
-    if (lds > 32 * 1024) // (more than 31 slabs: beyond the default dynamic-LDS limit of a launch)
-      HIPCHECK(hipFuncSetAttribute((const void *)k_thomas_corr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nrows = g.jr1 - g.jr0 + 1, per = THC_UNR * (THC_NT / 8); // rows per slice (blockIdx.z)
-    hipLaunchKernelGGL(k_thomas_corr, dim3(P.nblk, nlayers, (nrows + per - 1) / per), dim3(THC_NT), lds, st, P, T);
+    if (thomas_corr_allow_lds((const void *)k_thomas_corr, lds)) return 1;
+    hipLaunchKernelGGL(k_thomas_corr, dim3(P.nblk, nlayers, thomas_corr_slices(c->seg.maxlen)), dim3(THC_NT), lds, st, P, T);
     HIPCHECK(hipGetLastError());
     return 0;
   }
@@ -1696,11 +1681,11 @@ static int launch_thomas(qgcm_hip_ctx *c, double *wrk, const QgThomasTab &tab, i
   const bool cyca = (phase == 0 && g.cyc);
   if (cyc_part_a && (phase != 0 || !c->d_cycq || g.nl > 4)) QG_FAIL("k_thomas: part A of the constraint algebra needs the homogeneous solutions and nlo <= 4");
   if (cyca) P.cycq = cyc_part_a ? c->d_cycq : nullptr; // (its extra workgroup is added to the grid below)
-  return launch_thomas_rows(c, P, c->thR, phase, cyca, nlayers, st);
+  return launch_thomas_rows(c, P, phase, cyca, nlayers, st);
 }
 
-// the k_thomas instantiation of R rows per thread for the rows P.g.jr0 .. jr1
-static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, int phase, bool cyca, int nlayers, hipStream_t st) {
+// the k_thomas instantiation of the plan's rows per thread for the rows P.g.jr0 .. jr1; phases 4 / 5: set-up (k_thomas.h)
+static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int phase, bool cyca, int nlayers, hipStream_t st) {
   const QgGeom &g = c->g;
   KTimer t(c, KN_THOMAS, st);
 #define QG_TH(RV, KWV)                                                                                                  \
@@ -1719,7 +1704,7 @@ static int launch_thomas_rows(qgcm_hip_ctx *c, const QgThomasParams &P, int R, i
   // 8 .. 16 rows per thread: 512-thread workgroups of 8 wavenumbers, two per CU (128 VGPRs), the pair that shares the
   // 128-byte lines of a 16-wavenumber block on ONE XCD (k_thomas.h; r3: NAtl 5 km 10.6 -> 9.9 us against 1024-thread
   // workgroups); long columns (>= 20 rows per thread): 512 threads, 256 VGPRs
-  switch (R) {
+  switch (c->seg.R) {
     // (short columns too: 1024-thread workgroups of 16 wavenumbers measured slower everywhere - atmosphere 22.1 -> 21.3 us
     //  per step, 27.9 -> 26.3 on the two XCDs of a coupled run: profiles/r4_coupled_cu_masks.log)
 #define QG_TH_CASE(RV) case RV: QG_TH(RV, 8); break;
@@ -1764,14 +1749,11 @@ static int launch_thomas_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int 
   if (g.cyc && nlayers == g.nl) P.ybnd = c->ybnd;
   if (launch_thomas_seg_rows(c, P, ss.recs, nlayers, st)) return 1;
   {
-    const int nm = P.nblk * nlt * S;
-    QgThomasCorr T;
-    T.ptab = ss.ptab; T.qtab = ss.qtab;
-    T.np = ss.meta; T.nq = ss.meta + nm; T.poff = ss.meta + 2 * nm; T.qoff = ss.meta + 3 * nm;
+    const QgThomasCorr T = thomas_corr_tables(c, which);
     KTimer t(c, KN_THOMAS, st);
     const size_t lds = sizeof(double) * THC_LDS * S;
-    if (lds > 32 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_thomas_corr_seg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per = THC_UNR * (THC_NT / 8), nslice = (sg.maxlen + per - 1) / per; // rows per slice
+    if (thomas_corr_allow_lds((const void *)k_thomas_corr_seg, lds)) return 1;
+    const int nslice = thomas_corr_slices(sg.maxlen);
     hipLaunchKernelGGL(k_thomas_corr_seg, dim3(P.nblk, nlayers, S * nslice), dim3(THC_NT), lds, st, P, T, (const QgThomasSegRec *)ss.recs, nslice);
     HIPCHECK(hipGetLastError());
   }
@@ -1790,11 +1772,11 @@ static QgThomasFold thomas_fold_params(const qgcm_hip_ctx *c, double *send) {
   F.S = sg.S; F.nl = c->g.nl; F.ldw = c->g.ldw; F.nk = c->g.nk;
   return F;
 }
-static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int phase, int nlayers, hipStream_t st) {
+static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int which, int phase, int nlayers, hipStream_t st) {
   const QgGeom &g = c->g;
   const auto &sg = c->seg;
   const auto &ss = sg.set[0];
-  if (P.binf != c->tt.binf || nlayers != g.nl || P.layer0 != 0) QG_FAIL("qgcm_hip_thomas_phase: a column in segments folds all modal solves at once");
+  if (which != 0 || nlayers != g.nl) QG_FAIL("qgcm_hip_thomas_phase: a column in segments folds all modal solves at once");
   if (!ss.recs || !ss.meta || !sg.coef || !sg.ab) QG_FAIL("qgcm_hip_thomas_phase: the segments' tables have not been built (qgcm_hip_set_grid)");
   const QgThomasFold F = thomas_fold_params(c, P.send);
   if (phase == 1) {
@@ -1804,13 +1786,9 @@ static int launch_thomas_slab_seg(qgcm_hip_ctx *c, QgThomasParams &P, int phase,
     HIPCHECK(qg_launch_thomas_fold(false, st, F));
     return 0;
   }
-  const int nm = P.nblk * g.nl * sg.S;
-  QgThomasCorr T;
-  T.ptab = ss.ptab; T.qtab = ss.qtab;
-  T.np = ss.meta; T.nq = ss.meta + nm; T.poff = ss.meta + 2 * nm; T.qoff = ss.meta + 3 * nm;
+  const QgThomasCorr T = thomas_corr_tables(c, 0);
   KTimer t(c, KN_THOMAS, st);
-  const int per = THC_UNR * (THC_NT / 8), nslice = (sg.maxlen + per - 1) / per; // rows per slice
-  HIPCHECK(qg_launch_thomas_corr_slab(st, P, T, ss.recs, F, nslice, nlayers));
+  HIPCHECK(qg_launch_thomas_corr_slab(st, P, T, ss.recs, F, thomas_corr_slices(sg.maxlen), nlayers));
   return 0;
 }
 
@@ -2063,7 +2041,7 @@ static int ocinvq_impl(qgcm_hip_ctx *c, bool in_step = false, bool avg = false, 
   const QgStepPlan pl = step_plan(c, in_step);
   // (A per-mode side-stream variant of this chain was measured slower - 140 vs 116 us/step at 5 km - and removed.)
   if (!fwd_done && launch_dst(c, c->wrk, c->g.nl, false)) return 1; // (fwd_done: k_tend_rows has left the spectral rows in wrk)
-  if (launch_thomas(c, c->wrk, c->tt, c->g.nl, 0, nullptr, nullptr, 0, 1, 0, nullptr, pl.constr == CONSTR_AB)) return 1;
+  if (launch_thomas(c, 0, c->g.nl, 0, {}, pl.constr == CONSTR_AB)) return 1;
   // area (and, cyclic, line) integrals are a by-product of the y sweeps: the constraints precede the inverse transform
   if (pl.constr == CONSTR_OWN && launch_constr(c)) return 1;
   if (launch_inverse(c, pl, in_step, nullptr, nullptr, true, avg)) return 1; // (fuse_bdy = in_step)
@@ -3209,25 +3187,20 @@ extern "C" int qgcm_hip_helmholtz(qgcm_hip_handle c, double *wrk, const double *
   if (!c->whole) QG_FAIL("qgcm_hip_helmholtz: only for a handle that owns the whole domain");
   const QgGeom &g = c->g;
   // pivots for this boc (box: boc(i-1) multiplies sine wavenumber i-1, src/ocisubs.F:470-478)
-  if (c->seg.S > 1) {
-    // a column in segments: the responses of every segment for THIS diagonal too (the last one is kept)
-    auto &ss = c->seg.set[1];
-    if (ss.boc.size() != (size_t)g.nk || memcmp(ss.boc.data(), boc, sizeof(double) * g.nk)) {
-      ss.boc.clear();
-      if (build_segments(c, 1, {std::vector<double>(boc, boc + g.nk)})) return 1;
-      ss.boc.assign(boc, boc + g.nk);
-    }
-  } else {
-    ThomasTabHost T;
-    build_pivots(g, c->prm.aoc, boc, T);
-    if (upload_pivots(c, c->tt_tmp, T)) return 1;
+  // a column in segments builds the responses of every segment for THIS diagonal too: the last one's are kept
+  auto &ss = c->seg.set[1];
+  const bool kept = c->seg.S > 1 && ss.boc.size() == (size_t)g.nk && !memcmp(ss.boc.data(), boc, sizeof(double) * g.nk);
+  if (!kept) {
+    ss.boc.clear();
+    if (build_thomas_tables(c, 1, {std::vector<double>(boc, boc + g.nk)})) return 1;
+    ss.boc.assign(boc, boc + g.nk);
   }
   // box: interior columns i=2..nx-1 of every row -> wrk(c = i-2, j); cyclic: columns 1..nxto -> wrk(c = i-1, j)
   const int coff = g.cyc ? 0 : 1;
   HIPCHECK(hipMemcpy2DAsync(c->wrk, (size_t)g.ldw * 8, wrk + coff, (size_t)g.nx * 8, (size_t)g.nk * 8, (size_t)g.ny,
                             hipMemcpyHostToDevice, c->stream));
   if (launch_dst(c, c->wrk, 1, false)) return 1;
-  if (launch_thomas(c, c->wrk, c->tt_tmp, 1, 0, nullptr, nullptr, 0, 1, 0, nullptr)) return 1;
+  if (launch_thomas(c, 1, 1, 0)) return 1;
   if (launch_dst(c, c->wrk, 1, true)) return 1;
   HIPCHECK(hipMemcpy2DAsync(wrk + coff, (size_t)g.nx * 8, c->wrk, (size_t)g.ldw * 8, (size_t)g.nk * 8, (size_t)g.ny,
                             hipMemcpyDeviceToHost, c->stream));
@@ -3354,7 +3327,7 @@ extern "C" int qgcm_hip_thomas_phase(qgcm_hip_handle c, int phase, const double 
   if (phase < 1 || phase > 2) QG_FAIL("qgcm_hip_thomas_phase: phase must be 1 or 2");
   if ((phase == 1 && !send_dev) || (phase == 2 && !gath_dev)) QG_FAIL("qgcm_hip_thomas_phase: missing buffer");
   if (nranks > 64) QG_FAIL("qgcm_hip_thomas_phase: at most 64 slabs");
-  return launch_thomas(c, c->wrk, c->tt, c->g.nl, phase, gath_dev, send_dev, rank, nranks, 0, nullptr);
+  return launch_thomas(c, 0, c->g.nl, phase, {gath_dev, send_dev, rank, nranks});
 }
 
 extern "C" int qgcm_hip_constr(qgcm_hip_handle c) {

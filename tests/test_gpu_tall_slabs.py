@@ -13,7 +13,7 @@ import torch  # noqa: F401  (before the library: torch brings its own HIP runtim
 
 import test_gpu_areacfl as t_areacfl
 import test_gpu_monitors as t_mon
-from common import (FIELDS, GOLDEN, SNAPS, load_golden, make_oracle, preset, relerr, scal_err, state_errs)
+from common import (FIELDS, GOLDEN, SNAPS, load_golden, make_oracle, preset, relerr, same_bits, scal_err, state_errs)
 from qgcm_hip import AtmosModel, OceanModel, QgcmHipError, config, hostinit, lib, oml_preset, synth
 from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, global_consts, partition, rccl_unique_id, slab_slice
 from test_gpu_tall_columns import TOL_CALL, TOL_RUN, load_box, oracle_bsums, reference, tall_cfg
@@ -29,7 +29,8 @@ def interior_rows(cfg, g0, g1):
 
 
 def make_slabs(cfg, consts, parts, seg_rows=0, **kw):
-    """The slabs of `parts`, each asserted to be on the plan the rule gives for its rows - more than one segment."""
+    """The slabs of `parts`, each asserted to be on the plan the rule gives for its rows - more than one segment, but
+    for the one-segment ends of test_slab_tables_rebuilt_under_another_plan."""
     P = len(parts)
     slabs = []
     try:
@@ -398,6 +399,73 @@ def test_library_issued_exchanges_one_rank_in_segments(name, seg_rows, graph, mo
             assert np.array_equal(out[0][1], other[1])
     finally:
         close_all(slabs)
+        o.close()
+
+
+# 7b. one set of tables, rebuilt under another plan --------------------------------------------------------------------------
+def set_plan(monkeypatch, seg_rows):
+    if seg_rows:
+        monkeypatch.setenv(VAR, str(seg_rows))
+    else:
+        monkeypatch.delenv(VAR, raising=False)
+
+
+def set_grid_again(sl):
+    """qgcm_hip_set_grid once more with the arguments HipSlab's constructor gave it (the variable is read there)."""
+    from qgcm_hip.model import _dp
+    rows = slab_slice(sl.cfg.nypo, sl.g0, sl.g1)
+    yp = np.ascontiguousarray(sl.consts["yporel"][rows])
+    bd2 = np.ascontiguousarray(sl.consts["bd2oc"])
+    dd = np.asfortranarray(sl.consts["ddynoc"][:, rows])
+    lib.check(sl.L.qgcm_hip_set_grid(sl.h, _dp(yp), _dp(bd2), _dp(dd)))
+
+
+@pytest.mark.parametrize("plans", [(0, 7, 0), (7, 0, 7)])
+@pytest.mark.parametrize("name", ["box_tiny", "cyc_tiny"])
+def test_slab_tables_rebuilt_under_another_plan(name, plans, monkeypatch):
+    """A slab's one set of tables serves every plan: two slabs of the 37-row basins (18 / 17 interior rows) built under
+    plans[0] (0: the variable unset, one segment; 7: three segments each), then taken by qgcm_hip_set_grid to plans[1] and
+    back.  Only then are the set-up constants exchanged (SlabOcean); three steps from the golden state are bitwise -
+    fields and constraint scalars - those of fresh slabs that never left that plan.  Cyclic: ybnd comes from the
+    correction kernels' owner workgroup."""
+    cfg, g = preset(name), load_golden(name)
+    parts = partition(cfg.nypo, 2)
+    o = make_oracle(cfg)
+    consts = global_consts(cfg, None if cfg.cyclic else o.helmholtz)
+
+    def run(seq):
+        slabs = []
+        try:
+            set_plan(monkeypatch, seq[0])
+            slabs = make_slabs(cfg, consts, parts, seq[0])
+            for seg_rows in seq[1:]:
+                set_plan(monkeypatch, seg_rows)
+                for x, (g0, g1) in zip(slabs, parts):
+                    set_grid_again(x)
+                    assert x.thomas_plan() == lib.thomas_segments(interior_rows(cfg, g0, g1), seg_rows)
+            assert [len(x.thomas_plan()) for x in slabs] == [3 if seq[-1] else 1] * 2
+            so = slab_ocean(cfg, slabs)
+            po, pom = g["in_po"], g["in_pom"]
+            qo = hostinit.q_from_p(cfg, consts["amatoc"], consts["yporel"], consts["ddynoc"], po)
+            qom = hostinit.q_from_p(cfg, consts["amatoc"], consts["yporel"], consts["ddynoc"], pom)
+            so.scatter_state(po, pom, qo, qom, g["in_wekpo"], g["in_entoc"], g["in_xon"], hostinit.constr(cfg, consts["amatoc"], po, pom))
+            if cfg.cyclic:
+                for x in slabs:
+                    x.set_cyc_forcing(float(g["in_txis"]), float(g["in_txin"]), g["in_enis"], g["in_enin"])
+            so.steps(3, s0=1)
+            got = Gathered(so)
+            return got.get_state(), got.get_scalars()
+        finally:
+            close_all(slabs)
+
+    try:
+        moved, fresh = run(plans), run(plans[-1:])
+        assert all(np.isfinite(f).all() for f in fresh[0]) and np.isfinite(fresh[1]).all()
+        assert not np.array_equal(fresh[0][0], g["in_po"])
+        for f, x, y in zip(FIELDS, moved[0], fresh[0]):
+            same_bits(x, y, f)
+        same_bits(moved[1], fresh[1], "scalars")
+    finally:
         o.close()
 
 
