@@ -279,12 +279,7 @@ __device__ __forceinline__ void constr_cyc_partB(const QgCycConstrParams &P, int
 #pragma unroll
   for (int m = 1; m < NL; ++m) aipmod[m] = xin[m] + (c1[m - 1] + c2[m - 1]) * P.cs.aipcho[m - 1];
 #pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    double pl = 0.0;
-#pragma unroll
-    for (int m = 0; m < NL; ++m) pl = pl + P.ctm2l[m + NL * k] * aipmod[m];
-    aiplay[k] = pl;
-  }
+  for (int k = 0; k < NL; ++k) aiplay[k] = qg_modes_to_layer<NL>(P.ctm2l, k, aipmod);
   // ocisubs.F:268-294 / atisubs.F:232-257: the continuity monitors ermaso, emfroc (ermasa, emfrat) - the new integral
   // of the interface displacement against the one the entrainment predicts - then the step of dpioc / dpiocp
   const double ecrit = 1.0e-13; // ocisubs.F:93, atisubs.F:86
@@ -342,20 +337,15 @@ __global__ __launch_bounds__(256) void k_unpack_cyc(const QgUnpackParams P, cons
   auto point = [&](int jrow, double *pl) {
     const bool inner = (jrow + joff >= 2 && jrow + joff <= nyg - 1);
     double pm[NL];
-    pm[0] = (inner ? P.wrk[(long)(jrow - 1) * P.g.ldw + ci] : 0.0) + P.sc->c3 * P.pbh[jrow - 1];
+    pm[0] = (inner ? P.wrk[(long)(jrow - 1) * P.g.ldw + ci] : 0.0) + QG_HOM_CHANNEL0(P.sc->c3, P.pbh, jrow);
 #pragma unroll
     for (int m = 1; m < NL; ++m) {
       double wv = inner ? P.wrk[P.g.wstride * m + (long)(jrow - 1) * P.g.ldw + ci] : 0.0;
-      double homcor = P.sc->c1[m - 1] * P.pch1[(jrow - 1) + (long)ny * (m - 1)] + P.sc->c2[m - 1] * P.pch2[(jrow - 1) + (long)ny * (m - 1)];
+      double homcor = QG_HOM_CHANNEL(P.sc->c1, P.sc->c2, P.pch1, P.pch2, ny, jrow, m);
       pm[m] = wv + homcor;
     }
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      double v = 0.0;
-#pragma unroll
-      for (int m = 0; m < NL; ++m) v = v + P.ctm2l[m + NL * k] * pm[m];
-      pl[k] = v;
-    }
+    for (int k = 0; k < NL; ++k) pl[k] = qg_modes_to_layer<NL>(P.ctm2l, k, pm);
   };
   double pl[NL];
   point(gj, pl);
@@ -363,21 +353,21 @@ __global__ __launch_bounds__(256) void k_unpack_cyc(const QgUnpackParams P, cons
   for (int k = 0; k < NL; ++k) qg_pair_store_wt(P.pnew + P.g.fstride * k + o, pl[k], valid); // (qgcm_dev.h)
   if (!valid) return;
   const int G = gj + joff;
-  // y-slab halo messages (k_halo_pack's layout, k_misc.h), written here when the host passes the buffers (slab
+  // y-slab halo messages (QG_HALO_P / QG_HALO_Q, qg_ref_expr.h), written here when the host passes the buffers (slab
   // stage 2); an edge row with a neighbour is never a zonal boundary row, so its q is what k_tend set
   if (BDY && P.msg_lo && gj - P.g.jlo < 3) {
 #pragma unroll
-    for (int k = 0; k < NL; ++k) P.msg_lo[((long)k * 3 + (gj - P.g.jlo)) * P.g.ldx + (gi - 1)] = pl[k];
+    for (int k = 0; k < NL; ++k) P.msg_lo[QG_HALO_P(k, gj - P.g.jlo, P.g.ldx) + (gi - 1)] = pl[k];
     if (gj == P.g.jlo)
 #pragma unroll
-      for (int k = 0; k < NL; ++k) P.msg_lo[((long)NL * 3 + k) * P.g.ldx + (gi - 1)] = B.qo[P.g.fstride * k + o];
+      for (int k = 0; k < NL; ++k) P.msg_lo[QG_HALO_Q(NL, k, P.g.ldx) + (gi - 1)] = B.qo[P.g.fstride * k + o];
   }
   if (BDY && P.msg_hi && P.g.jhi - gj < 3) {
 #pragma unroll
-    for (int k = 0; k < NL; ++k) P.msg_hi[((long)k * 3 + (gj - (P.g.jhi - 2))) * P.g.ldx + (gi - 1)] = pl[k];
+    for (int k = 0; k < NL; ++k) P.msg_hi[QG_HALO_P(k, gj - (P.g.jhi - 2), P.g.ldx) + (gi - 1)] = pl[k];
     if (gj == P.g.jhi)
 #pragma unroll
-      for (int k = 0; k < NL; ++k) P.msg_hi[((long)NL * 3 + k) * P.g.ldx + (gi - 1)] = B.qo[P.g.fstride * k + o];
+      for (int k = 0; k < NL; ++k) P.msg_hi[QG_HALO_Q(NL, k, P.g.ldx) + (gi - 1)] = B.qo[P.g.fstride * k + o];
   }
   if (BDY && (G == 1 || G == nyg)) {
     double pin[NL];
@@ -385,14 +375,10 @@ __global__ __launch_bounds__(256) void k_unpack_cyc(const QgUnpackParams P, cons
     const double by = B.beta * B.yporel[gj - 1];
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
-      double ap;
-      if (k == 0) ap = B.f0A[0] * pl[0] + B.f0A[NL] * pl[1];
-      else if (k == NL - 1) ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pl[k];
-      else ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pl[k] + B.f0A[k + NL * (k + 1)] * pl[k + 1];
-      if (P.g.atm && k == NL - 1 && G == 1) // southern value of the top layer: src/vorsubs.F:470 reads row 2
-        ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pin[k];
-      double q = B.bcfaco_f0 * (pin[k] - pl[k]) - ap + by;
-      if (k == (P.g.atm ? 0 : NL - 1)) q = q + B.ddynoc[o]; // topography: ocean bottom layer nlo, atmosphere layer 1
+      double ap = QG_AP(B.f0A, NL, k, pl[k - 1], pl[k], pl[k + 1]);
+      if (P.g.atm && k == NL - 1 && G == 1) ap = QG_AP_ATQZBD(B.f0A, NL, k, pl[k - 1], pin[k]);
+      double q = qg_bdy_q(B.bcfaco_f0, pin[k], pl[k], ap, by);
+      if (k == QG_TOPO_LAYER(P.g.atm, NL)) q = q + B.ddynoc[o];
       B.qo[P.g.fstride * k + o] = q;
     }
   }

@@ -475,22 +475,22 @@ __global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_dst64_unpack(Q
   const int nx = U.g.nx, nyg = U.g.nyg, joff = U.g.joff;
   constexpr int NX = N + 1;
   double hc[NL];
-  // y-slab halo messages (k_halo_pack's layout: [k][3 rows][ldx] of p, then [k][ldx] of q): the first / last three
+  // y-slab halo messages (QG_HALO_P / QG_HALO_Q, qg_ref_expr.h: [k][3 rows][ldx] of p, then [k][ldx] of q): the first / last three
   // owned rows go to the lower / upper neighbour straight from here (no separate pack launch)
   const int jlo = U.g.jlo, jhi = U.g.jhi, ldxm = U.g.ldx;
   auto msg_p = [&](int gi, int gj, const double *pl) {
     if (HALO && U.msg_lo && gj - jlo < 3) {
 #pragma unroll
-      for (int k = 0; k < NL; ++k) U.msg_lo[((long)k * 3 + (gj - jlo)) * ldxm + (gi - 1)] = pl[k];
+      for (int k = 0; k < NL; ++k) U.msg_lo[QG_HALO_P(k, gj - jlo, ldxm) + (gi - 1)] = pl[k];
     }
     if (HALO && U.msg_hi && jhi - gj < 3) {
 #pragma unroll
-      for (int k = 0; k < NL; ++k) U.msg_hi[((long)k * 3 + (gj - (jhi - 2))) * ldxm + (gi - 1)] = pl[k];
+      for (int k = 0; k < NL; ++k) U.msg_hi[QG_HALO_P(k, gj - (jhi - 2), ldxm) + (gi - 1)] = pl[k];
     }
   };
   auto msg_q = [&](int gi, int gj, int k, double q) {
-    if (HALO && U.msg_lo && gj == jlo) U.msg_lo[((long)NL * 3 + k) * ldxm + (gi - 1)] = q;
-    if (HALO && U.msg_hi && gj == jhi) U.msg_hi[((long)NL * 3 + k) * ldxm + (gi - 1)] = q;
+    if (HALO && U.msg_lo && gj == jlo) U.msg_lo[QG_HALO_Q(NL, k, ldxm) + (gi - 1)] = q;
+    if (HALO && U.msg_hi && gj == jhi) U.msg_hi[QG_HALO_Q(NL, k, ldxm) + (gi - 1)] = q;
   };
   // fused leapfrog averaging: the value stored for the new po at field offset idx
   auto avg_p = [&](long idx, double v) { return AVG ? 0.5 * (v + U.pavg[idx]) : v; };
@@ -504,26 +504,18 @@ __global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_dst64_unpack(Q
 #pragma unroll
     for (int m = 0; m < NL; ++m) {
       const double wvv = inner ? reinterpret_cast<const double *>(Fsh[m])[ip] : 0.0;
-      pm[m] = (m == 0) ? wvv : wvv + hc[m] * (ocv ? ocv[m - 1] : U.ochom[fs * (m - 1) + o]);
+      pm[m] = (m == 0) ? wvv : qg_hom_box(wvv, hc[m], ocv ? ocv[m - 1] : U.ochom[fs * (m - 1) + o]);
     }
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      double v = 0.0;
-#pragma unroll
-      for (int m = 0; m < NL; ++m) v = v + U.ctm2l[m + NL * k] * pm[m];
-      pl[k] = v;
-    }
+    for (int k = 0; k < NL; ++k) pl[k] = qg_modes_to_layer<NL>(U.ctm2l, k, pm);
   };
   // boundary PV of one wall point (k_unpack_box / k_ocqbdy): by = beta*yporel(j), dd = ddynoc(i,j)
   auto bdy_q = [&](long o, const double *pl, const double *pin, double by, double dd, int gi, int gj) {
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
-      double ap;
-      if (k == 0) ap = B.f0A[0] * pl[0] + B.f0A[NL] * pl[1];
-      else if (k == NL - 1) ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pl[k];
-      else ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pl[k] + B.f0A[k + NL * (k + 1)] * pl[k + 1];
-      double q = B.bcfaco_f0 * (pin[k] - pl[k]) - ap + by;
-      if (k == NL - 1) q = q + dd;
+      const double ap = QG_AP(B.f0A, NL, k, pl[k - 1], pl[k], pl[k + 1]);
+      double q = qg_bdy_q(B.bcfaco_f0, pin[k], pl[k], ap, by);
+      if (k == QG_TOPO_LAYER(false, NL)) q = q + dd; // (a box is an ocean)
       if (AVG) q = 0.5 * (q + U.qavg[fs * k + o]);
       B.qo[fs * k + o] = q;
       msg_q(gi, gj, k, q);

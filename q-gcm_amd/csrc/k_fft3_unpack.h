@@ -13,6 +13,7 @@
 // reference within the same tolerances as before.
 #pragma once
 #include "k_fft3.h"
+#include "qg_ref_expr.h"
 
 // blockIdx.x -> (row pair, layer): ids x, x + 8, x + 16 ... run on the same XCD one after another
 __device__ __forceinline__ bool fft3u_block(int id, int nl, int nrp, int &rp, int &kl) {
@@ -30,9 +31,9 @@ __device__ __forceinline__ double fft3u_bdy_q(const QgBdyParams &B, int kl, cons
 #pragma unroll
   for (int l = 0; l < NL; ++l) {
     if (l == kl) plk = pl[l];
-    if (l >= kl - 1 && l <= kl + 1) ap = ap + B.f0A[kl + NL * l] * pl[l];
+    if (l >= kl - 1 && l <= kl + 1) ap = ap + QG_AP_TERM(B.f0A, NL, kl, l, pl[l]);
   }
-  return B.bcfaco_f0 * (pin - plk) - ap + by;
+  return qg_bdy_q(B.bcfaco_f0, pin, plk, ap, by);
 }
 
 // ---------------------------------------------------------------------------
@@ -81,15 +82,14 @@ __global__ __launch_bounds__(NT) void k_rfft3_unpack(const QgDstParams D, const 
   }
   // sum_m ctm2l(m, l) * (homogeneous part of mode m on local row j)
   auto homrow = [&](int j, int l) -> double {
-    double v = U.ctm2l[NL * l] * (c3 * U.pbh[j - 1]);
+    double v = QG_M2L_TERM(U.ctm2l, NL, 0, l, QG_HOM_CHANNEL0(c3, U.pbh, j));
 #pragma unroll
-    for (int m = 1; m < NL; ++m)
-      v = v + U.ctm2l[m + NL * l] * (c1[m - 1] * U.pch1[(j - 1) + (long)ny * (m - 1)] + c2[m - 1] * U.pch2[(j - 1) + (long)ny * (m - 1)]);
+    for (int m = 1; m < NL; ++m) v = v + QG_M2L_TERM(U.ctm2l, NL, m, l, QG_HOM_CHANNEL(c1, c2, U.pch1, U.pch2, ny, j, m));
     return v;
   };
   double cm[NL];
 #pragma unroll
-  for (int m = 0; m < NL; ++m) cm[m] = U.ctm2l[m + NL * kl];
+  for (int m = 0; m < NL; ++m) cm[m] = QG_CTM2L(U.ctm2l, NL, m, kl);
   const double ha = homrow(ja, kl), hb = homrow(has_b ? ja + 1 : ja, kl);
 
   // ---- the NL spectral rows of the pair, mixed on their way into LDS (half-complex rows -> conj(Z), as k_rfft_cyc) --
@@ -174,19 +174,19 @@ __global__ __launch_bounds__(NT) void k_rfft3_unpack(const QgDstParams D, const 
       hNk = hN[l];
     }
   }
-  const bool topo = kl == NL - 1; // topography term: bottom layer nlo
+  const bool topo = kl == QG_TOPO_LAYER(false, NL); // topography term (an ocean: bottom layer nlo)
   const double byS = doS ? B.beta * B.yporel[jS - 1] : 0.0, byN = doN ? B.beta * B.yporel[jN - 1] : 0.0;
-  // halo messages (k_halo_pack's layout): p rows gj - jlo < 3 / jhi - gj < 3, q row gj == jlo / jhi (set by k_tend)
+  // halo messages (QG_HALO_P / QG_HALO_Q, qg_ref_expr.h): p rows gj - jlo < 3 / jhi - gj < 3, q row gj == jlo / jhi (set by k_tend)
   auto msg_p = [&](int gj, int col, double v) {
-    if (U.msg_lo && gj - jlo < 3) U.msg_lo[((long)kl * 3 + (gj - jlo)) * ldx + col] = v;
-    if (U.msg_hi && jhi - gj < 3) U.msg_hi[((long)kl * 3 + (gj - (jhi - 2))) * ldx + col] = v;
+    if (U.msg_lo && gj - jlo < 3) U.msg_lo[QG_HALO_P(kl, gj - jlo, ldx) + col] = v;
+    if (U.msg_hi && jhi - gj < 3) U.msg_hi[QG_HALO_P(kl, gj - (jhi - 2), ldx) + col] = v;
   };
   auto msg_q = [&](int gj, int col) {
     const bool lo = U.msg_lo && gj == jlo, hi = U.msg_hi && gj == jhi;
     if (lo || hi) {
       const double q = B.qo[fs * kl + (long)(gj - 1) * ldx + col];
-      if (lo) U.msg_lo[((long)NL * 3 + kl) * ldx + col] = q;
-      if (hi) U.msg_hi[((long)NL * 3 + kl) * ldx + col] = q;
+      if (lo) U.msg_lo[QG_HALO_Q(NL, kl, ldx) + col] = q;
+      if (hi) U.msg_hi[QG_HALO_Q(NL, kl, ldx) + col] = q;
     }
   };
   // one column of a boundary row: its pressure is the row constant, its PV follows from the inward neighbour pin
@@ -233,8 +233,8 @@ __global__ __launch_bounds__(NT) void k_rfft3_unpack(const QgDstParams D, const 
     const bool mq_a = (U.msg_lo && ja == jlo) || (U.msg_hi && ja == jhi);
     const bool mq_b = has_b && ((U.msg_lo && ja + 1 == jlo) || (U.msg_hi && ja + 1 == jhi));
     auto msg_qv = [&](int gj, int col, double q) {
-      if (U.msg_lo && gj == jlo) U.msg_lo[((long)NL * 3 + kl) * ldx + col] = q;
-      if (U.msg_hi && gj == jhi) U.msg_hi[((long)NL * 3 + kl) * ldx + col] = q;
+      if (U.msg_lo && gj == jlo) U.msg_lo[QG_HALO_Q(NL, kl, ldx) + col] = q;
+      if (U.msg_hi && gj == jhi) U.msg_hi[QG_HALO_Q(NL, kl, ldx) + col] = q;
     };
     constexpr int CHK = 3; // rounds per batch of requests (all NST at once would not fit the registers)
 #pragma unroll

@@ -1,6 +1,7 @@
 // k_misc.h - constraint solve, mode->layer unpack, boundary PV, LF averaging.
 #pragma once
 #include "qgcm_dev.h"
+#include "qg_ref_expr.h" // the inversion epilogue, the halo-message layout
 
 #define CS_NT 256
 
@@ -218,15 +219,10 @@ __device__ __forceinline__ void unpack_point(const QgUnpackParams &P, int gi, in
 #pragma unroll
   for (int m = 1; m < NL; ++m) {
     double wv = inner ? P.wrk[P.g.wstride * m + ow] : 0.0;
-    pm[m] = wv + P.sc->hclco[m - 1] * P.ochom[P.g.fstride * (m - 1) + o];
+    pm[m] = qg_hom_box(wv, P.sc->hclco[m - 1], P.ochom[P.g.fstride * (m - 1) + o]);
   }
 #pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    double v = 0.0;
-#pragma unroll
-    for (int m = 0; m < NL; ++m) v = v + P.ctm2l[m + NL * k] * pm[m];
-    pl[k] = v;
-  }
+  for (int k = 0; k < NL; ++k) pl[k] = qg_modes_to_layer<NL>(P.ctm2l, k, pm);
 }
 
 // BDY = true additionally writes the boundary PV of the new pressure (ocqbdy,
@@ -247,16 +243,16 @@ __global__ __launch_bounds__(256) void k_unpack_box(const QgUnpackParams P, cons
 #pragma unroll
   for (int k = 0; k < NL; ++k) qg_pair_store_wt(P.pnew + P.g.fstride * k + o, pl[k], valid); // (qgcm_dev.h)
   if (!valid) return;
-  // y-slab halo messages (k_halo_pack's layout), written here when the host passes the buffers (slab stage 2): the
+  // y-slab halo messages (QG_HALO_P / QG_HALO_Q, qg_ref_expr.h), written here when the host passes the buffers (slab stage 2): the
   // first / last three owned rows of the new pressure, and below the edge row of q
   const bool qlo = BDY && P.msg_lo && gj == P.g.jlo, qhi = BDY && P.msg_hi && gj == P.g.jhi;
   if (BDY && P.msg_lo && gj - P.g.jlo < 3) {
 #pragma unroll
-    for (int k = 0; k < NL; ++k) P.msg_lo[((long)k * 3 + (gj - P.g.jlo)) * P.g.ldx + (gi - 1)] = pl[k];
+    for (int k = 0; k < NL; ++k) P.msg_lo[QG_HALO_P(k, gj - P.g.jlo, P.g.ldx) + (gi - 1)] = pl[k];
   }
   if (BDY && P.msg_hi && P.g.jhi - gj < 3) {
 #pragma unroll
-    for (int k = 0; k < NL; ++k) P.msg_hi[((long)k * 3 + (gj - (P.g.jhi - 2))) * P.g.ldx + (gi - 1)] = pl[k];
+    for (int k = 0; k < NL; ++k) P.msg_hi[QG_HALO_P(k, gj - (P.g.jhi - 2), P.g.ldx) + (gi - 1)] = pl[k];
   }
   if (BDY) {
     const bool ns = (G == 1 || G == nyg);
@@ -265,8 +261,8 @@ __global__ __launch_bounds__(256) void k_unpack_box(const QgUnpackParams P, cons
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
         const double q = B.qo[P.g.fstride * k + o];
-        if (qlo) P.msg_lo[((long)NL * 3 + k) * P.g.ldx + (gi - 1)] = q;
-        if (qhi) P.msg_hi[((long)NL * 3 + k) * P.g.ldx + (gi - 1)] = q;
+        if (qlo) P.msg_lo[QG_HALO_Q(NL, k, P.g.ldx) + (gi - 1)] = q;
+        if (qhi) P.msg_hi[QG_HALO_Q(NL, k, P.g.ldx) + (gi - 1)] = q;
       }
     }
     if (ns || we) {
@@ -277,15 +273,12 @@ __global__ __launch_bounds__(256) void k_unpack_box(const QgUnpackParams P, cons
       const double by = B.beta * B.yporel[gj - 1];
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
-        double ap;
-        if (k == 0) ap = B.f0A[0] * pl[0] + B.f0A[NL] * pl[1];
-        else if (k == NL - 1) ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pl[k];
-        else ap = B.f0A[k + NL * (k - 1)] * pl[k - 1] + B.f0A[k + NL * k] * pl[k] + B.f0A[k + NL * (k + 1)] * pl[k + 1];
-        double q = B.bcfaco_f0 * (pin[k] - pl[k]) - ap + by;
-        if (k == NL - 1) q = q + B.ddynoc[o];
+        const double ap = QG_AP(B.f0A, NL, k, pl[k - 1], pl[k], pl[k + 1]);
+        double q = qg_bdy_q(B.bcfaco_f0, pin[k], pl[k], ap, by);
+        if (k == QG_TOPO_LAYER(false, NL)) q = q + B.ddynoc[o]; // (a box is an ocean)
         B.qo[P.g.fstride * k + o] = q;
-        if (qlo) P.msg_lo[((long)NL * 3 + k) * P.g.ldx + (gi - 1)] = q;
-        if (qhi) P.msg_hi[((long)NL * 3 + k) * P.g.ldx + (gi - 1)] = q;
+        if (qlo) P.msg_lo[QG_HALO_Q(NL, k, P.g.ldx) + (gi - 1)] = q;
+        if (qhi) P.msg_hi[QG_HALO_Q(NL, k, P.g.ldx) + (gi - 1)] = q;
       }
     }
   }
@@ -322,14 +315,10 @@ __global__ __launch_bounds__(256) void k_ocqbdy(const QgBdyParams P) {
   const long oi = (long)(jj - 1) * ldx + (ii - 1);
   const double *po = P.po;
   double pb = po[fs * k + ob];
-  double ap;
-  if (k == 0) ap = P.f0A[0 + nl * 0] * pb + P.f0A[0 + nl * 1] * po[fs * 1 + ob];
-  else if (k == nl - 1) ap = P.f0A[k + nl * (k - 1)] * po[fs * (k - 1) + ob] + P.f0A[k + nl * k] * pb;
-  else ap = P.f0A[k + nl * (k - 1)] * po[fs * (k - 1) + ob] + P.f0A[k + nl * k] * pb + P.f0A[k + nl * (k + 1)] * po[fs * (k + 1) + ob];
-  if (P.g.atm && k == nl - 1 && side == 0) // atqzbd, southern value of the top layer: src/vorsubs.F:470 reads row 2
-    ap = P.f0A[k + nl * (k - 1)] * po[fs * (k - 1) + ob] + P.f0A[k + nl * k] * po[fs * k + oi];
-  double q = P.bcfaco_f0 * (po[fs * k + oi] - pb) - ap + P.beta * P.yporel[gj - 1];
-  if (k == (P.g.atm ? 0 : nl - 1)) q = q + P.ddynoc[ob]; // topography: ocean layer nlo, atmosphere layer 1
+  double ap = QG_AP(P.f0A, nl, k, po[fs * (k - 1) + ob], pb, po[fs * (k + 1) + ob]);
+  if (P.g.atm && k == nl - 1 && side == 0) ap = QG_AP_ATQZBD(P.f0A, nl, k, po[fs * (k - 1) + ob], po[fs * k + oi]);
+  double q = qg_bdy_q(P.bcfaco_f0, po[fs * k + oi], pb, ap, P.beta * P.yporel[gj - 1]);
+  if (k == QG_TOPO_LAYER(P.g.atm, nl)) q = q + P.ddynoc[ob];
   P.qo[fs * k + ob] = q;
 }
 
@@ -367,7 +356,7 @@ __global__ void k_lf_average_scalars(QgScalars *sc, int nl, int cyc) {
 
 // ---------------------------------------------------------------------------
 // y-slab halo messages: 3 rows of po and 1 row of qo per layer and direction.
-// message = [k][3 rows][ldx] of p, then [k][ldx] of q.   grid: (ceil(ldx/256), 4*nl, 2)
+// message = [k][3 rows][ldx] of p, then [k][ldx] of q (QG_HALO_P / QG_HALO_Q, qg_ref_expr.h).   grid: (ceil(ldx/256), 4*nl, 2)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_halo_pack(QgGeom g, const double *po, const double *qo, double *to_lower,
                                                    double *to_upper) {
@@ -379,10 +368,10 @@ __global__ __launch_bounds__(256) void k_halo_pack(QgGeom g, const double *po, c
   if (!msg) return;
   if (rr < 3) {
     const int j = dir == 0 ? g.jlo + rr : g.jhi - 2 + rr;
-    msg[((long)k * 3 + rr) * g.ldx + i] = po[g.fstride * k + (long)(j - 1) * g.ldx + i];
+    msg[QG_HALO_P(k, rr, g.ldx) + i] = po[g.fstride * k + (long)(j - 1) * g.ldx + i];
   } else {
     const int j = dir == 0 ? g.jlo : g.jhi;
-    msg[((long)g.nl * 3 + k) * g.ldx + i] = qo[g.fstride * k + (long)(j - 1) * g.ldx + i];
+    msg[QG_HALO_Q(g.nl, k, g.ldx) + i] = qo[g.fstride * k + (long)(j - 1) * g.ldx + i];
   }
 }
 
@@ -396,10 +385,10 @@ __global__ __launch_bounds__(256) void k_halo_unpack(QgGeom g, double *po, doubl
   if (!msg) return;
   if (rr < 3) {
     const int j = dir == 0 ? g.jlo - 3 + rr : g.jhi + 1 + rr;
-    po[g.fstride * k + (long)(j - 1) * g.ldx + i] = msg[((long)k * 3 + rr) * g.ldx + i];
+    po[g.fstride * k + (long)(j - 1) * g.ldx + i] = msg[QG_HALO_P(k, rr, g.ldx) + i];
   } else {
     const int j = dir == 0 ? g.jlo - 1 : g.jhi + 1;
-    qo[g.fstride * k + (long)(j - 1) * g.ldx + i] = msg[((long)g.nl * 3 + k) * g.ldx + i];
+    qo[g.fstride * k + (long)(j - 1) * g.ldx + i] = msg[QG_HALO_Q(g.nl, k, g.ldx) + i];
   }
 }
 

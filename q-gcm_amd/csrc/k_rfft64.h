@@ -273,17 +273,11 @@ __global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_rfft64_unpack(
         const cplx z = Fsh[m][zloc64<M>(ci)];
         wvv = sel ? -z.y : z.x;
       }
-      const double homcor = (m == 0) ? c3 * U.pbh[jrow - 1]
-                                     : c1[m - 1] * U.pch1[(jrow - 1) + (long)ny * (m - 1)] + c2[m - 1] * U.pch2[(jrow - 1) + (long)ny * (m - 1)];
+      const double homcor = (m == 0) ? QG_HOM_CHANNEL0(c3, U.pbh, jrow) : QG_HOM_CHANNEL(c1, c2, U.pch1, U.pch2, ny, jrow, m);
       pm[m] = wvv + homcor;
     }
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      double v = 0.0;
-#pragma unroll
-      for (int m = 0; m < NL; ++m) v = v + U.ctm2l[m + NL * k] * pm[m];
-      pl[k] = v;
-    }
+    for (int k = 0; k < NL; ++k) pl[k] = qg_modes_to_layer<NL>(U.ctm2l, k, pm);
   };
   constexpr int NT = 64 * NL;
 #pragma unroll
@@ -324,14 +318,10 @@ __global__ __launch_bounds__(64 * (NL + (CONSTR ? 1 : 0))) void k_rfft64_unpack(
         const double by = B.beta * B.yporel[wall - 1];
 #pragma unroll
         for (int k = 0; k < NL; ++k) {
-          double ap;
-          if (k == 0) ap = B.f0A[0] * pw[0] + B.f0A[NL] * pw[1];
-          else if (k == NL - 1) ap = B.f0A[k + NL * (k - 1)] * pw[k - 1] + B.f0A[k + NL * k] * pw[k];
-          else ap = B.f0A[k + NL * (k - 1)] * pw[k - 1] + B.f0A[k + NL * k] * pw[k] + B.f0A[k + NL * (k + 1)] * pw[k + 1];
-          if (U.g.atm && k == NL - 1 && wall == 1) // southern value of the top layer: src/vorsubs.F:470 reads row 2
-            ap = B.f0A[k + NL * (k - 1)] * pw[k - 1] + B.f0A[k + NL * k] * pin[k];
-          double q = B.bcfaco_f0 * (pin[k] - pw[k]) - ap + by;
-          if (k == (U.g.atm ? 0 : NL - 1)) q = q + ddw[it]; // topography: ocean layer nlo, atmosphere layer 1
+          double ap = QG_AP(B.f0A, NL, k, pw[k - 1], pw[k], pw[k + 1]);
+          if (U.g.atm && k == NL - 1 && wall == 1) ap = QG_AP_ATQZBD(B.f0A, NL, k, pw[k - 1], pin[k]);
+          double q = qg_bdy_q(B.bcfaco_f0, pin[k], pw[k], ap, by);
+          if (k == QG_TOPO_LAYER(U.g.atm, NL)) q = q + ddw[it];
           B.qo[fs * k + ow] = q;
         }
       }

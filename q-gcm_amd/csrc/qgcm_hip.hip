@@ -659,7 +659,7 @@ static inline size_t slab_msg_len(const QgGeom &g) {
 static inline size_t slab_msg_len_oml(const qgcm_hip_ctx *c) { return slab_msg_len(c->g) + (c->oml.on ? 3 : 0); }
 // halo message per direction: 3 rows of po + 1 row of qo per layer, + 3 rows of the new sst with the mixed layer on
 static inline size_t halo_msg_len(const qgcm_hip_ctx *c) {
-  return (size_t)4 * c->g.nl * c->g.ldx + (c->oml.on ? (size_t)3 * c->oml.ldt : 0);
+  return QG_HALO_LEN(c->g.nl, c->g.ldx) + (c->oml.on ? (size_t)3 * c->oml.ldt : 0); // (qg_ref_expr.h: the kernels' layout)
 }
 
 // Thomas pivots, exactly the recurrence of src/ocisubs.F:472-477 (box) / 577-582 (cyclic), run once on the host.
@@ -1830,11 +1830,14 @@ static void fill_bdy_params(qgcm_hip_ctx *c, QgBdyParams &P) {
     for (int l = 0; l < g.nl; ++l) P.f0A[k + g.nl * l] = pr.fnot * pr.amatoc[k + g.nl * l];
 }
 
-// what the unpack kernels read, stand-alone or fused with the inverse rows.  msg_lo / msg_hi: the y-slab halo messages
-// written by the same threads (the slab's solve and unpack).  avg: an averaging step of one_step, the launch stores the
-// averaged level; avg_ok: this launch is the fused whole-domain kernel that can (`who` names it otherwise)
-static int fill_unpack_params(qgcm_hip_ctx *c, QgUnpackParams &P, double *msg_lo, double *msg_hi, const char *who, bool avg, bool avg_ok) {
+// The kernel arguments of the four unpack launchers below, filled once: D for the row kernels (null: the stand-alone
+// unpack), P for the unpack kernels, B for the boundary PV (B.qo = current qo; B.po unused by the fused kernels).  msg_lo /
+// msg_hi: the y-slab halo messages written by the same threads (the slab's solve and unpack).  avg: an averaging step of
+// one_step, the launch stores the averaged level; avg_ok: this launch is the fused whole-domain kernel that can (`who` names it otherwise)
+static int fill_inv_args(qgcm_hip_ctx *c, QgDstParams *D, QgUnpackParams &P, QgBdyParams &B, double *msg_lo, double *msg_hi, const char *who, bool avg, bool avg_ok) {
   const QgGeom &g = c->g;
+  if (D) fill_dst_params(c, *D, c->wrk, g.nl, 0);
+  fill_bdy_params(c, B);
   memset(&P, 0, sizeof(P));
   P.g = g;
   P.wrk = c->wrk;
@@ -1857,9 +1860,8 @@ static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullpt
   const QgGeom &g = c->g;
   if ((msg_lo || msg_hi) && (!fuse_bdy || g.jhi - g.jlo + 1 < 3)) QG_FAIL("k_unpack: halo messages need the fused boundary PV and three owned rows");
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_unpack", avg, false)) return 1;
   QgBdyParams B;
-  fill_bdy_params(c, B); // B.qo = current qo; B.po unused by the fused kernel
+  if (fill_inv_args(c, nullptr, P, B, msg_lo, msg_hi, "k_unpack", avg, false)) return 1;
   dim3 grid((g.nx + 255) / 256, g.jhi - g.jlo + 1);
   KTimer t(c, KN_UNPACK);
 #define QG_UNPACK(NLV)                                                                                   \
@@ -1878,11 +1880,9 @@ static int launch_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nullpt
 static int launch_rfft_unpack(qgcm_hip_ctx *c, bool fuse_bdy, bool constr, bool avg = false) {
   const QgGeom &g = c->g;
   QgDstParams D;
-  fill_dst_params(c, D, c->wrk, g.nl, 0);
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, nullptr, nullptr, "k_rfft64_unpack", avg, false)) return 1;
   QgBdyParams B;
-  fill_bdy_params(c, B);
+  if (fill_inv_args(c, &D, P, B, nullptr, nullptr, "k_rfft64_unpack", avg, false)) return 1;
   if (constr && !c->d_cycq) QG_FAIL("k_rfft64_unpack: homogeneous solutions not set");
   QgCycConstrParams Qv; // by value: kernel arguments (k_rfft64.h)
   fill_cyc_constr_params(c, Qv);
@@ -1920,11 +1920,9 @@ static int launch_fft3_unpack(qgcm_hip_ctx *c, bool own_constr, double *msg_lo =
   if (!can_fuse_fft3_unpack(c)) QG_FAIL("k_fft3_unpack: not a long-row configuration of three layers");
   if ((msg_lo || msg_hi) && g.jhi - g.jlo + 1 < 3) QG_FAIL("k_fft3_unpack: halo messages need three owned rows");
   QgDstParams D;
-  fill_dst_params(c, D, c->wrk, g.nl, 0);
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_rfft3_unpack", avg, own_constr)) return 1;
   QgBdyParams B;
-  fill_bdy_params(c, B);
+  if (fill_inv_args(c, &D, P, B, msg_lo, msg_hi, "k_rfft3_unpack", avg, own_constr)) return 1;
   const int npairs = (g.jr1 - g.jr0 + 2) / 2;
   dim3 grid(8 * ((npairs + 7) / 8) * g.nl);
   KTimer t(c, KN_DSTI);
@@ -1948,11 +1946,9 @@ static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nu
                              bool constr = false, bool avg = false) {
   const QgGeom &g = c->g;
   QgDstParams D;
-  fill_dst_params(c, D, c->wrk, g.nl, 0);
   QgUnpackParams P;
-  if (fill_unpack_params(c, P, msg_lo, msg_hi, "k_dst64_unpack", avg, fuse_bdy && constr)) return 1;
   QgBdyParams B;
-  fill_bdy_params(c, B);
+  if (fill_inv_args(c, &D, P, B, msg_lo, msg_hi, "k_dst64_unpack", avg, fuse_bdy && constr)) return 1;
   QgConstrLite C;
   fill_constr_lite(c, C);
   const int nrows = g.jr1 - g.jr0 + 1;
@@ -1982,16 +1978,22 @@ static int launch_dst_unpack(qgcm_hip_ctx *c, bool fuse_bdy, double *msg_lo = nu
   return 0;
 }
 
-static int launch_ocqbdy(qgcm_hip_ctx *c) {
+// the boundary PV of pressure po into qo, device fields of the handle's shape (of the epilogue's arguments, B alone)
+static int launch_ocqbdy_on(qgcm_hip_ctx *c, const double *po, double *qo) {
   const QgGeom &g = c->g;
   QgBdyParams P;
   fill_bdy_params(c, P);
+  P.po = po; P.qo = qo;
   const int nmax = g.nx > g.ny ? g.nx : g.ny;
   dim3 grid((nmax + 255) / 256, g.cyc ? 2 : 4, g.nl);
-  KTimer t(c, KN_OCQBDY);
   hipLaunchKernelGGL(k_ocqbdy, grid, dim3(256), 0, c->stream, P);
   HIPCHECK(hipGetLastError());
   return 0;
+}
+
+static int launch_ocqbdy(qgcm_hip_ctx *c) {
+  KTimer t(c, KN_OCQBDY);
+  return launch_ocqbdy_on(c, c->p[c->ip], c->q[c->iq]);
 }
 
 static int launch_lfavg(qgcm_hip_ctx *c) {
@@ -2068,16 +2070,7 @@ extern "C" int qgcm_hip_ocqbdy_host(qgcm_hip_handle c, double *q, const double *
   if (dp.alloc(n, "the scratch copy of p") || dq.alloc(n, "the scratch copy of q")) return 1;
   const long rows = (long)g.ny * g.nl;
   int rc = upload2d(c, dp, g.ldx, p, g.nx, rows) || upload2d(c, dq, g.ldx, q, g.nx, rows);
-  if (!rc) {
-    QgBdyParams P;
-    fill_bdy_params(c, P);
-    P.po = dp;
-    P.qo = dq;
-    const int nmax = g.nx > g.ny ? g.nx : g.ny;
-    hipLaunchKernelGGL(k_ocqbdy, dim3((nmax + 255) / 256, g.cyc ? 2 : 4, g.nl), dim3(256), 0, c->stream, P);
-    rc = hipGetLastError() != hipSuccess;
-    if (rc) snprintf(g_err, sizeof(g_err), "qgcm_hip_ocqbdy_host: launch failed");
-  }
+  if (!rc && (rc = launch_ocqbdy_on(c, dp, dq))) snprintf(g_err, sizeof(g_err), "qgcm_hip_ocqbdy_host: launch failed");
   if (!rc) rc = download2d(c, q, dq, g.ldx, g.nx, rows);
   return rc;
 }
