@@ -42,7 +42,8 @@ extern "C" {
                            the fused single-launch forms of the inversion for nlo <= 4) */
 /* 2: qgcm_hip_params.atmos + the atmosphere entry points
  * 3: qgcm_hip_get_monitors (required by the Fortran shim), qgcm_hip_prepare_steps, qgcm_hip_stream_mix_bandwidth,
- *    qgcm_hip_set_sponge, qgcm_hip_set_cu_range; halo rows of qgcm_hip_slab_steps default to neighbour send/recv */
+ *    qgcm_hip_set_sponge, qgcm_hip_set_cu_range; halo rows of qgcm_hip_slab_steps default to neighbour send/recv
+ *    (entry points added since keep the number - there is no minor version: qgcm_hip_xforc_sst_* the latest) */
 #define QGCM_HIP_ABI_VERSION 3
 
 typedef struct qgcm_hip_ctx *qgcm_hip_handle;
@@ -852,6 +853,38 @@ typedef struct qgcm_hip_xforc_heat_params {
 } qgcm_hip_xforc_heat_params;
 int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p);
 int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *fnetoc, double *fnetat, double *scal);
+
+/* ---- heat half of xforc without an ocean: atmos_only -------------------------------------------------
+ * What a -Datmos_only build of the reference runs of src/xfosubs.F:711-853: the sea below the atmosphere is an SST that
+ * is read once and held (src/q-gcm.F:753-786, sstm = sst), fnetoc and arocsm are skipped (:805-812).  The atmosphere
+ * handle owns the SST, (nxto, nyto) = (nxaooc*ndxr, nyaooc*ndxr), at the position qgcm_hip_xforc_init was given.
+ * With it qgcm_hip_coupled_steps(NULL, atm, ...) after qgcm_hip_coupled_set_xforc(NULL, atm, 1) is the reference's
+ * atmos_only sequence xforc; (aml; qgastep; atinvq; atqzbd) x nstr without a host transfer.
+ * qgcm_hip_xforc_sst_init(atm, p): after qgcm_hip_xforc_init(NULL, atm, ...) and qgcm_hip_aml_init(atm).  The radiation
+ *   constants, fsa and the T-point coordinates are those of qgcm_hip_xforc_heat_params (bilint's tables are built by the
+ *   same code); dxo, dyo are the spacings of the SST grid (ocfrac = dxo*dyo/(dxa*dya), ocnorm = 1/(nxto*nyto));
+ *   sst (nxto, nyto) is a host array, dense Fortran order.  Refuses, naming the reason and changing nothing: a NULL
+ *   argument, a handle that is not a whole-domain atmosphere, qgcm_hip_xforc_init missing or called WITH an ocean (the
+ *   heat half of such an atmosphere is qgcm_hip_xforc_heat_init), qgcm_hip_aml_init missing, a sea that does not lie
+ *   inside the atmosphere, a coordinate that xta / yta does not cover.
+ * qgcm_hip_xforc(NULL, atm) then runs this heat half after the momentum half, on the same stream: fnetat into the
+ *   buffer of qgcm_hip_set_atm_tav_fields (it counts as given), where aml reads it; bitwise the reference's over land,
+ *   above the sea and in slhfav / oradav / arlaav equal to the serial reference to rounding (one wave per cell, fixed
+ *   order, no atomics: reproducible); arocav = 0 exactly.
+ * qgcm_hip_xforc_sst_set(atm, sst): replaces the held SST; a synchronous upload, ordered after what is queued on the
+ *   handle's stream.
+ * qgcm_hip_xforc_sst_get: synchronous copies, NULL skips: fnetat (nxta,nyta), scal[4] = arlaav, slhfav, oradav, arocav. */
+typedef struct qgcm_hip_xforc_sst_params {
+  double xlamda, D0up, Dmup, Dmdown, Adown11, Bmup, B1down, Cmup, C1down; /* MODULE radiate */
+  double hmadmp, hmat;                                                     /* MODULE intrfac */
+  const double *fsa;                   /* fsprim(ytarel(1:nyta)) */
+  const double *xta, *yta, *xto, *yto; /* T-point coordinates (nxta), (nyta), (nxto), (nyto) */
+  double dxo, dyo;                     /* spacing of the SST grid */
+  const double *sst;                   /* (nxto, nyto) */
+} qgcm_hip_xforc_sst_params;
+int qgcm_hip_xforc_sst_init(qgcm_hip_handle atm, const qgcm_hip_xforc_sst_params *p);
+int qgcm_hip_xforc_sst_set(qgcm_hip_handle atm, const double *sst);
+int qgcm_hip_xforc_sst_get(qgcm_hip_handle atm, double *fnetat, double *scal);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of

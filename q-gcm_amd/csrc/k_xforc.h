@@ -314,22 +314,7 @@ __global__ __launch_bounds__(XF_NT) void k_xf_lines(const QgXfParams P) {
 // About 15 MB of traffic at the 961 x 961 ocean (sstm in, fnetoc out): small beside the momentum half.
 #include "k_oml.h" // oml_block_sums
 
-struct QgXfHeatParams {
-  int nxta, nyta, nxto, nyto, ndxr, nx1, ny1, nxaooc, nyaooc;
-  int ldta, lda, ldto;             // pitches: atmosphere T / p grid, ocean T grid
-  long fstride;                    // doubles between two layers of pam
-  const double *astm, *hmm, *pam, *dtop; // atmosphere: lagged levels (T grid), lagged pressure, topography (or nullptr)
-  const double *sstm;              // ocean: lagged mixed-layer temperature
-  const double *fsa, *fso;         // fsprim tables (nyta), (nyto)
-  const int *ix, *iy;              // iam, iap (2, nxto); jam, jap (2, nyto): 1-based
-  const double *wx, *wy;           // wmx, wpx (2, nxto); wmy, wpy (2, nyto)
-  double *fnetoc, *fnetat;
-  double *cell;                    // (nxaooc, nyaooc) sums above the ocean
-  double *part;                    // (3, ncell) arocsm, slhfsm, oradsm per cell, then (nblkL) arlasm per workgroup of k_xf_heat_atm
-  double *scal;                    // arlaav, slhfav, oradav, arocav
-  int ncell, nblkL, natlan;
-  double D0up, xlamda, Dmdown, Dmup, dmdu, ocfrac, fmafac, fmatop, hmafac, hmat, ocnorm;
-};
+#include "k_xf_heat_params.h" // QgXfHeatParams
 
 // grid: (nxaooc, nyaooc), block 64
 __global__ __launch_bounds__(64) void k_xf_heat_oc(const QgXfHeatParams P) {
@@ -418,3 +403,6 @@ __global__ __launch_bounds__(OML_NT) void k_xf_heat_final(const QgXfHeatParams P
     P.scal[3] = a[0] * P.ocnorm; // arocav
   }
 }
+
+// The heat half without an ocean (atmos_only) replaces k_xf_heat_oc by k_xf_heat_sst, which lives in
+// k_xf_heat_sst.h / k_xf_heat_sst.hip, a device code object of its own: k_xf_heat_atm and k_xf_heat_final follow it unchanged.

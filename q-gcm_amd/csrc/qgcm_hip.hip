@@ -389,6 +389,15 @@ struct qgcm_hip_ctx {
       QgBuf<int> ix, iy;
       int nblkL = 0;
     } heat;
+    // heat half without an ocean (qgcm_hip_xforc_sst_init; atmos_only): the prescribed SST (nxaooc*ndxr, nyaooc*ndxr)
+    // with its own pitch and the spacing of its grid.  The constants, tables, sums and results are `heat`'s, whose
+    // `on` stays false: the two set-ups exclude each other (xf.oc != nullptr / == nullptr).
+    struct {
+      bool on = false;
+      int ldt = 0;
+      double dxo = 0.0, dyo = 0.0;
+      QgDbl sst;
+    } sst;
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
@@ -2739,6 +2748,7 @@ static void xf_off(qgcm_hip_ctx *a) {
   x.on = x.coupled = false;
   x.oc = nullptr;
   x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
+  x.sst.on = false;  // (likewise qgcm_hip_xforc_sst_init)
 }
 
 extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
@@ -2874,9 +2884,13 @@ static void xf_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfParams &P) {
 }
 
 static int launch_xf_heat(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm);
+static int launch_xf_heat_sst(qgcm_hip_ctx *atm);
+// k_xf_heat_sst and its launch live in k_xf_heat_sst.hip, a device code object of its own (as k_tend_rows.hip): this file
+// compiles to the device code it had without the kernel.
+hipError_t qg_launch_xf_heat_sst(hipStream_t st, const QgXfHeatParams &P);
 
 // One `call xforc` on the atmosphere's stream, ordered against the ocean's stream by two events: the momentum half and,
-// once qgcm_hip_xforc_heat_init has set it up, the heat half.
+// once qgcm_hip_xforc_heat_init (without an ocean: qgcm_hip_xforc_sst_init) has set it up, the heat half.
 extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
   if (xf_ready(oc, atm, "qgcm_hip_xforc")) return 1;
   auto &x = atm->xf;
@@ -2915,6 +2929,7 @@ extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
   hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
   HIPCHECK(hipGetLastError());
   if (x.heat.on && launch_xf_heat(oc, atm)) return 1; // the heat half, src/xfosubs.F:711-853
+  if (x.sst.on && launch_xf_heat_sst(atm)) return 1;  // ... as -Datmos_only builds it, from the prescribed SST
   if (oc) { // the ocean's next step reads wekpo, the stress and the line integrals
     HIPCHECK(hipEventRecord(x.ev_atm, st));
     HIPCHECK(hipStreamWaitEvent(oc->stream, x.ev_atm, 0));
@@ -2965,6 +2980,44 @@ extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, doubl
 // ---------------------------------------------------------------------------
 // heat half of xforc: src/xfosubs.F:711-853 on the device, kernels in k_xforc.h
 // ---------------------------------------------------------------------------
+// bilint's index and weight tables, as the reference computes them (src/xfosubs.F:916-980): ix = iam, iap (2, nxto),
+// iy = jam, jap (2, nyto), 1-based; wx = wmx, wpx; wy = wmy, wpy.  Host side only; refuses a coordinate that xta / yta
+// does not cover.
+static int xf_bilint_tables(const char *who, int nxta, int nyta, int nxto, int nyto, double dxa, double dya, const double *xta,
+                            const double *yta, const double *xto, const double *yto, std::vector<int> &ix, std::vector<int> &iy,
+                            std::vector<double> &wx, std::vector<double> &wy) {
+  const double dxainv = 1.0 / dxa, dyainv = 1.0 / dya;
+  ix.assign(2 * (size_t)nxto, 0);
+  iy.assign(2 * (size_t)nyto, 0);
+  wx.assign(2 * (size_t)nxto, 0.0);
+  wy.assign(2 * (size_t)nyto, 0.0);
+  for (int io = 0; io < nxto; ++io) {
+    int iam = (int)(1.0 + dxainv * (xto[io] - xta[0]));
+    int iap = iam + 1;
+    if (iam > nxta) QG_FAIL("%s: the atmosphere's xta does not cover ocean column %d", who, io + 1);
+    const double xam = iam >= 1 ? xta[iam - 1] : xta[0] - dxa;
+    wx[nxto + io] = dxainv * (xto[io] - xam);
+    wx[io] = 1.0 - wx[nxto + io];
+    iam = 1 + (iam + nxta - 1) % nxta; // (both pointers mended for the cyclic T grid)
+    iap = 1 + (iap + nxta - 1) % nxta;
+    if (iam < 1 || iap < 1) QG_FAIL("%s: the atmosphere's xta does not cover ocean column %d", who, io + 1);
+    ix[io] = iam;
+    ix[nxto + io] = iap;
+  }
+  for (int jo = 0; jo < nyto; ++jo) {
+    int jam = (int)(1.0 + dyainv * (yto[jo] - yta[0]));
+    int jap = jam + 1;
+    jam = std::max(jam, 1);
+    jap = std::min(jap, nyta);
+    if (jam > nyta || jap < 1) QG_FAIL("%s: the atmosphere's yta does not cover ocean row %d", who, jo + 1);
+    wy[nyto + jo] = dyainv * (yto[jo] - yta[jam - 1]);
+    wy[jo] = 1.0 - wy[nyto + jo];
+    iy[jo] = jam;
+    iy[nyto + jo] = jap;
+  }
+  return 0;
+}
+
 extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p) {
   const char *who = "qgcm_hip_xforc_heat_init";
   if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
@@ -2978,34 +3031,10 @@ extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm,
   if (!p->fsa || !p->fso || !p->xta || !p->yta || !p->xto || !p->yto) QG_FAIL("%s: a table or a coordinate array is NULL", who);
   const qgcm_hip_xforc_params &x = atm->xf.prm;
   const int nxta = atm->g.nxt, nyta = atm->g.ny - 1, nxto = oc->g.nxt, nyto = oc->g.ny - 1;
-  // bilint's index and weight tables, as the reference computes them (src/xfosubs.F:916-980)
-  const double dxa = atm->prm.dxo, dya = atm->prm.dyo, dxainv = 1.0 / dxa, dyainv = 1.0 / dya;
-  std::vector<int> ix(2 * (size_t)nxto), iy(2 * (size_t)nyto);
-  std::vector<double> wx(2 * (size_t)nxto), wy(2 * (size_t)nyto);
-  for (int io = 0; io < nxto; ++io) {
-    int iam = (int)(1.0 + dxainv * (p->xto[io] - p->xta[0]));
-    int iap = iam + 1;
-    if (iam > nxta) QG_FAIL("%s: the atmosphere's xta does not cover ocean column %d", who, io + 1);
-    const double xam = iam >= 1 ? p->xta[iam - 1] : p->xta[0] - dxa;
-    wx[nxto + io] = dxainv * (p->xto[io] - xam);
-    wx[io] = 1.0 - wx[nxto + io];
-    iam = 1 + (iam + nxta - 1) % nxta; // (both pointers mended for the cyclic T grid)
-    iap = 1 + (iap + nxta - 1) % nxta;
-    if (iam < 1 || iap < 1) QG_FAIL("%s: the atmosphere's xta does not cover ocean column %d", who, io + 1);
-    ix[io] = iam;
-    ix[nxto + io] = iap;
-  }
-  for (int jo = 0; jo < nyto; ++jo) {
-    int jam = (int)(1.0 + dyainv * (p->yto[jo] - p->yta[0]));
-    int jap = jam + 1;
-    jam = std::max(jam, 1);
-    jap = std::min(jap, nyta);
-    if (jam > nyta || jap < 1) QG_FAIL("%s: the atmosphere's yta does not cover ocean row %d", who, jo + 1);
-    wy[nyto + jo] = dyainv * (p->yto[jo] - p->yta[jam - 1]);
-    wy[jo] = 1.0 - wy[nyto + jo];
-    iy[jo] = jam;
-    iy[nyto + jo] = jap;
-  }
+  std::vector<int> ix, iy;
+  std::vector<double> wx, wy;
+  if (xf_bilint_tables(who, nxta, nyta, nxto, nyto, atm->prm.dxo, atm->prm.dyo, p->xta, p->yta, p->xto, p->yto, ix, iy, wx, wy))
+    return 1;
   HIPCHECK(hipStreamSynchronize(atm->stream));
   auto &h = atm->xf.heat;
   h.on = false; // (until this call has gone through: it replaces the buffers)
@@ -3030,23 +3059,27 @@ extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm,
   return 0;
 }
 
+// oc = nullptr: the set-up of qgcm_hip_xforc_sst_init - the SST grid is the atmosphere handle's own buffer, there is no
+// fnetoc and no fso (k_xf_heat_sst reads neither)
 static void xf_heat_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfHeatParams &P) {
   const auto &h = atm->xf.heat;
+  const auto &ss = atm->xf.sst;
   const qgcm_hip_xforc_heat_params &q = h.prm;
   const qgcm_hip_xforc_params &x = atm->xf.prm;
   const auto &a = atm->aml;
   memset(&P, 0, sizeof(P));
-  P.nxta = atm->g.nxt; P.nyta = atm->g.ny - 1; P.nxto = oc->g.nxt; P.nyto = oc->g.ny - 1;
+  P.nxta = atm->g.nxt; P.nyta = atm->g.ny - 1;
+  P.nxto = oc ? oc->g.nxt : x.nxaooc * x.ndxr; P.nyto = oc ? oc->g.ny - 1 : x.nyaooc * x.ndxr;
   P.ndxr = x.ndxr; P.nx1 = x.nx1; P.ny1 = x.ny1; P.nxaooc = x.nxaooc; P.nyaooc = x.nyaooc;
-  P.ldta = a.ldt; P.lda = atm->g.ldx; P.ldto = oc->oml.ldt; P.fstride = atm->g.fstride;
+  P.ldta = a.ldt; P.lda = atm->g.ldx; P.ldto = oc ? oc->oml.ldt : ss.ldt; P.fstride = atm->g.fstride;
   P.astm = a.ast[a.iam]; P.hmm = a.hm[a.iam]; P.pam = atm->p[atm->ip ^ 1]; P.dtop = a.dtop;
-  P.sstm = oc->oml.sst[oc->oml.ism];
-  P.fsa = h.fsa; P.fso = h.fso; P.ix = h.ix; P.iy = h.iy; P.wx = h.wx; P.wy = h.wy;
-  P.fnetoc = oc->oml.fnet; P.fnetat = atm->tav.fnet;
+  P.sstm = oc ? (const double *)oc->oml.sst[oc->oml.ism] : (const double *)ss.sst;
+  P.fsa = h.fsa; P.fso = oc ? (const double *)h.fso : nullptr; P.ix = h.ix; P.iy = h.iy; P.wx = h.wx; P.wy = h.wy;
+  P.fnetoc = oc ? (double *)oc->oml.fnet : nullptr; P.fnetat = atm->tav.fnet;
   P.cell = h.cell; P.part = h.part; P.scal = h.scal;
   P.ncell = x.nxaooc * x.nyaooc; P.nblkL = h.nblkL; P.natlan = P.nxta * P.nyta - P.ncell;
   // the scalar prologue, src/xfosubs.F:774-777
-  const double dxo = oc->prm.dxo, dyo = oc->prm.dyo, dxa = atm->prm.dxo, dya = atm->prm.dyo;
+  const double dxo = oc ? oc->prm.dxo : ss.dxo, dyo = oc ? oc->prm.dyo : ss.dyo, dxa = atm->prm.dxo, dya = atm->prm.dyo;
   P.D0up = q.D0up; P.xlamda = q.xlamda; P.Dmdown = q.Dmdown; P.Dmup = q.Dmup; P.dmdu = q.Dmdown - q.Dmup;
   P.ocfrac = dxo * dyo / (dxa * dya);
   P.fmafac = q.Adown11 * 0.25 / atm->prm.gpoc[0];
@@ -3074,6 +3107,98 @@ extern "C" int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, 
   if (!atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_init has not been called", who);
   HIPCHECK(hipStreamSynchronize(atm->stream)); // (xforc ran on the atmosphere's stream)
   if (fnetoc && download2d(oc, fnetoc, oc->oml.fnet, oc->oml.ldt, oc->g.nxt, oc->g.ny - 1)) return 1;
+  if (fnetat && download2d(atm, fnetat, atm->tav.fnet, atm->aml.ldt, atm->g.nxt, atm->g.ny - 1)) return 1;
+  if (scal) {
+    HIPCHECK(hipMemcpyAsync(scal, atm->xf.heat.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, atm->stream));
+    HIPCHECK(hipStreamSynchronize(atm->stream));
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// heat half of xforc without an ocean: what a -Datmos_only build of src/xfosubs.F:711-853 runs, from an SST
+// that is read once and held (src/q-gcm.F:753-786)
+// ---------------------------------------------------------------------------
+static int xf_sst_ready(qgcm_hip_ctx *atm, const char *who) {
+  if (xf_ready(nullptr, atm, who)) return 1;
+  if (!atm->xf.sst.on) QG_FAIL("%s: qgcm_hip_xforc_sst_init has not been called", who);
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_sst_init(qgcm_hip_handle atm, const qgcm_hip_xforc_sst_params *p) {
+  const char *who = "qgcm_hip_xforc_sst_init";
+  if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
+  if (check_atm(atm, who)) return 1;
+  if (!atm->whole) QG_FAIL("%s: the atmosphere handle is a y-slab (xforc needs the whole domain)", who);
+  if (!atm->xf.on) QG_FAIL("%s: qgcm_hip_xforc_init has not been called for this atmosphere", who);
+  if (atm->xf.oc) QG_FAIL("%s: this atmosphere's xforc was set up with an ocean: its heat half is qgcm_hip_xforc_heat_init", who);
+  if (!atm->aml.on) QG_FAIL("%s: qgcm_hip_aml_init has not been called for this atmosphere", who);
+  if (!p->fsa || !p->xta || !p->yta || !p->xto || !p->yto || !p->sst) QG_FAIL("%s: a table, a coordinate array or the SST is NULL", who);
+  const qgcm_hip_xforc_params &x = atm->xf.prm;
+  const int nxta = atm->g.nxt, nyta = atm->g.ny - 1;
+  // (qgcm_hip_xforc_init checks the position of the sea only against an ocean handle)
+  if (x.nxaooc < 1 || x.nyaooc < 1 || x.nx1 < 1 || x.ny1 < 1 || x.nx1 + x.nxaooc - 1 > nxta || x.ny1 + x.nyaooc - 1 > nyta)
+    QG_FAIL("%s: the sea (nx1 = %d, ny1 = %d, nxaooc = %d, nyaooc = %d) does not lie inside the atmosphere's %d x %d cells", who,
+            x.nx1, x.ny1, x.nxaooc, x.nyaooc, nxta, nyta);
+  if (!(p->dxo > 0.0) || !(p->dyo > 0.0)) QG_FAIL("%s: need dxo > 0 and dyo > 0", who);
+  const int nxto = x.nxaooc * x.ndxr, nyto = x.nyaooc * x.ndxr;
+  std::vector<int> ix, iy;
+  std::vector<double> wx, wy;
+  if (xf_bilint_tables(who, nxta, nyta, nxto, nyto, atm->prm.dxo, atm->prm.dyo, p->xta, p->yta, p->xto, p->yto, ix, iy, wx, wy))
+    return 1;
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  auto &h = atm->xf.heat;
+  auto &ss = atm->xf.sst;
+  ss.on = false; // (until this call has gone through: it replaces the buffers)
+  const int ncell = x.nxaooc * x.nyaooc;
+  h.nblkL = ((nxta + 63) / 64) * ((nyta + 3) / 4);
+  ss.ldt = round_up(nxto, 16);
+  if (h.fsa.alloc(nyta, "fsprim of the atmosphere") || h.wx.alloc(2 * (size_t)nxto, "bilint's x weights") ||
+      h.wy.alloc(2 * (size_t)nyto, "bilint's y weights") || h.cell.alloc(ncell, "the per-cell sums") ||
+      h.part.alloc(3 * (size_t)ncell + h.nblkL, "the heat half's partial sums") || h.scal.alloc(4, "the heat half's results") ||
+      h.ix.alloc(2 * (size_t)nxto, "bilint's x indices") || h.iy.alloc(2 * (size_t)nyto, "bilint's y indices") ||
+      ss.sst.alloc((size_t)ss.ldt * nyto, "the prescribed SST"))
+    return 1;
+  HIPCHECK(hipMemcpy(h.fsa, p->fsa, nyta * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.wx, wx.data(), wx.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.wy, wy.data(), wy.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.ix, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(h.iy, iy.data(), iy.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemset(ss.sst, 0, (size_t)ss.ldt * nyto * sizeof(double)));
+  HIPCHECK(hipMemset(h.scal, 0, 4 * sizeof(double)));
+  HIPCHECK(hipDeviceSynchronize());
+  if (upload2d(atm, ss.sst, ss.ldt, p->sst, nxto, nyto)) return 1;
+  memset(&h.prm, 0, sizeof(h.prm)); // (the constants; no host pointer is kept)
+  h.prm.xlamda = p->xlamda; h.prm.D0up = p->D0up; h.prm.Dmup = p->Dmup; h.prm.Dmdown = p->Dmdown; h.prm.Adown11 = p->Adown11;
+  h.prm.Bmup = p->Bmup; h.prm.B1down = p->B1down; h.prm.Cmup = p->Cmup; h.prm.C1down = p->C1down;
+  h.prm.hmadmp = p->hmadmp; h.prm.hmat = p->hmat;
+  ss.dxo = p->dxo;
+  ss.dyo = p->dyo;
+  ss.on = true;
+  return 0;
+}
+
+static int launch_xf_heat_sst(qgcm_hip_ctx *atm) {
+  QgXfHeatParams P;
+  xf_heat_fill(nullptr, atm, P);
+  hipStream_t st = atm->stream;
+  HIPCHECK(qg_launch_xf_heat_sst(st, P));
+  hipLaunchKernelGGL(k_xf_heat_atm, dim3((P.nxta + 63) / 64, (P.nyta + 3) / 4), dim3(OML_NT), 0, st, P);
+  hipLaunchKernelGGL(k_xf_heat_final, dim3(1), dim3(OML_NT), 0, st, P);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_sst_set(qgcm_hip_handle atm, const double *sst) {
+  const char *who = "qgcm_hip_xforc_sst_set";
+  if (xf_sst_ready(atm, who)) return 1;
+  if (!sst) QG_FAIL("%s: null argument", who);
+  const qgcm_hip_xforc_params &x = atm->xf.prm;
+  return upload2d(atm, atm->xf.sst.sst, atm->xf.sst.ldt, sst, x.nxaooc * x.ndxr, x.nyaooc * x.ndxr);
+}
+
+extern "C" int qgcm_hip_xforc_sst_get(qgcm_hip_handle atm, double *fnetat, double *scal) {
+  if (xf_sst_ready(atm, "qgcm_hip_xforc_sst_get")) return 1;
   if (fnetat && download2d(atm, fnetat, atm->tav.fnet, atm->aml.ldt, atm->g.nxt, atm->g.ny - 1)) return 1;
   if (scal) {
     HIPCHECK(hipMemcpyAsync(scal, atm->xf.heat.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, atm->stream));

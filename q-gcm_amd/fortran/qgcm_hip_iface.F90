@@ -70,6 +70,16 @@ module qgcm_hip_iface
     type(c_ptr) :: fsa, fso, xta, yta, xto, yto
   end type qgcm_hip_xforc_heat_params
 
+  ! struct qgcm_hip_xforc_sst_params: the heat half of xforc without an ocean (atmos_only; qgcm_hip_xforc_sst_init):
+  ! the constants and fsa, xta, yta, xto, yto as above; dxo, dyo = the spacing of the SST grid; sst = c_loc of the
+  ! (nxto, nyto) field that is read once and held
+  type, bind(C) :: qgcm_hip_xforc_sst_params
+    real(c_double) :: xlamda, D0up, Dmup, Dmdown, Adown11, Bmup, B1down, Cmup, C1down, hmadmp, hmat
+    type(c_ptr) :: fsa, xta, yta, xto, yto
+    real(c_double) :: dxo, dyo
+    type(c_ptr) :: sst
+  end type qgcm_hip_xforc_sst_params
+
   interface
     integer(c_int) function qgcm_hip_create(h, prm, device) bind(C, name='qgcm_hip_create')
       import :: c_ptr, c_int, qgcm_hip_params
@@ -639,6 +649,20 @@ module qgcm_hip_iface
     integer(c_int) function qgcm_hip_xforc_heat_get(oc, atm, fnetoc, fnetat, scal) bind(C, name='qgcm_hip_xforc_heat_get')
       import :: c_ptr, c_int
       type(c_ptr), value :: oc, atm, fnetoc, fnetat, scal
+    end function
+    ! ... without an ocean (atmos_only), from a prescribed SST held by the atmosphere handle
+    integer(c_int) function qgcm_hip_xforc_sst_init(atm, prm) bind(C, name='qgcm_hip_xforc_sst_init')
+      import :: c_ptr, c_int, qgcm_hip_xforc_sst_params
+      type(c_ptr), value :: atm
+      type(qgcm_hip_xforc_sst_params), intent(in) :: prm
+    end function
+    integer(c_int) function qgcm_hip_xforc_sst_set(atm, sst) bind(C, name='qgcm_hip_xforc_sst_set')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: atm, sst
+    end function
+    integer(c_int) function qgcm_hip_xforc_sst_get(atm, fnetat, scal) bind(C, name='qgcm_hip_xforc_sst_get')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: atm, fnetat, scal
     end function
   end interface
 

@@ -11,5 +11,5 @@ library or without a HIP device raises.
 from .config import AmlConfig, AtmosConfig, HeatConfig, OceanConfig, OmlConfig, PRESETS, atmos_of, atmos_preset, oml_preset, preset  # noqa: F401
 from .lib import QgcmHipError, check, load_library, library_path  # noqa: F401
 from .model import (AtmosModel, OceanModel, coupled_steps, share_gpu, xforc, xforc_get, xforc_heat_get,  # noqa: F401
-                    xforc_heat_setup, xforc_setup)
+                    xforc_heat_setup, xforc_setup, xforc_sst_get, xforc_sst_set, xforc_sst_setup)
 from . import hostinit, synth  # noqa: F401

@@ -95,6 +95,14 @@ class XforcHeatParams(C.Structure):
         (n, C.POINTER(C.c_double)) for n in ("fsa", "fso", "xta", "yta", "xto", "yto")]
 
 
+class XforcSstParams(C.Structure):
+    """struct qgcm_hip_xforc_sst_params (include/qgcm_hip.h)."""
+    _fields_ = [(n, C.c_double) for n in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup",
+                                          "C1down", "hmadmp", "hmat")] + [
+        (n, C.POINTER(C.c_double)) for n in ("fsa", "xta", "yta", "xto", "yto")] + [
+        ("dxo", C.c_double), ("dyo", C.c_double), ("sst", C.POINTER(C.c_double))]
+
+
 TAV_NOUT = 16  # QGCM_HIP_TAV_NOUT
 ATM_TAV_NOUT = 15  # QGCM_HIP_ATM_TAV_NOUT
 
@@ -137,6 +145,7 @@ SYMBOLS = [
     "qgcm_hip_xforc_init", "qgcm_hip_xforc", "qgcm_hip_xforc_get", "qgcm_hip_coupled_set_xforc",
     "qgcm_hip_aml_init", "qgcm_hip_aml_set_state", "qgcm_hip_aml_get_state", "qgcm_hip_aml", "qgcm_hip_aml_get_diag",
     "qgcm_hip_xforc_heat_init", "qgcm_hip_xforc_heat_get",
+    "qgcm_hip_xforc_sst_init", "qgcm_hip_xforc_sst_set", "qgcm_hip_xforc_sst_get",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
     "qgcm_hip_debug_live_allocs",
 ]
@@ -297,6 +306,10 @@ def load_library():
     L.qgcm_hip_aml_get_diag.argtypes = [vp, dp, dp]
     L.qgcm_hip_xforc_heat_init.argtypes = [vp, vp, C.POINTER(XforcHeatParams)]
     L.qgcm_hip_xforc_heat_get.argtypes = [vp, vp, dp, dp, dp]
+    if hasattr(L, "qgcm_hip_xforc_sst_init"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_xforc_sst_init.argtypes = [vp, C.POINTER(XforcSstParams)]
+        L.qgcm_hip_xforc_sst_set.argtypes = [vp, dp]
+        L.qgcm_hip_xforc_sst_get.argtypes = [vp, dp, dp]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

@@ -1125,6 +1125,66 @@ def xforc_heat_get(ocean, atmos):
     return out
 
 
+def xforc_sst_setup(atmos, ocean_cfg, heat, sst, hmadmp=None, hmat=None, fsa=None, coords=None):
+    """Set up the heat half of xforc WITHOUT an ocean (qgcm_hip_xforc_sst_init, DESIGN 6n: the reference's atmos_only
+    build) after xforc_setup(None, atmos, ndxr=..., nxaooc=..., nyaooc=...) and atmos.aml_init: xforc(None, atmos) and
+    coupled_steps(None, atmos, ..., xforc=True) then also compute fnetat (where aml reads it) from the prescribed,
+    held `sst` (nxto, nyto).  ocean_cfg: an OceanConfig used for the geometry of the sea only (nxaooc, nyaooc, ndxr,
+    dxo, dyo); no OceanModel is needed.  heat: qgcm_hip.config.HeatConfig; hmadmp, hmat default to the values aml_init
+    was given.  fsa: the table fsprim(ytarel(1:nyta)) (default hostinit.fsprim); coords: dict(xta, yta, xto, yto),
+    default hostinit.grid_coordinates with the sea placed where xforc_setup placed it (its nx1, ny1)."""
+    from .lib import XforcSstParams
+    am = getattr(atmos, "aml_cfg", None)
+    if (hmadmp is None or hmat is None) and am is None:
+        raise QgcmHipError("xforc_sst_setup: call atmos.aml_init first (qgcm_hip_aml_init has not been called)")
+    nx1, ny1 = getattr(atmos, "xforc_origin", (None, None))  # the position xforc_setup was given
+    G = hostinit.grid_coordinates(atmos.cfg, ocean_cfg, nx1=nx1, ny1=ny1)
+    if coords is not None:
+        G = dict(G, **coords)
+    fsa = hostinit.fsprim(G["ytarel"], heat.fspco, G["yla"]) if fsa is None else fsa
+    keep = [np.ascontiguousarray(v, dtype=np.float64) for v in (fsa, G["xta"], G["yta"], G["xto"], G["yto"])]
+    want = (atmos.cfg.nyta, atmos.cfg.nxta, atmos.cfg.nyta, ocean_cfg.nxto, ocean_cfg.nyto)
+    for v, n, name in zip(keep, want, ("fsa", "xta", "yta", "xto", "yto")):
+        if v.shape != (n,):
+            raise QgcmHipError("xforc_sst_setup: %s has shape %s, need (%d,)" % (name, v.shape, n))
+    s = _f(sst)
+    if s is None or s.shape != (ocean_cfg.nxto, ocean_cfg.nyto):
+        raise QgcmHipError("xforc_sst_setup: sst has shape %s, need (%d, %d)" % (None if s is None else s.shape,
+                                                                                 ocean_cfg.nxto, ocean_cfg.nyto))
+    p = XforcSstParams()
+    for k in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup", "C1down"):
+        setattr(p, k, float(getattr(heat, k)))
+    p.hmadmp = float(am.hmadmp if hmadmp is None else hmadmp)
+    p.hmat = float(am.hmat if hmat is None else hmat)
+    p.fsa, p.xta, p.yta, p.xto, p.yto = [_dp(v) for v in keep]
+    p.dxo, p.dyo = float(ocean_cfg.dxo), float(ocean_cfg.dyo)
+    p.sst = _dp(s)
+    check(atmos.L.qgcm_hip_xforc_sst_init(atmos.h, C.byref(p)))
+    atmos.sst_shape = (int(ocean_cfg.nxto), int(ocean_cfg.nyto))
+
+
+def xforc_sst_set(atmos, sst):
+    """Replace the SST that xforc_sst_setup gave (qgcm_hip_xforc_sst_set): (nxto, nyto), held until the next call."""
+    shape = getattr(atmos, "sst_shape", None)
+    if shape is None:
+        raise QgcmHipError("xforc_sst_set: qgcm_hip_xforc_sst_init has not been called (xforc_sst_setup first)")
+    s = _f(sst)
+    if s is None or s.shape != shape:
+        raise QgcmHipError("xforc_sst_set: sst has shape %s, need (%d, %d)" % ((None if s is None else s.shape,) + shape))
+    check(atmos.L.qgcm_hip_xforc_sst_set(atmos.h, _dp(s)))
+
+
+def xforc_sst_get(atmos):
+    """The outputs of the heat half of the last xforc(None, atmos): dict(fnetat (nxta,nyta), arlaav, slhfav, oradav,
+    arocav); arocav is 0: the reference does not accumulate it when atmos_only."""
+    a = atmos.cfg
+    fa, sc = np.zeros((a.nxta, a.nyta), order="F"), np.zeros(4)
+    check(atmos.L.qgcm_hip_xforc_sst_get(atmos.h, _dp(fa), _dp(sc)))
+    out = dict(fnetat=fa)
+    out.update({k: float(v) for k, v in zip(HEAT_SCALARS, sc)})
+    return out
+
+
 def coupled_steps(ocean, atmos, nt0, n, nstr, xforc=False):
     """n atmospheric steps nt = nt0.. with one ocean step before every one with mod(nt,nstr) == 1
     (src/q-gcm.F:1220-1268); either model may be None.  xforc = False: the forcing is held.  xforc = True (after

@@ -4,7 +4,11 @@ src/q-gcm.F:612-640): Fortran sequential unformatted records with 4-byte length 
     tyrs | po, pom | [pa, pam] | sst, sstm | ast, astm | hmixa, hmixam
 
 `[pa, pam]` is absent in an ocean_only build; the atmospheric mixed-layer arrays are (nxta, nyta) and are written
-even then (MODULE intrfac declares them unconditionally).  All fields are fp64, Fortran order.
+even then (MODULE intrfac declares them unconditionally).  An atmos_only build leaves `po, pom` out instead:
+
+    tyrs | pa, pam | sst, sstm | ast, astm | hmixa, hmixam
+
+where sst, sstm (nxto, nyto) are the prescribed SST it holds.  All fields are fp64, Fortran order.
 This is the on-disk contract either side of the device path: a host reads a dump, pushes po/pom (+ sst/sstm) with
 set_p / oml_set_state, and writes one from get_state / oml_get_state."""
 import struct
@@ -12,10 +16,16 @@ import struct
 import numpy as np
 
 
+class TruncatedRestart(EOFError, ValueError):
+    """The file ends before the records asked for do: the EOFError it always was, and a ValueError like every other
+    mismatch between a file and the layout it is read as (an atmos_only dump read as a coupled one ends one record
+    early)."""
+
+
 def _rec(f):
     head = f.read(4)
     if len(head) != 4:
-        raise EOFError("restart file ends inside a record marker")
+        raise TruncatedRestart("restart file ends inside a record marker")
     (n,) = struct.unpack("<i", head)
     data = f.read(n)
     (m,) = struct.unpack("<i", f.read(4))
@@ -31,9 +41,30 @@ def _put(f, *arrays):
     f.write(struct.pack("<i", len(body)))
 
 
-def read_restart(path, cfg, coupled=False):
+def _read_atmos_only(path, cfg):
+    nT, nA, nP = cfg.nxto * cfg.nyto, cfg.nxta * cfg.nyta, (cfg.nxta + 1) * (cfg.nyta + 1)
+    with open(path, "rb") as f:
+        t, pa, s, a, h = (_rec(f) for _ in range(5))
+        if f.read(1):
+            raise ValueError("restart file %s has more than the five records of an atmos_only dump" % path)
+    nla = pa.size // (2 * nP)
+    if t.size != 1 or nla < 2 or pa.size != 2 * nP * nla or s.size != 2 * nT or a.size != 2 * nA or h.size != 2 * nA:
+        raise ValueError("restart file %s is not an atmos_only dump of grid %s" % (path, cfg.name))
+    sha, shT, shA = (cfg.nxta + 1, cfg.nyta + 1, nla), (cfg.nxto, cfg.nyto), (cfg.nxta, cfg.nyta)
+    r = lambda v, sh: np.asfortranarray(v.reshape(sh, order="F"))
+    return dict(tyrs=float(t[0]), pa=r(pa[:nP * nla], sha), pam=r(pa[nP * nla:], sha), sst=r(s[:nT], shT),
+                sstm=r(s[nT:], shT), ast=r(a[:nA], shA), astm=r(a[nA:], shA), hmixa=r(h[:nA], shA), hmixam=r(h[nA:], shA))
+
+
+def read_restart(path, cfg, coupled=False, *, atmos_only=False):
     """-> dict(tyrs, po, pom, sst, sstm, ast, astm, hmixa, hmixam) of an ocean_only dump for grid `cfg`;
-    coupled=True: the dump of a coupled build, which also carries pa, pam (nxta+1, nyta+1, 3)."""
+    coupled=True: the dump of a coupled build, which also carries pa, pam (nxta+1, nyta+1, 3).
+    atmos_only=True: the dump of an atmos_only build, dict(tyrs, pa, pam, sst, sstm, ast, astm, hmixa, hmixam) with
+    pa, pam (nxta+1, nyta+1, nla), nla from the record's length; cfg gives nxta, nyta and the SST's nxto, nyto."""
+    if atmos_only:
+        if coupled:
+            raise ValueError("read_restart: a dump is either coupled or atmos_only")
+        return _read_atmos_only(path, cfg)
     np3, nT, nA = cfg.nxpo * cfg.nypo * cfg.nlo, cfg.nxto * cfg.nyto, cfg.nxta * cfg.nyta
     with open(path, "rb") as f:
         t = _rec(f)
@@ -57,11 +88,28 @@ def read_restart(path, cfg, coupled=False):
     return out
 
 
-def write_restart(path, cfg, tyrs, po, pom, sst=None, sstm=None, ast=None, astm=None, hmixa=None, hmixam=None,
-                  pa=None, pam=None):
-    """pa, pam given: the dump of a coupled build (record [pa, pam] after [po, pom])."""
+def write_restart(path, cfg, tyrs, po=None, pom=None, sst=None, sstm=None, ast=None, astm=None, hmixa=None, hmixam=None,
+                  pa=None, pam=None, *, atmos_only=False):
+    """pa, pam given: the dump of a coupled build (record [pa, pam] after [po, pom]).  atmos_only=True: the dump of an
+    atmos_only build, which has no [po, pom] record: pa, pam (nxta+1, nyta+1, nla) are required, po / pom refused."""
     zT, zA = np.zeros((cfg.nxto, cfg.nyto)), np.zeros((cfg.nxta, cfg.nyta))
     d = lambda x, z: z if x is None else x
+    if atmos_only:
+        if po is not None or pom is not None:
+            raise ValueError("an atmos_only dump has no po / pom")
+        sha = np.shape(pa)
+        if len(sha) != 3 or sha[:2] != (cfg.nxta + 1, cfg.nyta + 1) or sha[2] < 2 or np.shape(pam) != sha:
+            raise ValueError("pa / pam must be (%d, %d, nla)" % (cfg.nxta + 1, cfg.nyta + 1))
+        for x, z in ((sst, zT), (sstm, zT), (ast, zA), (astm, zA), (hmixa, zA), (hmixam, zA)):
+            if x is not None and np.shape(x) != z.shape:
+                raise ValueError("a mixed-layer field has shape %s, need %s" % (np.shape(x), z.shape))
+        with open(path, "wb") as f:
+            _put(f, np.array([tyrs], dtype=np.float64))
+            _put(f, pa, pam)
+            _put(f, d(sst, zT), d(sstm, zT))
+            _put(f, d(ast, zA), d(astm, zA))
+            _put(f, d(hmixa, zA), d(hmixam, zA))
+        return
     for x, sh in ((po, (cfg.nxpo, cfg.nypo, cfg.nlo)), (pom, (cfg.nxpo, cfg.nypo, cfg.nlo))):
         if np.shape(x) != sh:
             raise ValueError("po / pom must be %s" % (sh,))
