@@ -14,15 +14,9 @@ import ctypes as C
 import numpy as np
 
 from . import hostinit
-from .lib import MAXL, Params, QgcmHipError, check, load_library
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _f(a):
-    return None if a is None else np.asfortranarray(a, dtype=np.float64)
+from .handle import (COV_NAMES_ATM, COV_NAMES_OCN, OCNC_FIELDS, QOCDIAG_TERMS, TAV_LAYOUT, Handle, _dp, _f,  # noqa: F401
+                     read_dump, read_means, subsample_count, unpack_budget)
+from .lib import QgcmHipError, check
 
 
 # layout of qgcm_hip_monitors (include/qgcm_hip.h): (name, length in units of nlo: 0 = scalar, -1 = nlo-1, 1 = nlo)
@@ -94,152 +88,13 @@ def atm_mon_params(acfg, ocean=None, rhoat=1.0, cpat=1.0e3, hmat=1000.0, davgat=
 
 def unpack_monitors(v, nl):
     """dict name -> float or array from the packed vector of qgcm_hip_monitors; ocjpos as int (1-based row, 0: none)."""
-    out, i = {}, 0
-    for name, kind in MONITOR_LAYOUT:
-        n = {0: 1, -1: nl - 1, 1: nl}[kind]
-        x = np.array(v[i:i + n], dtype=np.float64)
-        out[name] = float(x[0]) if kind == 0 else (x.astype(np.int64) if name == "ocjpos" else x)
-        i += n
-    if i != len(v):
-        raise QgcmHipError("monitor vector has %d entries, the layout %d" % (len(v), i))
-    return out
-
-
-def mon_params(oml=None, rhooc=None, cpoc=None, hmoc=None, ycexp=None, sb_hflux=None, nb_hflux=None):
-    """struct qgcm_hip_mon_params: the given values, the others from `oml` (a qgcm_hip.OmlConfig; its defaults are the
-    examples' input.params values)."""
-    from .config import OmlConfig
-    from .lib import MonParams
-    om = OmlConfig() if oml is None else oml
-    pick = lambda v, d: d if v is None else v
-    p = MonParams()
-    p.rhooc, p.cpoc = float(pick(rhooc, om.rhooc)), float(pick(cpoc, om.cpoc))
-    p.hmoc, p.ycexp = float(pick(hmoc, om.hmoc)), float(pick(ycexp, om.ycexp))
-    p.sb_hflux, p.nb_hflux = int(pick(sb_hflux, om.sb_hflux)), int(pick(nb_hflux, om.nb_hflux))
-    return p
+    return _unpack(v, nl, MONITOR_LAYOUT, "ocjpos")
 
 
 def prsamp_dict(out, nl):
     """dict of the packed result of qgcm_hip_prsamp (4*nlo + 2 doubles)."""
     return dict(po_centre=out[:nl].copy(), qo_centre=out[nl:2 * nl].copy(), pavgoc=out[2 * nl:3 * nl].copy(),
                 qavgoc=out[3 * nl:4 * nl].copy(), sstmin=out[4 * nl], sstmax=out[4 * nl + 1])
-
-
-# outputs of qgcm_hip_tav_out in ABI order (names of MODULE timavge / tavout) and their grids: p = (nxpo, p rows),
-# t = (nxto, T rows), p3 = (nxpo, p rows, nlo), u = (nxpo, T rows), v = (nxto, p rows)
-TAV_LAYOUT = (("txocav", "p"), ("tyocav", "p"), ("wpocav", "p"), ("wtocav", "t"), ("fmocav", "t"), ("sstav", "t"),
-              ("pocav", "p3"), ("qocav", "p3"), ("uufo", "u"), ("tufo", "u"), ("utufo", "u"), ("vvfo", "v"),
-              ("tvfo", "v"), ("vtvfo", "v"), ("uptpoc", "u"), ("vptpoc", "v"))
-
-
-def tav_params(oml=None, hmoc=None, ycexp=None, tsbdy=None, tnbdy=None, sb_hflux=None, nb_hflux=None):
-    """struct qgcm_hip_tav_params: the given values, the others from `oml` (a qgcm_hip.OmlConfig)."""
-    from .config import OmlConfig
-    from .lib import TavParams
-    om = OmlConfig() if oml is None else oml
-    pick = lambda v, d: d if v is None else v
-    p = TavParams()
-    p.hmoc, p.ycexp = float(pick(hmoc, om.hmoc)), float(pick(ycexp, om.ycexp))
-    p.tsbdy, p.tnbdy = float(pick(tsbdy, om.tsbdy)), float(pick(tnbdy, om.tnbdy))
-    p.sb_hflux, p.nb_hflux = int(pick(sb_hflux, om.sb_hflux)), int(pick(nb_hflux, om.nb_hflux))
-    return p
-
-
-def _read_means(layout, entry, nout, h, shape, names):
-    """The means `entry` (qgcm_hip_tav_out / qgcm_hip_atm_tav_out, `nout` outputs in `layout`'s order) returns for the
-    given names (None = all): (dict name -> array, number of contributions).  shape: grid -> array shape."""
-    want = [n for n, _ in layout] if names is None else list(names)
-    out, ptrs = {}, (C.POINTER(C.c_double) * nout)()
-    for i, (name, grid) in enumerate(layout):
-        if name in want:
-            out[name] = np.zeros(shape[grid], order="F")
-            ptrs[i] = _dp(out[name])
-    n = C.c_int()
-    check(entry(h, ptrs, C.byref(n)))
-    return out, n.value
-
-
-def read_time_means(L, h, cfg, np_rows, nt_rows, names=None):
-    """qgcm_hip_tav_out for the given names (None = all): (dict name -> array, nsumoc)."""
-    from .lib import TAV_NOUT
-    shape = dict(p=(cfg.nxpo, np_rows), t=(cfg.nxto, nt_rows), p3=(cfg.nxpo, np_rows, cfg.nlo), u=(cfg.nxpo, nt_rows),
-                 v=(cfg.nxto, np_rows))
-    return _read_means(TAV_LAYOUT, L.qgcm_hip_tav_out, TAV_NOUT, h, shape, names)
-
-
-def read_po_mean(L, h, cfg, np_rows, reset):
-    """qgcm_hip_poavg_out: (po_avg / nsum (nxpo, p rows, nlo), nsum)."""
-    a = np.zeros((cfg.nxpo, np_rows, cfg.nlo), order="F")
-    n = C.c_int()
-    check(L.qgcm_hip_poavg_out(h, _dp(a), C.byref(n), int(bool(reset))))
-    return a, n.value
-
-
-# periodic ocean dumps (qgcm_hip_qocdiag / qgcm_hip_ocnc_sample; DESIGN 6g)
-QOCDIAG_TERMS = ("dqdt", "qotjac", "qt2dif", "qt4dif", "qotent")
-# ocnc_out's fields in its order: (name, grid, planes in units of nlo: 0 = one plane, 1 = nlo, -1 = nlo-1, flag index)
-# (tauxo and tauyo share outfloc(6))
-OCNC_FIELDS = (("sst", "t", 0, 0), ("po", "p", 1, 1), ("qo", "p", 1, 2), ("wekto", "t", 0, 3), ("h", "p", -1, 4),
-               ("tauxo", "p", 0, 5), ("tauyo", "p", 0, 5))
-
-
-def subsample_count(n, nsko):
-    """Points of a subsample: min(mod(n,nsko),1) + (n-mod(n,nsko))/nsko (src/qocdiag.F:360-363)."""
-    m = n % nsko
-    return min(m, 1) + (n - m) // nsko
-
-
-def subsample_rows(L, h, nsko):
-    """(mp0, mp1, mt0, mt1): the subsample rows [mp0, mp1) of the p grid and [mt0, mt1) of the T grid this handle owns."""
-    r = [C.c_int() for _ in range(4)]
-    check(L.qgcm_hip_subsample_rows(h, int(nsko), *[C.byref(x) for x in r]))
-    return tuple(x.value for x in r)
-
-
-def unpack_budget(v, nl, ipwk):
-    """dict term -> (nlo, rows, ipwk) array from the packed out[term][k][jp][ip] of qgcm_hip_qocdiag."""
-    a = v.reshape(len(QOCDIAG_TERMS), nl, -1, ipwk)
-    return {t: a[n].copy() for n, t in enumerate(QOCDIAG_TERMS)}
-
-
-def read_budget(L, h, cfg, nsko):
-    n = L.qgcm_hip_qocdiag_len(h, int(nsko))
-    if n < 0:
-        check(1)
-    out = np.zeros(n)
-    check(L.qgcm_hip_qocdiag(h, int(nsko), _dp(out)))
-    return unpack_budget(out, cfg.nlo, subsample_count(cfg.nxpo, nsko))
-
-
-def _read_dump(fields, length, sample, h, nsk, flags, nl, counts):
-    """The selected fields of `fields` (OCNC_FIELDS / ATNC_FIELDS) from the packed result of `sample`: dict name ->
-    (planes, rows, columns) array, (rows, columns) for the one-plane fields.  counts(): grid -> (rows, columns)."""
-    fl = (C.c_int * 7)(*[int(x) for x in flags])
-    n = length(h, int(nsk), fl)
-    if n < 0:
-        check(1)
-    out = np.zeros(n)
-    check(sample(h, int(nsk), fl, _dp(out)))
-    cnt, res, o = counts(), {}, 0
-    for name, grid, planes, flag in fields:
-        if int(flags[flag]) != 1:
-            continue
-        shp = ({0: 1, 1: nl, -1: nl - 1}[planes],) + cnt[grid]
-        m = int(np.prod(shp))
-        a = out[o:o + m].reshape(shp)
-        res[name] = a[0] if planes == 0 else a
-        o += m
-    assert o == n
-    return res
-
-
-def read_ocnc(L, h, cfg, nsko, outfloc):
-    """ocnc_out's selected fields on the subsample rows the handle owns: sst, wekto (jtwk, itwk); po, qo
-    (nlo, jpwk, ipwk); h (nlo-1, jpwk, ipwk); tauxo, tauyo (jpwk, ipwk)."""
-    def counts():
-        mp0, mp1, mt0, mt1 = subsample_rows(L, h, nsko)
-        return dict(p=(mp1 - mp0, subsample_count(cfg.nxpo, nsko)), t=(mt1 - mt0, subsample_count(cfg.nxto, nsko)))
-    return _read_dump(OCNC_FIELDS, L.qgcm_hip_ocnc_sample_len, L.qgcm_hip_ocnc_sample, h, nsko, outfloc, cfg.nlo, counts)
 
 
 # the atmosphere's time averages and dump (qgcm_hip_atm_tav_out / qgcm_hip_atnc_sample; DESIGN 6i): outputs of
@@ -254,11 +109,6 @@ ATNC_FIELDS = (("ast", "t", 0, 0), ("pa", "p", 1, 1), ("qa", "p", 1, 2), ("wekta
                ("tauxa", "p", 0, 5), ("tauya", "p", 0, 5), ("hmixa", "t", 0, 6))
 
 
-# covariance matrices (qgcm_hip_cov_*): covout's arrays under the reference's names, p-grid vector first
-COV_NAMES_OCN = ("covpo", "avgpo", "swtpo", "nupo", "covto", "avgto", "swtto", "nuto")
-COV_NAMES_ATM = ("covpa", "avgpa", "swtpa", "nupa", "covta", "avgta", "swtta", "nuta")
-
-
 def cov_row_split(nvar, r, nranks):
     """First packed matrix row of rank r of nranks (qgcm_hip_cov_init): the smallest i with i(i+1)/2 >= r*nmat//nranks."""
     nmat = nvar * (nvar + 1) // 2
@@ -269,38 +119,6 @@ def cov_row_split(nvar, r, nranks):
     while i * (i + 1) // 2 < t:
         i += 1
     return i
-
-
-def cov_size(L, h):
-    """qgcm_hip_cov_size: dict nvar, nmat, k0, k1 (the packed range [k0, k1) the handle holds)."""
-    v = [C.c_long() for _ in range(4)]
-    check(L.qgcm_hip_cov_size(h, *[C.byref(x) for x in v]))
-    return dict(zip(("nvar", "nmat", "k0", "k1"), (x.value for x in v)))
-
-
-def read_covariance(L, h, names, k0=None, count=None):
-    """qgcm_hip_cov_out for both vectors: dict keyed by `names` (cov, avg, swt, nu of p, then of T).  The packed entries
-    k0 .. k0+count-1 (default: all the handle holds), 0-based k = i(i+1)/2 + j."""
-    sz = cov_size(L, h)
-    k0 = sz["k0"] if k0 is None else int(k0)
-    count = sz["k1"] - k0 if count is None else int(count)
-    out = {}
-    for w in (0, 1):
-        cov, avg, swt, nu = np.zeros(max(count, 0)), np.zeros(sz["nvar"]), C.c_double(), C.c_long()
-        check(L.qgcm_hip_cov_out(h, w, _dp(avg), C.byref(swt), C.byref(nu), k0, count, _dp(cov)))
-        out.update(zip(names[4 * w:4 * w + 4], (cov, avg, swt.value, nu.value)))
-    return out
-
-
-def set_area_tables(L, h, tables):
-    """qgcm_hip_areavg_init from the dict qgcm_hip.hostinit.area_limits returns."""
-    ii = [np.ascontiguousarray(tables[k], dtype=np.int32) for k in ("i1", "i2", "j1", "j2")]
-    ww = [np.ascontiguousarray(tables[k], dtype=np.float64) for k in ("facw", "face", "facs", "facn")]
-    n = len(ii[0])
-    if any(len(a) != n for a in ii + ww):
-        raise ValueError("set_area_tables: the tables differ in length")
-    ip = C.POINTER(C.c_int)
-    check(L.qgcm_hip_areavg_init(h, n, *[a.ctypes.data_as(ip) for a in ii], *[_dp(a) for a in ww]))
 
 
 def cfl_names(nl):
@@ -315,8 +133,8 @@ def cfl_dict(cfg, maxima, nbad, loc):
             "nbad": nbad, "loc": loc.reshape(-1, 2)}
 
 
-class OceanModel:
-    """One ocean configuration on one MI355X.
+class OceanModel(Handle):
+    """One ocean configuration on one MI355X: the handle that owns the whole domain.
 
     Start-up follows src/q-gcm.F:380-976 for the ocean: grid, eigmod, tridiagonal
     coefficients, homsol (its Helmholtz solves run on the GPU through
@@ -325,12 +143,6 @@ class OceanModel:
     """
 
     def __init__(self, cfg, ddynoc=None, device=-1, consts=None):
-        self.cfg = cfg
-        self.L = load_library()
-        self.h = C.c_void_p()
-        nl = cfg.nlo
-        if nl > MAXL:
-            raise QgcmHipError("nlo=%d exceeds QGCM_HIP_MAXL" % nl)
         self.yporel = cfg.yporel()
         self.ddynoc = np.zeros((cfg.nxpo, cfg.nypo), order="F") if ddynoc is None else _f(ddynoc)
         atmos = bool(getattr(cfg, "atmos", False))
@@ -340,22 +152,8 @@ class OceanModel:
             A, rdm2, cl2m, cm2l = (consts[k] for k in ("amatoc", "rdm2oc", "ctl2moc", "ctm2loc"))
         self.amatoc, self.rdm2oc, self.ctl2moc, self.ctm2loc = A, rdm2, cl2m, cm2l
         self.aoc, self.bd2oc = hostinit.bd2oc(cfg)
-        p = Params()
-        p.nxpo, p.nypo, p.nlo, p.cyclic, p.atmos = cfg.nxpo, cfg.nypo, nl, int(cfg.cyclic), int(atmos)
-        p.fnot, p.beta, p.dxo, p.dyo = cfg.fnot, cfg.beta, cfg.dxo, cfg.dyo
-        p.tdto, p.delek, p.bccooc, p.aoc = cfg.tdto, cfg.delek, cfg.bccooc, self.aoc
-        for k in range(nl):
-            p.ah2oc[k], p.ah4oc[k], p.hoc[k], p.rdm2oc[k] = cfg.ah2oc[k], cfg.ah4oc[k], cfg.hoc[k], rdm2[k]
-        for k in range(nl - 1):
-            p.gpoc[k] = cfg.gpoc[k]
-        for name, M in (("amatoc", A), ("ctl2moc", cl2m), ("ctm2loc", cm2l)):
-            flat = np.asarray(M).ravel(order="F")
-            arr = getattr(p, name)
-            for i, v in enumerate(flat):
-                arr[i] = v
-        self.params = p
-        check(self.L.qgcm_hip_create(C.byref(self.h), C.byref(p), int(device)))
-        check(self.L.qgcm_hip_set_grid(self.h, _dp(self.yporel), _dp(self.bd2oc), _dp(self.ddynoc)))
+        Handle.__init__(self, cfg, dict(amatoc=A, rdm2oc=rdm2, ctl2moc=cl2m, ctm2loc=cm2l, aoc=self.aoc, bd2oc=self.bd2oc,
+                                        yporel=self.yporel, ddynoc=self.ddynoc), device, atmos=atmos)
         # homsol
         if consts is not None and ("ochom" in consts or "pch1oc" in consts):
             self.homog = consts
@@ -363,40 +161,19 @@ class OceanModel:
             self.homog = hostinit.homsol_cyc(cfg, rdm2, self.bd2oc, self.yporel, self.helmholtz)
         else:
             self.homog = hostinit.homsol_box(cfg, rdm2, cm2l, self.bd2oc, self.helmholtz)
-        hg = self.homog
         if cfg.cyclic:
-            args = [_f(hg["pch1oc"]), _f(hg["pch2oc"]), np.ascontiguousarray(hg["pbhoc"]),
-                    *[np.ascontiguousarray(hg[k], dtype=np.float64) for k in ("aipcho", "hc1soc", "hc2soc", "hc1noc", "hc2noc")]]
-            self._keep = args
-            check(self.L.qgcm_hip_set_homog_cyc(self.h, *[_dp(a) for a in args], float(hg["hbsioc"]), float(hg["aipbho"])))
+            self.set_homog_cyc(self.homog)
         else:
-            args = [_f(hg["ochom"]), _f(hg["cdiffo"]), _f(hg["cdhoc"])]
-            check(self.L.qgcm_hip_set_homog_box(self.h, *[_dp(a) for a in args]))
-        self.nscal = 2 * (nl - 1) + 4 * nl
+            self.set_homog_box(self.homog)
         self.step_index = 1  # next 1-based ocean step
         if getattr(cfg, "l_spl", 0.0) > 0.0:  # a -Dsponge_layer_k247 configuration
             self.set_sponge(hostinit.sponge_ramp(cfg), cfg.c1_spl)
-
-    # -- life cycle ----------------------------------------------------------
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.L.qgcm_hip_destroy(self.h)
-            self.h = C.c_void_p()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
-
-    def thomas_plan(self):
-        """[(first, count)] per segment of the column's interior rows (lib.thomas_plan); one entry: the single launch."""
-        from .lib import thomas_plan
-        return thomas_plan(self.h)
-
-    def _f3(self):
-        c = self.cfg
-        return np.zeros((c.nxpo, c.nypo, c.nlo), order="F")
 
     # -- state ----------------------------------------------------------------
     def set_p(self, po, pom=None):
@@ -430,66 +207,20 @@ class OceanModel:
         check(self.L.qgcm_hip_prsamp(self.h, _dp(out)))
         return prsamp_dict(out, nl)
 
-    def set_state(self, po=None, pom=None, qo=None, qom=None):
-        a = [_f(x) for x in (po, pom, qo, qom)]
-        check(self.L.qgcm_hip_set_state(self.h, *[_dp(x) for x in a]))
-
-    def get_state(self):
-        a = [self._f3() for _ in range(4)]
-        check(self.L.qgcm_hip_get_state(self.h, *[_dp(x) for x in a]))
-        return a
-
     po = property(lambda self: self.get_state()[0])
     pom = property(lambda self: self.get_state()[1])
     qo = property(lambda self: self.get_state()[2])
     qom = property(lambda self: self.get_state()[3])
-
-    def set_forcing(self, wekpo=None, entoc=None, xon=None):
-        w, e = _f(wekpo), _f(entoc)
-        x = None if xon is None else np.ascontiguousarray(xon, dtype=np.float64)
-        check(self.L.qgcm_hip_set_forcing(self.h, _dp(w), _dp(e), _dp(x)))
 
     def tend_zero_mask(self):
         """Which of entoc (bit 0) and ddynoc (bit 1) the next tendency launch leaves out because the library knows
         them to be all zero (qgcm_hip_tend_zero_mask); the results do not depend on it."""
         return int(self.L.qgcm_hip_tend_zero_mask(self.h))
 
-    def set_cyc_forcing(self, txisoc, txinoc, enisoc=None, eninoc=None):
-        nl = self.cfg.nlo
-        es = np.zeros(nl - 1) if enisoc is None else np.ascontiguousarray(enisoc, dtype=np.float64)
-        en = np.zeros(nl - 1) if eninoc is None else np.ascontiguousarray(eninoc, dtype=np.float64)
-        check(self.L.qgcm_hip_set_cyc_forcing(self.h, float(txisoc), float(txinoc), _dp(es), _dp(en)))
-
-    def set_sponge(self, r_spl, c1_spl):
-        """The fork's sponge layer (src/qgosubs.F:203-205): ramp r_spl(nxpo, nypo) and the constant c1_spl;
-        r_spl = None switches the term off."""
-        if r_spl is None:
-            check(self.L.qgcm_hip_set_sponge(self.h, None, 0.0))
-            return
-        r = _f(r_spl)
-        assert r.shape == (self.cfg.nxpo, self.cfg.nypo)
-        check(self.L.qgcm_hip_set_sponge(self.h, _dp(r), float(c1_spl)))
-
-    def set_scalars(self, s):
-        s = np.ascontiguousarray(s, dtype=np.float64)
-        assert s.size == self.nscal
-        check(self.L.qgcm_hip_set_scalars(self.h, _dp(s)))
-
-    def get_scalars(self):
-        s = np.zeros(self.nscal)
-        check(self.L.qgcm_hip_get_scalars(self.h, _dp(s)))
-        return s
-
-    def get_monitors(self):
-        """(ermaso, emfroc) of the last ocinvq of a zonally cyclic ocean (src/ocisubs.F:268-283; atmosphere: ermasa,
-        emfrat): nlo-1 values each."""
-        e, f = np.zeros(self.cfg.nlo - 1), np.zeros(self.cfg.nlo - 1)
-        check(self.L.qgcm_hip_get_monitors(self.h, _dp(e), _dp(f)))
-        return e, f
-
     def get_bsums(self):
         """ajisoc, ajinoc, ap5soc, ap5noc (nlo each): the boundary line sums of the last qgostep of a zonally cyclic
-        ocean (valid after the following ocinvq)."""
+        ocean (valid after the following ocinvq).  On an atmosphere: ajisat, ajinat, ap5sat, ap5nat (nla each) of the
+        last qgastep (valid after the following atinvq)."""
         b = np.zeros(4 * self.cfg.nlo)
         check(self.L.qgcm_hip_get_bsums(self.h, _dp(b)))
         return b
@@ -503,17 +234,11 @@ class OceanModel:
         return x, cf[:n].copy()
 
     # -- the path (same names as the reference's module procedures) ------------
-    def qgostep(self):
-        check(self.L.qgcm_hip_qgostep(self.h))
-
     def ocinvq(self):
         check(self.L.qgcm_hip_ocinvq(self.h))
 
     def ocqbdy(self):
         check(self.L.qgcm_hip_ocqbdy(self.h))
-
-    def lf_average(self):
-        check(self.L.qgcm_hip_lf_average(self.h))
 
     def ocqbdy_host(self, q, p):
         """`call ocqbdy (q, p)` / `call atqzbd (q, p)` on host arrays (start-up use, src/q-gcm.F:724-725, 743-744):
@@ -528,13 +253,7 @@ class OceanModel:
         check(self.L.qgcm_hip_steps(self.h, s0, int(n)))
         self.step_index = s0 + int(n)
 
-    def sync(self):
-        check(self.L.qgcm_hip_sync(self.h))
-
     # -- validity scan (`call valids (solnok)`, src/q-gcm.F:1278) --
-    def set_dtopoc(self, dtopoc):
-        check(self.L.qgcm_hip_set_dtopoc(self.h, _dp(_f(dtopoc))))
-
     def valids(self):
         """(solnok, out): out = min/max of po, qo, sst, wekto, layer thickness top/intermediate/bottom,
         then hfbad(1..nlo) in per cent (src/valsubs.F:272-527)."""
@@ -544,19 +263,6 @@ class OceanModel:
         return bool(ok.value), out
 
     # -- ocean monitors (ocean half of `call monnc_comp` + couroc, src/monitor_diag.F) --
-    def set_monitor_params(self, oml=None, rhooc=None, cpoc=None, hmoc=None, ycexp=None, sb_hflux=None, nb_hflux=None):
-        """Constants of MODULE occonst / intrfac that monnc_comp and couroc read and the handle does not hold:
-        rhooc, cpoc, and hmoc, ycexp, sb_hflux, nb_hflux of couroc's mixed-layer velocities.  Defaults come from
-        `oml` (a qgcm_hip.OmlConfig; its defaults are the examples' input.params values)."""
-        p = mon_params(oml, rhooc, cpoc, hmoc, ycexp, sb_hflux, nb_hflux)
-        check(self.L.qgcm_hip_set_mon_params(self.h, C.byref(p)))
-
-    def set_monitor_fields(self, tauxo=None, tauyo=None, wekto=None, sst=None):
-        """tauxo, tauyo (nxpo,nypo), wekto, sst (nxto,nyto): the fields the monitors read that do not evolve on the
-        device without the mixed layer (with it on, its own arrays are read).  None = leave unchanged."""
-        a = [_f(x) for x in (tauxo, tauyo, wekto, sst)]
-        check(self.L.qgcm_hip_set_monitor_fields(self.h, *[_dp(x) for x in a]))
-
     def monitor_vector(self):
         """The packed result of qgcm_hip_monitors (order: include/qgcm_hip.h)."""
         out = np.zeros(self.L.qgcm_hip_monitor_len(self.h))
@@ -569,18 +275,6 @@ class OceanModel:
         return unpack_monitors(self.monitor_vector(), self.cfg.nlo)
 
     # -- area averages and the CFL check (`call areavg`, `call cfltry`) ---------------------------------
-    def set_areas(self, xlo=None, xhi=None, ylo=None, yhi=None, tables=None):
-        """The areas of areavg: their limits in metres from the domain's south-west corner, as `areas.limits` gives
-        them (hostinit.read_areas_limits; at most nine), or the finished `tables` of hostinit.area_limits.  Returns
-        the tables (subscripts 1-based, weights)."""
-        if tables is None:
-            from .hostinit import area_limits
-            cfg = self.cfg
-            tables = area_limits(xlo, xhi, ylo, yhi, cfg.dxo, cfg.dyo, cfg.nxto, cfg.nyto,
-                                 fluid="atmos." if getattr(cfg, "atmos", False) else "ocean")
-        set_area_tables(self.L, self.h, tables)
-        return tables
-
     def area_averages(self, parts=False):
         """tavoc (tavat on an atmosphere) of one `call areavg`: the weighted averages of sst (ast) at its current
         level over the areas of set_areas, from the device.  parts: (averages, numerators, denominators) of areint."""
@@ -600,48 +294,20 @@ class OceanModel:
         return cfl_dict(self.cfg, mx, nb, loc)
 
     # -- time averages (avg_ocn_k247 / ocnc_avgout_k247, tavocn / tavout) --------------------------
-    def enable_po_mean(self, on=True):
-        """Start (at zero) or stop the running sum of po: while on, every step of steps() adds its po after ocqbdy
-        and before the leapfrog averaging (avg_ocn_k247, src/q-gcm.F:1250-1252)."""
-        check(self.L.qgcm_hip_poavg_enable(self.h, int(bool(on))))
-
     def po_mean(self, reset=False, count=False):
         """po_avg * (1/nsum) (nxpo, nypo, nlo), as ocnc_avgout_k247 scales it; reset=True then zeroes sum and count.
         count=True returns (mean, nsum)."""
-        a, n = read_po_mean(self.L, self.h, self.cfg, self.cfg.nypo, reset)
+        a, n = Handle.po_mean(self, reset)
         return (a, n) if count else a
-
-    def set_time_mean_params(self, oml=None, **kw):
-        """hmoc, ycexp, tsbdy, tnbdy, sb_hflux, nb_hflux of tavocn (defaults from `oml`, a qgcm_hip.OmlConfig).
-        Without this call the mixed layer's parameters are used."""
-        check(self.L.qgcm_hip_set_tav_params(self.h, C.byref(tav_params(oml, **kw))))
-
-    def set_time_mean_fields(self, fnetoc=None):
-        """fnetoc (nxto, nyto) for tavocn without the mixed layer (zero if never given)."""
-        check(self.L.qgcm_hip_set_tav_fields(self.h, _dp(_f(fnetoc))))
-
-    def tavocn(self):
-        """One tavocn contribution from the device state (src/timavge.F:425-619)."""
-        check(self.L.qgcm_hip_tavocn(self.h))
 
     def time_means(self, names=None):
         """tavout's means (src/timavge.F:667-880) keyed by the reference's names (TAV_LAYOUT), plus "nsumoc".  The
         sums are not changed.  names: the subset to compute and copy (None = all)."""
-        out, n = read_time_means(self.L, self.h, self.cfg, self.cfg.nypo, self.cfg.nyto, names)
+        out, n = Handle.time_means(self, names)
         out["nsumoc"] = n
         return out
 
-    def reset_time_means(self):
-        """tavini: zero the sums and the count."""
-        check(self.L.qgcm_hip_tav_reset(self.h))
-
     # -- periodic ocean dumps (qocdiag_out, ocnc_out; DESIGN 6g) ---------------------------------------------------
-    def vorticity_budget(self, nsko=1):
-        """qocdiag_out's terms from the device state (po, pom, qo, qom, the wekpo given, the entoc on the device):
-        dict dqdt, qotjac, qt2dif, qt4dif, qotent of (nlo, jpwk, ipwk) arrays at the points (1+i*nsko, 1+j*nsko).
-        The reference's dump when called between oml() and qgostep(), or at any time with the mixed layer off."""
-        return read_budget(self.L, self.h, self.cfg, nsko)
-
     def schedule_vorticity_budget(self, nsko, every, capacity=1):
         """Record the budget inside steps() on every step s with (s-1) % every == 0, after the step's oml and before
         its tendency, into a device ring of `capacity` snapshots.  every = 0 removes the schedule."""
@@ -663,37 +329,7 @@ class OceanModel:
         ip = subsample_count(self.cfg.nxpo, nsko)
         return [(st[r], unpack_budget(out[r * ln:(r + 1) * ln], self.cfg.nlo, ip)) for r in range(got.value)]
 
-    def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
-        """ocnc_out's subsampled fields (the selected ones): sst, wekto (jtwk, itwk); po, qo (nlo, jpwk, ipwk);
-        h (nlo-1, jpwk, ipwk); tauxo, tauyo (jpwk, ipwk)."""
-        return read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
-
     # -- ocean mixed layer (`call oml`, src/q-gcm.F:1232; SURVEY 8 row f1) -------
-    def oml_init(self, om):
-        """Switch the mixed layer on (om: qgcm_hip.config.OmlConfig): steps() then runs oml before
-        qgostep in every step and averages sst with the other fields."""
-        from .lib import OmlParams
-        p = OmlParams()
-        p.hmoc, p.toc1, p.toc2, p.st2d, p.st4d = om.hmoc, om.toc[0], om.toc[1], om.st2d, om.st4d
-        p.ycexp, p.rrcpoc, p.tsbdy, p.tnbdy = om.ycexp, om.rrcpoc, om.tsbdy, om.tnbdy
-        p.sb_hflux, p.nb_hflux = int(om.sb_hflux), int(om.nb_hflux)
-        check(self.L.qgcm_hip_oml_init(self.h, C.byref(p)))
-
-    def oml_set_state(self, sst=None, sstm=None):
-        a = [_f(x) for x in (sst, sstm)]
-        for x in a:
-            assert x is None or x.shape == (self.cfg.nxto, self.cfg.nyto)
-        check(self.L.qgcm_hip_oml_set_state(self.h, *[_dp(x) for x in a]))
-
-    def oml_get_state(self):
-        a = [np.zeros((self.cfg.nxto, self.cfg.nyto), order="F") for _ in range(2)]
-        check(self.L.qgcm_hip_oml_get_state(self.h, *[_dp(x) for x in a]))
-        return a
-
-    def oml_set_forcing(self, fnetoc=None, wekto=None, tauxo=None, tauyo=None):
-        a = [_f(x) for x in (fnetoc, wekto, tauxo, tauyo)]
-        check(self.L.qgcm_hip_oml_set_forcing(self.h, *[_dp(x) for x in a]))
-
     def oml(self):
         check(self.L.qgcm_hip_oml(self.h))
 
@@ -704,19 +340,11 @@ class OceanModel:
         check(self.L.qgcm_hip_oml_get_diag(self.h, _dp(e), _dp(d)))
         return e, d
 
-    # -- the row transforms by themselves (replacements of FFTPACK's dsint / drfftf / drfftb) -------------------
+    # -- the work array and the Helmholtz solve by themselves ---------------------------------------------------
     def wrk_set(self, wrk):
         w = _f(wrk)
         assert w.shape == (self.cfg.nxpo, self.cfg.nypo, self.cfg.nlo)
         check(self.L.qgcm_hip_wrk_set(self.h, _dp(w)))
-
-    def wrk_get(self):
-        w = np.zeros((self.cfg.nxpo, self.cfg.nypo, self.cfg.nlo), order="F")
-        check(self.L.qgcm_hip_wrk_get(self.h, _dp(w)))
-        return w
-
-    def row_transform(self, inverse):
-        check(self.L.qgcm_hip_row_transform(self.h, int(inverse)))
 
     def helmholtz(self, wrk, boc):
         """hsbxoc / hscyoc replacement (src/ocisubs.F:415-618); returns the solution."""
@@ -741,30 +369,10 @@ class OceanModel:
         check(self.L.qgcm_hip_prepare_steps(self.h, s0, int(n)))
 
     # -- covariance matrices (covini / covocn and covout's arrays, src/covaria_diag.F) ---------------------
-    _COV_NAMES = COV_NAMES_OCN
-
-    def enable_covariance(self, nsi=16):
-        """covini: allocate and zero the p and T matrices (nvar(nvar+1)/2 entries each, nvar = (nxt/nsi)*(nyt/nsi)),
-        the means and the counts.  nsi = 0 frees them."""
-        check(self.L.qgcm_hip_cov_init(self.h, int(nsi), 0, 1))
-
     def covocn(self):
         """One covocn contribution from the device state (po layer 1; sst of the mixed layer, else of
         set_monitor_fields)."""
         check(self.L.qgcm_hip_cov_add(self.h))
-
-    def covariance(self, k0=None, count=None):
-        """covout's arrays keyed by the reference's names (covpo, avgpo, swtpo, nupo, covto, ...); the matrices as the
-        packed entries k0 .. k0+count-1 (default all; 0-based k = i(i+1)/2 + j, j <= i)."""
-        return read_covariance(self.L, self.h, self._COV_NAMES, k0, count)
-
-    def covariance_size(self):
-        """dict nvar, nmat, k0, k1."""
-        return cov_size(self.L, self.h)
-
-    def reset_covariance(self):
-        """covini again: matrices, means and counts to zero."""
-        check(self.L.qgcm_hip_cov_reset(self.h))
 
     def schedule_covariance(self, every, phase=0):
         """Add a contribution inside steps() / coupled_steps() after every step s with s % every == phase (after the
@@ -836,12 +444,6 @@ class AtmosModel(OceanModel):
     def atqzbd(self):
         check(self.L.qgcm_hip_atqzbd(self.h))
 
-    def get_bsums(self):
-        """ajisat, ajinat, ap5sat, ap5nat (nla each) of the last qgastep (valid after the following atinvq)."""
-        b = np.zeros(4 * self.cfg.nlo)
-        check(self.L.qgcm_hip_get_bsums(self.h, _dp(b)))
-        return b
-
     # -- atmosphere monitors and valids (atmosphere half of `call monnc_comp` + courat, valids; DESIGN 6h) ---------
     def set_atm_monitor_params(self, ocean=None, **kw):
         """Constants of MODULE atconst / radiate / parameters that monnc_comp reads and the handle does not hold;
@@ -895,7 +497,7 @@ class AtmosModel(OceanModel):
             raise QgcmHipError("unknown time means %s (ATM_TAV_LAYOUT)" % sorted(unknown))
         nxp, nyp, nl = self.cfg.nxpa, self.cfg.nypa, self.cfg.nla
         shape = dict(p=(nxp, nyp), t=(nxp - 1, nyp - 1), p3=(nxp, nyp, nl), u=(nxp, nyp - 1), v=(nxp - 1, nyp))
-        out, n = _read_means(ATM_TAV_LAYOUT, self.L.qgcm_hip_atm_tav_out, ATM_TAV_NOUT, self.h, shape, names)
+        out, n = read_means(ATM_TAV_LAYOUT, self.L.qgcm_hip_atm_tav_out, ATM_TAV_NOUT, self.h, shape, names)
         out["nsumat"] = n
         return out
 
@@ -915,7 +517,7 @@ class AtmosModel(OceanModel):
         c, L = self.cfg, self.L
         counts = lambda: dict(p=(subsample_count(c.nypa, nska), subsample_count(c.nxpa, nska)),
                               t=(subsample_count(c.nypa - 1, nska), subsample_count(c.nxpa - 1, nska)))
-        return _read_dump(ATNC_FIELDS, L.qgcm_hip_atnc_sample_len, L.qgcm_hip_atnc_sample, self.h, nska, outflat, c.nla,
+        return read_dump(ATNC_FIELDS, L.qgcm_hip_atnc_sample_len, L.qgcm_hip_atnc_sample, self.h, nska, outflat, c.nla,
                           counts)
 
     # -- covariance matrices (covatm): pa layer 1 and ast of set_atm_monitor_fields -------------------------
@@ -1081,6 +683,43 @@ def xforc_get(ocean, atmos, names=None):
 HEAT_SCALARS = ("arlaav", "slhfav", "oradav", "arocav")
 
 
+def _heat_params(who, p, atmos, ocean_cfg, heat, hmadmp, hmat, coords, **fs):
+    """What xforc_heat_setup and xforc_sst_setup (`who`, for the messages) share: fills into `p` (XforcHeatParams /
+    XforcSstParams) the radiation constants of `heat`, hmadmp, hmat (default: what aml_init was given), the tables
+    fs = fsa[, fso] (None: hostinit.fsprim) and the coordinates xta, yta, xto, yto of hostinit.grid_coordinates with the
+    ocean where xforc_setup placed it, overridden by `coords`.  Returns the arrays `p` points to: keep them until the
+    library has copied them."""
+    am = getattr(atmos, "aml_cfg", None)
+    if (hmadmp is None or hmat is None) and am is None:
+        raise QgcmHipError("%s: call atmos.aml_init first (qgcm_hip_aml_init has not been called)" % who)
+    nx1, ny1 = getattr(atmos, "xforc_origin", (None, None))  # the position xforc_setup was given
+    G = hostinit.grid_coordinates(atmos.cfg, ocean_cfg, nx1=nx1, ny1=ny1)
+    if coords is not None:
+        G = dict(G, **coords)
+    for name, rel in (("fsa", "ytarel"), ("fso", "ytorel")):
+        if name in fs:
+            G[name] = hostinit.fsprim(G[rel], heat.fspco, G["yla"]) if fs[name] is None else fs[name]
+    a, o = atmos.cfg, ocean_cfg
+    want = dict(fsa=a.nyta, fso=o.nyto, xta=a.nxta, yta=a.nyta, xto=o.nxto, yto=o.nyto)
+    keep = []
+    for name in list(fs) + ["xta", "yta", "xto", "yto"]:
+        v = np.ascontiguousarray(G[name], dtype=np.float64)
+        if v.shape != (want[name],):
+            raise QgcmHipError("%s: %s has shape %s, need (%d,)" % (who, name, v.shape, want[name]))
+        setattr(p, name, _dp(v))
+        keep.append(v)
+    for k in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup", "C1down"):
+        setattr(p, k, float(getattr(heat, k)))
+    p.hmadmp = float(am.hmadmp if hmadmp is None else hmadmp)
+    p.hmat = float(am.hmat if hmat is None else hmat)
+    return keep
+
+
+def _heat_out(sc, **fields):
+    """dict of the fields and the HEAT_SCALARS `sc` of qgcm_hip_xforc_heat_get / qgcm_hip_xforc_sst_get."""
+    return dict(fields, **{k: float(v) for k, v in zip(HEAT_SCALARS, sc)})
+
+
 def xforc_heat_setup(ocean, atmos, heat, hmadmp=None, hmat=None, fsa=None, fso=None, coords=None):
     """Set up the heat half of xforc on the device (qgcm_hip_xforc_heat_init) after xforc_setup(ocean,
     atmos), atmos.aml_init and ocean.oml_init: xforc() and coupled_steps(..., xforc=True) then also compute fnetoc
@@ -1089,29 +728,12 @@ def xforc_heat_setup(ocean, atmos, heat, hmadmp=None, hmat=None, fsa=None, fso=N
     (default hostinit.fsprim); coords: dict(xta, yta, xto, yto), default hostinit.grid_coordinates with the ocean
     placed where xforc_setup placed it (its nx1, ny1)."""
     from .lib import XforcHeatParams
-    if ocean is None:  # (the library's own refusal: no coordinate can be derived without an ocean, so nothing else is passed)
-        check(atmos.L.qgcm_hip_xforc_heat_init(None, atmos.h, C.byref(XforcHeatParams())))
-    am = getattr(atmos, "aml_cfg", None)
-    if (hmadmp is None or hmat is None) and am is None:
-        raise QgcmHipError("xforc_heat_setup: call atmos.aml_init first (qgcm_hip_aml_init has not been called)")
-    nx1, ny1 = getattr(atmos, "xforc_origin", (None, None))  # the position xforc_setup was given
-    G = hostinit.grid_coordinates(atmos.cfg, ocean.cfg, nx1=nx1, ny1=ny1)
-    if coords is not None:
-        G = dict(G, **coords)
-    fsa = hostinit.fsprim(G["ytarel"], heat.fspco, G["yla"]) if fsa is None else fsa
-    fso = hostinit.fsprim(G["ytorel"], heat.fspco, G["yla"]) if fso is None else fso
-    keep = [np.ascontiguousarray(v, dtype=np.float64) for v in (fsa, fso, G["xta"], G["yta"], G["xto"], G["yto"])]
-    want = (atmos.cfg.nyta, ocean.cfg.nyto, atmos.cfg.nxta, atmos.cfg.nyta, ocean.cfg.nxto, ocean.cfg.nyto)
-    for v, n, name in zip(keep, want, ("fsa", "fso", "xta", "yta", "xto", "yto")):
-        if v.shape != (n,):
-            raise QgcmHipError("xforc_heat_setup: %s has shape %s, need (%d,)" % (name, v.shape, n))
     p = XforcHeatParams()
-    for k in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup", "C1down"):
-        setattr(p, k, float(getattr(heat, k)))
-    p.hmadmp = float(am.hmadmp if hmadmp is None else hmadmp)
-    p.hmat = float(am.hmat if hmat is None else hmat)
-    p.fsa, p.fso, p.xta, p.yta, p.xto, p.yto = [_dp(v) for v in keep]
+    if ocean is None:  # (the library's own refusal: no coordinate can be derived without an ocean, so nothing else is passed)
+        check(atmos.L.qgcm_hip_xforc_heat_init(None, atmos.h, C.byref(p)))
+    keep = _heat_params("xforc_heat_setup", p, atmos, ocean.cfg, heat, hmadmp, hmat, coords, fsa=fsa, fso=fso)
     check(atmos.L.qgcm_hip_xforc_heat_init(ocean.h, atmos.h, C.byref(p)))
+    del keep  # (copied by now)
 
 
 def xforc_heat_get(ocean, atmos):
@@ -1120,9 +742,7 @@ def xforc_heat_get(ocean, atmos):
     o, a = ocean.cfg, atmos.cfg
     fo, fa, sc = np.zeros((o.nxto, o.nyto), order="F"), np.zeros((a.nxta, a.nyta), order="F"), np.zeros(4)
     check(atmos.L.qgcm_hip_xforc_heat_get(ocean.h if ocean is not None else None, atmos.h, _dp(fo), _dp(fa), _dp(sc)))
-    out = dict(fnetoc=fo, fnetat=fa)
-    out.update({k: float(v) for k, v in zip(HEAT_SCALARS, sc)})
-    return out
+    return _heat_out(sc, fnetoc=fo, fnetat=fa)
 
 
 def xforc_sst_setup(atmos, ocean_cfg, heat, sst, hmadmp=None, hmat=None, fsa=None, coords=None):
@@ -1134,32 +754,16 @@ def xforc_sst_setup(atmos, ocean_cfg, heat, sst, hmadmp=None, hmat=None, fsa=Non
     was given.  fsa: the table fsprim(ytarel(1:nyta)) (default hostinit.fsprim); coords: dict(xta, yta, xto, yto),
     default hostinit.grid_coordinates with the sea placed where xforc_setup placed it (its nx1, ny1)."""
     from .lib import XforcSstParams
-    am = getattr(atmos, "aml_cfg", None)
-    if (hmadmp is None or hmat is None) and am is None:
-        raise QgcmHipError("xforc_sst_setup: call atmos.aml_init first (qgcm_hip_aml_init has not been called)")
-    nx1, ny1 = getattr(atmos, "xforc_origin", (None, None))  # the position xforc_setup was given
-    G = hostinit.grid_coordinates(atmos.cfg, ocean_cfg, nx1=nx1, ny1=ny1)
-    if coords is not None:
-        G = dict(G, **coords)
-    fsa = hostinit.fsprim(G["ytarel"], heat.fspco, G["yla"]) if fsa is None else fsa
-    keep = [np.ascontiguousarray(v, dtype=np.float64) for v in (fsa, G["xta"], G["yta"], G["xto"], G["yto"])]
-    want = (atmos.cfg.nyta, atmos.cfg.nxta, atmos.cfg.nyta, ocean_cfg.nxto, ocean_cfg.nyto)
-    for v, n, name in zip(keep, want, ("fsa", "xta", "yta", "xto", "yto")):
-        if v.shape != (n,):
-            raise QgcmHipError("xforc_sst_setup: %s has shape %s, need (%d,)" % (name, v.shape, n))
+    p = XforcSstParams()
+    keep = _heat_params("xforc_sst_setup", p, atmos, ocean_cfg, heat, hmadmp, hmat, coords, fsa=fsa)
     s = _f(sst)
     if s is None or s.shape != (ocean_cfg.nxto, ocean_cfg.nyto):
         raise QgcmHipError("xforc_sst_setup: sst has shape %s, need (%d, %d)" % (None if s is None else s.shape,
                                                                                  ocean_cfg.nxto, ocean_cfg.nyto))
-    p = XforcSstParams()
-    for k in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup", "C1down"):
-        setattr(p, k, float(getattr(heat, k)))
-    p.hmadmp = float(am.hmadmp if hmadmp is None else hmadmp)
-    p.hmat = float(am.hmat if hmat is None else hmat)
-    p.fsa, p.xta, p.yta, p.xto, p.yto = [_dp(v) for v in keep]
     p.dxo, p.dyo = float(ocean_cfg.dxo), float(ocean_cfg.dyo)
     p.sst = _dp(s)
     check(atmos.L.qgcm_hip_xforc_sst_init(atmos.h, C.byref(p)))
+    del keep  # (copied by now)
     atmos.sst_shape = (int(ocean_cfg.nxto), int(ocean_cfg.nyto))
 
 
@@ -1180,9 +784,7 @@ def xforc_sst_get(atmos):
     a = atmos.cfg
     fa, sc = np.zeros((a.nxta, a.nyta), order="F"), np.zeros(4)
     check(atmos.L.qgcm_hip_xforc_sst_get(atmos.h, _dp(fa), _dp(sc)))
-    out = dict(fnetat=fa)
-    out.update({k: float(v) for k, v in zip(HEAT_SCALARS, sc)})
-    return out
+    return _heat_out(sc, fnetat=fa)
 
 
 def coupled_steps(ocean, atmos, nt0, n, nstr, xforc=False):

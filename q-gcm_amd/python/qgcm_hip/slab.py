@@ -29,7 +29,9 @@ import ctypes as C
 import numpy as np
 
 from . import hostinit
-from .lib import Params, check, load_library
+from .handle import TAV_LAYOUT, Handle, _dp, subsample_count
+from .lib import check, load_library
+from .model import cfl_dict, cov_row_split, prsamp_dict, unpack_monitors
 
 HALO = 3
 
@@ -198,70 +200,33 @@ def broadcast_unique_id(dist, device, group=None):
 # --------------------------------------------------------------------------
 # one slab on one GPU through the C ABI
 # --------------------------------------------------------------------------
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-class HipSlab:
-    """The slab kernels of include/qgcm_hip.h ("y-slab building blocks")."""
+class HipSlab(Handle):
+    """The slab kernels of include/qgcm_hip.h ("y-slab building blocks") on the handle that owns the global rows
+    g0..g1; what it shares with the whole-domain OceanModel is Handle's."""
 
     def __init__(self, cfg, consts, g0, g1, rank, nranks, device=-1, sync_each_call=False):
         import torch
         self.torch = torch
-        self.cfg, self.rank, self.nranks = cfg, rank, nranks
-        self.g0, self.g1 = g0, g1
-        self.L = load_library()
-        nl, nyg = cfg.nlo, cfg.nypo
-        self.nyl, self.joff, self.jlo, self.jhi = local_rows(nyg, g0, g1)
-        sl = slab_slice(nyg, g0, g1)
-        p = Params()
-        p.nxpo, p.nypo, p.nlo, p.cyclic = cfg.nxpo, nyg, nl, int(cfg.cyclic)
-        p.fnot, p.beta, p.dxo, p.dyo = cfg.fnot, cfg.beta, cfg.dxo, cfg.dyo
-        p.tdto, p.delek, p.bccooc, p.aoc = cfg.tdto, cfg.delek, cfg.bccooc, consts["aoc"]
-        p.slab_g0, p.slab_g1 = g0, g1
-        for k in range(nl):
-            p.ah2oc[k], p.ah4oc[k], p.hoc[k], p.rdm2oc[k] = cfg.ah2oc[k], cfg.ah4oc[k], cfg.hoc[k], consts["rdm2oc"][k]
-        for k in range(nl - 1):
-            p.gpoc[k] = cfg.gpoc[k]
-        for name in ("amatoc", "ctl2moc", "ctm2loc"):
-            arr = getattr(p, name)
-            for i, v in enumerate(np.asarray(consts[name]).ravel(order="F")):
-                arr[i] = v
-        self.h = C.c_void_p()
-        check(self.L.qgcm_hip_create(C.byref(self.h), C.byref(p), int(device)))
-        yp = np.ascontiguousarray(consts["yporel"][sl])
-        bd2 = np.ascontiguousarray(consts["bd2oc"])
-        dd = np.asfortranarray(consts["ddynoc"][:, sl])
-        check(self.L.qgcm_hip_set_grid(self.h, _dp(yp), _dp(bd2), _dp(dd)))
-        self.consts = consts
-        if cfg.cyclic:
-            # the homogeneous solutions of a channel depend on y only (conhoms.F:376-543): local slices + global scalars
-            hg = consts
-            args = [np.asfortranarray(hg["pch1oc"][sl, :]), np.asfortranarray(hg["pch2oc"][sl, :]),
-                    np.ascontiguousarray(hg["pbhoc"][sl]),
-                    *[np.ascontiguousarray(hg[k], dtype=np.float64) for k in ("aipcho", "hc1soc", "hc2soc", "hc1noc", "hc2noc")]]
-            check(self.L.qgcm_hip_set_homog_cyc(self.h, *[_dp(a) for a in args], float(hg["hbsioc"]), float(hg["aipbho"])))
-        elif "ochom" in consts:  # global homogeneous solutions given; else SlabOcean.homsol() computes them on the slabs
-            self.set_homog(np.asfortranarray(consts["ochom"][:, sl, :]), consts["cdiffo"], consts["cdhoc"])
+        self.g0, self.g1, self.consts = g0, g1, consts
         self.sync_each_call = sync_each_call
+        _, self.joff, self.jlo, self.jhi = local_rows(cfg.nypo, g0, g1)
+        Handle.__init__(self, cfg, consts, device, g=(g0, g1), p_rows=slab_slice(cfg.nypo, g0, g1), rank=rank, nranks=nranks)
+        if cfg.cyclic:
+            self.set_homog_cyc(consts)
+        elif "ochom" in consts:  # global homogeneous solutions given; else SlabOcean.homsol() computes them on the slabs
+            self.set_homog_box(consts)
         self.device = torch.device("cuda", torch.cuda.current_device() if device < 0 else device)
-        self.th_len = self.L.qgcm_hip_thomas_msg_len(self.h)
         self.cst_len = self.L.qgcm_hip_thomas_const_len(self.h)
-        self.halo_len = self.L.qgcm_hip_halo_msg_len(self.h)
         self.stream_ptr = self.L.qgcm_hip_stream(self.h)
         self.oml_on = False
+        self._msg_lens()
 
-    def set_homog(self, ochom_local, cdiffo, cdhoc):
-        oh, cd, ch = np.asfortranarray(ochom_local), np.asfortranarray(cdiffo), np.asfortranarray(cdhoc)
-        check(self.L.qgcm_hip_set_homog_box(self.h, _dp(oh), _dp(cd), _dp(ch)))
+    def _msg_lens(self):
+        self.th_len = self.L.qgcm_hip_thomas_msg_len(self.h)
+        self.halo_len = self.L.qgcm_hip_halo_msg_len(self.h)
 
     def wrk_fill(self, v):
         check(self.L.qgcm_hip_wrk_fill(self.h, float(v))); self._done()
-
-    def wrk_get(self):
-        w = np.zeros((self.cfg.nxpo, self.nyl, self.cfg.nlo), order="F")
-        check(self.L.qgcm_hip_wrk_get(self.h, _dp(w)))
-        return w
 
     def area_integrals(self):
         x = np.zeros(self.cfg.nlo)
@@ -280,123 +245,14 @@ class HipSlab:
         if self.sync_each_call:
             check(self.L.qgcm_hip_sync(self.h))
 
-    def sync(self):
-        check(self.L.qgcm_hip_sync(self.h))
-
-    def close(self):
-        if self.h:
-            self.L.qgcm_hip_destroy(self.h)
-            self.h = None
-
-    # state (local blocks incl. halos) ---------------------------------------
-    def set_state(self, po, pom, qo, qom):
-        a = [np.asfortranarray(x, dtype=np.float64) for x in (po, pom, qo, qom)]
-        check(self.L.qgcm_hip_set_state(self.h, *[_dp(x) for x in a]))
-
-    def get_state(self):
-        a = [np.zeros((self.cfg.nxpo, self.nyl, self.cfg.nlo), order="F") for _ in range(4)]
-        check(self.L.qgcm_hip_get_state(self.h, *[_dp(x) for x in a]))
-        return a
-
-    def set_forcing(self, wekpo, entoc, xon):
-        w, e = np.asfortranarray(wekpo, dtype=np.float64), np.asfortranarray(entoc, dtype=np.float64)
-        x = np.ascontiguousarray(xon, dtype=np.float64)
-        check(self.L.qgcm_hip_set_forcing(self.h, _dp(w), _dp(e), _dp(x)))
-
-    def set_cyc_forcing(self, txisoc, txinoc, enisoc=None, eninoc=None):
-        nl = self.cfg.nlo
-        es = np.zeros(nl - 1) if enisoc is None else np.ascontiguousarray(enisoc, dtype=np.float64)
-        en = np.zeros(nl - 1) if eninoc is None else np.ascontiguousarray(eninoc, dtype=np.float64)
-        check(self.L.qgcm_hip_set_cyc_forcing(self.h, float(txisoc), float(txinoc), _dp(es), _dp(en)))
-
-    # ocean mixed layer (T grid: row j between p rows j and j+1; local arrays hold rows 1..nyl-1 of the slab view) ------
     def oml_init(self, om):
         """Switch the mixed layer on for this slab (before SlabOcean sizes its message buffers)."""
-        from .lib import OmlParams
-        p = OmlParams()
-        p.hmoc, p.toc1, p.toc2, p.st2d, p.st4d = om.hmoc, om.toc[0], om.toc[1], om.st2d, om.st4d
-        p.ycexp, p.rrcpoc, p.tsbdy, p.tnbdy = om.ycexp, om.rrcpoc, om.tsbdy, om.tnbdy
-        p.sb_hflux, p.nb_hflux = int(om.sb_hflux), int(om.nb_hflux)
-        check(self.L.qgcm_hip_oml_init(self.h, C.byref(p)))
+        Handle.oml_init(self, om)
         self.oml_on = True
-        self.th_len = self.L.qgcm_hip_thomas_msg_len(self.h)
-        self.halo_len = self.L.qgcm_hip_halo_msg_len(self.h)
+        self._msg_lens()
         self.oml_len = self.L.qgcm_hip_oml_msg_len(self.h)
 
-    def t_slice(self):
-        """Rows of a GLOBAL (nxto, nyto) T-grid array that this slab's local T array holds."""
-        return slice(self.joff, self.joff + self.nyl - 1)
-
-    def oml_set_state(self, sst, sstm):
-        """sst, sstm: GLOBAL (nxto, nyto) arrays; the local rows (incl. halo rows) are cut out here."""
-        a = [np.asfortranarray(x[:, self.t_slice()], dtype=np.float64) for x in (sst, sstm)]
-        check(self.L.qgcm_hip_oml_set_state(self.h, *[_dp(x) for x in a]))
-
-    def oml_get_state(self):
-        """Local (nxto, nyl-1) sst, sstm; owned T rows are local rows jlo..(jhi or jhi-1 on the last rank)."""
-        a = [np.zeros((self.cfg.nxto, self.nyl - 1), order="F") for _ in range(2)]
-        check(self.L.qgcm_hip_oml_get_state(self.h, *[_dp(x) for x in a]))
-        return a
-
-    def oml_set_forcing(self, fnetoc, wekto, tauxo, tauyo):
-        """GLOBAL arrays: fnetoc, wekto on the T grid (nxto, nyto); tauxo, tauyo on the p grid (nxpo, nypo)."""
-        sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
-        a = [np.asfortranarray(fnetoc[:, self.t_slice()], dtype=np.float64), np.asfortranarray(wekto[:, self.t_slice()], dtype=np.float64),
-             np.asfortranarray(tauxo[:, sl], dtype=np.float64), np.asfortranarray(tauyo[:, sl], dtype=np.float64)]
-        check(self.L.qgcm_hip_oml_set_forcing(self.h, *[_dp(x) for x in a]))
-
-    # diagnostics: the ocean monitors, valids and prsamp as per-rank summaries (SlabOcean.monitors / valids / prsamp)
-    def set_monitor_params(self, oml=None, **kw):
-        """As OceanModel.set_monitor_params."""
-        from .model import mon_params
-        check(self.L.qgcm_hip_set_mon_params(self.h, C.byref(mon_params(oml, **kw))))
-
-    def set_monitor_fields(self, tauxo=None, tauyo=None, wekto=None, sst=None):
-        """GLOBAL arrays: tauxo, tauyo (nxpo, nypo), wekto, sst (nxto, nyto); the local rows (incl. halo rows) are cut
-        out here.  None = leave unchanged.  With the mixed layer on the monitors read its own arrays."""
-        sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
-        cut = lambda x, rows: None if x is None else np.asfortranarray(np.asarray(x, dtype=np.float64)[:, rows])
-        a = [cut(tauxo, sl), cut(tauyo, sl), cut(wekto, self.t_slice()), cut(sst, self.t_slice())]
-        check(self.L.qgcm_hip_set_monitor_fields(self.h, *[_dp(x) for x in a]))
-
-    # time averages of the owned rows (SlabOcean.po_mean / time_means assemble the basin)
-    def owned_t_rows(self):
-        """Owned T rows: g1 - g0 + 1, one less on the rank that owns row nypo."""
-        return self.g1 - self.g0 + (0 if self.g1 == self.cfg.nypo else 1)
-
-    def enable_po_mean(self, on=True):
-        check(self.L.qgcm_hip_poavg_enable(self.h, int(bool(on))))
-
-    def po_mean(self, reset=False):
-        """(po_avg / nsum of the owned rows (nxpo, g1-g0+1, nlo), nsum)."""
-        from .model import read_po_mean
-        return read_po_mean(self.L, self.h, self.cfg, self.g1 - self.g0 + 1, reset)
-
-    def set_time_mean_params(self, oml=None, **kw):
-        from .model import tav_params
-        check(self.L.qgcm_hip_set_tav_params(self.h, C.byref(tav_params(oml, **kw))))
-
-    def set_time_mean_fields(self, fnetoc=None):
-        """GLOBAL fnetoc (nxto, nyto); the local T rows are cut out here."""
-        f = None if fnetoc is None else np.asfortranarray(np.asarray(fnetoc, dtype=np.float64)[:, self.t_slice()])
-        check(self.L.qgcm_hip_set_tav_fields(self.h, _dp(f)))
-
-    def tavocn(self):
-        check(self.L.qgcm_hip_tavocn(self.h))
-        self._done()
-
-    def time_means(self, names=None):
-        """(dict of the owned rows' means, nsumoc)."""
-        from .model import read_time_means
-        return read_time_means(self.L, self.h, self.cfg, self.g1 - self.g0 + 1, self.owned_t_rows(), names)
-
-    def reset_time_means(self):
-        check(self.L.qgcm_hip_tav_reset(self.h))
-
-    # covariance matrices (DESIGN 6j): this rank's row sums, the combine, and the matrix rows this rank holds
-    def enable_covariance(self, nsi=16):
-        check(self.L.qgcm_hip_cov_init(self.h, int(nsi), int(self.rank), int(self.nranks)))
-
+    # covariance matrices (DESIGN 6j): this rank's row sums and the combine (Handle: the matrix rows this rank holds)
     def cov_part_len(self):
         n = self.L.qgcm_hip_cov_part_len(self.h)
         if n < 0:
@@ -413,51 +269,7 @@ class HipSlab:
         check(self.L.qgcm_hip_cov_combine(self.h, self._ptr(gath), int(self.nranks)))
         self._done()
 
-    def covariance(self, k0=None, count=None):
-        """This rank's share: dict keyed by the reference's names (covpo .. nuto); the matrices hold packed entries
-        k0 .. k0+count-1 (default: covariance_size()'s [k0, k1))."""
-        from .model import COV_NAMES_OCN, read_covariance
-        return read_covariance(self.L, self.h, COV_NAMES_OCN, k0, count)
-
-    def covariance_size(self):
-        from .model import cov_size
-        return cov_size(self.L, self.h)
-
-    def reset_covariance(self):
-        check(self.L.qgcm_hip_cov_reset(self.h))
-
-    # periodic ocean dumps (DESIGN 6g): the subsample rows this rank owns (subsample_rows)
-    def subsample_rows(self, nsko):
-        """(mp0, mp1, mt0, mt1): the p-grid subsample rows [mp0, mp1) and T-grid rows [mt0, mt1) this rank owns."""
-        from .model import subsample_rows
-        return subsample_rows(self.L, self.h, nsko)
-
-    def vorticity_budget(self, nsko=1):
-        """As OceanModel.vorticity_budget for the owned subsample rows: (nlo, mp1 - mp0, ipwk) arrays."""
-        from .model import read_budget
-        return read_budget(self.L, self.h, self.cfg, nsko)
-
-    def ocean_dump(self, nsko=1, outfloc=(1, 1, 1, 1, 1, 1, 0)):
-        """As OceanModel.ocean_dump for the owned subsample rows."""
-        from .model import read_ocnc
-        return read_ocnc(self.L, self.h, self.cfg, nsko, outfloc)
-
-    def set_dtopoc(self, dtopoc):
-        """GLOBAL bottom topography (nxpo, nypo) for valids, None = flat."""
-        sl = slab_slice(self.cfg.nypo, self.g0, self.g1)
-        d = None if dtopoc is None else np.asfortranarray(np.asarray(dtopoc, dtype=np.float64)[:, sl])
-        check(self.L.qgcm_hip_set_dtopoc(self.h, _dp(d)))
-
-    def set_areas(self, xlo=None, xhi=None, ylo=None, yhi=None, tables=None):
-        """As OceanModel.set_areas: the areas of the whole basin (global rows), the same on every rank."""
-        from .model import set_area_tables
-        if tables is None:
-            from .hostinit import area_limits
-            cfg = self.cfg
-            tables = area_limits(xlo, xhi, ylo, yhi, cfg.dxo, cfg.dyo, cfg.nxto, cfg.nyto)
-        set_area_tables(self.L, self.h, tables)
-        return tables
-
+    # diagnostics: the ocean monitors, valids, prsamp, areavg and cfl as per-rank summaries (SlabOcean.diagnostic)
     def diag_part_len(self, kind):
         return {"monitors": self.L.qgcm_hip_monitor_part_len, "valids": self.L.qgcm_hip_valids_part_len,
                 "prsamp": self.L.qgcm_hip_prsamp_part_len, "areavg": self.L.qgcm_hip_areavg_part_len,
@@ -484,7 +296,6 @@ class HipSlab:
             check(self.L.qgcm_hip_areavg_combine(self.h, self._ptr(gath), P, _dp(avg), _dp(num), _dp(den)))
             return avg[:n], num[:n], den[:n]
         if kind == "cfl":
-            from .model import cfl_dict
             nq = self.L.qgcm_hip_cfl_len(self.h)
             mx, nb, loc = np.zeros(nq), np.zeros(nq, dtype=np.int32), np.zeros(2 * nq, dtype=np.int32)
             ip = C.POINTER(C.c_int)
@@ -503,45 +314,10 @@ class HipSlab:
         check(self.L.qgcm_hip_prsamp_combine(self.h, self._ptr(gath), P, _dp(out)))
         return out
 
-    def set_scalars(self, s):
-        s = np.ascontiguousarray(s, dtype=np.float64)
-        check(self.L.qgcm_hip_set_scalars(self.h, _dp(s)))
-
-    def get_scalars(self):
-        s = np.zeros(2 * (self.cfg.nlo - 1) + 4 * self.cfg.nlo)
-        check(self.L.qgcm_hip_get_scalars(self.h, _dp(s)))
-        return s
-
-    def set_sponge(self, r_spl, c1_spl):
-        """The fork's sponge layer on this slab: the GLOBAL ramp r_spl(nxpo, nypo), of which the local rows (incl. halo
-        rows) are sent; None switches the term off."""
-        if r_spl is None:
-            check(self.L.qgcm_hip_set_sponge(self.h, None, 0.0))
-            return
-        loc = np.asfortranarray(np.asarray(r_spl, dtype=np.float64)[:, self.joff:self.joff + self.nyl])
-        check(self.L.qgcm_hip_set_sponge(self.h, _dp(loc), float(c1_spl)))
-
-    def get_monitors(self):
-        """(ermaso, emfroc) of the last constraint solve of a zonally cyclic slab (every rank holds the same numbers)."""
-        e, f = np.zeros(self.cfg.nlo - 1), np.zeros(self.cfg.nlo - 1)
-        check(self.L.qgcm_hip_get_monitors(self.h, _dp(e), _dp(f)))
-        return e, f
-
     # slab kernels -------------------------------------------------------------
-    def qgostep(self):
-        check(self.L.qgcm_hip_qgostep(self.h)); self._done()
-
-    def row_transform(self, inverse):
-        check(self.L.qgcm_hip_row_transform(self.h, int(inverse))); self._done()
-
     def thomas_phase(self, phase, gath, send):
         check(self.L.qgcm_hip_thomas_phase(self.h, int(phase), self._ptr(gath), self._ptr(send), self.rank, self.nranks))
         self._done()
-
-    def thomas_plan(self):
-        """[(first, count)] per segment of this slab's interior rows (lib.thomas_plan); one entry: the single launch."""
-        from .lib import thomas_plan
-        return thomas_plan(self.h)
 
     def thomas_consts(self, dst):
         """This slab's right-hand-side independent summary constants -> dst (device buffer of cst_len doubles)."""
@@ -562,9 +338,6 @@ class HipSlab:
 
     def halo_unpack(self, from_lo, from_hi):
         check(self.L.qgcm_hip_halo_unpack(self.h, self._ptr(from_lo), self._ptr(from_hi))); self._done()
-
-    def lf_average(self):
-        check(self.L.qgcm_hip_lf_average(self.h)); self._done()
 
     # exchanges issued by the library itself (RCCL on its own stream) ---------------
     def comm_init(self, comm_id):
@@ -727,7 +500,6 @@ class SlabOcean:
 
     def monitors(self):
         """As OceanModel.monitors(): the ocean half of monnc_comp and couroc over the whole basin."""
-        from .model import unpack_monitors
         return unpack_monitors(self.diagnostic("monitors")[0], self.cfg.nlo)
 
     def valids(self):
@@ -736,7 +508,6 @@ class SlabOcean:
 
     def prsamp(self):
         """As OceanModel.prsamp()."""
-        from .model import prsamp_dict
         return prsamp_dict(self.diagnostic("prsamp")[0], self.cfg.nlo)
 
     def set_areas(self, xlo=None, xhi=None, ylo=None, yhi=None, tables=None):
@@ -756,7 +527,6 @@ class SlabOcean:
     def _assemble(self, parts):
         """parts[i]: dict name -> owned-row array (rows on axis 1) of local slab i.  One all-gather of the packed arrays
         (g0, g1, then every field padded to the largest slab's rows); returns dict name -> whole-basin array."""
-        from .model import TAV_LAYOUT
         S, cfg = self.slabs, self.cfg
         grids = dict(TAV_LAYOUT)
         names = sorted(parts[0])
@@ -863,7 +633,6 @@ class SlabOcean:
 
     def covariance(self):
         """As OceanModel.covariance(): the whole matrices, assembled from every rank's rows with one all-gather."""
-        from .model import COV_NAMES_OCN, cov_row_split
         S = self.slabs
         parts = self.covariance_parts()
         sz = S[0].covariance_size()
@@ -897,7 +666,6 @@ class SlabOcean:
         """parts[i]: dict name -> (planes, rows, columns) owned subsample rows of local slab i; rows[i] its
         (mp0, mp1, mt0, mt1) (HipSlab.subsample_rows), T-grid rows for the names in `tnames`.  One all-gather of the
         packed blocks (row ranges, then every field padded to the largest rank's rows); dict name -> basin array."""
-        from .model import subsample_count
         S, cfg = self.slabs, self.cfg
         names = sorted(parts[0])
         first = lambda g0: (g0 - 1 + nsko - 1) // nsko
