@@ -43,7 +43,7 @@ extern "C" {
 /* 2: qgcm_hip_params.atmos + the atmosphere entry points
  * 3: qgcm_hip_get_monitors (required by the Fortran shim), qgcm_hip_prepare_steps, qgcm_hip_stream_mix_bandwidth,
  *    qgcm_hip_set_sponge, qgcm_hip_set_cu_range; halo rows of qgcm_hip_slab_steps default to neighbour send/recv
- *    (entry points added since keep the number - there is no minor version: qgcm_hip_xforc_sst_* the latest) */
+ *    (entry points added since keep the number - there is no minor version: qgcm_hip_row_split / _row_plan the latest) */
 #define QGCM_HIP_ABI_VERSION 3
 
 typedef struct qgcm_hip_ctx *qgcm_hip_handle;
@@ -131,6 +131,23 @@ int qgcm_hip_thomas_segments(int nrows, int max_rows, int *nseg, int *first, int
  * first[s] .. first[s] + count[s] - 1 (0-based from its first interior row; QGCM_HIP_THOMAS_MAX_SEG ints each, may be
  * NULL).  One segment of all interior rows for a handle on the single-segment kernel, the atmosphere included. */
 int qgcm_hip_thomas_plan(qgcm_hip_handle h, int *nseg, int *first, int *count);
+/* Row length.  The row kernels hold a row pair of at most 5104 points in LDS.  A ZONALLY CYCLIC OCEAN handle (whole
+ * domain or y-slab) with longer rows (the reference's SOcn 4 km .. 1 km: nxto = 5760, 7680, 11520, 23040) transforms
+ * each row as P interleaved sub-rows of length L = nxto / P through one scratch array of the work array's size, three
+ * launches per transform instead of one; every entry point drives such a handle unchanged.  qgcm_hip_row_split gives
+ * the plan: P = 1 (L = nxto) up to 5104 points; beyond, the smallest P in 2 .. QGCM_HIP_ROW_SPLIT_MAX_P that divides
+ * nxto and leaves an even L <= 5104 the row kernels take (5760 = 2 x 2880, 7680 = 2 x 3840, 11520 = 3 x 3840,
+ * 23040 = 5 x 4608).  forced_P > 0: that P at any length, under the same conditions.  Pure host code, no handle and no
+ * device needed.  Fails (non-zero, the message names the limit) when no P qualifies (an odd nxto > 5104, say) and for a
+ * forced_P outside 2 .. 5, one that does not divide nxto or one that leaves an odd or too long L.
+ * QGCM_HIP_ROW_SPLIT=<P> (environment, read by qgcm_hip_set_grid for zonally cyclic OCEAN handles only) forces the
+ * split on rows of any length - tests use it on small basins; anything but a positive integer is refused.
+ * Box oceans and atmosphere handles with nxto > 5104 are refused by qgcm_hip_set_grid. */
+#define QGCM_HIP_ROW_SPLIT_MAX_P 5
+int qgcm_hip_row_split(int nxto, int forced_P, int *P, int *L);
+/* The row plan the handle uses (after qgcm_hip_set_grid): *P sub-rows of length *L per row; (1, nxto) for a handle that
+ * transforms its rows whole. */
+int qgcm_hip_row_plan(qgcm_hip_handle h, int *P, int *L);
 /* The part of set_grid that does not need bd2oc: yporel and ddynoc only.  The main program calls ocqbdy / atqzbd on
  * host arrays (src/q-gcm.F:724-725, 743-744) before it computes bd2oc (:932-972); qgcm_hip_ocqbdy_host needs no more
  * than this.  The stepping entry points still require qgcm_hip_set_grid. */

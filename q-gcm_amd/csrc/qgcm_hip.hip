@@ -46,6 +46,7 @@
 #include "k_qocdiag.h"
 #include "k_setup.h"
 #include "k_xforc.h"
+#include "k_row_split.h"
 
 // kernels that are templates on the number of layers: instantiated for nlo = 2 .. QGCM_HIP_MAXL (8); the fused fast
 // paths (k_dst64_unpack, k_rfft64_unpack, k_rfft3_unpack, the riding constraint solves) stay with nlo <= 4
@@ -240,7 +241,16 @@ struct qgcm_hip_ctx {
   QgBuf<QgScalars> sc;
   QgBuf<double2> twid;
   QgDbl sintab;
-  int fftN, nfac, fac[QG_MAXFAC];
+  int fftN, nfac, fac[QG_MAXFAC]; // fftN = nxto; the factors (and dst_single, dst_lds, fft3 below) belong to the length the
+                                  // row kernels transform: nxto, or split.L on a handle that splits its rows
+  // Cyclic ocean rows longer than one LDS buffer (nxto > 5104, or QGCM_HIP_ROW_SPLIT; k_row_split.h): the
+  // plan nxto = P * L of qgcm_hip_row_split, the table exp(-2 pi i t / L) of the sub-transforms and the scratch array
+  // of wrk's size - both allocated on handles that split only.  P = 1: the rows are transformed whole.
+  struct {
+    int P = 1, L = 0;
+    QgBuf<double2> twid;
+    QgDbl scr;
+  } split;
   QgConstr cs;
   bool grid_set, homog_set;
   bool geom_set = false; // yporel / ddynoc are on the device (qgcm_hip_set_geometry or set_grid)
@@ -660,6 +670,69 @@ extern "C" int qgcm_hip_thomas_plan(qgcm_hip_handle c, int *nseg, int *first, in
   return 0;
 }
 
+// The generic row kernels' LDS (k_dst.h): two ping-pong buffers, or ONE buffer with in-place stages for long rows whose
+// factors all have an in-place stage
+static bool row_single_buffer(int N) {
+  if (N < DST_SINGLE_MINN || N > DST_SINGLE_MAXN || N % 2) return false;
+  int fac[64]; // (2^31 has 31 factors)
+  const int nf = factorize(N, fac);
+  for (int f = 0; f < nf; ++f)
+    if (fac[f] != 2 && fac[f] != 3 && fac[f] != 4 && fac[f] != 5 && fac[f] != 8) return false;
+  return true;
+}
+static size_t row_lds_bytes(int N, bool cyc, bool single) {
+  if (single) return (size_t)N * sizeof(cplx) + 2 * (RFFT_NT / 64) * sizeof(double); // RFFT_NT == DST_NT_BIG
+  return (size_t)2 * N * sizeof(cplx) + 2 * (cyc ? RFFT_NT : (N >= DST_BIG_N ? DST_NT_BIG : DST_NT)) * sizeof(double);
+}
+static const size_t kRowLdsMax = 160 * 1024;
+
+// The row plan of a zonally cyclic ocean with rows of nxto points (pure host code): nxto = P * L, P interleaved
+// sub-rows of length L per row (k_row_split.h).  forced_P <= 0: P = 1 up to DST_SINGLE_MAXN = 5104 points; beyond, the
+// smallest P in 2 .. 5 that divides nxto and leaves an even L <= 5104 which the generic cyclic row kernel holds in LDS.
+// forced_P > 0 (QGCM_HIP_ROW_SPLIT): that P, at any length, under the same conditions.
+extern "C" int qgcm_hip_row_split(int nxto, int forced_P, int *P, int *L) {
+  if (!P || !L) QG_FAIL("qgcm_hip_row_split: null argument");
+  if (nxto < 2) QG_FAIL("qgcm_hip_row_split: nxto = %d", nxto);
+  auto fits = [&](int p) {
+    if (nxto % p) return false;
+    const int l = nxto / p;
+    return l % 2 == 0 && l <= DST_SINGLE_MAXN && row_lds_bytes(l, true, row_single_buffer(l)) <= kRowLdsMax;
+  };
+  if (forced_P > 0) {
+    if (forced_P < 2 || forced_P > QGCM_HIP_ROW_SPLIT_MAX_P)
+      QG_FAIL("qgcm_hip_row_split: QGCM_HIP_ROW_SPLIT=%d is outside 2 .. %d", forced_P, QGCM_HIP_ROW_SPLIT_MAX_P);
+    if (nxto % forced_P) QG_FAIL("qgcm_hip_row_split: QGCM_HIP_ROW_SPLIT=%d does not divide nxto=%d", forced_P, nxto);
+    if ((nxto / forced_P) % 2) QG_FAIL("qgcm_hip_row_split: QGCM_HIP_ROW_SPLIT=%d leaves sub-rows of an odd length %d (nxto=%d)", forced_P, nxto / forced_P, nxto);
+    if (!fits(forced_P))
+      QG_FAIL("qgcm_hip_row_split: QGCM_HIP_ROW_SPLIT=%d leaves sub-rows of %d points, more than the row kernels hold (<= %d)", forced_P, nxto / forced_P, DST_SINGLE_MAXN);
+    *P = forced_P;
+    *L = nxto / forced_P;
+    return 0;
+  }
+  if (nxto <= DST_SINGLE_MAXN) {
+    *P = 1;
+    *L = nxto;
+    return 0;
+  }
+  for (int p = 2; p <= QGCM_HIP_ROW_SPLIT_MAX_P; ++p)
+    if (fits(p)) {
+      *P = p;
+      *L = nxto / p;
+      return 0;
+    }
+  QG_FAIL("qgcm_hip_row_split: nxto=%d is longer than one row transform (<= %d points) and no P in 2 .. %d splits it into even sub-rows of at most %d points "
+          "that the row kernels hold; supported: nxto = P * L with L even, L <= %d",
+          nxto, DST_SINGLE_MAXN, QGCM_HIP_ROW_SPLIT_MAX_P, DST_SINGLE_MAXN, DST_SINGLE_MAXN);
+}
+
+extern "C" int qgcm_hip_row_plan(qgcm_hip_handle c, int *P, int *L) {
+  if (!c || !P || !L) QG_FAIL("qgcm_hip_row_plan: null argument");
+  if (!c->grid_set) QG_FAIL("qgcm_hip_row_plan: the plan is made by qgcm_hip_set_grid");
+  *P = c->split.P;
+  *L = c->split.P > 1 ? c->split.L : c->g.nxt;
+  return 0;
+}
+
 // per-step message of one slab: the summaries of the two y sweeps; a cyclic ocean appends its boundary line sums
 static inline size_t slab_msg_len(const QgGeom &g) {
   return (size_t)TH_MSG * g.nl * g.ldw + (g.cyc ? (size_t)5 * BSUM_NB * 2 * g.nl : 0);
@@ -927,8 +1000,25 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
     for (int k = 0; k < g.nk; ++k) bocs[m][k] = bd2oc[k] - c->prm.rdm2oc[m];
   // FFT tables: complex length N = nxto (box DST-I of length nxto-1)
   const int N = g.nxt;
+  // The row plan (qgcm_hip_row_split): a zonally cyclic ocean transforms rows of more than 5104 points - or, with
+  // QGCM_HIP_ROW_SPLIT=<P> set, rows of any length - as P interleaved sub-rows of length Ls = N / P; every other handle
+  // transforms its rows whole (Ls = N) and does not read the variable.
+  int splitP = 1, Ls = N;
+  if (g.cyc && !g.atm) {
+    int forced = 0;
+    if (const char *sp = getenv("QGCM_HIP_ROW_SPLIT")) {
+      char *end = nullptr;
+      const long v = strtol(sp, &end, 10);
+      if (end == sp || *end != '\0' || v < 1 || v > 1000000) QG_FAIL("qgcm_hip_set_grid: QGCM_HIP_ROW_SPLIT=\"%s\" is not a positive number of sub-rows", sp);
+      forced = (int)v;
+    }
+    if (qgcm_hip_row_split(N, forced, &splitP, &Ls)) return 1;
+  } else if (N > DST_SINGLE_MAXN) {
+    QG_FAIL("qgcm_hip_set_grid: nxto=%d is longer than one row transform (<= %d points); only zonally cyclic ocean handles split longer rows "
+            "(box oceans and atmosphere handles: nxto <= %d)", N, DST_SINGLE_MAXN, DST_SINGLE_MAXN);
+  }
   c->fftN = N;
-  c->nfac = factorize(N, c->fac);
+  c->nfac = factorize(Ls, c->fac);
   if (c->nfac > QG_MAXFAC) QG_FAIL("qgcm_hip_set_grid: too many FFT factors");
   std::vector<double2> tw(N);
   const double twopi = 6.28318530717958647692528676655900577;
@@ -943,16 +1033,24 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   if (c->twid.alloc(N, "the twiddle factors") || c->sintab.alloc(st.size(), "the sine table")) return 1;
   HIPCHECK(hipMemcpy(c->twid, tw.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(c->sintab, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice));
-  // generic row kernels: two ping-pong buffers, or ONE buffer with in-place stages for long rows
-  c->dst_single = false;
-  if (N >= DST_SINGLE_MINN && N <= DST_SINGLE_MAXN && N % 2 == 0 && !getenv("QGCM_HIP_NO_SINGLE_BUFFER")) {
-    c->dst_single = true;
-    for (int f = 0; f < c->nfac; ++f)
-      if (c->fac[f] != 2 && c->fac[f] != 3 && c->fac[f] != 4 && c->fac[f] != 5 && c->fac[f] != 8) c->dst_single = false;
+  // a handle that splits its rows: the sub-transforms' table exp(-2 pi i t / Ls) = every P-th entry of the table above,
+  // and the scratch array; a handle that does not holds neither
+  if (splitP != c->split.P || Ls != c->split.L) HIPCHECK(hipStreamSynchronize(c->stream));
+  c->split.P = splitP;
+  c->split.L = Ls;
+  if (splitP > 1) {
+    std::vector<double2> tws(Ls);
+    for (int t = 0; t < Ls; ++t) tws[t] = tw[(size_t)t * splitP];
+    if (c->split.twid.alloc(Ls, "the sub-rows' twiddle factors") || c->split.scr.grow((size_t)g.wstride * g.nl, "the split rows' scratch array")) return 1;
+    HIPCHECK(hipMemcpy(c->split.twid, tws.data(), sizeof(double2) * Ls, hipMemcpyHostToDevice));
+  } else {
+    c->split.twid.reset();
+    c->split.scr.reset();
   }
-  c->dst_lds = (size_t)(c->dst_single ? 1 : 2) * N * sizeof(cplx) + 2 * (g.cyc ? RFFT_NT : (N >= DST_BIG_N ? DST_NT_BIG : DST_NT)) * sizeof(double);
-  if (c->dst_single) c->dst_lds = (size_t)N * sizeof(cplx) + 2 * (RFFT_NT / 64) * sizeof(double); // RFFT_NT == DST_NT_BIG
-  if (c->dst_lds > 160 * 1024) QG_FAIL("qgcm_hip_set_grid: nxto=%d needs %zu B of LDS per row pair (> 160 KiB)", N, c->dst_lds);
+  // generic row kernels (of length Ls): two ping-pong buffers, or ONE buffer with in-place stages for long rows
+  c->dst_single = row_single_buffer(Ls) && !getenv("QGCM_HIP_NO_SINGLE_BUFFER");
+  c->dst_lds = row_lds_bytes(Ls, g.cyc, c->dst_single);
+  if (c->dst_lds > kRowLdsMax) QG_FAIL("qgcm_hip_set_grid: nxto=%d needs %zu B of LDS per row pair (> 160 KiB)", Ls, c->dst_lds);
   HIPCHECK(hipFuncSetAttribute((const void *)k_dst_box<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->dst_lds));
   HIPCHECK(hipFuncSetAttribute((const void *)k_dst_box<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->dst_lds));
   HIPCHECK(hipFuncSetAttribute((const void *)k_dst_box<false, DST_NT_BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->dst_lds));
@@ -962,7 +1060,7 @@ extern "C" int qgcm_hip_set_grid(qgcm_hip_handle c, const double *yporel, const 
   c->fft3 = 0;
   if (!getenv("QGCM_HIP_NO_FFT3")) {
 #define QG_FFT3_SETUP(ID, R1, R2, R3)                                                                                        \
-    if (N == R1 * R2 * R3) {                                                                                                 \
+    if (Ls == R1 * R2 * R3) {                                                                                                \
       typedef Fft3Plan<R1, R2, R3> PL;                                                                                       \
       c->fft3 = ID;                                                                                                          \
       c->fft3_lds = (size_t)PL::LDS_CPLX * sizeof(cplx) + 2 * (FFT3_NT / 64) * sizeof(double);                               \
@@ -1364,12 +1462,13 @@ static bool tend_can_split(const qgcm_hip_ctx *c) {
 
 // The step plan: which launches one inversion makes, derived in ONE place from the geometry and the handle's switches
 // (DESIGN 3.5 has the table).  ocinvq_impl, one_step, launch_tend, launch_dst and the slab stages 1 / 2 read it.
-enum { ROWS_GENERIC = 0, ROWS_DST64, ROWS_RFFT64, ROWS_FFT3 };                    // the row kernels' family
+enum { ROWS_GENERIC = 0, ROWS_DST64, ROWS_RFFT64, ROWS_FFT3, ROWS_SPLIT };        // the row kernels' family
 enum { INV_PLAIN = 0, INV_DST64_UNPACK, INV_RFFT64_UNPACK, INV_FFT3_UNPACK };      // inverse rows: alone, or fused with the unpack
 enum { CONSTR_OWN = 0, CONSTR_INV_WAVE, CONSTR_BOX_WG, CONSTR_AB };                // where the constraint solve runs
 struct QgStepPlan {
   int rows;     // ROWS_GENERIC: k_dst_box / k_rfft_cyc (Stockham); ROWS_DST64 / ROWS_RFFT64: a wave per row pair (k_dst64.h,
-                // k_rfft64.h); ROWS_FFT3: the three-stage plans of k_fft3.h
+                // k_rfft64.h); ROWS_FFT3: the three-stage plans of k_fft3.h; ROWS_SPLIT: P sub-rows per row through the
+                // scratch array (k_row_split.h), three launches per transform
   int m64;      // wave-per-row-pair families: nxto = 64 * m64
   int inv;      // INV_PLAIN: launch_dst + launch_unpack; else k_dst64_unpack / k_rfft64_unpack / k_rfft3_unpack
   int constr;   // CONSTR_OWN: a launch of its own (k_constr_box / k_constr_cyc); CONSTR_INV_WAVE: the extra wave of
@@ -1391,6 +1490,12 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
   const int N = c->fftN;
   pl.m64 = c->force_generic_dst ? 0 : (N == 64 * 3 ? 3 : N == 64 * 15 ? 15 : (g.cyc && N == 64 * 6) ? 6 : 0);
   pl.rows = (c->fft3 && !c->force_generic_dst) ? ROWS_FFT3 : pl.m64 ? (g.cyc ? ROWS_RFFT64 : ROWS_DST64) : ROWS_GENERIC;
+  // split rows (cyclic oceans): the unfused inverse rows + k_unpack_cyc and the stand-alone k_constr_cyc, as a column
+  // cut into segments has them - every fused or riding form below asks for another row family
+  if (c->split.P > 1) {
+    pl.rows = ROWS_SPLIT;
+    pl.m64 = 0;
+  }
   // inverse rows + homogeneous corrections + modes -> layers (+ boundary PV) in one launch, 2 .. 4 layers:
   // box (k_dst64_unpack); cyclic / atmosphere, whole domain (k_rfft64_unpack; the slab stages keep the plain rows);
   // long cyclic ocean rows of three layers (k_fft3_unpack.h: it reads the solved modes once, the boundary PV always fused)
@@ -1410,7 +1515,7 @@ static QgStepPlan step_plan(const qgcm_hip_ctx *c, bool in_step = false, bool sl
       // and then keep the stand-alone constraint launch.)
       // (a column cut into segments launches no k_thomas<R, 0, true>, whose extra workgroup part A rides in: the
       //  stand-alone k_constr_cyc there)
-      if (in_step && !slab && g.nl <= 4 && c->seg.S == 1 && (pl.inv == INV_RFFT64_UNPACK || pl.rows != ROWS_RFFT64)) pl.constr = CONSTR_AB;
+      if (in_step && !slab && g.nl <= 4 && c->seg.S == 1 && pl.rows != ROWS_SPLIT && (pl.inv == INV_RFFT64_UNPACK || pl.rows != ROWS_RFFT64)) pl.constr = CONSTR_AB;
     } else if (pl.inv == INV_DST64_UNPACK) {
       // (y-slabs with the mixed layer on: xon(1) is only complete after the all-gather of stage 2 - no riding solve)
       if (in_step && !(slab && c->oml.on)) pl.constr = CONSTR_INV_WAVE;
@@ -1563,14 +1668,57 @@ static void fill_dst_params(const qgcm_hip_ctx *c, QgDstParams &D, double *wrk, 
   D.single = c->dst_single ? 1 : 0;
 }
 
+// The radix-P pass and the copies of split rows live in k_row_split.hip, a device code object of its own (as
+// k_tend_rows.hip): this file compiles to the device code it had without them.
+hipError_t qg_launch_row_split(int which, hipStream_t st, const QgRowSplit &S, int nlayers);
+static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, int layer0, hipStream_t st, bool cyc_part_b,
+                      bool box_constr, bool sub);
+
+// ROWS_SPLIT (k_row_split.h): forward = sub-rows out of the rows, their transforms, the radix-P pass into the rows;
+// inverse = the radix-P pass out of the rows, the sub-rows' transforms, the sub-rows back into the rows.  Three
+// launches, each counted in the transform's class.
+static int launch_dst_split(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, int layer0, hipStream_t st) {
+  const QgGeom &g = c->g;
+  QgRowSplit S;
+  memset(&S, 0, sizeof(S));
+  S.wrk = wrk; S.scr = c->split.scr; S.twid = c->twid;
+  S.wstride = g.wstride; S.ldw = g.ldw; S.jr0 = g.jr0; S.nrows = g.jr1 - g.jr0 + 1;
+  S.N = c->fftN; S.P = c->split.P; S.L = c->split.L;
+  S.layer0 = layer0;
+  if (!S.scr || S.P * S.L != S.N || S.N > g.ldw) QG_FAIL("launch_dst: the handle has no split-row plan");
+  const int kn = inverse ? KN_DSTI : KN_DSTF;
+  {
+    KTimer t(c, kn, st);
+    HIPCHECK(qg_launch_row_split(inverse ? SPLIT_INV : SPLIT_GATHER, st, S, nlayers));
+  }
+  if (launch_dst(c, c->split.scr, nlayers, inverse, layer0, st, false, false, true)) return 1;
+  KTimer t(c, kn, st);
+  HIPCHECK(qg_launch_row_split(inverse ? SPLIT_SCATTER : SPLIT_FWD, st, S, nlayers));
+  return 0;
+}
+
+// sub: the sub-rows of split rows - wrk = the scratch array, seen as P * nrows rows of length and pitch L per mode
 static int launch_dst(qgcm_hip_ctx *c, double *wrk, int nlayers, bool inverse, int layer0 = 0, hipStream_t st = nullptr,
-                      bool cyc_part_b = false, bool box_constr = false) {
+                      bool cyc_part_b = false, bool box_constr = false, bool sub = false) {
   if (!st) st = c->stream;
   const QgGeom &g = c->g;
-  const QgStepPlan pl = step_plan(c);
+  QgStepPlan pl = step_plan(c);
+  if (pl.rows == ROWS_SPLIT && !sub) {
+    if (cyc_part_b || box_constr) QG_FAIL("launch_dst: no constraint solve rides in split rows");
+    return launch_dst_split(c, wrk, nlayers, inverse, layer0, st);
+  }
   QgDstParams P;
   fill_dst_params(c, P, wrk, nlayers, layer0);
-  const int nrows = g.jr1 - g.jr0 + 1;
+  int nrows = g.jr1 - g.jr0 + 1;
+  if (sub) { // (the row kernels read N, ldw, wstride, jr0, jr1 of their parameters; ny only with row sums, which are off)
+    pl.rows = (c->fft3 && !c->force_generic_dst) ? ROWS_FFT3 : ROWS_GENERIC;
+    nrows *= c->split.P;
+    P.N = c->split.L;
+    P.twid = c->split.twid;
+    P.g.ldw = c->split.L;
+    P.g.jr0 = 1;
+    P.g.jr1 = nrows;
+  }
   const int npairs = (nrows + 1) / 2;
   dim3 grid(npairs, nlayers);
   dim3 grid64((npairs + D64_WAVES - 1) / D64_WAVES, nlayers);

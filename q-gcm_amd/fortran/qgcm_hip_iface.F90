@@ -318,6 +318,17 @@ module qgcm_hip_iface
       type(c_ptr), value :: h, gath_dev
       integer(c_int), value :: nranks
     end function
+    ! the row plan of a zonally cyclic ocean: nxto = P * L (host code; forced_P = 0: the default rule), and a handle's
+    integer(c_int) function qgcm_hip_row_split(nxto, forced_P, P, L) bind(C, name='qgcm_hip_row_split')
+      import :: c_int
+      integer(c_int), value :: nxto, forced_P
+      integer(c_int) :: P, L
+    end function
+    integer(c_int) function qgcm_hip_row_plan(h, P, L) bind(C, name='qgcm_hip_row_plan')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int) :: P, L
+    end function
     integer(c_int) function qgcm_hip_comm_probe(h, reps, us) bind(C, name='qgcm_hip_comm_probe')
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: h

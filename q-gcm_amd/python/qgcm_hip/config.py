@@ -280,6 +280,24 @@ PRESETS = {
 }
 
 
+def _socn_scaled(name, nxta, nyta, nyaooc, ndxr, dxo):
+    """SOcn 4 km .. 1 km: the grid lines of src/parameters_data.F.SOcn.{4,3,2,1}km.wideatm (nxaooc = nxta).  The
+    reference ships no input.params for them: dta, bccooc and ah4oc are scaled from socn5 the way natl1's were from natl5
+    (dxo / 5 there went with dta / 3, bccooc / 2, ah4oc / 40) - the same power laws of dxo / 5 km, which give natl1's
+    constants at 1 km; dta in whole seconds."""
+    r = dxo / 5.0e3
+    e = lambda f: np.log(f) / np.log(5.0)  # noqa: E731
+    return OceanConfig(name, nxta, nyta, nxta, nyaooc, ndxr, 3, dxo=dxo, dta=float(round(180.0 * r ** e(3.0))),
+                       bccooc=round(0.2 * r ** e(2.0), 4), ah4oc=(float("%.3g" % (2.0e9 * r ** e(40.0))),) * 3, **_SOCN)
+
+
+# rows longer than one row transform (DESIGN 3.5c): nxto = 5760, 7680, 11520, 23040; nypo = 721, 961, 1441, 2881
+PRESETS["socn4"] = _socn_scaled("socn4", 288, 108, 36, 20, 4.0e3)
+PRESETS["socn3"] = _socn_scaled("socn3", 384, 144, 48, 20, 3.0e3)
+PRESETS["socn2"] = _socn_scaled("socn2", 576, 216, 72, 20, 2.0e3)
+PRESETS["socn1"] = _socn_scaled("socn1", 576, 216, 72, 40, 1.0e3)
+
+
 # coupled grids (oracle/ref_binding.CONFIGS "cpl_*"): the ocean half; atmos_preset gives the atmosphere.
 # cpl_natl5 = examples/double_gyre_coupled (BASELINE configs[3]): NAtl 5 km ocean under a 385 x 97 x 3 atmosphere.
 PRESETS["cpl_tiny"] = OceanConfig("cpl_tiny", 16, 12, 4, 3, 12, 3, dxo=1.0e4, dta=360.0, ah4oc=(3.2e10,) * 3, **_NATL)

@@ -14,7 +14,7 @@ import numpy as np
 
 from .config import OmlConfig
 from .hostinit import area_limits
-from .lib import MAXL, TAV_NOUT, MonParams, OmlParams, Params, QgcmHipError, TavParams, check, load_library, thomas_plan
+from .lib import MAXL, TAV_NOUT, MonParams, OmlParams, Params, QgcmHipError, TavParams, check, load_library, row_plan, thomas_plan
 
 
 def _dp(a):
@@ -209,6 +209,10 @@ class Handle:
     def thomas_plan(self):
         """[(first, count)] per segment of the handle's interior rows (lib.thomas_plan); one entry: the single launch."""
         return thomas_plan(self.h)
+
+    def row_plan(self):
+        """(P, L): the handle transforms each row as P interleaved sub-rows of length L (lib.row_plan); (1, nxto): whole."""
+        return row_plan(self.h)
 
     # -- state (LOCAL blocks: the handle's rows, halo rows included) -------------
     def set_state(self, po=None, pom=None, qo=None, qom=None):

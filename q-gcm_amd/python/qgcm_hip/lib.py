@@ -119,6 +119,7 @@ SYMBOLS = [
     "qgcm_hip_wrk_fill", "qgcm_hip_wrk_get", "qgcm_hip_wrk_set", "qgcm_hip_area_integrals",
     "qgcm_hip_local_rows", "qgcm_hip_row_transform", "qgcm_hip_thomas_msg_len", "qgcm_hip_thomas_phase",
     "qgcm_hip_thomas_const_len", "qgcm_hip_thomas_consts", "qgcm_hip_set_thomas_consts", "qgcm_hip_thomas_segments", "qgcm_hip_thomas_plan",
+    "qgcm_hip_row_split", "qgcm_hip_row_plan",
     "qgcm_hip_constr", "qgcm_hip_unpack",
     "qgcm_hip_halo_msg_len", "qgcm_hip_halo_pack", "qgcm_hip_halo_unpack", "qgcm_hip_slab_stage", "qgcm_hip_oml_msg_len",
     "qgcm_hip_comm_unique_id", "qgcm_hip_comm_init", "qgcm_hip_slab_steps", "qgcm_hip_comm_set_halo_p2p", "qgcm_hip_comm_set_overlap", "qgcm_hip_comm_probe",
@@ -210,6 +211,9 @@ def load_library():
     L.qgcm_hip_thomas_phase.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
     L.qgcm_hip_thomas_segments.argtypes = [C.c_int, C.c_int, ip, ip, ip]
     L.qgcm_hip_thomas_plan.argtypes = [vp, ip, ip, ip]
+    if hasattr(L, "qgcm_hip_row_split"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_row_split.argtypes = [C.c_int, C.c_int, ip, ip]
+        L.qgcm_hip_row_plan.argtypes = [vp, ip, ip]
     L.qgcm_hip_constr.argtypes = [vp]
     L.qgcm_hip_unpack.argtypes = [vp, C.c_int]
     L.qgcm_hip_halo_msg_len.argtypes = [vp]
@@ -359,3 +363,23 @@ def thomas_plan(handle):
     first, count = (C.c_int * THOMAS_MAX_SEG)(), (C.c_int * THOMAS_MAX_SEG)()
     check(load_library().qgcm_hip_thomas_plan(handle, C.byref(n), first, count))
     return [(first[s], count[s]) for s in range(n.value)]
+
+
+ROW_MAX = 5104          # DST_SINGLE_MAXN (k_dst.h): the longest row (or sub-row) one row transform holds
+ROW_SPLIT_MAX_P = 5     # QGCM_HIP_ROW_SPLIT_MAX_P
+
+
+def row_split(nxto, forced=0):
+    """The row plan (P, L) of a zonally cyclic ocean with rows of `nxto` points (qgcm_hip_row_split; host code, no
+    device): each row is transformed as P interleaved sub-rows of length L = nxto / P; (1, nxto) up to 5104 points.
+    forced > 0: that P (QGCM_HIP_ROW_SPLIT); forced = 0: the default rule."""
+    p, l = C.c_int(0), C.c_int(0)
+    check(load_library().qgcm_hip_row_split(nxto, forced, C.byref(p), C.byref(l)))
+    return p.value, l.value
+
+
+def row_plan(handle):
+    """The row plan (P, L) a handle uses (qgcm_hip_row_plan); (1, nxto) for a handle that transforms its rows whole."""
+    p, l = C.c_int(0), C.c_int(0)
+    check(load_library().qgcm_hip_row_plan(handle, C.byref(p), C.byref(l)))
+    return p.value, l.value
