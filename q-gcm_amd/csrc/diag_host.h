@@ -213,12 +213,15 @@ static int mon_params(qgcm_hip_ctx *c, QgMonParams &P, const char *who) {
 // the scan and the jet rows over the owned rows; then `last` (k_mon_final or k_monslab_part) reduces them
 static int launch_monitors(qgcm_hip_ctx *c, const QgMonParams &P, bool part) {
   const QgGeom &g = c->g;
-#define QG_MON(NLV)                                                                                         \
+  // k_mon_jet's LDS: the row when it fits MON_JET_CHUNK, else one chunk (the kernel then takes the row in passes)
+  static_assert(sizeof(double) * MON_JET_CHUNK <= 65536, "k_mon_jet's chunk exceeds the LDS a launch gets by default");
+  const size_t jet_lds = sizeof(double) * (g.nx < MON_JET_CHUNK ? g.nx : MON_JET_CHUNK);
+#define QG_MON(NLV)                                                                                      \
   if (c->whole && g.cyc) hipLaunchKernelGGL((k_mon_scan<NLV, true>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);  \
   else if (c->whole) hipLaunchKernelGGL((k_mon_scan<NLV, false>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);      \
   else if (g.cyc) hipLaunchKernelGGL((k_monslab_scan<NLV, true>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);      \
   else hipLaunchKernelGGL((k_monslab_scan<NLV, false>), dim3(P.nblk), dim3(MON_NT), 0, c->stream, P);                \
-  hipLaunchKernelGGL(k_mon_jet, dim3(P.njet, g.nl), dim3(64), sizeof(double) * g.nx, c->stream, P);         \
+  hipLaunchKernelGGL(k_mon_jet, dim3(P.njet, g.nl), dim3(64), jet_lds, c->stream, P);                       \
   if (part) hipLaunchKernelGGL((k_monslab_part<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P);                 \
   else hipLaunchKernelGGL((k_mon_final<NLV>), dim3(1), dim3(MON_FT), 0, c->stream, P)
   QG_SWITCH_NL(g.nl, QG_MON, "k_mon");

@@ -288,18 +288,29 @@ template <int NL, bool CYC>
 __global__ __launch_bounds__(MON_NT) void k_monslab_scan(const QgMonParams P) { mon_scan<NL, CYC, true>(P); }
 
 // ujeto(j) of layer k (:671-688) in the reference's order: one wave per (row, layer) puts the row's ugeos into LDS
-// (dynamic, nxpo doubles), then one lane sums i = 1..nxpo serially and subtracts ugeos(nxpo), as the Fortran loop does -
-// bitwise the reference's ujeto, so ocjpos / ocjval are too.  grid (owned T rows njet, nlo), 64 threads.
+// (dynamic, min(nxpo, MON_JET_CHUNK) doubles: launch_monitors), then one lane sums i = 1..nxpo serially and subtracts
+// ugeos(nxpo), as the Fortran loop does - bitwise the reference's ujeto, so ocjpos / ocjval are too.  A row longer than
+// MON_JET_CHUNK (the split rows of DESIGN 3.5c: 11521 and 23041 points) passes through the same LDS chunk by chunk; the
+// one lane keeps its running sum across the chunks, so the order of the additions is that of one pass.  Every row of
+// at most MON_JET_CHUNK points is one pass with the barriers it always had.  grid (owned T rows njet, nlo), 64 threads.
+#define MON_JET_CHUNK 8192 // ugeos values per LDS pass: 64 KiB, the most a launch gets without an attribute
 __global__ __launch_bounds__(64) void k_mon_jet(const QgMonParams P) {
   extern __shared__ double urow[];
   const int j = blockIdx.x + P.jlo, k = blockIdx.y, nx = P.g.nx;
   const double *pk = P.po + P.g.fstride * k + (long)(j - 1) * P.g.ldx;
-  for (int i = threadIdx.x; i < nx; i += 64) urow[i] = -P.rdxof0 * (pk[P.g.ldx + i] - pk[i]);
-  __syncthreads();
+  double ujet = 0.0, last = 0.0;
+  for (int c0 = 0; c0 < nx; c0 += MON_JET_CHUNK) {
+    const int n = nx - c0 < MON_JET_CHUNK ? nx - c0 : MON_JET_CHUNK;
+    if (c0) __syncthreads(); // the one lane has read the chunk before
+    for (int i = threadIdx.x; i < n; i += 64) urow[i] = -P.rdxof0 * (pk[P.g.ldx + c0 + i] - pk[c0 + i]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int i = 0; i < n; ++i) ujet = ujet + urow[i];
+      last = urow[n - 1];
+    }
+  }
   if (threadIdx.x != 0) return;
-  double ujet = 0.0;
-  for (int i = 0; i < nx; ++i) ujet = ujet + urow[i];
-  ujet = ujet - urow[nx - 1];
+  ujet = ujet - last;
   P.ujet[(long)k * P.njet + blockIdx.x] = fabs(ujet) / (double)P.g.nxt;
 }
 

@@ -69,6 +69,50 @@ def test_monitor_kernels_do_not_spill(repo_root):
     assert sum(1 for k in res if "k_mon_" in k) == 3 * 7 + 1   # nlo = 2 .. 8: box + cyclic scan, final; k_mon_jet
 
 
+def _jet_chunk(repo_root):
+    src = open(os.path.join(repo_root, "q-gcm_amd", "csrc", "k_monitors.h")).read()
+    return int(re.search(r"#define MON_JET_CHUNK (\d+)", src).group(1))
+
+
+def _chunked_jet_sum(u, chunk):
+    """k_mon_jet's arithmetic on one row of ugeos: the row passes through a buffer of `chunk` values; one lane keeps
+    its running sum across the passes, adding the values of each in order, and remembers the last value of the last
+    pass, which it subtracts at the end."""
+    ujet, last = np.float64(0.0), np.float64(0.0)
+    for c0 in range(0, len(u), chunk):
+        buf = u[c0:c0 + chunk].copy()
+        for x in buf:
+            ujet = ujet + x
+        last = buf[-1]
+    return ujet - last
+
+
+@pytest.mark.parametrize("nxpo", [8191, 8192, 8193, 11521, 23041])
+def test_chunked_jet_sum_is_the_row_sum(repo_root, nxpo):
+    """Rows longer than MON_JET_CHUNK pass through k_mon_jet's LDS in chunks.  The running sum carried across the
+    chunk boundaries is bitwise numpy_monitors' row sum (np.cumsum: serial over i, then - u(nxpo)), because the order of
+    the additions is the same; sums per chunk added afterwards are not - the fix rests on the order."""
+    chunk = _jet_chunk(repo_root)
+    assert chunk == 8192 and chunk * 8 <= 65536 and chunk >= 5105  # every row the 5 km basins have is one pass
+    rng = np.random.default_rng(nxpo)
+    po = rng.uniform(-1.0, 1.0, (nxpo, 2, 1)) * 10.0 ** rng.uniform(-3.0, 3.0, (nxpo, 1, 1))
+    rdxof0 = 1.0 / (5.0e3 * -1.19467e-04)
+    ugeos = -rdxof0 * (po[:, 1:, 0] - po[:, :-1, 0])
+    want = np.cumsum(ugeos, axis=0)[-1, :] - ugeos[-1, :]  # numpy_monitors.monitors, ujeto before abs and / nxt
+    got = _chunked_jet_sum(ugeos[:, 0], chunk)
+    assert got.tobytes() == want[0].tobytes()
+    npass = -(-nxpo // chunk)
+    assert npass == {8191: 1, 8192: 1, 8193: 2, 11521: 2, 23041: 3}[nxpo]
+    if nxpo > chunk + 1:  # (8193: the second chunk is one value, both orders are the same additions)
+        parts = [np.cumsum(ugeos[c0:c0 + chunk, 0])[-1] for c0 in range(0, nxpo, chunk)]
+        tree = parts[0]
+        for p in parts[1:]:
+            tree = tree + p
+        assert (tree - ugeos[-1, 0]) != want[0]  # another order of the same terms: not the reference's bits
+        # ... and the columns past the first chunk matter
+        assert (np.cumsum(ugeos[:chunk, 0])[-1] - ugeos[chunk - 1, 0]) != want[0]
+
+
 def _loop_lap(a, dxm2, cyc):
     """Del-sqd of del4bx / del4ch point by point, as the Fortran writes it (1-based indices shifted by one)."""
     nx, ny = a.shape
