@@ -158,9 +158,33 @@ __device__ __forceinline__ void d64_wave_scan2(double &a, double &b) {
 // i = 0..N-2, pidx(i) = i + (i >> 4), NP = N + N/16.  rsa / rsb = sums of the output rows.
 // Split in two so that a caller can issue its own prefetches BETWEEN the halves: the front half (row loads,
 // pre-twiddle, M-point DFTs) peaks at ~230 VGPRs, all dead when it returns.
+// PRE: the caller has requested the tables itself (dst64_tables, below) and written its W64 row - a kernel whose rows
+// are in LDS already (k_tend_rows) does so ahead of the barrier the rows wait behind; twid, sintab and W64 are then not
+// used here.  Without PRE (k_dst64, k_dst64_unpack) the text, and the instruction stream, are what they were.
 template <int M>
+struct D64Tables {
+  double2 w1;            // twid[lane]
+  double sn[M / 2 + 1];  // the dsint sine factors of the lane's lower-half elements
+};
+// the element of sintab that pre-twiddles z[64*n1 + lane] (0: lanes past the middle of register M/2, clamped, unused)
+template <int M>
+__device__ __forceinline__ int dst64_sin_index(int n1, int lane) {
+  constexpr int N = 64 * M, n = N - 1, NS2 = n / 2;
+  const int j = 64 * n1 + lane;
+  const int k = (j <= NS2 + 1) ? j : 0;
+  return (k <= NS2) ? k : 0;
+}
+template <int M>
+__device__ __forceinline__ void dst64_tables(const double2 *twid, const double *sintab, cplx *W64, int lane, D64Tables<M> &T) {
+  T.w1 = twid[lane];
+  const double2 w = twid[M * lane];
+#pragma unroll
+  for (int n1 = 0; n1 <= M / 2; ++n1) T.sn[n1] = sintab[dst64_sin_index<M>(n1, lane)];
+  W64[lane] = {w.x, w.y};
+}
+template <int M, bool PRE = false>
 __device__ __forceinline__ void dst64_front(const double2 *twid, const double *sintab, const double *rowa, const double *rowb,
-                                            bool has_b, cplx *F, cplx *W64, int lane) {
+                                            bool has_b, cplx *F, cplx *W64, int lane, const D64Tables<M> *pre = nullptr) {
   constexpr int N = 64 * M, n = N - 1, NS2 = n / 2; // n odd: NS2 = N/2 - 1 = K
 
   // Everything this lane will need from global tables is requested up front so
@@ -168,12 +192,12 @@ __device__ __forceinline__ void dst64_front(const double2 *twid, const double *s
   // factors, and this wave's copy of the 64-point twiddles.
   cplx tw1[M]; // W_N^(lane*k1) as powers of W_N^lane (one coalesced load; depth-4 product tree)
   {
-    double2 w = twid[lane];
+    double2 w = PRE ? pre->w1 : twid[lane];
     tw1[1 % M] = {w.x, w.y};
 #pragma unroll
     for (int k1 = 2; k1 < M; ++k1) tw1[k1] = cmul(tw1[k1 / 2], tw1[k1 - k1 / 2]);
   }
-  {
+  if (!PRE) {
     double2 w = twid[M * lane];
     W64[lane] = {w.x, w.y};
   }
@@ -197,7 +221,7 @@ __device__ __forceinline__ void dst64_front(const double2 *twid, const double *s
       const int j = 64 * n1 + lane;
       const int k = (j <= NS2 + 1) ? j : 0;                    // (lanes past the middle of register MH: clamped, unused)
       const int i1 = k > 0 ? k - 1 : 0, i2 = k > 0 ? n - k : 0; // j = 0: z = 0, loads clamped
-      snv[n1] = sintab[(k <= NS2) ? k : 0];
+      snv[n1] = PRE ? pre->sn[n1] : sintab[(k <= NS2) ? k : 0];
       xav[n1] = rowa[i1];
       xac[n1] = rowa[i2];
       xbv[n1] = rb[i1];

@@ -17,10 +17,14 @@
 //     A strip out of reach of every wall - all but 2 of 240 bands, all but 2 of 18 strips at NAtl 5 km - takes a body
 //     without the wall rule, the clamps and the wall-column masks (k_tend_rows_strip.inc, one text included twice);
 //   * ONE workgroup barrier;
-//   * phase 2 (forward rows): B/2 x NL of the waves run dst64_front / dst64_back (k_dst64.h, unchanged) on one (row
-//     pair, mode) each, reading the rows from LDS, and store the spectral rows to wrk as k_dst64 does.  The transform
-//     buffer F of a wave lies over the two right-hand-side rows that this wave alone reads: dst64_front has all its row
-//     loads in registers before it writes F.
+//   * phase 2 (forward rows): the last B/2 x NL waves run dst64_front / dst64_back (k_dst64.h) on one (row pair, mode)
+//     each, reading the rows from LDS, and store the spectral rows to wrk as k_dst64 does.  The transform buffer F of a
+//     wave lies over the two right-hand-side rows that this wave alone reads: dst64_front has all its row loads in
+//     registers before it writes F.  The tables of the front half are requested in FRONT of the barrier (see there).
+// What a wave waits on: vmcnt counts loads and stores alike and retires them in order, and the compiler does not count
+// the write-through stores (inline asm) - a wait it places for one load behind such a store waits for the store's
+// acknowledgement too.  So no vector-memory wait stands between a strip's first store and its end, and none of phase
+// 2's global loads behind the barrier (tests/test_band_rows_epilogue_asm.py reads both off the assembly).
 // No workgroup waits for another one: no flags, no counters.
 // The wall rows (not stepped: the new-qo buffer keeps qo) are copied by the first and the last band.
 #pragma once
@@ -88,8 +92,31 @@ struct TrKernArgs {
   QgTendParams P;
 };
 typedef const __attribute__((address_space(4))) QgTendParams *TrParamPtr;
+// a table in global memory that no kernel of a step writes (yporel), seen through the constant address space: scalar loads
+typedef const __attribute__((address_space(4))) double *TrConstRow;
 
-#define TR_WAVES_PER_EU 3 // the transform waves need ~146 VGPRs (k_dst64): three waves per SIMD
+// Phase stamps (development builds only, -DQG_STAMPS; qgcm_dev.h, profiles/tools/stamps_band.py), kernel slot 3 of this
+// translation unit's own table.  Thread 0 (wave 0, which has two strips at NAtl 5 km): 0 / 10 kernel entry, 1 first strip
+// done, 2 last strip done, in front of the barrier.  Lane 0 of the first transform wave: 3 its strips done, 4 tables in,
+// 5 past the barrier, 9 front half done, 6 transform done, 7 stores issued, 8 stores drained.
+#ifdef QG_STAMPS
+#define TR_STAMP(thread, i)                                                                                         \
+  do {                                                                                                              \
+    if (threadIdx.x == (thread) && blockIdx.x < QG_STAMP_BLOCKS) qg_stamps[3][blockIdx.x][i] = wall_clock64();       \
+  } while (0)
+// lane 0 of EVERY wave, kernel slots 1 / 0 of the table, one stamp per wave number: its first strip done / all its
+// strips done, in front of the barrier - which wave the barrier waits for
+#define TR_STAMP_W(kern, w)                                                                                         \
+  do {                                                                                                              \
+    static_assert(TrCfg<B>::NW <= QG_NSTAMP, "a stamp per wave");                                                   \
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < QG_STAMP_BLOCKS) qg_stamps[kern][blockIdx.x][w] = wall_clock64();    \
+  } while (0)
+#else
+#define TR_STAMP(thread, i) do { } while (0)
+#define TR_STAMP_W(kern, w) do { } while (0)
+#endif
+
+#define TR_WAVES_PER_EU 3// the transform waves need ~146 VGPRs (k_dst64): three waves per SIMD
 // rows per band.  Measured at NAtl 5 km: 2 (two six-wave workgroups per CU): 71.9 us per step, 4 (one
 // twelve-wave workgroup per CU): 59.4; the parent 61.9.
 constexpr int TR_BAND = 4;
@@ -106,6 +133,8 @@ struct TrCfg {
 template <int NL, int B, int ZM>
 __global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(const double *pom, const double2 *twid, const double *sintab,
                                                                   int nx, int ny, int ldx, int side, const QgTendParams P) {
+  TR_STAMP(0, 10);
+  TR_STAMP(0, 0);
   constexpr int M = 15, N = 64 * M, NW = TrCfg<B>::NW, REG = TrCfg<B>::REG, NPW = B / 2;
   static_assert(B % 2 == 0 && NPW * NL <= NW, "a wave per (row pair, mode)");
   static_assert(2 * N <= M * D64_ROW * 2, "the two right-hand-side rows lie inside the transform buffer");
@@ -158,6 +187,8 @@ __global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(con
   //  and a lane never holds more than one layer's rows.  TR_PIN: the value exists HERE - pure arithmetic is otherwise
   //  sunk past the fences to its use in the epilogue, and the DPP shifts it reads, which cannot move, stay live until then.)
 #define TR_PIN(x) asm volatile("" : "+v"(x))
+#define TR_STR_(x) #x
+#define TR_STR(x) TR_STR_(x)
 #define TR_FENCE()                       \
   do {                                   \
     asm volatile("" ::: "memory");       \
@@ -186,25 +217,62 @@ __global__ __launch_bounds__(TrCfg<B>::NT, TR_WAVES_PER_EU) void k_tend_rows(con
 #undef TR_WALLS
     }
 #undef PE
+    if (strip < NW) {
+      TR_STAMP(0, 1);
+      TR_STAMP_W(1, wv);
+    }
   }
 #undef TR_FENCE
-#undef TR_PIN
-  __syncthreads();
-
+  TR_STAMP(0, 2);
+  TR_STAMP_W(0, wv);
   // ---- phase 2: forward DST-I of the band's rows, a wave per (row pair, mode), as k_dst64 --------------------------
-  if (wv >= NPW * NL) return;
-  const int pair = wv / NL, m = wv - pair * NL;
+  // The transforms run on the LAST NPW * NL waves: with 18 strips on 12 waves those have one strip, reach the barrier
+  // a strip ahead of the others, and the acknowledgements of their write-through stores are long in.  What the front
+  // half reads from global tables - twid[lane], this wave's W64 row, the dsint sine factors: no address depends on
+  // phase 1 - they request HERE, in front of the barrier, and write W64 to LDS (past the two right-hand-side rows of
+  // their region, which phase 1 is still filling).  Behind the barrier these loads were a global round trip on the
+  // critical path of every band, queued - vmcnt retires in order - behind whatever stores the wave still had in flight;
+  // stand-alone k_dst64 never sees it (there the tables travel with the row loads).  The LDS region and the (pair, mode)
+  // follow from the transform index tx, not from the wave number.  Every wave reaches the barrier exactly once; a
+  // transform wave whose pair is absent (a partial last band) has requested its tables like the others and leaves.
+  constexpr int TW0 = NW - NPW * NL; // first transform wave
+  static_assert(M * D64_ROW * 2 >= 2 * N && M * D64_ROW * 2 + 2 * 64 <= REG,
+                "a region's W64 row lies past its two right-hand-side rows and inside the region");
+  const int tx = wv - TW0; // = pair * NL + m; negative: a wave without a transform
+  double *reg = lds + (tx < 0 ? 0 : tx) * REG;
+  cplx *F = reinterpret_cast<cplx *>(reg);
+  cplx *W64 = reinterpret_cast<cplx *>(reg + M * D64_ROW * 2);
+  D64Tables<M> tab;
+  if (tx >= 0) {
+    TR_STAMP(64 * TW0, 3);
+    dst64_tables<M>(twid, sintab, W64, lane, tab);
+    // in hand before the barrier (the wait is hidden behind the other waves' second strip)
+    TR_PIN(tab.w1.x);
+    TR_PIN(tab.w1.y);
+#pragma unroll
+    for (int n1 = 0; n1 <= M / 2; ++n1) TR_PIN(tab.sn[n1]);
+    TR_STAMP(64 * TW0, 4);
+  }
+#undef TR_PIN
+#undef TR_STR
+#undef TR_STR_
+  __syncthreads();
+  if (tx < 0) return;
+  TR_STAMP(64 * TW0, 5);
+  const int pair = tx / NL, m = tx - pair * NL;
   const int ja = j0 + 2 * pair;
   if (ja > jr1) return;
   const bool has_b = (ja + 1 <= jr1);
-  double *reg = lds + wv * REG; // (wv = pair * NL + m)
-  cplx *F = reinterpret_cast<cplx *>(reg);
-  cplx *W64 = reinterpret_cast<cplx *>(reg + M * D64_ROW * 2);
   double *rowa = P.wrk + P.g.wstride * m + (long)(ja - 1) * P.g.ldw;
   double *rowb = rowa + P.g.ldw;
   double rsa, rsb;
-  dst64_front<M>(twid, sintab, reg, reg + N, has_b, F, W64, lane);
+  dst64_front<M, true>(twid, sintab, reg, reg + N, has_b, F, W64, lane, &tab);
+  TR_STAMP(64 * TW0, 9);
   dst64_back<M>(F, W64, lane, rsa, rsb);
+  TR_STAMP(64 * TW0, 6);
   const double *raw = reg;
 #include "k_dst64_store.inc"
+  TR_STAMP(64 * TW0, 7);
+  QG_STAMP_DRAIN();
+  TR_STAMP(64 * TW0, 8);
 }

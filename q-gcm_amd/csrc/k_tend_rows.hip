@@ -2,6 +2,9 @@
 // code object, of its own.  Why: appended to qgcm_hip.hip's code object the two instantiations left every other kernel
 // its instruction stream and its place, and yet the unchanged kernels of the 5 km step ran 0.2 - 0.7 us slower per launch
 // (DESIGN 3.10).  Built here, qgcm_hip.hip compiles to the device code it compiled to before the kernel existed.
+#ifdef QG_STAMPS
+#define qg_stamps qg_stamps_rows // (development builds: this code object's own table of phase stamps, read below)
+#endif
 #include "qgcm_dev.h"
 // (the kernel headers also define non-template kernels: qgcm_hip.hip owns those; here they are static and unused - a few dead kernels
 //  of some hundred bytes each in this code object, no clash of their host stubs at link time)
@@ -23,3 +26,13 @@ void qg_launch_tend_rows(int zm, hipStream_t st, const QgTendParams &P, const do
   if (zm) hipLaunchKernelGGL((k_tend_rows<3, B, 3>), grid, dim3(TrCfg<B>::NT), 0, st, P.pom, twid, sintab, g.nx, g.ny, g.ldx, side, P);
   else hipLaunchKernelGGL((k_tend_rows<3, B, 0>), grid, dim3(TrCfg<B>::NT), 0, st, P.pom, twid, sintab, g.nx, g.ny, g.ldx, side, P);
 }
+
+#ifdef QG_STAMPS
+// development builds only (profiles/tools/stamps_band.py): the phase stamps of the last launch of the band kernel
+// (TR_STAMP, k_tend_rows.h), laid out as qgcm_hip_debug_stamps lays out qgcm_hip.hip's
+extern "C" int qgcm_hip_debug_stamps_rows(long long *out, size_t nbytes) {
+  if (nbytes > sizeof(qg_stamps)) nbytes = sizeof(qg_stamps);
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(qg_stamps), nbytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
+}
+#endif

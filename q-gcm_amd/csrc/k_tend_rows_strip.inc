@@ -40,6 +40,10 @@
   }
   double dq[NL][B], d2bot[B];
   double e_qm[NL][B], e_wek[B], e_ent[ENT ? B : 1], e_ddy[DDY ? B : 1];
+  // yporel of the band's rows, on the SCALAR path (the table is written when the handle is set up, never during a step):
+  // read as a per-row global load inside the epilogue it was a vector load of a wave-uniform value whose wait,
+  // vmcnt(0), also waited for the acknowledgement of the row's write-through stores (k_tend_rows.h)
+  double e_yp[B];
   // (TR_FENCE, TR_PIN: k_tend_rows.h - between the fences the order is the one written here)
 #pragma unroll
   for (int k = 0; k < NL; ++k) {
@@ -56,6 +60,9 @@
 #pragma unroll
       for (int r = 0; r < B + 6; ++r) w[r] = tr_ld(pomk, rowoff(jb - 3 + r) + lcol);
     } else { // the operands of the point-wise epilogue
+      const TrConstRow yprow = (TrConstRow)PE.yporel;
+#pragma unroll
+      for (int t = 0; t < B; ++t) e_yp[t] = yprow[(WALLS && jb + t > ny ? ny : jb + t) - 1]; // (a partial band: clamped, unused)
 #pragma unroll
       for (int t = 0; t < B; ++t) {
         const unsigned o = rowoff(jb + t) + lcol;
@@ -104,6 +111,25 @@
     }
   }
   // ---- forcing, bottom drag, leapfrog, projection: tend_point's expressions (k_tend.h), every lane goes through ----
+  // No vector-memory wait from the first store of the epilogue to the end of the strip: vmcnt counts loads AND stores and
+  // retires them in order, the compiler does not count the write-through stores (inline asm), so any wait it places
+  // behind one of them for a load of its own also waits for that store's acknowledgement.  The operands were requested
+  // a layer's arithmetic ago; pinned here, their waits all stand in front of the first store
+  // (tests/test_band_rows_epilogue_asm.py).
+  // the epilogue's scalars, read once per strip: left inside the row loop each predicated block re-read its own
+  // (s_load + s_waitcnt lgkmcnt(0), some twenty scalar round trips per strip)
+  const double s_foh0 = PE.fohfac[0], s_foh1 = PE.fohfac[1], s_bdr = PE.bdrfac, s_beta = PE.beta, s_tdto = PE.tdto, s_fnot = PE.fnot;
+  double s_ctl[NL * NL];
+#pragma unroll
+  for (int q = 0; q < NL * NL; ++q) s_ctl[q] = PE.ctl2m[q];
+#pragma unroll
+  for (int t = 0; t < B; ++t) {
+    TR_PIN(e_wek[t]);
+    if (ENT) TR_PIN(e_ent[ENT ? t : 0]);
+    if (DDY) TR_PIN(e_ddy[DDY ? t : 0]);
+#pragma unroll
+    for (int kk = 0; kk < NL; ++kk) TR_PIN(e_qm[kk][t]);
+  }
 #pragma unroll
   for (int t = 0; t < B; ++t) {
     const int gj = jb + t;
@@ -114,14 +140,14 @@
     double qdot[NL];
 #pragma unroll
     for (int k = 0; k < NL; ++k) qdot[k] = dq[k][t];
-    qdot[0] = dq[0][t] + PE.fohfac[0] * (wek - ent);
-    qdot[1] = dq[1][t] + PE.fohfac[1] * ent;
-    qdot[NL - 1] = qdot[NL - 1] - PE.bdrfac * d2bot[t];
+    qdot[0] = dq[0][t] + s_foh0 * (wek - ent);
+    qdot[1] = dq[1][t] + s_foh1 * ent;
+    qdot[NL - 1] = qdot[NL - 1] - s_bdr * d2bot[t];
     double ql[NL];
-    const double betay = PE.beta * PE.yporel[gj - 1];
+    const double betay = s_beta * e_yp[t]; // (yporel[gj - 1])
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
-      const double qn = e_qm[k][t] + PE.tdto * qdot[k]; // qom + tdto*qdot
+      const double qn = e_qm[k][t] + s_tdto * qdot[k]; // qom + tdto*qdot
       qg_pair_store_wt(PE.qnew + fs * k + o, qn, WALLS ? (own && gi <= nx - 1) : own);
       if (WALLS && own && gi == nx) PE.qnew[fs * k + o] = qn; // (the E wall column has no partner: the odd one out of 961)
       ql[k] = qn - betay;
@@ -132,8 +158,11 @@
     for (int m = 0; m < NL; ++m) {
       double qmm = 0.0;
 #pragma unroll
-      for (int k = 0; k < NL; ++k) qmm = qmm + PE.ctl2m[k + NL * m] * ql[k];
-      if (own && cint) dst[m * REG] = PE.fnot * qmm;
+      for (int k = 0; k < NL; ++k) qmm = qmm + s_ctl[k + NL * m] * ql[k];
+      if (own && cint) dst[m * REG] = s_fnot * qmm;
     }
   }
+  // (a comment in the device assembly, no instruction: where this body ends - the compiler lays the two bodies out one
+  //  behind the other with a flag in place of the else branch; tests/test_band_rows_epilogue_asm.py reads up to here)
+  asm volatile("; tr_strip_end " TR_STR(TR_WALLS));
 }
