@@ -78,9 +78,42 @@ def preset(name):
     return config.preset(name)
 
 
+# layer tables of the oceans that no preset carries: nlo -> hoc, gpoc, ah2oc, ah4oc (test_gpu_parity's
+# test_fast_kernels_with_two_and_four_layers, tests/test_gpu_ocean_layers.py)
+OCEAN_LAYERS = {
+    2: dict(hoc=(500.0, 3500.0), gpoc=(0.02,), ah2oc=(0.0, 0.0), ah4oc=(1.2e10,) * 2),
+    4: dict(hoc=(300.0, 500.0, 1200.0, 2000.0), gpoc=(0.02, 0.01, 0.005), ah2oc=(0.0,) * 4, ah4oc=(1.2e10,) * 4),
+    5: dict(hoc=(300.0, 400.0, 600.0, 1000.0, 1700.0), gpoc=(0.02, 0.012, 0.008, 0.005), ah2oc=(0.0,) * 5, ah4oc=(1.2e10,) * 5),
+    6: dict(hoc=(250.0, 350.0, 500.0, 700.0, 1000.0, 1200.0), gpoc=(0.02, 0.015, 0.01, 0.007, 0.004), ah2oc=(0.0,) * 6,
+            ah4oc=(1.2e10,) * 6),
+    8: dict(hoc=(200.0, 250.0, 300.0, 400.0, 500.0, 650.0, 800.0, 900.0), gpoc=(0.02, 0.016, 0.013, 0.01, 0.008, 0.006, 0.004),
+            ah2oc=(0.0,) * 8, ah4oc=(1.2e10,) * 8)}
+
+
+def layer_cfg(nlo, cyclic):
+    """The 193-column grids of test_fast_kernels_with_two_and_four_layers: nl<nlo>_box 193 x 97, nl<nlo>_cyc 193 x 65,
+    nxto = 192 = 64 * 3 (the wave-per-row-pair kernels; two to four layers take their fused forms)."""
+    base = dict(fnot=-1.19467e-04, beta=1.31301e-11, cyclic=True) if cyclic else dict(fnot=9.37456e-05, beta=1.7536e-11, cyclic=False)
+    cfg = config.OceanConfig("nl%d_%s" % (nlo, "cyc" if cyclic else "box"), 12 if cyclic else 16, 10, 12, 4 if cyclic else 6, 16, nlo,
+                             dxo=2.5e4, dta=240.0, **OCEAN_LAYERS[nlo], **base)
+    assert cfg.nxto == 192
+    return cfg
+
+
 # ---- ocean mixed layer fixtures (tests/golden/make_golden_oml.py) -----------------------------
-OML_CASES = (("oml_box_tiny", "box_tiny"), ("oml_box_tiny_sb", "box_tiny"), ("oml_cyc_tiny", "cyc_tiny"))
+OML_CASES = (("oml_box_tiny", "box_tiny"), ("oml_box_tiny_sb", "box_tiny"), ("oml_cyc_tiny", "cyc_tiny"),
+             # two, five and six layers: entoc enters layers 1 and 2; at two layers layer 2 is the bottom layer
+             ("oml_box_tiny2", "box_tiny2"), ("oml_box_tiny5", "box_tiny5"), ("oml_cyc_tiny6", "cyc_tiny6"))
 OML_SNAPS = (1, 2, 26, 40)
+# ... of which the five- and six-layer fixtures hold the first two (step 1 averages; each further snapshot is four
+# fields of five or six layers, and a committed file stays under 1 MiB)
+OML_CASE_SNAPS = {"oml_box_tiny5": (1, 2), "oml_cyc_tiny6": (1, 2)}
+
+
+def oml_snaps(case):
+    return OML_CASE_SNAPS.get(case, OML_SNAPS)
+
+
 # ... and the short fixtures on grids that cross the seams of the device kernels' tiles (k_oml_step: 64 x 8 T points,
 # k_oml_entoc: 64 x 16 p points): one call and two coupled steps each
 OML_SEAM_CASES = (("oml_box_seam", "box_seam"), ("oml_box_seam_nb", "box_seam"), ("oml_box_seam_sbnb", "box_seam"),

@@ -32,6 +32,10 @@ The device kernels' tiles: one wave (64 lanes) strides an area's row segment; th
              the last scanned row, none in layer 3
   cfl_cyc    a cyclic ocean of 129 x 25: a third tile column one point wide, offenders next to the seam
   cfl_atm    atmosphere 33 x 13 with uekat / vekat
+  cfl_box2, cfl_box5, cfl_cyc6
+             the grids of cfl_box and cfl_cyc with nlo = 2, 5, 6 (NLO) and a po that differs in every layer.  The
+             largest |v| of the LAST layer lies at two points with bit-equal values (TIES): the later one in scan order
+             (j outer) has the smaller i, so the reference's order - its Bad lines - decides between them
 
   python tests/golden/make_golden_areacfl.py           # writes tests/golden/areacfl_*.npz and areas_limits_*.txt
   python tests/golden/make_golden_areacfl.py NAME ...  # only the named cases
@@ -177,7 +181,14 @@ CASES = [
     ("cfl_box", (32, 12, 24, 10, 4), [(0.0, 480.0, 0.0, 200.0)], [(0.0, 640.0, 0.0, 240.0)]),
     ("cfl_cyc", (32, 8, 32, 6, 4), [(0.0, 640.0, 0.0, 120.0)], [(0.0, 640.0, 0.0, 160.0)]),
     ("cfl_atm", (32, 12, 4, 3, 4), [(0.0, 80.0, 0.0, 60.0)], [(0.0, 640.0, 0.0, 240.0)]),
+    ("cfl_box2", (32, 12, 24, 10, 4), [(0.0, 480.0, 0.0, 200.0)], [(0.0, 640.0, 0.0, 240.0)]),
+    ("cfl_box5", (32, 12, 24, 10, 4), [(0.0, 480.0, 0.0, 200.0)], [(0.0, 640.0, 0.0, 240.0)]),
+    ("cfl_cyc6", (32, 8, 32, 6, 4), [(0.0, 640.0, 0.0, 120.0)], [(0.0, 640.0, 0.0, 160.0)]),
 ]
+NLO = {"cfl_box2": 2, "cfl_box5": 5, "cfl_cyc6": 6}  # ocean layers (every other case: 3)
+# the tied pair of the last layer's |v| (1-based i, j of the difference p(i+1,j) - p(i,j)): first and second in scan order
+TIES = {"cfl_box2": ((80, 7), (10, 30)), "cfl_box5": ((80, 7), (10, 30)), "cfl_cyc6": ((100, 5), (20, 18))}
+TIE_COURANT = 1.6
 NAMES = ("oc1", "oc2", "oc3", "oc4", "oc5", "oc6", "oc7", "oc8", "oc9")
 
 
@@ -197,7 +208,7 @@ def metres(areas):
     return np.array([[float("%.2fe3" % v) for v in a] for a in areas])
 
 
-def build(wrk, dims):
+def build(wrk, dims, nlo=3):
     nxta, nyta, nxaooc, nyaooc, ndxr = dims
     src = os.path.join(REF, "src")
     with open(os.path.join(REF, "examples", "double_gyre_coupled", "parameters_data.F.dg_oo")) as f:
@@ -208,7 +219,7 @@ def build(wrk, dims):
             lines[i] = "      PARAMETER ( nxta = %d, nyta = %d, nla = 3 )" % (nxta, nyta)
             hits += 1
         elif ln.startswith("      PARAMETER ( nxaooc = "):
-            lines[i] = "      PARAMETER ( nxaooc = %d, nyaooc = %d, ndxr = %d, nlo = 3 )" % (nxaooc, nyaooc, ndxr)
+            lines[i] = "      PARAMETER ( nxaooc = %d, nyaooc = %d, ndxr = %d, nlo = %d )" % (nxaooc, nyaooc, ndxr, nlo)
             hits += 1
         elif ln.startswith("      PARAMETER ( fnot = "):
             lines[i] = "      PARAMETER ( fnot = %s, beta = %s )" % (FNOT, BETA)
@@ -256,12 +267,13 @@ def smooth(rng, nx, ny, periodic, nmodes=5):
     return f / max(np.abs(f).max(), 1e-30)
 
 
-def pressure(rng, nx, ny, dx, dt, cyc, spikes):
-    """Three layers of pressure whose geostrophic Courant numbers stay near 0.3, 0.2, 0.1, plus `spikes`: (layer, i, j,
-    Courant number) of single points raised so that the four differences around them exceed that number."""
+def pressure(rng, nx, ny, dx, dt, cyc, spikes, nl=3):
+    """nl layers of pressure whose geostrophic Courant numbers stay near 0.3, 0.2, 0.1 (three layers; otherwise 0.32
+    falling by 0.03 per layer), plus `spikes`: (layer, i, j, Courant number) of single points raised so that the four
+    differences around them exceed that number."""
     unit = dx / dt * dx * F0  # the pressure difference of Courant number 1
-    p = np.zeros((nx, ny, 3))
-    for k, c in enumerate((0.3, 0.2, 0.1)):
+    p = np.zeros((nx, ny, nl))
+    for k, c in enumerate((0.3, 0.2, 0.1) if nl == 3 else [0.32 - 0.03 * k for k in range(nl)]):
         f = smooth(rng, nx - 1 if cyc else nx, ny, cyc)
         if cyc:
             f = np.concatenate([f, f[:1]], axis=0)
@@ -274,25 +286,41 @@ def pressure(rng, nx, ny, dx, dt, cyc, spikes):
     return p
 
 
+def tie(p, pair, dx, dt):
+    """Gives the last layer's |v| the same value, bit for bit, at the two differences of `pair`, above every other one.
+    Both differences get the same operands up to a shift that is exact: p(i,j) is rounded to a multiple of 2^-30 and
+    p(i+1,j) = p(i,j) +- D with D a multiple of 2^-30, so that p(i+1,j) - p(i,j) = +-D without rounding.  The sign is
+    that of the background's p(i+2,j) - p(i,j), which keeps the next difference, p(i+2,j) - p(i+1,j), below D."""
+    q = 2.0 ** -30
+    D = np.round(TIE_COURANT * (dx / dt * dx * F0) / q) * q
+    for i, j in pair:
+        a = np.round(p[i - 1, j - 1, -1] / q) * q
+        sg = 1.0 if p[i + 1, j - 1, -1] >= a else -1.0
+        p[i - 1, j - 1, -1], p[i, j - 1, -1] = a, a + sg * D
+        assert (a + sg * D) - a == sg * D
+
+
 def inputs(name, dims, seed):
     nxta, nyta, nxaooc, nyaooc, ndxr = dims
     nxto, nyto = nxaooc * ndxr, nyaooc * ndxr
     nxpo, nypo, nxpa, nypa = nxto + 1, nyto + 1, nxta + 1, nyta + 1
     dxa = ndxr * DXO
     rng = np.random.default_rng(seed)
-    cyc = name == "cfl_cyc"
+    cyc = name in ("cfl_cyc", "cfl_cyc6")
     F = {}
     # temperatures of both signs, a few K, with grid-scale noise (so that sum|terms| is well above |sum|)
     F["sst"] = 6.0 * smooth(rng, nxto, nyto, False) + 1.5 * rng.standard_normal((nxto, nyto)) + 0.7
     F["ast"] = 9.0 * smooth(rng, nxta, nyta, True) + 2.0 * rng.standard_normal((nxta, nyta)) - 1.3
     # offenders: layer 1 across the seam of the first two tile columns / rows; layer 2 on the last scanned row
-    if name == "cfl_cyc":
+    if cyc:
         oc_sp = [(0, nxpo, 17, 1.3), (1, 64, nypo, 1.2)]
-    elif name == "cfl_box":
+    elif name.startswith("cfl_box"):
         oc_sp = [(0, 65, 17, 1.3), (1, 40, nypo, 1.2)]
     else:
         oc_sp = [(0, max(2, nxpo // 2), max(2, nypo // 2), 1.3), (1, 3, nypo, 1.2)]
-    F["po"] = pressure(rng, nxpo, nypo, DXO, DTO, cyc, oc_sp)
+    F["po"] = pressure(rng, nxpo, nypo, DXO, DTO, cyc, oc_sp, NLO.get(name, 3))
+    if name in TIES:
+        tie(F["po"], TIES[name], DXO, DTO)
     F["pa"] = pressure(rng, nxpa, nypa, dxa, DTA, True, [(0, nxpa, 9, 1.3), (1, 20, nypa, 1.2)])
     # stresses of 1e-4 m^2 s^-2 with one strong spot each, so that the mixed layer has offenders of its own
     vo = DXO / DTO
@@ -360,13 +388,13 @@ def parse_areas(txt):
     return out
 
 
-def parse_cfl(txt, nl=3):
-    """cfltry's print-out per fluid: printed maxima and Courant numbers in the order ml |u|, ml |v|, |u|(k), |v|(k),
+def parse_cfl(txt, nlo=3, nla=3):
+    """cfltry's print-out per fluid (nlo ocean layers, nla atmospheric ones): printed maxima and Courant numbers in the order ml |u|, ml |v|, |u|(k), |v|(k),
     and the Bad lines as rows (quantity, i, j, printed Courant number) in print order."""
     out = {}
     body = txt[txt.index("CFL testing"):]
     cut = body.index("Atm. m.l.")
-    for key, tag, part in (("oc", "Ocn.", body[:cut]), ("at", "Atm.", body[cut:])):
+    for key, tag, part, nl in (("oc", "Ocn.", body[:cut], nlo), ("at", "Atm.", body[cut:], nla)):
         num = r"([-+0-9.DE]+)"
         mu = re.search(re.escape(tag) + r" m\.l\. \|u\| max, CFL =\s*" + num + r"\s+" + num, part)
         mv = re.search(re.escape(tag) + r" m\.l\. \|v\| max, CFL =\s*" + num + r"\s+" + num, part)
@@ -408,6 +436,19 @@ def check(name, res):
             isu = q == 0 or 2 <= q < 5
             last |= (j == (nypo - 1 if isu else nypo)) or (i == (nxpo if isu else nxpo - 1))
         assert last, bad
+    if name in TIES:  # the tie exists in the input, and the reference reports the first of the pair in scan order
+        p, nl = res["in_po"], res["in_po"].shape[2]
+        v = np.abs((1.0 / (DXO * F0)) * (p[1:, :, -1] - p[:-1, :, -1]))
+        at = np.argwhere(v == v.max()) + 1
+        (ia, ja), (ib, jb) = TIES[name]
+        assert sorted(map(tuple, at.tolist())) == sorted([(ia, ja), (ib, jb)]), at
+        assert v[ia - 1, ja - 1].tobytes() == v[ib - 1, jb - 1].tobytes()
+        assert ja < jb and ia > ib  # j outer: the first in scan order is not the one with the smaller i
+        assert res["oc_max"][2 + 2 * nl - 1] == float("%.7e" % v.max())
+        rows = res["oc_bad"][res["oc_bad"][:, 0] == 2 + 2 * nl - 1]
+        top = rows[rows[:, 3] == rows[:, 3].max()]
+        assert [tuple(r) for r in top[:, 1:3].astype(int).tolist()] == [(ia, ja), (ib, jb)], rows
+        assert len({po.tobytes() for po in np.moveaxis(p, 2, 0)}) == nl
     if name == "area_box":
         it, wt = res["oc_it"], res["oc_wt"]
         nxto, nyto = res["in_sst"].shape
@@ -427,18 +468,18 @@ if __name__ == "__main__":
         F = inputs(name, dims, 700 + ic)
         wrk = tempfile.mkdtemp(prefix="areacfl_")
         try:
-            build(wrk, dims)
+            build(wrk, dims, NLO.get(name, 3))
             txt, raw = run(wrk, dims, F, oc, at)
         finally:
             shutil.rmtree(wrk, ignore_errors=True)
         nc = parse_nc(raw)
         res = dict(c_dims=np.array(dims, dtype=np.int64), c_fnot=np.float64(F0), c_dxo=np.float64(DXO),
                    c_dto=np.float64(DTO), c_dxa=np.float64(dims[4] * DXO), c_dta=np.float64(DTA), c_hmoc=np.float64(HMOC),
-                   c_cflcrit=np.float64(CFLCRIT), c_cyclic=np.int64(name == "cfl_cyc"),
+                   c_cflcrit=np.float64(CFLCRIT), c_cyclic=np.int64(name in ("cfl_cyc", "cfl_cyc6")),
                    oc_lim=metres(oc), at_lim=metres(at), oc_tav=nc["ocdata"], at_tav=nc["atdata"])
         res.update({"in_" + k: np.asfortranarray(v) for k, v in F.items()})
         res.update(parse_areas(txt))
-        res.update(parse_cfl(txt))
+        res.update(parse_cfl(txt, NLO.get(name, 3)))
         assert len(res["oc_tav"]) == len(oc) and len(res["at_tav"]) == len(at)
         check(name, res)
         path = os.path.join(HERE, "areacfl_%s.npz" % name)

@@ -142,7 +142,8 @@ if __name__ == "__main__":
     from qgcm_hip import preset
     timing = len(sys.argv) > 1 and sys.argv[1] == "time"
     cases = [("box_natl5", "natl5")] if timing else [("box_tiny", "box_tiny"), ("cyc_tiny", "cyc_tiny"),
-                                                       ("box_tiny5", "box_tiny5")]
+                                                       ("box_tiny5", "box_tiny5"), ("box_tiny2", "box_tiny2"),
+                                                       ("cyc_tiny6", "cyc_tiny6")]
     for refcfg, name in cases:
         a = ref_binding.CONFIGS[refcfg]
         cfg = preset(name)

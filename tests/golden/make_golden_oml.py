@@ -4,11 +4,15 @@ reference compiled by oracle/build_ref.sh.  Run in the build container only (nee
 
     python tests/golden/make_golden_oml.py
 
-One reference build per fixture (grid and boundary variant are compile-time options there), nine in all.
+One reference build per fixture (grid and boundary variant are compile-time options there), twelve in all.
 On the 48 x 36 T grid of the tiny presets:
   oml_box_tiny      box ocean, no-flux walls                      (-Docean_only)
   oml_box_tiny_sb   box ocean, specified southern temperature     (-Docean_only -Dsb_hflux)
   oml_cyc_tiny      zonally cyclic ocean, specified northern T    (-Docean_only -Dcyclic_ocean -Dnb_hflux)
+and on the tiny grids with two, five and six layers (entoc enters layers 1 and 2: at two layers layer 2 is the bottom;
+the five- and six-layer files hold the coupled runs after 1 and 2 steps only):
+  oml_box_tiny2     box_tiny2, 30 x 24 T cells, two layers;  oml_box_tiny5  box_tiny5, five layers
+  oml_cyc_tiny6     cyc_tiny6, six layers, -Dnb_hflux
 Each of these holds the inputs, the result of ONE `call oml` from them, and coupled runs
 (oml, qgostep, ocinvq, ocqbdy + averaging, src/q-gcm.F:1232-1249,1328-1366) after 1, 2, 26 and 40 steps.
 
@@ -39,10 +43,14 @@ sys.path.insert(0, os.path.join(ROOT, "q-gcm_amd", "python"))
 # fixture -> (reference configuration of oracle/ref_binding.CONFIGS, preset of qgcm_hip.config)
 VARIANTS = {"oml_box_tiny": ("box_tiny", "box_tiny"), "oml_box_tiny_sb": ("box_tiny_sb", "box_tiny"),
             "oml_cyc_tiny": ("cyc_tiny", "cyc_tiny"),
+            # two, five and six layers: entoc enters layers 1 and 2, and at two layers layer 2 is the bottom layer
+            "oml_box_tiny2": ("box_tiny2", "box_tiny2"), "oml_box_tiny5": ("box_tiny5", "box_tiny5"),
+            "oml_cyc_tiny6": ("cyc_tiny6", "cyc_tiny6"),
             "oml_box_seam": ("box_seam", "box_seam"), "oml_box_seam_nb": ("box_seam_nb", "box_seam"),
             "oml_box_seam_sbnb": ("box_seam_sbnb", "box_seam"), "oml_box_128_sbnb": ("box_128_sbnb", "box_128"),
             "oml_cyc_128": ("cyc_128", "cyc_128"), "oml_cyc_72_sbnb": ("cyc_72_sbnb", "cyc_72")}
 SNAPS = (1, 2, 26, 40)
+SHORT = {"oml_box_tiny5": (1, 2), "oml_cyc_tiny6": (1, 2)}  # the prefix of SNAPS that keeps the file under 1 MiB
 SEAM = tuple(v for v in VARIANTS if "tiny" not in v)  # the short fixtures of the tile-seam grids
 SEAM_SNAPS = (1, 2)
 SEAM_SEED = 11  # one seed: the three oml_box_seam* fixtures differ by the wall option alone
@@ -114,7 +122,7 @@ def make(name):
     out.update(call_sst=a, call_sstm=b, call_entoc=e, call_scal=s)
     load()
     done = 0
-    for n in (SEAM_SNAPS if seam else SNAPS):
+    for n in (SEAM_SNAPS if seam else SHORT.get(name, SNAPS)):
         r.steps_oml(done + 1, n - done)
         done = n
         st = r.get_state()

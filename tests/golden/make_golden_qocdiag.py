@@ -12,7 +12,7 @@ make_golden_tavg.py, and deleted.  The driver fills MODULE occonst / ocstate / i
 does, qocdiag_init (nsko) and qocdiag_out (nsko) (src/q-gcm.F:1052, 1234-1239), and ocnc_init / ocnc_out
 (src/q-gcm.F:1050, 1459-1461).
 
-  python tests/golden/make_golden_qocdiag.py          # writes tests/golden/qod_{box_tiny,cyc_tiny,box_tiny_ah2,box_tiny5}.npz
+  python tests/golden/make_golden_qocdiag.py          # writes tests/golden/qod_{box_tiny,cyc_tiny,box_tiny_ah2,box_tiny5,cyc_tiny6}.npz
   python tests/golden/make_golden_qocdiag.py time     # the reference's qocdiag_out time at 961 x 961 x 3, 16 threads
 """
 import os
@@ -292,7 +292,8 @@ def inputs(cfg, g, om, state, seed):
 
 # (golden file, fixture, reference configuration, state)
 CASES = [("box_tiny", "box_tiny", "box_tiny", "steps26"), ("cyc_tiny", "cyc_tiny", "cyc_tiny", "steps26"),
-         ("box_tiny_ah2", "box_tiny_ah2", "box_tiny", "steps26"), ("box_tiny5", "box_tiny5", "box_tiny5", "steps26")]
+         ("box_tiny_ah2", "box_tiny_ah2", "box_tiny", "steps26"), ("box_tiny5", "box_tiny5", "box_tiny5", "steps26"),
+         ("cyc_tiny6", "cyc_tiny6", "cyc_tiny6", "steps26")]
 
 
 def time_mode():

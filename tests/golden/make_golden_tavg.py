@@ -12,7 +12,8 @@ netCDF): they are derived here from the reference's scaled arrays with tavout's 
 ocnc_avgout_k247's scaling (netCDF-only in the reference), restated in the driver: rnsum = 1/nsum, rnsum * po_avg.
 All reference sources, objects and .mod files stay in the temporary directory, which is deleted.
 
-  python tests/golden/make_golden_tavg.py     # writes tests/golden/tav_{box_tiny,box_tiny_sb,cyc_tiny}.npz
+  python tests/golden/make_golden_tavg.py            # writes tests/golden/tav_<case>.npz for every case of CASES
+  python tests/golden/make_golden_tavg.py NAME ...   # only the named cases
 """
 import os
 import shutil
@@ -29,8 +30,14 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 REF = os.environ.get("QGCM_REFERENCE", "/root/reference")
 FC = os.environ.get("FC", "/opt/rocm/bin/amdflang")
 MODS = ["atconst_data.F", "occonst_data.F", "ocstate_data.F", "intrfac_data.F", "timinfo_data.F", "nc_subs.F"]
-TAV_STATES = ("steps25", "steps26", "steps60")          # tavocn inputs (after the step's averaging)
-AVG_STATES = ("ocqbdy", "steps2", "steps25", "steps60")  # avg_ocn_k247 inputs
+# per case: the tavocn inputs (after the step's averaging) and the avg_ocn_k247 inputs, from the snapshots the case's
+# fixture carries (tests/common.py SNAPS, plus ocqbdy)
+_T3, _A3 = ("steps25", "steps26", "steps60"), ("ocqbdy", "steps2", "steps25", "steps60")
+_T5, _A5 = ("steps1", "steps26", "steps2"), ("ocqbdy", "steps2", "steps1", "steps26")
+TAV_STATES = {"box_tiny": _T3, "box_tiny_sb": _T3, "cyc_tiny": _T3, "box_tiny2": ("steps1", "steps26", "steps1"),
+              "box_tiny5": _T5, "box_tiny5_sb": _T5, "cyc_tiny6": _T5}
+AVG_STATES = {"box_tiny": _A3, "box_tiny_sb": _A3, "cyc_tiny": _A3, "box_tiny2": ("ocqbdy", "steps1", "steps26", "steps1"),
+              "box_tiny5": _A5, "box_tiny5_sb": _A5, "cyc_tiny6": _A5}
 SUMS = ("txocav", "tyocav", "wpocav", "wtocav", "fmocav", "sstav", "pocav", "qocav", "uufo", "tufo", "utufo",
         "vvfo", "tvfo", "vtvfo")
 
@@ -103,11 +110,11 @@ def build(wrk, dims, opts):
     subprocess.check_call([FC, "-o", "tav_driver", "tav_driver.o"] + objs, cwd=wrk)
 
 
-def inputs(cfg, g, om):
+def inputs(cfg, g, om, states):
     """Per tavocn call: the fixture's state and forcing of its own (seeded), all stored in the golden file."""
     from qgcm_hip import synth
     calls = []
-    for n, st in enumerate(TAV_STATES):
+    for n, st in enumerate(states):
         sst, _, fnet, tx, ty = synth.mixed_layer_fields(cfg, om, seed=5 + n)
         wekto, wekpo = synth.wekpo_from_tau(cfg, tx, ty)
         calls.append(dict(po=g[st + "_po"], qo=g[st + "_qo"], wekpo=wekpo, tauxo=tx, tauyo=ty, wekto=wekto, sst=sst,
@@ -146,17 +153,24 @@ def run(wrk, cfg, om, calls, avg):
 
 # (golden file, fixture, reference configuration, cpp options)
 CASES = [("box_tiny", "box_tiny", "box_tiny", []), ("box_tiny_sb", "box_tiny", "box_tiny", ["sb_hflux"]),
-         ("cyc_tiny", "cyc_tiny", "cyc_tiny", ["cyclic_ocean", "nb_hflux"])]
+         ("cyc_tiny", "cyc_tiny", "cyc_tiny", ["cyclic_ocean", "nb_hflux"]),
+         # two, five and six layers: TAV_UU(nl) of every advection sum behind pocav / qocav
+         ("box_tiny2", "box_tiny2", "box_tiny2", []), ("box_tiny5", "box_tiny5", "box_tiny5", []),
+         ("box_tiny5_sb", "box_tiny5", "box_tiny5", ["sb_hflux"]),
+         ("cyc_tiny6", "cyc_tiny6", "cyc_tiny6", ["cyclic_ocean", "nb_hflux"])]
 
 if __name__ == "__main__":
     import ref_binding
     from qgcm_hip import oml_preset, preset
+    only = sys.argv[1:]
     for out_name, fixture, refcfg, opts in CASES:
+        if only and out_name not in only:
+            continue
         cfg = preset(fixture)
         om = oml_preset(cfg, sb_hflux="sb_hflux" in opts, nb_hflux="nb_hflux" in opts)
         g = np.load(os.path.join(HERE, fixture + ".npz"))
-        calls = inputs(cfg, g, om)
-        avg = [g[s + "_po"] for s in AVG_STATES]
+        calls = inputs(cfg, g, om, TAV_STATES[out_name])
+        avg = [g[s + "_po"] for s in AVG_STATES[out_name]]
         wrk = tempfile.mkdtemp(prefix="tavg_")
         try:
             build(wrk, ref_binding.CONFIGS[refcfg][:8], opts)
@@ -167,9 +181,16 @@ if __name__ == "__main__":
                                                         tsbdy=om.tsbdy, tnbdy=om.tnbdy).items()}
         out.update(c_cyclic=np.int64(cfg.cyclic), c_sb_hflux=np.int64("sb_hflux" in opts),
                    c_nb_hflux=np.int64("nb_hflux" in opts))
-        for n, f in enumerate(calls):
-            out.update({"in%d_%s" % (n, k): v for k, v in f.items()})
-        out["avg_po"] = np.stack(avg)
+        if cfg.nlo == 3:
+            for n, f in enumerate(calls):
+                out.update({"in%d_%s" % (n, k): v for k, v in f.items()})
+            out["avg_po"] = np.stack(avg)
+        else:  # po and qo are the fixture's own snapshots: their names are stored, not a second copy (file size)
+            out["c_fixture"] = np.array(fixture)
+            for n, f in enumerate(calls):
+                out.update({"in%d_%s" % (n, k): v for k, v in f.items() if k not in ("po", "qo")})
+                out["in%d_state" % n] = np.array(TAV_STATES[out_name][n])
+            out["avg_states"] = np.array(AVG_STATES[out_name])
         out.update({"out_" + k: np.asarray(v) for k, v in res.items()})
         np.savez_compressed(os.path.join(HERE, "tav_%s.npz" % out_name), **out)
         sys.stderr.write("wrote tav_%s.npz (nsumoc %d, nsum_ocavg %d)\n" % (out_name, res["nsumoc"], res["nsum_ocavg"]))

@@ -9,6 +9,9 @@ from qgcm_hip import hostinit
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ("area_box", "area_atm", "cfl_box", "cfl_cyc", "cfl_atm")
+# the ocean's CFL check at other layer counts: case -> ocean layers (their areas and atmosphere repeat cfl_box / cfl_cyc
+# and are not run again)
+CFL_LAYER_CASES = {"cfl_box2": 2, "cfl_box5": 5, "cfl_cyc6": 6}
 EXTREM = 1.0e30
 
 

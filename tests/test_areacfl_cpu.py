@@ -44,8 +44,7 @@ def test_area_tables_match_the_print_out(case, fluid):
     assert np.all(np.abs(w - g[fluid + "_wt"]) <= 0.5e-3 + 1e-12), (case, fluid, w, g[fluid + "_wt"])
 
 
-@pytest.mark.parametrize("fluid", FLUIDS)
-@pytest.mark.parametrize("case", na.CASES)
+@pytest.mark.parametrize("case,fluid", [(c, f) for c in na.CASES for f in FLUIDS] + [(c, "oc") for c in na.CFL_LAYER_CASES])
 def test_cfltry_restatement(case, fluid):
     """Maxima and Courant numbers to half a unit of the eighth significant digit (what `1p,9d15.7` prints, so a
     contraction in the reference build could not be told from it); the Bad lines exactly: quantity, i, j in print order,
@@ -98,6 +97,31 @@ def test_case_geometry():
     bad = na.cfl_of_fixture(na.load("cfl_cyc"), "oc")["bad"]
     assert 128 in bad[bad[:, 0] == names.index("v1"), 1]  # an offender whose +i neighbour is the one-point third tile
     assert 129 in bad[bad[:, 0] == names.index("u1"), 1]  # and one inside it
+
+
+@pytest.mark.parametrize("case,shape", [("cfl_box2", (97, 41, 2)), ("cfl_box5", (97, 41, 5)), ("cfl_cyc6", (129, 25, 6))])
+def test_layer_cases_tie_in_the_last_layer(case, shape):
+    """The cases at two, five and six layers: po differs in every layer, and the largest |v| of the LAST layer lies at
+    two points with bit-equal values.  The restatement reports the first in scan order (j outer), which is the one with
+    the larger i - and so does the reference: of its Bad lines with the largest printed value that one comes first."""
+    g = na.load(case)
+    p = g["in_po"]
+    nl = na.CFL_LAYER_CASES[case]
+    assert p.shape == shape and shape[2] == nl
+    assert len({p[:, :, k].tobytes() for k in range(nl)}) == nl
+    R = na.cfl_of_fixture(g, "oc")
+    assert len(R["maxima"]) == 2 * (nl + 1) and len(set(R["maxima"])) == 2 * (nl + 1) and np.all(R["maxima"] > 0.0)
+    q = R["names"].index("v%d" % nl)
+    assert q == 2 + nl + nl - 1
+    v = np.abs((1.0 / (float(g["c_dxo"]) * float(g["c_fnot"]))) * (p[1:, :, -1] - p[:-1, :, -1]))
+    at = np.argwhere(_bits(v) == _bits(v.max())) + 1
+    assert len(at) == 2
+    first, second = sorted(map(tuple, at.tolist()), key=lambda ij: (ij[1], ij[0]))
+    assert first[0] > second[0] + 64 and first[1] < second[1]  # j outer decides; the pair lies in different tile columns
+    assert tuple(R["loc"][q]) == first
+    rows = g["oc_bad"][g["oc_bad"][:, 0] == q]
+    top = rows[rows[:, 3] == rows[:, 3].max()]
+    assert [tuple(r) for r in top[:, 1:3].astype(int).tolist()] == [first, second]
 
 
 def test_read_areas_limits(tmp_path):

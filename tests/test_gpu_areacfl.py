@@ -12,6 +12,7 @@ import pytest
 import torch  # noqa: F401  (before the library: torch brings its own HIP runtime)
 
 import numpy_areacfl as na
+from common import OCEAN_LAYERS
 from qgcm_hip import AtmosModel, OceanConfig, OceanModel, QgcmHipError
 from qgcm_hip.config import atmos_of
 from qgcm_hip.slab import global_consts, partition, slab_slice
@@ -27,8 +28,11 @@ def bits(a):
 
 def config(g, case):
     nxta, nyta, nxaooc, nyaooc, ndxr = (int(v) for v in g["c_dims"])
-    return OceanConfig("areacfl_" + case, nxta, nyta, nxaooc, nyaooc, ndxr, 3, fnot=float(g["c_fnot"]), beta=1.7536e-11,
-                       cyclic=bool(g["c_cyclic"]), dxo=float(g["c_dxo"]))
+    nl = int(g["in_po"].shape[2])  # three, but for numpy_areacfl.CFL_LAYER_CASES
+    assert nl == na.CFL_LAYER_CASES.get(case, 3)
+    lay = OCEAN_LAYERS[nl] if nl != 3 else {}
+    return OceanConfig("areacfl_" + case, nxta, nyta, nxaooc, nyaooc, ndxr, nl, fnot=float(g["c_fnot"]), beta=1.7536e-11,
+                       cyclic=bool(g["c_cyclic"]), dxo=float(g["c_dxo"]), **lay)
 
 
 _MODELS = {}
@@ -127,7 +131,8 @@ def check_cfl(tag, got, want):
 
 
 @pytest.mark.parametrize("case,fluid", [("cfl_box", "oc"), ("cfl_cyc", "oc"), ("cfl_atm", "at"), ("cfl_box", "at"),
-                                        ("area_box", "oc"), ("area_atm", "at")])
+                                        ("area_box", "oc"), ("area_atm", "at"), ("cfl_box2", "oc"), ("cfl_box5", "oc"),
+                                        ("cfl_cyc6", "oc")])
 def test_cfl_against_the_reference(case, fluid):
     m, g = model(case, fluid)
     want = na.cfl_of_fixture(g, fluid)
@@ -147,6 +152,11 @@ def test_cfl_against_the_reference(case, fluid):
         assert np.array_equal(got[k], again[k])
     # another criterion: nothing at or above it -> no offenders; a low one -> many
     assert m.cfl(1.0e3)["nbad"].sum() == 0
+    if case in na.CFL_LAYER_CASES:  # the tie of the last layer's |v|: two Bad lines share the largest value, the first wins
+        q = got["names"].index("v%d" % na.CFL_LAYER_CASES[case])
+        rows = bad[bad[:, 0] == q]
+        top = rows[rows[:, 3] == rows[:, 3].max()]
+        assert len(top) == 2 and tuple(top[0, 1:3]) == tuple(got["loc"][q]) and top[0, 1] > top[1, 1] + 64
     low = 0.05
     check_cfl("%s %s crit %g" % (case, fluid, low), m.cfl(low), dict(na.cfl_of_fixture(dict(g, c_cflcrit=low), fluid)))
 
@@ -218,7 +228,8 @@ def test_slab_area_averages(split):
         close_slabs(so)
 
 
-@pytest.mark.parametrize("case,nranks", [("cfl_box", 0), ("cfl_box", 2), ("cfl_box", 3), ("cfl_cyc", 2), ("cfl_cyc", 3)])
+@pytest.mark.parametrize("case,nranks", [("cfl_box", 0), ("cfl_box", 2), ("cfl_box", 3), ("cfl_cyc", 2), ("cfl_cyc", 3),
+                                         ("cfl_box2", 2), ("cfl_box5", 2), ("cfl_box5", 3), ("cfl_cyc6", 2), ("cfl_cyc6", 3)])
 def test_slab_cfl(case, nranks):
     whole, g = model(case, "oc")
     crit = float(g["c_cflcrit"])

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 EXACT = ("sstmin", "sstmax", "umminoc", "ummaxoc", "vmminoc", "vmmaxoc", "cnmloc", "ugminoc", "ugmaxoc", "vgminoc",
          "vgmaxoc", "cnqgoc", "osfmin", "osfmax", "occirc", "occtot", "ocjpos", "ocjval")
 TOL = 1e-12
-GOLDEN_CASES = ["box_tiny", "cyc_tiny", "box_tiny5"]
+GOLDEN_CASES = ["box_tiny", "cyc_tiny", "box_tiny5", "box_tiny2", "cyc_tiny6"]
 
 
 def entoc_field(cfg):

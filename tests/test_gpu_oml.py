@@ -5,19 +5,20 @@ Bars: everything point-wise is bit exact (same expressions, contraction off); th
 the global sums (reference: sequential over i then j; here a fixed tree): the mean entrainment, and through it entoc,
 xon(1) and the line sums, and centoc.  sst itself is bitwise after one call and after the first step.
 
-Pinned by the reference (nine builds, tests/golden/make_golden_oml.py): the three tiny fixtures on one 48 x 36 tile
+Pinned by the reference (twelve builds, tests/golden/make_golden_oml.py; three of them the tiny grids with two, five and
+six layers, under the same fixed bars): the three tiny fixtures on one 48 x 36 tile
 column for 40 steps at fixed bars; six fixtures on grids that cross the tiles of k_oml_step (64 x 8) and k_oml_entoc
 (64 x 16) - one seam with a last tile of one column and one row, exact multiples of the tile with the wall rows on tile
 edges, the zonal wrap between tiles with a full and with a short last tile - under no-flux walls, -Dnb_hflux and both
 options on a box, -Dnb_hflux and both on a channel: sst / sstm by integer view, the reordered sums within the bounds
-derived in common.oml_bounds.  Pinned by the oracle only (itself bitwise the reference at all nine): grids of two and
+derived in common.oml_bounds.  Pinned by the oracle only (itself bitwise the reference at all twelve): grids of two and
 three tile columns and eight to twelve tile rows under all four option pairs, among them the channel without -Dnb_hflux,
 which no reference build carries, and -Dsb_hflux alone on a channel."""
 import numpy as np
 import pytest
 
-from common import (OML_CASES, OML_SEAM_CASES, OML_SNAPS, FIELDS, load_golden, make_oracle, oml_bounds, oml_check_sums,
-                    oml_config, oml_init_oracle, oml_load, relerr, same_bits)
+from common import (OML_CASES, OML_SEAM_CASES, FIELDS, load_golden, make_oracle, oml_bounds, oml_check_sums,
+                    oml_config, oml_init_oracle, oml_load, oml_snaps, relerr, same_bits)
 from qgcm_hip import OceanModel, oml_preset, preset, synth
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +51,8 @@ def test_one_call_vs_reference(case, cfgname):
 @pytest.mark.parametrize("case,cfgname", OML_CASES)
 def test_coupled_steps_vs_reference(case, cfgname):
     """qgcm_hip_steps with the mixed layer on = oml, qgostep, ocinvq, ocqbdy + averaging incl. sst
-    (src/q-gcm.F:1232-1249, 1328-1366); 40 steps cross the averaging twice and the three sst buffers rotate."""
+    (src/q-gcm.F:1232-1249, 1328-1366); 40 steps cross the averaging twice and the three sst buffers rotate (the
+    five- and six-layer fixtures hold steps 1 and 2 only: common.oml_snaps)."""
     g, cfg = load_golden(case), preset(cfgname)
     om = oml_config(g)
     m = OceanModel(cfg)
@@ -58,7 +60,7 @@ def test_coupled_steps_vs_reference(case, cfgname):
         m.oml_init(om)
         oml_load(m, g, cfg, False)
         done = 0
-        for n in OML_SNAPS:
+        for n in oml_snaps(case):
             m.steps(n - done, s0=done + 1)
             done = n
             sst, sstm = m.oml_get_state()

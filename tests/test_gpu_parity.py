@@ -253,16 +253,8 @@ def test_fast_kernels_with_two_and_four_layers(nlo, cyclic):
     from qgcm_hip import OceanModel, hostinit, synth
     from qgcm_hip.config import OceanConfig
     from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, global_consts, partition
-    lay = {2: dict(hoc=(500.0, 3500.0), gpoc=(0.02,), ah2oc=(0.0, 0.0), ah4oc=(1.2e10,) * 2),
-           4: dict(hoc=(300.0, 500.0, 1200.0, 2000.0), gpoc=(0.02, 0.01, 0.005), ah2oc=(0.0,) * 4, ah4oc=(1.2e10,) * 4),
-           5: dict(hoc=(300.0, 400.0, 600.0, 1000.0, 1700.0), gpoc=(0.02, 0.012, 0.008, 0.005), ah2oc=(0.0,) * 5, ah4oc=(1.2e10,) * 5),
-           6: dict(hoc=(250.0, 350.0, 500.0, 700.0, 1000.0, 1200.0), gpoc=(0.02, 0.015, 0.01, 0.007, 0.004), ah2oc=(0.0,) * 6,
-                   ah4oc=(1.2e10,) * 6),
-           8: dict(hoc=(200.0, 250.0, 300.0, 400.0, 500.0, 650.0, 800.0, 900.0), gpoc=(0.02, 0.016, 0.013, 0.01, 0.008, 0.006, 0.004),
-                   ah2oc=(0.0,) * 8, ah4oc=(1.2e10,) * 8)}[nlo]
-    base = dict(fnot=-1.19467e-04, beta=1.31301e-11, cyclic=True) if cyclic else dict(fnot=9.37456e-05, beta=1.7536e-11, cyclic=False)
-    cfg = OceanConfig("nl%d_%s" % (nlo, "cyc" if cyclic else "box"), 12 if cyclic else 16, 10, 12, 4 if cyclic else 6, 16, nlo,
-                      dxo=2.5e4, dta=240.0, **lay, **base)
+    from common import layer_cfg
+    cfg = layer_cfg(nlo, cyclic)  # nl<nlo>_box 193 x 97, nl<nlo>_cyc 193 x 65; layer tables: common.OCEAN_LAYERS
     assert cfg.nxto == 192
     o = make_oracle(cfg)
     m = OceanModel(cfg)

@@ -14,7 +14,7 @@ from common import load_golden
 from qgcm_hip import OceanModel, oml_preset, preset, synth
 from qgcm_hip.slab import partition
 from test_gpu_slab_diagnostics import close, gathered_model, make_slabs, slabs_like, stepped_slabs
-from test_tavg_cpu import calls, golden_consts
+from test_tavg_cpu import CASES, LAYER_CASES, calls, golden_consts, load_tav
 
 pytestmark = pytest.mark.gpu
 NAMES = nt.SUM_NAMES + ("uptpoc", "vptpoc")
@@ -27,11 +27,12 @@ def same(got, want):
 
 
 # 1. golden values of the reference ----------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["box_tiny", "box_tiny_sb", "cyc_tiny"])
+@pytest.mark.parametrize("case", CASES + LAYER_CASES)
 @pytest.mark.parametrize("mixed_layer", [False, True])
 def test_golden_time_means(case, mixed_layer):
-    g = load_golden("tav_" + case)
-    cfg = preset("cyc_tiny" if g["c_cyclic"] else "box_tiny")
+    g = load_tav(case)
+    cfg = preset(case[:-3] if case.endswith("_sb") else case)  # the fixture's grid and layers
+    assert bool(cfg.cyclic) == bool(g["c_cyclic"]) and (cfg.nxpo, cfg.nypo, cfg.nlo) == g["in0_po"].shape
     om = oml_preset(cfg, sb_hflux=bool(g["c_sb_hflux"]), nb_hflux=bool(g["c_nb_hflux"]))
     m = OceanModel(cfg)
     try:

@@ -187,7 +187,7 @@ def test_restatement_properties(cfgname):
         assert np.all(np.asarray(s[n]) >= np.abs(v[n]) * (1 - 1e-12)), n
 
 
-@pytest.mark.parametrize("name", ["box_tiny", "cyc_tiny", "box_tiny5"])
+@pytest.mark.parametrize("name", ["box_tiny", "cyc_tiny", "box_tiny5", "box_tiny2", "cyc_tiny6"])
 def test_restatement_reproduces_the_reference(name):
     """tests/golden/mon_<name>.npz holds the reference's own monnc_comp / couroc (make_golden_monnc.py): the restatement
     gives its extrema, jet position and value, transports and Courant numbers bitwise, and every integral to 1e-13 of

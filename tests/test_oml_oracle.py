@@ -1,5 +1,5 @@
 """Ocean mixed layer: the CPU restatement of oml / omladf (oracle/qgcm_oracle.c) against the
-golden vectors of the TRUE reference (tests/golden/make_golden_oml.py; nine reference builds).  Three on the 48 x 36 T
+golden vectors of the TRUE reference (tests/golden/make_golden_oml.py; twelve reference builds, three of them the tiny grids with two, five and six layers).  Three on the 48 x 36 T
 grid of the tiny presets (box with no-flux walls, box with -Dsb_hflux, cyclic with -Dnb_hflux), run for 40 steps; six on
 grids that cross the seams of the device kernels' tiles (65 x 25, 128 x 16, channels of 128 and 72 columns) with the wall
 options the tiny ones lack (-Dnb_hflux on a box, both options on a box, -Dsb_hflux on a channel), one call and two steps
@@ -9,9 +9,9 @@ checked against a numpy re-summation of the reference's own terms."""
 import numpy as np
 import pytest
 
-from common import (OML_CASES, OML_SEAM_CASES, OML_SEAM_SNAPS, OML_SNAPS, FIELDS, load_golden, make_oracle, oml_bounds,
+from common import (OML_CASES, OML_SEAM_CASES, OML_SEAM_SNAPS, FIELDS, load_golden, make_oracle, oml_bounds,
                     oml_check_sums, oml_config, oml_convecting, oml_init_oracle, oml_load, oml_numpy_sums,
-                    oml_seam_columns, relerr, same_bits)
+                    oml_seam_columns, oml_snaps, relerr, same_bits)
 from qgcm_hip import preset
 
 
@@ -53,7 +53,7 @@ def test_coupled_steps(case, cfgname):
                    om.nb_hflux, om.tnbdy)
         oml_load(o, g, cfg, True)
         done = 0
-        for n in OML_SNAPS:
+        for n in oml_snaps(case):
             o.steps_oml(done + 1, n - done)
             done = n
             sst, sstm, ent, _ = o.oml_get()

@@ -12,7 +12,7 @@ from common import load_golden
 from qgcm_hip import lib, model, preset
 from qgcm_hip.slab import HipSlab, SlabOcean
 
-CASES = ["box_tiny", "cyc_tiny", "box_tiny_ah2", "box_tiny5"]
+CASES = ["box_tiny", "cyc_tiny", "box_tiny_ah2", "box_tiny5", "cyc_tiny6"]
 NSKO = (1, 2, 7)
 NEW = ["qgcm_hip_qocdiag_len", "qgcm_hip_qocdiag", "qgcm_hip_qocdiag_schedule", "qgcm_hip_qocdiag_read",
        "qgcm_hip_ocnc_sample_len", "qgcm_hip_ocnc_sample", "qgcm_hip_subsample_rows"]
