@@ -903,6 +903,49 @@ int qgcm_hip_xforc_sst_init(qgcm_hip_handle atm, const qgcm_hip_xforc_sst_params
 int qgcm_hip_xforc_sst_set(qgcm_hip_handle atm, const double *sst);
 int qgcm_hip_xforc_sst_get(qgcm_hip_handle atm, double *fnetat, double *scal);
 
+/* ---- xforc on a y-slab ocean under a replicated atmosphere -------------------------------------------
+ * Every rank holds its ocean slab and, on the same device, a whole-domain atmosphere handle: a replica, stepped
+ * redundantly on every rank.  The replicas stay bitwise identical: everything one reads is computed from replicated
+ * data by the same kernels, or added from an all-gathered buffer in rank order on every rank.  With tau_udiff off the
+ * fine stress and tauxa, tauya, uekat, vekat, wekta, wekpa, txisat, txinat depend on pam only, so the atmosphere side
+ * is the whole-domain call's, unchanged, on each replica.  The ocean side is local: tauxo, tauyo, wekto on every local
+ * row of the slab (owned and halo) from the fine rows at the slab's global offset; wekpo on every local row but the
+ * outermost halo row towards a neighbour (the T row beyond it is not held; no kernel reads wekpo there); txisoc /
+ * txinoc of a cyclic ocean from the replicated fine rows on every rank, the whole-domain call's bits.  The heat half
+ * computes fnetoc pointwise on every local T row and, per atmosphere cell above the ocean, the sums over the points
+ * the slab OWNS (T rows g0..g1, g1-1 on the rank that owns row nypo) in the whole-domain kernel's order; the message
+ * is (4, nxaooc*nyaooc): the cell's fnetat sum and its arocav / slhfav / oradav parts, +0.0 for a cell the slab owns no
+ * point of.  The caller all-gathers the messages (rank-major); the combine adds them in rank order, then runs the
+ * whole-domain call's tail.  A cell inside one slab keeps the whole-domain bits; a cell a seam cuts, and the three
+ * monitors, agree to the rounding of a reordered sum.  With one rank every output is bitwise the whole-domain call's.
+ * qgcm_hip_xforc_slab_init(oc_slab, atm, p) / qgcm_hip_xforc_heat_slab_init(oc_slab, atm, p): as qgcm_hip_xforc_init /
+ *   _heat_init (same structs; fso, yto and nyaooc*ndxr describe the WHOLE basin's nypo - 1 T rows), for an ocean
+ *   handle that holds a slab - or the whole domain, as a lone slab.  Refuse, naming the reason and changing nothing: an
+ *   atmosphere handle that is not a whole-domain atmosphere, handles on different devices, tau_udiff (the fine stress
+ *   above the sea would need every slab's pom on every rank), geometry that does not match the slab's global grid, the
+ *   heat half before qgcm_hip_oml_init on the slab or qgcm_hip_aml_init on the atmosphere.  An atmosphere set up this
+ *   way is refused by qgcm_hip_xforc, _xforc_get, _xforc_heat_init / _get and qgcm_hip_coupled_set_xforc, and the
+ *   other way round.
+ * qgcm_hip_xforc_slab_msg_len(atm): doubles per rank's message: 4*nxaooc*nyaooc with the heat half, else 0.
+ * qgcm_hip_xforc_slab_part(oc_slab, atm, send_dev): asynchronous, on the atmosphere's stream, ordered against the
+ *   slab's stream as qgcm_hip_xforc is: the momentum half, fnetoc and the message into send_dev (device; may be NULL
+ *   without the heat half).  Results land where the whole-domain call puts them: wekpo, txisoc / txinoc where the slab
+ *   stages read them, tauxo, tauyo, wekto in the buffers of qgcm_hip_set_monitor_fields and the mixed layer's own,
+ *   fnetoc in the mixed layer's, the atmosphere's in its usual places.
+ * qgcm_hip_xforc_slab_combine(oc_slab, atm, gath_dev, nranks): heat half only; the rank-ordered sums of nranks
+ *   messages, then fnetat and the four monitors as the whole-domain call computes them; the slab's stream then waits.
+ * qgcm_hip_xforc_slab_get: synchronous copies, NULL skips: what qgcm_hip_xforc_get and qgcm_hip_xforc_heat_get return,
+ *   the ocean's fields with the slab's LOCAL rows: tauxo, tauyo, wekpo (nxpo, nyl), wekto, fnetoc (nxto, nyl-1).
+ * Not extended to the library's own RCCL exchanges (qgcm_hip_slab_steps): the caller carries the message. */
+int qgcm_hip_xforc_slab_init(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p);
+int qgcm_hip_xforc_heat_slab_init(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p);
+int qgcm_hip_xforc_slab_msg_len(qgcm_hip_handle atm);
+int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, double *send_dev);
+int qgcm_hip_xforc_slab_combine(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, const double *gath_dev, int nranks);
+int qgcm_hip_xforc_slab_get(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
+                            double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
+                            double *wekpo, double *txi, double *fnetoc, double *fnetat, double *scal);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

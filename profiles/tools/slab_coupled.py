@@ -1,0 +1,164 @@
+"""Timings of xforc and of the coupled window on a y-slab ocean under a replicated atmosphere at cpl_natl5
+(atmosphere 385 x 97, ocean 961 x 961, ndxr 16) on cuda:0, printed as a log (profiles/slab_coupled.log).  Virtual ranks
+on one GPU: every rank's replica and slab share the device, so the figures say what the calls cost, not how they
+scale.  Host clock around work that ends in a synchronise; medians.
+  python3 profiles/tools/slab_coupled.py   the whole-domain xforc() and coupled window (tau_udiff off, both mixed layers
+                                           and the heat half on), then - where the library has the slab entry points -
+                                           1, 2 and 4 virtual ranks: every rank's xforc_slab_part, every rank's combine,
+                                           and the window per ocean step
+With QGCM_HIP_LIB pointing at a build of the parent commit the same script gives the parent's whole-domain figures."""
+import os
+import sys
+import time
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+sys.path.insert(0, os.path.join(ROOT, "q-gcm_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+NWIN = 60  # atmospheric steps per timed window
+
+
+def inputs():
+    from common import cpl_fullsize_inputs, load_golden
+    from qgcm_hip import config
+    g = load_golden("cpl_natl5_sample")
+    oc, at = config.preset("cpl_natl5"), config.atmos_preset("cpl_natl5")
+    po, pom, wekpo, f = cpl_fullsize_inputs(g, oc, at)
+    yo = (np.arange(oc.nyto) + 0.5) / oc.nyto
+    sst = np.asfortranarray(np.broadcast_to(4.0 * np.cos(np.pi * yo)[None, :], (oc.nxto, oc.nyto)))
+    return dict(oc=oc, at=at, po=po, pom=pom, wekpo=wekpo, f=f, sst=sst, nstr=int(g["nstr"]))
+
+
+AM = dict(tat=(30.0, 40.0), aface=(1.1e-6, -0.4e-6), bface=0.7e-6, cface=-0.3e-6, dface=2.3e-4)
+HT = dict(D0up=6.5, Dmup=5.1, Dmdown=-5.6, Adown11=-4.7e-3, Bmup=8.9e-3, B1down=-3.1e-3, Cmup=-2.2e-3, C1down=1.3e-3)
+
+
+def atmosphere(I):
+    from common import atm_apply
+    from qgcm_hip import AtmosModel, config
+    at = I["at"]
+    a = AtmosModel(at, ddynat=I["f"]["ddynat"])
+    atm_apply(a, I["f"])
+    a.aml_init(config.AmlConfig(**AM))
+    x, y = (np.arange(at.nxta) + 0.5) / at.nxta, (np.arange(at.nyta) + 0.5) / at.nyta
+    ast = np.asfortranarray(-5.0 + 6.0 * np.cos(np.pi * y)[None, :] + 1.5 * np.cos(2 * np.pi * x)[:, None] * np.sin(np.pi * y)[None, :])
+    hm = np.asfortranarray(1000.0 + 40.0 * np.sin(2 * np.pi * x)[:, None] * np.sin(np.pi * y)[None, :])
+    a.aml_set_state(ast, ast, hm, hm)
+    return a
+
+
+def ocean(I):
+    from qgcm_hip import OceanModel, oml_preset
+    oc = I["oc"]
+    o = OceanModel(oc)
+    o.set_p(I["po"], I["pom"])
+    o.set_forcing(I["wekpo"], np.zeros_like(I["wekpo"]), np.zeros(oc.nlo - 1))
+    o.oml_init(oml_preset(oc))
+    o.oml_set_state(sst=I["sst"], sstm=I["sst"])
+    return o
+
+
+def med(v):
+    return float(np.median(v))
+
+
+def whole(I):
+    from qgcm_hip import config, coupled_steps, xforc, xforc_heat_setup, xforc_setup
+    o, a = ocean(I), atmosphere(I)
+    xforc_setup(o, a, tau_udiff=False)
+    xforc_heat_setup(o, a, config.HeatConfig(**HT))
+    t = []
+    for k in range(35):
+        t0 = time.perf_counter()
+        xforc(o, a)
+        a.sync()
+        t.append(1e6 * (time.perf_counter() - t0))
+    print("whole domain: one synchronised xforc() (both halves, tau_udiff off), us, median of 30: %.1f" % med(t[5:]), flush=True)
+    nstr, nt0, w = I["nstr"], 1, []
+    for k in range(5):
+        t0 = time.perf_counter()
+        coupled_steps(o, a, nt0, NWIN, nstr, xforc=True)
+        o.sync()
+        a.sync()
+        w.append(1e6 * (time.perf_counter() - t0) / (NWIN // nstr))
+        nt0 += NWIN
+    print("whole domain: coupled window of %d atmospheric steps (nstr %d, no CU ranges), us per ocean step: median of 4 "
+          "after one warm-up %.1f (%s)" % (NWIN, nstr, med(w[1:]), " ".join("%.1f" % v for v in w)), flush=True)
+    consts = None
+    if hasattr(o.L, "qgcm_hip_xforc_slab_init"):
+        from qgcm_hip.slab import global_consts
+        consts = (global_consts(I["oc"], o.helmholtz),)
+    o.close()
+    a.close()
+    return consts
+
+
+def slabbed(I, consts, nranks):
+    from qgcm_hip import config, oml_preset
+    from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, partition
+    oc = I["oc"]
+    o = ocean(I)
+    st, scal = o.get_state(), o.get_scalars()
+    o.close()
+    slabs = [HipSlab(oc, consts, g0, g1, r, nranks, sync_each_call=True) for r, (g0, g1) in enumerate(partition(oc.nypo, nranks))]
+    for x in slabs:
+        x.oml_init(oml_preset(oc))
+    so = SlabOcean(oc, slabs, LocalComm(nranks, after=torch.cuda.synchronize))
+    so.scatter_state(st[0], st[1], st[2], st[3], I["wekpo"], np.zeros_like(I["wekpo"]), np.zeros(oc.nlo - 1), scal)
+    for x in slabs:
+        x.oml_set_state(sst=I["sst"], sstm=I["sst"])
+    reps = [atmosphere(I) for _ in slabs]
+    so.xforc_setup(reps, tau_udiff=False)
+    so.xforc_heat_setup(config.HeatConfig(**HT))
+    send, gath = so._xf_bufs
+    tp, tc, tx = [], [], []
+    for k in range(35):
+        t0 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_part(a, send[i])
+        for a in reps:
+            a.sync()
+        t1 = time.perf_counter()
+        so.comm.all_gather(gath, send)
+        t2 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_combine(a, gath[i])
+        for a in reps:
+            a.sync()
+        t3 = time.perf_counter()
+        tp.append(1e6 * (t1 - t0))
+        tc.append(1e6 * (t3 - t2))
+        t0 = time.perf_counter()
+        so.xforc()
+        for a in reps:
+            a.sync()
+        tx.append(1e6 * (time.perf_counter() - t0))
+    print("%d virtual rank(s): synchronised, us, median of 30: xforc_slab_part on every rank %.1f (%.1f per rank), combine "
+          "on every rank %.1f (%.1f per rank), SlabOcean.xforc() with its host-staged all-gather %.1f; message %d doubles per rank"
+          % (nranks, med(tp[5:]), med(tp[5:]) / nranks, med(tc[5:]), med(tc[5:]) / nranks, med(tx[5:]), send[0].numel()), flush=True)
+    nstr, nt0, w = I["nstr"], 1, []
+    for k in range(5):
+        t0 = time.perf_counter()
+        so.coupled_steps(nt0, NWIN, nstr, xforc=True)
+        for m in slabs + reps:
+            m.sync()
+        w.append(1e6 * (time.perf_counter() - t0) / (NWIN // nstr))
+        nt0 += NWIN
+    ok = all(np.isfinite(x.get_state()[0]).all() for x in slabs) and all(np.isfinite(a.get_state()[0]).all() for a in reps)
+    print("%d virtual rank(s): coupled window of %d atmospheric steps (stage calls from Python, a synchronise after each, "
+          "every replica stepped), us per ocean step: median of 4 after one warm-up %.1f (%s); state finite: %s"
+          % (nranks, NWIN, med(w[1:]), " ".join("%.1f" % v for v in w), ok), flush=True)
+    for m in slabs + reps:
+        m.close()
+
+
+if __name__ == "__main__":
+    print("device: %s; library: %s" % (torch.cuda.get_device_name(0), "the build QGCM_HIP_LIB names" if os.environ.get("QGCM_HIP_LIB") else "in-tree"), flush=True)
+    I = inputs()
+    c = whole(I)
+    if c is not None:
+        for n in (1, 2, 4):
+            slabbed(I, c[0], n)

@@ -46,6 +46,7 @@
 #include "k_qocdiag.h"
 #include "k_setup.h"
 #include "k_xforc.h"
+#include "k_xforc_slab.h" // (the parameter structs; the kernels are k_xforc_slab.hip's)
 #include "k_row_split.h"
 
 // kernels that are templates on the number of layers: instantiated for nlo = 2 .. QGCM_HIP_MAXL (8); the fused fast
@@ -385,6 +386,7 @@ struct qgcm_hip_ctx {
   // Ekman velocity), the transposed weight tables and the two events that order the streams
   struct {
     bool on = false, coupled = false; // coupled: qgcm_hip_coupled_steps calls xforc before every ocean step
+    bool slab = false;                // set up by qgcm_hip_xforc_slab_init: `oc` is a y-slab, this atmosphere a replica
     qgcm_hip_xforc_params prm;
     qgcm_hip_ctx *oc = nullptr; // not owned
     int ldf = 0, ldtf = 0;
@@ -2893,24 +2895,27 @@ extern "C" int qgcm_hip_aml_get_diag(qgcm_hip_handle c, double *entat, double *d
 // xforc is off until qgcm_hip_xforc_init has gone through (it replaces the buffers)
 static void xf_off(qgcm_hip_ctx *a) {
   auto &x = a->xf;
-  x.on = x.coupled = false;
+  x.on = x.coupled = x.slab = false;
   x.oc = nullptr;
   x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
   x.sst.on = false;  // (likewise qgcm_hip_xforc_sst_init)
 }
 
-extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
-  const char *who = "qgcm_hip_xforc_init";
+// slab: the set-up of qgcm_hip_xforc_slab_init - the ocean handle holds rows of a basin of g.nyg rows
+static int xf_init(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const qgcm_hip_xforc_params *p, const char *who, bool slab) {
   if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
+  if (slab && !oc) QG_FAIL("%s: null ocean handle", who);
   if (check_atm(atm, who)) return 1;
   if (!atm->whole) QG_FAIL("%s: the atmosphere handle is a y-slab (xforc needs the whole domain)", who);
   if (oc) {
     if (oc->g.atm) QG_FAIL("%s: the first handle is an atmosphere (pass the ocean, or NULL for atmos_only)", who);
-    if (!oc->whole) QG_FAIL("%s: the ocean handle is a y-slab (xforc needs the whole domain)", who);
+    if (!slab && !oc->whole) QG_FAIL("%s: the ocean handle is a y-slab (xforc needs the whole domain)", who);
     if (check_ready(oc, who)) return 1;
     if (oc->device != atm->device) QG_FAIL("%s: the two handles live on different devices (%d, %d)", who, oc->device, atm->device);
   }
   if (p->tau_udiff && !oc) QG_FAIL("%s: tau_udiff needs an ocean (the reference ignores it when atmos_only)", who);
+  if (p->tau_udiff && slab)
+    QG_FAIL("%s: tau_udiff is not available with a y-slab ocean (the fine stress above the sea would need every slab's pom on every rank)", who);
   if (!p->stbbb || !p->stbus || !p->stbvs || !p->stbun || !p->stbvn) QG_FAIL("%s: a weight table is NULL", who);
   const int ndxr = p->ndxr, nxta = atm->g.nxt, nyta = atm->g.ny - 1;
   if (ndxr < 1 || ndxr > 64) QG_FAIL("%s: ndxr = %d outside 1..64", who, ndxr);
@@ -2919,7 +2924,7 @@ extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, cons
     QG_FAIL("%s: the fine grid %d*%d x %d*%d exceeds the kernels' launch limits", who, nxta, ndxr, nyta, ndxr);
   if (!(p->hmat > 0.0) || !(p->cdat > 0.0)) QG_FAIL("%s: need hmat > 0 and cdat > 0", who);
   if (oc) {
-    const int nxto = oc->g.nxt, nyto = oc->g.ny - 1;
+    const int nxto = oc->g.nxt, nyto = (slab ? oc->g.nyg : oc->g.ny) - 1;
     if (!(p->hmoc > 0.0)) QG_FAIL("%s: need hmoc > 0", who);
     if (p->nxaooc < 1 || p->nyaooc < 1 || nxto != p->nxaooc * ndxr || nyto != p->nyaooc * ndxr)
       QG_FAIL("%s: mismatched geometry: the ocean has %d x %d T cells, nxaooc*ndxr x nyaooc*ndxr = %d*%d x %d*%d", who, nxto,
@@ -2976,14 +2981,26 @@ extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, cons
   if (!x.ev_oc) HIPCHECK(hipEventCreateWithFlags(&x.ev_oc, hipEventDisableTiming));
   if (!x.ev_atm) HIPCHECK(hipEventCreateWithFlags(&x.ev_atm, hipEventDisableTiming));
   x.oc = oc;
+  x.slab = slab;
   x.on = true;
   return 0;
 }
 
-static int xf_ready(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const char *who) {
+extern "C" int qgcm_hip_xforc_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
+  return xf_init(oc, atm, p, "qgcm_hip_xforc_init", false);
+}
+
+// slab: one of the qgcm_hip_xforc_slab_* calls (their set-up and the whole-domain one exclude each other)
+static int xf_ready(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const char *who, bool slab = false) {
   if (!atm) QG_FAIL("%s: null atmosphere handle", who);
   if (check_atm(atm, who)) return 1;
+  if (slab) {
+    if (!atm->xf.on || !atm->xf.slab) QG_FAIL("%s: qgcm_hip_xforc_slab_init has not been called for this atmosphere", who);
+    if (!oc || atm->xf.oc != oc) QG_FAIL("%s: the ocean handle is not the one qgcm_hip_xforc_slab_init was called with", who);
+    return 0;
+  }
   if (!atm->xf.on) QG_FAIL("%s: qgcm_hip_xforc_init has not been called for this atmosphere", who);
+  if (atm->xf.slab) QG_FAIL("%s: this atmosphere's xforc was set up for a y-slab ocean (qgcm_hip_xforc_slab_init): use the qgcm_hip_xforc_slab_ calls", who);
   if (atm->xf.oc != oc) QG_FAIL("%s: the ocean handle is not the one qgcm_hip_xforc_init was called with", who);
   return 0;
 }
@@ -3037,6 +3054,17 @@ static int launch_xf_heat_sst(qgcm_hip_ctx *atm);
 // compiles to the device code it had without the kernel.
 hipError_t qg_launch_xf_heat_sst(hipStream_t st, const QgXfHeatParams &P);
 
+// the atmosphere side of the momentum half up to wekpa: the fine stress and every product that depends on pam only
+static void launch_xf_atmos(const QgXfParams &P, hipStream_t st) {
+  const dim3 b(XF_NT);
+  hipLaunchKernelGGL(k_xf_coarse, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_fine, dim3((P.nxta + XF_CX - 1) / XF_CX, P.nyta), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_atm, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_wekta, dim3((P.nxta + XF_NT - 1) / XF_NT, P.nyta), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_wektaor, dim3((P.nxtaor + XF_NT - 1) / XF_NT, P.nytaor), b, 0, st, P);
+  hipLaunchKernelGGL(k_xf_wekpa, dim3((P.nxpa + 63) / 64, P.nypa), dim3(64), 0, st, P);
+}
+
 // One `call xforc` on the atmosphere's stream, ordered against the ocean's stream by two events: the momentum half and,
 // once qgcm_hip_xforc_heat_init (without an ocean: qgcm_hip_xforc_sst_init) has set it up, the heat half.
 extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
@@ -3050,12 +3078,7 @@ extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
     HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
   }
   const dim3 b(XF_NT);
-  hipLaunchKernelGGL(k_xf_coarse, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
-  hipLaunchKernelGGL(k_xf_fine, dim3((P.nxta + XF_CX - 1) / XF_CX, P.nyta), b, 0, st, P);
-  hipLaunchKernelGGL(k_xf_atm, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
-  hipLaunchKernelGGL(k_xf_wekta, dim3((P.nxta + XF_NT - 1) / XF_NT, P.nyta), b, 0, st, P);
-  hipLaunchKernelGGL(k_xf_wektaor, dim3((P.nxtaor + XF_NT - 1) / XF_NT, P.nytaor), b, 0, st, P);
-  hipLaunchKernelGGL(k_xf_wekpa, dim3((P.nxpa + 63) / 64, P.nypa), dim3(64), 0, st, P);
+  launch_xf_atmos(P, st);
   if (oc) {
     const QgGeom &go = oc->g;
     auto &mo = oc->mon;
@@ -3085,10 +3108,9 @@ extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
   return 0;
 }
 
-extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
-                                  double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
-                                  double *wekpo, double *txi) {
-  if (xf_ready(oc, atm, "qgcm_hip_xforc_get")) return 1;
+// (an ocean's fields come with the rows its handle holds: a y-slab's local rows for qgcm_hip_xforc_slab_get)
+static int xf_get(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, double *tauxa, double *tauya, double *uekat, double *vekat, double *wekta,
+                  double *wekpa, double *tauxo, double *tauyo, double *wekto, double *wekpo, double *txi) {
   const QgGeom &g = atm->g;
   const auto &m = atm->atmon;
   const int nxt = g.nxt, nyt = g.ny - 1;
@@ -3123,6 +3145,13 @@ extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, doubl
     }
   }
   return 0;
+}
+
+extern "C" int qgcm_hip_xforc_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
+                                  double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
+                                  double *wekpo, double *txi) {
+  if (xf_ready(oc, atm, "qgcm_hip_xforc_get")) return 1;
+  return xf_get(oc, atm, tauxa, tauya, uekat, vekat, wekta, wekpa, tauxo, tauyo, wekto, wekpo, txi);
 }
 
 // ---------------------------------------------------------------------------
@@ -3166,19 +3195,20 @@ static int xf_bilint_tables(const char *who, int nxta, int nyta, int nxto, int n
   return 0;
 }
 
-extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p) {
-  const char *who = "qgcm_hip_xforc_heat_init";
+// slab: the set-up of qgcm_hip_xforc_heat_slab_init - the tables cover the whole basin's T rows (g.nyg - 1), which the
+// kernels of k_xforc_slab.h index by global row
+static int xf_heat_init(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const qgcm_hip_xforc_heat_params *p, const char *who, bool slab) {
   if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
   if (!oc) QG_FAIL("%s: the heat half needs an ocean (oc = NULL)", who);
   if (!atm->g.atm) QG_FAIL("%s: the second handle is an ocean (pass the atmosphere)", who);
   if (oc->g.atm) QG_FAIL("%s: the first handle is an atmosphere (pass the ocean)", who);
-  if (!atm->whole || !oc->whole) QG_FAIL("%s: the %s handle is a y-slab (xforc needs the whole domain)", who, atm->whole ? "ocean" : "atmosphere");
-  if (xf_ready(oc, atm, who)) return 1;
+  if (!atm->whole || (!slab && !oc->whole)) QG_FAIL("%s: the %s handle is a y-slab (xforc needs the whole domain)", who, atm->whole ? "ocean" : "atmosphere");
+  if (xf_ready(oc, atm, who, slab)) return 1;
   if (!atm->aml.on) QG_FAIL("%s: qgcm_hip_aml_init has not been called for this atmosphere", who);
   if (!oc->oml.on) QG_FAIL("%s: qgcm_hip_oml_init has not been called for this ocean", who);
   if (!p->fsa || !p->fso || !p->xta || !p->yta || !p->xto || !p->yto) QG_FAIL("%s: a table or a coordinate array is NULL", who);
   const qgcm_hip_xforc_params &x = atm->xf.prm;
-  const int nxta = atm->g.nxt, nyta = atm->g.ny - 1, nxto = oc->g.nxt, nyto = oc->g.ny - 1;
+  const int nxta = atm->g.nxt, nyta = atm->g.ny - 1, nxto = oc->g.nxt, nyto = (slab ? oc->g.nyg : oc->g.ny) - 1;
   std::vector<int> ix, iy;
   std::vector<double> wx, wy;
   if (xf_bilint_tables(who, nxta, nyta, nxto, nyto, atm->prm.dxo, atm->prm.dyo, p->xta, p->yta, p->xto, p->yto, ix, iy, wx, wy))
@@ -3207,6 +3237,10 @@ extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm,
   return 0;
 }
 
+extern "C" int qgcm_hip_xforc_heat_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p) {
+  return xf_heat_init(oc, atm, p, "qgcm_hip_xforc_heat_init", false);
+}
+
 // oc = nullptr: the set-up of qgcm_hip_xforc_sst_init - the SST grid is the atmosphere handle's own buffer, there is no
 // fnetoc and no fso (k_xf_heat_sst reads neither)
 static void xf_heat_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfHeatParams &P) {
@@ -3217,7 +3251,7 @@ static void xf_heat_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfHeatParams &P)
   const auto &a = atm->aml;
   memset(&P, 0, sizeof(P));
   P.nxta = atm->g.nxt; P.nyta = atm->g.ny - 1;
-  P.nxto = oc ? oc->g.nxt : x.nxaooc * x.ndxr; P.nyto = oc ? oc->g.ny - 1 : x.nyaooc * x.ndxr;
+  P.nxto = oc ? oc->g.nxt : x.nxaooc * x.ndxr; P.nyto = oc ? oc->g.nyg - 1 : x.nyaooc * x.ndxr; // (a y-slab: the basin's rows)
   P.ndxr = x.ndxr; P.nx1 = x.nx1; P.ny1 = x.ny1; P.nxaooc = x.nxaooc; P.nyaooc = x.nyaooc;
   P.ldta = a.ldt; P.lda = atm->g.ldx; P.ldto = oc ? oc->oml.ldt : ss.ldt; P.fstride = atm->g.fstride;
   P.astm = a.ast[a.iam]; P.hmm = a.hm[a.iam]; P.pam = atm->p[atm->ip ^ 1]; P.dtop = a.dtop;
@@ -3248,11 +3282,8 @@ static int launch_xf_heat(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm) {
   return 0;
 }
 
-extern "C" int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *fnetoc, double *fnetat, double *scal) {
-  const char *who = "qgcm_hip_xforc_heat_get";
-  if (!oc) QG_FAIL("%s: the heat half needs an ocean (oc = NULL)", who);
-  if (xf_ready(oc, atm, who)) return 1;
-  if (!atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_init has not been called", who);
+// (fnetoc comes with the T rows the ocean handle holds: a y-slab's local rows for qgcm_hip_xforc_slab_get)
+static int xf_heat_get(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, double *fnetoc, double *fnetat, double *scal) {
   HIPCHECK(hipStreamSynchronize(atm->stream)); // (xforc ran on the atmosphere's stream)
   if (fnetoc && download2d(oc, fnetoc, oc->oml.fnet, oc->oml.ldt, oc->g.nxt, oc->g.ny - 1)) return 1;
   if (fnetat && download2d(atm, fnetat, atm->tav.fnet, atm->aml.ldt, atm->g.nxt, atm->g.ny - 1)) return 1;
@@ -3261,6 +3292,123 @@ extern "C" int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, 
     HIPCHECK(hipStreamSynchronize(atm->stream));
   }
   return 0;
+}
+
+extern "C" int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *fnetoc, double *fnetat, double *scal) {
+  const char *who = "qgcm_hip_xforc_heat_get";
+  if (!oc) QG_FAIL("%s: the heat half needs an ocean (oc = NULL)", who);
+  if (xf_ready(oc, atm, who)) return 1;
+  if (!atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_init has not been called", who);
+  return xf_heat_get(oc, atm, fnetoc, fnetat, scal);
+}
+
+// ---------------------------------------------------------------------------
+// xforc for an ocean held as y-slabs under a replicated whole-domain atmosphere: every rank holds its slab
+// and, on the same device, a replica of the atmosphere that it steps redundantly.  With tau_udiff off the fine stress
+// and every atmosphere-side product depend on pam only: the kernels of k_xforc.h run unchanged on the replica.  The
+// ocean side is local to the slab's rows (k_xf_tauo at the slab's global row offset, k_wekto, k_xforc_slab.h); the
+// cells' heat sums are partial sums over the owned points, all-gathered by the caller between _part and _combine and
+// added in rank order on every rank, so the replicas stay bitwise identical.
+// ---------------------------------------------------------------------------
+hipError_t qg_launch_xf_slab_ocean(hipStream_t st, const QgXfSlabParams &P);
+hipError_t qg_launch_xf_heat_oc_slab(hipStream_t st, const QgXfHeatSlabParams &S);
+hipError_t qg_launch_xf_heat_combine(hipStream_t st, const double *gath, int nranks, int ncell, double *cell, double *part);
+
+extern "C" int qgcm_hip_xforc_slab_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
+  return xf_init(oc, atm, p, "qgcm_hip_xforc_slab_init", true);
+}
+
+extern "C" int qgcm_hip_xforc_heat_slab_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_heat_params *p) {
+  return xf_heat_init(oc, atm, p, "qgcm_hip_xforc_heat_slab_init", true);
+}
+
+extern "C" int qgcm_hip_xforc_slab_msg_len(qgcm_hip_handle atm) {
+  if (!atm || !atm->xf.on || !atm->xf.slab || !atm->xf.heat.on) return 0; // (the momentum half alone exchanges nothing)
+  return 4 * atm->xf.prm.nxaooc * atm->xf.prm.nyaooc;
+}
+
+// the ocean's next step reads wekpo, the stress, the line integrals and the mixed layer's forcing
+static int xf_slab_handover(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm) {
+  HIPCHECK(hipEventRecord(atm->xf.ev_atm, atm->stream));
+  HIPCHECK(hipStreamWaitEvent(oc->stream, atm->xf.ev_atm, 0));
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm, double *send_dev) {
+  const char *who = "qgcm_hip_xforc_slab_part";
+  if (xf_ready(oc, atm, who, true)) return 1;
+  auto &x = atm->xf;
+  if (x.heat.on && !send_dev) QG_FAIL("%s: the heat half is set up: send_dev must hold qgcm_hip_xforc_slab_msg_len doubles", who);
+  hipStream_t st = atm->stream;
+  QgXfParams P;
+  xf_fill(oc, atm, P);
+  const QgGeom &go = oc->g;
+  auto &mo = oc->mon;
+  // the slab's rows of the ocean: local row j is row j + joff of the basin (k_xf_tauo reads the fine row jocoff + j)
+  P.jocoff += go.joff;
+  P.sco = nullptr; // (k_xf_lines: the atmosphere's two sums; the cyclic ocean's are k_xf_lines_oc_slab's)
+  HIPCHECK(hipEventRecord(x.ev_oc, oc->stream));
+  HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
+  const dim3 b(XF_NT);
+  launch_xf_atmos(P, st);
+  hipLaunchKernelGGL(k_xf_tauo, dim3((P.nxpo + XF_NT - 1) / XF_NT, P.nypo), b, 0, st, P);
+  QgWekParams W;
+  memset(&W, 0, sizeof(W));
+  W.g = go; W.taux = mo.taux; W.tauy = mo.tauy; W.wekto = mo.wekto; W.wekpo = oc->wekpo; W.ldt = mo.ldt;
+  W.hxofac = P.hxofac;
+  hipLaunchKernelGGL(k_wekto, dim3((go.nxt + 255) / 256, go.ny - 1), dim3(256), 0, st, W);
+  QgXfSlabParams S;
+  memset(&S, 0, sizeof(S));
+  S.nx = go.nx; S.nxt = go.nxt; S.nyl = go.ny; S.joff = go.joff; S.nyg = go.nyg;
+  S.ldx = go.ldx; S.ldt = mo.ldt; S.ldf = x.ldf;
+  S.cyc = go.cyc; S.iocoff = P.iocoff; S.jocoff = P.jocoff - go.joff;
+  S.txf = x.txf; S.wekto = mo.wekto; S.wekpo = oc->wekpo; S.sco = oc->sc;
+  S.raoro = P.raoro; S.dxo = P.dxo;
+  HIPCHECK(qg_launch_xf_slab_ocean(st, S));
+  if (oc->oml.on) { // the mixed layer's own forcing buffers (same pitches)
+    auto &o = oc->oml;
+    const size_t nP = (size_t)go.ldx * go.ny * sizeof(double), nT = (size_t)o.ldt * (go.ny - 1) * sizeof(double);
+    HIPCHECK(hipMemcpyAsync(o.taux, mo.taux, nP, hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipMemcpyAsync(o.tauy, mo.tauy, nP, hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipMemcpyAsync(o.wekto, mo.wekto, nT, hipMemcpyDeviceToDevice, st));
+  }
+  hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
+  HIPCHECK(hipGetLastError());
+  if (x.heat.on) { // fnetoc on the slab's T rows and this rank's partial cell sums (src/xfosubs.F:774-817)
+    QgXfHeatSlabParams H;
+    memset(&H, 0, sizeof(H));
+    xf_heat_fill(oc, atm, H.h);
+    H.joff = go.joff; H.nytl = go.ny - 1;
+    H.jT0 = go.jlo; H.jT1 = (go.jhi + go.joff == go.nyg) ? go.jhi - 1 : go.jhi; // T row j lies between p rows j and j+1
+    H.msg = send_dev;
+    HIPCHECK(qg_launch_xf_heat_oc_slab(st, H));
+  }
+  return xf_slab_handover(oc, atm);
+}
+
+extern "C" int qgcm_hip_xforc_slab_combine(qgcm_hip_handle oc, qgcm_hip_handle atm, const double *gath_dev, int nranks) {
+  const char *who = "qgcm_hip_xforc_slab_combine";
+  if (xf_ready(oc, atm, who, true)) return 1;
+  if (!atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_slab_init has not been called (the momentum half has nothing to combine)", who);
+  if (!gath_dev || nranks < 1) QG_FAIL("%s: null buffer or nranks = %d", who, nranks);
+  QgXfHeatParams P;
+  xf_heat_fill(oc, atm, P);
+  hipStream_t st = atm->stream;
+  HIPCHECK(qg_launch_xf_heat_combine(st, gath_dev, nranks, P.ncell, P.cell, P.part));
+  hipLaunchKernelGGL(k_xf_heat_atm, dim3((P.nxta + 63) / 64, (P.nyta + 3) / 4), dim3(OML_NT), 0, st, P);
+  hipLaunchKernelGGL(k_xf_heat_final, dim3(1), dim3(OML_NT), 0, st, P);
+  HIPCHECK(hipGetLastError());
+  return xf_slab_handover(oc, atm);
+}
+
+extern "C" int qgcm_hip_xforc_slab_get(qgcm_hip_handle oc, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
+                                       double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
+                                       double *wekpo, double *txi, double *fnetoc, double *fnetat, double *scal) {
+  const char *who = "qgcm_hip_xforc_slab_get";
+  if (xf_ready(oc, atm, who, true)) return 1;
+  if ((fnetoc || fnetat || scal) && !atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_slab_init has not been called", who);
+  if (xf_get(oc, atm, tauxa, tauya, uekat, vekat, wekta, wekpa, tauxo, tauyo, wekto, wekpo, txi)) return 1;
+  return (fnetoc || fnetat || scal) ? xf_heat_get(oc, atm, fnetoc, fnetat, scal) : 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -147,6 +147,8 @@ SYMBOLS = [
     "qgcm_hip_aml_init", "qgcm_hip_aml_set_state", "qgcm_hip_aml_get_state", "qgcm_hip_aml", "qgcm_hip_aml_get_diag",
     "qgcm_hip_xforc_heat_init", "qgcm_hip_xforc_heat_get",
     "qgcm_hip_xforc_sst_init", "qgcm_hip_xforc_sst_set", "qgcm_hip_xforc_sst_get",
+    "qgcm_hip_xforc_slab_init", "qgcm_hip_xforc_heat_slab_init", "qgcm_hip_xforc_slab_msg_len", "qgcm_hip_xforc_slab_part",
+    "qgcm_hip_xforc_slab_combine", "qgcm_hip_xforc_slab_get",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
     "qgcm_hip_debug_live_allocs",
 ]
@@ -314,6 +316,13 @@ def load_library():
         L.qgcm_hip_xforc_sst_init.argtypes = [vp, C.POINTER(XforcSstParams)]
         L.qgcm_hip_xforc_sst_set.argtypes = [vp, dp]
         L.qgcm_hip_xforc_sst_get.argtypes = [vp, dp, dp]
+    if hasattr(L, "qgcm_hip_xforc_slab_init"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_xforc_slab_init.argtypes = [vp, vp, C.POINTER(XforcParams)]
+        L.qgcm_hip_xforc_heat_slab_init.argtypes = [vp, vp, C.POINTER(XforcHeatParams)]
+        L.qgcm_hip_xforc_slab_msg_len.argtypes = [vp]
+        L.qgcm_hip_xforc_slab_part.argtypes = [vp, vp, vp]
+        L.qgcm_hip_xforc_slab_combine.argtypes = [vp, vp, vp, C.c_int]
+        L.qgcm_hip_xforc_slab_get.argtypes = [vp, vp] + [dp] * 14
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),

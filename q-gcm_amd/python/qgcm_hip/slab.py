@@ -314,6 +314,43 @@ class HipSlab(Handle):
         check(self.L.qgcm_hip_prsamp_combine(self.h, self._ptr(gath), P, _dp(out)))
         return out
 
+    # xforc under a replicated atmosphere (SlabOcean.xforc): `atm` is this rank's AtmosModel --------------
+    def xforc_init(self, atm, p):
+        check(self.L.qgcm_hip_xforc_slab_init(self.h, atm.h, C.byref(p)))
+
+    def xforc_heat_init(self, atm, p, arrays=None):
+        """p: lib.XforcHeatParams; arrays: what it points to (fsa, fso, xta, yta, xto, yto), unused here."""
+        check(self.L.qgcm_hip_xforc_heat_slab_init(self.h, atm.h, C.byref(p)))
+
+    def xforc_msg_len(self, atm):
+        return self.L.qgcm_hip_xforc_slab_msg_len(atm.h)
+
+    def xforc_part(self, atm, send):
+        """The momentum half, fnetoc and this rank's partial cell sums -> send (device buffer of xforc_msg_len doubles,
+        None without the heat half); asynchronous, on the atmosphere's stream."""
+        check(self.L.qgcm_hip_xforc_slab_part(self.h, atm.h, self._ptr(send)))
+
+    def xforc_combine(self, atm, gath):
+        """All ranks' partial cell sums (rank-major) -> fnetat and the monitors on this rank's replica."""
+        check(self.L.qgcm_hip_xforc_slab_combine(self.h, atm.h, self._ptr(gath), int(self.nranks)))
+
+    def xforc_fetch(self, atm, heat):
+        """dict of the last xforc's outputs (qgcm_hip_xforc_slab_get): the momentum half's, or (heat) the heat half's."""
+        from .model import HEAT_SCALARS, XFORC_FIELDS, XFORC_INTEGRALS
+        c, o, nyl = atm.cfg, self.cfg, self.nyl
+        shapes = dict(tauxa=(c.nxpa, c.nypa), tauya=(c.nxpa, c.nypa), uekat=(c.nxpa, c.nyta), vekat=(c.nxta, c.nypa),
+                      wekta=(c.nxta, c.nyta), wekpa=(c.nxpa, c.nypa), tauxo=(o.nxpo, nyl), tauyo=(o.nxpo, nyl),
+                      wekto=(o.nxto, nyl - 1), wekpo=(o.nxpo, nyl))
+        if heat:
+            fo, fa, sc = np.zeros((o.nxto, nyl - 1), order="F"), np.zeros((c.nxta, c.nyta), order="F"), np.zeros(4)
+            check(self.L.qgcm_hip_xforc_slab_get(self.h, atm.h, *([None] * 11 + [_dp(fo), _dp(fa), _dp(sc)])))
+            return dict(fnetoc=fo, fnetat=fa, **{k: float(v) for k, v in zip(HEAT_SCALARS, sc)})
+        d = {n: np.zeros(shapes[n], order="F") for n in XFORC_FIELDS}
+        txi = np.zeros(4)
+        check(self.L.qgcm_hip_xforc_slab_get(self.h, atm.h, *([_dp(d[n]) for n in XFORC_FIELDS] + [_dp(txi), None, None, None])))
+        d.update({n: float(txi[k]) for k, n in enumerate(XFORC_INTEGRALS)})
+        return d
+
     # slab kernels -------------------------------------------------------------
     def thomas_phase(self, phase, gath, send):
         check(self.L.qgcm_hip_thomas_phase(self.h, int(phase), self._ptr(gath), self._ptr(send), self.rank, self.nranks))
@@ -770,6 +807,104 @@ class SlabOcean:
                 self.step(s)
             self._join()
         self.step_index = s0 + int(n)
+
+    # coupled runs: xforc under a replicated atmosphere, collective ---------------------------------------
+    def xforc_setup(self, atmospheres, cdat=1.3e-3, rhoat=1.0, rhooc=1.0e3, hmat=1000.0, hmoc=100.0, tau_udiff=False,
+                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None):
+        """As model.xforc_setup (ndxr, nxaooc, nyaooc default to the ocean configuration's), for the slabs: `atmospheres` holds one whole-domain AtmosModel per local slab, on that
+        slab's device - replicas of one atmosphere, which every rank steps redundantly and which stay bitwise identical.
+        tau_udiff is refused (the fine stress above the sea would need every slab's pom on every rank)."""
+        from .lib import XforcParams
+        S, oc = self.slabs, self.cfg
+        if len(atmospheres) != len(S):
+            raise ValueError("xforc_setup: %d atmospheres for %d local slabs" % (len(atmospheres), len(S)))
+        acfg = atmospheres[0].cfg
+        ndxr = int(oc.ndxr if ndxr is None else ndxr)
+        if tables is None:
+            tables = hostinit.bcuini(ndxr, acfg.bccoat, acfg.dya)
+        keep = [np.asfortranarray(tables[k], dtype=np.float64) for k in ("stbbb", "stbus", "stbvs", "stbun", "stbvn")]
+        for t in keep:
+            if t.shape != (16, ndxr + 1, ndxr + 1):
+                raise ValueError("xforc_setup: a weight table has shape %s, need (16, %d, %d)" % (t.shape, ndxr + 1, ndxr + 1))
+        p = XforcParams()
+        p.ndxr = ndxr
+        p.nxaooc, p.nyaooc = int(oc.nxaooc if nxaooc is None else nxaooc), int(oc.nyaooc if nyaooc is None else nyaooc)
+        p.nx1 = 1 + (acfg.nxta - p.nxaooc) // 2 if nx1 is None else int(nx1)
+        p.ny1 = 1 + (acfg.nyta - p.nyaooc) // 2 if ny1 is None else int(ny1)
+        p.cdat, p.raoro, p.hmat, p.hmoc = float(cdat), float(rhoat) / float(rhooc), float(hmat), float(hmoc)
+        p.bccoat, p.bccooc = float(acfg.bccoat), float(oc.bccooc)
+        p.tau_udiff = int(bool(tau_udiff))
+        p.stbbb, p.stbus, p.stbvs, p.stbun, p.stbvn = [_dp(t) for t in keep]
+        for x, a in zip(S, atmospheres):
+            x.xforc_init(a, p)
+            a.xforc_origin = (int(p.nx1), int(p.ny1))  # (where xforc_heat_setup finds the ocean)
+        self.atmos = list(atmospheres)
+        self._xf_bufs = None
+
+    def xforc_heat_setup(self, heat, hmadmp=None, hmat=None, fsa=None, fso=None, coords=None):
+        """As model.xforc_heat_setup, after xforc_setup, oml_init on every slab and aml_init on every replica; the tables
+        and coordinates are the whole basin's."""
+        from .lib import XforcHeatParams
+        from .model import _heat_params
+        for x, a in zip(self.slabs, self.atmos):
+            p = XforcHeatParams()
+            keep = _heat_params("SlabOcean.xforc_heat_setup", p, a, self.cfg, heat, hmadmp, hmat, coords, fsa=fsa, fso=fso)
+            x.xforc_heat_init(a, p, keep)
+            del keep  # (copied by now)
+        n = [x.xforc_msg_len(a) for x, a in zip(self.slabs, self.atmos)]
+        self._xf_bufs = ([x.new_buffer(m) for x, m in zip(self.slabs, n)], [x.new_buffer(m * self.P) for x, m in zip(self.slabs, n)])
+        self._settle()
+
+    def xforc(self):
+        """One `call xforc`: every local rank runs the momentum half on its replica and its slab's rows; with the heat
+        half, one all-gather of the partial cell sums (4*nxaooc*nyaooc doubles per rank) and the rank-ordered combine."""
+        S, A = self.slabs, self.atmos
+        self._join()
+        send, gath = self._xf_bufs if self._xf_bufs else ([None] * len(S), None)
+        for i, (x, a) in enumerate(zip(S, A)):
+            x.xforc_part(a, send[i])
+        if gath is None:
+            return
+        for a in A:  # the messages are complete before a transport reads them (they are written on the replicas' streams)
+            a.sync()
+        self._comm(self.comm.all_gather, gath, send)
+        for x in S:  # ... and gathered before the replicas' streams read them (a transport may run on the slab's stream)
+            x.sync()
+        for i, (x, a) in enumerate(zip(S, A)):
+            x.xforc_combine(a, gath[i])
+
+    def xforc_get(self):
+        """The momentum half's outputs of the last xforc(), one dict per local slab: model.xforc_get's names, the
+        ocean's fields with the slab's local rows (owned + halo; global row = local + slab.joff)."""
+        return [x.xforc_fetch(a, False) for x, a in zip(self.slabs, self.atmos)]
+
+    def xforc_heat_get(self):
+        """The heat half's outputs of the last xforc(), one dict per local slab: model.xforc_heat_get's names, fnetoc
+        with the slab's local T rows."""
+        return [x.xforc_fetch(a, True) for x, a in zip(self.slabs, self.atmos)]
+
+    def coupled_steps(self, nt0, n, nstr, xforc=False):
+        """As model.coupled_steps (src/q-gcm.F:1220-1268): n atmospheric steps nt = nt0.. on every replica with one slab
+        ocean step before every one with mod(nt,nstr) == 1; xforc = True: xforc() before each ocean step, False: the
+        forcing is held.  With the mixed layers on the window is xforc; oml; qgostep ...; (aml; qgastep ...) x nstr."""
+        nt0, n, nstr = int(nt0), int(n), int(nstr)
+        if nt0 < 1 or n < 0 or nstr < 1:
+            raise ValueError("coupled_steps: bad step range")
+        if not hasattr(self, "atmos"):
+            raise ValueError("coupled_steps: call xforc_setup first (it names the replicas of the atmosphere)")
+        nt, end = nt0, nt0 + n
+        while nt < end:
+            nxt = end
+            if nstr > 1:  # (nstr = 1 never steps the ocean in the reference)
+                if nt % nstr == 1:
+                    if xforc:
+                        self.xforc()
+                    self.steps(1, s0=(nt - 1) // nstr + 1)
+                nn = nt + (nstr - (nt - 1) % nstr)  # the next nt with mod(nt,nstr) == 1
+                nxt = min(nn, end)
+            for a in self.atmos:
+                a.steps(nxt - nt, s0=nt)
+            nt = nxt
 
     # helpers to scatter / gather global arrays (host side, for tests and set-up) --
     def scatter_state(self, po, pom, qo, qom, wekpo, entoc, xon, scal):
