@@ -926,13 +926,14 @@ int qgcm_hip_xforc_sst_get(qgcm_hip_handle atm, double *fnetat, double *scal);
  *   heat half before qgcm_hip_oml_init on the slab or qgcm_hip_aml_init on the atmosphere.  An atmosphere set up this
  *   way is refused by qgcm_hip_xforc, _xforc_get, _xforc_heat_init / _get and qgcm_hip_coupled_set_xforc, and the
  *   other way round.
- * qgcm_hip_xforc_slab_msg_len(atm): doubles per rank's message: 4*nxaooc*nyaooc with the heat half, else 0.
+ * qgcm_hip_xforc_slab_msg_len(atm): doubles per rank's message: 4*nxaooc*nyaooc with the heat half, else 0 (banded,
+ *   below: the momentum block in front).
  * qgcm_hip_xforc_slab_part(oc_slab, atm, send_dev): asynchronous, on the atmosphere's stream, ordered against the
  *   slab's stream as qgcm_hip_xforc is: the momentum half, fnetoc and the message into send_dev (device; may be NULL
  *   without the heat half).  Results land where the whole-domain call puts them: wekpo, txisoc / txinoc where the slab
  *   stages read them, tauxo, tauyo, wekto in the buffers of qgcm_hip_set_monitor_fields and the mixed layer's own,
  *   fnetoc in the mixed layer's, the atmosphere's in its usual places.
- * qgcm_hip_xforc_slab_combine(oc_slab, atm, gath_dev, nranks): heat half only; the rank-ordered sums of nranks
+ * qgcm_hip_xforc_slab_combine(oc_slab, atm, gath_dev, nranks): heat half only (banded, below: always); the rank-ordered sums of nranks
  *   messages, then fnetat and the four monitors as the whole-domain call computes them; the slab's stream then waits.
  * qgcm_hip_xforc_slab_get: synchronous copies, NULL skips: what qgcm_hip_xforc_get and qgcm_hip_xforc_heat_get return,
  *   the ocean's fields with the slab's LOCAL rows: tauxo, tauyo, wekpo (nxpo, nyl), wekto, fnetoc (nxto, nyl-1).
@@ -945,6 +946,49 @@ int qgcm_hip_xforc_slab_combine(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, co
 int qgcm_hip_xforc_slab_get(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, double *tauxa, double *tauya, double *uekat,
                             double *vekat, double *wekta, double *wekpa, double *tauxo, double *tauyo, double *wekto,
                             double *wekpo, double *txi, double *fnetoc, double *fnetat, double *scal);
+
+/* ---- the atmosphere side of the slab xforc split by bands of atmosphere rows ---------------------------
+ * An opt-in mode of the calls above.  The default stays the replicated path: every rank runs the atmosphere side on
+ * the whole fine grid.  Banded, rank r owns a band a0..a1 of the atmosphere's p rows ja = 1..nypa and runs the
+ * atmosphere side only on the fine rows that band's outputs, the line sums it owns and its slab's rows of tauxo / tauyo
+ * read: row-windowed launches of the same kernel text, so a row holds the bits the replicated call gives it.  The
+ * ranks' bands of tauxa, tauya, uekat, vekat, wekta, wekpa and the four line sums travel in front of the heat block in
+ * the ONE all-gather; the combine copies every rank's rows into the replica (no sum, no atomics), then runs the heat
+ * tail.  Every replica ends with the arrays of the replicated call, bitwise.  The fine arrays keep their full height;
+ * outside a rank's windows they hold stale values that nothing reads.
+ * qgcm_hip_xforc_bands: the plan, host code without a device; a pure function of its arguments.  Bands: rows 1..nypa
+ *   (nypa = nyta + 1) split evenly, the first nypa % nranks bands one row longer.  slab_lo[r]..slab_hi[r]: the global
+ *   ocean p rows rank r's slab OWNS (it holds three halo rows more towards each neighbour).  out[r], per rank:
+ *     a0, a1       the band
+ *     own          the line sums the rank forms: bit 0 txisat (a0 = 1), 1 txinat (a1 = nypa), 2 txisoc (the slab owns
+ *                  ocean row 1), 3 txinoc (it owns row nypo); bits 2, 3 matter for a cyclic ocean only
+ *     nseg, c0, c1 one or two intervals of cell rows (1-based, inclusive) k_xf_fine runs on: the band's and the slab's,
+ *                  one where they touch
+ *     f0, f1       the fine p rows those cell rows cover: the rank's fine-row window
+ *     t0, t1       the fine T rows of wektaor that wekpa on the band reads
+ *     nrow         rows per field in the message: the longest band
+ *     mom_len      doubles of the message's momentum block: 8 + 6 * nrow * nxpa - a0, a1, own, 0, the four line sums
+ *                  (0.0 where not owned), then tauxa, tauya, uekat, vekat, wekta, wekpa as (nrow, nxpa) from row a0
+ *                  on, 0.0 past the band, past a field's last row and past its last column
+ *   Refuses nranks outside 1..nypa and slab rows outside 1..nyaooc*ndxr+1.
+ * qgcm_hip_xforc_slab_bands(oc_slab, atm, a0, a1, nrow, nranks): after qgcm_hip_xforc_slab_init, switches the pair to
+ *   bands: this rank's band, the common row count and the rank count of the plan (the caller takes them from
+ *   qgcm_hip_xforc_bands; the library derives the windows from the band and the slab's own rows with the same code).
+ *   Refuses, naming the reason and changing nothing: a pair not set up by qgcm_hip_xforc_slab_init, a band outside
+ *   1..nypa, nrow shorter than the band.  qgcm_hip_xforc_slab_init again returns the pair to the replicated path.
+ *   Reads QGCM_HIP_XF_POISON (INTEGRATION): 1 = every _slab_part first fills the fine arrays with NaN bytes.
+ * Banded, qgcm_hip_xforc_slab_msg_len is mom_len plus the heat block's 4*nxaooc*nyaooc (0 without the heat half),
+ *   qgcm_hip_xforc_slab_part needs send_dev, and qgcm_hip_xforc_slab_combine is required without the heat half too:
+ *   the scatter, then the heat tail if the heat half is on; it refuses an nranks other than the plan's.
+ * Handles of one pair on different devices are refused as before; ranks on different GPUs are untested. */
+typedef struct qgcm_hip_xforc_band {
+  int a0, a1, own, nseg;
+  int c0[2], c1[2], f0[2], f1[2];
+  int t0, t1, nrow, mom_len;
+} qgcm_hip_xforc_band;
+int qgcm_hip_xforc_bands(int nxpa, int nyta, int ndxr, int ny1, int nyaooc, int nranks, const int *slab_lo,
+                         const int *slab_hi, qgcm_hip_xforc_band *out);
+int qgcm_hip_xforc_slab_bands(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, int a0, int a1, int nrow, int nranks);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of

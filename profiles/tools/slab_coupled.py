@@ -6,6 +6,9 @@ scale.  Host clock around work that ends in a synchronise; medians.
                                            and the heat half on), then - where the library has the slab entry points -
                                            1, 2 and 4 virtual ranks: every rank's xforc_slab_part, every rank's combine,
                                            and the window per ocean step
+  python3 profiles/tools/slab_coupled.py bands   the banded atmosphere side (profiles/slab_bands.log): on 1, 2
+                                           and 4 virtual ranks two set-ups side by side, replicated and banded, timed in
+                                           alternating blocks in one session: xforc_slab_part and the combine per rank
 With QGCM_HIP_LIB pointing at a build of the parent commit the same script gives the parent's whole-domain figures."""
 import os
 import sys
@@ -96,26 +99,11 @@ def whole(I):
     return consts
 
 
-def slabbed(I, consts, nranks):
-    from qgcm_hip import config, oml_preset
-    from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, partition
-    oc = I["oc"]
-    o = ocean(I)
-    st, scal = o.get_state(), o.get_scalars()
-    o.close()
-    slabs = [HipSlab(oc, consts, g0, g1, r, nranks, sync_each_call=True) for r, (g0, g1) in enumerate(partition(oc.nypo, nranks))]
-    for x in slabs:
-        x.oml_init(oml_preset(oc))
-    so = SlabOcean(oc, slabs, LocalComm(nranks, after=torch.cuda.synchronize))
-    so.scatter_state(st[0], st[1], st[2], st[3], I["wekpo"], np.zeros_like(I["wekpo"]), np.zeros(oc.nlo - 1), scal)
-    for x in slabs:
-        x.oml_set_state(sst=I["sst"], sstm=I["sst"])
-    reps = [atmosphere(I) for _ in slabs]
-    so.xforc_setup(reps, tau_udiff=False)
-    so.xforc_heat_setup(config.HeatConfig(**HT))
+def time_xforc(so, slabs, reps, n):
+    """n synchronised xforc calls in their parts: us of (every rank's part, every rank's combine, SlabOcean.xforc())."""
     send, gath = so._xf_bufs
     tp, tc, tx = [], [], []
-    for k in range(35):
+    for k in range(n):
         t0 = time.perf_counter()
         for i, (x, a) in enumerate(zip(slabs, reps)):
             x.xforc_part(a, send[i])
@@ -136,6 +124,33 @@ def slabbed(I, consts, nranks):
         for a in reps:
             a.sync()
         tx.append(1e6 * (time.perf_counter() - t0))
+    return tp, tc, tx
+
+
+def slab_setup(I, consts, nranks, bands=False):
+    from qgcm_hip import config, oml_preset
+    from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, partition
+    oc = I["oc"]
+    o = ocean(I)
+    st, scal = o.get_state(), o.get_scalars()
+    o.close()
+    slabs = [HipSlab(oc, consts, g0, g1, r, nranks, sync_each_call=True) for r, (g0, g1) in enumerate(partition(oc.nypo, nranks))]
+    for x in slabs:
+        x.oml_init(oml_preset(oc))
+    so = SlabOcean(oc, slabs, LocalComm(nranks, after=torch.cuda.synchronize))
+    so.scatter_state(st[0], st[1], st[2], st[3], I["wekpo"], np.zeros_like(I["wekpo"]), np.zeros(oc.nlo - 1), scal)
+    for x in slabs:
+        x.oml_set_state(sst=I["sst"], sstm=I["sst"])
+    reps = [atmosphere(I) for _ in slabs]
+    so.xforc_setup(reps, tau_udiff=False, **(dict(bands=True) if bands else {}))
+    so.xforc_heat_setup(config.HeatConfig(**HT))
+    return so, slabs, reps
+
+
+def slabbed(I, consts, nranks):
+    so, slabs, reps = slab_setup(I, consts, nranks)
+    send, gath = so._xf_bufs
+    tp, tc, tx = time_xforc(so, slabs, reps, 35)
     print("%d virtual rank(s): synchronised, us, median of 30: xforc_slab_part on every rank %.1f (%.1f per rank), combine "
           "on every rank %.1f (%.1f per rank), SlabOcean.xforc() with its host-staged all-gather %.1f; message %d doubles per rank"
           % (nranks, med(tp[5:]), med(tp[5:]) / nranks, med(tc[5:]), med(tc[5:]) / nranks, med(tx[5:]), send[0].numel()), flush=True)
@@ -155,9 +170,44 @@ def slabbed(I, consts, nranks):
         m.close()
 
 
+def banded(I, consts, nranks, rounds=4):
+    """Replicated and banded set-ups of `nranks` virtual ranks side by side, timed in alternating blocks of 25 calls (the
+    first 5 of a block dropped): per mode the median of each block, then the median and the spread (max - min) of the
+    block medians.  The two agree bitwise (tests/test_gpu_xforc_bands.py); checked here on wekpa and fnetat."""
+    sets = [slab_setup(I, consts, nranks, bands=b) for b in (False, True)]
+    blocks = {False: [], True: []}
+    for rnd in range(rounds):
+        for b, (so, slabs, reps) in zip((False, True), sets):
+            tp, tc, tx = time_xforc(so, slabs, reps, 25)
+            blocks[b].append((med(tp[5:]) / nranks, med(tc[5:]) / nranks, med(tx[5:])))
+    out = [[dict(m, **h) for m, h in zip(so.xforc_get(), so.xforc_heat_get())] for so, _, _ in sets]
+    same = all(np.array_equal(x[f].view(np.int64), y[f].view(np.int64)) for x, y in zip(*out) for f in ("wekpa", "fnetat", "tauxo", "vekat"))
+    plan = sets[1][0].xforc_plan
+    nfine = I["at"].nyta * I["oc"].ndxr + 1
+    print("%d virtual rank(s): message %d (replicated) / %d (banded) doubles per rank; fine rows computed per rank, of %d: %s; "
+          "outputs bit-equal: %s" % (nranks, sets[0][0]._xf_bufs[0][0].numel(), sets[1][0]._xf_bufs[0][0].numel(), nfine,
+                                     " ".join(str(sum(f1 - f0 + 1 for f0, f1 in p["fine"])) for p in plan), same), flush=True)
+    for b, name in ((False, "replicated"), (True, "banded    ")):
+        for k, what in enumerate(("xforc_slab_part per rank", "combine per rank", "SlabOcean.xforc() with its host-staged all-gather")):
+            v = [blk[k] for blk in blocks[b]]
+            print("%d virtual rank(s), %s: %s, us: median of the block medians %.1f, spread %.1f (%s)"
+                  % (nranks, name, what, med(v), max(v) - min(v), " ".join("%.1f" % t for t in v)), flush=True)
+    for so, slabs, reps in sets:
+        for m in slabs + reps:
+            m.close()
+
+
 if __name__ == "__main__":
     print("device: %s; library: %s" % (torch.cuda.get_device_name(0), "the build QGCM_HIP_LIB names" if os.environ.get("QGCM_HIP_LIB") else "in-tree"), flush=True)
     I = inputs()
+    if sys.argv[1:] == ["bands"]:
+        from qgcm_hip.slab import global_consts
+        o = ocean(I)
+        consts = global_consts(I["oc"], o.helmholtz)
+        o.close()
+        for n in (1, 2, 4):
+            banded(I, consts, n)
+        sys.exit(0)
     c = whole(I)
     if c is not None:
         for n in (1, 2, 4):

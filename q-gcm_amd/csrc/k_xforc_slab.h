@@ -11,11 +11,21 @@
 //                         point of
 //   k_xf_heat_combine     cell sums and monitor partials = the ranks' messages added in rank order (the same on every rank)
 //
+// and, for the banded mode (rank r runs the atmosphere side on the fine rows its band of atmosphere p rows and
+// its slab need, instead of on the whole replica), what the atmosphere side becomes:
+//
+//   k_xf_*_win            the atmosphere-side kernels of k_xforc.h on the rows j0 .. j0 + gridDim.y - 1: the same text
+//                         (k_xforc_rows.inc), so a row holds the bits the whole-domain launch gives it
+//   k_xf_band_pack        the band's rows of tauxa, tauya, uekat, vekat, wekta, wekpa and the line sums the rank owns
+//                         -> the message's momentum block
+//   k_xf_band_scatter     every rank's rows and line sums -> the replica's arrays and scalars: a copy, no sum
+//
 // A cell wholly inside one slab keeps the bits of the whole-domain sum (x + 0.0 = x); a cell a seam cuts is a sum of the
 // same terms in another order.  No atomics; every sum has a fixed tree.
 #pragma once
 #include "qgcm_dev.h"
 #include "k_xf_heat_params.h"
+#include "k_xforc_rows.h" // QgXfParams, xf_point
 
 #define XFS_NT 256
 
@@ -28,7 +38,33 @@ struct QgXfSlabParams {
   double *wekpo;
   QgScalars *sco;              // the cyclic ocean's device scalars
   double raoro, dxo;
+  int lines;                   // k_xf_lines_oc_slab: bit 0 txisoc, bit 1 txinoc (replicated: 3; banded: what the slab's rows hold)
 };
+
+// the window of a k_xf_*_win launch
+struct QgXfWin {
+  int j0;     // the row of blockIdx.y = 0
+  int jumax;  // k_xf_atm_win: the last row that forms uekat (the row past a band is computed for its vekat alone)
+  int lines;  // k_xf_lines_win: bit 0 txisat, bit 1 txinat
+};
+
+// The momentum block of a banded rank's message: XFB_HDR doubles - a0, a1 (the band, p rows of the atmosphere), own
+// (bit 0 txisat, 1 txinat, 2 txisoc, 3 txinoc: the line sums this rank formed), 0, then the four sums (0.0 where not
+// owned) - and six fields of nrow rows (the longest band) by nxpa columns: tauxa, tauya, uekat, vekat, wekta, wekpa from
+// row a0 on, 0.0 past the band, past a field's last row (uekat, wekta: nyta) and past its last column (vekat, wekta: nxta).
+#define XFB_HDR 8
+#define XFB_NF 6
+struct QgXfBandMsg {
+  int nxpa, nxta, nypa, nyta, lda, ldta;
+  int a0, a1, own, nrow;  // pack: this rank's band
+  int nranks;             // scatter
+  long stride;            // scatter: rank r's message starts at gath + r * stride
+  double *fld[XFB_NF];    // tauxa, tauya, uekat, vekat, wekta, wekpa
+  QgScalars *sca, *sco;   // (sco: the cyclic ocean's, or nullptr)
+  double *msg;            // pack
+  const double *gath;     // scatter
+};
+static inline long xfb_mom_len(int nrow, int nxpa) { return XFB_HDR + (long)XFB_NF * nrow * nxpa; }
 
 struct QgXfHeatSlabParams {
   QgXfHeatParams h;   // nyto and the tables: the GLOBAL ocean's; sstm, fnetoc, ldto: the slab's local T rows
@@ -65,7 +101,7 @@ __global__ __launch_bounds__(XFS_NT) void k_xf_wekpo_slab(const QgXfSlabParams P
 }
 
 // One workgroup of 256: sums 2 and 3 of k_xf_lines (tauxo rows 1 + 2 and nypo-1 + nypo of the GLOBAL ocean), thread-strided
-// along the row, wave butterfly, waves left to right.
+// along the row, wave butterfly, waves left to right.  P.lines: which of the two; the other's rows are not read.
 __global__ __launch_bounds__(XFS_NT) void k_xf_lines_oc_slab(const QgXfSlabParams P) {
   __shared__ double red[2][XFS_NT / 64];
   const int tid = threadIdx.x;
@@ -73,10 +109,14 @@ __global__ __launch_bounds__(XFS_NT) void k_xf_lines_oc_slab(const QgXfSlabParam
   for (int i = 1 + tid; i <= P.nx; i += XFS_NT) {
     const double w = (i == 1 || i == P.nx) ? 0.5 : 1.0;
     const double *c = P.txf + (long)P.jocoff * P.ldf + (P.iocoff + i - 1); // fine row of ocean row 1
-    const double a0 = P.raoro * c[0], a1 = P.raoro * c[P.ldf];
-    const double b0 = P.raoro * c[(long)(P.nyg - 2) * P.ldf], b1 = P.raoro * c[(long)(P.nyg - 1) * P.ldf];
-    s[0] += w * (a0 + a1);
-    s[1] += w * (b0 + b1);
+    if (P.lines & 1) {
+      const double a0 = P.raoro * c[0], a1 = P.raoro * c[P.ldf];
+      s[0] += w * (a0 + a1);
+    }
+    if (P.lines & 2) {
+      const double b0 = P.raoro * c[(long)(P.nyg - 2) * P.ldf], b1 = P.raoro * c[(long)(P.nyg - 1) * P.ldf];
+      s[1] += w * (b0 + b1);
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
@@ -92,8 +132,8 @@ __global__ __launch_bounds__(XFS_NT) void k_xf_lines_oc_slab(const QgXfSlabParam
       t[v] = 0.0;
       for (int w = 0; w < XFS_NT / 64; ++w) t[v] += red[v][w];
     }
-    P.sco->txisoc = 0.5 * P.dxo * t[0];
-    P.sco->txinoc = 0.5 * P.dxo * t[1];
+    if (P.lines & 1) P.sco->txisoc = 0.5 * P.dxo * t[0];
+    if (P.lines & 2) P.sco->txinoc = 0.5 * P.dxo * t[1];
   }
 }
 
@@ -136,16 +176,88 @@ __global__ __launch_bounds__(64) void k_xf_heat_oc_slab(const QgXfHeatSlabParams
   }
 }
 
-// grid: ceil(ncell/256): thread c adds the ranks' four partials of cell c in rank order
-__global__ __launch_bounds__(XFS_NT) void k_xf_heat_combine(const double *gath, int nranks, int ncell, double *cell, double *part) {
+// grid: ceil(ncell/256): thread c adds the ranks' four partials of cell c in rank order; rank r's heat block (4, ncell)
+// starts at gath + r * stride + off (replicated: stride 4 * ncell, off 0; banded: behind the momentum block)
+__global__ __launch_bounds__(XFS_NT) void k_xf_heat_combine(const double *gath, int nranks, int ncell, long stride, long off,
+                                                            double *cell, double *part) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncell) return;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    double s = gath[q * ncell + c];
-    for (int r = 1; r < nranks; ++r) s += gath[((long)r * 4 + q) * ncell + c];
+    const double *g = gath + off + (long)q * ncell + c;
+    double s = g[0];
+    for (int r = 1; r < nranks; ++r) s += g[r * stride];
     if (q == 0) cell[c] = s;
     else part[(q - 1) * ncell + c] = s;
   }
+}
+
+// ---- banded mode -------------------------------------------------------------------------------------------
+// The atmosphere-side kernels on a window of rows: the text of k_xforc.h's kernels with the row of blockIdx.y = 0, the
+// last uekat row and the choice of line sums taken from W.
+#define XF_K(name) name##_win
+#define XF_WIN_ARG , const QgXfWin W
+#define XF_J0 W.j0
+#define XF_JUMAX W.jumax
+#define XF_SOUTH ((W.lines & 1) != 0)
+#define XF_NORTH ((W.lines & 2) != 0)
+#define XF_LINES_OC false
+#define XF_WINDOWED 1
+#include "k_xforc_rows.inc"
+#undef XF_K
+#undef XF_WIN_ARG
+#undef XF_J0
+#undef XF_JUMAX
+#undef XF_SOUTH
+#undef XF_NORTH
+#undef XF_LINES_OC
+#undef XF_WINDOWED
+
+// field f of the message: its width, its height and its pitch in the replica
+__device__ __forceinline__ void xfb_field(const QgXfBandMsg &B, int f, int &w, int &h, int &ld) {
+  const bool tcol = f == 3 || f == 4, trow = f == 2 || f == 4; // vekat, wekta: nxta columns; uekat, wekta: nyta rows
+  w = tcol ? B.nxta : B.nxpa;
+  h = trow ? B.nyta : B.nypa;
+  ld = tcol ? B.ldta : B.lda;
+}
+
+// grid: (ceil(nxpa/256), nrow, XFB_NF): message row jr of field f = the replica's row a0 + jr, or 0.0
+__global__ __launch_bounds__(XFS_NT) void k_xf_band_pack(const QgXfBandMsg B) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, jr = blockIdx.y, f = blockIdx.z;
+  if (i == 0 && jr == 0 && f == 0) {
+    double *h = B.msg;
+    h[0] = (double)B.a0; h[1] = (double)B.a1; h[2] = (double)B.own; h[3] = 0.0;
+    h[4] = (B.own & 1) ? B.sca->txisoc : 0.0;
+    h[5] = (B.own & 2) ? B.sca->txinoc : 0.0;
+    h[6] = (B.own & 4) ? B.sco->txisoc : 0.0;
+    h[7] = (B.own & 8) ? B.sco->txinoc : 0.0;
+  }
+  if (i >= B.nxpa) return;
+  int w, h, ld;
+  xfb_field(B, f, w, h, ld);
+  const int ja = B.a0 + jr;
+  double v = 0.0;
+  if (ja <= B.a1 && ja <= h && i < w) v = B.fld[f][(long)(ja - 1) * ld + i];
+  B.msg[XFB_HDR + ((long)f * B.nrow + jr) * B.nxpa + i] = v;
+}
+
+// grid: (ceil(nxpa/256), nrow, XFB_NF * nranks): rank r's message row jr of field f -> the replica's row a0(r) + jr.  The
+// bands tile the rows, so every point has one writer; a header that does not describe a band inside the grid writes nothing.
+__global__ __launch_bounds__(XFS_NT) void k_xf_band_scatter(const QgXfBandMsg B) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, jr = blockIdx.y, r = blockIdx.z / XFB_NF, f = blockIdx.z % XFB_NF;
+  const double *m = B.gath + (long)r * B.stride;
+  const int a0 = (int)m[0], a1 = (int)m[1], own = (int)m[2];
+  if (a0 < 1 || a1 > B.nypa || a1 < a0 || a1 - a0 + 1 > B.nrow) return;
+  if (i == 0 && jr == 0 && f == 0) {
+    if (own & 1) B.sca->txisoc = m[4];
+    if (own & 2) B.sca->txinoc = m[5];
+    if (B.sco && (own & 4)) B.sco->txisoc = m[6];
+    if (B.sco && (own & 8)) B.sco->txinoc = m[7];
+  }
+  int w, h, ld;
+  xfb_field(B, f, w, h, ld);
+  const int ja = a0 + jr;
+  if (i >= w || ja > a1 || ja > h) return;
+  B.fld[f][(long)(ja - 1) * ld + i] = m[XFB_HDR + ((long)f * B.nrow + jr) * B.nxpa + i];
 }
 #endif // QG_XFORC_SLAB_KERNELS

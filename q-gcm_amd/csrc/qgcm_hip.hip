@@ -410,6 +410,13 @@ struct qgcm_hip_ctx {
       double dxo = 0.0, dyo = 0.0;
       QgDbl sst;
     } sst;
+    // banded mode of the slab set-up (qgcm_hip_xforc_slab_bands): this rank's band and windows, the common
+    // row count of the message and the rank count the plan was made for
+    struct {
+      bool on = false, poison = false; // poison: QGCM_HIP_XF_POISON=1 - NaN bytes into the fine arrays before every part
+      int nranks = 0;
+      qgcm_hip_xforc_band plan;
+    } bands;
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
@@ -2895,7 +2902,7 @@ extern "C" int qgcm_hip_aml_get_diag(qgcm_hip_handle c, double *entat, double *d
 // xforc is off until qgcm_hip_xforc_init has gone through (it replaces the buffers)
 static void xf_off(qgcm_hip_ctx *a) {
   auto &x = a->xf;
-  x.on = x.coupled = x.slab = false;
+  x.on = x.coupled = x.slab = x.bands.on = false;
   x.oc = nullptr;
   x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
   x.sst.on = false;  // (likewise qgcm_hip_xforc_sst_init)
@@ -3312,7 +3319,12 @@ extern "C" int qgcm_hip_xforc_heat_get(qgcm_hip_handle oc, qgcm_hip_handle atm, 
 // ---------------------------------------------------------------------------
 hipError_t qg_launch_xf_slab_ocean(hipStream_t st, const QgXfSlabParams &P);
 hipError_t qg_launch_xf_heat_oc_slab(hipStream_t st, const QgXfHeatSlabParams &S);
-hipError_t qg_launch_xf_heat_combine(hipStream_t st, const double *gath, int nranks, int ncell, double *cell, double *part);
+hipError_t qg_launch_xf_heat_combine(hipStream_t st, const double *gath, int nranks, int ncell, long stride, long off, double *cell,
+                                     double *part);
+hipError_t qg_launch_xf_win_fine(hipStream_t st, const QgXfParams &P, int c0, int c1);
+hipError_t qg_launch_xf_win_band(hipStream_t st, const QgXfParams &P, int a0, int a1, int t0, int t1, int lines);
+hipError_t qg_launch_xf_band_pack(hipStream_t st, const QgXfBandMsg &B);
+hipError_t qg_launch_xf_band_scatter(hipStream_t st, const QgXfBandMsg &B);
 
 extern "C" int qgcm_hip_xforc_slab_init(qgcm_hip_handle oc, qgcm_hip_handle atm, const qgcm_hip_xforc_params *p) {
   return xf_init(oc, atm, p, "qgcm_hip_xforc_slab_init", true);
@@ -3322,9 +3334,119 @@ extern "C" int qgcm_hip_xforc_heat_slab_init(qgcm_hip_handle oc, qgcm_hip_handle
   return xf_heat_init(oc, atm, p, "qgcm_hip_xforc_heat_slab_init", true);
 }
 
+// ---- the band plan, host code without a device -----------------------------------------------------------------
+// One rank's windows from its band a0 .. a1 of atmosphere p rows and the global ocean p rows g0 .. g1 its slab owns (it
+// holds three halo rows more towards each neighbour: qgcm_hip_create); nyg: the basin's p rows.  The fine p rows the band's outputs, the line sums the rank owns and the
+// slab's k_xf_tauo read are two intervals (read off k_xforc_rows.inc); each becomes the cell rows that hold it.
+static void xf_band_windows(int nyta, int ndxr, int ny1, int nyg, int a0, int a1, int g0, int g1, qgcm_hip_xforc_band *b) {
+  const int n = ndxr, nypa = nyta + 1, nytaor = nyta * n, nypaor = nytaor + 1, odd = n % 2, nijwid = n + odd;
+  const int slo = g0 - 3 > 1 ? g0 - 3 : 1, shi = g1 + 3 < nyg ? g1 + 3 : nyg; // the rows the slab holds
+  memset(b, 0, sizeof(*b));
+  b->a0 = a0; b->a1 = a1;
+  // a line sum belongs to the rank that owns its outer row: one owner each
+  b->own = (a0 == 1 ? 1 : 0) | (a1 == nypa ? 2 : 0) | (g0 == 1 ? 4 : 0) | (g1 == nyg ? 8 : 0);
+  // tauxa, tauya, vekat at ja: fine row 1 + (ja-1) n, on a0 .. min(a1+1, nypa); uekat at ja <= nyta: that row and the n above
+  int lo = 1 + (a0 - 1) * n, hi = 1 + (a1 < nyta ? a1 : nyta) * n;
+  // wekpa at ja: fine T rows jbeg .. jbeg + nijwid - 1 clipped to 1 .. nytaor; T row j reads p rows j, j + 1
+  const int jb0 = (a0 - 1) * n - (n - 1) / 2, jb1 = (a1 - 1) * n - (n - 1) / 2;
+  b->t0 = jb0 > 1 ? jb0 : 1;
+  b->t1 = jb1 + nijwid - 1 < nytaor ? jb1 + nijwid - 1 : nytaor;
+  if (b->t0 < lo) lo = b->t0;
+  if (b->t1 + 1 > hi) hi = b->t1 + 1;
+  // the atmosphere's line sums: rows jsou (odd n: and jsou + 1), jnor (and jnor - 1)
+  const int jsou = 1 + n / 2, jnor = nypaor - n / 2;
+  if (b->own & 1) { if (jsou < lo) lo = jsou; if (jsou + odd > hi) hi = jsou + odd; }
+  if (b->own & 2) { if (jnor - odd < lo) lo = jnor - odd; if (jnor > hi) hi = jnor; }
+  auto cell = [&](int f) { const int c = (f - 1) / n + 1; return c < nyta ? c : nyta; }; // (fine row nypaor: cell row nyta)
+  const int ca0 = cell(lo), ca1 = cell(hi);
+  // the slab: k_xf_tauo at local row j reads the fine row jocoff + joff + j; the cyclic ocean's line sums read the fine
+  // rows of ocean rows 1, 2 (the slab that owns row 1) and nyg - 1, nyg (the slab that owns row nyg): among them
+  const int jocoff = (ny1 - 1) * n, cb0 = cell(jocoff + slo), cb1 = cell(jocoff + shi);
+  if (cb0 <= ca1 + 1 && ca0 <= cb1 + 1) { // they touch: one interval
+    b->nseg = 1;
+    b->c0[0] = ca0 < cb0 ? ca0 : cb0;
+    b->c1[0] = ca1 > cb1 ? ca1 : cb1;
+  } else {
+    b->nseg = 2;
+    const bool af = ca0 < cb0;
+    b->c0[0] = af ? ca0 : cb0; b->c1[0] = af ? ca1 : cb1;
+    b->c0[1] = af ? cb0 : ca0; b->c1[1] = af ? cb1 : ca1;
+  }
+  for (int s = 0; s < b->nseg; ++s) { // the fine p rows k_xf_fine writes on these cell rows
+    b->f0[s] = 1 + (b->c0[s] - 1) * n;
+    b->f1[s] = b->c1[s] == nyta ? nypaor : b->c1[s] * n;
+  }
+}
+
+// the bands: atmosphere p rows 1 .. nypa split evenly, the first nypa % nranks bands one row longer
+static void xf_band_of(int nypa, int rank, int nranks, int *a0, int *a1) {
+  const int base = nypa / nranks, rem = nypa % nranks;
+  *a0 = 1 + rank * base + (rank < rem ? rank : rem);
+  *a1 = *a0 + base + (rank < rem ? 1 : 0) - 1;
+}
+
+extern "C" int qgcm_hip_xforc_bands(int nxpa, int nyta, int ndxr, int ny1, int nyaooc, int nranks, const int *slab_lo,
+                                    const int *slab_hi, qgcm_hip_xforc_band *out) {
+  const char *who = "qgcm_hip_xforc_bands";
+  if (!slab_lo || !slab_hi || !out) QG_FAIL("%s: null argument", who);
+  if (nxpa < 2 || nyta < 2 || ndxr < 1 || ny1 < 1 || nyaooc < 1 || ny1 + nyaooc - 1 > nyta)
+    QG_FAIL("%s: bad geometry (nxpa %d, nyta %d, ndxr %d, ny1 %d, nyaooc %d)", who, nxpa, nyta, ndxr, ny1, nyaooc);
+  const int nypa = nyta + 1, nyg = nyaooc * ndxr + 1;
+  if (nranks < 1 || nranks > nypa) QG_FAIL("%s: %d ranks for %d atmosphere rows (every rank needs a band)", who, nranks, nypa);
+  for (int r = 0; r < nranks; ++r)
+    if (slab_lo[r] < 1 || slab_hi[r] > nyg || slab_hi[r] < slab_lo[r])
+      QG_FAIL("%s: rank %d owns ocean rows %d..%d outside 1..%d", who, r, slab_lo[r], slab_hi[r], nyg);
+  const int nrow = (nypa + nranks - 1) / nranks; // the longest band
+  for (int r = 0; r < nranks; ++r) {
+    int a0, a1;
+    xf_band_of(nypa, r, nranks, &a0, &a1);
+    xf_band_windows(nyta, ndxr, ny1, nyg, a0, a1, slab_lo[r], slab_hi[r], &out[r]);
+    out[r].nrow = nrow;
+    out[r].mom_len = (int)xfb_mom_len(nrow, nxpa);
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_slab_bands(qgcm_hip_handle oc, qgcm_hip_handle atm, int a0, int a1, int nrow, int nranks) {
+  const char *who = "qgcm_hip_xforc_slab_bands";
+  if (xf_ready(oc, atm, who, true)) return 1;
+  auto &x = atm->xf;
+  const int nypa = atm->g.ny;
+  if (a0 < 1 || a1 > nypa || a1 < a0) QG_FAIL("%s: the band %d..%d lies outside the atmosphere's rows 1..%d", who, a0, a1, nypa);
+  if (nranks < 1 || nranks > nypa) QG_FAIL("%s: %d ranks for %d atmosphere rows", who, nranks, nypa);
+  if (nrow < a1 - a0 + 1 || nrow > nypa) QG_FAIL("%s: the common row count %d does not hold the band %d..%d (or exceeds %d)", who, nrow, a0, a1, nypa);
+  if ((long)XFB_NF * nranks > 65535) QG_FAIL("%s: %d ranks exceed the scatter's launch limit", who, nranks);
+  const QgGeom &go = oc->g;
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  xf_band_windows(nypa - 1, x.prm.ndxr, x.prm.ny1, go.nyg, a0, a1, go.joff + go.jlo, go.joff + go.jhi, &x.bands.plan);
+  x.bands.plan.nrow = nrow;
+  x.bands.plan.mom_len = (int)xfb_mom_len(nrow, atm->g.nx);
+  x.bands.nranks = nranks;
+  const char *e = getenv("QGCM_HIP_XF_POISON");
+  x.bands.poison = e && atoi(e) == 1;
+  x.bands.on = true;
+  return 0;
+}
+
 extern "C" int qgcm_hip_xforc_slab_msg_len(qgcm_hip_handle atm) {
-  if (!atm || !atm->xf.on || !atm->xf.slab || !atm->xf.heat.on) return 0; // (the momentum half alone exchanges nothing)
-  return 4 * atm->xf.prm.nxaooc * atm->xf.prm.nyaooc;
+  if (!atm || !atm->xf.on || !atm->xf.slab) return 0;
+  const int heat = atm->xf.heat.on ? 4 * atm->xf.prm.nxaooc * atm->xf.prm.nyaooc : 0;
+  if (atm->xf.bands.on) return atm->xf.bands.plan.mom_len + heat; // the momentum block, then the heat block
+  return heat; // (replicated: the momentum half alone exchanges nothing)
+}
+
+// the pack's / the scatter's view of the replica
+static void xf_band_msg_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfBandMsg &B) {
+  const auto &m = atm->atmon;
+  const QgGeom &g = atm->g;
+  const auto &b = atm->xf.bands.plan;
+  memset(&B, 0, sizeof(B));
+  B.nxpa = g.nx; B.nxta = g.nxt; B.nypa = g.ny; B.nyta = g.ny - 1; B.lda = g.ldx; B.ldta = m.ldt;
+  B.a0 = b.a0; B.a1 = b.a1; B.nrow = b.nrow;
+  B.own = oc->g.cyc ? b.own : (b.own & 3); // (a box ocean has no line sums)
+  B.fld[0] = m.tauxa; B.fld[1] = m.tauya; B.fld[2] = m.uekat; B.fld[3] = m.vekat; B.fld[4] = m.wekta; B.fld[5] = atm->wekpo;
+  B.sca = atm->sc;
+  B.sco = oc->g.cyc ? oc->sc : nullptr;
 }
 
 // the ocean's next step reads wekpo, the stress, the line integrals and the mixed layer's forcing
@@ -3339,6 +3461,8 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   if (xf_ready(oc, atm, who, true)) return 1;
   auto &x = atm->xf;
   if (x.heat.on && !send_dev) QG_FAIL("%s: the heat half is set up: send_dev must hold qgcm_hip_xforc_slab_msg_len doubles", who);
+  const bool banded = x.bands.on;
+  if (banded && !send_dev) QG_FAIL("%s: the bands are set up: send_dev must hold qgcm_hip_xforc_slab_msg_len doubles", who);
   hipStream_t st = atm->stream;
   QgXfParams P;
   xf_fill(oc, atm, P);
@@ -3350,7 +3474,18 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   HIPCHECK(hipEventRecord(x.ev_oc, oc->stream));
   HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
   const dim3 b(XF_NT);
-  launch_xf_atmos(P, st);
+  if (banded) { // the atmosphere side on this rank's windows only
+    const auto &bp = x.bands.plan;
+    if (x.bands.poison) { // a read outside the computed windows shows in the results
+      const size_t nf = (size_t)x.ldf * P.nypaor * sizeof(double);
+      HIPCHECK(hipMemsetAsync(x.txf, 0xFF, nf, st));
+      HIPCHECK(hipMemsetAsync(x.tyf, 0xFF, nf, st));
+      HIPCHECK(hipMemsetAsync(x.wf, 0xFF, (size_t)x.ldtf * P.nytaor * sizeof(double), st));
+    }
+    for (int s = 0; s < bp.nseg; ++s) HIPCHECK(qg_launch_xf_win_fine(st, P, bp.c0[s], bp.c1[s]));
+    HIPCHECK(qg_launch_xf_win_band(st, P, bp.a0, bp.a1, bp.t0, bp.t1, bp.own & 3));
+  } else
+    launch_xf_atmos(P, st);
   hipLaunchKernelGGL(k_xf_tauo, dim3((P.nxpo + XF_NT - 1) / XF_NT, P.nypo), b, 0, st, P);
   QgWekParams W;
   memset(&W, 0, sizeof(W));
@@ -3364,6 +3499,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   S.cyc = go.cyc; S.iocoff = P.iocoff; S.jocoff = P.jocoff - go.joff;
   S.txf = x.txf; S.wekto = mo.wekto; S.wekpo = oc->wekpo; S.sco = oc->sc;
   S.raoro = P.raoro; S.dxo = P.dxo;
+  S.lines = banded ? (x.bands.plan.own >> 2) & 3 : 3; // banded: only the sums whose ocean rows this slab holds
   HIPCHECK(qg_launch_xf_slab_ocean(st, S));
   if (oc->oml.on) { // the mixed layer's own forcing buffers (same pitches)
     auto &o = oc->oml;
@@ -3372,7 +3508,13 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
     HIPCHECK(hipMemcpyAsync(o.tauy, mo.tauy, nP, hipMemcpyDeviceToDevice, st));
     HIPCHECK(hipMemcpyAsync(o.wekto, mo.wekto, nT, hipMemcpyDeviceToDevice, st));
   }
-  hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
+  if (banded) { // the message's momentum block (the atmosphere's line sums were k_xf_lines_win's, on the ranks that own them)
+    QgXfBandMsg B;
+    xf_band_msg_fill(oc, atm, B);
+    B.msg = send_dev;
+    HIPCHECK(qg_launch_xf_band_pack(st, B));
+  } else
+    hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
   HIPCHECK(hipGetLastError());
   if (x.heat.on) { // fnetoc on the slab's T rows and this rank's partial cell sums (src/xfosubs.F:774-817)
     QgXfHeatSlabParams H;
@@ -3380,7 +3522,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
     xf_heat_fill(oc, atm, H.h);
     H.joff = go.joff; H.nytl = go.ny - 1;
     H.jT0 = go.jlo; H.jT1 = (go.jhi + go.joff == go.nyg) ? go.jhi - 1 : go.jhi; // T row j lies between p rows j and j+1
-    H.msg = send_dev;
+    H.msg = send_dev + (banded ? x.bands.plan.mom_len : 0);
     HIPCHECK(qg_launch_xf_heat_oc_slab(st, H));
   }
   return xf_slab_handover(oc, atm);
@@ -3389,12 +3531,26 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
 extern "C" int qgcm_hip_xforc_slab_combine(qgcm_hip_handle oc, qgcm_hip_handle atm, const double *gath_dev, int nranks) {
   const char *who = "qgcm_hip_xforc_slab_combine";
   if (xf_ready(oc, atm, who, true)) return 1;
-  if (!atm->xf.heat.on) QG_FAIL("%s: qgcm_hip_xforc_heat_slab_init has not been called (the momentum half has nothing to combine)", who);
+  auto &x = atm->xf;
+  const bool banded = x.bands.on;
+  if (!x.heat.on && !banded) QG_FAIL("%s: qgcm_hip_xforc_heat_slab_init has not been called (the momentum half has nothing to combine)", who);
   if (!gath_dev || nranks < 1) QG_FAIL("%s: null buffer or nranks = %d", who, nranks);
+  if (banded && nranks != x.bands.nranks)
+    QG_FAIL("%s: nranks = %d, the bands were set up for %d ranks (qgcm_hip_xforc_slab_bands)", who, nranks, x.bands.nranks);
+  hipStream_t st = atm->stream;
+  const long mom = banded ? x.bands.plan.mom_len : 0;
+  if (banded) { // every rank's rows and line sums into this replica (a copy: no sum changes its order)
+    QgXfBandMsg B;
+    xf_band_msg_fill(oc, atm, B);
+    B.gath = gath_dev;
+    B.nranks = nranks;
+    B.stride = qgcm_hip_xforc_slab_msg_len(atm);
+    HIPCHECK(qg_launch_xf_band_scatter(st, B));
+    if (!x.heat.on) return xf_slab_handover(oc, atm);
+  }
   QgXfHeatParams P;
   xf_heat_fill(oc, atm, P);
-  hipStream_t st = atm->stream;
-  HIPCHECK(qg_launch_xf_heat_combine(st, gath_dev, nranks, P.ncell, P.cell, P.part));
+  HIPCHECK(qg_launch_xf_heat_combine(st, gath_dev, nranks, P.ncell, mom + 4L * P.ncell, mom, P.cell, P.part));
   hipLaunchKernelGGL(k_xf_heat_atm, dim3((P.nxta + 63) / 64, (P.nyta + 3) / 4), dim3(OML_NT), 0, st, P);
   hipLaunchKernelGGL(k_xf_heat_final, dim3(1), dim3(OML_NT), 0, st, P);
   HIPCHECK(hipGetLastError());

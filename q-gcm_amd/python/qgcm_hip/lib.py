@@ -95,6 +95,13 @@ class XforcHeatParams(C.Structure):
         (n, C.POINTER(C.c_double)) for n in ("fsa", "fso", "xta", "yta", "xto", "yto")]
 
 
+class XforcBand(C.Structure):
+    """struct qgcm_hip_xforc_band (include/qgcm_hip.h): one rank's part of the band plan."""
+    _fields_ = [("a0", C.c_int), ("a1", C.c_int), ("own", C.c_int), ("nseg", C.c_int),
+                ("c0", C.c_int * 2), ("c1", C.c_int * 2), ("f0", C.c_int * 2), ("f1", C.c_int * 2),
+                ("t0", C.c_int), ("t1", C.c_int), ("nrow", C.c_int), ("mom_len", C.c_int)]
+
+
 class XforcSstParams(C.Structure):
     """struct qgcm_hip_xforc_sst_params (include/qgcm_hip.h)."""
     _fields_ = [(n, C.c_double) for n in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup",
@@ -148,7 +155,7 @@ SYMBOLS = [
     "qgcm_hip_xforc_heat_init", "qgcm_hip_xforc_heat_get",
     "qgcm_hip_xforc_sst_init", "qgcm_hip_xforc_sst_set", "qgcm_hip_xforc_sst_get",
     "qgcm_hip_xforc_slab_init", "qgcm_hip_xforc_heat_slab_init", "qgcm_hip_xforc_slab_msg_len", "qgcm_hip_xforc_slab_part",
-    "qgcm_hip_xforc_slab_combine", "qgcm_hip_xforc_slab_get",
+    "qgcm_hip_xforc_slab_combine", "qgcm_hip_xforc_slab_get", "qgcm_hip_xforc_bands", "qgcm_hip_xforc_slab_bands",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
     "qgcm_hip_debug_live_allocs",
 ]
@@ -323,6 +330,9 @@ def load_library():
         L.qgcm_hip_xforc_slab_part.argtypes = [vp, vp, vp]
         L.qgcm_hip_xforc_slab_combine.argtypes = [vp, vp, vp, C.c_int]
         L.qgcm_hip_xforc_slab_get.argtypes = [vp, vp] + [dp] * 14
+    if hasattr(L, "qgcm_hip_xforc_bands"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_xforc_bands.argtypes = [C.c_int] * 6 + [ip, ip, C.POINTER(XforcBand)]
+        L.qgcm_hip_xforc_slab_bands.argtypes = [vp, vp] + [C.c_int] * 4
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),
@@ -385,6 +395,28 @@ def row_split(nxto, forced=0):
     p, l = C.c_int(0), C.c_int(0)
     check(load_library().qgcm_hip_row_split(nxto, forced, C.byref(p), C.byref(l)))
     return p.value, l.value
+
+
+XFORC_BAND_LINES = ("txisat", "txinat", "txisoc", "txinoc")  # the bits of `own`
+XFORC_BAND_HEADER = 8   # XFB_HDR (k_xforc_slab.h): a0, a1, own, 0 and the four line sums in front of the fields
+XFORC_BAND_FIELDS = ("tauxa", "tauya", "uekat", "vekat", "wekta", "wekpa")  # the message's fields, (nrow, nxpa) each
+
+
+def xforc_bands(nxpa, nyta, ndxr, ny1, nyaooc, slab_rows):
+    """The band plan of the banded slab xforc (qgcm_hip_xforc_bands; host code, no device) for
+    len(slab_rows) ranks; slab_rows[r] = (g0, g1): the global ocean p rows rank r's slab owns.  One
+    dict per rank: band (a0, a1) - atmosphere p rows; cells [(c0, c1)] - the one or two intervals of cell rows the fine
+    stress is computed on; fine [(f0, f1)] - the fine p rows they cover; trows (t0, t1) - the fine T rows of wektaor;
+    own - the names of the line sums the rank forms; nrow - rows per field in the message (the longest band);
+    mom_len - doubles of the message's momentum block."""
+    n = len(slab_rows)
+    lo, hi = (C.c_int * n)(*[int(a) for a, _ in slab_rows]), (C.c_int * n)(*[int(b) for _, b in slab_rows])
+    out = (XforcBand * n)()
+    check(load_library().qgcm_hip_xforc_bands(int(nxpa), int(nyta), int(ndxr), int(ny1), int(nyaooc), n, lo, hi, out))
+    return [dict(band=(b.a0, b.a1), cells=[(b.c0[s], b.c1[s]) for s in range(b.nseg)],
+                 fine=[(b.f0[s], b.f1[s]) for s in range(b.nseg)], trows=(b.t0, b.t1),
+                 own=tuple(nm for k, nm in enumerate(XFORC_BAND_LINES) if b.own >> k & 1), nrow=b.nrow, mom_len=b.mom_len)
+            for b in out]
 
 
 def row_plan(handle):

@@ -322,16 +322,23 @@ class HipSlab(Handle):
         """p: lib.XforcHeatParams; arrays: what it points to (fsa, fso, xta, yta, xto, yto), unused here."""
         check(self.L.qgcm_hip_xforc_heat_slab_init(self.h, atm.h, C.byref(p)))
 
+    def xforc_bands_init(self, atm, band, nrow):
+        """Switch this pair to the banded atmosphere side (qgcm_hip_xforc_slab_bands): band = (a0, a1) and
+        nrow from lib.xforc_bands."""
+        check(self.L.qgcm_hip_xforc_slab_bands(self.h, atm.h, int(band[0]), int(band[1]), int(nrow), int(self.nranks)))
+
     def xforc_msg_len(self, atm):
         return self.L.qgcm_hip_xforc_slab_msg_len(atm.h)
 
     def xforc_part(self, atm, send):
         """The momentum half, fnetoc and this rank's partial cell sums -> send (device buffer of xforc_msg_len doubles,
-        None without the heat half); asynchronous, on the atmosphere's stream."""
+        None without the heat half); asynchronous, on the atmosphere's stream.  Banded (xforc_bands_init): the atmosphere
+        side on this rank's windows only, and its band of the coarse fields in front of the cell sums in `send`."""
         check(self.L.qgcm_hip_xforc_slab_part(self.h, atm.h, self._ptr(send)))
 
     def xforc_combine(self, atm, gath):
-        """All ranks' partial cell sums (rank-major) -> fnetat and the monitors on this rank's replica."""
+        """All ranks' partial cell sums (rank-major) -> fnetat and the monitors on this rank's replica.  Banded: first every
+        rank's band of the coarse fields and the line sums into the replica; required without the heat half too."""
         check(self.L.qgcm_hip_xforc_slab_combine(self.h, atm.h, self._ptr(gath), int(self.nranks)))
 
     def xforc_fetch(self, atm, heat):
@@ -810,11 +817,14 @@ class SlabOcean:
 
     # coupled runs: xforc under a replicated atmosphere, collective ---------------------------------------
     def xforc_setup(self, atmospheres, cdat=1.3e-3, rhoat=1.0, rhooc=1.0e3, hmat=1000.0, hmoc=100.0, tau_udiff=False,
-                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None):
+                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None, bands=False):
         """As model.xforc_setup (ndxr, nxaooc, nyaooc default to the ocean configuration's), for the slabs: `atmospheres` holds one whole-domain AtmosModel per local slab, on that
         slab's device - replicas of one atmosphere, which every rank steps redundantly and which stay bitwise identical.
-        tau_udiff is refused (the fine stress above the sea would need every slab's pom on every rank)."""
-        from .lib import XforcParams
+        tau_udiff is refused (the fine stress above the sea would need every slab's pom on every rank).
+        bands = True: every rank runs the atmosphere side only on the fine rows its band of atmosphere rows
+        (lib.xforc_bands, kept as self.xforc_plan) and its slab need; the bands travel in front of the heat block in the
+        one all-gather, so xforc() then always gathers and combines.  The results are bitwise the default's."""
+        from .lib import XforcParams, xforc_bands
         S, oc = self.slabs, self.cfg
         if len(atmospheres) != len(S):
             raise ValueError("xforc_setup: %d atmospheres for %d local slabs" % (len(atmospheres), len(S)))
@@ -840,6 +850,21 @@ class SlabOcean:
             a.xforc_origin = (int(p.nx1), int(p.ny1))  # (where xforc_heat_setup finds the ocean)
         self.atmos = list(atmospheres)
         self._xf_bufs = None
+        self.xforc_plan = None
+        if bands:
+            rows = partition(oc.nypo, self.P)
+            for x in S:  # (slabs cut otherwise than partition(): their own rows)
+                rows[x.rank] = (x.g0, x.g1)
+            self.xforc_plan = xforc_bands(acfg.nxpa, acfg.nyta, ndxr, p.ny1, p.nyaooc, rows)
+            for x, a in zip(S, atmospheres):
+                b = self.xforc_plan[x.rank]
+                x.xforc_bands_init(a, b["band"], b["nrow"])
+            self._xf_size_bufs()
+
+    def _xf_size_bufs(self):
+        n = [x.xforc_msg_len(a) for x, a in zip(self.slabs, self.atmos)]
+        self._xf_bufs = ([x.new_buffer(m) for x, m in zip(self.slabs, n)], [x.new_buffer(m * self.P) for x, m in zip(self.slabs, n)])
+        self._settle()
 
     def xforc_heat_setup(self, heat, hmadmp=None, hmat=None, fsa=None, fso=None, coords=None):
         """As model.xforc_heat_setup, after xforc_setup, oml_init on every slab and aml_init on every replica; the tables
@@ -851,13 +876,12 @@ class SlabOcean:
             keep = _heat_params("SlabOcean.xforc_heat_setup", p, a, self.cfg, heat, hmadmp, hmat, coords, fsa=fsa, fso=fso)
             x.xforc_heat_init(a, p, keep)
             del keep  # (copied by now)
-        n = [x.xforc_msg_len(a) for x, a in zip(self.slabs, self.atmos)]
-        self._xf_bufs = ([x.new_buffer(m) for x, m in zip(self.slabs, n)], [x.new_buffer(m * self.P) for x, m in zip(self.slabs, n)])
-        self._settle()
+        self._xf_size_bufs()
 
     def xforc(self):
         """One `call xforc`: every local rank runs the momentum half on its replica and its slab's rows; with the heat
-        half, one all-gather of the partial cell sums (4*nxaooc*nyaooc doubles per rank) and the rank-ordered combine."""
+        half, one all-gather of the partial cell sums (4*nxaooc*nyaooc doubles per rank) and the rank-ordered combine.
+        Banded (xforc_setup(bands=True)): always one all-gather - the ranks' bands, then the heat block - and the combine."""
         S, A = self.slabs, self.atmos
         self._join()
         send, gath = self._xf_bufs if self._xf_bufs else ([None] * len(S), None)
