@@ -990,6 +990,39 @@ int qgcm_hip_xforc_bands(int nxpa, int nyta, int ndxr, int ny1, int nyaooc, int 
                          const int *slab_hi, qgcm_hip_xforc_band *out);
 int qgcm_hip_xforc_slab_bands(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, int a0, int a1, int nrow, int nranks);
 
+/* ---- tau_udiff on a y-slab ocean: the surface pressure gathered ahead of xforc ----------------------
+ * The ocean enters the momentum half at one place: the fine stress above the sea subtracts the ocean's geostrophic
+ * surface velocity, formed from pom(:,:,1).  Before the atmosphere side runs, every rank assembles the basin's
+ * pom(:,:,1) from the ranks' OWNED rows: pack, one all-gather by the caller (rank-major), assemble.  The stress kernels
+ * then run unchanged on the assembled array, replicated or banded, and no sum changes its order: every momentum
+ * output is bitwise the whole-domain qgcm_hip_xforc set up with tau_udiff = 1, on any rank count.  The heat half keeps
+ * its statement above.  All four calls come after qgcm_hip_xforc_slab_init with tau_udiff = 0 in its struct (which,
+ * like tau_udiff = 1 there, keeps its meaning: the shear-free path, and the refusal).
+ * qgcm_hip_xforc_slab_udiff(oc_slab, atm, nrow, nranks): switches the shear term on for this pair.  nrow: the longest
+ *   owned p-row range of any rank; nranks: the rank count.  Allocates the assembled array (nxpo x nypo of the basin,
+ *   its own pitch) in the atmosphere handle.  The drag constants of the sea and the ocean's velocity factors are those
+ *   of the whole-domain set-up with tau_udiff.  Refuses, naming the reason and changing nothing: a pair not set up by
+ *   qgcm_hip_xforc_slab_init, nrow smaller than this slab's owned rows (or larger than the basin), nranks < 1.
+ *   qgcm_hip_xforc_slab_init again returns the pair to the shear-free path.  Composes with qgcm_hip_xforc_slab_bands
+ *   in either order.  Reads QGCM_HIP_XF_POISON (INTEGRATION): 1 = every assemble first fills the assembled array with
+ *   NaN bytes, so a row no rank owns, or one the copy misses, shows.
+ * qgcm_hip_xforc_slab_pom_len(oc_slab, atm, &n): n = 8 + nrow * nxpo doubles per rank's message.
+ * qgcm_hip_xforc_slab_pom_pack(oc_slab, atm, send_dev): asynchronous, on the atmosphere's stream after everything
+ *   queued on the slab's stream: a header of 8 doubles - g0, g1 (the global p rows the slab owns), nxpo, zeros - then
+ *   rows g0 .. g1 of layer 1 of the lagged pressure (what the whole-domain call would read) as (nrow, nxpo) row-major,
+ *   +0.0 past the slab's rows.  Halo rows are never packed.
+ * qgcm_hip_xforc_slab_pom_assemble(oc_slab, atm, gath_dev, nranks): every rank's rows copied into the assembled
+ *   array, one writer per point, no atomics; a header that does not describe rows inside 1 .. nypo writes nothing;
+ *   refuses an nranks other than the set-up's.
+ * With the shear term on, qgcm_hip_xforc_slab_part refuses unless an assemble has run since the last part ("the
+ *   surface pressure has not been assembled for this call"); a part that goes through clears the flag.
+ * Every rank receives nranks * (8 + nrow * nxpo) doubles per xforc: this is the exact form, not the scalable one
+ * (DESIGN 6q).  Ranks on different GPUs are untested. */
+int qgcm_hip_xforc_slab_udiff(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, int nrow, int nranks);
+int qgcm_hip_xforc_slab_pom_len(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, long *n);
+int qgcm_hip_xforc_slab_pom_pack(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, double *send_dev);
+int qgcm_hip_xforc_slab_pom_assemble(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, const double *gath_dev, int nranks);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

@@ -9,6 +9,10 @@ scale.  Host clock around work that ends in a synchronise; medians.
   python3 profiles/tools/slab_coupled.py bands   the banded atmosphere side (profiles/slab_bands.log): on 1, 2
                                            and 4 virtual ranks two set-ups side by side, replicated and banded, timed in
                                            alternating blocks in one session: xforc_slab_part and the combine per rank
+  python3 profiles/tools/slab_coupled.py udiff   the shear term on slabs (profiles/slab_udiff.log): on 1, 2 and
+                                           4 virtual ranks two set-ups side by side, shear-free and udiff_gather, timed
+                                           in alternating blocks in one session: pom_pack, pom_assemble, xforc_slab_part
+                                           and the combine per rank
 With QGCM_HIP_LIB pointing at a build of the parent commit the same script gives the parent's whole-domain figures."""
 import os
 import sys
@@ -127,7 +131,7 @@ def time_xforc(so, slabs, reps, n):
     return tp, tc, tx
 
 
-def slab_setup(I, consts, nranks, bands=False):
+def slab_setup(I, consts, nranks, bands=False, udiff=False):
     from qgcm_hip import config, oml_preset
     from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, partition
     oc = I["oc"]
@@ -142,7 +146,7 @@ def slab_setup(I, consts, nranks, bands=False):
     for x in slabs:
         x.oml_set_state(sst=I["sst"], sstm=I["sst"])
     reps = [atmosphere(I) for _ in slabs]
-    so.xforc_setup(reps, tau_udiff=False, **(dict(bands=True) if bands else {}))
+    so.xforc_setup(reps, tau_udiff=False, **dict(dict(bands=True) if bands else {}, **(dict(udiff_gather=True) if udiff else {})))
     so.xforc_heat_setup(config.HeatConfig(**HT))
     return so, slabs, reps
 
@@ -197,16 +201,116 @@ def banded(I, consts, nranks, rounds=4):
             m.close()
 
 
+def time_pom(so, slabs, reps, n):
+    """n synchronised gathers of the surface pressure in their parts: us of (every rank's pack, every rank's assemble).
+    Every assemble is followed by nothing: the next part of time_xforc's loop finds the flag set."""
+    send, gath = so._xf_pom_bufs
+    tk, ta = [], []
+    for k in range(n):
+        t0 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_pom_pack(a, send[i])
+        for a in reps:
+            a.sync()
+        t1 = time.perf_counter()
+        so.comm.all_gather(gath, send)
+        t2 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_pom_assemble(a, gath[i])
+        for a in reps:
+            a.sync()
+        t3 = time.perf_counter()
+        tk.append(1e6 * (t1 - t0))
+        ta.append(1e6 * (t3 - t2))
+    return tk, ta
+
+
+def time_xforc_udiff(so, slabs, reps, n):
+    """time_xforc for a set-up with the shear term: an (untimed) gather of the pressure ahead of every timed part."""
+    send, gath = so._xf_bufs
+    psend, pgath = so._xf_pom_bufs
+    tp, tc, tx = [], [], []
+    for k in range(n):
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_pom_pack(a, psend[i])
+        for a in reps:
+            a.sync()
+        so.comm.all_gather(pgath, psend)
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_pom_assemble(a, pgath[i])
+        for a in reps:
+            a.sync()
+        t0 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_part(a, send[i])
+        for a in reps:
+            a.sync()
+        t1 = time.perf_counter()
+        so.comm.all_gather(gath, send)
+        t2 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_combine(a, gath[i])
+        for a in reps:
+            a.sync()
+        t3 = time.perf_counter()
+        tp.append(1e6 * (t1 - t0))
+        tc.append(1e6 * (t3 - t2))
+        t0 = time.perf_counter()
+        so.xforc()
+        for a in reps:
+            a.sync()
+        tx.append(1e6 * (time.perf_counter() - t0))
+    return tp, tc, tx
+
+
+def sheared(I, consts, nranks, rounds=4):
+    """Shear-free and udiff_gather set-ups of `nranks` virtual ranks side by side (replicated atmosphere side, the heat
+    half on), timed in alternating blocks of 25 calls (the first 5 of a block dropped): per mode the median of each
+    block, then the median and the spread (max - min) of the block medians.  With the shear term the outputs are the
+    whole-domain call's with tau_udiff (tests/test_gpu_slab_udiff.py); checked here: finite, and tauxo moved."""
+    sets = [slab_setup(I, consts, nranks, udiff=u) for u in (False, True)]
+    blocks = {False: [], True: []}
+    pom = []
+    for rnd in range(rounds):
+        for u, (so, slabs, reps) in zip((False, True), sets):
+            if u:
+                tk, ta = time_pom(so, slabs, reps, 25)
+                pom.append((med(tk[5:]) / nranks, med(ta[5:]) / nranks))
+                tp, tc, tx = time_xforc_udiff(so, slabs, reps, 25)
+            else:
+                tp, tc, tx = time_xforc(so, slabs, reps, 25)
+            blocks[u].append((med(tp[5:]) / nranks, med(tc[5:]) / nranks, med(tx[5:])))
+    out = [so.xforc_get() for so, _, _ in sets]
+    finite = all(np.isfinite(m[f]).all() for m in out[1] for f in ("wekpa", "tauxo", "wekto"))
+    moved = float(np.mean([np.mean(x["tauxo"] != y["tauxo"]) for x, y in zip(*out)]))
+    print("%d virtual rank(s): pressure message %d doubles per rank (%d gathered per rank); heat message %d; outputs finite: %s; "
+          "tauxo differs from the shear-free run at %.3f of the slabs' points" % (
+              nranks, sets[1][0]._xf_pom_bufs[0][0].numel(), sets[1][0]._xf_pom_bufs[1][0].numel(),
+              sets[1][0]._xf_bufs[0][0].numel(), finite, moved), flush=True)
+    for k, what in enumerate(("pom_pack per rank", "pom_assemble per rank")):
+        v = [blk[k] for blk in pom]
+        print("%d virtual rank(s), shear term on : %s, us: median of the block medians %.1f, spread %.1f (%s)"
+              % (nranks, what, med(v), max(v) - min(v), " ".join("%.1f" % t for t in v)), flush=True)
+    for u, name in ((False, "shear term off"), (True, "shear term on ")):
+        for k, what in enumerate(("xforc_slab_part per rank", "combine per rank", "SlabOcean.xforc() with its host-staged all-gather(s)")):
+            v = [blk[k] for blk in blocks[u]]
+            print("%d virtual rank(s), %s: %s, us: median of the block medians %.1f, spread %.1f (%s)"
+                  % (nranks, name, what, med(v), max(v) - min(v), " ".join("%.1f" % t for t in v)), flush=True)
+    for so, slabs, reps in sets:
+        for m in slabs + reps:
+            m.close()
+
+
 if __name__ == "__main__":
     print("device: %s; library: %s" % (torch.cuda.get_device_name(0), "the build QGCM_HIP_LIB names" if os.environ.get("QGCM_HIP_LIB") else "in-tree"), flush=True)
     I = inputs()
-    if sys.argv[1:] == ["bands"]:
+    if sys.argv[1:] in (["bands"], ["udiff"]):
         from qgcm_hip.slab import global_consts
         o = ocean(I)
         consts = global_consts(I["oc"], o.helmholtz)
         o.close()
         for n in (1, 2, 4):
-            banded(I, consts, n)
+            (banded if sys.argv[1] == "bands" else sheared)(I, consts, n)
         sys.exit(0)
     c = whole(I)
     if c is not None:

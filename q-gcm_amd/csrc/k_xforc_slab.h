@@ -20,6 +20,12 @@
 //                         -> the message's momentum block
 //   k_xf_band_scatter     every rank's rows and line sums -> the replica's arrays and scalars: a copy, no sum
 //
+// and, for tau_udiff (the basin's pom(:,:,1) assembled on every rank ahead of the atmosphere side, which then
+// runs k_xf_fine / k_xf_fine_win with P.udiff = 1 on the assembled array, their text unchanged):
+//
+//   k_xf_pom_pack         the slab's OWNED p rows of layer 1 of the lagged pressure -> the message
+//   k_xf_pom_assemble     every rank's rows -> the assembled array (nxpo, nypo): a copy, one writer per point
+//
 // A cell wholly inside one slab keeps the bits of the whole-domain sum (x + 0.0 = x); a cell a seam cuts is a sum of the
 // same terms in another order.  No atomics; every sum has a fixed tree.
 #pragma once
@@ -65,6 +71,22 @@ struct QgXfBandMsg {
   const double *gath;     // scatter
 };
 static inline long xfb_mom_len(int nrow, int nxpa) { return XFB_HDR + (long)XFB_NF * nrow * nxpa; }
+
+// The message of the surface pressure: XFP_HDR doubles - g0, g1 (the global p rows the slab owns), nxpo,
+// zeros - then nrow rows (the longest owned range of any rank) of nxpo columns from row g0 on, +0.0 past row g1.
+#define XFP_HDR 8
+struct QgXfPomMsg {
+  int nxpo, nypo;      // the BASIN's p grid
+  int ldo, lda;        // pitches: the slab's p grid, the assembled array
+  int g0, g1, jlo;     // pack: the owned global rows and the local row of g0
+  int nrow, nranks;    // (nranks: assemble)
+  long stride;         // assemble: rank r's message starts at gath + r * stride
+  const double *pom;   // pack: layer 1 of the slab's lagged pressure (local rows)
+  double *msg;         // pack
+  const double *gath;  // assemble
+  double *all;         // assemble: (lda, nypo)
+};
+static inline long xfp_len(int nrow, int nxpo) { return XFP_HDR + (long)nrow * nxpo; }
 
 struct QgXfHeatSlabParams {
   QgXfHeatParams h;   // nyto and the tables: the GLOBAL ocean's; sstm, fnetoc, ldto: the slab's local T rows
@@ -259,5 +281,35 @@ __global__ __launch_bounds__(XFS_NT) void k_xf_band_scatter(const QgXfBandMsg B)
   const int ja = a0 + jr;
   if (i >= w || ja > a1 || ja > h) return;
   B.fld[f][(long)(ja - 1) * ld + i] = m[XFB_HDR + ((long)f * B.nrow + jr) * B.nxpa + i];
+}
+
+// ---- tau_udiff ---------------------------------------------------------------------------------------------
+// grid: (ceil(nxpo/256), nrow): message row jr = the slab's owned row g0 + jr (local row jlo + jr), or +0.0 past g1.  Halo
+// rows are never read.  Consecutive lanes, consecutive doubles on both sides.
+__global__ __launch_bounds__(XFS_NT) void k_xf_pom_pack(const QgXfPomMsg M) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, jr = blockIdx.y;
+  if (i == 0 && jr == 0) {
+    double *h = M.msg;
+    h[0] = (double)M.g0; h[1] = (double)M.g1; h[2] = (double)M.nxpo;
+#pragma unroll
+    for (int k = 3; k < XFP_HDR; ++k) h[k] = 0.0;
+  }
+  if (i >= M.nxpo) return;
+  double v = 0.0;
+  if (M.g0 + jr <= M.g1) v = M.pom[(long)(M.jlo - 1 + jr) * M.ldo + i];
+  M.msg[XFP_HDR + (long)jr * M.nxpo + i] = v;
+}
+
+// grid: (ceil(nxpo/256), nrow, nranks): rank r's message row jr -> row g0(r) + jr of the assembled array.  The owned
+// ranges tile 1 .. nypo, so every point has one writer; a header that does not describe rows inside the basin (or
+// another row length) writes nothing.
+__global__ __launch_bounds__(XFS_NT) void k_xf_pom_assemble(const QgXfPomMsg M) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, jr = blockIdx.y, r = blockIdx.z;
+  const double *m = M.gath + (long)r * M.stride;
+  const int g0 = (int)m[0], g1 = (int)m[1], nx = (int)m[2];
+  if (g0 < 1 || g1 > M.nypo || g1 < g0 || g1 - g0 + 1 > M.nrow || nx != M.nxpo) return;
+  const int g = g0 + jr;
+  if (i >= M.nxpo || g > g1) return;
+  M.all[(long)(g - 1) * M.lda + i] = m[XFP_HDR + (long)jr * M.nxpo + i];
 }
 #endif // QG_XFORC_SLAB_KERNELS

@@ -1,4 +1,4 @@
-// k_xforc_slab.hip - the kernels of xforc on a y-slab ocean (k_xforc_slab.h, DESIGN 6o, 6p) as a translation unit, and so a
+// k_xforc_slab.hip - the kernels of xforc on a y-slab ocean (k_xforc_slab.h, DESIGN 6o, 6p, 6q) as a translation unit, and so a
 // device code object, of its own, for the reason k_tend_rows.hip gives: qgcm_hip.hip compiles to the device code it
 // compiled to before these kernels existed.
 #define QG_XFORC_SLAB_KERNELS
@@ -60,5 +60,16 @@ hipError_t qg_launch_xf_band_pack(hipStream_t st, const QgXfBandMsg &B) {
 
 hipError_t qg_launch_xf_band_scatter(hipStream_t st, const QgXfBandMsg &B) {
   hipLaunchKernelGGL(k_xf_band_scatter, dim3((B.nxpa + XFS_NT - 1) / XFS_NT, B.nrow, XFB_NF * B.nranks), dim3(XFS_NT), 0, st, B);
+  return hipGetLastError();
+}
+
+// ---- tau_udiff -------------------------------------------------------------------------------------------------
+hipError_t qg_launch_xf_pom_pack(hipStream_t st, const QgXfPomMsg &M) {
+  hipLaunchKernelGGL(k_xf_pom_pack, dim3((M.nxpo + XFS_NT - 1) / XFS_NT, M.nrow), dim3(XFS_NT), 0, st, M);
+  return hipGetLastError();
+}
+
+hipError_t qg_launch_xf_pom_assemble(hipStream_t st, const QgXfPomMsg &M) {
+  hipLaunchKernelGGL(k_xf_pom_assemble, dim3((M.nxpo + XFS_NT - 1) / XFS_NT, M.nrow, M.nranks), dim3(XFS_NT), 0, st, M);
   return hipGetLastError();
 }

@@ -417,6 +417,14 @@ struct qgcm_hip_ctx {
       int nranks = 0;
       qgcm_hip_xforc_band plan;
     } bands;
+    // tau_udiff on a slab set-up (qgcm_hip_xforc_slab_udiff): the basin's pom(:,:,1) assembled from every
+    // rank's owned rows (nxpo, nyg; pitch ld), the common row count of the message and the rank count; fresh: an
+    // assemble has run since the last qgcm_hip_xforc_slab_part
+    struct {
+      bool on = false, fresh = false, poison = false; // poison: QGCM_HIP_XF_POISON=1 - NaN bytes before every assemble
+      int nrow = 0, nranks = 0, ld = 0;
+      QgDbl pom;
+    } udiff;
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
@@ -2902,7 +2910,7 @@ extern "C" int qgcm_hip_aml_get_diag(qgcm_hip_handle c, double *entat, double *d
 // xforc is off until qgcm_hip_xforc_init has gone through (it replaces the buffers)
 static void xf_off(qgcm_hip_ctx *a) {
   auto &x = a->xf;
-  x.on = x.coupled = x.slab = x.bands.on = false;
+  x.on = x.coupled = x.slab = x.bands.on = x.udiff.on = x.udiff.fresh = false;
   x.oc = nullptr;
   x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
   x.sst.on = false;  // (likewise qgcm_hip_xforc_sst_init)
@@ -3435,6 +3443,99 @@ extern "C" int qgcm_hip_xforc_slab_msg_len(qgcm_hip_handle atm) {
   return heat; // (replicated: the momentum half alone exchanges nothing)
 }
 
+// ---- tau_udiff on a slab set-up ----------------------------------------------------------------------------------
+// The ocean enters the momentum half at one place, xf_point (k_xforc_rows.h), which reads pom(:,:,1) around a fine point
+// above the sea.  Every rank assembles the basin's pom(:,:,1) from the ranks' owned rows ahead of the atmosphere side
+// (pack, the caller's all-gather, assemble); the stress kernels then run unchanged with P.udiff = 1 on the assembled
+// array.  No sum changes its order: the results are the whole-domain call's bits on any rank count.  The drag constants
+// of the sea (cdrfab, qu2fab) and zbfcoc, hxofac are xf_fill's, from the constants the set-up kept, as the whole-domain
+// set-up with tau_udiff has them.
+hipError_t qg_launch_xf_pom_pack(hipStream_t st, const QgXfPomMsg &M);
+hipError_t qg_launch_xf_pom_assemble(hipStream_t st, const QgXfPomMsg &M);
+
+extern "C" int qgcm_hip_xforc_slab_udiff(qgcm_hip_handle oc, qgcm_hip_handle atm, int nrow, int nranks) {
+  const char *who = "qgcm_hip_xforc_slab_udiff";
+  if (xf_ready(oc, atm, who, true)) return 1;
+  auto &x = atm->xf;
+  const QgGeom &go = oc->g;
+  const int own = go.jhi - go.jlo + 1;
+  if (nranks < 1 || nranks > 65535) QG_FAIL("%s: nranks = %d outside 1..65535", who, nranks);
+  if (nrow < own || nrow > go.nyg)
+    QG_FAIL("%s: the common row count %d does not hold this slab's %d owned rows (or exceeds the basin's %d)", who, nrow, own, go.nyg);
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  const int ld = round_up(go.nx, 16);
+  const size_t n = (size_t)ld * go.nyg;
+  if (x.udiff.pom.grow(n, "xforc's assembled surface pressure")) return 1;
+  HIPCHECK(hipMemsetAsync(x.udiff.pom, 0, n * sizeof(double), atm->stream));
+  x.udiff.ld = ld;
+  x.udiff.nrow = nrow;
+  x.udiff.nranks = nranks;
+  const char *e = getenv("QGCM_HIP_XF_POISON");
+  x.udiff.poison = e && atoi(e) == 1;
+  x.udiff.fresh = false;
+  x.udiff.on = true;
+  return 0;
+}
+
+static int xf_udiff_ready(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const char *who) {
+  if (xf_ready(oc, atm, who, true)) return 1;
+  if (!atm->xf.udiff.on) QG_FAIL("%s: qgcm_hip_xforc_slab_udiff has not been called for this pair", who);
+  return 0;
+}
+
+static void xf_pom_msg_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfPomMsg &M) {
+  const QgGeom &go = oc->g;
+  const auto &u = atm->xf.udiff;
+  memset(&M, 0, sizeof(M));
+  M.nxpo = go.nx; M.nypo = go.nyg; M.ldo = go.ldx; M.lda = u.ld;
+  M.g0 = go.joff + go.jlo; M.g1 = go.joff + go.jhi; M.jlo = go.jlo;
+  M.nrow = u.nrow; M.nranks = u.nranks;
+  M.stride = xfp_len(u.nrow, go.nx);
+}
+
+extern "C" int qgcm_hip_xforc_slab_pom_len(qgcm_hip_handle oc, qgcm_hip_handle atm, long *n) {
+  const char *who = "qgcm_hip_xforc_slab_pom_len";
+  if (!n) QG_FAIL("%s: null argument", who);
+  if (xf_udiff_ready(oc, atm, who)) return 1;
+  *n = xfp_len(atm->xf.udiff.nrow, oc->g.nx);
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_slab_pom_pack(qgcm_hip_handle oc, qgcm_hip_handle atm, double *send_dev) {
+  const char *who = "qgcm_hip_xforc_slab_pom_pack";
+  if (xf_udiff_ready(oc, atm, who)) return 1;
+  if (!send_dev) QG_FAIL("%s: send_dev must hold qgcm_hip_xforc_slab_pom_len doubles", who);
+  auto &x = atm->xf;
+  hipStream_t st = atm->stream;
+  QgXfPomMsg M;
+  xf_pom_msg_fill(oc, atm, M);
+  M.pom = oc->p[oc->ip ^ 1]; // layer 1 of the lagged pressure, as xf_fill's P.pom
+  M.msg = send_dev;
+  HIPCHECK(hipEventRecord(x.ev_oc, oc->stream)); // after everything queued on the slab's stream, as the part waits
+  HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
+  HIPCHECK(qg_launch_xf_pom_pack(st, M));
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_slab_pom_assemble(qgcm_hip_handle oc, qgcm_hip_handle atm, const double *gath_dev, int nranks) {
+  const char *who = "qgcm_hip_xforc_slab_pom_assemble";
+  if (xf_udiff_ready(oc, atm, who)) return 1;
+  auto &x = atm->xf;
+  if (!gath_dev) QG_FAIL("%s: gath_dev must hold nranks messages of qgcm_hip_xforc_slab_pom_len doubles", who);
+  if (nranks != x.udiff.nranks)
+    QG_FAIL("%s: nranks = %d, the shear term was set up for %d ranks (qgcm_hip_xforc_slab_udiff)", who, nranks, x.udiff.nranks);
+  hipStream_t st = atm->stream;
+  QgXfPomMsg M;
+  xf_pom_msg_fill(oc, atm, M);
+  M.gath = gath_dev;
+  M.all = x.udiff.pom;
+  if (x.udiff.poison) // a row no rank owns, or one the copy misses, shows in the stress above it
+    HIPCHECK(hipMemsetAsync(x.udiff.pom, 0xFF, (size_t)x.udiff.ld * M.nypo * sizeof(double), st));
+  HIPCHECK(qg_launch_xf_pom_assemble(st, M));
+  x.udiff.fresh = true;
+  return 0;
+}
+
 // the pack's / the scatter's view of the replica
 static void xf_band_msg_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfBandMsg &B) {
   const auto &m = atm->atmon;
@@ -3463,11 +3564,25 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   if (x.heat.on && !send_dev) QG_FAIL("%s: the heat half is set up: send_dev must hold qgcm_hip_xforc_slab_msg_len doubles", who);
   const bool banded = x.bands.on;
   if (banded && !send_dev) QG_FAIL("%s: the bands are set up: send_dev must hold qgcm_hip_xforc_slab_msg_len doubles", who);
+  if (x.udiff.on && !x.udiff.fresh)
+    QG_FAIL("%s: the surface pressure has not been assembled for this call (qgcm_hip_xforc_slab_pom_pack, the all-gather, qgcm_hip_xforc_slab_pom_assemble)", who);
+  x.udiff.fresh = false;
   hipStream_t st = atm->stream;
   QgXfParams P;
   xf_fill(oc, atm, P);
   const QgGeom &go = oc->g;
   auto &mo = oc->mon;
+  // Two parameter blocks.  PA, the atmosphere side's (k_xf_fine, k_xf_fine_win: xf_point): with tau_udiff the BASIN's
+  // ocean grid, offsets and the assembled pom(:,:,1); without it no kernel of that side reads the ocean's
+  // entries.  P, the ocean side's (k_xf_tauo): the slab's local rows at the slab's offset.
+  QgXfParams PA = P;
+  PA.sco = nullptr;
+  if (x.udiff.on) {
+    PA.udiff = 1;
+    PA.nypo = go.nyg;
+    PA.ldo = x.udiff.ld;
+    PA.pom = x.udiff.pom;
+  }
   // the slab's rows of the ocean: local row j is row j + joff of the basin (k_xf_tauo reads the fine row jocoff + j)
   P.jocoff += go.joff;
   P.sco = nullptr; // (k_xf_lines: the atmosphere's two sums; the cyclic ocean's are k_xf_lines_oc_slab's)
@@ -3482,10 +3597,10 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
       HIPCHECK(hipMemsetAsync(x.tyf, 0xFF, nf, st));
       HIPCHECK(hipMemsetAsync(x.wf, 0xFF, (size_t)x.ldtf * P.nytaor * sizeof(double), st));
     }
-    for (int s = 0; s < bp.nseg; ++s) HIPCHECK(qg_launch_xf_win_fine(st, P, bp.c0[s], bp.c1[s]));
-    HIPCHECK(qg_launch_xf_win_band(st, P, bp.a0, bp.a1, bp.t0, bp.t1, bp.own & 3));
+    for (int s = 0; s < bp.nseg; ++s) HIPCHECK(qg_launch_xf_win_fine(st, PA, bp.c0[s], bp.c1[s]));
+    HIPCHECK(qg_launch_xf_win_band(st, PA, bp.a0, bp.a1, bp.t0, bp.t1, bp.own & 3));
   } else
-    launch_xf_atmos(P, st);
+    launch_xf_atmos(PA, st);
   hipLaunchKernelGGL(k_xf_tauo, dim3((P.nxpo + XF_NT - 1) / XF_NT, P.nypo), b, 0, st, P);
   QgWekParams W;
   memset(&W, 0, sizeof(W));

@@ -156,6 +156,7 @@ SYMBOLS = [
     "qgcm_hip_xforc_sst_init", "qgcm_hip_xforc_sst_set", "qgcm_hip_xforc_sst_get",
     "qgcm_hip_xforc_slab_init", "qgcm_hip_xforc_heat_slab_init", "qgcm_hip_xforc_slab_msg_len", "qgcm_hip_xforc_slab_part",
     "qgcm_hip_xforc_slab_combine", "qgcm_hip_xforc_slab_get", "qgcm_hip_xforc_bands", "qgcm_hip_xforc_slab_bands",
+    "qgcm_hip_xforc_slab_udiff", "qgcm_hip_xforc_slab_pom_len", "qgcm_hip_xforc_slab_pom_pack", "qgcm_hip_xforc_slab_pom_assemble",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
     "qgcm_hip_debug_live_allocs",
 ]
@@ -333,6 +334,11 @@ def load_library():
     if hasattr(L, "qgcm_hip_xforc_bands"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
         L.qgcm_hip_xforc_bands.argtypes = [C.c_int] * 6 + [ip, ip, C.POINTER(XforcBand)]
         L.qgcm_hip_xforc_slab_bands.argtypes = [vp, vp] + [C.c_int] * 4
+    if hasattr(L, "qgcm_hip_xforc_slab_udiff"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_xforc_slab_udiff.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.qgcm_hip_xforc_slab_pom_len.argtypes = [vp, vp, C.POINTER(C.c_long)]
+        L.qgcm_hip_xforc_slab_pom_pack.argtypes = [vp, vp, vp]
+        L.qgcm_hip_xforc_slab_pom_assemble.argtypes = [vp, vp, vp, C.c_int]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),
@@ -399,6 +405,7 @@ def row_split(nxto, forced=0):
 
 XFORC_BAND_LINES = ("txisat", "txinat", "txisoc", "txinoc")  # the bits of `own`
 XFORC_BAND_HEADER = 8   # XFB_HDR (k_xforc_slab.h): a0, a1, own, 0 and the four line sums in front of the fields
+XFORC_POM_HEADER = 8    # XFP_HDR (k_xforc_slab.h): g0, g1, nxpo and zeros in front of the surface pressure's rows
 XFORC_BAND_FIELDS = ("tauxa", "tauya", "uekat", "vekat", "wekta", "wekpa")  # the message's fields, (nrow, nxpa) each
 
 

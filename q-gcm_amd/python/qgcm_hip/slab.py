@@ -47,6 +47,19 @@ def partition(nyg, nranks):
     return out
 
 
+def owned_rows_tile(rows, nyg):
+    """rows[r] = (g0, g1), the global p rows rank r owns: raises unless they tile 1 .. nyg in rank order; returns the
+    longest range (the common row count of a message that carries every rank's owned rows)."""
+    nxt = 1
+    for r, (g0, g1) in enumerate(rows):
+        if g0 != nxt or g1 < g0:
+            raise ValueError("rank %d owns rows %d..%d: the slabs' owned rows do not tile 1..%d" % (r, g0, g1, nyg))
+        nxt = g1 + 1
+    if nxt != nyg + 1:
+        raise ValueError("the slabs' owned rows end at %d, the basin has %d" % (nxt - 1, nyg))
+    return max(g1 - g0 + 1 for g0, g1 in rows)
+
+
 def local_rows(nyg, g0, g1):
     """(nyl, joff, jlo, jhi): local array rows, global = local + joff, owned local range."""
     hlo = HALO if g0 > 1 else 0
@@ -326,6 +339,26 @@ class HipSlab(Handle):
         """Switch this pair to the banded atmosphere side (qgcm_hip_xforc_slab_bands): band = (a0, a1) and
         nrow from lib.xforc_bands."""
         check(self.L.qgcm_hip_xforc_slab_bands(self.h, atm.h, int(band[0]), int(band[1]), int(nrow), int(self.nranks)))
+
+    # tau_udiff on slabs (DESIGN 6q): the basin's pom(:,:,1) assembled on every rank ahead of the part
+    def xforc_udiff_init(self, atm, nrow, nranks):
+        """Switch the shear term on for this pair (qgcm_hip_xforc_slab_udiff), after xforc_init with tau_udiff = 0: nrow =
+        the longest owned p-row range of any rank."""
+        check(self.L.qgcm_hip_xforc_slab_udiff(self.h, atm.h, int(nrow), int(nranks)))
+
+    def xforc_pom_len(self, atm):
+        n = C.c_long()
+        check(self.L.qgcm_hip_xforc_slab_pom_len(self.h, atm.h, C.byref(n)))
+        return int(n.value)
+
+    def xforc_pom_pack(self, atm, send):
+        """This slab's owned rows of pom(:,:,1) behind their header -> send (device buffer of xforc_pom_len doubles);
+        asynchronous, on the atmosphere's stream."""
+        check(self.L.qgcm_hip_xforc_slab_pom_pack(self.h, atm.h, self._ptr(send)))
+
+    def xforc_pom_assemble(self, atm, gath):
+        """All ranks' rows (rank-major) -> the assembled pom(:,:,1) the next xforc_part reads."""
+        check(self.L.qgcm_hip_xforc_slab_pom_assemble(self.h, atm.h, self._ptr(gath), int(self.nranks)))
 
     def xforc_msg_len(self, atm):
         return self.L.qgcm_hip_xforc_slab_msg_len(atm.h)
@@ -817,15 +850,21 @@ class SlabOcean:
 
     # coupled runs: xforc under a replicated atmosphere, collective ---------------------------------------
     def xforc_setup(self, atmospheres, cdat=1.3e-3, rhoat=1.0, rhooc=1.0e3, hmat=1000.0, hmoc=100.0, tau_udiff=False,
-                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None, bands=False):
+                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None, bands=False, udiff_gather=False):
         """As model.xforc_setup (ndxr, nxaooc, nyaooc default to the ocean configuration's), for the slabs: `atmospheres` holds one whole-domain AtmosModel per local slab, on that
         slab's device - replicas of one atmosphere, which every rank steps redundantly and which stay bitwise identical.
-        tau_udiff is refused (the fine stress above the sea would need every slab's pom on every rank).
+        tau_udiff = True is refused by the library (the fine stress above the sea needs every slab's pom on every rank);
+        udiff_gather = True is that physics on slabs: every xforc() first all-gathers the slabs' owned rows of
+        pom(:,:,1) and assembles the basin's layer on every rank, and the stress kernels run on it unchanged - every
+        momentum output is bitwise the whole-domain xforc's with tau_udiff = True.  Pass only udiff_gather.
         bands = True: every rank runs the atmosphere side only on the fine rows its band of atmosphere rows
         (lib.xforc_bands, kept as self.xforc_plan) and its slab need; the bands travel in front of the heat block in the
         one all-gather, so xforc() then always gathers and combines.  The results are bitwise the default's."""
         from .lib import XforcParams, xforc_bands
         S, oc = self.slabs, self.cfg
+        if udiff_gather and tau_udiff:
+            raise ValueError("xforc_setup: pass only udiff_gather = True (tau_udiff = True alone asks the library for the "
+                             "shear term without the gather, which it refuses)")
         if len(atmospheres) != len(S):
             raise ValueError("xforc_setup: %d atmospheres for %d local slabs" % (len(atmospheres), len(S)))
         acfg = atmospheres[0].cfg
@@ -850,11 +889,20 @@ class SlabOcean:
             a.xforc_origin = (int(p.nx1), int(p.ny1))  # (where xforc_heat_setup finds the ocean)
         self.atmos = list(atmospheres)
         self._xf_bufs = None
+        self._xf_pom_bufs = None
         self.xforc_plan = None
-        if bands:
+        if bands or udiff_gather:
             rows = partition(oc.nypo, self.P)
             for x in S:  # (slabs cut otherwise than partition(): their own rows)
                 rows[x.rank] = (x.g0, x.g1)
+        if udiff_gather:
+            nrow = owned_rows_tile(rows, oc.nypo)
+            for x, a in zip(S, atmospheres):
+                x.xforc_udiff_init(a, nrow, self.P)
+            n = [x.xforc_pom_len(a) for x, a in zip(S, atmospheres)]
+            self._xf_pom_bufs = ([x.new_buffer(m) for x, m in zip(S, n)], [x.new_buffer(m * self.P) for x, m in zip(S, n)])
+            self._settle()
+        if bands:
             self.xforc_plan = xforc_bands(acfg.nxpa, acfg.nyta, ndxr, p.ny1, p.nyaooc, rows)
             for x, a in zip(S, atmospheres):
                 b = self.xforc_plan[x.rank]
@@ -881,9 +929,22 @@ class SlabOcean:
     def xforc(self):
         """One `call xforc`: every local rank runs the momentum half on its replica and its slab's rows; with the heat
         half, one all-gather of the partial cell sums (4*nxaooc*nyaooc doubles per rank) and the rank-ordered combine.
-        Banded (xforc_setup(bands=True)): always one all-gather - the ranks' bands, then the heat block - and the combine."""
+        Banded (xforc_setup(bands=True)): always one all-gather - the ranks' bands, then the heat block - and the combine.
+        With the shear term (xforc_setup(udiff_gather=True)) one more all-gather in front: pack, the gather of the pressure
+        rows (8 + nrow * nxpo doubles per rank), assemble on every local rank; then the sequence above, unchanged."""
         S, A = self.slabs, self.atmos
         self._join()
+        if getattr(self, "_xf_pom_bufs", None):  # the shear term (DESIGN 6q): the basin's pom(:,:,1) onto every rank first
+            psend, pgath = self._xf_pom_bufs
+            for i, (x, a) in enumerate(zip(S, A)):
+                x.xforc_pom_pack(a, psend[i])
+            for a in A:
+                a.sync()
+            self._comm(self.comm.all_gather, pgath, psend)
+            for x in S:
+                x.sync()
+            for i, (x, a) in enumerate(zip(S, A)):
+                x.xforc_pom_assemble(a, pgath[i])
         send, gath = self._xf_bufs if self._xf_bufs else ([None] * len(S), None)
         for i, (x, a) in enumerate(zip(S, A)):
             x.xforc_part(a, send[i])
