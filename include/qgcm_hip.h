@@ -1023,6 +1023,57 @@ int qgcm_hip_xforc_slab_pom_len(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, lo
 int qgcm_hip_xforc_slab_pom_pack(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, double *send_dev);
 int qgcm_hip_xforc_slab_pom_assemble(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, const double *gath_dev, int nranks);
 
+/* ---- tau_udiff on a y-slab ocean without the gather: owner-computed sums -------------------------------
+ * A third opt-in mode of the slab calls, beside the bands and the gather above; it excludes both and implies the shear
+ * term.  Rank r forms the fine stress only above the ocean rows it OWNS (the land south of the sea is rank 0's, the land
+ * north of it the last rank's), from its own rows of pom(:,:,1) and the 4 rows beyond each seam, which the direct
+ * neighbours send: one small all-gather of 8 + 8 * nxpo doubles per rank.  tauxa, tauya, vekat and the line sums have
+ * one owner each; uekat's meridional lines and wekpa's boxes are sent as partial sums over the owned fine rows and added
+ * in rank order by the combine, which every replica runs alike.  A line or box inside one rank's rows keeps the bits
+ * of the whole-domain call; one that a seam cuts is a sum of the same terms in another order.
+ * qgcm_hip_xforc_sums: the ownership plan, host code without a device; a pure function of its arguments.
+ *   slab_lo[r]..slab_hi[r]: the global ocean p rows rank r owns.  out[r], per rank:
+ *     g0, g1       the owned ocean p rows
+ *     f0, f1       the owned fine p rows (fine row jocoff + g above ocean row g, jocoff = (ny1 - 1) * ndxr); the ranks'
+ *                  intervals tile 1 .. nypaor in rank order
+ *     t0, t1       the owned fine T rows: T row j belongs to the owner of p row j
+ *     w0, w1       the fine p rows whose stress the rank holds correct: max(1, f0 - 3) .. min(nypaor, f1 + 3)
+ *     c0, c1       the cell rows k_xf_fine runs on (they cover w0 .. w1); u0, u1: the coarse rows of u1at / v1at
+ *     a0, a1       the coarse rows whose sample, uekat line or wekpa box meets f0 .. f1
+ *     own          the line sums the rank forms: the bits of qgcm_hip_xforc_band
+ *     nrow         rows per field in the message: the longest a0 .. a1 of any rank
+ *     mom_len      doubles of the message's momentum block: 8 + 5 * nrow * nxpa - f0, f1, a0, own, the four line sums
+ *                  (0.0 where not owned), then tauxa, tauya, vekat, the partial uekat line (without -uvekfc) and the
+ *                  partial wekpa numerator as (nrow, nxpa) from row a0 on
+ *   Refuses, naming the reason: nranks < 1, owned ranges that do not tile 1 .. nypo, a rank that owns fewer than 4
+ *   ocean rows, and (odd ndxr) a line sum whose two fine rows two ranks would share.
+ * qgcm_hip_xforc_slab_sums(oc_slab, atm, rank, nranks, slab_lo, slab_hi): after qgcm_hip_xforc_slab_init with
+ *   tau_udiff = 0, switches the pair to this mode; the library derives the plan with the same code and keeps entry
+ *   `rank`, whose rows must be the slab's.  Refuses a pair in the banded or the gather mode.  qgcm_hip_xforc_slab_init
+ *   again returns the pair to the replicated, shear-free path.  Reads QGCM_HIP_XF_POISON (INTEGRATION): 1 = NaN bytes
+ *   into the basin-sized array before every edge assemble and into the fine arrays before every part.
+ * qgcm_hip_xforc_slab_edge_len(oc_slab, atm, &n): n = 8 + 8 * nxpo doubles.
+ * qgcm_hip_xforc_slab_edge_pack(oc_slab, atm, send_dev): a header - g0, g1, nxpo, zeros - then owned rows g0 .. g0 + 3
+ *   and g1 - 3 .. g1 of layer 1 of the lagged pressure.  Halo rows are never packed.
+ * qgcm_hip_xforc_slab_edge_assemble(oc_slab, atm, gath_dev, nranks): the slab's owned rows (a local copy) and the 4 rows
+ *   beyond each seam from the neighbours' messages into the basin-sized array; rows g0 - 4 .. g1 + 4 are then the
+ *   basin's bits, everything else is stale (or NaN bytes).  A neighbour's header that does not fit writes nothing.
+ * In this mode qgcm_hip_xforc_slab_part refuses without a fresh edge assemble and needs send_dev;
+ *   qgcm_hip_xforc_slab_msg_len is mom_len plus the heat block; qgcm_hip_xforc_slab_combine is required without the
+ *   heat half too and refuses an nranks other than the plan's.  Ranks on different GPUs are untested. */
+typedef struct qgcm_hip_xforc_sum {
+  int g0, g1, f0, f1, t0, t1, w0, w1;
+  int c0, c1, u0, u1, a0, a1, own, nrow;
+  int mom_len, pad;
+} qgcm_hip_xforc_sum;
+int qgcm_hip_xforc_sums(int nxpa, int nyta, int ndxr, int ny1, int nyaooc, int nranks, const int *slab_lo,
+                        const int *slab_hi, qgcm_hip_xforc_sum *out);
+int qgcm_hip_xforc_slab_sums(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, int rank, int nranks, const int *slab_lo,
+                             const int *slab_hi);
+int qgcm_hip_xforc_slab_edge_len(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, long *n);
+int qgcm_hip_xforc_slab_edge_pack(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, double *send_dev);
+int qgcm_hip_xforc_slab_edge_assemble(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, const double *gath_dev, int nranks);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Runs n steps like qgcm_hip_steps and returns the HIP-event time (ms) of
  * the whole region, measured on the handle's stream. */

@@ -13,6 +13,11 @@ scale.  Host clock around work that ends in a synchronise; medians.
                                            4 virtual ranks two set-ups side by side, shear-free and udiff_gather, timed
                                            in alternating blocks in one session: pom_pack, pom_assemble, xforc_slab_part
                                            and the combine per rank
+  python3 profiles/tools/slab_coupled.py sums    the shear term by owner-computed sums (DESIGN 6r;
+                                           profiles/slab_udiff_sums.log): on 1, 2 and 4 virtual ranks three set-ups side by
+                                           side - udiff_gather replicated, udiff_gather banded, udiff_sums - timed in
+                                           alternating blocks in one session: the pack and the assemble ahead of the part,
+                                           xforc_slab_part and the combine per rank, SlabOcean.xforc() for all ranks
 With QGCM_HIP_LIB pointing at a build of the parent commit the same script gives the parent's whole-domain figures."""
 import os
 import sys
@@ -131,7 +136,7 @@ def time_xforc(so, slabs, reps, n):
     return tp, tc, tx
 
 
-def slab_setup(I, consts, nranks, bands=False, udiff=False):
+def slab_setup(I, consts, nranks, bands=False, udiff=False, sums=False):
     from qgcm_hip import config, oml_preset
     from qgcm_hip.slab import HipSlab, LocalComm, SlabOcean, partition
     oc = I["oc"]
@@ -146,7 +151,8 @@ def slab_setup(I, consts, nranks, bands=False, udiff=False):
     for x in slabs:
         x.oml_set_state(sst=I["sst"], sstm=I["sst"])
     reps = [atmosphere(I) for _ in slabs]
-    so.xforc_setup(reps, tau_udiff=False, **dict(dict(bands=True) if bands else {}, **(dict(udiff_gather=True) if udiff else {})))
+    kw = dict(dict(bands=True) if bands else {}, **(dict(udiff_gather=True) if udiff else {}))
+    so.xforc_setup(reps, tau_udiff=False, **dict(kw, **(dict(udiff_sums=True) if sums else {})))
     so.xforc_heat_setup(config.HeatConfig(**HT))
     return so, slabs, reps
 
@@ -301,16 +307,96 @@ def sheared(I, consts, nranks, rounds=4):
             m.close()
 
 
+def time_shear(so, slabs, reps, n):
+    """n synchronised xforc calls of a set-up with the shear term, in their parts: us of (every rank's pack ahead of the
+    part, every rank's assemble, every rank's part, every rank's combine, SlabOcean.xforc()).  The pack and the assemble are
+    the gather's (pom rows) or the sums' (edge rows), whichever the set-up has."""
+    send, gath = so._xf_bufs
+    edge = getattr(so, "_xf_edge_bufs", None)
+    psend, pgath = edge if edge else so._xf_pom_bufs
+    T = [[] for _ in range(5)]
+    for k in range(n):
+        t0 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            (x.xforc_edge_pack if edge else x.xforc_pom_pack)(a, psend[i])
+        for a in reps:
+            a.sync()
+        t1 = time.perf_counter()
+        so.comm.all_gather(pgath, psend)
+        t2 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            (x.xforc_edge_assemble if edge else x.xforc_pom_assemble)(a, pgath[i])
+        for a in reps:
+            a.sync()
+        t3 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_part(a, send[i])
+        for a in reps:
+            a.sync()
+        t4 = time.perf_counter()
+        so.comm.all_gather(gath, send)
+        t5 = time.perf_counter()
+        for i, (x, a) in enumerate(zip(slabs, reps)):
+            x.xforc_combine(a, gath[i])
+        for a in reps:
+            a.sync()
+        t6 = time.perf_counter()
+        so.xforc()
+        for a in reps:
+            a.sync()
+        t7 = time.perf_counter()
+        for v, d in zip(T, (t1 - t0, t3 - t2, t4 - t3, t6 - t5, t7 - t6)):
+            v.append(1e6 * d)
+    return T
+
+
+def summed(I, consts, nranks, rounds=4):
+    """udiff_gather replicated, udiff_gather banded and udiff_sums set-ups of `nranks` virtual ranks side by side (the heat
+    half on), timed in alternating blocks of 25 calls (the first 5 of a block dropped): per mode the median of each block,
+    then the median and the spread (max - min) of the block medians.  The gather's two forms are the whole-domain call's
+    bits; the sums differ from them at the cut entries of uekat, wekpa, wekta only (tests/test_gpu_xforc_sums.py); checked
+    here: tauxo and vekat bit-equal across the three, the largest relative difference of wekpa."""
+    modes = (("gather, replicated", dict(udiff=True)), ("gather, banded    ", dict(udiff=True, bands=True)), ("sums              ", dict(sums=True)))
+    sets = [slab_setup(I, consts, nranks, **kw) for _, kw in modes]
+    blocks = [[] for _ in modes]
+    for rnd in range(rounds):
+        for k, (so, slabs, reps) in enumerate(sets):
+            T = time_shear(so, slabs, reps, 25)
+            blocks[k].append([med(v[5:]) / (1 if j == 4 else nranks) for j, v in enumerate(T)])
+    out = [so.xforc_get() for so, _, _ in sets]
+    same = all(np.array_equal(x[f].view(np.int64), y[f].view(np.int64)) for o in out[1:] for x, y in zip(out[0], o) for f in ("tauxo", "vekat", "tauxa"))
+    rel = max(float(np.abs(x["wekpa"] - y["wekpa"]).max() / np.abs(x["wekpa"]).max()) for x, y in zip(out[0], out[2]))
+    so = sets[2][0]
+    nfine = I["at"].nyta * I["oc"].ndxr + 1
+    print("%d virtual rank(s): pressure message %d (gather) / %d (sums: edges) doubles per rank; main message %d (gather, replicated) / "
+          "%d (gather, banded) / %d (sums) doubles per rank; fine rows computed per rank in the sums' windows, of %d: %s; coarse "
+          "rows per rank: %s; tauxa, vekat, tauxo bit-equal across the three: %s; wekpa, sums against gather: largest |diff| / max %.2e"
+          % (nranks, sets[0][0]._xf_pom_bufs[0][0].numel(), so._xf_edge_bufs[0][0].numel(), sets[0][0]._xf_bufs[0][0].numel(),
+             sets[1][0]._xf_bufs[0][0].numel(), so._xf_bufs[0][0].numel(), nfine,
+             " ".join(str((p["cells"][1] - p["cells"][0] + 1) * I["oc"].ndxr) for p in so.xforc_plan),
+             " ".join("%d-%d" % p["arows"] for p in so.xforc_plan), same, rel), flush=True)
+    names = ("pack per rank", "assemble per rank", "xforc_slab_part per rank", "combine per rank",
+             "SlabOcean.xforc() for all ranks with its host-staged all-gathers")
+    for k, (name, _) in enumerate(modes):
+        for j, what in enumerate(names):
+            v = [blk[j] for blk in blocks[k]]
+            print("%d virtual rank(s), %s: %s, us: median of the block medians %.1f, spread %.1f (%s)"
+                  % (nranks, name, what, med(v), max(v) - min(v), " ".join("%.1f" % t for t in v)), flush=True)
+    for so, slabs, reps in sets:
+        for m in slabs + reps:
+            m.close()
+
+
 if __name__ == "__main__":
     print("device: %s; library: %s" % (torch.cuda.get_device_name(0), "the build QGCM_HIP_LIB names" if os.environ.get("QGCM_HIP_LIB") else "in-tree"), flush=True)
     I = inputs()
-    if sys.argv[1:] in (["bands"], ["udiff"]):
+    if sys.argv[1:] in (["bands"], ["udiff"], ["sums"]):
         from qgcm_hip.slab import global_consts
         o = ocean(I)
         consts = global_consts(I["oc"], o.helmholtz)
         o.close()
         for n in (1, 2, 4):
-            (banded if sys.argv[1] == "bands" else sheared)(I, consts, n)
+            dict(bands=banded, udiff=sheared, sums=summed)[sys.argv[1]](I, consts, n)
         sys.exit(0)
     c = whole(I)
     if c is not None:

@@ -26,6 +26,18 @@
 //   k_xf_pom_pack         the slab's OWNED p rows of layer 1 of the lagged pressure -> the message
 //   k_xf_pom_assemble     every rank's rows -> the assembled array (nxpo, nypo): a copy, one writer per point
 //
+// and, for tau_udiff without that gather (every rank forms the fine stress above the rows it OWNS and the ranks
+// exchange rank-ordered partial sums of the coarse fields):
+//
+//   k_xf_edge_pack        the first 4 and the last 4 OWNED p rows of layer 1 of the lagged pressure -> the edge message
+//   k_xf_edge_assemble    the slab's owned rows and the 4 rows beyond each seam (the direct neighbours' edges) -> the
+//                         basin-sized array of 6q: rows g0 - 4 .. g1 + 4 are the basin's bits, the rest is not written
+//   k_xf_sums_atm         coarse rows a0 .. : tauxa, tauya, vekat where the rank owns the sampled fine row (k_xf_atm's
+//                         expressions) and the terms of uekat's meridional line that lie in the owned fine rows
+//   k_xf_sums_wekpa       the rows of wekpa's box that lie in the owned fine T rows: the numerator, k_xf_wekpa's order
+//   k_xf_sums_combine     samples and line sums from their one owner; uekat, wekpa from the contributing ranks' partials,
+//                         the first one's value then the others added in rank order
+//
 // A cell wholly inside one slab keeps the bits of the whole-domain sum (x + 0.0 = x); a cell a seam cuts is a sum of the
 // same terms in another order.  No atomics; every sum has a fixed tree.
 #pragma once
@@ -87,6 +99,46 @@ struct QgXfPomMsg {
   double *all;         // assemble: (lda, nypo)
 };
 static inline long xfp_len(int nrow, int nxpo) { return XFP_HDR + (long)nrow * nxpo; }
+
+// ---- owner-computed sums -----------------------------------------------------------------------------------------
+// The edge message: XFE_HDR doubles - g0, g1 (the global p rows the slab owns), nxpo, zeros - then 2 * XFE_ROWS rows of
+// nxpo columns: rows g0 .. g0 + 3, then rows g1 - 3 .. g1 (a slab owns at least 4 rows).
+#define XFE_HDR 8
+#define XFE_ROWS 4
+struct QgXfEdgeMsg {
+  int nxpo, nypo;      // the BASIN's p grid
+  int ldo, lda;        // pitches: the slab's p grid, the basin-sized array
+  int g0, g1, jlo;     // the owned global rows and the local row of g0
+  int rank, nranks;    // assemble: the neighbours are ranks rank - 1 and rank + 1
+  long stride;         // assemble: rank r's message starts at gath + r * stride
+  const double *pom;   // layer 1 of the slab's lagged pressure (local rows)
+  double *msg;         // pack
+  const double *gath;  // assemble
+  double *all;         // assemble: (lda, nypo)
+};
+static inline long xfe_len(int nxpo) { return XFE_HDR + 2L * XFE_ROWS * nxpo; }
+
+// The momentum block of a rank's message in this mode: XFS_HDR doubles - f0, f1 (the fine p rows the rank owns), a0 (the
+// first coarse row of the fields), own (the line sums it formed: the bits of QgXfBandMsg), then the four sums (0.0
+// where not owned) - and five fields of nrow rows by nxpa columns from coarse row a0 on: tauxa, tauya, vekat (0.0 where
+// the rank does not own the sampled fine row), the partial uekat line (without the factor -uvekfc) and the partial
+// wekpa numerator; 0.0 past the rank's range, past a field's last row and past its last column.
+#define XFS_HDR 8
+#define XFS_NF 5
+struct QgXfSumMsg {
+  int nxpa, nxta, nypa, nyta, lda, ldta, ldf, ldtf;
+  int ndxr, ndxodd, nijwid, nxtaor, nytaor, nypaor;
+  int f0, f1, t0, t1, a0, a1, own, nrow; // the part: this rank's plan (t0 .. t1: the owned fine T rows)
+  int nranks;                            // combine
+  long stride;                           // combine: rank r's message starts at gath + r * stride
+  const double *txf, *tyf, *wf;          // the part
+  double *tauxa, *tauya, *uekat, *vekat, *wekpa; // combine
+  double uvekfc;
+  QgScalars *sca, *sco;                  // (sco: the cyclic ocean's, or nullptr)
+  double *msg;                           // the part
+  const double *gath;                    // combine
+};
+static inline long xfs_mom_len(int nrow, int nxpa) { return XFS_HDR + (long)XFS_NF * nrow * nxpa; }
 
 struct QgXfHeatSlabParams {
   QgXfHeatParams h;   // nyto and the tables: the GLOBAL ocean's; sstm, fnetoc, ldto: the slab's local T rows
@@ -311,5 +363,193 @@ __global__ __launch_bounds__(XFS_NT) void k_xf_pom_assemble(const QgXfPomMsg M) 
   const int g = g0 + jr;
   if (i >= M.nxpo || g > g1) return;
   M.all[(long)(g - 1) * M.lda + i] = m[XFP_HDR + (long)jr * M.nxpo + i];
+}
+// ---- owner-computed sums -----------------------------------------------------------------------------------------
+// grid: (ceil(nxpo/256), 2 * XFE_ROWS): message row jr = owned row g0 + jr (jr < 4) or g1 - 7 + jr.  Halo rows are never
+// read.  Consecutive lanes, consecutive doubles on both sides.
+__global__ __launch_bounds__(XFS_NT) void k_xf_edge_pack(const QgXfEdgeMsg M) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, jr = blockIdx.y;
+  if (i == 0 && jr == 0) {
+    double *h = M.msg;
+    h[0] = (double)M.g0; h[1] = (double)M.g1; h[2] = (double)M.nxpo;
+#pragma unroll
+    for (int k = 3; k < XFE_HDR; ++k) h[k] = 0.0;
+  }
+  if (i >= M.nxpo) return;
+  const int g = jr < XFE_ROWS ? M.g0 + jr : M.g1 - (2 * XFE_ROWS - 1) + jr;
+  M.msg[XFE_HDR + (long)jr * M.nxpo + i] = M.pom[(long)(M.jlo - 1 + g - M.g0) * M.ldo + i];
+}
+
+// grid: (ceil(nxpo/256), own + 2 * XFE_ROWS), own = g1 - g0 + 1: rows jr < own copy the slab's owned row g0 + jr; the next
+// four are rows g0 - 4 .. g0 - 1 from the last four rows of rank - 1's message, the last four rows g1 + 1 .. g1 + 4 from
+// the first four of rank + 1's.  One writer per point.  A neighbour's header that does not describe at least 4 rows
+// inside 1 .. nypo that end (begin) at this slab's seam, or another row length, writes nothing.
+__global__ __launch_bounds__(XFS_NT) void k_xf_edge_assemble(const QgXfEdgeMsg M) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, jr = blockIdx.y, own = M.g1 - M.g0 + 1;
+  if (i >= M.nxpo) return;
+  if (jr < own) {
+    M.all[(long)(M.g0 + jr - 1) * M.lda + i] = M.pom[(long)(M.jlo - 1 + jr) * M.ldo + i];
+    return;
+  }
+  const int k = jr - own;
+  const bool south = k < XFE_ROWS;
+  const int r = south ? M.rank - 1 : M.rank + 1;
+  if (r < 0 || r >= M.nranks) return;
+  const double *m = M.gath + (long)r * M.stride;
+  const int h0 = (int)m[0], h1 = (int)m[1], nx = (int)m[2];
+  if (h0 < 1 || h1 > M.nypo || h1 - h0 + 1 < XFE_ROWS || nx != M.nxpo) return;
+  if (south ? h1 != M.g0 - 1 : h0 != M.g1 + 1) return;
+  const int g = south ? M.g0 - XFE_ROWS + k : M.g1 + 1 + (k - XFE_ROWS); // (inside h0 .. h1, hence inside the basin)
+  const int mr = south ? XFE_ROWS + k : k - XFE_ROWS;
+  M.all[(long)(g - 1) * M.lda + i] = m[XFE_HDR + (long)mr * M.nxpo + i];
+}
+
+// grid: (ceil(nxpa/256), nrow): coarse row ja = a0 + jr.  k_xf_atm's expressions and order; the line's terms k = 0 .. ndxr
+// (fine rows joff + k, end weights 0.5) restricted to the owned fine rows f0 .. f1, ascending, the first term starting
+// the sum.  A line inside f0 .. f1 is k_xf_atm's sum.
+__global__ __launch_bounds__(XFS_NT) void k_xf_sums_atm(const QgXfSumMsg B) {
+  const int ia = blockIdx.x * blockDim.x + threadIdx.x + 1, jr = blockIdx.y, ja = B.a0 + jr;
+  if (ia == 1 && jr == 0) {
+    double *h = B.msg;
+    h[0] = (double)B.f0; h[1] = (double)B.f1; h[2] = (double)B.a0; h[3] = (double)B.own;
+    h[4] = (B.own & 1) ? B.sca->txisoc : 0.0;
+    h[5] = (B.own & 2) ? B.sca->txinoc : 0.0;
+    h[6] = (B.own & 4) ? B.sco->txisoc : 0.0;
+    h[7] = (B.own & 8) ? B.sco->txinoc : 0.0;
+  }
+  if (ia > B.nxpa) return;
+  const int ndxr = B.ndxr, ldf = B.ldf;
+  double tx = 0.0, ty = 0.0, ve = 0.0, up = 0.0;
+  if (ja <= B.a1 && ja <= B.nypa) {
+    const int joff = 1 + (ja - 1) * ndxr;
+    if (joff >= B.f0 && joff <= B.f1) { // the sampled fine row is this rank's
+      const long o = (long)(joff - 1) * ldf + (long)(ia - 1) * ndxr;
+      tx = B.txf[o];
+      ty = B.tyf[o];
+      if (ia <= B.nxta) {
+        const double *t = B.txf + o;
+        double s = 0.5 * t[0];
+        for (int i = 1; i < ndxr; ++i) s = s + t[i];
+        s = s + 0.5 * t[ndxr];
+        ve = B.uvekfc * s;
+      }
+    }
+    if (ja <= B.nyta) {
+      const int k0 = B.f0 - joff > 0 ? B.f0 - joff : 0, k1 = B.f1 - joff < ndxr ? B.f1 - joff : ndxr;
+      if (k0 <= k1) {
+        const int ic = (ia == B.nxpa) ? 1 : ia;
+        const double *t = B.tyf + (long)(joff - 1) * ldf + (long)(ic - 1) * ndxr;
+        auto term = [&](int k) { const double v = t[(long)k * ldf]; return (k == 0 || k == ndxr) ? 0.5 * v : v; };
+        double s = term(k0);
+        for (int k = k0 + 1; k <= k1; ++k) s = s + term(k);
+        up = s;
+      }
+    }
+  }
+  double *f = B.msg + XFS_HDR + (long)jr * B.nxpa + (ia - 1);
+  const long nf = (long)B.nrow * B.nxpa;
+  f[0] = tx; f[nf] = ty; f[2 * nf] = ve; f[3 * nf] = up;
+}
+
+// grid: (ceil(nxpa/64), nrow), block 64: k_xf_wekpa's loops on the rows of the box that lie in the owned fine T rows
+// t0 .. t1; wsum does not depend on the data and is the combine's.
+__global__ __launch_bounds__(64) void k_xf_sums_wekpa(const QgXfSumMsg B) {
+  const int ia = blockIdx.x * blockDim.x + threadIdx.x + 1, jr = blockIdx.y, ja = B.a0 + jr;
+  if (ia > B.nxpa) return;
+  const int ndxr = B.ndxr, nijwid = B.nijwid, nxtaor = B.nxtaor;
+  auto wt = [&](int d) { return B.ndxodd ? ((d == 0 || d == ndxr) ? 0.5 : 1.0) : (d == ndxr ? 0.0 : 1.0); };
+  double wtasum = 0.0;
+  if (ja <= B.a1 && ja <= B.nypa) {
+    const int jbeg = (ja - 1) * ndxr - (ndxr - 1) / 2;
+    int jlo = jbeg > 1 ? jbeg : 1;
+    int jhi = (jbeg + nijwid - 1 < B.nytaor) ? jbeg + nijwid - 1 : B.nytaor;
+    if (jlo < B.t0) jlo = B.t0;
+    if (jhi > B.t1) jhi = B.t1;
+    const int ibeg = (ia - 1) * ndxr - (ndxr - 1) / 2;
+    for (int j = jlo; j <= jhi; ++j) {
+      const double wtj = wt(j - jbeg);
+      const double *row = B.wf + (long)(j - 1) * B.ldtf;
+      for (int d0 = 0; d0 < nijwid; d0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          int it = ibeg + d0 + u - 1; // 0-based cyclic column
+          it = it < 0 ? it + nxtaor : (it >= nxtaor ? it - nxtaor : it);
+          v[u] = d0 + u < nijwid ? row[it] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (d0 + u < nijwid) {
+            const double w = wt(d0 + u) * wtj;
+            wtasum = wtasum + w * v[u];
+          }
+      }
+    }
+  }
+  B.msg[XFS_HDR + ((long)4 * B.nrow + jr) * B.nxpa + (ia - 1)] = wtasum;
+}
+
+// grid: (ceil(nxpa/256), nypa): thread (ia, ja) reads the ranks' messages in rank order.  Whether rank r holds the sample
+// of row ja, terms of its uekat line or rows of its wekpa box is read from r's f0, f1; a header that does not describe
+// fine rows inside 1 .. nypaor, or whose fields do not hold row ja, contributes nothing.  Every output point has one
+// writer: this thread.
+__global__ __launch_bounds__(XFS_NT) void k_xf_sums_combine(const QgXfSumMsg B) {
+  const int ia = blockIdx.x * blockDim.x + threadIdx.x + 1, ja = blockIdx.y + 1;
+  if (ia == 1 && ja == 1)
+    for (int r = 0; r < B.nranks; ++r) {
+      const double *m = B.gath + (long)r * B.stride;
+      const int f0 = (int)m[0], f1 = (int)m[1], own = (int)m[3];
+      if (f0 < 1 || f1 > B.nypaor || f1 < f0) continue;
+      if (own & 1) B.sca->txisoc = m[4];
+      if (own & 2) B.sca->txinoc = m[5];
+      if (B.sco && (own & 4)) B.sco->txisoc = m[6];
+      if (B.sco && (own & 8)) B.sco->txinoc = m[7];
+    }
+  if (ia > B.nxpa) return;
+  const int ndxr = B.ndxr, nijwid = B.nijwid;
+  const int joff = 1 + (ja - 1) * ndxr;
+  const int jbeg = (ja - 1) * ndxr - (ndxr - 1) / 2;
+  const int jlo = jbeg > 1 ? jbeg : 1;
+  const int jhi = (jbeg + nijwid - 1 < B.nytaor) ? jbeg + nijwid - 1 : B.nytaor;
+  const long nf = (long)B.nrow * B.nxpa;
+  double us = 0.0, wp = 0.0;
+  bool hu = false, hw = false;
+  for (int r = 0; r < B.nranks; ++r) {
+    const double *m = B.gath + (long)r * B.stride;
+    const int f0 = (int)m[0], f1 = (int)m[1], a0 = (int)m[2];
+    if (f0 < 1 || f1 > B.nypaor || f1 < f0) continue;
+    const int jr = ja - a0;
+    if (a0 < 1 || jr < 0 || jr >= B.nrow) continue;
+    const int t1 = f1 < B.nytaor ? f1 : B.nytaor;
+    const double *f = m + XFS_HDR + (long)jr * B.nxpa + (ia - 1);
+    if (joff >= f0 && joff <= f1) {
+      B.tauxa[(long)(ja - 1) * B.lda + (ia - 1)] = f[0];
+      B.tauya[(long)(ja - 1) * B.lda + (ia - 1)] = f[nf];
+      if (ia <= B.nxta) B.vekat[(long)(ja - 1) * B.ldta + (ia - 1)] = f[2 * nf];
+    }
+    if (ja <= B.nyta && joff <= f1 && joff + ndxr >= f0) {
+      const double v = f[3 * nf];
+      us = hu ? us + v : v;
+      hu = true;
+    }
+    if (jlo <= t1 && jhi >= f0) {
+      const double v = f[4 * nf];
+      wp = hw ? wp + v : v;
+      hw = true;
+    }
+  }
+  if (hu) B.uekat[(long)(ja - 1) * B.lda + (ia - 1)] = -B.uvekfc * us;
+  if (hw) {
+    auto wt = [&](int d) { return B.ndxodd ? ((d == 0 || d == ndxr) ? 0.5 : 1.0) : (d == ndxr ? 0.0 : 1.0); };
+    double wsum = 0.0; // k_xf_wekpa's own sum, term for term
+    for (int j = jlo; j <= jhi; ++j) {
+      const double wtj = wt(j - jbeg);
+      for (int d = 0; d < nijwid; ++d) {
+        const double w = wt(d) * wtj;
+        wsum = wsum + w;
+      }
+    }
+    B.wekpa[(long)(ja - 1) * B.lda + (ia - 1)] = wp / wsum;
+  }
 }
 #endif // QG_XFORC_SLAB_KERNELS

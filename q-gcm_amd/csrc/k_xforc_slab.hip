@@ -1,4 +1,4 @@
-// k_xforc_slab.hip - the kernels of xforc on a y-slab ocean (k_xforc_slab.h, DESIGN 6o, 6p, 6q) as a translation unit, and so a
+// k_xforc_slab.hip - the kernels of xforc on a y-slab ocean (k_xforc_slab.h, DESIGN 6o, 6p, 6q, 6r) as a translation unit, and so a
 // device code object, of its own, for the reason k_tend_rows.hip gives: qgcm_hip.hip compiles to the device code it
 // compiled to before these kernels existed.
 #define QG_XFORC_SLAB_KERNELS
@@ -71,5 +71,37 @@ hipError_t qg_launch_xf_pom_pack(hipStream_t st, const QgXfPomMsg &M) {
 
 hipError_t qg_launch_xf_pom_assemble(hipStream_t st, const QgXfPomMsg &M) {
   hipLaunchKernelGGL(k_xf_pom_assemble, dim3((M.nxpo + XFS_NT - 1) / XFS_NT, M.nrow, M.nranks), dim3(XFS_NT), 0, st, M);
+  return hipGetLastError();
+}
+
+// ---- owner-computed sums -------------------------------------------------------------------------------------------
+hipError_t qg_launch_xf_edge_pack(hipStream_t st, const QgXfEdgeMsg &M) {
+  hipLaunchKernelGGL(k_xf_edge_pack, dim3((M.nxpo + XFS_NT - 1) / XFS_NT, 2 * XFE_ROWS), dim3(XFS_NT), 0, st, M);
+  return hipGetLastError();
+}
+
+hipError_t qg_launch_xf_edge_assemble(hipStream_t st, const QgXfEdgeMsg &M) {
+  hipLaunchKernelGGL(k_xf_edge_assemble, dim3((M.nxpo + XFS_NT - 1) / XFS_NT, M.g1 - M.g0 + 1 + 2 * XFE_ROWS), dim3(XFS_NT), 0, st, M);
+  return hipGetLastError();
+}
+
+// wektaor on the owned fine T rows t0 .. t1 (after qg_launch_xf_win_fine on the plan's one window)
+hipError_t qg_launch_xf_sums_wektaor(hipStream_t st, const QgXfParams &P, int t0, int t1) {
+  const QgXfWin W = {t0, 0, 0};
+  hipLaunchKernelGGL(k_xf_wektaor_win, dim3((P.nxtaor + XF_NT - 1) / XF_NT, t1 - t0 + 1), dim3(XF_NT), 0, st, P, W);
+  return hipGetLastError();
+}
+
+// the atmosphere's line sums the rank owns, then its samples and partial sums into the message's momentum block
+hipError_t qg_launch_xf_sums_part(hipStream_t st, const QgXfParams &P, const QgXfSumMsg &B) {
+  const QgXfWin W = {1, 0, B.own & 3};
+  if (W.lines) hipLaunchKernelGGL(k_xf_lines_win, dim3(1), dim3(XF_NT), 0, st, P, W);
+  hipLaunchKernelGGL(k_xf_sums_atm, dim3((B.nxpa + XFS_NT - 1) / XFS_NT, B.nrow), dim3(XFS_NT), 0, st, B);
+  hipLaunchKernelGGL(k_xf_sums_wekpa, dim3((B.nxpa + 63) / 64, B.nrow), dim3(64), 0, st, B);
+  return hipGetLastError();
+}
+
+hipError_t qg_launch_xf_sums_combine(hipStream_t st, const QgXfSumMsg &B) {
+  hipLaunchKernelGGL(k_xf_sums_combine, dim3((B.nxpa + XFS_NT - 1) / XFS_NT, B.nypa), dim3(XFS_NT), 0, st, B);
   return hipGetLastError();
 }

@@ -425,6 +425,14 @@ struct qgcm_hip_ctx {
       int nrow = 0, nranks = 0, ld = 0;
       QgDbl pom;
     } udiff;
+    // tau_udiff by owner-computed sums (qgcm_hip_xforc_slab_sums): this rank's part of the ownership plan
+    // and the rank count; the basin-sized array is udiff.pom (udiff.on stays false: the modes exclude each other), of
+    // which an edge assemble fills rows g0 - 4 .. g1 + 4; fresh: one has run since the last qgcm_hip_xforc_slab_part
+    struct {
+      bool on = false, fresh = false, poison = false; // poison: QGCM_HIP_XF_POISON=1 - NaN bytes before every assemble / part
+      int rank = 0, nranks = 0;
+      qgcm_hip_xforc_sum plan;
+    } sums;
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
@@ -2910,7 +2918,7 @@ extern "C" int qgcm_hip_aml_get_diag(qgcm_hip_handle c, double *entat, double *d
 // xforc is off until qgcm_hip_xforc_init has gone through (it replaces the buffers)
 static void xf_off(qgcm_hip_ctx *a) {
   auto &x = a->xf;
-  x.on = x.coupled = x.slab = x.bands.on = x.udiff.on = x.udiff.fresh = false;
+  x.on = x.coupled = x.slab = x.bands.on = x.udiff.on = x.udiff.fresh = x.sums.on = x.sums.fresh = false;
   x.oc = nullptr;
   x.heat.on = false; // (set up against the geometry qgcm_hip_xforc_init was given: qgcm_hip_xforc_heat_init again)
   x.sst.on = false;  // (likewise qgcm_hip_xforc_sst_init)
@@ -3419,6 +3427,7 @@ extern "C" int qgcm_hip_xforc_slab_bands(qgcm_hip_handle oc, qgcm_hip_handle atm
   const char *who = "qgcm_hip_xforc_slab_bands";
   if (xf_ready(oc, atm, who, true)) return 1;
   auto &x = atm->xf;
+  if (x.sums.on) QG_FAIL("%s: this pair runs the owner-computed sums (qgcm_hip_xforc_slab_sums): the modes exclude each other", who);
   const int nypa = atm->g.ny;
   if (a0 < 1 || a1 > nypa || a1 < a0) QG_FAIL("%s: the band %d..%d lies outside the atmosphere's rows 1..%d", who, a0, a1, nypa);
   if (nranks < 1 || nranks > nypa) QG_FAIL("%s: %d ranks for %d atmosphere rows", who, nranks, nypa);
@@ -3440,6 +3449,7 @@ extern "C" int qgcm_hip_xforc_slab_msg_len(qgcm_hip_handle atm) {
   if (!atm || !atm->xf.on || !atm->xf.slab) return 0;
   const int heat = atm->xf.heat.on ? 4 * atm->xf.prm.nxaooc * atm->xf.prm.nyaooc : 0;
   if (atm->xf.bands.on) return atm->xf.bands.plan.mom_len + heat; // the momentum block, then the heat block
+  if (atm->xf.sums.on) return atm->xf.sums.plan.mom_len + heat;
   return heat; // (replicated: the momentum half alone exchanges nothing)
 }
 
@@ -3460,6 +3470,7 @@ extern "C" int qgcm_hip_xforc_slab_udiff(qgcm_hip_handle oc, qgcm_hip_handle atm
   const QgGeom &go = oc->g;
   const int own = go.jhi - go.jlo + 1;
   if (nranks < 1 || nranks > 65535) QG_FAIL("%s: nranks = %d outside 1..65535", who, nranks);
+  if (x.sums.on) QG_FAIL("%s: this pair runs the owner-computed sums (qgcm_hip_xforc_slab_sums): the modes exclude each other", who);
   if (nrow < own || nrow > go.nyg)
     QG_FAIL("%s: the common row count %d does not hold this slab's %d owned rows (or exceeds the basin's %d)", who, nrow, own, go.nyg);
   HIPCHECK(hipStreamSynchronize(atm->stream));
@@ -3536,6 +3547,199 @@ extern "C" int qgcm_hip_xforc_slab_pom_assemble(qgcm_hip_handle oc, qgcm_hip_han
   return 0;
 }
 
+// ---- tau_udiff by owner-computed sums -----------------------------------------------------------------------------
+// xf_point reads pom at ocean rows jo - 1 .. jo + 1 of a fine point above the sea, so the fine stress on a fine row needs
+// three ocean rows: a rank forms it above the rows it owns from its own pressure and four rows beyond each seam, which the
+// direct neighbours send (pack, a small all-gather by the caller, assemble).  Of the coarse products only uekat's
+// meridional lines and wekpa's boxes are sums a seam can cut: they travel as partial sums and are added in rank order.
+hipError_t qg_launch_xf_edge_pack(hipStream_t st, const QgXfEdgeMsg &M);
+hipError_t qg_launch_xf_edge_assemble(hipStream_t st, const QgXfEdgeMsg &M);
+hipError_t qg_launch_xf_sums_wektaor(hipStream_t st, const QgXfParams &P, int t0, int t1);
+hipError_t qg_launch_xf_sums_part(hipStream_t st, const QgXfParams &P, const QgXfSumMsg &B);
+hipError_t qg_launch_xf_sums_combine(hipStream_t st, const QgXfSumMsg &B);
+
+// The ownership plan, host code without a device: the windows are read off the kernels' index expressions
+// (k_xforc_rows.inc, k_xforc_slab.h), as xf_band_windows' are.
+static int xf_sums_plan(const char *who, int nxpa, int nyta, int ndxr, int ny1, int nyaooc, int nranks, const int *lo, const int *hi,
+                        qgcm_hip_xforc_sum *out) {
+  if (!lo || !hi || !out) QG_FAIL("%s: null argument", who);
+  if (nxpa < 2 || nyta < 2 || ndxr < 1 || ny1 < 1 || nyaooc < 1 || ny1 + nyaooc - 1 > nyta)
+    QG_FAIL("%s: bad geometry (nxpa %d, nyta %d, ndxr %d, ny1 %d, nyaooc %d)", who, nxpa, nyta, ndxr, ny1, nyaooc);
+  if (nranks < 1) QG_FAIL("%s: nranks = %d, need at least one rank", who, nranks);
+  const int n = ndxr, nypa = nyta + 1, nytaor = nyta * n, nypaor = nytaor + 1, odd = n % 2, nijwid = n + odd;
+  const int nyg = nyaooc * n + 1, jocoff = (ny1 - 1) * n;
+  for (int r = 0; r < nranks; ++r) {
+    const int want = r ? hi[r - 1] + 1 : 1;
+    if (lo[r] != want || hi[r] < lo[r] || hi[r] > nyg)
+      QG_FAIL("%s: the owned rows do not tile 1..%d: rank %d owns %d..%d, its range must begin at %d", who, nyg, r, lo[r], hi[r], want);
+  }
+  if (hi[nranks - 1] != nyg) QG_FAIL("%s: the owned rows do not tile 1..%d: the last rank's end at %d", who, nyg, hi[nranks - 1]);
+  for (int r = 0; r < nranks; ++r)
+    if (hi[r] - lo[r] + 1 < 4)
+      QG_FAIL("%s: rank %d owns %d ocean rows, fewer than 4 (the rows beyond a seam come from the direct neighbours' edges only)", who,
+              r, hi[r] - lo[r] + 1);
+  auto cell = [&](int f) { const int c = (f - 1) / n + 1; return c < nyta ? c : nyta; }; // (fine row nypaor: cell row nyta)
+  const int jsou = 1 + n / 2, jnor = nypaor - n / 2;
+  int nrow = 0;
+  for (int r = 0; r < nranks; ++r) {
+    qgcm_hip_xforc_sum &s = out[r];
+    memset(&s, 0, sizeof(s));
+    s.g0 = lo[r]; s.g1 = hi[r];
+    s.f0 = r == 0 ? 1 : jocoff + lo[r];
+    s.f1 = r == nranks - 1 ? nypaor : jocoff + hi[r];
+    s.t0 = s.f0; s.t1 = s.f1 < nytaor ? s.f1 : nytaor; // T row j reads p rows j, j + 1
+    // the stress the rank holds correct: its own rows, row f1 + 1 for its last T row, and the fine rows under the three
+    // halo rows of its slab (k_xf_tauo)
+    s.w0 = s.f0 - 3 > 1 ? s.f0 - 3 : 1;
+    s.w1 = s.f1 + 3 < nypaor ? s.f1 + 3 : nypaor;
+    s.c0 = cell(s.w0); s.c1 = cell(s.w1);
+    s.u0 = s.c0 > 1 ? s.c0 - 1 : 1; s.u1 = s.c1 + 2 < nypa ? s.c1 + 2 : nypa; // (qg_launch_xf_win_fine)
+    // a line sum belongs to the rank whose rows hold its outer row; odd ndxr: the partner row must be that rank's too
+    if (jsou >= s.f0 && jsou <= s.f1) {
+      if (odd && jsou + 1 > s.f1)
+        QG_FAIL("%s: txisat reads the fine rows %d and %d, which rank %d (fine rows %d..%d) and the next would share", who, jsou,
+                jsou + 1, r, s.f0, s.f1);
+      s.own |= 1;
+    }
+    if (jnor >= s.f0 && jnor <= s.f1) {
+      if (odd && jnor - 1 < s.f0)
+        QG_FAIL("%s: txinat reads the fine rows %d and %d, which rank %d (fine rows %d..%d) and the one before would share", who,
+                jnor - 1, jnor, r, s.f0, s.f1);
+      s.own |= 2;
+    }
+    s.own |= (lo[r] == 1 ? 4 : 0) | (hi[r] == nyg ? 8 : 0);
+    // the coarse rows whose sample (fine row joff), uekat line (joff .. joff + n) or wekpa box (fine T rows) meets the rank's
+    s.a0 = 0;
+    for (int ja = 1; ja <= nypa; ++ja) {
+      const int joff = 1 + (ja - 1) * n;
+      const int jbeg = (ja - 1) * n - (n - 1) / 2;
+      const int jlo = jbeg > 1 ? jbeg : 1, jhi = jbeg + nijwid - 1 < nytaor ? jbeg + nijwid - 1 : nytaor;
+      const bool hit = (joff >= s.f0 && joff <= s.f1) || (ja <= nyta && joff <= s.f1 && joff + n >= s.f0) || (jlo <= s.t1 && jhi >= s.t0);
+      if (!hit) continue;
+      if (!s.a0) s.a0 = ja;
+      s.a1 = ja;
+    }
+    if (s.a1 - s.a0 + 1 > nrow) nrow = s.a1 - s.a0 + 1;
+  }
+  for (int r = 0; r < nranks; ++r) {
+    out[r].nrow = nrow;
+    out[r].mom_len = (int)xfs_mom_len(nrow, nxpa);
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_sums(int nxpa, int nyta, int ndxr, int ny1, int nyaooc, int nranks, const int *slab_lo,
+                                   const int *slab_hi, qgcm_hip_xforc_sum *out) {
+  return xf_sums_plan("qgcm_hip_xforc_sums", nxpa, nyta, ndxr, ny1, nyaooc, nranks, slab_lo, slab_hi, out);
+}
+
+extern "C" int qgcm_hip_xforc_slab_sums(qgcm_hip_handle oc, qgcm_hip_handle atm, int rank, int nranks, const int *slab_lo,
+                                        const int *slab_hi) {
+  const char *who = "qgcm_hip_xforc_slab_sums";
+  if (xf_ready(oc, atm, who, true)) return 1;
+  auto &x = atm->xf;
+  const QgGeom &go = oc->g;
+  if (x.bands.on) QG_FAIL("%s: this pair runs the banded atmosphere side (qgcm_hip_xforc_slab_bands): the modes exclude each other", who);
+  if (x.udiff.on) QG_FAIL("%s: this pair gathers the surface pressure (qgcm_hip_xforc_slab_udiff): the modes exclude each other", who);
+  if (nranks < 1 || nranks > 65535) QG_FAIL("%s: nranks = %d outside 1..65535", who, nranks);
+  if (rank < 0 || rank >= nranks) QG_FAIL("%s: rank %d outside 0..%d", who, rank, nranks - 1);
+  std::vector<qgcm_hip_xforc_sum> plan(nranks);
+  if (xf_sums_plan(who, atm->g.nx, atm->g.ny - 1, x.prm.ndxr, x.prm.ny1, x.prm.nyaooc, nranks, slab_lo, slab_hi, plan.data())) return 1;
+  if (slab_lo[rank] != go.joff + go.jlo || slab_hi[rank] != go.joff + go.jhi)
+    QG_FAIL("%s: rank %d of the plan owns ocean rows %d..%d, this slab owns %d..%d", who, rank, slab_lo[rank], slab_hi[rank],
+            go.joff + go.jlo, go.joff + go.jhi);
+  if (go.jhi - go.jlo + 1 + 2 * XFE_ROWS > 65535) QG_FAIL("%s: %d owned rows exceed the assemble's launch limit", who, go.jhi - go.jlo + 1);
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  const int ld = round_up(go.nx, 16);
+  const size_t n = (size_t)ld * go.nyg;
+  if (x.udiff.pom.grow(n, "xforc's assembled surface pressure")) return 1;
+  HIPCHECK(hipMemsetAsync(x.udiff.pom, 0, n * sizeof(double), atm->stream));
+  x.udiff.ld = ld;
+  x.sums.plan = plan[rank];
+  x.sums.rank = rank;
+  x.sums.nranks = nranks;
+  const char *e = getenv("QGCM_HIP_XF_POISON");
+  x.sums.poison = e && atoi(e) == 1;
+  x.sums.fresh = false;
+  x.sums.on = true;
+  return 0;
+}
+
+static int xf_sums_ready(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const char *who) {
+  if (xf_ready(oc, atm, who, true)) return 1;
+  if (!atm->xf.sums.on) QG_FAIL("%s: qgcm_hip_xforc_slab_sums has not been called for this pair", who);
+  return 0;
+}
+
+static void xf_edge_msg_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfEdgeMsg &M) {
+  const QgGeom &go = oc->g;
+  const auto &x = atm->xf;
+  memset(&M, 0, sizeof(M));
+  M.nxpo = go.nx; M.nypo = go.nyg; M.ldo = go.ldx; M.lda = x.udiff.ld;
+  M.g0 = go.joff + go.jlo; M.g1 = go.joff + go.jhi; M.jlo = go.jlo;
+  M.rank = x.sums.rank; M.nranks = x.sums.nranks;
+  M.stride = xfe_len(go.nx);
+  M.pom = oc->p[oc->ip ^ 1]; // layer 1 of the lagged pressure, as xf_fill's P.pom
+}
+
+extern "C" int qgcm_hip_xforc_slab_edge_len(qgcm_hip_handle oc, qgcm_hip_handle atm, long *n) {
+  const char *who = "qgcm_hip_xforc_slab_edge_len";
+  if (!n) QG_FAIL("%s: null argument", who);
+  if (xf_sums_ready(oc, atm, who)) return 1;
+  *n = xfe_len(oc->g.nx);
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_slab_edge_pack(qgcm_hip_handle oc, qgcm_hip_handle atm, double *send_dev) {
+  const char *who = "qgcm_hip_xforc_slab_edge_pack";
+  if (xf_sums_ready(oc, atm, who)) return 1;
+  if (!send_dev) QG_FAIL("%s: send_dev must hold qgcm_hip_xforc_slab_edge_len doubles", who);
+  auto &x = atm->xf;
+  hipStream_t st = atm->stream;
+  QgXfEdgeMsg M;
+  xf_edge_msg_fill(oc, atm, M);
+  M.msg = send_dev;
+  HIPCHECK(hipEventRecord(x.ev_oc, oc->stream)); // after everything queued on the slab's stream, as the part waits
+  HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
+  HIPCHECK(qg_launch_xf_edge_pack(st, M));
+  return 0;
+}
+
+extern "C" int qgcm_hip_xforc_slab_edge_assemble(qgcm_hip_handle oc, qgcm_hip_handle atm, const double *gath_dev, int nranks) {
+  const char *who = "qgcm_hip_xforc_slab_edge_assemble";
+  if (xf_sums_ready(oc, atm, who)) return 1;
+  auto &x = atm->xf;
+  if (!gath_dev) QG_FAIL("%s: gath_dev must hold nranks messages of qgcm_hip_xforc_slab_edge_len doubles", who);
+  if (nranks != x.sums.nranks)
+    QG_FAIL("%s: nranks = %d, the sums were set up for %d ranks (qgcm_hip_xforc_slab_sums)", who, nranks, x.sums.nranks);
+  hipStream_t st = atm->stream;
+  QgXfEdgeMsg M;
+  xf_edge_msg_fill(oc, atm, M);
+  M.gath = gath_dev;
+  M.all = x.udiff.pom;
+  HIPCHECK(hipEventRecord(x.ev_oc, oc->stream)); // (the owned rows are read from the slab's pressure once more)
+  HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
+  if (x.sums.poison) // a row the rank does not hold shows in the stress above it
+    HIPCHECK(hipMemsetAsync(x.udiff.pom, 0xFF, (size_t)x.udiff.ld * M.nypo * sizeof(double), st));
+  HIPCHECK(qg_launch_xf_edge_assemble(st, M));
+  x.sums.fresh = true;
+  return 0;
+}
+
+static void xf_sum_msg_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const QgXfParams &P, QgXfSumMsg &B) {
+  const auto &s = atm->xf.sums.plan;
+  memset(&B, 0, sizeof(B));
+  B.nxpa = P.nxpa; B.nxta = P.nxta; B.nypa = P.nypa; B.nyta = P.nyta; B.lda = P.lda; B.ldta = P.ldta; B.ldf = P.ldf; B.ldtf = P.ldtf;
+  B.ndxr = P.ndxr; B.ndxodd = P.ndxodd; B.nijwid = P.nijwid; B.nxtaor = P.nxtaor; B.nytaor = P.nytaor; B.nypaor = P.nypaor;
+  B.f0 = s.f0; B.f1 = s.f1; B.t0 = s.t0; B.t1 = s.t1; B.a0 = s.a0; B.a1 = s.a1; B.nrow = s.nrow;
+  B.own = oc->g.cyc ? s.own : (s.own & 3); // (a box ocean has no line sums)
+  B.txf = P.txf; B.tyf = P.tyf; B.wf = P.wf;
+  B.tauxa = P.tauxa; B.tauya = P.tauya; B.uekat = P.uekat; B.vekat = P.vekat; B.wekpa = P.wekpa;
+  B.uvekfc = P.uvekfc;
+  B.sca = atm->sc;
+  B.sco = oc->g.cyc ? oc->sc : nullptr;
+}
+
 // the pack's / the scatter's view of the replica
 static void xf_band_msg_fill(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, QgXfBandMsg &B) {
   const auto &m = atm->atmon;
@@ -3567,6 +3771,11 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   if (x.udiff.on && !x.udiff.fresh)
     QG_FAIL("%s: the surface pressure has not been assembled for this call (qgcm_hip_xforc_slab_pom_pack, the all-gather, qgcm_hip_xforc_slab_pom_assemble)", who);
   x.udiff.fresh = false;
+  const bool sums = x.sums.on;
+  if (sums && !send_dev) QG_FAIL("%s: the sums are set up: send_dev must hold qgcm_hip_xforc_slab_msg_len doubles", who);
+  if (sums && !x.sums.fresh)
+    QG_FAIL("%s: the edge rows have not been assembled for this call (qgcm_hip_xforc_slab_edge_pack, the all-gather, qgcm_hip_xforc_slab_edge_assemble)", who);
+  x.sums.fresh = false;
   hipStream_t st = atm->stream;
   QgXfParams P;
   xf_fill(oc, atm, P);
@@ -3577,7 +3786,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   // entries.  P, the ocean side's (k_xf_tauo): the slab's local rows at the slab's offset.
   QgXfParams PA = P;
   PA.sco = nullptr;
-  if (x.udiff.on) {
+  if (x.udiff.on || sums) { // (sums: rows g0 - 4 .. g1 + 4 of the array hold the basin's bits)
     PA.udiff = 1;
     PA.nypo = go.nyg;
     PA.ldo = x.udiff.ld;
@@ -3599,6 +3808,16 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
     }
     for (int s = 0; s < bp.nseg; ++s) HIPCHECK(qg_launch_xf_win_fine(st, PA, bp.c0[s], bp.c1[s]));
     HIPCHECK(qg_launch_xf_win_band(st, PA, bp.a0, bp.a1, bp.t0, bp.t1, bp.own & 3));
+  } else if (sums) { // the fine stress on the plan's one window, wektaor on the owned T rows
+    const auto &sp = x.sums.plan;
+    if (x.sums.poison) {
+      const size_t nf = (size_t)x.ldf * P.nypaor * sizeof(double);
+      HIPCHECK(hipMemsetAsync(x.txf, 0xFF, nf, st));
+      HIPCHECK(hipMemsetAsync(x.tyf, 0xFF, nf, st));
+      HIPCHECK(hipMemsetAsync(x.wf, 0xFF, (size_t)x.ldtf * P.nytaor * sizeof(double), st));
+    }
+    HIPCHECK(qg_launch_xf_win_fine(st, PA, sp.c0, sp.c1));
+    HIPCHECK(qg_launch_xf_sums_wektaor(st, PA, sp.t0, sp.t1));
   } else
     launch_xf_atmos(PA, st);
   hipLaunchKernelGGL(k_xf_tauo, dim3((P.nxpo + XF_NT - 1) / XF_NT, P.nypo), b, 0, st, P);
@@ -3614,7 +3833,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
   S.cyc = go.cyc; S.iocoff = P.iocoff; S.jocoff = P.jocoff - go.joff;
   S.txf = x.txf; S.wekto = mo.wekto; S.wekpo = oc->wekpo; S.sco = oc->sc;
   S.raoro = P.raoro; S.dxo = P.dxo;
-  S.lines = banded ? (x.bands.plan.own >> 2) & 3 : 3; // banded: only the sums whose ocean rows this slab holds
+  S.lines = banded ? (x.bands.plan.own >> 2) & 3 : sums ? (x.sums.plan.own >> 2) & 3 : 3; // only the sums whose ocean rows this slab holds
   HIPCHECK(qg_launch_xf_slab_ocean(st, S));
   if (oc->oml.on) { // the mixed layer's own forcing buffers (same pitches)
     auto &o = oc->oml;
@@ -3628,6 +3847,11 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
     xf_band_msg_fill(oc, atm, B);
     B.msg = send_dev;
     HIPCHECK(qg_launch_xf_band_pack(st, B));
+  } else if (sums) { // the line sums this rank owns, its samples and its partial sums -> the message's momentum block
+    QgXfSumMsg B;
+    xf_sum_msg_fill(oc, atm, PA, B);
+    B.msg = send_dev;
+    HIPCHECK(qg_launch_xf_sums_part(st, PA, B));
   } else
     hipLaunchKernelGGL(k_xf_lines, dim3(1), b, 0, st, P);
   HIPCHECK(hipGetLastError());
@@ -3637,7 +3861,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
     xf_heat_fill(oc, atm, H.h);
     H.joff = go.joff; H.nytl = go.ny - 1;
     H.jT0 = go.jlo; H.jT1 = (go.jhi + go.joff == go.nyg) ? go.jhi - 1 : go.jhi; // T row j lies between p rows j and j+1
-    H.msg = send_dev + (banded ? x.bands.plan.mom_len : 0);
+    H.msg = send_dev + (banded ? x.bands.plan.mom_len : sums ? x.sums.plan.mom_len : 0);
     HIPCHECK(qg_launch_xf_heat_oc_slab(st, H));
   }
   return xf_slab_handover(oc, atm);
@@ -3647,13 +3871,28 @@ extern "C" int qgcm_hip_xforc_slab_combine(qgcm_hip_handle oc, qgcm_hip_handle a
   const char *who = "qgcm_hip_xforc_slab_combine";
   if (xf_ready(oc, atm, who, true)) return 1;
   auto &x = atm->xf;
-  const bool banded = x.bands.on;
-  if (!x.heat.on && !banded) QG_FAIL("%s: qgcm_hip_xforc_heat_slab_init has not been called (the momentum half has nothing to combine)", who);
+  const bool banded = x.bands.on, sums = x.sums.on;
+  if (!x.heat.on && !banded && !sums) QG_FAIL("%s: qgcm_hip_xforc_heat_slab_init has not been called (the momentum half has nothing to combine)", who);
   if (!gath_dev || nranks < 1) QG_FAIL("%s: null buffer or nranks = %d", who, nranks);
   if (banded && nranks != x.bands.nranks)
     QG_FAIL("%s: nranks = %d, the bands were set up for %d ranks (qgcm_hip_xforc_slab_bands)", who, nranks, x.bands.nranks);
+  if (sums && nranks != x.sums.nranks)
+    QG_FAIL("%s: nranks = %d, the sums were set up for %d ranks (qgcm_hip_xforc_slab_sums)", who, nranks, x.sums.nranks);
   hipStream_t st = atm->stream;
-  const long mom = banded ? x.bands.plan.mom_len : 0;
+  const long mom = banded ? x.bands.plan.mom_len : sums ? x.sums.plan.mom_len : 0;
+  if (sums) { // samples and line sums from their owners, the cut sums added in rank order; then wekta on the whole grid
+    QgXfParams P;
+    xf_fill(oc, atm, P);
+    QgXfSumMsg B;
+    xf_sum_msg_fill(oc, atm, P, B);
+    B.gath = gath_dev;
+    B.nranks = nranks;
+    B.stride = qgcm_hip_xforc_slab_msg_len(atm);
+    HIPCHECK(qg_launch_xf_sums_combine(st, B));
+    hipLaunchKernelGGL(k_xf_wekta, dim3((P.nxta + XF_NT - 1) / XF_NT, P.nyta), dim3(XF_NT), 0, st, P);
+    HIPCHECK(hipGetLastError());
+    if (!x.heat.on) return xf_slab_handover(oc, atm);
+  }
   if (banded) { // every rank's rows and line sums into this replica (a copy: no sum changes its order)
     QgXfBandMsg B;
     xf_band_msg_fill(oc, atm, B);

@@ -102,6 +102,12 @@ class XforcBand(C.Structure):
                 ("t0", C.c_int), ("t1", C.c_int), ("nrow", C.c_int), ("mom_len", C.c_int)]
 
 
+class XforcSum(C.Structure):
+    """struct qgcm_hip_xforc_sum (include/qgcm_hip.h): one rank's part of the ownership plan of the owner-computed sums."""
+    _fields_ = [(n, C.c_int) for n in ("g0", "g1", "f0", "f1", "t0", "t1", "w0", "w1", "c0", "c1", "u0", "u1", "a0", "a1", "own",
+                                       "nrow", "mom_len", "pad")]
+
+
 class XforcSstParams(C.Structure):
     """struct qgcm_hip_xforc_sst_params (include/qgcm_hip.h)."""
     _fields_ = [(n, C.c_double) for n in ("xlamda", "D0up", "Dmup", "Dmdown", "Adown11", "Bmup", "B1down", "Cmup",
@@ -157,6 +163,8 @@ SYMBOLS = [
     "qgcm_hip_xforc_slab_init", "qgcm_hip_xforc_heat_slab_init", "qgcm_hip_xforc_slab_msg_len", "qgcm_hip_xforc_slab_part",
     "qgcm_hip_xforc_slab_combine", "qgcm_hip_xforc_slab_get", "qgcm_hip_xforc_bands", "qgcm_hip_xforc_slab_bands",
     "qgcm_hip_xforc_slab_udiff", "qgcm_hip_xforc_slab_pom_len", "qgcm_hip_xforc_slab_pom_pack", "qgcm_hip_xforc_slab_pom_assemble",
+    "qgcm_hip_xforc_sums", "qgcm_hip_xforc_slab_sums", "qgcm_hip_xforc_slab_edge_len", "qgcm_hip_xforc_slab_edge_pack",
+    "qgcm_hip_xforc_slab_edge_assemble",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
     "qgcm_hip_debug_live_allocs",
 ]
@@ -339,6 +347,12 @@ def load_library():
         L.qgcm_hip_xforc_slab_pom_len.argtypes = [vp, vp, C.POINTER(C.c_long)]
         L.qgcm_hip_xforc_slab_pom_pack.argtypes = [vp, vp, vp]
         L.qgcm_hip_xforc_slab_pom_assemble.argtypes = [vp, vp, vp, C.c_int]
+    if hasattr(L, "qgcm_hip_xforc_sums"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_xforc_sums.argtypes = [C.c_int] * 6 + [ip, ip, C.POINTER(XforcSum)]
+        L.qgcm_hip_xforc_slab_sums.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip]
+        L.qgcm_hip_xforc_slab_edge_len.argtypes = [vp, vp, C.POINTER(C.c_long)]
+        L.qgcm_hip_xforc_slab_edge_pack.argtypes = [vp, vp, vp]
+        L.qgcm_hip_xforc_slab_edge_assemble.argtypes = [vp, vp, vp, C.c_int]
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),
@@ -422,6 +436,30 @@ def xforc_bands(nxpa, nyta, ndxr, ny1, nyaooc, slab_rows):
     check(load_library().qgcm_hip_xforc_bands(int(nxpa), int(nyta), int(ndxr), int(ny1), int(nyaooc), n, lo, hi, out))
     return [dict(band=(b.a0, b.a1), cells=[(b.c0[s], b.c1[s]) for s in range(b.nseg)],
                  fine=[(b.f0[s], b.f1[s]) for s in range(b.nseg)], trows=(b.t0, b.t1),
+                 own=tuple(nm for k, nm in enumerate(XFORC_BAND_LINES) if b.own >> k & 1), nrow=b.nrow, mom_len=b.mom_len)
+            for b in out]
+
+
+XFORC_SUM_HEADER = 8    # XFS_HDR (k_xforc_slab.h): f0, f1, a0, own and the four line sums in front of the fields
+XFORC_EDGE_HEADER = 8   # XFE_HDR: g0, g1, nxpo and zeros in front of the 4 + 4 edge rows
+XFORC_EDGE_ROWS = 4     # XFE_ROWS: the owned rows sent from each end of a slab
+XFORC_SUM_FIELDS = ("tauxa", "tauya", "vekat", "uekat", "wekpa")  # (uekat, wekpa: partial sums), (nrow, nxpa) each
+
+
+def xforc_sums(nxpa, nyta, ndxr, ny1, nyaooc, slab_rows):
+    """The ownership plan of the owner-computed sums (qgcm_hip_xforc_sums; host code, no device) for
+    len(slab_rows) ranks; slab_rows[r] = (g0, g1): the global ocean p rows rank r's slab owns.  One dict per rank: rows
+    (g0, g1); fine (f0, f1) - the owned fine p rows; trows (t0, t1) - the owned fine T rows; window (w0, w1) - the fine
+    rows whose stress the rank holds correct; cells (c0, c1) - the cell rows k_xf_fine runs on; coarse (u0, u1) - the
+    rows of u1at / v1at; arows (a0, a1) - the coarse rows whose sample, uekat line or wekpa box meets the owned rows; own -
+    the names of the line sums the rank forms; nrow - rows per field in the message; mom_len - doubles of its momentum
+    block."""
+    n = len(slab_rows)
+    lo, hi = (C.c_int * max(n, 1))(*[int(a) for a, _ in slab_rows]), (C.c_int * max(n, 1))(*[int(b) for _, b in slab_rows])
+    out = (XforcSum * max(n, 1))()
+    check(load_library().qgcm_hip_xforc_sums(int(nxpa), int(nyta), int(ndxr), int(ny1), int(nyaooc), n, lo, hi, out))
+    return [dict(rows=(b.g0, b.g1), fine=(b.f0, b.f1), trows=(b.t0, b.t1), window=(b.w0, b.w1), cells=(b.c0, b.c1),
+                 coarse=(b.u0, b.u1), arows=(b.a0, b.a1),
                  own=tuple(nm for k, nm in enumerate(XFORC_BAND_LINES) if b.own >> k & 1), nrow=b.nrow, mom_len=b.mom_len)
             for b in out]
 

@@ -360,6 +360,29 @@ class HipSlab(Handle):
         """All ranks' rows (rank-major) -> the assembled pom(:,:,1) the next xforc_part reads."""
         check(self.L.qgcm_hip_xforc_slab_pom_assemble(self.h, atm.h, self._ptr(gath), int(self.nranks)))
 
+    # tau_udiff without that gather (DESIGN 6r): the stress above the owned rows, rank-ordered partial sums
+    def xforc_sums_init(self, atm, rows):
+        """Switch this pair to the owner-computed sums (qgcm_hip_xforc_slab_sums), after xforc_init with tau_udiff = 0:
+        rows[r] = (g0, g1), the global ocean p rows rank r owns; the library keeps this rank's part of lib.xforc_sums."""
+        n = len(rows)
+        lo, hi = (C.c_int * n)(*[int(a) for a, _ in rows]), (C.c_int * n)(*[int(b) for _, b in rows])
+        check(self.L.qgcm_hip_xforc_slab_sums(self.h, atm.h, int(self.rank), n, lo, hi))
+
+    def xforc_edge_len(self, atm):
+        n = C.c_long(0)
+        check(self.L.qgcm_hip_xforc_slab_edge_len(self.h, atm.h, C.byref(n)))
+        return int(n.value)
+
+    def xforc_edge_pack(self, atm, send):
+        """The first 4 and the last 4 owned rows of pom(:,:,1) behind their header -> send (device buffer of
+        xforc_edge_len doubles); asynchronous, on the atmosphere's stream."""
+        check(self.L.qgcm_hip_xforc_slab_edge_pack(self.h, atm.h, self._ptr(send)))
+
+    def xforc_edge_assemble(self, atm, gath):
+        """The slab's owned rows and the neighbours' edge rows (gath: all ranks' messages, rank-major) -> rows
+        g0 - 4 .. g1 + 4 of the array the next xforc_part reads."""
+        check(self.L.qgcm_hip_xforc_slab_edge_assemble(self.h, atm.h, self._ptr(gath), int(self.nranks)))
+
     def xforc_msg_len(self, atm):
         return self.L.qgcm_hip_xforc_slab_msg_len(atm.h)
 
@@ -850,7 +873,8 @@ class SlabOcean:
 
     # coupled runs: xforc under a replicated atmosphere, collective ---------------------------------------
     def xforc_setup(self, atmospheres, cdat=1.3e-3, rhoat=1.0, rhooc=1.0e3, hmat=1000.0, hmoc=100.0, tau_udiff=False,
-                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None, bands=False, udiff_gather=False):
+                    tables=None, ndxr=None, nxaooc=None, nyaooc=None, nx1=None, ny1=None, bands=False, udiff_gather=False,
+                    udiff_sums=False):
         """As model.xforc_setup (ndxr, nxaooc, nyaooc default to the ocean configuration's), for the slabs: `atmospheres` holds one whole-domain AtmosModel per local slab, on that
         slab's device - replicas of one atmosphere, which every rank steps redundantly and which stay bitwise identical.
         tau_udiff = True is refused by the library (the fine stress above the sea needs every slab's pom on every rank);
@@ -859,9 +883,17 @@ class SlabOcean:
         momentum output is bitwise the whole-domain xforc's with tau_udiff = True.  Pass only udiff_gather.
         bands = True: every rank runs the atmosphere side only on the fine rows its band of atmosphere rows
         (lib.xforc_bands, kept as self.xforc_plan) and its slab need; the bands travel in front of the heat block in the
-        one all-gather, so xforc() then always gathers and combines.  The results are bitwise the default's."""
-        from .lib import XforcParams, xforc_bands
+        one all-gather, so xforc() then always gathers and combines.  The results are bitwise the default's.
+        udiff_sums = True is the shear term without that gather: every rank forms the fine stress above the
+        ocean rows it owns, from its own pressure and the 4 rows beyond each seam (a small all-gather of 8 + 8 * nxpo
+        doubles per rank), and the ranks exchange rank-ordered partial sums of uekat and wekpa; xforc() then always runs
+        two all-gathers.  A line or box of the sums that no seam cuts keeps the whole-domain bits, a cut one differs by
+        rounding.  It excludes bands, udiff_gather and tau_udiff; the plan (lib.xforc_sums) is kept as self.xforc_plan."""
+        from .lib import XforcParams, xforc_bands, xforc_sums
         S, oc = self.slabs, self.cfg
+        if udiff_sums and (bands or udiff_gather or tau_udiff):
+            raise ValueError("xforc_setup: udiff_sums = True excludes bands, udiff_gather and tau_udiff (it implies the shear "
+                             "term and splits the atmosphere side by the slabs' own rows)")
         if udiff_gather and tau_udiff:
             raise ValueError("xforc_setup: pass only udiff_gather = True (tau_udiff = True alone asks the library for the "
                              "shear term without the gather, which it refuses)")
@@ -890,8 +922,9 @@ class SlabOcean:
         self.atmos = list(atmospheres)
         self._xf_bufs = None
         self._xf_pom_bufs = None
+        self._xf_edge_bufs = None
         self.xforc_plan = None
-        if bands or udiff_gather:
+        if bands or udiff_gather or udiff_sums:
             rows = partition(oc.nypo, self.P)
             for x in S:  # (slabs cut otherwise than partition(): their own rows)
                 rows[x.rank] = (x.g0, x.g1)
@@ -902,6 +935,14 @@ class SlabOcean:
             n = [x.xforc_pom_len(a) for x, a in zip(S, atmospheres)]
             self._xf_pom_bufs = ([x.new_buffer(m) for x, m in zip(S, n)], [x.new_buffer(m * self.P) for x, m in zip(S, n)])
             self._settle()
+        if udiff_sums:
+            owned_rows_tile(rows, oc.nypo)
+            self.xforc_plan = xforc_sums(acfg.nxpa, acfg.nyta, ndxr, p.ny1, p.nyaooc, rows)
+            for x, a in zip(S, atmospheres):
+                x.xforc_sums_init(a, rows)
+            n = [x.xforc_edge_len(a) for x, a in zip(S, atmospheres)]
+            self._xf_edge_bufs = ([x.new_buffer(m) for x, m in zip(S, n)], [x.new_buffer(m * self.P) for x, m in zip(S, n)])
+            self._xf_size_bufs()
         if bands:
             self.xforc_plan = xforc_bands(acfg.nxpa, acfg.nyta, ndxr, p.ny1, p.nyaooc, rows)
             for x, a in zip(S, atmospheres):
@@ -931,9 +972,22 @@ class SlabOcean:
         half, one all-gather of the partial cell sums (4*nxaooc*nyaooc doubles per rank) and the rank-ordered combine.
         Banded (xforc_setup(bands=True)): always one all-gather - the ranks' bands, then the heat block - and the combine.
         With the shear term (xforc_setup(udiff_gather=True)) one more all-gather in front: pack, the gather of the pressure
-        rows (8 + nrow * nxpo doubles per rank), assemble on every local rank; then the sequence above, unchanged."""
+        rows (8 + nrow * nxpo doubles per rank), assemble on every local rank; then the sequence above, unchanged.
+        With the owner-computed sums (xforc_setup(udiff_sums=True)) always two all-gathers: edge pack, the gather of the
+        edge rows (8 + 8 * nxpo doubles per rank), edge assemble, part, the gather of the messages, combine."""
         S, A = self.slabs, self.atmos
         self._join()
+        if getattr(self, "_xf_edge_bufs", None):  # DESIGN 6r: the 4 rows beyond each seam onto the neighbours first
+            esend, egath = self._xf_edge_bufs
+            for i, (x, a) in enumerate(zip(S, A)):
+                x.xforc_edge_pack(a, esend[i])
+            for a in A:
+                a.sync()
+            self._comm(self.comm.all_gather, egath, esend)
+            for x in S:
+                x.sync()
+            for i, (x, a) in enumerate(zip(S, A)):
+                x.xforc_edge_assemble(a, egath[i])
         if getattr(self, "_xf_pom_bufs", None):  # the shear term (DESIGN 6q): the basin's pom(:,:,1) onto every rank first
             psend, pgath = self._xf_pom_bufs
             for i, (x, a) in enumerate(zip(S, A)):
