@@ -768,7 +768,9 @@ int qgcm_hip_cfl_combine(qgcm_hip_handle h, const double *gath_dev, int nranks, 
  *   (dxo), dxo from the ocean's (dxa / ndxr without one).  The five weight tables are host pointers laid out as
  *   MODULE xfosubs holds them, (16, 0:ndxr, 0:ndxr) Fortran order (qgcm_hip.hostinit.bcuini restates bcuini).  Refuses,
  *   naming the reason and changing nothing: a y-slab handle, an ocean whose T grid is not nxaooc*ndxr x nyaooc*ndxr,
- *   an ocean that does not lie inside the atmosphere, a cyclic ocean with nxaooc != nxta, tau_udiff without an ocean.
+ *   an ocean that does not lie inside the atmosphere, a cyclic ocean with nxaooc != nxta, tau_udiff without an ocean,
+ *   ndxr outside 1..128, a fine grid whose padded arrays pass 2^31 - 1 elements.  Above ndxr = 64 the box average wekpa
+ *   is formed by k_xf_wekpa_stage (QGCM_HIP_XF_WEKPA_STAGE=0/1, read here, forces either form at any ndxr).
  *   Allocates the scratch (two fine p-grid stress arrays and the fine T-grid Ekman velocity; u1ator / v1ator are never
  *   stored) and, where they do not exist yet, the buffers of qgcm_hip_set_atm_monitor_fields (wekta, tauxa, tauya,
  *   uekat, vekat) and of qgcm_hip_set_monitor_fields (tauxo, tauyo, wekto).

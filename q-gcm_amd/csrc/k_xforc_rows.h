@@ -12,6 +12,8 @@
 #include "qgcm_dev.h"
 
 #define XF_NT 256
+// the box average of ndxr above this is k_xf_wekpa_stage's (k_xf_wekpa_stage.h)
+#define XF_WEKPA_STAGE_ABOVE 64
 
 struct QgXfParams {
   int ndxr, nxta, nyta, nxpa, nypa, nxtaor, nytaor, nxpaor, nypaor;

@@ -38,8 +38,9 @@ hipError_t qg_launch_xf_win_fine(hipStream_t st, const QgXfParams &P, int c0, in
 
 // the band a0 .. a1 of atmosphere p rows from the fine stress: tauxa, tauya, vekat on a0 .. min(a1 + 1, nypa) (wekta at
 // a1 reads vekat at a1 + 1), uekat and wekta on a0 .. min(a1, nyta), wektaor on the fine T rows t0 .. t1 that wekpa on
-// a0 .. a1 reads; lines: the atmosphere's line sums to form (QgXfWin)
-hipError_t qg_launch_xf_win_band(hipStream_t st, const QgXfParams &P, int a0, int a1, int t0, int t1, int lines) {
+// a0 .. a1 reads; lines: the atmosphere's line sums to form (QgXfWin); stage: wekpa by k_xf_wekpa_stage
+hipError_t qg_launch_xf_wekpa_stage(hipStream_t st, const QgXfParams &P, int ja0, int nrow); // k_xf_wekpa_stage.hip
+hipError_t qg_launch_xf_win_band(hipStream_t st, const QgXfParams &P, int a0, int a1, int t0, int t1, int lines, bool stage) {
   const dim3 b(XF_NT);
   const int ae = a1 + 1 < P.nypa ? a1 + 1 : P.nypa, au = a1 < P.nyta ? a1 : P.nyta;
   QgXfWin W = {a0, au, lines};
@@ -48,7 +49,11 @@ hipError_t qg_launch_xf_win_band(hipStream_t st, const QgXfParams &P, int a0, in
   W.j0 = t0;
   hipLaunchKernelGGL(k_xf_wektaor_win, dim3((P.nxtaor + XF_NT - 1) / XF_NT, t1 - t0 + 1), b, 0, st, P, W);
   W.j0 = a0;
-  hipLaunchKernelGGL(k_xf_wekpa_win, dim3((P.nxpa + 63) / 64, a1 - a0 + 1), dim3(64), 0, st, P, W);
+  if (stage) {
+    const hipError_t e = qg_launch_xf_wekpa_stage(st, P, a0, a1 - a0 + 1);
+    if (e != hipSuccess) return e;
+  } else
+    hipLaunchKernelGGL(k_xf_wekpa_win, dim3((P.nxpa + 63) / 64, a1 - a0 + 1), dim3(64), 0, st, P, W);
   if (lines) hipLaunchKernelGGL(k_xf_lines_win, dim3(1), b, 0, st, P, W);
   return hipGetLastError();
 }

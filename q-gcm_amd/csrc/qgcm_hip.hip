@@ -390,6 +390,7 @@ struct qgcm_hip_ctx {
     qgcm_hip_xforc_params prm;
     qgcm_hip_ctx *oc = nullptr; // not owned
     int ldf = 0, ldtf = 0;
+    bool wekpa_stage = false; // wekpa by k_xf_wekpa_stage: ndxr above 64, or QGCM_HIP_XF_WEKPA_STAGE=1
     QgDbl u1at, v1at, txf, tyf, wf, tab;
     hipEvent_t ev_oc = nullptr, ev_atm = nullptr;
     // heat half (qgcm_hip_xforc_heat_init): constants, the two fsprim tables, bilint's index / weight tables, the
@@ -2924,6 +2925,10 @@ static void xf_off(qgcm_hip_ctx *a) {
   x.sst.on = false;  // (likewise qgcm_hip_xforc_sst_init)
 }
 
+// k_xf_wekpa_stage and its launch live in k_xf_wekpa_stage.hip, a device code object of its own as k_tend_rows.hip
+hipError_t qg_setup_xf_wekpa_stage(int ndxr);
+hipError_t qg_launch_xf_wekpa_stage(hipStream_t st, const QgXfParams &P, int ja0, int nrow);
+
 // slab: the set-up of qgcm_hip_xforc_slab_init - the ocean handle holds rows of a basin of g.nyg rows
 static int xf_init(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const qgcm_hip_xforc_params *p, const char *who, bool slab) {
   if (!atm || !p) QG_FAIL("%s: null atmosphere handle or parameters", who);
@@ -2941,10 +2946,14 @@ static int xf_init(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const qgcm_hip_xforc_par
     QG_FAIL("%s: tau_udiff is not available with a y-slab ocean (the fine stress above the sea would need every slab's pom on every rank)", who);
   if (!p->stbbb || !p->stbus || !p->stbvs || !p->stbun || !p->stbvn) QG_FAIL("%s: a weight table is NULL", who);
   const int ndxr = p->ndxr, nxta = atm->g.nxt, nyta = atm->g.ny - 1;
-  if (ndxr < 1 || ndxr > 64) QG_FAIL("%s: ndxr = %d outside 1..64", who, ndxr);
+  if (ndxr < 1 || ndxr > 128) QG_FAIL("%s: ndxr = %d outside 1..128", who, ndxr);
   if (nxta < 4 || nyta < 2) QG_FAIL("%s: atmosphere of %d x %d cells is too small", who, nxta, nyta);
   if ((double)nxta * ndxr >= 1.0e6 || (long)nyta * ndxr >= 65535)
     QG_FAIL("%s: the fine grid %d*%d x %d*%d exceeds the kernels' launch limits", who, nxta, ndxr, nyta, ndxr);
+  // (the kernels index the fine arrays with int products of a row and a pitch where the row is not cast: DESIGN 6s)
+  if ((double)round_up(nxta * ndxr + 1, 16) * (double)(nyta * ndxr + 1) > 2147483647.0)
+    QG_FAIL("%s: the fine grid's padded arrays of %d x %d elements pass 2^31 - 1 elements", who, round_up(nxta * ndxr + 1, 16),
+            nyta * ndxr + 1);
   if (!(p->hmat > 0.0) || !(p->cdat > 0.0)) QG_FAIL("%s: need hmat > 0 and cdat > 0", who);
   if (oc) {
     const int nxto = oc->g.nxt, nyto = (slab ? oc->g.nyg : oc->g.ny) - 1;
@@ -3000,6 +3009,13 @@ static int xf_init(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const qgcm_hip_xforc_par
         mo.tauy.ensure((size_t)go.ldx * go.ny, "an ocean monitor field") ||
         mo.wekto.ensure((size_t)mo.ldt * (go.ny - 1), "an ocean monitor field"))
       return 1;
+  }
+  {
+    // the form of the box average: k_xf_wekpa up to ndxr = 64, k_xf_wekpa_stage above; QGCM_HIP_XF_WEKPA_STAGE
+    // = 0 / 1 forces the plain / the staged form at any ndxr
+    const char *e = getenv("QGCM_HIP_XF_WEKPA_STAGE");
+    x.wekpa_stage = e && *e ? atoi(e) != 0 : ndxr > XF_WEKPA_STAGE_ABOVE;
+    if (x.wekpa_stage) HIPCHECK(qg_setup_xf_wekpa_stage(ndxr));
   }
   if (!x.ev_oc) HIPCHECK(hipEventCreateWithFlags(&x.ev_oc, hipEventDisableTiming));
   if (!x.ev_atm) HIPCHECK(hipEventCreateWithFlags(&x.ev_atm, hipEventDisableTiming));
@@ -3078,14 +3094,17 @@ static int launch_xf_heat_sst(qgcm_hip_ctx *atm);
 hipError_t qg_launch_xf_heat_sst(hipStream_t st, const QgXfHeatParams &P);
 
 // the atmosphere side of the momentum half up to wekpa: the fine stress and every product that depends on pam only
-static void launch_xf_atmos(const QgXfParams &P, hipStream_t st) {
+// (stage: wekpa by k_xf_wekpa_stage)
+static hipError_t launch_xf_atmos(const QgXfParams &P, hipStream_t st, bool stage) {
   const dim3 b(XF_NT);
   hipLaunchKernelGGL(k_xf_coarse, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
   hipLaunchKernelGGL(k_xf_fine, dim3((P.nxta + XF_CX - 1) / XF_CX, P.nyta), b, 0, st, P);
   hipLaunchKernelGGL(k_xf_atm, dim3((P.nxpa + XF_NT - 1) / XF_NT, P.nypa), b, 0, st, P);
   hipLaunchKernelGGL(k_xf_wekta, dim3((P.nxta + XF_NT - 1) / XF_NT, P.nyta), b, 0, st, P);
   hipLaunchKernelGGL(k_xf_wektaor, dim3((P.nxtaor + XF_NT - 1) / XF_NT, P.nytaor), b, 0, st, P);
+  if (stage) return qg_launch_xf_wekpa_stage(st, P, 1, P.nypa);
   hipLaunchKernelGGL(k_xf_wekpa, dim3((P.nxpa + 63) / 64, P.nypa), dim3(64), 0, st, P);
+  return hipGetLastError();
 }
 
 // One `call xforc` on the atmosphere's stream, ordered against the ocean's stream by two events: the momentum half and,
@@ -3101,7 +3120,7 @@ extern "C" int qgcm_hip_xforc(qgcm_hip_handle oc, qgcm_hip_handle atm) {
     HIPCHECK(hipStreamWaitEvent(st, x.ev_oc, 0));
   }
   const dim3 b(XF_NT);
-  launch_xf_atmos(P, st);
+  HIPCHECK(launch_xf_atmos(P, st, x.wekpa_stage));
   if (oc) {
     const QgGeom &go = oc->g;
     auto &mo = oc->mon;
@@ -3338,7 +3357,7 @@ hipError_t qg_launch_xf_heat_oc_slab(hipStream_t st, const QgXfHeatSlabParams &S
 hipError_t qg_launch_xf_heat_combine(hipStream_t st, const double *gath, int nranks, int ncell, long stride, long off, double *cell,
                                      double *part);
 hipError_t qg_launch_xf_win_fine(hipStream_t st, const QgXfParams &P, int c0, int c1);
-hipError_t qg_launch_xf_win_band(hipStream_t st, const QgXfParams &P, int a0, int a1, int t0, int t1, int lines);
+hipError_t qg_launch_xf_win_band(hipStream_t st, const QgXfParams &P, int a0, int a1, int t0, int t1, int lines, bool stage);
 hipError_t qg_launch_xf_band_pack(hipStream_t st, const QgXfBandMsg &B);
 hipError_t qg_launch_xf_band_scatter(hipStream_t st, const QgXfBandMsg &B);
 
@@ -3807,7 +3826,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
       HIPCHECK(hipMemsetAsync(x.wf, 0xFF, (size_t)x.ldtf * P.nytaor * sizeof(double), st));
     }
     for (int s = 0; s < bp.nseg; ++s) HIPCHECK(qg_launch_xf_win_fine(st, PA, bp.c0[s], bp.c1[s]));
-    HIPCHECK(qg_launch_xf_win_band(st, PA, bp.a0, bp.a1, bp.t0, bp.t1, bp.own & 3));
+    HIPCHECK(qg_launch_xf_win_band(st, PA, bp.a0, bp.a1, bp.t0, bp.t1, bp.own & 3, x.wekpa_stage));
   } else if (sums) { // the fine stress on the plan's one window, wektaor on the owned T rows
     const auto &sp = x.sums.plan;
     if (x.sums.poison) {
@@ -3819,7 +3838,7 @@ extern "C" int qgcm_hip_xforc_slab_part(qgcm_hip_handle oc, qgcm_hip_handle atm,
     HIPCHECK(qg_launch_xf_win_fine(st, PA, sp.c0, sp.c1));
     HIPCHECK(qg_launch_xf_sums_wektaor(st, PA, sp.t0, sp.t1));
   } else
-    launch_xf_atmos(PA, st);
+    HIPCHECK(launch_xf_atmos(PA, st, x.wekpa_stage));
   hipLaunchKernelGGL(k_xf_tauo, dim3((P.nxpo + XF_NT - 1) / XF_NT, P.nypo), b, 0, st, P);
   QgWekParams W;
   memset(&W, 0, sizeof(W));

@@ -303,6 +303,8 @@ PRESETS["socn1"] = _socn_scaled("socn1", 576, 216, 72, 40, 1.0e3)
 PRESETS["cpl_tiny"] = OceanConfig("cpl_tiny", 16, 12, 4, 3, 12, 3, dxo=1.0e4, dta=360.0, ah4oc=(3.2e10,) * 3, **_NATL)
 PRESETS["cpl_small"] = OceanConfig("cpl_small", 32, 20, 6, 5, 16, 3, dxo=5.0e3, **_NATL)
 PRESETS["cpl_natl5"] = OceanConfig("cpl_natl5", 384, 96, 60, 60, 16, 3, dxo=5.0e3, **_NATL)
+# cpl_natl1 = the natl1 ocean (4801 x 4801, ndxr = 80) as a coupled preset: the same 385 x 97 x 3 atmosphere at 80 km
+PRESETS["cpl_natl1"] = replace(PRESETS["natl1"], name="cpl_natl1")
 
 
 # cpl_tiny with two, four and five atmospheric layers (oracle/ref_binding.CONFIGS "cpl_tiny_a<nla>"): the same ocean

@@ -440,6 +440,16 @@ def xforc_bands(nxpa, nyta, ndxr, ny1, nyaooc, slab_rows):
             for b in out]
 
 
+XFORC_NDXR_MAX = 128    # the widest refinement xforc's set-ups accept
+XFORC_WEKPA_STAGE_ABOVE = 64  # XF_WEKPA_STAGE_ABOVE (k_xforc_rows.h): above it the box average is k_xf_wekpa_stage's
+
+
+def xforc_wekpa_stage_points():
+    """XFW_G (k_xf_wekpa_stage.h): the zonally adjacent atmosphere p points a workgroup of the staged box
+    average owns (qgcm_hip_xf_wekpa_stage_points; host code, no device)."""
+    return int(load_library().qgcm_hip_xf_wekpa_stage_points())
+
+
 XFORC_SUM_HEADER = 8    # XFS_HDR (k_xforc_slab.h): f0, f1, a0, own and the four line sums in front of the fields (DESIGN 6r)
 XFORC_EDGE_HEADER = 8   # XFE_HDR: g0, g1, nxpo and zeros in front of the 4 + 4 edge rows
 XFORC_EDGE_ROWS = 4     # XFE_ROWS: the owned rows sent from each end of a slab
