@@ -43,7 +43,8 @@ extern "C" {
 /* 2: qgcm_hip_params.atmos + the atmosphere entry points
  * 3: qgcm_hip_get_monitors (required by the Fortran shim), qgcm_hip_prepare_steps, qgcm_hip_stream_mix_bandwidth,
  *    qgcm_hip_set_sponge, qgcm_hip_set_cu_range; halo rows of qgcm_hip_slab_steps default to neighbour send/recv
- *    (entry points added since keep the number - there is no minor version: qgcm_hip_row_split / _row_plan the latest) */
+ *    (entry points added since keep the number - there is no minor version: qgcm_hip_slab_coupled_plan / _init / _steps
+ *    the latest) */
 #define QGCM_HIP_ABI_VERSION 3
 
 typedef struct qgcm_hip_ctx *qgcm_hip_handle;
@@ -355,6 +356,70 @@ int qgcm_hip_comm_set_overlap(qgcm_hip_handle h, int on);
 /* measurement aid (collective): the step's exchanges back to back, microseconds each:
  * us[0] summaries all-gather, us[1] halo rows as all-gather, us[2] halo rows as send/recv */
 int qgcm_hip_comm_probe(qgcm_hip_handle h, int reps, double *us);
+
+/* ---- the coupled window on a y-slab ocean, driven by the library ------------------------------------------
+ * What SlabOcean.coupled_steps issues call by call - xforc in the mode set up with its one or two all-gathers, the
+ * mixed layer's two halves, the four stages of the slab step, the replica's atmospheric steps - issued from here: every
+ * collective an RCCL call on the slab's stream, every dependency between the slab's stream and the replica's an event,
+ * no host wait.  The order exists once, as a plan of (code, doubles per rank) pairs:
+ *
+ * qgcm_hip_slab_coupled_plan(sw, nranks, nt0, n, nstr, xforc, cap, codes, lens, count): host code without a handle or a
+ *   device, a pure function of its arguments.  sw: the switches and the message lengths of the run.  Writes the window's
+ *   operations in order into codes[] / lens[] (cap entries each; NULL with cap = 0 only counts) and their number into
+ *   *count; lens[k] is the doubles per rank an exchange moves (HALO_GATHER: both edge messages, HALO_P2P: one of them)
+ *   and 0 for everything else.  The plan does not depend on the rank: ranks that pass the same arguments issue the same
+ *   collectives with the same lengths in the same order.  Refuses a bad step range, nranks < 1, an exchange of the
+ *   chosen mode with a length < 1, udiff_sums together with bands or udiff_gather, and cap < *count (after setting it).
+ * qgcm_hip_slab_coupled_init(oc, atm): after qgcm_hip_comm_init(oc), qgcm_hip_xforc_slab_init(oc, atm) and whichever of
+ *   _heat_slab_init, _slab_bands, _slab_udiff, _slab_sums, qgcm_hip_oml_init, qgcm_hip_aml_init the run uses.  Allocates
+ *   the exchange buffers of xforc's all-gathers (qgcm_hip_xforc_slab_msg_len, _pom_len, _edge_len doubles per rank; the
+ *   step's and the mixed layer's are the communicator's), owned by the slab's handle and released by qgcm_hip_destroy.
+ *   Refuses, by name: handles on different devices, an atmosphere not set up for this slab, a missing communicator, a
+ *   handle with qgcm_hip_comm_set_overlap on (the window runs the plain stage order).  Call it again after a set-up call
+ *   changed the mode; qgcm_hip_slab_coupled_steps refuses when the lengths no longer match.
+ * qgcm_hip_slab_coupled_steps(oc, atm, nt0, n, nstr, xforc): collective.  n atmospheric steps nt = nt0 .. on the replica
+ *   with one slab ocean step before every nt with mod(nt, nstr) == 1 (src/q-gcm.F:1220-1268; nstr = 1 never steps the
+ *   ocean), xforc != 0: xforc before each ocean step.  It executes qgcm_hip_slab_coupled_plan's sequence for the handles'
+ *   own switches and lengths; the leapfrog averaging follows every 25th ocean step, the atmosphere's every 100th of its
+ *   own, as in qgcm_hip_steps.  Asynchronous like qgcm_hip_slab_steps: it returns with the work queued.  The replica's
+ *   steps wait only for what xforc left them, so they may run beside the ocean step; the results do not depend on it. */
+enum {
+  QGCM_HIP_CPL_XF_EDGE_PACK = 1,    /* qgcm_hip_xforc_slab_edge_pack */
+  QGCM_HIP_CPL_GATHER_EDGE = 2,     /* all-gather, qgcm_hip_xforc_slab_edge_len doubles per rank */
+  QGCM_HIP_CPL_XF_EDGE_ASSEMBLE = 3,
+  QGCM_HIP_CPL_XF_POM_PACK = 4,     /* qgcm_hip_xforc_slab_pom_pack */
+  QGCM_HIP_CPL_GATHER_POM = 5,      /* all-gather, qgcm_hip_xforc_slab_pom_len */
+  QGCM_HIP_CPL_XF_POM_ASSEMBLE = 6,
+  QGCM_HIP_CPL_XF_PART = 7,         /* qgcm_hip_xforc_slab_part */
+  QGCM_HIP_CPL_GATHER_XFORC = 8,    /* all-gather, qgcm_hip_xforc_slab_msg_len */
+  QGCM_HIP_CPL_XF_COMBINE = 9,      /* qgcm_hip_xforc_slab_combine */
+  QGCM_HIP_CPL_OML_A = 10,          /* slab stage 10 */
+  QGCM_HIP_CPL_GATHER_OML = 11,     /* all-gather, qgcm_hip_oml_msg_len */
+  QGCM_HIP_CPL_OML_B = 12,          /* slab stage 11 */
+  QGCM_HIP_CPL_STAGE1 = 13,         /* slab stage 1 */
+  QGCM_HIP_CPL_GATHER_SUMMARY = 14, /* all-gather, qgcm_hip_thomas_msg_len */
+  QGCM_HIP_CPL_STAGE2 = 15,         /* slab stage 2 */
+  QGCM_HIP_CPL_HALO_GATHER = 16,    /* edge rows as one all-gather, 2 * qgcm_hip_halo_msg_len */
+  QGCM_HIP_CPL_HALO_P2P = 17,       /* edge rows as grouped send/recv with the neighbours, qgcm_hip_halo_msg_len each */
+  QGCM_HIP_CPL_STAGE3 = 18,         /* slab stage 3 */
+  QGCM_HIP_CPL_STAGE3_AVG = 19,     /* slab stage 3 with the leapfrog averaging */
+  QGCM_HIP_CPL_ATM_STEP = 20,       /* one atmospheric step on the replica: (aml;) qgastep; atinvq; atqzbd */
+  QGCM_HIP_CPL_NCODES = 21
+};
+typedef struct qgcm_hip_slab_coupled_switches {
+  int oml;          /* the ocean mixed layer steps on the slabs (qgcm_hip_oml_init) */
+  int heat;         /* xforc's heat half (qgcm_hip_xforc_heat_slab_init) */
+  int bands;        /* qgcm_hip_xforc_slab_bands */
+  int udiff_gather; /* qgcm_hip_xforc_slab_udiff */
+  int udiff_sums;   /* qgcm_hip_xforc_slab_sums */
+  int halo_p2p;     /* qgcm_hip_comm_set_halo_p2p */
+  long xforc_len, pom_len, edge_len, oml_len, summary_len, halo_len; /* doubles per rank, the calls named above */
+} qgcm_hip_slab_coupled_switches;
+const char *qgcm_hip_slab_coupled_code_name(int code);
+int qgcm_hip_slab_coupled_plan(const qgcm_hip_slab_coupled_switches *sw, int nranks, int nt0, int n, int nstr, int xforc,
+                               long cap, int *codes, long *lens, long *count);
+int qgcm_hip_slab_coupled_init(qgcm_hip_handle oc_slab, qgcm_hip_handle atm);
+int qgcm_hip_slab_coupled_steps(qgcm_hip_handle oc_slab, qgcm_hip_handle atm, int nt0, int n, int nstr, int xforc);
 
 /* ---- ocean mixed layer -----------------------------------
  * `call oml` (src/q-gcm.F:1232; body src/omlsubs.F:47-236 + omladf 244-763) on the device: steps the

@@ -437,6 +437,7 @@ struct qgcm_hip_ctx {
   } xf;
   // y-slab exchanges over RCCL (qgcm_hip_comm_init); slab-step graphs keyed like `graphs`
   QgSlabComm *sc_comm = nullptr;
+  QgSlabCoupled *sc_cpl = nullptr; // the coupled window's exchange buffers (qgcm_hip_slab_coupled_init)
   std::map<long long, hipGraphExec_t> slab_graphs;
   bool slab_graph_mode = false; // QGCM_HIP_SLAB_GRAPH=1: capture 50 distributed steps (collectives included)
   size_t dst_lds;
@@ -450,6 +451,7 @@ struct qgcm_hip_ctx {
     for (auto &kv : graphs) hipGraphExecDestroy(kv.second.exec);
     for (auto &kv : slab_graphs) hipGraphExecDestroy(kv.second);
     delete sc_comm;
+    delete sc_cpl;
     if (xf.ev_oc) hipEventDestroy(xf.ev_oc);
     if (xf.ev_atm) hipEventDestroy(xf.ev_atm);
     if (ev0) hipEventDestroy(ev0);
@@ -4542,6 +4544,38 @@ extern "C" int qgcm_hip_comm_probe(qgcm_hip_handle c, int reps, double *us) {
   return 0;
 }
 
+// The edge rows of a step to both neighbours, on stream xs: grouped send/recv with the neighbours alone (p2p; the
+// receive areas are the neighbour's slots of h_gath, as with the all-gather) or one all-gather of every rank's pair.
+static int slab_halo_exchange(QgSlabComm *m, bool p2p, hipStream_t xs) {
+  const int r = m->rank, P = m->nranks;
+  const size_t n = m->halo_len;
+  if (!p2p) {
+    NCCLCHECK(m->api, m->api->AllGather(m->h_send, m->h_gath, 2 * n, ncclDouble, m->comm, xs));
+    return 0;
+  }
+  double *to_lo = m->h_send, *to_hi = m->h_send + n;
+  double *rl = m->h_gath + (size_t)(2 * (r > 0 ? r - 1 : 0) + 1) * n, *rh = m->h_gath + (size_t)(2 * (r < P - 1 ? r + 1 : 0)) * n;
+  NCCLCHECK(m->api, m->api->GroupStart());
+  if (r > 0) {
+    NCCLCHECK(m->api, m->api->Send(to_lo, n, ncclDouble, r - 1, m->comm, xs));
+    NCCLCHECK(m->api, m->api->Recv(rl, n, ncclDouble, r - 1, m->comm, xs));
+  }
+  if (r < P - 1) {
+    NCCLCHECK(m->api, m->api->Send(to_hi, n, ncclDouble, r + 1, m->comm, xs));
+    NCCLCHECK(m->api, m->api->Recv(rh, n, ncclDouble, r + 1, m->comm, xs));
+  }
+  NCCLCHECK(m->api, m->api->GroupEnd());
+  return 0;
+}
+
+// where the neighbours' edge rows lie after either exchange (nullptr towards a wall)
+static void slab_halo_from(QgSlabComm *m, const double *&from_lo, const double *&from_hi) {
+  const int r = m->rank, P = m->nranks;
+  const size_t n = m->halo_len;
+  from_lo = r > 0 ? m->h_gath + (size_t)(2 * (r - 1) + 1) * n : nullptr; // what the lower neighbour sent upwards
+  from_hi = r < P - 1 ? m->h_gath + (size_t)(2 * (r + 1)) * n : nullptr; // what the upper neighbour sent downwards
+}
+
 // one distributed ocean step: the communication-free pieces above (what SlabOcean.step runs through
 // qgcm_hip_slab_stage) and two exchanges, all ordered on c->stream; no host synchronisation
 // next_follows: step s + 1 is executed by the same qgcm_hip_slab_steps call / captured block (its tendency may be started);
@@ -4587,24 +4621,8 @@ static int slab_step_issue(qgcm_hip_ctx *c, int s, bool next_follows, bool &fork
   }
   const double *from_lo = nullptr, *from_hi = nullptr;
   if (P > 1 || ov) { // (one rank, overlapped: the all-gather is a local copy - it keeps the one-GPU tests on this path)
-    if (m->halo_p2p && P > 1) {
-      // neighbours only; receive areas are the neighbour's slots of h_gath, as with the all-gather
-      double *rl = m->h_gath + (size_t)(2 * (r > 0 ? r - 1 : 0) + 1) * n, *rh = m->h_gath + (size_t)(2 * (r < P - 1 ? r + 1 : 0)) * n;
-      NCCLCHECK(m->api, m->api->GroupStart());
-      if (r > 0) {
-        NCCLCHECK(m->api, m->api->Send(to_lo, n, ncclDouble, r - 1, m->comm, xs));
-        NCCLCHECK(m->api, m->api->Recv(rl, n, ncclDouble, r - 1, m->comm, xs));
-      }
-      if (r < P - 1) {
-        NCCLCHECK(m->api, m->api->Send(to_hi, n, ncclDouble, r + 1, m->comm, xs));
-        NCCLCHECK(m->api, m->api->Recv(rh, n, ncclDouble, r + 1, m->comm, xs));
-      }
-      NCCLCHECK(m->api, m->api->GroupEnd());
-    } else {
-      NCCLCHECK(m->api, m->api->AllGather(m->h_send, m->h_gath, 2 * n, ncclDouble, m->comm, xs));
-    }
-    if (r > 0) from_lo = m->h_gath + (size_t)(2 * (r - 1) + 1) * n;  // what the lower neighbour sent upwards
-    if (r < P - 1) from_hi = m->h_gath + (size_t)(2 * (r + 1)) * n;  // what the upper neighbour sent downwards
+    if (slab_halo_exchange(m, m->halo_p2p && P > 1, xs)) return 1;
+    slab_halo_from(m, from_lo, from_hi);
   }
   // 3. edge rows in, behind the exchange on its stream (+ leapfrog averaging: never overlapped, xs is the handle's stream)
   if ((P > 1 || avg) && slab_halo_in(c, from_lo, from_hi, P, avg, xs)) return 1;
@@ -4684,6 +4702,267 @@ extern "C" int qgcm_hip_slab_steps(qgcm_hip_handle c, int s0, int n) {
   for (; n > 0; --n, ++s)
     if (slab_step(c, s, n > 1)) return 1;
   return slab_join(c);
+}
+
+// ---------------------------------------------------------------------------
+// the coupled window on a y-slab ocean: SlabOcean.coupled_steps with the library as the driver
+// ---------------------------------------------------------------------------
+static const char *const kCplNames[QGCM_HIP_CPL_NCODES] = {
+    "", "xforc_edge_pack", "gather_edge", "xforc_edge_assemble", "xforc_pom_pack", "gather_pom", "xforc_pom_assemble",
+    "xforc_part", "gather_xforc", "xforc_combine", "oml_a", "gather_oml", "oml_b", "stage1", "gather_summary", "stage2",
+    "halo_gather", "halo_p2p", "stage3", "stage3_avg", "atm_step"};
+
+extern "C" const char *qgcm_hip_slab_coupled_code_name(int code) {
+  return code > 0 && code < QGCM_HIP_CPL_NCODES ? kCplNames[code] : "";
+}
+
+// The window's order, once: host code without a handle.  `emit` receives every operation in turn.
+template <class Emit>
+static int cpl_plan(const char *who, const qgcm_hip_slab_coupled_switches &sw, int nranks, int nt0, int n, int nstr, int xforc,
+                    Emit emit) {
+  if (nt0 < 1 || n < 0 || nstr < 1) QG_FAIL("%s: bad step range", who);
+  if (nranks < 1) QG_FAIL("%s: nranks = %d, need at least one rank", who, nranks);
+  if (sw.udiff_sums && (sw.bands || sw.udiff_gather))
+    QG_FAIL("%s: udiff_sums excludes bands and udiff_gather (qgcm_hip_xforc_slab_sums)", who);
+  const bool xf_gather = sw.heat || sw.bands || sw.udiff_sums; // (replicated, momentum half alone: nothing to exchange)
+  struct { bool used; long len; const char *what; } need[] = {
+      {xforc && xf_gather, sw.xforc_len, "xforc_len"},    {xforc && sw.udiff_gather, sw.pom_len, "pom_len"},
+      {xforc && sw.udiff_sums, sw.edge_len, "edge_len"}, {sw.oml != 0, sw.oml_len, "oml_len"},
+      {true, sw.summary_len, "summary_len"},             {nranks > 1, sw.halo_len, "halo_len"}};
+  for (const auto &q : need)
+    if (q.used && q.len < 1) QG_FAIL("%s: %s = %ld, but the window exchanges that message", who, q.what, q.len);
+  const int ocean_avg_period = 25; // the leapfrog averaging of an ocean handle (qgcm_hip_ctx::avg_period)
+  const int end = nt0 + n;         // one past the last step
+  for (int nt = nt0; nt < end;) {
+    int next = end;
+    if (nstr > 1) { // (nstr = 1 never steps the ocean in the reference)
+      if (nt % nstr == 1) {
+        if (xforc) { // `call xforc`, in the mode set up (SlabOcean.xforc)
+          if (sw.udiff_sums) { // the 4 rows beyond each seam onto the neighbours first
+            emit(QGCM_HIP_CPL_XF_EDGE_PACK, 0L);
+            emit(QGCM_HIP_CPL_GATHER_EDGE, sw.edge_len);
+            emit(QGCM_HIP_CPL_XF_EDGE_ASSEMBLE, 0L);
+          }
+          if (sw.udiff_gather) { // the basin's pom(:,:,1) onto every rank first
+            emit(QGCM_HIP_CPL_XF_POM_PACK, 0L);
+            emit(QGCM_HIP_CPL_GATHER_POM, sw.pom_len);
+            emit(QGCM_HIP_CPL_XF_POM_ASSEMBLE, 0L);
+          }
+          emit(QGCM_HIP_CPL_XF_PART, 0L);
+          if (xf_gather) {
+            emit(QGCM_HIP_CPL_GATHER_XFORC, sw.xforc_len);
+            emit(QGCM_HIP_CPL_XF_COMBINE, 0L);
+          }
+        }
+        const int s = (nt - 1) / nstr + 1; // the ocean step
+        if (sw.oml) {                      // `call oml` precedes qgostep (src/q-gcm.F:1232)
+          emit(QGCM_HIP_CPL_OML_A, 0L);
+          emit(QGCM_HIP_CPL_GATHER_OML, sw.oml_len);
+          emit(QGCM_HIP_CPL_OML_B, 0L);
+        }
+        emit(QGCM_HIP_CPL_STAGE1, 0L);
+        emit(QGCM_HIP_CPL_GATHER_SUMMARY, sw.summary_len);
+        emit(QGCM_HIP_CPL_STAGE2, 0L);
+        if (nranks > 1) {
+          if (sw.halo_p2p) emit(QGCM_HIP_CPL_HALO_P2P, sw.halo_len);
+          else emit(QGCM_HIP_CPL_HALO_GATHER, 2 * sw.halo_len);
+        }
+        const bool avg = (s - 1) % ocean_avg_period == 0;
+        if (nranks > 1 || avg) emit(avg ? QGCM_HIP_CPL_STAGE3_AVG : QGCM_HIP_CPL_STAGE3, 0L);
+      }
+      const int nn = nt + (nstr - (nt - 1) % nstr); // the next nt with mod(nt,nstr) == 1
+      if (nn < end) next = nn;
+    }
+    for (; nt < next; ++nt) emit(QGCM_HIP_CPL_ATM_STEP, 0L);
+  }
+  return 0;
+}
+
+extern "C" int qgcm_hip_slab_coupled_plan(const qgcm_hip_slab_coupled_switches *sw, int nranks, int nt0, int n, int nstr, int xforc,
+                                          long cap, int *codes, long *lens, long *count) {
+  const char *who = "qgcm_hip_slab_coupled_plan";
+  if (!sw || !count || cap < 0 || (cap > 0 && (!codes || !lens))) QG_FAIL("%s: null argument", who);
+  long k = 0;
+  if (cpl_plan(who, *sw, nranks, nt0, n, nstr, xforc, [&](int code, long len) {
+        if (k < cap) {
+          codes[k] = code;
+          lens[k] = len;
+        }
+        ++k;
+      }))
+    return 1;
+  *count = k;
+  if (cap > 0 && k > cap) QG_FAIL("%s: the plan has %ld operations, the arrays hold %ld", who, k, cap);
+  return 0;
+}
+
+// what both handle calls check first
+static int cpl_ready(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const char *who) {
+  if (!oc || !atm) QG_FAIL("%s: null handle", who);
+  if (check_ready(oc, who)) return 1;
+  if (oc->g.atm) QG_FAIL("%s: the first handle must be a y-slab ocean", who);
+  if (oc->device != atm->device)
+    QG_FAIL("%s: the slab lives on device %d, the atmosphere on device %d: a replica steps beside its slab", who, oc->device, atm->device);
+  if (xf_ready(oc, atm, who, true)) return 1;
+  if (!oc->sc_comm) QG_FAIL("%s: no communicator (qgcm_hip_comm_init)", who);
+  if (oc->sc_comm->overlap)
+    QG_FAIL("%s: the overlapped halo exchange is switched on (qgcm_hip_comm_set_overlap): the window runs the plain stage order", who);
+  return 0;
+}
+
+// the switches and message lengths of a pair as it is set up now
+static int cpl_switches(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, qgcm_hip_slab_coupled_switches &sw) {
+  const auto &x = atm->xf;
+  memset(&sw, 0, sizeof(sw));
+  sw.oml = oc->oml.on;
+  sw.heat = x.heat.on;
+  sw.bands = x.bands.on;
+  sw.udiff_gather = x.udiff.on;
+  sw.udiff_sums = x.sums.on;
+  sw.halo_p2p = oc->sc_comm->halo_p2p;
+  sw.xforc_len = qgcm_hip_xforc_slab_msg_len(atm);
+  if (x.udiff.on && qgcm_hip_xforc_slab_pom_len(oc, atm, &sw.pom_len)) return 1;
+  if (x.sums.on && qgcm_hip_xforc_slab_edge_len(oc, atm, &sw.edge_len)) return 1;
+  sw.oml_len = qgcm_hip_oml_msg_len(oc);
+  sw.summary_len = qgcm_hip_thomas_msg_len(oc);
+  sw.halo_len = qgcm_hip_halo_msg_len(oc);
+  return 0;
+}
+
+extern "C" int qgcm_hip_slab_coupled_init(qgcm_hip_handle oc, qgcm_hip_handle atm) {
+  const char *who = "qgcm_hip_slab_coupled_init";
+  if (cpl_ready(oc, atm, who)) return 1;
+  qgcm_hip_slab_coupled_switches sw;
+  if (cpl_switches(oc, atm, sw)) return 1;
+  const int P = oc->sc_comm->nranks;
+  HIPCHECK(hipSetDevice(oc->device));
+  // a window queued earlier may still read the buffers this call replaces, on either stream
+  HIPCHECK(hipStreamSynchronize(oc->stream));
+  HIPCHECK(hipStreamSynchronize(atm->stream));
+  delete oc->sc_cpl;
+  oc->sc_cpl = nullptr;
+  std::unique_ptr<QgSlabCoupled> k(new QgSlabCoupled); // (a failure below leaves the handle without the buffers)
+  k->atm = atm;
+  k->xf_len = sw.xforc_len;
+  k->pom_len = sw.pom_len;
+  k->edge_len = sw.edge_len;
+  struct { QgDbl *buf; size_t n; } bufs[] = {{&k->xf_send, (size_t)k->xf_len},     {&k->xf_gath, (size_t)k->xf_len * P},
+                                             {&k->pom_send, (size_t)k->pom_len},   {&k->pom_gath, (size_t)k->pom_len * P},
+                                             {&k->edge_send, (size_t)k->edge_len}, {&k->edge_gath, (size_t)k->edge_len * P}};
+  for (auto &b : bufs) {
+    if (!b.n) continue;
+    if (b.buf->alloc(b.n, "an exchange buffer of the coupled window")) return 1;
+    HIPCHECK(hipMemsetAsync(*b.buf, 0, b.n * sizeof(double), oc->stream));
+  }
+  HIPCHECK(hipEventCreateWithFlags(&k->ev_msg, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&k->ev_gath, hipEventDisableTiming));
+  HIPCHECK(hipStreamSynchronize(oc->stream));
+  oc->sc_cpl = k.release(); // owned by the handle from here on (~qgcm_hip_ctx)
+  return 0;
+}
+
+// One all-gather of the window's xforc messages.  The message was written on the replica's stream and the gathered
+// messages are read there; the collective runs on the slab's stream, like every other one of this communicator.
+static int cpl_gather(qgcm_hip_ctx *oc, qgcm_hip_ctx *atm, const double *send, double *gath, long len) {
+  QgSlabComm *m = oc->sc_comm;
+  QgSlabCoupled *k = oc->sc_cpl;
+  HIPCHECK(hipEventRecord(k->ev_msg, atm->stream));
+  HIPCHECK(hipStreamWaitEvent(oc->stream, k->ev_msg, 0));
+  NCCLCHECK(m->api, m->api->AllGather(send, gath, (size_t)len, ncclDouble, m->comm, oc->stream));
+  HIPCHECK(hipEventRecord(k->ev_gath, oc->stream));
+  HIPCHECK(hipStreamWaitEvent(atm->stream, k->ev_gath, 0));
+  return 0;
+}
+
+extern "C" int qgcm_hip_slab_coupled_steps(qgcm_hip_handle oc, qgcm_hip_handle atm, int nt0, int n, int nstr, int xforc) {
+  const char *who = "qgcm_hip_slab_coupled_steps";
+  if (cpl_ready(oc, atm, who)) return 1;
+  QgSlabCoupled *k = oc->sc_cpl;
+  if (!k || k->atm != atm) QG_FAIL("%s: qgcm_hip_slab_coupled_init has not been called for this slab and atmosphere", who);
+  if (!oc->homog_set) QG_FAIL("%s: homogeneous solutions not set", who);
+  QgSlabComm *m = oc->sc_comm;
+  const int r = m->rank, P = m->nranks;
+  qgcm_hip_slab_coupled_switches sw;
+  if (cpl_switches(oc, atm, sw)) return 1;
+  if (sw.xforc_len != k->xf_len || sw.pom_len != k->pom_len || sw.edge_len != k->edge_len)
+    QG_FAIL("%s: xforc's set-up changed after qgcm_hip_slab_coupled_init (message sizes differ): call it again", who);
+  if ((long)m->th_len != sw.summary_len || (long)m->halo_len != sw.halo_len)
+    QG_FAIL("%s: the mixed layer was switched on after qgcm_hip_comm_init (message sizes differ)", who);
+  std::vector<std::pair<int, long>> plan;
+  if (cpl_plan(who, sw, P, nt0, n, nstr, xforc, [&](int code, long len) { plan.push_back({code, len}); })) return 1;
+  const size_t nh = m->halo_len;
+  double *to_lo = r > 0 ? (double *)m->h_send : nullptr, *to_hi = r < P - 1 ? m->h_send + nh : nullptr;
+  const double *from_lo = nullptr, *from_hi = nullptr;
+  if (P > 1) slab_halo_from(m, from_lo, from_hi);
+  int nt = nt0; // the next atmospheric step
+  for (size_t i = 0; i < plan.size(); ++i) {
+    const long len = plan[i].second;
+    switch (plan[i].first) {
+      case QGCM_HIP_CPL_XF_EDGE_PACK:
+        if (qgcm_hip_xforc_slab_edge_pack(oc, atm, k->edge_send)) return 1;
+        break;
+      case QGCM_HIP_CPL_GATHER_EDGE:
+        if (cpl_gather(oc, atm, k->edge_send, k->edge_gath, len)) return 1;
+        break;
+      case QGCM_HIP_CPL_XF_EDGE_ASSEMBLE:
+        if (qgcm_hip_xforc_slab_edge_assemble(oc, atm, k->edge_gath, P)) return 1;
+        break;
+      case QGCM_HIP_CPL_XF_POM_PACK:
+        if (qgcm_hip_xforc_slab_pom_pack(oc, atm, k->pom_send)) return 1;
+        break;
+      case QGCM_HIP_CPL_GATHER_POM:
+        if (cpl_gather(oc, atm, k->pom_send, k->pom_gath, len)) return 1;
+        break;
+      case QGCM_HIP_CPL_XF_POM_ASSEMBLE:
+        if (qgcm_hip_xforc_slab_pom_assemble(oc, atm, k->pom_gath, P)) return 1;
+        break;
+      case QGCM_HIP_CPL_XF_PART: // (ends with the hand-over: the slab's stream waits for it)
+        if (qgcm_hip_xforc_slab_part(oc, atm, k->xf_len ? (double *)k->xf_send : nullptr)) return 1;
+        break;
+      case QGCM_HIP_CPL_GATHER_XFORC:
+        if (cpl_gather(oc, atm, k->xf_send, k->xf_gath, len)) return 1;
+        break;
+      case QGCM_HIP_CPL_XF_COMBINE: // (likewise)
+        if (qgcm_hip_xforc_slab_combine(oc, atm, k->xf_gath, P)) return 1;
+        break;
+      case QGCM_HIP_CPL_OML_A:
+        if (launch_oml_a(oc, m->oml_send)) return 1;
+        break;
+      case QGCM_HIP_CPL_GATHER_OML:
+        NCCLCHECK(m->api, m->api->AllGather(m->oml_send, m->oml_gath, (size_t)len, ncclDouble, m->comm, oc->stream));
+        break;
+      case QGCM_HIP_CPL_OML_B:
+        oc->oml_gath = m->oml_gath; // (slab_solve_unpack reads it)
+        if (launch_oml_b(oc, m->oml_gath, P)) return 1;
+        break;
+      case QGCM_HIP_CPL_STAGE1:
+        if (slab_tend(oc, TEND_ALL, m->th_send) || slab_forward(oc, m->th_send, r, P)) return 1;
+        break;
+      case QGCM_HIP_CPL_GATHER_SUMMARY:
+        NCCLCHECK(m->api, m->api->AllGather(m->th_send, m->th_gath, (size_t)len, ncclDouble, m->comm, oc->stream));
+        break;
+      case QGCM_HIP_CPL_STAGE2:
+        if (slab_solve_unpack(oc, m->th_gath, to_lo, to_hi, r, P)) return 1;
+        break;
+      case QGCM_HIP_CPL_HALO_GATHER:
+      case QGCM_HIP_CPL_HALO_P2P:
+        if (slab_halo_exchange(m, plan[i].first == QGCM_HIP_CPL_HALO_P2P, oc->stream)) return 1;
+        break;
+      case QGCM_HIP_CPL_STAGE3:
+      case QGCM_HIP_CPL_STAGE3_AVG:
+        if (slab_halo_in(oc, from_lo, from_hi, P, plan[i].first == QGCM_HIP_CPL_STAGE3_AVG)) return 1;
+        break;
+      case QGCM_HIP_CPL_ATM_STEP: { // a run of them is one call: the replica's own graphs, averaging and schedules
+        int cnt = 1;
+        while (i + 1 < plan.size() && plan[i + 1].first == QGCM_HIP_CPL_ATM_STEP) ++i, ++cnt;
+        if (steps_impl(atm, nt, cnt, false)) return 1;
+        nt += cnt;
+        break;
+      }
+      default: QG_FAIL("%s: internal: the plan holds the unknown operation %d", who, plan[i].first);
+    }
+  }
+  return 0;
 }
 
 // Instantiate (and upload) the graphs qgcm_hip_steps(s0, n) will replay, without running anything: a caller that

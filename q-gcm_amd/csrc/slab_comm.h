@@ -80,3 +80,20 @@ struct QgSlabComm {
     if (cstream) hipStreamDestroy(cstream);
   }
 };
+
+// the coupled window driven by the library (qgcm_hip_slab_coupled_init): the exchange buffers of xforc's
+// all-gathers for one slab and its replica of the atmosphere, and the two events that carry a message from the
+// replica's stream to the slab's (where every collective runs) and the gathered messages back
+struct QgSlabCoupled {
+  qgcm_hip_ctx *atm = nullptr; // not owned
+  long xf_len = 0, pom_len = 0, edge_len = 0; // doubles per rank (0: the mode set up has no such exchange)
+  QgDbl xf_send, xf_gath, pom_send, pom_gath, edge_send, edge_gath;
+  hipEvent_t ev_msg = nullptr, ev_gath = nullptr;
+
+  QgSlabCoupled() = default;
+  QgSlabCoupled(const QgSlabCoupled &) = delete;
+  ~QgSlabCoupled() {
+    if (ev_msg) hipEventDestroy(ev_msg);
+    if (ev_gath) hipEventDestroy(ev_gath);
+  }
+};

@@ -304,6 +304,18 @@ module qgcm_hip_iface
       type(c_ptr), value :: h
       integer(c_int), value :: s0, n
     end function
+    ! the coupled window on a y-slab ocean with the library as the driver (DESIGN 6t): after qgcm_hip_comm_init and the
+    ! xforc set-ups of the slab and its replica of the atmosphere; collective, asynchronous
+    integer(c_int) function qgcm_hip_slab_coupled_init(oc, atm) bind(C, name='qgcm_hip_slab_coupled_init')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: oc, atm
+    end function
+    integer(c_int) function qgcm_hip_slab_coupled_steps(oc, atm, nt0, n, nstr, xforc) &
+        bind(C, name='qgcm_hip_slab_coupled_steps')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: oc, atm
+      integer(c_int), value :: nt0, n, nstr, xforc
+    end function
     ! own exchanges: the right-hand-side independent part of the slab summaries, once after set_grid
     integer(c_int) function qgcm_hip_thomas_const_len(h) bind(C, name='qgcm_hip_thomas_const_len')
       import :: c_ptr, c_int

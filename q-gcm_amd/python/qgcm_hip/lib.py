@@ -116,6 +116,12 @@ class XforcSstParams(C.Structure):
         ("dxo", C.c_double), ("dyo", C.c_double), ("sst", C.POINTER(C.c_double))]
 
 
+class SlabCoupledSwitches(C.Structure):
+    """struct qgcm_hip_slab_coupled_switches (include/qgcm_hip.h): the switches and message lengths of a coupled window."""
+    _fields_ = [(n, C.c_int) for n in ("oml", "heat", "bands", "udiff_gather", "udiff_sums", "halo_p2p")] + [
+        (n, C.c_long) for n in ("xforc_len", "pom_len", "edge_len", "oml_len", "summary_len", "halo_len")]
+
+
 TAV_NOUT = 16  # QGCM_HIP_TAV_NOUT
 ATM_TAV_NOUT = 15  # QGCM_HIP_ATM_TAV_NOUT
 
@@ -165,6 +171,7 @@ SYMBOLS = [
     "qgcm_hip_xforc_slab_udiff", "qgcm_hip_xforc_slab_pom_len", "qgcm_hip_xforc_slab_pom_pack", "qgcm_hip_xforc_slab_pom_assemble",
     "qgcm_hip_xforc_sums", "qgcm_hip_xforc_slab_sums", "qgcm_hip_xforc_slab_edge_len", "qgcm_hip_xforc_slab_edge_pack",
     "qgcm_hip_xforc_slab_edge_assemble",
+    "qgcm_hip_slab_coupled_code_name", "qgcm_hip_slab_coupled_plan", "qgcm_hip_slab_coupled_init", "qgcm_hip_slab_coupled_steps",
     "qgcm_hip_time_steps", "qgcm_hip_prepare_steps", "qgcm_hip_profile_steps", "qgcm_hip_copy_bandwidth", "qgcm_hip_stream_mix_bandwidth", "qgcm_hip_stream",
     "qgcm_hip_debug_live_allocs",
 ]
@@ -353,6 +360,13 @@ def load_library():
         L.qgcm_hip_xforc_slab_edge_len.argtypes = [vp, vp, C.POINTER(C.c_long)]
         L.qgcm_hip_xforc_slab_edge_pack.argtypes = [vp, vp, vp]
         L.qgcm_hip_xforc_slab_edge_assemble.argtypes = [vp, vp, vp, C.c_int]
+    if hasattr(L, "qgcm_hip_slab_coupled_plan"):  # (added within ABI version 3: a QGCM_HIP_LIB build may predate it)
+        L.qgcm_hip_slab_coupled_code_name.argtypes = [C.c_int]
+        L.qgcm_hip_slab_coupled_code_name.restype = C.c_char_p
+        L.qgcm_hip_slab_coupled_plan.argtypes = [C.POINTER(SlabCoupledSwitches)] + [C.c_int] * 5 + [C.c_long, ip, C.POINTER(C.c_long),
+                                                                                                  C.POINTER(C.c_long)]
+        L.qgcm_hip_slab_coupled_init.argtypes = [vp, vp]
+        L.qgcm_hip_slab_coupled_steps.argtypes = [vp, vp] + [C.c_int] * 4
     L.qgcm_hip_time_steps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.qgcm_hip_prepare_steps.argtypes = [vp, C.c_int, C.c_int]
     L.qgcm_hip_profile_steps.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int),
@@ -472,6 +486,26 @@ def xforc_sums(nxpa, nyta, ndxr, ny1, nyaooc, slab_rows):
                  coarse=(b.u0, b.u1), arows=(b.a0, b.a1),
                  own=tuple(nm for k, nm in enumerate(XFORC_BAND_LINES) if b.own >> k & 1), nrow=b.nrow, mom_len=b.mom_len)
             for b in out]
+
+
+def slab_coupled_plan(nranks, nt0, n, nstr, xforc, oml=False, heat=False, bands=False, udiff_gather=False, udiff_sums=False,
+                      halo_p2p=True, xforc_len=0, pom_len=0, edge_len=0, oml_len=0, summary_len=0, halo_len=0):
+    """The operations of one coupled window on a y-slab ocean, in the order qgcm_hip_slab_coupled_steps issues them
+    (qgcm_hip_slab_coupled_plan; host code, no device): a list of (name, length) - the names of
+    qgcm_hip_slab_coupled_code_name, length = doubles per rank of an exchange (gather_*, halo_*) and 0 otherwise.  The
+    switches say what the run has set up, the lengths are those of xforc_msg_len, xforc_pom_len, xforc_edge_len,
+    oml_len, th_len and halo_len.  The plan is the same on every rank."""
+    L = load_library()
+    sw = SlabCoupledSwitches(int(bool(oml)), int(bool(heat)), int(bool(bands)), int(bool(udiff_gather)), int(bool(udiff_sums)),
+                             int(bool(halo_p2p)), int(xforc_len), int(pom_len), int(edge_len), int(oml_len), int(summary_len),
+                             int(halo_len))
+    args = (C.byref(sw), int(nranks), int(nt0), int(n), int(nstr), int(bool(xforc)))
+    count = C.c_long(0)
+    check(L.qgcm_hip_slab_coupled_plan(*args, 0, None, None, C.byref(count)))
+    m = max(count.value, 1)
+    codes, lens = (C.c_int * m)(), (C.c_long * m)()
+    check(L.qgcm_hip_slab_coupled_plan(*args, m, codes, lens, C.byref(count)))
+    return [(L.qgcm_hip_slab_coupled_code_name(codes[k]).decode(), int(lens[k])) for k in range(count.value)]
 
 
 def row_plan(handle):

@@ -462,6 +462,17 @@ class HipSlab(Handle):
         check(self.L.qgcm_hip_slab_steps(self.h, int(s0), int(n)))
         self._done()
 
+    # the coupled window driven by the library ---------------------------
+    def coupled_init(self, atm):
+        """Size the window's exchange buffers for this slab and its replica (qgcm_hip_slab_coupled_init): after comm_init
+        and every xforc set-up call."""
+        check(self.L.qgcm_hip_slab_coupled_init(self.h, atm.h))
+
+    def coupled_steps(self, atm, nt0, n, nstr, xforc):
+        """One window (qgcm_hip_slab_coupled_steps): collective, asynchronous."""
+        check(self.L.qgcm_hip_slab_coupled_steps(self.h, atm.h, int(nt0), int(n), int(nstr), int(bool(xforc))))
+        self._done()
+
     def stage(self, n, a=None, b=None, c=None, flags=0):
         """One C call per communication-free stage (qgcm_hip_slab_stage)."""
         check(self.L.qgcm_hip_slab_stage(self.h, int(n), self._ptr(a), self._ptr(b), self._ptr(c), self.rank, self.nranks, int(flags)))
@@ -920,6 +931,7 @@ class SlabOcean:
             x.xforc_init(a, p)
             a.xforc_origin = (int(p.nx1), int(p.ny1))  # (where xforc_heat_setup finds the ocean)
         self.atmos = list(atmospheres)
+        self.native_coupling = False  # (use_library_coupling sized its buffers for the set-up this call replaces)
         self._xf_bufs = None
         self._xf_pom_bufs = None
         self._xf_edge_bufs = None
@@ -1022,6 +1034,22 @@ class SlabOcean:
         with the slab's local T rows."""
         return [x.xforc_fetch(a, True) for x, a in zip(self.slabs, self.atmos)]
 
+    def use_library_coupling(self):
+        """From now on coupled_steps() runs qgcm_hip_slab_coupled_steps: the library issues the whole window -
+        xforc with its all-gathers over RCCL, the mixed layers, the slab step, the replica's steps - with events between
+        the slab's stream and the replica's and no host wait; Python is out of the window.  Opt-in, one slab per process,
+        after use_library_exchanges() and the xforc set-ups (call it again after a set-up call changed the mode).  xforc()
+        on its own and the virtual ranks keep the Python-driven path."""
+        if len(self.slabs) != 1:
+            raise ValueError("use_library_coupling: one slab per process (virtual ranks keep the Python-driven window)")
+        if not getattr(self, "native", False):
+            raise ValueError("use_library_coupling: call use_library_exchanges first (it creates the communicator)")
+        if not hasattr(self, "atmos"):
+            raise ValueError("use_library_coupling: call xforc_setup first (it names the replica of the atmosphere)")
+        self._join()
+        self.slabs[0].coupled_init(self.atmos[0])
+        self.native_coupling = True
+
     def coupled_steps(self, nt0, n, nstr, xforc=False):
         """As model.coupled_steps (src/q-gcm.F:1220-1268): n atmospheric steps nt = nt0.. on every replica with one slab
         ocean step before every one with mod(nt,nstr) == 1; xforc = True: xforc() before each ocean step, False: the
@@ -1031,6 +1059,14 @@ class SlabOcean:
             raise ValueError("coupled_steps: bad step range")
         if not hasattr(self, "atmos"):
             raise ValueError("coupled_steps: call xforc_setup first (it names the replicas of the atmosphere)")
+        if getattr(self, "native_coupling", False):  # use_library_coupling: the library runs the whole window
+            self.slabs[0].coupled_steps(self.atmos[0], nt0, n, nstr, xforc)
+            self.atmos[0].step_index = nt0 + n
+            if nstr > 1 and n > 0:  # ocean steps s with nt = 1 + (s - 1) * nstr inside the window
+                sfirst, slast = (nt0 + nstr - 2) // nstr + 1, (nt0 + n - 2) // nstr + 1
+                if slast >= sfirst:
+                    self.step_index = slast + 1
+            return
         nt, end = nt0, nt0 + n
         while nt < end:
             nxt = end
